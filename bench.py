@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — particle-updates/s of the particle-filter frame loop on synthetic 360-beam scans.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
         N = 1: this process.  N > 1 without a launcher: bench.py starts `python -m torch.distributed.run --nnodes=1
         --nproc-per-node N --master-addr 127.0.0.1 ...` on itself BEFORE anything touches the GPU and relays rank 0's line.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -18,7 +18,13 @@ the next frame's motion / EKF kernels) -> exchange between GPUs.  Workload = BAS
 particles, 360 beams, 500 landmarks all observed, 1024 x 1024 EDT grid; weak scaling (per-GPU work fixed) unless
 --scaling strong.  Particles, maps, EDT and scan are resident in HBM when the timed region starts, and so is the sensor
 data of every frame (--host-sensor sends its 8.9 KB over PCIe frame by frame instead).
-value = N_total_particles * K / max-over-ranks wall time.
+value = N_total_particles * K / max-over-ranks wall time; ms_per_step = that wall time / K.
+
+A plain run does only what the headline needs: set-up, the untimed pre-roll and W warm-up frames, the K timed steps, the line.
+--full adds everything else listed below as "--full" (the stage pass, the no-reuse sweep, the extra legs, the CPU baselines,
+the north-star strong-scaling leg); --no-cpu-baseline / --no-extra-legs / --no-sweep trim a --full run.
+--dump-outputs DIR: after the timed steps, what the last step computed (see outputs_of_last_step) as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Other workloads (never the default; used to fill BASELINE.md):
     --mode score   scan-match-only microbench (configs[2]: --particles 1048576 --grid 2048)
@@ -32,15 +38,16 @@ One JSON line on stdout (rank 0).  Beyond the contract's fields:
                 (slam_profile_*).  `achieved` names its basis and the kernel it belongs to (`achieved_basis`,
                 `achieved_kernel`): HBM traffic from a PMC record of this workload and kernel (profiles/traffic.json)
                 over the live duration; else the no-reuse sweep; else algorithmic bytes.  `logical_rate_gbs` is always
-                SURVEY 8(d)'s algorithmic bytes over the live duration.
-  stage_avg_ms  every stage of a frame through the ABI's per-stage timers (a short pass after the timed region)
-  north_star, copy_ceiling, end_to_end_obs32   (N = 1, default workload) bounded extra legs after the timed region:
+                SURVEY 8(d)'s algorithmic bytes over the live duration.  `no_reuse` (the sweep) only with --full.
+  stage_avg_ms  (--full) every stage of a frame through the ABI's per-stage timers (a short pass after the timed region)
+  north_star, copy_ceiling, end_to_end_obs32   (--full, N = 1) bounded extra legs after the timed region:
                 the EKF sweep at 1 048 576 x 1 000, a pure copy of the same shape, and the configs[1] frame with the 32
                 nearest landmarks observed on rows and on pages; `headline_round2_method`: configs[1] measured the way
                 BENCH_r01 / BENCH_r02 were (cold filter, 5 + 20 frames, every frame bracketed), as two launches and fused.
                 `sharded_rehearsal_2_ranks_one_card`: the sharded session (two ranks as threads on this card, in-process
                 transport) with its per-stage timers, run as a child process.  They never touch `value`.
-  cpu_baseline  the CPU port of the same frame loop (oracle/, one thread) on a bounded sample; cpu_baseline_threads:
+  north_star_strong   (--full, default workload) the north-star problem split over the same ranks (wants_strong_leg).
+  cpu_baseline  (--full, else null) the CPU port of the same frame loop (oracle/, one thread) on a bounded sample; cpu_baseline_threads:
                 its per-particle stages on up to 16 host threads; cpu_baseline_main_c: the reference's own pipeline
                 (main.c rows A1-A8) on this host's CPU — the compiled reference when oracle/_ref/ travelled here, and
                 the oracle's restatement — beside the engine's drop-in programs on the same scans.
@@ -469,6 +476,10 @@ class ThreadCtx:
 
 # ------------------------------------------------------------------------------------------------ one rank
 SETTLE_S = 0.25
+# every rank fills its maps from a device generator of its own with this seed (not torch's default generator, which need not
+# start from the same seed in every process and is shared by ranks that are threads): the same maps in every run
+MAP_SEED = 1234
+DUMP_BYTES = 64 << 20   # --dump-outputs: all ranks' files together
 
 
 def settle(torch, seconds=None):
@@ -481,13 +492,13 @@ def settle(torch, seconds=None):
     time.sleep(SETTLE_S if seconds is None else seconds)
 
 
-def fill_maps(torch, m0, landmarks, L, dev, n):
+def fill_maps(torch, m0, landmarks, L, dev, n, gen=None):
     """Plausible maps [n][5][Lp]: every landmark near its true place with a loose covariance."""
     lm = torch.from_numpy(landmarks.astype(np.float32)).to(dev)
     for i0 in range(0, n, 65536):                     # in chunks: the temporaries of a 1M x 1k map are 4 GB each
         i1 = min(i0 + 65536, n)
-        m0[i0:i1, 0, :L] = lm[:, 0] + 0.1 * torch.randn((i1 - i0, L), device=dev)
-        m0[i0:i1, 1, :L] = lm[:, 1] + 0.1 * torch.randn((i1 - i0, L), device=dev)
+        m0[i0:i1, 0, :L] = lm[:, 0] + 0.1 * torch.randn((i1 - i0, L), device=dev, generator=gen)
+        m0[i0:i1, 1, :L] = lm[:, 1] + 0.1 * torch.randn((i1 - i0, L), device=dev, generator=gen)
     m0[:n, 2, :L] = 0.05
     m0[:n, 3, :L] = 0.0
     m0[:n, 4, :L] = 0.05
@@ -500,6 +511,23 @@ def obs_tables(torch, frames, L, dev):
         tab[k, 0, f["ids"]] = f["zx"]
         tab[k, 1, f["ids"]] = f["zy"]
     return torch.from_numpy(tab).to(dev)
+
+
+def sample_rows(n, row_bytes, budget):
+    """Indices of a fixed, seeded sample of n rows that fits in `budget` bytes, ascending (every row when all fit)."""
+    k = int(min(n, max(1, budget // row_bytes)))
+    if k == n:
+        return np.arange(n, dtype=np.int32)
+    return np.sort(np.random.default_rng(2024).choice(n, k, replace=False)).astype(np.int32)
+
+
+def dump_outputs(directory, arrays, prefix=""):
+    """--dump-outputs: one DIR/<prefix><name>.npy per array, float64 kept, everything else as float32."""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(d / f"{prefix}{name}.npy", np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32))
 
 
 def run_rank(args, ctx, inp, last=True):
@@ -553,7 +581,7 @@ def run_rank(args, ctx, inp, last=True):
         rows_now = views()[1]
         # a session on pages has no rows to write into: the same rows are made in a scratch tensor and handed over once
         m0 = rows_now if rows_now is not None else torch.empty((n, 5, Lp), dtype=torch.float32, device=dev)
-        fill_maps(torch, m0, landmarks, L, dev, n)
+        fill_maps(torch, m0, landmarks, L, dev, n, torch.Generator(device=dev).manual_seed(MAP_SEED))
         if rows_now is None:
             torch.cuda.synchronize()
             pf.set_map_dev(m0, 5 * Lp, Lp)
@@ -654,6 +682,41 @@ def run_rank(args, ctx, inp, last=True):
     elapsed = ctx.max_over_ranks(elapsed)
     migrated = ctx.max_over_ranks(migrated / max(args.steps, 1))
 
+    def outputs_of_last_step():
+        """What a caller of the timed path receives after its last step: the session's poses, best and mean pose and the maps
+        of a sample of particles (--mode score: scores and hit counts; --mode ekf: log-likelihoods and the rows the last
+        sweep wrote).  Per-particle arrays beyond half this rank's share of the byte budget, and map rows beyond a quarter
+        or 256 rows, are a fixed, seeded sample; `particle_index` / `map_rows_index` name the rows kept."""
+        budget = DUMP_BYTES // world
+        res = {}
+        if args.mode == "pf":
+            best, best_logw, best_idx = pf.best()
+            res.update(best_pose=best, best_logw_index=np.array([best_logw, best_idx], np.float64),
+                       mean_pose=pf.mean(float(best[2])))
+            per_particle = {"poses": pf.poses()}                                                  # [3][n]
+        elif args.mode == "score":
+            per_particle = {"score": score_t.cpu().numpy(), "count": count_t.cpu().numpy()}
+        else:
+            per_particle = {"loglik": loglik_t.cpu().numpy()}
+        sel = sample_rows(n, sum(a.nbytes // n for a in per_particle.values()), budget // 2)
+        res.update({k: a[..., sel] for k, a in per_particle.items()})
+        if len(sel) < n:
+            res["particle_index"] = sel
+        if L and args.mode != "score":
+            rsel = sample_rows(n, 20 * L, min(budget // 4, 256 * 20 * L))
+            if args.mode == "pf":
+                res["map_rows"] = pf.map_rows(rsel)                                               # [k][5][L]
+            else:   # step k of the sweep wrote maps[1 - (k & 1)]
+                last = args.warmup + args.steps - 1
+                rows = sweep["maps"][1 - (last & 1)]
+                res["map_rows"] = rows[torch.from_numpy(rsel).to(dev).long(), :, :L].cpu().numpy()
+            res["map_rows_index"] = rsel
+        return res
+
+    if args.dump_outputs:
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, outputs_of_last_step(), f"rank{rank}_" if world > 1 else "")
+
     score_ms, score_n = eng.profile_read(eng.PROF_SCORE)
     ekf_ms, ekf_n = eng.profile_read(eng.PROF_EKF)
     # A start/stop event bracket around ONE kernel also contains the stream's marker handling; an empty bracket
@@ -664,28 +727,29 @@ def run_rank(args, ctx, inp, last=True):
     def kernel_ms(total_ms, launches):
         return max(total_ms / max(launches, 1) - bracket_overhead_ms, 0.0)
 
-    # every stage of a frame through the per-stage timers: a short extra pass, outside the timing (the trajectory simply
+    # --full: every stage of a frame through the per-stage timers, a short extra pass outside the timing (the trajectory simply
     # continues; the brackets cost stream time, which is why the timed region carries only the dominant kernel's)
-    eng.profile_enable(*range(eng.PROF_COUNT))
-    eng.frame_fusion_set(False)   # the stages one by one: score and landmark update as two launches (same bits)
-    extra = min(10, args.steps)
-    for k in range(extra):
-        one_step(args.warmup + args.steps + k)
-    eng.profile_enable()
-    eng.frame_fusion_set(True)
+    extra = min(10, args.steps) if args.full else 0
     stage_avg_ms = {}
-    for kk in range(eng.PROF_COUNT):
-        ms, cnt = eng.profile_read(kk)
-        # several ranks: the slowest rank's average and the busiest rank's launch count (a stage like `unpack` runs only on
-        # ranks that received rows in these few frames; every rank takes part in the reduction, in the same order)
-        avg = ctx.max_over_ranks(kernel_ms(ms, cnt) if cnt else 0.0) if world > 1 else kernel_ms(ms, cnt)
-        per_frame = ctx.max_over_ranks(cnt / max(extra, 1)) if world > 1 else cnt / max(extra, 1)
-        if per_frame > 0:
-            stage_avg_ms[eng.PROF_NAMES[kk]] = {"avg_ms": avg, "per_frame": per_frame}
-        if kk == eng.PROF_SCORE and not score_n:
-            score_ms, score_n = ms, cnt
-        if kk == eng.PROF_EKF and not ekf_n:
-            ekf_ms, ekf_n = ms, cnt
+    if extra:
+        eng.profile_enable(*range(eng.PROF_COUNT))
+        eng.frame_fusion_set(False)   # the stages one by one: score and landmark update as two launches (same bits)
+        for k in range(extra):
+            one_step(args.warmup + args.steps + k)
+        eng.profile_enable()
+        eng.frame_fusion_set(True)
+        for kk in range(eng.PROF_COUNT):
+            ms, cnt = eng.profile_read(kk)
+            # several ranks: the slowest rank's average and the busiest rank's launch count (a stage like `unpack` runs only on
+            # ranks that received rows in these few frames; every rank takes part in the reduction, in the same order)
+            avg = ctx.max_over_ranks(kernel_ms(ms, cnt) if cnt else 0.0) if world > 1 else kernel_ms(ms, cnt)
+            per_frame = ctx.max_over_ranks(cnt / max(extra, 1)) if world > 1 else cnt / max(extra, 1)
+            if per_frame > 0:
+                stage_avg_ms[eng.PROF_NAMES[kk]] = {"avg_ms": avg, "per_frame": per_frame}
+            if kk == eng.PROF_SCORE and not score_n:
+                score_ms, score_n = ms, cnt
+            if kk == eng.PROF_EKF and not ekf_n:
+                ekf_ms, ekf_n = ms, cnt
     n_total = n * world
     value = n_total * args.steps / elapsed
 
@@ -707,7 +771,8 @@ def run_rank(args, ctx, inp, last=True):
     if layout_in_region == "split":
         classes_in_use = int(torch.as_tensor(pf.split_view()["live_count"], device=dev)[0])
     sweep_rows = views()[1:3]
-    if L and args.mode != "score" and not args.no_sweep and sweep_rows[0] is None and not paged_in_region:
+    sweep_on = args.full and not args.no_sweep   # the no-reuse sweep: a run of its own after the timed region (--full)
+    if L and args.mode != "score" and sweep_on and sweep_rows[0] is None and not paged_in_region:
         # a split session has no rows: the sweep of the ROW kernel (the 20 B + 20 B streaming figure the north star's
         # read-only fraction is defined on) runs on scratch rows of the same shape, when they fit beside the session
         free_b, _ = torch.cuda.mem_get_info(dev)
@@ -718,7 +783,7 @@ def run_rank(args, ctx, inp, last=True):
             torch.cuda.synchronize()
             sweep_rows = (ma, mb)
             del ma, mb
-    if L and args.mode != "score" and not args.no_sweep and sweep_rows[0] is not None:
+    if L and args.mode != "score" and sweep_on and sweep_rows[0] is not None:
         eng.profile_enable(eng.PROF_EKF)
         eng.profile_read(eng.PROF_EKF)
         p = views()[0]
@@ -875,8 +940,9 @@ def run_rank(args, ctx, inp, last=True):
                                                 "ekf_update_kernel(in place)": forms[2], "ekf_sparse_kernel": forms[3]},
                      "other_kernel_avg_ms": {"score_poses_kernel": kernel_ms(score_ms, score_n),
                                              ekf_name: kernel_ms(ekf_ms, ekf_n)}},
-        "stage_avg_ms": stage_avg_ms,
     }
+    if args.full:
+        out["stage_avg_ms"] = stage_avg_ms
     torch.cuda.synchronize()
     pf.close()
     if comm:
@@ -884,7 +950,7 @@ def run_rank(args, ctx, inp, last=True):
     del d_scan, d_z, scan_v, obs_v, sweep
     torch.cuda.empty_cache()
 
-    legs_ok = rank == 0 and world == 1 and not ctx.threads
+    legs_ok = rank == 0 and world == 1 and not ctx.threads and args.full
     if legs_ok and args.mode == "pf" and not args.no_extra_legs and not args.force_collectives:
         try:
             out.update(extra_legs(args, torch, pkg, eng, dev, inp, kernel_ms))
@@ -916,7 +982,8 @@ def sharded_rehearsal(args):
     the ranks share one GPU and the transport is device copies behind a host rendezvous; RCCL between ranks needs more than
     one GPU."""
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--transport", "local", "--steps", "40", "--warmup", "10",
-           "--particles", "32768", "--no-cpu-baseline", "--no-extra-legs", "--no-sweep", "--settle-ms", str(args.settle_ms)]
+           "--particles", "32768", "--full", "--no-cpu-baseline", "--no-extra-legs", "--no-sweep", "--settle-ms",
+           str(args.settle_ms)]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1075,11 +1142,11 @@ def extra_legs(args, torch, pkg, eng, dev, inp, kernel_ms):
 
 def wants_strong_leg(args):
     """The north star's scaling target (>= 6x at 8 GPUs against 1) is defined on ONE problem, 1 048 576 particles x 1 000
-    landmarks, split over the ranks — not on the weak-scaling headline.  A default run (the driver's `bench.py --gpus N`)
-    therefore measures that problem too, as a second leg at every N, 1 included: the curve falls out of the legs' values."""
-    return (args.mode == "pf" and args.scaling == "weak" and not args.no_extra_legs and not args.force_collectives and args.ess == 0.0
-            and args.observed == 0 and (args.particles, args.landmarks, args.beams, args.grid) == (65536, 500, 360, 1024)
-            and 1048576 % args.gpus == 0)
+    landmarks, split over the ranks — not on the weak-scaling headline.  A --full run of the default workload (`bench.py --gpus N
+    --full`) therefore measures that problem too, as a second leg at every N, 1 included: the curve falls out of the legs' values."""
+    return (args.full and args.mode == "pf" and args.scaling == "weak" and not args.no_extra_legs and not args.force_collectives
+            and args.ess == 0.0 and args.observed == 0
+            and (args.particles, args.landmarks, args.beams, args.grid) == (65536, 500, 360, 1024) and 1048576 % args.gpus == 0)
 
 
 def strong_leg(args, ctx):
@@ -1090,6 +1157,7 @@ def strong_leg(args, ctx):
     a.scaling, a.particles_total, a.particles, a.landmarks = "strong", 1048576, 1048576 // args.gpus, 1000
     a.steps, a.warmup, a.preroll = min(args.steps, 30), 5, 30
     a.no_extra_legs = a.no_cpu_baseline = a.no_sweep = True
+    a.dump_outputs = None
     a.event_every = 2
     r = run_rank(a, ctx, build_inputs(a))
     if r is None:
@@ -1163,7 +1231,17 @@ def parse_args():
     ap.add_argument("--force-collectives", action="store_true",
                     help="diagnostics, --gpus 1 only: run the multi-GPU code path (every RCCL collective, the sharded index "
                          "kernels, the plan read-back) on a one-rank group to price its control overhead")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the per-stage pass, the no-reuse sweep, the extra legs, the north-star "
+                         "strong-scaling leg, the sharded rehearsal and the CPU baselines (a plain run only sets up, warms up, "
+                         "times the steps and prints the line; --no-cpu-baseline / --no-extra-legs / --no-sweep trim a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (the session's poses, best and mean pose, "
+                         "a fixed sample of map rows; --mode score / ekf: their outputs) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     global SETTLE_S
     SETTLE_S = max(0.0, args.settle_ms * 1e-3)
     if args.paged:

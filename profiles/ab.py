@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """profiles/ab.py REPS "BENCH ARGS" NAME=ENV[,ENV...] [NAME=...] — A/B of library builds / environment switches on one box:
-runs `python3 bench.py --no-cpu-baseline --no-extra-legs --no-sweep BENCH ARGS` REPS times per variant, interleaved (the
+runs `python3 bench.py --full --no-cpu-baseline --no-extra-legs --no-sweep BENCH ARGS` REPS times per variant, interleaved (the
 boxes' clock and power states drift by several per cent within a call, so variants are never compared across blocks of
 runs), and prints per variant the median and the minimum of ms/step and of the dominant kernel's launch time.
 ENV entries are VAR=value; LIB=dir is short for SLAM_HIP_LIB=<package>/dir/libslam_hip.so.  Measurement tooling."""
@@ -27,7 +27,7 @@ for spec in sys.argv[3:]:
 res = {name: [] for name, _ in variants}
 for r in range(reps):
     for name, env in variants:
-        out = subprocess.run([sys.executable, str(root / "bench.py"), "--no-cpu-baseline", "--no-extra-legs", "--no-sweep", *args],
+        out = subprocess.run([sys.executable, str(root / "bench.py"), "--full", "--no-cpu-baseline", "--no-extra-legs", "--no-sweep", *args],
                              env=env, capture_output=True, text=True)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])

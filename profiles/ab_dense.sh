@@ -1,6 +1,6 @@
 # dense default, north star, config 5 share: one run each (compare with the previous build's lines on the same box by running this
 # script from both trees in one call: profiles/ab.py)
-Q="--no-cpu-baseline --no-extra-legs --no-sweep"
+Q="--full --no-cpu-baseline --no-extra-legs --no-sweep"
 T=${1:-dense}
 for rep in 1 2 3; do
   python3 bench.py $Q > gpurun_out/${T}_d_$rep.json 2> gpurun_out/${T}_d_$rep.err || echo fail dense

@@ -1,5 +1,5 @@
 # the free list of a paged frame inside the scorer's launch (default) against a launch of its own (SLAM_FREE_LIST_RIDER=0)
-Q="--no-cpu-baseline --no-extra-legs --no-sweep"
+Q="--full --no-cpu-baseline --no-extra-legs --no-sweep"
 for rep in 1 2; do
   for m in 1 0; do
     SLAM_FREE_LIST_RIDER=$m python3 bench.py $Q --observed 32 > gpurun_out/rider_o32_m${m}_$rep.json 2> gpurun_out/rider_o32_m${m}_$rep.err || echo fail o32 $m

@@ -1,6 +1,6 @@
 # the classes' update inside the launch of the weights (default) against a launch of its own (SLAM_COV_MERGE=0), and the free list
 # kernel without fences: dense default, 32 observed (split pages)
-Q="--no-cpu-baseline --no-extra-legs --no-sweep"
+Q="--full --no-cpu-baseline --no-extra-legs --no-sweep"
 for rep in 1 2; do
   for m in 1 0; do
     SLAM_COV_MERGE=$m python3 bench.py $Q > gpurun_out/tail_dense_m${m}_$rep.json 2> gpurun_out/tail_dense_m${m}_$rep.err || echo fail dense $m

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-extra-legs"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-extra-legs"
 step() { echo "[collect] $*"; }
 
 step "kernel trace, default workload (configs[1])"

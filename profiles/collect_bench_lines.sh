@@ -11,7 +11,7 @@ cd "$ROOT"
 line() {   # name, flags...
   local name=$1; shift
   echo "[lines] $name: bench.py $*"
-  timeout -k 10 280 python3 bench.py "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/${TAG}_bench_$name.err"
+  timeout -k 10 280 python3 bench.py --full "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/${TAG}_bench_$name.err"
   local rc=$?
   if [ $rc -ge 124 ]; then echo "[lines] $name killed at its limit (rc=$rc): stopping"; exit $rc; fi
   [ $rc -ne 0 ] && { echo "[lines] $name FAILED rc=$rc"; tail -3 "$OUT/${TAG}_bench_$name.err"; }

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-extra-legs --no-sweep --steps 8 --warmup 2 --preroll 0 --events none"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-extra-legs --no-sweep --steps 8 --warmup 2 --preroll 0 --events none"
 for C in FETCH_SIZE WRITE_SIZE; do
   echo "[big_pmc] $C north star"
   timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d "$OUT/${TAG}_bigpmc_${C}_ns" -- $B --scaling strong --particles-total 1048576 --landmarks 1000 > /dev/null 2> "$OUT/${TAG}_bigpmc_${C}_ns.err"

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out
 PKG=$ROOT/hardware-acceleration-of-lidar-slam_amd
 mkdir -p "$OUT"
 cd "$ROOT"
-B="python3 bench.py --no-cpu-baseline --no-extra-legs --no-sweep --observed 32 --paged --steps 60 --warmup 10"
+B="python3 bench.py --full --no-cpu-baseline --no-extra-legs --no-sweep --observed 32 --paged --steps 60 --warmup 10"
 for P in 32 16 8; do
   LIB=$PKG/lib/libslam_hip.so; [ $P != 32 ] && LIB=$PKG/lib_p$P/libslam_hip.so
   [ -f "$LIB" ] || { echo "[page_sizes] $LIB missing"; continue; }

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-extra-legs --no-sweep --observed 32"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-extra-legs --no-sweep --observed 32"
 for L in 500 5000; do
   for P in rows paged; do
     F="--map-layout rows"; [ $P = paged ] && F="--paged"

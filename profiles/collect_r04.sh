@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-extra-legs --no-sweep $*"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-extra-legs --no-sweep $*"
 step() { echo "[collect] $*"; }
 step "kernel trace + stats"
 timeout -k 5 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_trace" -- $B --steps 100 --warmup 10 > "$OUT/${TAG}_trace.json" 2> "$OUT/${TAG}_trace.err" || echo "[collect] trace FAILED"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """profiles/early_frames.py TAG — the front kernel of a frame, frame by frame from a cold start:
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/TAG_early -- python3 bench.py --no-cpu-baseline --no-extra-legs \
-        --no-sweep --steps 150 --warmup 0 --preroll 0 --events none
+    rocprofv3 --kernel-trace --output-format csv -d DIR/TAG_early -- python3 bench.py --full --no-cpu-baseline --no-extra-legs \
+        --no-sweep --steps 150 --warmup 0 --preroll 0 --events none       (DIR: the second argument)
 -> profiles/TAG_early_frames.md (why bench.py pre-rolls the filter before its warm-up steps)."""
 import csv
 import glob
@@ -19,7 +19,7 @@ fr = [dur(r) for r in rows if "frame_front_kernel" in r["Kernel_Name"]]
 sc = [dur(r) for r in rows if "score_poses" in r["Kernel_Name"]]
 avg = lambda v: sum(v) / max(len(v), 1)
 md = [f"# {tag}: the front kernel of a frame, frame by frame from a cold start (configs[1])", "",
-      "`rocprofv3 --kernel-trace -- python3 bench.py --no-cpu-baseline --no-extra-legs --no-sweep --steps 150 --warmup 0 --preroll 0 --events none`:",
+      "`rocprofv3 --kernel-trace -- python3 bench.py --full --no-cpu-baseline --no-extra-legs --no-sweep --steps 150 --warmup 0 --preroll 0 --events none`:",
       "durations of `frame_front_kernel<2, 4, 4, 8>` (motion + score + landmark update of one frame) in launch order, µs; frames 0 and 1 run",
       "the two-launch path (no resample indices yet / group size not yet known).", "", "```", " ".join(f"{d:.0f}" for d in fr[:150]), "```", "",
       f"Frames 3-10: {avg(fr[1:9]):.0f} µs; 15-30: {avg(fr[13:28]):.0f}; 40-50: {avg(fr[38:48]):.0f}; 90-100: {avg(fr[88:98]):.0f}; 140-148: {avg(fr[138:146]):.0f}.  "

@@ -1,4 +1,4 @@
-Q="--no-cpu-baseline --no-extra-legs"
+Q="--full --no-cpu-baseline --no-extra-legs"
 for lay in pages split_pages auto; do
   python3 bench.py $Q --observed 32 --map-layout $lay > gpurun_out/sp_o32_$lay.json 2> gpurun_out/sp_o32_$lay.err || echo fail $lay
   python3 bench.py $Q --landmarks 5000 --observed 32 --map-layout $lay --steps 40 > gpurun_out/sp_5k_$lay.json 2> gpurun_out/sp_5k_$lay.err || echo fail 5k $lay

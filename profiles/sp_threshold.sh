@@ -1,5 +1,5 @@
 # split against split pages as the share of observed landmarks grows (where should SLAM_MAP_AUTO change over?)
-Q="--no-cpu-baseline --no-extra-legs --no-sweep"
+Q="--full --no-cpu-baseline --no-extra-legs --no-sweep"
 for K in 128 160 192 224 256; do
   for lay in split split_pages; do
     python3 bench.py $Q --observed $K --map-layout $lay > gpurun_out/th_${K}_$lay.json 2> gpurun_out/th_${K}_$lay.err || echo fail $K $lay

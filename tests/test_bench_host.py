@@ -3,6 +3,7 @@ steps + the stage pass, the synthetic world of SURVEY 8(d)."""
 import sys
 
 import numpy as np
+import pytest
 
 import bench
 
@@ -44,3 +45,26 @@ def test_landmark_ids_follow_a_space_filling_sweep():
     assert np.all(np.diff(key) >= 0)
     d = np.hypot(*(lm[1:] - lm[:-1]).T)
     assert np.median(d) < 1.0                                              # neighbours in the row are neighbours in the room
+
+
+def test_a_plain_run_leaves_everything_beyond_the_headline_to_full():
+    a = _args()
+    assert not a.full and a.dump_outputs is None and not bench.wants_strong_leg(a)
+    assert bench.wants_strong_leg(_args("--full")) and not bench.wants_strong_leg(_args("--full", "--no-extra-legs"))
+    assert _args("--dump-outputs", "out").dump_outputs == "out"
+
+
+def test_steps_must_be_positive():
+    with pytest.raises(SystemExit):
+        _args("--steps", "0")
+
+
+def test_dumped_outputs_are_a_fixed_sample_within_the_budget(tmp_path):
+    assert np.array_equal(bench.sample_rows(100, 12, 1 << 20), np.arange(100))
+    s = bench.sample_rows(1 << 22, 12, 32 << 20)
+    assert len(s) * 12 <= 32 << 20 and len(s) > 0 and np.all(np.diff(s) > 0) and s[-1] < 1 << 22
+    assert np.array_equal(s, bench.sample_rows(1 << 22, 12, 32 << 20))   # the same rows in every run
+    assert len(bench.sample_rows(10, 1 << 30, 1)) == 1
+    bench.dump_outputs(tmp_path / "d", {"count": np.arange(4, dtype=np.int32), "best": np.ones(2)}, "rank1_")
+    c, b = np.load(tmp_path / "d" / "rank1_count.npy"), np.load(tmp_path / "d" / "rank1_best.npy")
+    assert c.dtype == np.float32 and np.array_equal(c, [0, 1, 2, 3]) and b.dtype == np.float64

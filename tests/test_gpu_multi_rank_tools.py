@@ -22,9 +22,9 @@ def _bench(*flags, timeout=600):
 
 
 def test_bench_two_ranks_on_one_card_local_transport():
-    """python bench.py --gpus 2 --transport local: two ranks as threads sharing this card, the sharded C session with every
+    """python bench.py --gpus 2 --transport local --full: two ranks as threads sharing this card, the sharded C session with every
     exchange step; ONE JSON line, rows really travel."""
-    r = _bench("--gpus", "2", "--transport", "local", "--steps", "5", "--warmup", "3", "--no-cpu-baseline", "--particles", "16384")
+    r = _bench("--gpus", "2", "--transport", "local", "--steps", "5", "--warmup", "3", "--full", "--no-cpu-baseline", "--particles", "16384")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -39,7 +39,7 @@ def test_bench_two_ranks_on_one_card_local_transport():
 
 def test_bench_two_ranks_paged_local_transport():
     """... the same with the maps on pages and 32 landmarks observed (bench.py --paged used to refuse several ranks)."""
-    r = _bench("--gpus", "2", "--transport", "local", "--steps", "5", "--warmup", "3", "--no-cpu-baseline", "--particles", "8192",
+    r = _bench("--gpus", "2", "--transport", "local", "--steps", "5", "--warmup", "3", "--full", "--no-cpu-baseline", "--particles", "8192",
                "--paged", "--observed", "32")
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
