@@ -106,18 +106,25 @@ __device__ __forceinline__ v2f ekf_log(v2f d) { return det_logf2(d); }
 //     S_sensor = H P H^T + q I = H (P + q I) H^T,   K = P H^T S_sensor^-1 = P (P + q I)^-1 H^T = W H^T,
 //     K nu = W (H^T nu) = W (w - mu)   with w = t + H^T z the observed point in the world frame,
 //     P' = (I - K H) P = (I - W) P,    nu^T S_sensor^-1 nu = (w - mu)^T (P + q I)^-1 (w - mu),   det S_sensor = det (P + q I):
-// everything that involves the covariance — S^-1, the gain W, P', the determinant's logarithm — depends on the prior P and
+// everything that involves the covariance — S^-1, the posterior, the determinant's logarithm — depends on the prior P and
 // on q ALONE, not on the particle's pose and not on the measurement.  The offspring of one ancestor share its P, so a
 // wavefront that updates several of them (the grouped kernels) works that part out ONCE per landmark; per particle there
-// remain the observed point w, the innovation d = w - mu, mu' = mu + W d and the Mahalanobis term.  Round 3 replaced the
-// sensor-frame formulation (the same algebra with H carried through every product: ~160 vector instructions per landmark
-// pair and particle) by this one: ~75 shared + ~31 per particle.
+// remain the observed point w, the innovation d = w - mu, the new mean and the Mahalanobis term.
+// W = P (P + q I)^-1 = I - q (P + q I)^-1, and it tends to I as P / q grows: (I - W) P and mu + W d then cancel, and in
+// float32 they do so catastrophically (with q = 0.01 a prior of 1e6 m^2 gave P' = 0, one of 1e9 m^2 a P' 6 400 times too
+// large; elongated priors gave posteriors that were not positive definite).  So neither is formed.  With S = P + q I,
+//     P'  = q S^-1 P = q / det S * [[det P + q P_xx, q P_xy], [q P_xy, det P + q P_yy]],
+//     mu' = mu + d - q S^-1 d = w - q S^-1 d,
+// and S^-1 d is the vector the Mahalanobis term needs anyway: no gain W at all, and no difference of nearly equal values
+// beyond det P (whose error is that of the rounded prior itself, u kappa(P)).  Round 3 replaced the sensor-frame
+// formulation (the same algebra with H carried through every product: ~160 vector instructions per landmark pair and
+// particle) by this one.
 
 // the part that depends on the prior covariance and q only
 template <class T> struct EkfShared {
     T i00, i01, i11;        // (P + q I)^-1
-    T w00, w01, w10, w11;   // gain in the world frame, W = P (P + q I)^-1
-    T o2, o3, o4;           // posterior covariance (I - W) P: P_xx, P_xy, P_yy
+    T q;                    // the measurement variance (the new mean is w - q (P + q I)^-1 d)
+    T o2, o3, o4;           // posterior covariance q (P + q I)^-1 P: P_xx, P_xy, P_yy
     T hl;                   // 0.5 * log det (P + q I)
 };
 
@@ -141,14 +148,13 @@ __device__ __forceinline__ EkfShared<T> ekf_shared_from(T pxx, T pxy, T pyy, T q
     h.i00 = c * idet;
     h.i01 = -pxy * idet;
     h.i11 = a * idet;
-    h.w00 = pxx * h.i00 + pxy * h.i01;
-    h.w01 = pxx * h.i01 + pxy * h.i11;
-    h.w10 = pxy * h.i00 + pyy * h.i01;
-    h.w11 = pxy * h.i01 + pyy * h.i11;
+    h.q = q;
     if constexpr (WITH_POSTERIOR) {
-        h.o2 = pxx - (h.w00 * pxx + h.w01 * pxy);
-        h.o3 = pxy - (h.w00 * pxy + h.w01 * pyy);
-        h.o4 = pyy - (h.w10 * pxy + h.w11 * pyy);
+        const T s = q * idet;
+        const T detp = pxx * pyy - pxy * pxy;
+        h.o2 = s * (detp + q * pxx);
+        h.o3 = s * (q * pxy);
+        h.o4 = s * (detp + q * pyy);
     }
     h.hl = hl;
     return h;
@@ -175,9 +181,10 @@ __device__ __forceinline__ EkfParticle<T> ekf_particle(const EkfShared<T>& h, T 
     r.wx = px + (c * zx + s * zy);
     r.wy = py + (c * zy - s * zx);
     const T dx = r.wx - mx, dy = r.wy - my;
-    r.o0 = mx + (h.w00 * dx + h.w01 * dy);
-    r.o1 = my + (h.w10 * dx + h.w11 * dy);
-    const T maha = dx * (h.i00 * dx + h.i01 * dy) + dy * (h.i01 * dx + h.i11 * dy);
+    const T t0 = h.i00 * dx + h.i01 * dy, t1 = h.i01 * dx + h.i11 * dy;   // S^-1 d
+    r.o0 = r.wx - h.q * t0;
+    r.o1 = r.wy - h.q * t1;
+    const T maha = dx * t0 + dy * t1;
     r.ll = ((ekf_splat<T>(0.0f) - ekf_splat<T>(0.5f) * maha) - h.hl) - ekf_splat<T>(1.8378770664f);
     return r;
 }

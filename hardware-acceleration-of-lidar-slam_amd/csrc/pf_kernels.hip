@@ -561,6 +561,8 @@ __device__ __forceinline__ void split_apply_one(const SplitBatch<NB>& b, int g, 
         // the whole expression and then packs each landmark's w00 * dx + w01 * dy as ONE product pair + a horizontal add — with
         // two register moves per pair to line the operands up: 20 instructions for the four new means where 8 packed ones do
         // (counted in the ISA, profiles/r04_split_tuning.md section 10).  The packed values are made opaque before the extracts.
+        // Re-checked since the new mean is w - q S^-1 d (no gain W): ekf_split_kernel compiles to the same code without these
+        // two statements, the split frame-front kernels do not, so they stay.
         asm("" : "+v"(r0));
         asm("" : "+v"(r1));
     }
@@ -2075,6 +2077,18 @@ hipError_t launch_motion_sample(hipStream_t stream, const float* sx, const float
     return hipGetLastError();
 }
 
+// SLAM_SPLIT_G (measurements): particles per updating wavefront on the split layout.  Only the instantiated 2, 4 and 8 are
+// taken; any other value is ignored (a grid sized for one G and a kernel built for another would skip particles).
+static int forced_split_g()
+{
+    static const int g = [] {
+        const char* e = getenv("SLAM_SPLIT_G");
+        const int v = e ? atoi(e) : 0;
+        return v == 2 || v == 4 || v == 8 ? v : 0;
+    }();
+    return g;
+}
+
 hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const EventPair* ev, int group_size)
 {
     if (a_in.n <= 0) return hipSuccess;
@@ -2086,7 +2100,7 @@ hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const Even
         blocks = 8 * a.xcd_chunk;
     }
     if (a.cov) {   // split layout: always the grouped form (2 particles per wavefront unless the caller asks for 4 or 8)
-        static const int forced = getenv("SLAM_SPLIT_G") ? atoi(getenv("SLAM_SPLIT_G")) : 0;   // measurements
+        const int forced = forced_split_g();
         const int G = forced ? forced : (group_size == 4 || group_size == 8 ? group_size : 2);
         int gblocks = (a.n + kEkfWaves * G - 1) / (kEkfWaves * G);
         a.xcd_chunk = 0;
@@ -2160,7 +2174,7 @@ hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const floa
     *launched = false;
     const int n = a_in.n;
     static const int quad_max = getenv("SLAM_SCORE_QUAD_MAX") ? atoi(getenv("SLAM_SCORE_QUAD_MAX")) : kQuadMaxPoses;
-    static const int forced_g = getenv("SLAM_SPLIT_G") ? atoi(getenv("SLAM_SPLIT_G")) : 0;   // measurements (split layout)
+    const int forced_g = forced_split_g();
     if (a_in.cov && forced_g) group_size = forced_g;
     if (!a_in.cov && group_size == 8) group_size = 4;   // rows: 2 or 4 particles per updating wavefront
     if (a_in.map_in == a_in.map_out || !frame_front_fits(n, a_in.nlandmarks, group_size)) return hipSuccess;

@@ -243,24 +243,28 @@ void orc_ekf_update(const float *map_in, float *map_out, int64_t row_stride, int
                 } else {
                     /* Observation model z = H (mu - t), H = [[ct,-st],[st,ct]] (inverse of the reference's R^T, main.c:115-116),
                      * R = q I.  H is a rotation, so the update is carried out in the WORLD frame, where everything that
-                     * involves the covariance is independent of the pose: S = P + q I, W = P S^-1, P' = (I - W) P,
-                     * mu' = mu + W (w - mu) with w = t + H^T z the observed point, nu^T S_sensor^-1 nu = (w-mu)^T S^-1 (w-mu),
-                     * det S_sensor = det S (hardware-acceleration-of-lidar-slam_amd/csrc/ekf_math.h: the same operations) */
+                     * involves the covariance is independent of the pose: S = P + q I, nu^T S_sensor^-1 nu = d^T S^-1 d with
+                     * d = w - mu and w = t + H^T z the observed point, det S_sensor = det S.  The gain W = P S^-1 = I - q S^-1
+                     * tends to I as P / q grows, so (I - W) P and mu + W d are not formed (they cancel catastrophically):
+                     *     P' = q S^-1 P = (q / det S) [[det P + q P_xx, q P_xy], [q P_xy, det P + q P_yy]],
+                     *     mu' = w - q S^-1 d
+                     * (hardware-acceleration-of-lidar-slam_amd/csrc/ekf_math.h: the same operations) */
                     const float wx = px + (ct * zx + st * zy);
                     const float wy = py + (ct * zy - st * zx);
                     const float a = pxx + q, c = pyy + q;
                     const float det = a * c - pxy * pxy;
                     const float idet = 1.0f / det;
                     const float i00 = c * idet, i01 = -pxy * idet, i11 = a * idet;         /* S^-1 */
-                    const float w00 = pxx * i00 + pxy * i01, w01 = pxx * i01 + pxy * i11;   /* W = P S^-1 */
-                    const float w10 = pxy * i00 + pyy * i01, w11 = pxy * i01 + pyy * i11;
                     const float dx = wx - mx, dy = wy - my;
-                    out[l] = mx + (w00 * dx + w01 * dy);
-                    out[ps + l] = my + (w10 * dx + w11 * dy);
-                    out[2 * ps + l] = pxx - (w00 * pxx + w01 * pxy);                      /* (I - W) P */
-                    out[3 * ps + l] = pxy - (w00 * pxy + w01 * pyy);
-                    out[4 * ps + l] = pyy - (w10 * pxy + w11 * pyy);
-                    const float maha = dx * (i00 * dx + i01 * dy) + dy * (i01 * dx + i11 * dy);
+                    const float t0 = i00 * dx + i01 * dy, t1 = i01 * dx + i11 * dy;         /* S^-1 d */
+                    out[l] = wx - q * t0;
+                    out[ps + l] = wy - q * t1;
+                    const float sq = q * idet;
+                    const float detp = pxx * pyy - pxy * pxy;
+                    out[2 * ps + l] = sq * (detp + q * pxx);                              /* q S^-1 P */
+                    out[3 * ps + l] = sq * (q * pxy);
+                    out[4 * ps + l] = sq * (detp + q * pyy);
+                    const float maha = dx * t0 + dy * t1;
                     const float hl = 0.5f * orc_det_logf(det);
                     ll = ((0.0f - 0.5f * maha) - hl) - 1.8378770664f;
                 }
