@@ -74,17 +74,13 @@ __device__ __forceinline__ float ekf_rcp_core(float d)
     t = __builtin_fmaf(-d, q, 1.0f);
     return __builtin_fmaf(t, r, q);
 }
-// (SLAM_EKF_PLAIN_DIV: measurement builds with the division itself everywhere)
 __device__ __forceinline__ float ekf_rcp(float d)
 {
-#ifndef SLAM_EKF_PLAIN_DIV
     if (__ballot(!ekf_rcp_in_range(d)) == 0) return ekf_rcp_core(d);
-#endif
     return 1.0f / d;
 }
 __device__ __forceinline__ v2f ekf_rcp(v2f d)
 {
-#ifndef SLAM_EKF_PLAIN_DIV
     if (__ballot(!(ekf_rcp_in_range(d[0]) && ekf_rcp_in_range(d[1]))) == 0) {
         v2f r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
         const v2f one = {1.0f, 1.0f}, nd = -d;
@@ -95,7 +91,6 @@ __device__ __forceinline__ v2f ekf_rcp(v2f d)
         t = __builtin_elementwise_fma(nd, q, one);
         return __builtin_elementwise_fma(t, r, q);
     }
-#endif
     return (v2f){1.0f / d[0], 1.0f / d[1]};
 }
 __device__ __forceinline__ float ekf_log(float d) { return det_logf(d); }

@@ -74,14 +74,12 @@ int check_score_inputs(slam_engine* e, int slot)
 // The grid as the scorers of MANY poses want it: with the byte-per-cell copy (kernels.h: ScoreGrid::packed) when the grid
 // has one.  The copy is made on the first such call after the grid changed — two small launches and ONE wait for their verdict
 // (does the 256-entry table give every cell back bit for bit?), then nothing until the grid changes again.  Few poses (the
-// one-wavefront-per-pose kernel, the lattice) keep the float grid.  SLAM_SCORE_PACKED=0: never (measurements).
+// one-wavefront-per-pose kernel, the lattice) keep the float grid.
 int many_pose_grid(slam_engine* e, int slot, int nposes, ScoreGrid* out)
 {
     GridSlot& g = e->grid[slot];
     *out = score_grid(g);
-    static const bool enabled = !(getenv("SLAM_SCORE_PACKED") && atoi(getenv("SLAM_SCORE_PACKED")) == 0);
-    static const int wave_max = getenv("SLAM_SCORE_WAVE_MAX") ? atoi(getenv("SLAM_SCORE_WAVE_MAX")) : 3072;   // score_body.h: kWaveMaxPoses
-    if (!enabled || nposes < wave_max || g.meta.rows < 8 || g.meta.cols < 16) return SLAM_OK;
+    if (nposes < kWaveMaxPoses || g.meta.rows < 8 || g.meta.cols < 16) return SLAM_OK;
     const int strip_bytes = 16 * ((g.meta.rows + 7) / 8 * 8);
     if (strip_bytes >= (1 << 24)) return SLAM_OK;   // 24-bit multiply in the scorer's cell offset
     if (g.packed_state == 0) {
@@ -221,8 +219,6 @@ int slam_engine_create(int device, slam_engine** out)
     e->h_heads[1] = -1;   // nothing known yet
     e->h_obs[0] = 0;
     e->h_obs[1] = -1;
-    if (getenv("SLAM_EKF_INPLACE")) e->ekf_inplace_form = atoi(getenv("SLAM_EKF_INPLACE"));
-    if (getenv("SLAM_PF_PAGED")) e->pf_paged = atoi(getenv("SLAM_PF_PAGED")) != 0;
     {
         const int32_t one[kGateBufWords] = { 1 };   // "the previous frame resampled": nothing is carried into the first frame; the rest 0
         if (hipMemcpy(e->gate_buf.p, one, sizeof one, hipMemcpyHostToDevice) != hipSuccess) {
@@ -232,7 +228,6 @@ int slam_engine_create(int device, slam_engine** out)
         }
     }
     e->stream = e->own_stream;
-    if (getenv("SLAM_EKF_GROUP")) e->ekf_form = atoi(getenv("SLAM_EKF_GROUP"));
     *out = e;
     return SLAM_OK;
 }
@@ -957,8 +952,7 @@ int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src_x, const f
 {
     ENTER(e);
     *launched = false;
-    static const int env_fusion = getenv("SLAM_FRAME_FUSION") ? atoi(getenv("SLAM_FRAME_FUSION")) : -1;
-    if (!(env_fusion >= 0 ? env_fusion != 0 : e->frame_fusion)) return SLAM_OK;
+    if (!e->frame_fusion) return SLAM_OK;
     if (e->prof_mask & (1 << SLAM_PROF_SCORE)) return SLAM_OK;   // the score stage is being timed: it stays a launch of its own
     // the checks of slam_motion_score_dev and of slam_ekf_update_dev (out of place)
     if (n <= 0 || first_id < 0 || !dp || !sigma || !d_src_x || !d_src_y || !d_src_th || !d_x || !d_y || !d_th || !d_score ||
@@ -1054,7 +1048,8 @@ int slam_ekf_split_dev(slam_engine* e, const float* d_mean_in, float* d_mean_out
     a.cls_out = split->cls_out;
     a.cstamp = split->cstamp;
     a.stamp_now = split->stamp_now;
-    const int group = e->ekf_group_size(n, d_anc != nullptr, plane_stride, false, true);
+    // the tail of a sharded fused frame (group_filter 2) must group the particles as the front launch did
+    const int group = split->group_filter == 2 ? e->front_last[0] : e->ekf_group_size(n, d_anc != nullptr, plane_stride, false, true);
     HIP_TRY(launch_ekf_update(e->stream, a, e->prof_next(split->group_filter == 2 ? SLAM_PROF_EKF_TAIL : SLAM_PROF_EKF), group));
     if (split->group_filter != 2) e->ekf_form_launches[1]++;
     e->ll_n = n;
@@ -1090,7 +1085,7 @@ int slam_ekf_form_set(slam_engine* e, int form)
 {
     ENTER(e);
     if (form < -1 || form > 2) return SLAM_ERR_INVALID_ARG;
-    e->ekf_form = getenv("SLAM_EKF_GROUP") ? atoi(getenv("SLAM_EKF_GROUP")) : form;   // the environment wins (measurements)
+    e->ekf_form = form;
     return SLAM_OK;
 }
 
@@ -1106,7 +1101,7 @@ int slam_ekf_inplace_form_set(slam_engine* e, int form)
 {
     ENTER(e);
     if (form < -1 || form > 1) return SLAM_ERR_INVALID_ARG;
-    e->ekf_inplace_form = getenv("SLAM_EKF_INPLACE") ? atoi(getenv("SLAM_EKF_INPLACE")) : form;
+    e->ekf_inplace_form = form;
     return SLAM_OK;
 }
 

@@ -36,6 +36,13 @@ struct ScoreGrid {
 size_t edt_packed_bytes(int rows, int cols);
 hipError_t launch_edt_pack(hipStream_t stream, const float* edt, int ld, int rows, int cols, uint8_t* packed, float* table,
                            uint32_t* flag);
+// Pose-count threshold below which the scorers' 4-lanes-per-pose form wins (measured on MI355X, 360 beams, pipelined kernels of
+// round 2: 64k poses 28.5 vs 30.1 us; 128k poses 55.4 vs 53.2 us; 256k poses 109 vs 104 us).
+constexpr int kQuadMaxPoses = 131072;
+// ... and below which one wavefront per pose wins over the quad form (360 / 1079 beams: 2k poses 6.1 vs 7.9 us / 18.3 vs
+// 24.4 us; 4k poses 9.2 vs 8.0 us / 27.8 vs 24.6 us; 8k poses 14.9 vs 8.0 us / 44.1 vs 25.1 us).  The quad form is flat
+// up to 8k poses: there its time is the chain of beam steps, not the work.
+constexpr int kWaveMaxPoses = 3072;
 hipError_t launch_score_poses(hipStream_t stream, const ScoreGrid& g, const float* bx, const float* by, int nbeams,
                               const float* x, const float* y, const float* th_or_ct, const float* st_or_null,
                               int nposes, float* score, int32_t* count, const EventPair* ev = nullptr);
@@ -130,7 +137,7 @@ struct EkfArgs {
     // (mu_x, mu_y) of plane_stride floats, row_stride floats apart — and the covariance planes (P_xx, P_xy, P_yy) exist once
     // per COVARIANCE CLASS: in the world-frame update the posterior covariance of a landmark depends on its prior covariance,
     // on q and on whether the frame observes it, never on the particle, so particles whose covariances were equal once stay
-    // equal for ever and share one row cov[class].  The update reads it (launch_cov_update rewrites it afterwards, once per
+    // equal for ever and share one row cov[class].  The update reads it (cov_update_body rewrites it afterwards, once per
     // class), hands the class of the source particle on to its offspring and marks it as still in use.
     const float* cov = nullptr;       // [classes][3][plane_stride]
     int64_t cov_stride = 0;           // floats between the rows of two classes
@@ -201,7 +208,6 @@ struct CovArgs {
     uint32_t epoch;
     uint32_t mark;         // the host's running count of classes appended to the list so far (sharded sessions: rows received)
 };
-hipError_t launch_cov_update(hipStream_t stream, const CovArgs& a, int bound, const EventPair* ev = nullptr);
 // rows [n][5][plane_stride_in] (row_stride_in floats apart) -> means [n][2][Lp], classes, class rows [..][3][Lp]: neighbouring
 // particles whose three covariance planes are equal bit for bit share a class (classes are numbered 0, 1, .. in particle
 // order; all particles alike -> one class).  scratch: split_scratch_words(n) int32 words.  live[k] = k, cnt[phase] = number
@@ -252,11 +258,7 @@ hipError_t launch_build_obs_list(hipStream_t stream, const float* tzx, const flo
 hipError_t launch_ekf_sparse(hipStream_t stream, const EkfArgs& a, const int32_t* id, const float* zx, const float* zy,
                              const int32_t* round, const int32_t* count, const EventPair* ev = nullptr);
 // ---- paged_kernels.hip: landmark maps as copy-on-write pages of kPageLandmarks landmarks (5 planes x 32 floats = 640 B)
-// (SLAM_PAGE_LANDMARKS: a power of two <= 32, for measurement builds — profiles/collect_page_sizes.sh; the product is built with 32)
-#ifndef SLAM_PAGE_LANDMARKS
-#define SLAM_PAGE_LANDMARKS 32
-#endif
-constexpr int kPageLandmarks = SLAM_PAGE_LANDMARKS;
+constexpr int kPageLandmarks = 32;   // 16- and 8-landmark pages measured no faster: profiles/r03_page_sizes.md
 // the compact observation list launch_build_obs_list makes: ids ascending, measurements, accumulator rounds, {nobs, highest round}
 struct ObsListView {
     const int32_t* id = nullptr;
@@ -362,7 +364,9 @@ hipError_t launch_migrate_unpack_paged(hipStream_t stream, const float* in, int 
 hipError_t launch_logweight(hipStream_t stream, const float* score, const float* loglik, float gain, int n,
                             float* logw, float* block_max_scratch, float* d_max, const float* carry = nullptr,
                             const int32_t* prev_resampled = nullptr, const CovArgs* cov = nullptr, int cov_bound = 0);
-// (cov: the same launch carries launch_cov_update(cov, cov_bound) in workgroups of its own — cov_update_body.h)
+// (cov: the same launch carries the covariance classes' update of cov_bound classes in workgroups of its own — cov_update_body.h;
+// cov->nlandmarks == 0: a frame without observations — only the list is brought up to date (classes whose last particle went
+// with the frame's gather leave it: a sharded session may hand their numbers out again, and a number must not be listed twice))
 int logweight_scratch_elems(int n);
 int logweight_scratch_floats();   // size of block_max_scratch: block maxima + two words, zero-initialised once
 hipError_t launch_quantise_weights(hipStream_t stream, const float* logw, const float* d_max, int n, uint64_t* wq,

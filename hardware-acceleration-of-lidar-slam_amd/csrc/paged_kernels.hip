@@ -712,13 +712,12 @@ hipError_t launch_ekf_paged(hipStream_t stream, const PagedEkfArgs& a, const Eve
     if (ev) (void)hipEventRecord(ev->start, stream);
     constexpr int per_block = kWaves * (64 / kPage);
     const int grid = (a.n + per_block - 1) / per_block;
-    static const int pg_env = getenv("SLAM_PAGED_PG") ? atoi(getenv("SLAM_PAGED_PG")) : 0;
     // pages staged per pass: what the last frame touched (a frame's touched pages then go through in one pass without idle
     // slots); any value gives the same results.  Frames that touch more than six pages per particle run the page-wide form:
     // with that many pages the LDS image costs more wavefronts in flight than the list form saves (measured, 64k x 500 with
     // 128 observed / 64k x 5000 with 512: 120 / 460 us page-wide against 123 / 474 us at best).
-    const int pg = pg_env > 0 ? pg_env : (touched_hint > 0 ? touched_hint : 6);
-    const bool wide = form == 0 || !a.ol.id || (pg_env <= 0 && touched_hint > 6);
+    const int pg = touched_hint > 0 ? touched_hint : 6;
+    const bool wide = form == 0 || !a.ol.id || touched_hint > 6;
 #define SLAM_PAGED(SP_)                                                                              \
     do {                                                                                             \
         if (wide) ekf_paged_kernel<SP_><<<grid, kWaves * 64, 0, stream>>>(a);                        \

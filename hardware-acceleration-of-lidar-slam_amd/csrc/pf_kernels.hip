@@ -69,19 +69,14 @@ typedef __attribute__((address_space(1))) float gfloat;
 // cache policy of the row stores: 2 = nt (streaming; the written rows are next read a frame later, long after they
 // left the caches).  Measured at 64k x 500: default 170 us, nt 162 us, sc0 170 us, sc1 171 us in the filter;
 // 243 / 248 / 244 / 243 us for a sweep without shared ancestors.
-#ifndef EKF_STORE_AUX
-#define EKF_STORE_AUX 2
-#endif
+constexpr int kEkfStoreAux = 2;
 __device__ __forceinline__ float row_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
 {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, soff, 0));
 }
 __device__ __forceinline__ void row_store(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff, float v)
 {
-#ifdef EKF_MEASURE_NO_STORES   // measurement builds only (wrong results): what the kernels take without their row stores
-    if (__float_as_uint(v) == 0x7fc12345u)
-#endif
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)voff, soff, EKF_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)voff, soff, kEkfStoreAux);
 }
 __device__ __forceinline__ gchar* uniform_gptr(const void* p)   // tell the compiler the pointer is wave-uniform
 {
@@ -364,7 +359,7 @@ __device__ __forceinline__ float lane_value(float v, int k)   // lane k's value,
     return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), k));
 }
 
-// EKF_GROUP_NB: batches of 128 landmarks a wavefront of the grouped kernels holds in registers per pass; EKF_GROUP_WPE: waves
+// kEkfGroupNb: batches of 128 landmarks a wavefront of the grouped kernels holds in registers per pass; kEkfGroupWpe: waves
 // per SIMD the register allocation is held to.  With the pose-independent part of the update hoisted (ekf_prepare) a batch
 // costs 13 register pairs: two batches need 97 VGPRs (5 waves at 96 with two dwords of scratch), one batch 69 (7 waves).
 // Interleaved A/B on one box (profiles/ab.py, 64k x 500 in the filter): 2 batches at 5 waves — fused front 125.7 us
@@ -374,22 +369,10 @@ __device__ __forceinline__ float lane_value(float v, int k)   // lane k's value,
 // at 6 waves): fused front 148-153 us, update alone 133-149 us.
 // 4 waves (97 VGPRs, nothing spilled) against 5 on another, slower box: fused front 142.7 against 147.3 us, update alone
 // 145.0 against 146.3 us; equal at 2000 landmarks and with 32 of 500 observed.
-#ifndef EKF_GROUP_WPE
-#define EKF_GROUP_WPE 4
-#endif
-#ifndef EKF_GROUP_NB
-#define EKF_GROUP_NB 2
-#endif
-#define EKF_GROUP_ATTR __attribute__((amdgpu_waves_per_eu(EKF_GROUP_WPE, EKF_GROUP_WPE)))
-// the same two knobs for the kernels of the split layout (a batch costs fewer registers there: no covariance planes to carry)
-#ifndef EKF_SPLIT_WPE
-#define EKF_SPLIT_WPE 5   // 64k x 500, fused front: 4 waves 97.7 us, 5 waves 94.8 us, 6 waves 99.4 us, 8 waves (spills) 149 us
-#endif
-#ifndef EKF_SPLIT_NB
-#define EKF_SPLIT_NB 2
-#endif
-#define EKF_SPLIT_ATTR __attribute__((amdgpu_waves_per_eu(EKF_SPLIT_WPE, EKF_SPLIT_WPE)))
-#define EKF_FRONT_ATTR(SPLIT_) __attribute__((amdgpu_waves_per_eu((SPLIT_) ? EKF_SPLIT_WPE : EKF_GROUP_WPE, (SPLIT_) ? EKF_SPLIT_WPE : EKF_GROUP_WPE)))
+constexpr int kEkfGroupWpe = 4, kEkfGroupNb = 2;
+// the same two for the kernels of the split layout (a batch costs fewer registers there: no covariance planes to carry)
+constexpr int kEkfSplitWpe = 5;   // 64k x 500, fused front: 4 waves 97.7 us, 5 waves 94.8 us, 6 waves 99.4 us, 8 waves (spills) 149 us
+constexpr int kEkfSplitNb = 2;
 // `bid`: the workgroup's index after the XCD-contiguous renumbering; s_acc: per particle of the group the 128 accumulators of
 // the specification.  OWN_MOTION (the fused front kernel of a frame, below): the poses are not read from a.x / a.y / a.th but
 // worked out here — pose = motion_sample(source pose of the ancestor), the very computation the scoring workgroups of the
@@ -515,7 +498,8 @@ __device__ __forceinline__ void ekf_group_body(const EkfArgs& a, int bid, float 
 }
 
 template <int NB, int G>
-__global__ __launch_bounds__(kEkfWaves * 64) EKF_GROUP_ATTR void ekf_update_group_kernel(EkfArgs a)
+__global__ __launch_bounds__(kEkfWaves * 64) __attribute__((amdgpu_waves_per_eu(kEkfGroupWpe, kEkfGroupWpe)))
+void ekf_update_group_kernel(EkfArgs a)
 {
     __shared__ float s_acc[kEkfWaves][G][128];
     int bid = blockIdx.x;
@@ -802,7 +786,8 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
 // occupancy at 4).  Removed; profiles/r04_split_tuning.md.)
 
 template <int NB, int G>
-__global__ __launch_bounds__(kEkfWaves * 64) EKF_SPLIT_ATTR void ekf_split_kernel(EkfArgs a)
+__global__ __launch_bounds__(kEkfWaves * 64) __attribute__((amdgpu_waves_per_eu(kEkfSplitWpe, kEkfSplitWpe)))
+void ekf_split_kernel(EkfArgs a)
 {
     __shared__ float s_acc[kEkfWaves][G][128];
     int bid = blockIdx.x;
@@ -834,15 +819,16 @@ struct FrontArgs {
 };
 
 template <int NB, int G, int LPP, int DEPTH, bool SPLIT = false, bool PACKED = false>
-__global__ __launch_bounds__(kEkfWaves * 64) EKF_FRONT_ATTR(SPLIT) void frame_front_kernel(FrontArgs f)
+__global__ __launch_bounds__(kEkfWaves * 64) __attribute__((amdgpu_waves_per_eu(SPLIT ? kEkfSplitWpe : kEkfGroupWpe, SPLIT ? kEkfSplitWpe : kEkfGroupWpe)))
+void frame_front_kernel(FrontArgs f)
 {
     static_assert(kScoreBlock == kEkfWaves * 64, "both kinds of workgroup have 256 threads");
     extern __shared__ float4 s_pair[];
     __shared__ float s_acc[kEkfWaves][G][128];
     const int o = (int)blockIdx.x >> 3, xcd = (int)blockIdx.x & 7;
-    // the scoring octets are spread evenly over the first `span` octets of the grid: the whole grid, unless SLAM_FRONT_SPAN (per
-    // cent, measurements) says otherwise — 64k x 500, 4 / 2 particles per updating wavefront: 100 % 130.7 / 158.5 us, 75 %
-    // 134.0 / 156.3, 50 % 155.1 / 154.8, 25 % 141.2 / 157.9
+    // the scoring octets are spread evenly over the first `span` octets of the grid: the whole grid (against the first part of it
+    // only — 64k x 500, 4 / 2 particles per updating wavefront: 100 % 130.7 / 158.5 us, 75 % 134.0 / 156.3, 50 % 155.1 / 154.8,
+    // 25 % 141.2 / 157.9)
     const int64_t span = f.score_span;
     const int before = o < span ? (int)((int64_t)o * f.score_octets / span) : f.score_octets;             // scoring octets among 0 .. o - 1
     const int upto = o + 1 < span ? (int)((int64_t)(o + 1) * f.score_octets / span) : f.score_octets;    // ... among 0 .. o
@@ -2077,18 +2063,6 @@ hipError_t launch_motion_sample(hipStream_t stream, const float* sx, const float
     return hipGetLastError();
 }
 
-// SLAM_SPLIT_G (measurements): particles per updating wavefront on the split layout.  Only the instantiated 2, 4 and 8 are
-// taken; any other value is ignored (a grid sized for one G and a kernel built for another would skip particles).
-static int forced_split_g()
-{
-    static const int g = [] {
-        const char* e = getenv("SLAM_SPLIT_G");
-        const int v = e ? atoi(e) : 0;
-        return v == 2 || v == 4 || v == 8 ? v : 0;
-    }();
-    return g;
-}
-
 hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const EventPair* ev, int group_size)
 {
     if (a_in.n <= 0) return hipSuccess;
@@ -2100,8 +2074,7 @@ hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const Even
         blocks = 8 * a.xcd_chunk;
     }
     if (a.cov) {   // split layout: always the grouped form (2 particles per wavefront unless the caller asks for 4 or 8)
-        const int forced = forced_split_g();
-        const int G = forced ? forced : (group_size == 4 || group_size == 8 ? group_size : 2);
+        const int G = group_size == 4 || group_size == 8 ? group_size : 2;
         int gblocks = (a.n + kEkfWaves * G - 1) / (kEkfWaves * G);
         a.xcd_chunk = 0;
         if (gblocks >= 64) {
@@ -2109,9 +2082,9 @@ hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const Even
             gblocks = 8 * a.xcd_chunk;
         }
         if (ev) (void)hipEventRecord(ev->start, stream);
-        if (G == 8) ekf_split_kernel<EKF_SPLIT_NB, 8><<<gblocks, kEkfWaves * 64, 0, stream>>>(a);
-        else if (G == 4) ekf_split_kernel<EKF_SPLIT_NB, 4><<<gblocks, kEkfWaves * 64, 0, stream>>>(a);
-        else ekf_split_kernel<EKF_SPLIT_NB, 2><<<gblocks, kEkfWaves * 64, 0, stream>>>(a);
+        if (G == 8) ekf_split_kernel<kEkfSplitNb, 8><<<gblocks, kEkfWaves * 64, 0, stream>>>(a);
+        else if (G == 4) ekf_split_kernel<kEkfSplitNb, 4><<<gblocks, kEkfWaves * 64, 0, stream>>>(a);
+        else ekf_split_kernel<kEkfSplitNb, 2><<<gblocks, kEkfWaves * 64, 0, stream>>>(a);
         if (ev) (void)hipEventRecord(ev->stop, stream);
         return hipGetLastError();
     }
@@ -2123,11 +2096,10 @@ hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const Even
         // group size: measured on MI355X (64k x 500 | 1M x 1000 | 64k x 500 with 50 % distinct ancestors | 512k x 5000; one
         // wavefront per particle: 156 us | 4.28 ms | 177 us | 10.09 ms): 2 particles 148 | 4.09 | 169 | 9.79; 3: 135;
         // 4: 139 | 3.86 | 180 | 9.82; 6: 141; 8: 150 | 3.84 | 199 | 9.92.  Hence 4 when neighbours share ancestors, 2 when
-        // they rarely do.  SLAM_EKF_G overrides (measurements).  Batches in flight per pass (the first template argument),
+        // they rarely do.  Batches in flight per pass (the first template argument),
         // group of 4, 64k x 500 | 1M x 1000 | 512k x 5000: 1: 150 us | 3.97 ms; 2: 140-145 | 3.90-3.92 | 9.79; 3: 144 | 4.02;
         // 4: 137-139 | 3.86 | 9.86 — within the run-to-run spread: 2 kept (82 VGPRs, 5 waves per SIMD; 4 needs 114).
-        static const int forced = getenv("SLAM_EKF_G") ? atoi(getenv("SLAM_EKF_G")) : 0;
-        const int G = forced ? forced : group_size;
+        const int G = group_size;
         int gblocks = (a.n + kEkfWaves * G - 1) / (kEkfWaves * G);
         a.xcd_chunk = 0;
         if (gblocks >= 64) {
@@ -2136,9 +2108,9 @@ hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const Even
         }
         if (ev) (void)hipEventRecord(ev->start, stream);
         switch (G) {
-        case 2: ekf_update_group_kernel<EKF_GROUP_NB, 2><<<gblocks, kEkfWaves * 64, 0, stream>>>(a); break;
-        case 8: ekf_update_group_kernel<EKF_GROUP_NB, 8><<<gblocks, kEkfWaves * 64, 0, stream>>>(a); break;
-        default: ekf_update_group_kernel<EKF_GROUP_NB, 4><<<gblocks, kEkfWaves * 64, 0, stream>>>(a); break;
+        case 2: ekf_update_group_kernel<kEkfGroupNb, 2><<<gblocks, kEkfWaves * 64, 0, stream>>>(a); break;
+        case 8: ekf_update_group_kernel<kEkfGroupNb, 8><<<gblocks, kEkfWaves * 64, 0, stream>>>(a); break;
+        default: ekf_update_group_kernel<kEkfGroupNb, 4><<<gblocks, kEkfWaves * 64, 0, stream>>>(a); break;
         }
         if (ev) (void)hipEventRecord(ev->stop, stream);
         return hipGetLastError();
@@ -2158,8 +2130,7 @@ hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const Even
 
 bool frame_front_fits(int n, int nlandmarks, int group_size)
 {
-    static const int wave_max = getenv("SLAM_SCORE_WAVE_MAX") ? atoi(getenv("SLAM_SCORE_WAVE_MAX")) : kWaveMaxPoses;
-    if (n < wave_max || nlandmarks <= 128 || (group_size != 2 && group_size != 4 && group_size != 8)) return false;
+    if (n < kWaveMaxPoses || nlandmarks <= 128 || (group_size != 2 && group_size != 4 && group_size != 8)) return false;
     return (n + kEkfWaves * group_size - 1) / (kEkfWaves * group_size) >= 64;
 }
 
@@ -2173,17 +2144,11 @@ hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const floa
 {
     *launched = false;
     const int n = a_in.n;
-    static const int quad_max = getenv("SLAM_SCORE_QUAD_MAX") ? atoi(getenv("SLAM_SCORE_QUAD_MAX")) : kQuadMaxPoses;
-    const int forced_g = forced_split_g();
-    if (a_in.cov && forced_g) group_size = forced_g;
     if (!a_in.cov && group_size == 8) group_size = 4;   // rows: 2 or 4 particles per updating wavefront
     if (a_in.map_in == a_in.map_out || !frame_front_fits(n, a_in.nlandmarks, group_size)) return hipSuccess;
     const int G = group_size;
     const int gblocks = (n + kEkfWaves * G - 1) / (kEkfWaves * G);
-    // inside the fused launch the scorer's latency is hidden anyway; what counts is how long its wavefronts hold slots the
-    // update would fill: SLAM_FRONT_QUAD_MAX = population below which the 4-lanes-per-pose scorer is used here (measurements)
-    static const int front_quad_max = getenv("SLAM_FRONT_QUAD_MAX") ? atoi(getenv("SLAM_FRONT_QUAD_MAX")) : quad_max;
-    const bool quad = n < front_quad_max;
+    const bool quad = n < kQuadMaxPoses;
     FrontArgs f;
     f.g = g;
     f.bx = bx;
@@ -2198,15 +2163,13 @@ hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const floa
     f.a.xcd_chunk = f.ekf_octets;
     f.score_blocks = (int)(((quad ? 4L : 1L) * n + kScoreBlock - 1) / kScoreBlock);
     f.score_octets = (f.score_blocks + 7) / 8;
-    const int grid = 8 * (f.score_octets + f.ekf_octets);
-    static const int span_pct = getenv("SLAM_FRONT_SPAN") ? atoi(getenv("SLAM_FRONT_SPAN")) : 100;
-    const int64_t span = (int64_t)(f.score_octets + f.ekf_octets) * (span_pct < 1 ? 1 : span_pct > 100 ? 100 : span_pct) / 100;
-    f.score_span = (int)(span > f.score_octets ? span : f.score_octets);
+    f.score_span = f.score_octets + f.ekf_octets;
+    const int grid = 8 * f.score_span;
     const size_t lds = sizeof(float2) * (size_t)(nbeams + (quad ? 4 * kQuadDepth : kLaneDepth)) + (g.packed ? 1024 : 0);
     if (ev) (void)hipEventRecord(ev->start, stream);
     // the instantiation: particles per updating wavefront x scorer's lane mapping x map layout x grid copy the scorer reads
 #define SLAM_FRONT(G_, LPP_, DEPTH_, SP_, PK_) \
-    frame_front_kernel<(SP_) ? EKF_SPLIT_NB : EKF_GROUP_NB, G_, LPP_, DEPTH_, SP_, PK_><<<grid, kEkfWaves * 64, lds, stream>>>(f)
+    frame_front_kernel<(SP_) ? kEkfSplitNb : kEkfGroupNb, G_, LPP_, DEPTH_, SP_, PK_><<<grid, kEkfWaves * 64, lds, stream>>>(f)
 #define SLAM_FRONT_GL(SP_, PK_)                          \
     do {                                                 \
         if (quad) {                                      \
@@ -2297,7 +2260,7 @@ hipError_t launch_logweight(hipStream_t stream, const float* score, const float*
 {
     if (n <= 0) return hipSuccess;
     const int nb = capped_blocks(n);
-    if (cov && cov_bound > 0) {   // + the covariance classes' update (launch_cov_update's grid, flattened)
+    if (cov && cov_bound > 0) {   // + the covariance classes' update (a grid of cov_bound x ly workgroups, flattened)
         const int ly = cov->nlandmarks > 0 ? (cov->nlandmarks + 255) / 256 : 1;
         logweight_cov_kernel<<<nb + (int64_t)cov_bound * ly, kBlock, 0, stream>>>(score, loglik, gain, n, carry, prev_resampled, logw,
                                                                                block_max_scratch, nb, ly, *cov);

@@ -44,7 +44,6 @@ struct slam_pf {
     float* pose_stage = nullptr;    // [3][cap]: where the poses inside migrated records land (nothing reads them)
     int32_t* pose_idx[2] = { nullptr, nullptr };   // position of every slot's ancestor in pose_all
     int32_t* first_all = nullptr;   // [n_total]
-    float* d_max = nullptr;         // weight normaliser (all-reduced)
     uint64_t *d_sum = nullptr, *totals = nullptr;   // shard total; all-gathered shard totals [world]
     int32_t* d_plan = nullptr;      // exchange plan of the frame, device copy
     float *sbuf = nullptr, *rbuf = nullptr;   // grow-only exchange buffers
@@ -85,7 +84,7 @@ struct slam_pf {
     int sp_cur = 0;                 // mean / class buffer of the current particles
     int32_t* cls[2] = { nullptr, nullptr };    // [cap]
     int32_t* live[2] = { nullptr, nullptr };   // [cap] the classes in use, current list and next
-    int32_t* cov_cnt = nullptr;     // [3] list lengths, rotating (see cov_update_kernel)
+    int32_t* cov_cnt = nullptr;     // [3] list lengths, rotating (see cov_update_body.h)
     uint32_t* cstamp = nullptr;     // [cap]
     uint32_t cstamp_now = 0, cls_epoch = 0;
     int live_cur = 0, cov_phase = 0;
@@ -94,7 +93,7 @@ struct slam_pf {
     int32_t* cls_free = nullptr;    // [cap]
     int32_t* cls_fs = nullptr;      // two words of the list kernel's bookkeeping
     int64_t cls_cursor = 0;         // entries of the current list handed out so far (beyond its guaranteed length: make a new one)
-    uint32_t cls_appended = 0;      // classes appended to the list so far in this epoch (what cov_update_kernel's `mark` carries)
+    uint32_t cls_appended = 0;      // classes appended to the list so far in this epoch (what cov_update_body's `mark` carries)
     void* split_scratch = nullptr;  // flags, prefix sums of a rows -> split move
     bool gated = false;             // cfg.resample_ess_frac in (0, 1): a frame resamples only when its ESS is low
     int64_t frames_resampled = 0;   // (as far as the host has looked: one frame behind)
@@ -653,7 +652,7 @@ int create_common(slam_engine* e, const slam_pf_config* cfg, slam_comm* comm, in
     if (comm)
         ok = ok && dev_alloc((void**)&pf->pose_all, 3 * n * G * 4) == hipSuccess &&
              dev_alloc((void**)&pf->pose_stage, 3 * cap * 4) == hipSuccess &&
-             dev_alloc((void**)&pf->first_all, n * G * 4) == hipSuccess && dev_alloc((void**)&pf->d_max, 4) == hipSuccess &&
+             dev_alloc((void**)&pf->first_all, n * G * 4) == hipSuccess &&
              dev_alloc((void**)&pf->d_sum, 3 * 8) == hipSuccess && dev_alloc((void**)&pf->totals, 3 * 8 * G) == hipSuccess &&
              dev_alloc((void**)&pf->d_plan, 4 * SLAM_PLAN_WORDS(kMaxRanks)) == hipSuccess;
     if (!ok) {
@@ -716,7 +715,7 @@ int slam_pf_destroy(slam_pf* pf)
     free_page_tables(pf);
     free_split_tables(pf);
     for (void* p : { (void*)pf->score, (void*)pf->logw, (void*)pf->count, (void*)pf->first, (void*)pf->pose_all, (void*)pf->pose_stage, (void*)pf->first_all,
-                     (void*)pf->d_max, (void*)pf->d_sum, (void*)pf->totals, (void*)pf->d_plan, (void*)pf->sbuf,
+                     (void*)pf->d_sum, (void*)pf->totals, (void*)pf->d_plan, (void*)pf->sbuf,
                      (void*)pf->rbuf, (void*)pf->res_dev, (void*)pf->sums_acc, pf->res_all })
         (void)hipFree(p);
     (void)hipFree(pf->sel);
@@ -829,13 +828,13 @@ int slam_pf_set_map_dev(slam_pf* pf, const float* d_rows, int64_t row_stride, in
 
 int slam_pf_is_paged(const slam_pf* pf) { return pf && pf->paged ? 1 : 0; }
 
-// The classes' update of a frame (cov_update_kernel), in place, once per class still in use; nlandmarks = 0: only the list of
+// The classes' update of a frame (cov_update_body.h), in place, once per class still in use; nlandmarks = 0: only the list of
 // classes in use is brought up to date (a frame without observations).  The launch is as wide as the host knows the list to
 // be at most: its length as of some earlier launch (mapped memory, read without waiting) plus the classes that arrived since
 // (sharded sessions) — the second word is the running count of arrivals as of that launch; it is read FIRST and written
 // last, so a torn pair only over-estimates; before anything of this epoch has arrived: every class there can be.
 // the arguments and the width of the classes' update of this frame (and the session's bookkeeping moved on as if it had been
-// launched: the caller launches it, by itself or inside the launch of the weights)
+// launched: the launch of the weights carries it)
 static void split_class_prepare(slam_pf* pf, int nlandmarks, CovArgs& ca, int& bound)
 {
     slam_engine* e = pf->e;
@@ -869,29 +868,13 @@ static void split_class_prepare(slam_pf* pf, int nlandmarks, CovArgs& ca, int& b
     pf->cov_phase = (pf->cov_phase + 1) % 3;
 }
 
-static int split_class_update(slam_pf* pf, int nlandmarks)
+// the classes' update of the frame + the weights: ONE launch
+static int weights_with_classes(slam_pf* pf, int nlandmarks, bool use_ekf)
 {
     CovArgs ca;
     int bound = 0;
     split_class_prepare(pf, nlandmarks, ca, bound);
-    SLAM_HIP_TRY(pf->e, launch_cov_update(pf->e->stream, ca, bound, pf->e->prof_next(SLAM_PROF_PAGES)));
-    return SLAM_OK;
-}
-
-// the classes' update of the frame + the weights: ONE launch (SLAM_COV_MERGE=0: two, as round 4 first had them)
-static int weights_with_classes(slam_pf* pf, int nlandmarks, bool use_ekf, float* d_max)
-{
-    static const bool merge = !(getenv("SLAM_COV_MERGE") && atoi(getenv("SLAM_COV_MERGE")) == 0);
-    slam_engine* e = pf->e;
-    if (!merge) {
-        if (int rc = split_class_update(pf, nlandmarks)) return rc;
-        return use_ekf ? slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, pf->n, pf->logw, d_max)
-                       : slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, pf->n, pf->logw, d_max);
-    }
-    CovArgs ca;
-    int bound = 0;
-    split_class_prepare(pf, nlandmarks, ca, bound);
-    return slam_logweight_cov_dev(e, pf->score, use_ekf, pf->cfg.score_gain, pf->n, pf->logw, d_max, &ca, bound);
+    return slam_logweight_cov_dev(pf->e, pf->score, use_ekf, pf->cfg.score_gain, pf->n, pf->logw, nullptr, &ca, bound);
 }
 
 static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations, bool* collective_verdict);
@@ -954,9 +937,8 @@ static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observ
     // session issues both behind its exchange, which takes pages from the same list first.
     int32_t *pstate = pf->page_scratch, *count = pstate + pool_state_words(), *tpage = count + 1, *tindex = tpage + pf->nb,
             *tmask = tindex + pf->nb, *tbase = tmask + pf->nb, *lst = tbase + pf->nb + 1;
-    // the list form (one lane per observation) whenever a list can be made; SLAM_PAGED_FORM=0 keeps the page-wide form
-    static const int env_form = getenv("SLAM_PAGED_FORM") ? atoi(getenv("SLAM_PAGED_FORM")) : 1;
-    const int form = env_form != 0 && L <= kObsListMaxLandmarks ? 1 : 0;
+    // the list form (one lane per observation) whenever a list can be made
+    const int form = L <= kObsListMaxLandmarks ? 1 : 0;
     ObsListOut lo;
     if (form && pf->paged) {
         lo.id = lst;
@@ -972,10 +954,9 @@ static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observ
                                          sample_obs ? pf->votes : nullptr, reinterpret_cast<int32_t*>(pf->d_hres) + 30, lo));
         return SLAM_OK;
     };
-    static const bool ride = !(getenv("SLAM_FREE_LIST_RIDER") && atoi(getenv("SLAM_FREE_LIST_RIDER")) == 0);
     bool paged_listed = false;
     FreeListRider rider;
-    if (ride && !comm && pf->paged && L > 0 && use_observations && e->obs_nlandmarks == L) {
+    if (!comm && pf->paged && L > 0 && use_observations && e->obs_nlandmarks == L) {
         if (int rc1 = issue_page_list()) return rc1;
         rider.stamp = pf->stamp;
         rider.npages = pf->npages;
@@ -1053,12 +1034,6 @@ static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observ
     // 3. per-landmark EKF (+ fused gather); the log-likelihood stays inside the engine for step 4
     const bool ekf = L > 0 && use_observations;
     const int mc = pf->map_cur, mn = 1 - mc;
-    // Sharded: the ranks all-reduce the BLOCK maxima the weights' launch leaves in the engine (element by element: a few hundred
-    // floats cost the wire what one costs) and the scan takes their maximum itself, as it does on one GPU — the maximum of the
-    // same set of values, and one single-workgroup launch less per frame than reducing them to one float first
-    // (SLAM_MAX_FINALIZE=1: that launch and a one-float all-reduce, as before).
-    static const bool finalize = getenv("SLAM_MAX_FINALIZE") && atoi(getenv("SLAM_MAX_FINALIZE")) != 0;
-    float* d_max = comm && finalize ? pf->d_max : nullptr;
     if (pf->split && !pf->paged && L > 0) {
         const int sc = pf->sp_cur;
         make_sio();   // (again: a layout move in front of the frame leaves other buffers than the ones the first look saw)
@@ -1076,16 +1051,16 @@ static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observ
             pf->cstamp_now++;
             pf->sp_cur = 1 - sc;
             // ... then the classes' update, in place, once per class still in use
-            rc = weights_with_classes(pf, L, true, d_max);
+            rc = weights_with_classes(pf, L, true);
         } else {
             if (anc) {   // means and classes follow their particles
                 const ProfScope prof(e, SLAM_PROF_PAGES);
                 SLAM_HIP_TRY(e, launch_split_gather(e->stream, pf->mean[sc], pf->mean[1 - sc], pf->cls[sc], pf->cls[1 - sc], pf->Lp, anc, n,
                                                     pf->cstamp, ++pf->cstamp_now));
                 pf->sp_cur = 1 - sc;
-                rc = weights_with_classes(pf, 0, false, d_max);   // no observations: the list of classes in use only
+                rc = weights_with_classes(pf, 0, false);   // no observations: the list of classes in use only
             } else
-                rc = slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, d_max);
+                rc = slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
         }
     } else if (pf->paged) {
         const int pc = pf->pt_cur;
@@ -1149,9 +1124,9 @@ static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observ
             if (pf->split) {   // the classes went with their particles; their covariances, once per class, with the weights
                 pf->cstamp_now++;
                 pf->sp_cur = 1 - pf->sp_cur;
-                rc = weights_with_classes(pf, L, true, d_max);
+                rc = weights_with_classes(pf, L, true);
             } else
-                rc = slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, d_max);
+                rc = slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
         } else {
             if (anc) {   // the tables follow their particles
                 const ProfScope prof(e, SLAM_PROF_PAGES);
@@ -1164,15 +1139,15 @@ static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observ
                     pf->sp_cur = 1 - pf->sp_cur;
                 }
             }
-            rc = anc && pf->split ? weights_with_classes(pf, 0, false, d_max)
-                                  : slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, d_max);
+            rc = anc && pf->split ? weights_with_classes(pf, 0, false)
+                                  : slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
         }
     } else if (ekf && in_place) {
         if (sample_obs) SLAM_HIP_TRY(e, launch_obs_count(e->stream, e->d_obs_zx, e->d_obs_zy, L, d_hobs, ++pf->obs_seq_issued, pf->votes));
         rc = slam_ekf_update_dev(e, pf->map[mc], pf->map[mc], 5 * (int64_t)pf->Lp, pf->Lp, L, dst, dst + sn, dst + 2 * sn, nullptr, n,
                                  pf->cfg.meas_var, nullptr);
         if (rc != SLAM_OK) return rc;
-        rc = slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, d_max);
+        rc = slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
     } else if (ekf) {
         if (sample_obs) SLAM_HIP_TRY(e, launch_obs_count(e->stream, e->d_obs_zx, e->d_obs_zy, L, d_hobs, ++pf->obs_seq_issued, pf->votes));
         rc = fused ? SLAM_OK   // the update went out with the score
@@ -1180,7 +1155,7 @@ static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observ
                                          n, pf->cfg.meas_var, nullptr);
         if (rc != SLAM_OK) return rc;
         pf->map_cur = mn;
-        rc = slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, d_max);
+        rc = slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
     } else {
         if (L > 0 && anc && !in_place) {   // the maps follow their particles even without an observation
             rc = slam_gather_map_dev(e, pf->map[mc], pf->map[mn], 5 * (int64_t)pf->Lp, 5 * (int64_t)pf->Lp, pf->Lp, pf->Lp, L,
@@ -1188,19 +1163,18 @@ static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observ
             if (rc != SLAM_OK) return rc;
             pf->map_cur = mn;
         }
-        rc = slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, d_max);
+        rc = slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
     }
     if (rc != SLAM_OK) return rc;
     // 4. weights: the maximum over all ranks, then fixed-point weights scanned as they are produced
+    // Sharded: the ranks all-reduce the BLOCK maxima the weights' launch leaves in the engine (element by element: a few hundred
+    // floats cost the wire what one costs) and the scan takes their maximum itself, as it does on one GPU — the maximum of the
+    // same set of values, and one single-workgroup launch less per frame than reducing them to one float first.
     if (comm) {
-        if (d_max) {
-            if ((rc = comm_all_reduce_max_f32(comm, pf->d_max, 1)) != SLAM_OK) return rc;
-        } else {
-            if (e->bmax_n != n || e->bmax_count <= 0) return SLAM_ERR_NOT_READY;
-            if ((rc = comm_all_reduce_max_f32(comm, e->bmax_buf.as<float>(), e->bmax_count)) != SLAM_OK) return rc;
-        }
+        if (e->bmax_n != n || e->bmax_count <= 0) return SLAM_ERR_NOT_READY;
+        if ((rc = comm_all_reduce_max_f32(comm, e->bmax_buf.as<float>(), e->bmax_count)) != SLAM_OK) return rc;
     }
-    if ((rc = slam_quantise_scan_dev(e, pf->logw, d_max, n, comm ? pf->d_sum : nullptr)) != SLAM_OK) return rc;
+    if ((rc = slam_quantise_scan_dev(e, pf->logw, nullptr, n, comm ? pf->d_sum : nullptr)) != SLAM_OK) return rc;
     // 5. resample on the integer CDF
     if (!comm) {
         if ((rc = slam_ancestors_from_scan_dev(e, n, pf->cfg.seed, pf->frame, pf->anc[nxt])) != SLAM_OK) return rc;

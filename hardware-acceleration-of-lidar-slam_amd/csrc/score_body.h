@@ -230,12 +230,4 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
     }
 }
 
-// Pose-count threshold below which the 4-lanes-per-pose form wins (measured on MI355X, 360 beams, pipelined kernels of
-// round 2: 64k poses 28.5 vs 30.1 us; 128k poses 55.4 vs 53.2 us; 256k poses 109 vs 104 us).
-constexpr int kQuadMaxPoses = 131072;
-// ... and below which one wavefront per pose wins over the quad form (360 / 1079 beams: 2k poses 6.1 vs 7.9 us / 18.3 vs
-// 24.4 us; 4k poses 9.2 vs 8.0 us / 27.8 vs 24.6 us; 8k poses 14.9 vs 8.0 us / 44.1 vs 25.1 us).  The quad form is flat
-// up to 8k poses: there its time is the chain of beam steps, not the work.
-constexpr int kWaveMaxPoses = 3072;
-
 }  // namespace slam

@@ -374,10 +374,7 @@ hipError_t launch_score_any(hipStream_t stream, const ScoreGrid& g, const float*
     if (rode) *rode = false;
     if (nposes <= 0) return hipSuccess;
     MotionIO mio = mio_in;
-    // tuning knobs for measurements (pose counts below which the wave / quad lane mappings are used)
-    static const int wave_max = getenv("SLAM_SCORE_WAVE_MAX") ? atoi(getenv("SLAM_SCORE_WAVE_MAX")) : kWaveMaxPoses;
-    static const int quad_max = getenv("SLAM_SCORE_QUAD_MAX") ? atoi(getenv("SLAM_SCORE_QUAD_MAX")) : kQuadMaxPoses;
-    if (nposes < wave_max) {   // one wavefront per pose
+    if (nposes < kWaveMaxPoses) {   // one wavefront per pose
         const int blocks = (nposes + kScoreBlock / 64 - 1) / (kScoreBlock / 64);
         const size_t lds = sizeof(float) * (size_t)(kScoreBlock / 64) * (size_t)(nbeams > 0 ? nbeams : 1);
         if (ev) (void)hipEventRecord(ev->start, stream);
@@ -390,7 +387,7 @@ hipError_t launch_score_any(hipStream_t stream, const ScoreGrid& g, const float*
         if (ev) (void)hipEventRecord(ev->stop, stream);
         return hipGetLastError();
     }
-    const bool quad = nposes < quad_max;
+    const bool quad = nposes < kQuadMaxPoses;
     const long threads = quad ? 4L * nposes : nposes;
     const int score_blocks = (int)((threads + kScoreBlock - 1) / kScoreBlock);
     int blocks = score_blocks;

@@ -11,7 +11,7 @@
 // Here a particle's row holds its MEANS only (two planes), and the covariance planes exist once per COVARIANCE CLASS:
 //     mean[particle][2][Lp]     two buffers, the update writes the other one (resample gather fused, as with rows)
 //     cls[particle]             the particle's class, handed from ancestor to offspring by the update itself
-//     cov[class][3][Lp]         updated IN PLACE, once per class and frame, by cov_update_kernel — after the particles' update,
+//     cov[class][3][Lp]         updated IN PLACE, once per class and frame, by cov_update_body — after the particles' update,
 //                               which reads the prior
 //     covx[class][2][Lp]        1 / det (P + q I) and 0.5 log det (P + q I) of the same covariances: the two expensive values
 //                               of the update (a reciprocal and a logarithm), worked out by whoever writes cov so that the
@@ -22,7 +22,7 @@
 // part of the specification.  HBM traffic of a dense frame: 8 B read + 8 B written per (particle, landmark) + 24 B per (class
 // in use, landmark), against 20 + 20.
 //
-// This file: the classes' update, the conversions rows <-> split, the gather of a frame without an update.  The particles'
+// This file: the conversions rows <-> split, the gather of a frame without an update.  The particles'
 // update on this layout is ekf_split_body in pf_kernels.hip (it shares the grouped row kernel's machinery).
 
 #include "ekf_math.h"
@@ -34,10 +34,6 @@ namespace slam {
 namespace {
 
 inline int blocks256(int64_t n) { return (int)((n + 255) / 256); }
-
-// ---- the classes' update: workgroup (k, y) takes landmarks [256 y, 256 y + 256) of class live[k] (cov_update_body.h; the frame
-// path carries it in the launch of the weights, this launch serves everybody else)
-__global__ __launch_bounds__(256) void cov_update_kernel(CovArgs a) { cov_update_body(a, (int)blockIdx.x, (int)blockIdx.y); }
 
 // the determinant terms of classes 0 .. *count - 1 from their covariance planes (after a conversion or a reset)
 __global__ __launch_bounds__(256) void cov_terms_kernel(const float* __restrict__ cov, float* __restrict__ covx, int Lp, int nlandmarks,
@@ -255,17 +251,6 @@ __global__ __launch_bounds__(256) void split_reset_kernel(float* __restrict__ me
 }
 
 }  // namespace
-
-hipError_t launch_cov_update(hipStream_t stream, const CovArgs& a, int bound, const EventPair* ev)
-{
-    if (bound <= 0) return hipSuccess;
-    if (ev) (void)hipEventRecord(ev->start, stream);
-    // nlandmarks == 0: a frame without observations — only the list is brought up to date (classes whose last particle went
-    // with the frame's gather leave it: a sharded session may hand their numbers out again, and a number must not be listed twice)
-    cov_update_kernel<<<dim3((unsigned)bound, (unsigned)(a.nlandmarks > 0 ? (a.nlandmarks + 255) / 256 : 1)), 256, 0, stream>>>(a);
-    if (ev) (void)hipEventRecord(ev->stop, stream);
-    return hipGetLastError();
-}
 
 // flags u64[n] | sums u64[n] | scratch of the prefix sum
 size_t split_scratch_words(int n) { return 2 * (2 * (size_t)n + (size_t)prefix_sum_scratch_elems(n)) + 4; }

@@ -257,8 +257,7 @@ int slam_ekf_update_dev(slam_engine *e, const float *d_map_in, float *d_map_out,
  * share their ancestor's row through L2), and one wavefront per 2 or 4 neighbouring particles (the shared row stays in
  * registers).  form = -1 (the initial state): the engine chooses — grouped whenever the update gathers through resample
  * indices, 4 particles per wavefront when its last resample stage reported few distinct ancestors, else 2; 0 forces the
- * first kernel, 1 / 2 the second with 4 / 2 particles per wavefront (tests, measurements; the environment variable
- * SLAM_EKF_GROUP overrides). */
+ * first kernel, 1 / 2 the second with 4 / 2 particles per wavefront (tests, measurements). */
 int slam_ekf_form_set(slam_engine *e, int form);
 /* out-of-place EKF launches of this engine so far: counts[0] one wavefront per particle, counts[1] the grouped kernel
  * (by itself or inside the fused front launch below) */
@@ -267,21 +266,22 @@ int slam_ekf_form_counts(slam_engine *e, int64_t counts[2]);
  * main.c:459-518, for every particle) and the out-of-place landmark update — goes out as ONE launch whose scoring and
  * updating workgroups are dealt out interleaved: the scorer's gathers (texture addresser, L2) run in the shadow of the
  * update's row stores (HBM).  Same bits as the two launches.  on = 1 (the initial state) / 0: two launches (stage timers,
- * measurements; the environment variable SLAM_FRAME_FUSION overrides).  Paged sessions, gated sessions on rows, sharded sessions
+ * measurements).  Paged sessions, gated sessions on rows, sharded sessions
  * on rows, short rows and small populations always take the two launches (a sharded session on the split layout fuses the
  * score with the update of the groups whose ancestors are local), and so does every frame while SLAM_PROF_SCORE is being timed
  * (slam_profile_enable: a fused launch is bracketed as SLAM_PROF_EKF).  slam_frame_fusion_count: fused launches of this engine so far. */
 int slam_frame_fusion_set(slam_engine *e, int on);
 int slam_frame_fusion_count(slam_engine *e, int64_t *launches);
 /* Which instantiation the LAST fused front launch of this engine was (tests pin the kernel at the shapes its numbers are
- * quoted on and say which one they pinned): info[0] = particles per updating wavefront (2 or 4), info[1] = lanes per pose of
- * its scoring workgroups (4 below 131 072 particles, else 1); both 0 before the first fused launch. */
+ * quoted on and say which one they pinned): info[0] = particles per updating wavefront (2 or 4; 2, 4 or 8 on the split
+ * layout), info[1] = lanes per pose of its scoring workgroups (4 below 131 072 particles, else 1); both 0 before the first
+ * fused launch. */
 int slam_frame_front_last(slam_engine *e, int32_t info[2]);
 /* The in-place update (d_map_in == d_map_out: frames that keep their population, slam_resample_gate_set) also has two
  * kernels with the SAME bits: whole rows in batches of 128 landmarks, and the observed landmarks only, from a list
  * the engine compacts out of the observation table once per table (nlandmarks <= 65536).  form = -1 (initial): the
  * second whenever the last list built for this nlandmarks held at most nlandmarks / 4 observations; 0 / 1 force the
- * first / second (tests, measurements; environment variable SLAM_EKF_INPLACE overrides).
+ * first / second (tests, measurements).
  * counts[0] / counts[1]: in-place launches so far of the first / second. */
 int slam_ekf_inplace_form_set(slam_engine *e, int form);
 int slam_ekf_inplace_form_counts(slam_engine *e, int64_t counts[2]);

@@ -53,7 +53,6 @@ line north_star_obs32_paged $Q --scaling strong --particles-total 1048576 --land
 line north_star_obs32_auto $Q --scaling strong --particles-total 1048576 --landmarks 1000 --observed 32 --steps 30
 line ekf_sweep_1m $Q --mode ekf --particles 1048576 --landmarks 1000 --steps 30
 line score_config3 $Q --mode score --particles 1048576 --grid 2048
-SLAM_SCORE_PACKED=0 line score_config3_float_grid $Q --mode score --particles 1048576 --grid 2048
 line config4_share $Q --particles 1048576 --landmarks 0
 line config5_share $Q --particles 524288 --landmarks 5000 --steps 20
 line config5_share_rows $Q --particles 524288 --landmarks 5000 --steps 20 --map-layout rows

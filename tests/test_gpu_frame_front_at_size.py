@@ -10,7 +10,7 @@ landmark update and the log-likelihood have no reference counterpart: PARITY UNP
 
 Both layouts that launch it are pinned: rows (20 B per particle and landmark) and split (means per particle, covariances per
 covariance class: csrc/split_kernels.hip), the latter with a few thousand classes so that class hand-over, class rows and the
-classes' own update (cov_update_kernel) are all in the comparison.
+classes' own update (cov_update_body.h, in the launch of the weights) are all in the comparison.
 
 Per frame, on a session with fusion on: the pending gather index, the source poses and — for >= 4 096 sampled slots —
 the ancestor's map row are read from slam_pf_device_view BEFORE the step; after it

@@ -10,11 +10,6 @@ numbers up to 1e4, ~1e10 m^2 priors in the same wavefronts as ordinary ones (the
 reciprocal), poses and landmarks up to 1e3 m away, headings up to 1e3 rad, first sightings, observation lists that are
 empty, single, complete and out of order.
 """
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 import torch
@@ -24,7 +19,6 @@ from __graft_entry__ import load_package
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-ROOT = Path(__file__).resolve().parents[1]
 
 
 @pytest.fixture(scope="module")
@@ -248,14 +242,8 @@ def test_session_frames_64k_x_500(layout, fusion):
     _session_frames(layout, 65536, 500, 1e-2, fusion=fusion, frames=3)
 
 
-def test_split_g_outside_2_4_8_is_ignored():
-    """SLAM_SPLIT_G = 3 once sized the grid for 3 particles per wavefront and launched the kernel for 2, so a third of
-    the particles were never updated.  Values outside {2, 4, 8} are ignored: every slot is updated."""
-    env = dict(os.environ, SLAM_SPLIT_G="3")
-    code = ("import sys; sys.path[:0] = [sys.argv[1], sys.argv[1] + '/tests']\n"
-            "import test_gpu_pf_f64 as T\n"
-            "T._session_frames('split', 4097, 257, 1e-2, fusion=False, frames=2)\n"
-            "T._session_frames('split', 65536, 200, 1e-2, fusion=True, frames=2)\n"
-            "print('SPLIT_G OK')\n")
-    p = subprocess.run([sys.executable, "-c", code, str(ROOT)], env=env, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0 and "SPLIT_G OK" in p.stdout, p.stdout[-3000:] + p.stderr[-3000:]
+def test_split_session_frames_more_shapes():
+    """Split-layout shapes outside the lists above: a population that is not a multiple of any group size, two launches;
+    65 536 x 200, the fused front launch."""
+    _session_frames("split", 4097, 257, 1e-2, fusion=False, frames=2)
+    _session_frames("split", 65536, 200, 1e-2, fusion=True, frames=2)
