@@ -876,18 +876,13 @@ int slam_obs_set_dev(slam_engine* e, const float* d_zx_by_landmark, const float*
     return SLAM_OK;
 }
 
-int slam_ekf_update_dev(slam_engine* e, const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride,
-                        int nlandmarks, const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc,
-                        int n, float meas_var, float* d_loglik)
+// What every landmark-update stage puts into an EkfArgs alike: the caller's maps, strides, poses and gather index, the engine's
+// observation table and its log-likelihood buffer (what slam_logweight_ekf_dev will consume; ll_buf must hold n floats), an
+// optional second copy of the log-likelihoods for the caller.  xcd_chunk belongs to the launchers.
+static EkfArgs ekf_args(slam_engine* e, const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride, int nlandmarks,
+                        const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc, int n, float meas_var,
+                        float* d_loglik_user)
 {
-    ENTER(e);
-    if (n < 0 || nlandmarks < 0 || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
-        !(meas_var > 0.0f) || (n > 0 && (!d_map_in || !d_map_out || !d_x || !d_y || !d_th)))
-        return SLAM_ERR_INVALID_ARG;
-    if (d_anc && d_map_in == d_map_out) return SLAM_ERR_INVALID_ARG;
-    if (e->obs_nlandmarks < 0 || e->obs_nlandmarks != nlandmarks) return SLAM_ERR_NOT_READY;
-    if (n == 0) return SLAM_OK;
-    HIP_TRY(e->ll_buf.ensure(sizeof(float) * (size_t)n));
     EkfArgs a;
     a.map_in = d_map_in;
     a.map_out = d_map_out;
@@ -902,8 +897,39 @@ int slam_ekf_update_dev(slam_engine* e, const float* d_map_in, float* d_map_out,
     a.obs_zx = e->d_obs_zx;
     a.obs_zy = e->d_obs_zy;
     a.meas_var = meas_var;
-    a.loglik = e->ll_buf.as<float>();   // what slam_logweight_ekf_dev will consume
-    a.loglik_user = d_loglik;
+    a.loglik = e->ll_buf.as<float>();
+    a.loglik_user = d_loglik_user;
+    a.xcd_chunk = 0;
+    return a;
+}
+
+// the split layout's part (SplitIO::map_anc is the caller's business: only the fused front gathers poses and maps differently)
+static void apply_split(EkfArgs& a, const SplitIO& s)
+{
+    a.group_filter = s.group_filter;
+    a.cov = s.cov;
+    a.cov_stride = s.cov_stride;
+    a.covx = s.covx;
+    a.covx_stride = s.covx_stride;
+    a.cls_in = s.cls_in;
+    a.cls_out = s.cls_out;
+    a.cstamp = s.cstamp;
+    a.stamp_now = s.stamp_now;
+}
+
+int slam_ekf_update_dev(slam_engine* e, const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride,
+                        int nlandmarks, const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc,
+                        int n, float meas_var, float* d_loglik)
+{
+    ENTER(e);
+    if (n < 0 || nlandmarks < 0 || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
+        !(meas_var > 0.0f) || (n > 0 && (!d_map_in || !d_map_out || !d_x || !d_y || !d_th)))
+        return SLAM_ERR_INVALID_ARG;
+    if (d_anc && d_map_in == d_map_out) return SLAM_ERR_INVALID_ARG;
+    if (e->obs_nlandmarks < 0 || e->obs_nlandmarks != nlandmarks) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    HIP_TRY(e->ll_buf.ensure(sizeof(float) * (size_t)n));
+    const EkfArgs a = ekf_args(e, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, meas_var, d_loglik);
     if (d_map_in == d_map_out) {
         // in place: whole rows, or — when the last list that was built had few observations — the observed landmarks only
         const bool can_list = nlandmarks <= kObsListMaxLandmarks;
@@ -966,34 +992,10 @@ int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src_x, const f
     const int group = e->ekf_group_size(n, true, plane_stride, true, split != nullptr);
     if (!frame_front_fits(n, nlandmarks, group)) return SLAM_OK;
     HIP_TRY(e->ll_buf.ensure(sizeof(float) * (size_t)n));
-    EkfArgs a;
-    a.map_in = d_map_in;
-    a.map_out = d_map_out;
-    a.row_stride = row_stride;
-    a.plane_stride = plane_stride;
-    a.nlandmarks = nlandmarks;
-    a.x = d_x;   // not read by the fused launch: the update works out its motion samples itself
-    a.y = d_y;
-    a.th = d_th;
-    a.anc = split && split->map_anc ? split->map_anc : d_anc;
-    a.n = n;
-    a.obs_zx = e->d_obs_zx;
-    a.obs_zy = e->d_obs_zy;
-    a.meas_var = meas_var;
-    a.loglik = e->ll_buf.as<float>();
-    a.loglik_user = nullptr;
-    a.xcd_chunk = 0;
-    if (split) {
-        a.group_filter = split->group_filter;
-        a.cov = split->cov;
-        a.cov_stride = split->cov_stride;
-        a.covx = split->covx;
-        a.covx_stride = split->covx_stride;
-        a.cls_in = split->cls_in;
-        a.cls_out = split->cls_out;
-        a.cstamp = split->cstamp;
-        a.stamp_now = split->stamp_now;
-    }
+    // (a.x / a.y / a.th are not read by the fused launch: the update works out its motion samples itself)
+    EkfArgs a = ekf_args(e, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th,
+                         split && split->map_anc ? split->map_anc : d_anc, n, meas_var, nullptr);
+    if (split) apply_split(a, *split);
     MotionIO io{ d_src_x, d_src_y, d_src_th, d_anc, d_x, d_y, d_th, FreeListRider() };
     int lanes = 0;
     // one bracket for the whole launch: it counts as the frame's landmark update (the dominant stage)
@@ -1022,32 +1024,8 @@ int slam_ekf_split_dev(slam_engine* e, const float* d_mean_in, float* d_mean_out
         return SLAM_ERR_INVALID_ARG;
     if (e->obs_nlandmarks < 0 || e->obs_nlandmarks != nlandmarks) return SLAM_ERR_NOT_READY;
     HIP_TRY(e->ll_buf.ensure(sizeof(float) * (size_t)n));
-    EkfArgs a;
-    a.map_in = d_mean_in;
-    a.map_out = d_mean_out;
-    a.row_stride = row_stride;
-    a.plane_stride = plane_stride;
-    a.nlandmarks = nlandmarks;
-    a.x = d_x;
-    a.y = d_y;
-    a.th = d_th;
-    a.anc = d_anc;
-    a.n = n;
-    a.obs_zx = e->d_obs_zx;
-    a.obs_zy = e->d_obs_zy;
-    a.meas_var = meas_var;
-    a.loglik = e->ll_buf.as<float>();
-    a.loglik_user = nullptr;
-    a.xcd_chunk = 0;
-    a.group_filter = split->group_filter;
-    a.cov = split->cov;
-    a.cov_stride = split->cov_stride;
-    a.covx = split->covx;
-    a.covx_stride = split->covx_stride;
-    a.cls_in = split->cls_in;
-    a.cls_out = split->cls_out;
-    a.cstamp = split->cstamp;
-    a.stamp_now = split->stamp_now;
+    EkfArgs a = ekf_args(e, d_mean_in, d_mean_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, meas_var, nullptr);
+    apply_split(a, *split);
     // the tail of a sharded fused frame (group_filter 2) must group the particles as the front launch did
     const int group = split->group_filter == 2 ? e->front_last[0] : e->ekf_group_size(n, d_anc != nullptr, plane_stride, false, true);
     HIP_TRY(launch_ekf_update(e->stream, a, e->prof_next(split->group_filter == 2 ? SLAM_PROF_EKF_TAIL : SLAM_PROF_EKF), group));

@@ -1,4 +1,5 @@
-// kernels.h — launchers of the gfx950 kernels, called by the C-ABI layer (engine.hip).
+// kernels.h — launchers of the gfx950 kernels, one section per kernel file in the Makefile's order; called by the C-ABI layer
+// (engine.hip), the particle-filter session (pf_session.hip) and the mapper (mapper.hip).
 // Every launcher enqueues on `stream` and returns the hipError_t of the launch; none synchronises.
 #pragma once
 
@@ -96,25 +97,12 @@ hipError_t launch_lattice_pair(hipStream_t stream, const ScoreGrid& g1, const Sc
                                const int32_t* d_nbeams, const float* cand1, const float* pair_in, float* work1, float* work2, float* out1,
                                float* out2, float* persist, float* host_out1, float* host_out2, uint32_t* host_flag, uint32_t seq);
 
-// ---- mapper_kernels.hip (SURVEY §8f rows N1/N2; reference: main.c:71-198, 271-354, 941-953)
-hipError_t launch_clean_scan(hipStream_t s, const float* range, const float* cos_tab, const float* sin_tab, int nbeams,
-                             float range_min, float usable, float* bx, float* by, int32_t* nscan);
-hipError_t launch_transform(hipStream_t s, const float* bx, const float* by, const int32_t* nscan, float px, float py,
-                            float ct, float st, float* tx, float* ty);
-hipError_t launch_crop(hipStream_t s, const float* tx, const float* ty, const int32_t* nscan, float border,
-                       const float* mx, const float* my, const int32_t* msize, int local_cap, float* lx, float* ly,
-                       int32_t* lsize);
-hipError_t launch_rasterise(hipStream_t s, const float* lx, const float* ly, const int32_t* lsize, float pixel, int ld,
-                            int32_t* grid, slam_grid_meta* meta);
-hipError_t launch_map_append(hipStream_t s, const float* hits, int nhits, const float* tx, const float* ty, float* mx,
-                             float* my, int32_t* msize, int map_cap, float threshold);
-
 // ---- edt_kernels.hip (row A6; reference: main.c:223-269, main_accelerated.c:215-283)
 enum { EDT_MAX_RADIUS = 32 };
 hipError_t launch_edt(hipStream_t stream, const int32_t* occ, int ld, int rows, int cols, float cap, float* out,
                       const EventPair* ev = nullptr);
 
-// ---- pf_kernels.hip (rows A9-A12; no reference counterpart)
+// ---- ekf_kernels.hip (rows A9-A10; no reference counterpart): motion sample and landmark update
 hipError_t launch_motion_sample(hipStream_t stream, const float* sx, const float* sy, const float* sth,
                                 const int32_t* anc, float* x, float* y, float* th, int n, int64_t first_id,
                                 const float dp[3], const float sigma[3], uint64_t seed, uint32_t frame);
@@ -171,84 +159,15 @@ struct SplitIO {
 // group_size: 0 = one wavefront per particle; 2 / 4 / 8 = the grouped out-of-place form (that many neighbouring particles
 // per wavefront share their source rows in registers) — a speed choice only, every form gives the same bits
 hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a, const EventPair* ev = nullptr, int group_size = 0);
+bool frame_front_fits(int n, int nlandmarks, int group_size);   // the shapes launch_frame_front takes
 // motion sample + scan-match score AND the grouped out-of-place landmark update in ONE launch (single-GPU frames on rows): the
 // gathers of the scorer run in the shadow of the update's row stores.  `a.x / a.y / a.th` are not read (the update works out
 // its particles' motion samples itself, the same bits the scorer writes to io.x / io.y / io.th).  *launched = false: shapes
 // that this kernel does not take; nothing was issued.
-hipError_t launch_selftest_reciprocal(hipStream_t stream, unsigned long long* out /* [2], zeroed: mismatches, values checked */);
-bool frame_front_fits(int n, int nlandmarks, int group_size);   // the shapes launch_frame_front takes
 hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const float* bx, const float* by, int nbeams,
                               const MotionIO& io, int64_t first_id, const float dp[3], const float sigma[3], uint64_t seed,
                               uint32_t frame, float* score, int32_t* count, const EkfArgs& a, int group_size,
                               const EventPair* ev, bool* launched, int* lanes_per_pose = nullptr);
-
-// ---- split_kernels.hip: the covariance classes of the split layout (see EkfArgs)
-// The posterior covariance of every class that is still in use, in place, once per class: P' = (I - W) P for an observed
-// landmark seen before, q I for a first sighting, the prior without an observation — the values every particle of the class
-// would have written into its own row (ekf_math.h: ekf_shared).  `live`: the classes that were in use after the previous
-// frame, cnt[phase] of them; those that still are (cstamp == stamp_now) are updated and appended to the next list (cnt[(phase
-// + 1) % 3]; cnt[(phase + 2) % 3] is zeroed for the frame after).  bound >= cnt[phase]: the launch's width (the host's stale
-// knowledge is good enough: the list only shrinks).  h_live (mapped host memory): {cnt[phase], epoch}.
-struct CovArgs {
-    float* cov;
-    int64_t cov_stride;
-    float* covx;           // the determinant terms of the NEW covariances go here (EkfArgs::covx)
-    int64_t covx_stride;
-    int plane_stride, nlandmarks;
-    const float *obs_zx, *obs_zy;
-    float meas_var;
-    const int32_t* live_in;
-    int32_t* live_out;
-    int32_t* cnt;          // [3]
-    int phase;
-    const uint32_t* cstamp;
-    uint32_t stamp_now;
-    int32_t* h_live;       // 8-byte word {cnt[phase], epoch} in mapped host memory
-    int32_t* h_mark;       // ... and, written behind a system-scope fence, {mark, epoch}
-    uint32_t epoch;
-    uint32_t mark;         // the host's running count of classes appended to the list so far (sharded sessions: rows received)
-};
-// rows [n][5][plane_stride_in] (row_stride_in floats apart) -> means [n][2][Lp], classes, class rows [..][3][Lp]: neighbouring
-// particles whose three covariance planes are equal bit for bit share a class (classes are numbered 0, 1, .. in particle
-// order; all particles alike -> one class).  scratch: split_scratch_words(n) int32 words.  live[k] = k, cnt[phase] = number
-// of classes (cnt[other] = 0), every class stamped stamp_now; h_live = {classes, epoch}.
-size_t split_scratch_words(int n);
-// covx (written by a second launch, so that it may lie where the rows came from): the determinant terms of every class.
-hipError_t launch_split_from_rows(hipStream_t stream, const float* rows, int64_t row_stride_in, int plane_stride_in, int nlandmarks,
-                                  int n, int Lp, float* mean, float* cov, float* covx, float meas_var, int32_t* cls, int32_t* live,
-                                  int32_t* cnt, int phase, uint32_t* cstamp, uint32_t stamp_now, int32_t* h_live, uint32_t epoch,
-                                  void* scratch);
-// out row k = [means of particle idx[k] (or k) | the covariance planes of its class], nlandmarks columns of each plane
-hipError_t launch_rows_from_split(hipStream_t stream, const float* mean, const float* cov, const int32_t* cls, int Lp,
-                                  const int32_t* idx, int count, float* rows, int64_t row_stride, int plane_stride, int nlandmarks);
-// Sharded sessions on the split layout.  A migrating particle travels as the same record whatever the layouts of the two ranks
-// (pose, then five planes of nlandmarks values): launch_migrate_pack(.., split_cov, split_cls) reads it from the means and the
-// class's covariance row, and this launch puts record p of `in` into staging row n + p of the means, with a class of its own —
-// first_class + p, covariance planes and determinant terms filled in, appended to the list of classes in use (live[*cnt ..)).
-// Class numbers for the arrivals come from a free list on the device: the classes no current particle belongs to, i.e. whose
-// stamp is older than `min_live` — the stamp of the last update whose particles are the current ones.  At most n classes are in
-// use and there are n + staging rows of them, so a list made anew holds at least as many numbers as a rank has staging rows,
-// whatever else it holds: the HOST hands them out (entries [first, first + total) of the list go to this launch) and asks for
-// a new list (launch_class_free_list, in front of the unpack) when the guaranteed part of the old one is used up.
-//   fs: two int32 words on the device, zero before the first launch and zero again behind every launch.
-hipError_t launch_class_free_list(hipStream_t stream, const uint32_t* cstamp, int nclasses, uint32_t min_live, int32_t* freelist,
-                                  int32_t* fs);
-// the arrivals' classes are stamped `stamp` (= min_live: in use until the next update has said which of them have offspring)
-hipError_t launch_migrate_unpack_split(hipStream_t stream, const float* in, int total, int n, float* pose, int64_t pose_ld, float* mean,
-                                       float* cov, float* covx, int32_t* cls, int Lp, int nlandmarks, float meas_var,
-                                       const int32_t* freelist, int first, uint32_t* cstamp, uint32_t stamp, int32_t* live,
-                                       int32_t* cnt);
-// a frame without a landmark update: means and classes follow their particles (out[i] = in[anc[i]])
-hipError_t launch_split_gather(hipStream_t stream, const float* mean_in, float* mean_out, const int32_t* cls_in, int32_t* cls_out,
-                               int Lp, const int32_t* anc, int n, uint32_t* cstamp, uint32_t stamp_now);
-// the classes alone follow their particles (split pages: the means follow through the page tables)
-hipError_t launch_class_gather(hipStream_t stream, const int32_t* cls_in, int32_t* cls_out, const int32_t* anc, int n, uint32_t* cstamp,
-                               uint32_t stamp_now);
-// every particle: all landmarks "not seen yet", one class
-hipError_t launch_split_reset(hipStream_t stream, float* mean, float* cov, float* covx, int32_t* cls, int Lp, int n, int32_t* live,
-                              int32_t* cnt, int phase, uint32_t* cstamp, uint32_t stamp_now, int32_t* h_live, uint32_t epoch);
-
-// carry / prev_resampled (optional): see logweight_kernel — the weights a frame without resample left behind
 // In-place update of the OBSERVED landmarks only (frames that keep their population): the observation table is first
 // compacted into a list in landmark order (ids, measurements, accumulator rounds; count[2] = {nobs, highest round} on the
 // device, {nobs, L} optionally in mapped host memory), then one lane per observation gathers, updates and scatters.
@@ -257,6 +176,11 @@ hipError_t launch_build_obs_list(hipStream_t stream, const float* tzx, const flo
                                  float* zy, int32_t* round, int32_t* count, int32_t* h_count);
 hipError_t launch_ekf_sparse(hipStream_t stream, const EkfArgs& a, const int32_t* id, const float* zx, const float* zy,
                              const int32_t* round, const int32_t* count, const EventPair* ev = nullptr);
+// measurement support: rows of 5 x plane_stride floats copied with the update's access shape (slam_profile_copy_ceiling)
+hipError_t launch_copy_rows(hipStream_t stream, const float* in, float* out, int n, int plane_stride);
+// every float in the fast reciprocal's range, ekf_rcp_core against IEEE division
+hipError_t launch_selftest_reciprocal(hipStream_t stream, unsigned long long* out /* [2], zeroed: mismatches, values checked */);
+
 // ---- paged_kernels.hip: landmark maps as copy-on-write pages of kPageLandmarks landmarks (5 planes x 32 floats = 640 B)
 constexpr int kPageLandmarks = 32;   // 16- and 8-landmark pages measured no faster: profiles/r03_page_sizes.md
 // the compact observation list launch_build_obs_list makes: ids ascending, measurements, accumulator rounds, {nobs, highest round}
@@ -361,26 +285,94 @@ hipError_t launch_migrate_unpack_paged(hipStream_t stream, const float* in, int 
                                        float* pool, int32_t* pt, int nb, int nlandmarks, const int32_t* freelist,
                                        const int32_t* pool_state, uint32_t* stamp, uint32_t live);
 
+// ---- split_kernels.hip: the covariance classes of the split layout (see EkfArgs)
+// The posterior covariance of every class that is still in use, in place, once per class: P' = (I - W) P for an observed
+// landmark seen before, q I for a first sighting, the prior without an observation — the values every particle of the class
+// would have written into its own row (ekf_math.h: ekf_shared).  `live`: the classes that were in use after the previous
+// frame, cnt[phase] of them; those that still are (cstamp == stamp_now) are updated and appended to the next list (cnt[(phase
+// + 1) % 3]; cnt[(phase + 2) % 3] is zeroed for the frame after).  bound >= cnt[phase]: the launch's width (the host's stale
+// knowledge is good enough: the list only shrinks).  h_live (mapped host memory): {cnt[phase], epoch}.
+struct CovArgs {
+    float* cov;
+    int64_t cov_stride;
+    float* covx;           // the determinant terms of the NEW covariances go here (EkfArgs::covx)
+    int64_t covx_stride;
+    int plane_stride, nlandmarks;
+    const float *obs_zx, *obs_zy;
+    float meas_var;
+    const int32_t* live_in;
+    int32_t* live_out;
+    int32_t* cnt;          // [3]
+    int phase;
+    const uint32_t* cstamp;
+    uint32_t stamp_now;
+    int32_t* h_live;       // 8-byte word {cnt[phase], epoch} in mapped host memory
+    int32_t* h_mark;       // ... and, written behind a system-scope fence, {mark, epoch}
+    uint32_t epoch;
+    uint32_t mark;         // the host's running count of classes appended to the list so far (sharded sessions: rows received)
+};
+// rows [n][5][plane_stride_in] (row_stride_in floats apart) -> means [n][2][Lp], classes, class rows [..][3][Lp]: neighbouring
+// particles whose three covariance planes are equal bit for bit share a class (classes are numbered 0, 1, .. in particle
+// order; all particles alike -> one class).  scratch: split_scratch_words(n) int32 words.  live[k] = k, cnt[phase] = number
+// of classes (cnt[other] = 0), every class stamped stamp_now; h_live = {classes, epoch}.
+size_t split_scratch_words(int n);
+// covx (written by a second launch, so that it may lie where the rows came from): the determinant terms of every class.
+hipError_t launch_split_from_rows(hipStream_t stream, const float* rows, int64_t row_stride_in, int plane_stride_in, int nlandmarks,
+                                  int n, int Lp, float* mean, float* cov, float* covx, float meas_var, int32_t* cls, int32_t* live,
+                                  int32_t* cnt, int phase, uint32_t* cstamp, uint32_t stamp_now, int32_t* h_live, uint32_t epoch,
+                                  void* scratch);
+// out row k = [means of particle idx[k] (or k) | the covariance planes of its class], nlandmarks columns of each plane
+hipError_t launch_rows_from_split(hipStream_t stream, const float* mean, const float* cov, const int32_t* cls, int Lp,
+                                  const int32_t* idx, int count, float* rows, int64_t row_stride, int plane_stride, int nlandmarks);
+// Sharded sessions on the split layout.  A migrating particle travels as the same record whatever the layouts of the two ranks
+// (pose, then five planes of nlandmarks values): launch_migrate_pack(.., split_cov, split_cls) reads it from the means and the
+// class's covariance row, and this launch puts record p of `in` into staging row n + p of the means, with a class of its own —
+// first_class + p, covariance planes and determinant terms filled in, appended to the list of classes in use (live[*cnt ..)).
+// Class numbers for the arrivals come from a free list on the device: the classes no current particle belongs to, i.e. whose
+// stamp is older than `min_live` — the stamp of the last update whose particles are the current ones.  At most n classes are in
+// use and there are n + staging rows of them, so a list made anew holds at least as many numbers as a rank has staging rows,
+// whatever else it holds: the HOST hands them out (entries [first, first + total) of the list go to this launch) and asks for
+// a new list (launch_class_free_list, in front of the unpack) when the guaranteed part of the old one is used up.
+//   fs: two int32 words on the device, zero before the first launch and zero again behind every launch.
+hipError_t launch_class_free_list(hipStream_t stream, const uint32_t* cstamp, int nclasses, uint32_t min_live, int32_t* freelist,
+                                  int32_t* fs);
+// the arrivals' classes are stamped `stamp` (= min_live: in use until the next update has said which of them have offspring)
+hipError_t launch_migrate_unpack_split(hipStream_t stream, const float* in, int total, int n, float* pose, int64_t pose_ld, float* mean,
+                                       float* cov, float* covx, int32_t* cls, int Lp, int nlandmarks, float meas_var,
+                                       const int32_t* freelist, int first, uint32_t* cstamp, uint32_t stamp, int32_t* live,
+                                       int32_t* cnt);
+// a frame without a landmark update: means and classes follow their particles (out[i] = in[anc[i]])
+hipError_t launch_split_gather(hipStream_t stream, const float* mean_in, float* mean_out, const int32_t* cls_in, int32_t* cls_out,
+                               int Lp, const int32_t* anc, int n, uint32_t* cstamp, uint32_t stamp_now);
+// the classes alone follow their particles (split pages: the means follow through the page tables)
+hipError_t launch_class_gather(hipStream_t stream, const int32_t* cls_in, int32_t* cls_out, const int32_t* anc, int n, uint32_t* cstamp,
+                               uint32_t stamp_now);
+// every particle: all landmarks "not seen yet", one class
+hipError_t launch_split_reset(hipStream_t stream, float* mean, float* cov, float* covx, int32_t* cls, int Lp, int n, int32_t* live,
+                              int32_t* cnt, int phase, uint32_t* cstamp, uint32_t stamp_now, int32_t* h_live, uint32_t epoch);
+
+// ---- resample_kernels.hip (rows A11-A12; no reference counterpart): weights, resampling on one GPU, results and gathers
+// carry / prev_resampled (optional): see logweight_kernel — the weights a frame without resample left behind
+// cov (optional): the same launch carries the covariance classes' update of cov_bound classes in workgroups of its own — cov_update_body.h;
+// cov->nlandmarks == 0: a frame without observations — only the list is brought up to date (classes whose last particle went
+// with the frame's gather leave it: a sharded session may hand their numbers out again, and a number must not be listed twice)
 hipError_t launch_logweight(hipStream_t stream, const float* score, const float* loglik, float gain, int n,
                             float* logw, float* block_max_scratch, float* d_max, const float* carry = nullptr,
                             const int32_t* prev_resampled = nullptr, const CovArgs* cov = nullptr, int cov_bound = 0);
-// (cov: the same launch carries the covariance classes' update of cov_bound classes in workgroups of its own — cov_update_body.h;
-// cov->nlandmarks == 0: a frame without observations — only the list is brought up to date (classes whose last particle went
-// with the frame's gather leave it: a sharded session may hand their numbers out again, and a number must not be listed twice))
 int logweight_scratch_elems(int n);
 int logweight_scratch_floats();   // size of block_max_scratch: block maxima + two words, zero-initialised once
 hipError_t launch_quantise_weights(hipStream_t stream, const float* logw, const float* d_max, int n, uint64_t* wq,
                                    uint64_t* d_sum);
 
-// The resample gate (ESS-gated resampling; oracle: orc_ess_resample).  frac_q16 = threshold * 65536, 0 = no gate
-// (resample every frame).  Where the verdict goes: a device flag and, optionally, mapped host memory
-// {int32 resampled, uint32 sequence number}.
 // Where a resample stage reports roughly how many distinct ancestors it left: counter = one 8-byte-aligned pair of words
 // (device, zeroed once, left zeroed), h_out = {count, n} in mapped host memory.
 struct HeadsOut {
     unsigned int* counter = nullptr;
     int32_t* h_out = nullptr;
 };
+// The resample gate (ESS-gated resampling; oracle: orc_ess_resample).  frac_q16 = threshold * 65536, 0 = no gate
+// (resample every frame).  Where the verdict goes: a device flag and, optionally, mapped host memory
+// {int32 resampled, uint32 sequence number}.
 // The gate's small device buffer, int32 words: [0] "the last resample stage did resample" (the flag logweight_kernel reads),
 // [1] pad, [2] the ticket of quantise_scan_kernel's shard sums, [3] pad, [4..9] its three 64-bit accumulators (8-byte aligned)
 enum { kGateFlagWord = 0, kGateTicketWord = 2, kGateBufWords = 16 };
@@ -413,7 +405,22 @@ bool ancestors_from_scan_fits(int n);
 hipError_t launch_ancestors_from_scan(hipStream_t stream, const uint64_t* cdf_local, const uint64_t* tile_total, int n,
                                       uint64_t seed, uint32_t frame, int32_t* anc, uint32_t frac_q16 = 0,
                                       const GateOut& gate = GateOut(), const HeadsOut& heads = HeadsOut());
-// multi-GPU resample (see pf_kernels.hip): per-peer slot runs, offsets in the packed exchange buffers
+hipError_t launch_argmax(hipStream_t stream, const float* v, int n, int32_t* idx_out, float* val_out);
+// heaviest particle {logw, global id (int bits), x, y, theta} -> out5 (device) and optionally mapped host memory + seq
+hipError_t launch_best_particle(hipStream_t stream, const float* v, int n, const float* px, const float* py,
+                                const float* pth, int64_t first_id, float* out5, float* h_out5, uint32_t* h_seq,
+                                uint32_t seq);
+// exact fixed-point sums of the population {x, y: 2^-32; sin, cos of (theta - ref): 2^-30} -> out4 (device), optionally
+// mapped host memory + seq; acc[4] / ticket: zero-initialised device scratch the kernel leaves zeroed
+hipError_t launch_pose_sums(hipStream_t stream, const float* x, const float* y, const float* th, const int32_t* idx,
+                            int n, float ref_th, unsigned long long* acc, unsigned int* ticket, long long* out4,
+                            long long* h_out4, uint32_t* h_seq, uint32_t seq);
+hipError_t launch_gather_f32(hipStream_t stream, const float* src, const int32_t* idx, int n, float* dst);
+hipError_t launch_gather_map(hipStream_t stream, const float* in, float* out, int64_t in_row_stride,
+                             int64_t out_row_stride, int in_plane_stride, int out_plane_stride, int nlandmarks,
+                             const int32_t* idx, int n);
+
+// ---- shard_kernels.hip: the resample of a sharded (multi-GPU) session — per-peer slot runs, offsets in the packed exchange buffers
 enum { kMaxRanks = 16 };
 struct MigratePlan {
     int64_t lo[kMaxRanks];       // pack: prefix count at the first particle sent to peer q (send_base); unpack: unused
@@ -434,21 +441,18 @@ hipError_t launch_migrate_pack(hipStream_t stream, const int32_t* scratch, int n
                                const PageGeom& geom = PageGeom());   // pt AND split_cls: split pages (means behind pt in pages of geom)
 hipError_t launch_migrate_unpack(hipStream_t stream, const float* in, const MigratePlan& plan, int n, float* pose,
                                  int64_t pose_ld, float* map, int64_t row_stride, int plane_stride, int nlandmarks);
-hipError_t launch_argmax(hipStream_t stream, const float* v, int n, int32_t* idx_out, float* val_out);
-// heaviest particle {logw, global id (int bits), x, y, theta} -> out5 (device) and optionally mapped host memory + seq
-hipError_t launch_best_particle(hipStream_t stream, const float* v, int n, const float* px, const float* py,
-                                const float* pth, int64_t first_id, float* out5, float* h_out5, uint32_t* h_seq,
-                                uint32_t seq);
-// exact fixed-point sums of the population {x, y: 2^-32; sin, cos of (theta - ref): 2^-30} -> out4 (device), optionally
-// mapped host memory + seq; acc[4] / ticket: zero-initialised device scratch the kernel leaves zeroed
-hipError_t launch_pose_sums(hipStream_t stream, const float* x, const float* y, const float* th, const int32_t* idx,
-                            int n, float ref_th, unsigned long long* acc, unsigned int* ticket, long long* out4,
-                            long long* h_out4, uint32_t* h_seq, uint32_t seq);
-// measurement support: rows of 5 x plane_stride floats copied with the update's access shape (slam_profile_copy_ceiling)
-hipError_t launch_copy_rows(hipStream_t stream, const float* in, float* out, int n, int plane_stride);
-hipError_t launch_gather_f32(hipStream_t stream, const float* src, const int32_t* idx, int n, float* dst);
-hipError_t launch_gather_map(hipStream_t stream, const float* in, float* out, int64_t in_row_stride,
-                             int64_t out_row_stride, int in_plane_stride, int out_plane_stride, int nlandmarks,
-                             const int32_t* idx, int n);
+
+// ---- mapper_kernels.hip (SURVEY §8f rows N1/N2; reference: main.c:71-198, 271-354, 941-953)
+hipError_t launch_clean_scan(hipStream_t s, const float* range, const float* cos_tab, const float* sin_tab, int nbeams,
+                             float range_min, float usable, float* bx, float* by, int32_t* nscan);
+hipError_t launch_transform(hipStream_t s, const float* bx, const float* by, const int32_t* nscan, float px, float py,
+                            float ct, float st, float* tx, float* ty);
+hipError_t launch_crop(hipStream_t s, const float* tx, const float* ty, const int32_t* nscan, float border,
+                       const float* mx, const float* my, const int32_t* msize, int local_cap, float* lx, float* ly,
+                       int32_t* lsize);
+hipError_t launch_rasterise(hipStream_t s, const float* lx, const float* ly, const int32_t* lsize, float pixel, int ld,
+                            int32_t* grid, slam_grid_meta* meta);
+hipError_t launch_map_append(hipStream_t s, const float* hits, int nhits, const float* tx, const float* ty, float* mx,
+                             float* my, int32_t* msize, int map_cap, float threshold);
 
 }  // namespace slam

@@ -1,6 +1,6 @@
 // paged_kernels.hip — landmark maps as copy-on-write PAGES (the K-observed frame).
 //
-// One row per particle (pf_kernels.hip) makes every resampling frame rewrite every row in full, because the fused gather
+// One row per particle (ekf_kernels.hip) makes every resampling frame rewrite every row in full, because the fused gather
 // writes particle j's copy of its ancestor's row into the other buffer: 10 KB per particle at 500 landmarks, whether the
 // frame observed 500 landmarks or 5.  Here a particle's map is a PAGE TABLE: entry b names the page that holds landmarks
 // 32 b ... 32 b + 31 (5 planes x 32 floats = 640 bytes = five 128-byte lines).  Resampling copies page-table rows (4 bytes
@@ -11,7 +11,7 @@
 // pages without this frame's stamp (a compaction: count, offsets, scatter).
 //
 // Arithmetic, its order and the log-likelihood summation order (landmark l adds to accumulator l mod 128 in order of l,
-// then j + (j + 64), then the xor butterfly) are those of ekf_batches in pf_kernels.hip: a paged and a row-per-particle
+// then j + (j + 64), then the xor butterfly) are those of ekf_batches in ekf_kernels.hip: a paged and a row-per-particle
 // session give the same bits (tests/test_gpu_paged.py).
 // No counterpart in the reference (it has no particles or landmarks).
 
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(1024) void page_list_kernel(const float* __restrict
                                                          int32_t* __restrict__ h_touched, ObsListOut ol)
 {
     // ol.id != nullptr (L <= kObsListMaxLandmarks): the same pass also makes the compact observation list of
-    // build_obs_list_kernel (pf_kernels.hip) — ids ascending, measurements, accumulator rounds, {count, highest round}
+    // build_obs_list_kernel (ekf_kernels.hip) — ids ascending, measurements, accumulator rounds, {count, highest round}
     __shared__ unsigned s_bits[kObsListMaxLandmarks / 32];
     __shared__ int s_wave[16], s_wobs[16];
     __shared__ int s_base, s_obase, s_max_round;

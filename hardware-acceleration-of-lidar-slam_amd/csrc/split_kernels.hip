@@ -23,7 +23,7 @@
 // in use, landmark), against 20 + 20.
 //
 // This file: the conversions rows <-> split, the gather of a frame without an update.  The particles'
-// update on this layout is ekf_split_body in pf_kernels.hip (it shares the grouped row kernel's machinery).
+// update on this layout is ekf_split_body in ekf_kernels.hip (it shares the grouped row kernel's machinery).
 
 #include "ekf_math.h"
 #include "cov_update_body.h"

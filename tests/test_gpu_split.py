@@ -1,4 +1,4 @@
-"""The SPLIT layout of the landmark maps (csrc/split_kernels.hip, ekf_split_body in csrc/pf_kernels.hip): means per particle,
+"""The SPLIT layout of the landmark maps (csrc/split_kernels.hip, ekf_split_body in csrc/ekf_kernels.hip): means per particle,
 covariances per covariance class.  The layout is not part of the specification: a split session must give the bits of a row
 session — poses, maps, heaviest particle, frame after frame — whatever the classes look like (one for the whole population;
 one per particle; anything between), for every row length (whole passes, tails, rows shorter than a batch), fused with the
