@@ -3,6 +3,8 @@
 // (slam_pf_create_sharded): the frame is built on the public stage entry points either way, and in the sharded
 // form every exchange step between the ranks is issued from here through comm.h (RCCL over xGMI, or the
 // in-process transport) — nothing but this file sits between the launches.
+// The landmark maps are kept as rows, pages, split (means per particle, covariances per class) or split pages; a
+// SLAM_MAP_AUTO session lives on split and moves its means onto pages and back while it runs (auto_layout).
 // No counterpart in the reference; specification: oracle/slam_oracle_pf.c; the shape
 // "handle created once in main and threaded through" is the reference's (Hadrware_acclereated.cpp:842-845, 284).
 
@@ -20,6 +22,19 @@
 #include "kernels.h"
 
 using namespace slam;
+
+// The 32 words of the engine's mapped result block (slam_pf::h_res as the host sees it, d_hres as the device does)
+enum ResWord {
+    RES_PAYLOAD = 0,      // 0..15: 8 x 8 bytes, what slam_pf_best / slam_pf_mean ask for
+    RES_SEQ = 16,         // the sequence number behind the payload
+    RES_CLS_MARK = 18,    // 18..19 {classes appended as of the last classes' update, its epoch} (cov_update_body.h)
+    RES_SHORT_LIST = 20,  // "a free list came out shorter than its reservation" (paged maps; see free_list_kernel)
+    RES_LIVE = 22,        // 22..23 {classes in use, epoch}
+    RES_OBS = 24,         // 24..28 SLAM_MAP_AUTO's sample {observed, L, seq, votes_pages, votes_rows}, left by
+    RES_OBS_SEQ = 26,     //        page_list_kernel / obs_count_kernel
+    RES_VOTES_PAGES = 27, RES_VOTES_ROWS = 28,
+    RES_PAGE_HINT = 30,   // pages the last frames touched per pass (page_list_kernel)
+};
 
 struct slam_pf {
     slam_engine* e = nullptr;
@@ -52,8 +67,7 @@ struct slam_pf {
     int rows_received = 0;
     // results a host asks for every frame (heaviest particle, posterior mean): written by ONE kernel to mapped host
     // memory behind a sequence number — no device-to-host copies, no stream synchronisation
-    float* h_res = nullptr;         // pinned + mapped: 8 x 8 bytes of payload, the sequence number (word 16), and word 20:
-                                    // "a free list came out shorter than its reservation" (paged maps; see free_list_kernel)
+    float* h_res = nullptr;         // pinned + mapped: the words of ResWord
     float* d_hres = nullptr;        // the same memory as the device sees it
     uint32_t res_seq = 0;
     float* res_dev = nullptr;       // device copy of the payload (what the ranks all-gather)
@@ -97,8 +111,8 @@ struct slam_pf {
     void* split_scratch = nullptr;  // flags, prefix sums of a rows -> split move
     bool gated = false;             // cfg.resample_ess_frac in (0, 1): a frame resamples only when its ESS is low
     int64_t frames_resampled = 0;   // (as far as the host has looked: one frame behind)
-    // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe ({observed, L, seq} in words 24..26 of h_res,
-    // left there by page_list_kernel / obs_count_kernel) and moves between rows and pages while it runs
+    // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe (RES_OBS) and moves between split and
+    // split pages while it runs (between rows and pages when it could not have the split layout's tables)
     int layout_cfg = SLAM_MAP_AUTO;
     uint32_t obs_seq_issued = 0, obs_seq_seen = 0;
     int votes_pages = 0, votes_rows = 0;
@@ -108,7 +122,7 @@ struct slam_pf {
     bool last_ekf = false;          // the last frame ran the landmark update (its log-likelihoods are in the engine)
     int32_t* sel = nullptr;         // grow-only scratch of slam_pf_get_map_rows_host: chosen particles | their source rows
     int sel_cap = 0;
-    float* conv_tmp = nullptr;      // grow-only scratch of a pages -> rows move (convert_to_rows)
+    float* conv_tmp = nullptr;      // grow-only scratch of a move off pages (convert_to_rows, convert_split_pages_to_split)
     size_t conv_floats = 0;
 };
 
@@ -116,23 +130,56 @@ namespace {
 
 hipError_t dev_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes ? bytes : 4); }
 
-int convert_rows_to_split(slam_pf* pf);
+// a word of the mapped result block as the host / the device sees it
+int32_t* host_word(const slam_pf* pf, ResWord w) { return reinterpret_cast<int32_t*>(pf->h_res) + w; }
+int32_t* dev_word(const slam_pf* pf, ResWord w) { return reinterpret_cast<int32_t*>(pf->d_hres) + w; }
+
+int wait_stream(slam_pf* pf)
+{
+    if (pf->comm) return comm_wait_stream(pf->comm);
+    SLAM_HIP_TRY(pf->e, hipStreamSynchronize(pf->e->stream));
+    return SLAM_OK;
+}
+
+// Grow-only device scratch: *buf is replaced by one of `bytes` bytes.  Work in flight may still read the old one, so the stream
+// is drained first (`drain_always`: also when there is none).  Memory not to be had: SLAM_OK with *buf == nullptr, the caller decides.
+int replace_scratch(slam_pf* pf, void** buf, size_t bytes, bool drain_always)
+{
+    if (*buf || drain_always)
+        if (int rc = wait_stream(pf)) return rc;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    if (hipMalloc(buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *buf = nullptr;
+    }
+    return SLAM_OK;
+}
 
 int grow(slam_pf* pf, float** buf, size_t* have, size_t want)
 {
     if (want <= *have) return SLAM_OK;
-    slam_engine* e = pf->e;
-    if (pf->comm) {   // an exchange still in flight may read the old buffer
-        if (int rc = comm_wait_stream(pf->comm)) return rc;
-    } else {
-        SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
-    }
     const size_t cap = want > 2 * *have ? want + want / 2 : 2 * *have;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    SLAM_HIP_TRY(e, hipMalloc((void**)buf, cap * sizeof(float)));
-    *have = cap;
+    if (int rc = replace_scratch(pf, (void**)buf, cap * sizeof(float), true)) return rc;
+    *have = *buf ? cap : 0;
+    return *buf ? SLAM_OK : slam_engine_fail_hip(pf->e, hipErrorOutOfMemory, "exchange buffer");
+}
+
+// the scratch rows of a move off pages; not to be had: the session stays where it is (auto_stuck, no error)
+int conversion_scratch(slam_pf* pf, size_t floats)
+{
+    if (pf->conv_floats >= floats) return SLAM_OK;   // (an alloc + free per move would serialise the frame every time)
+    if (int rc = replace_scratch(pf, (void**)&pf->conv_tmp, floats * 4, false)) return rc;
+    pf->conv_floats = pf->conv_tmp ? floats : 0;
+    if (!pf->conv_tmp) pf->auto_stuck = true;
+    return SLAM_OK;
+}
+
+// a new free list when the old one runs short (decided on the device; the pages in use carry the last stamp)
+int issue_free_list(slam_pf* pf)
+{
+    SLAM_HIP_TRY(pf->e, launch_free_list(pf->e->stream, pf->stamp, pf->npages, pf->stamp_now, pf->freelist, pf->page_scratch,
+                                         dev_word(pf, RES_SHORT_LIST)));
     return SLAM_OK;
 }
 
@@ -189,12 +236,10 @@ int migrate(slam_pf* pf)
             pf->cls_cursor = 0;
         }
         if (spages) {   // the means onto fresh pages (a new free list first if the old one runs short), table rows n .. n + rtot - 1
-            int32_t* pstate = pf->page_scratch;
-            SLAM_HIP_TRY(e, launch_pool_reserve(e->stream, pstate, rtot * pf->nb));
-            SLAM_HIP_TRY(e, launch_free_list(e->stream, pf->stamp, pf->npages, pf->stamp_now, pf->freelist, pstate,
-                                             reinterpret_cast<int32_t*>(pf->d_hres) + 20));
+            SLAM_HIP_TRY(e, launch_pool_reserve(e->stream, pf->page_scratch, rtot * pf->nb));
+            if (int rc = issue_free_list(pf)) return rc;
             SLAM_HIP_TRY(e, launch_migrate_unpack_split_pages(e->stream, pf->rbuf, (int)rtot, n, pf->pose_stage, pf->cap, split_pool(pf), geom,
-                                                              pf->pt[pf->pt_cur], pf->nb, L, pf->freelist, pstate, pf->stamp, pf->stamp_now,
+                                                              pf->pt[pf->pt_cur], pf->nb, L, pf->freelist, pf->page_scratch, pf->stamp, pf->stamp_now,
                                                               pf->cov, pf->covx, pf->cls[pf->sp_cur], pf->Lp, pf->cfg.meas_var, pf->cls_free,
                                                               (int)pf->cls_cursor, pf->cstamp, pf->cstamp_now, pf->live[pf->live_cur],
                                                               pf->cov_cnt + pf->cov_phase));
@@ -207,13 +252,11 @@ int migrate(slam_pf* pf)
         pf->cls_appended += (uint32_t)rtot;
     } else if (rtot && pf->paged) {
         // fresh pages for the received rows (a new free list first if the old one runs short), table rows n .. n + rtot - 1
-        int32_t* pstate = pf->page_scratch;
         const ProfScope prof(e, SLAM_PROF_UNPACK);
-        SLAM_HIP_TRY(e, launch_pool_reserve(e->stream, pstate, rtot * pf->nb));
-        SLAM_HIP_TRY(e, launch_free_list(e->stream, pf->stamp, pf->npages, pf->stamp_now, pf->freelist, pstate,
-                                         reinterpret_cast<int32_t*>(pf->d_hres) + 20));
+        SLAM_HIP_TRY(e, launch_pool_reserve(e->stream, pf->page_scratch, rtot * pf->nb));
+        if (int rc = issue_free_list(pf)) return rc;
         SLAM_HIP_TRY(e, launch_migrate_unpack_paged(e->stream, pf->rbuf, (int)rtot, n, pf->pose_stage, pf->cap, pf->pool,
-                                                    pf->pt[pf->pt_cur], pf->nb, L, pf->freelist, pstate, pf->stamp,
+                                                    pf->pt[pf->pt_cur], pf->nb, L, pf->freelist, pf->page_scratch, pf->stamp,
                                                     pf->stamp_now));
     } else if (rtot) {
         if (int rc = slam_migrate_unpack_dev(e, pf->rbuf, G, rcnt, n, pf->pose_stage, pf->cap,
@@ -251,14 +294,21 @@ int drop_resample(slam_pf* pf)
     return SLAM_OK;
 }
 
+// bounded spin on a word in mapped host memory; false: it never showed `want`
+bool spin_flag(const volatile uint32_t* flag, uint32_t want)
+{
+    for (long spin = 0; spin < 400000000L; ++spin)
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == want) return true;
+    return false;
+}
+
 // wait for a result kernel's sequence number in mapped host memory (bounded spin, then let the runtime tell us)
 int wait_result(slam_pf* pf, uint32_t seq)
 {
     slam_engine* e = pf->e;
-    volatile uint32_t* h_seq = reinterpret_cast<volatile uint32_t*>(pf->h_res + 16);
+    const volatile uint32_t* h_seq = reinterpret_cast<const volatile uint32_t*>(host_word(pf, RES_SEQ));
     if (pf->comm) return comm_wait_flag(pf->comm, h_seq, seq);
-    for (long spin = 0; spin < 400000000L; ++spin)
-        if (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) == seq) return SLAM_OK;
+    if (spin_flag(h_seq, seq)) return SLAM_OK;
     SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
     if (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != seq) return slam_engine_fail_hip(e, hipErrorUnknown, "result flag");
     return SLAM_OK;
@@ -272,8 +322,7 @@ int gathered_copy_out(slam_pf* pf, const float* d_src, const int32_t* idx, float
         if (rc != SLAM_OK) return rc;
         d_src = d_tmp;
     }
-    int rc = slam_engine_sync(pf->e);
-    if (rc != SLAM_OK) return rc;
+    if (int rc = slam_engine_sync(pf->e)) return rc;
     return hipMemcpy(h_dst, d_src, sizeof(float) * (size_t)pf->n, hipMemcpyDeviceToHost) == hipSuccess ? SLAM_OK
                                                                                                       : SLAM_ERR_HIP;
 }
@@ -353,25 +402,8 @@ int convert_to_rows(slam_pf* pf)
     slam_engine* e = pf->e;
     const int nrows = rows_to_convert(pf);
     const size_t used = 5 * (size_t)pf->Lp * (size_t)nrows;
-    if (pf->conv_floats < used) {   // grow-only scratch (an alloc + free per move would serialise the frame every time)
-        if (pf->conv_tmp) {
-            if (pf->comm) {
-                if (int rc = comm_wait_stream(pf->comm)) return rc;
-            } else {
-                SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
-            }
-            (void)hipFree(pf->conv_tmp);
-        }
-        pf->conv_tmp = nullptr;
-        pf->conv_floats = 0;
-        if (hipMalloc((void**)&pf->conv_tmp, used * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            pf->conv_tmp = nullptr;
-            pf->auto_stuck = true;
-            return SLAM_OK;
-        }
-        pf->conv_floats = used;
-    }
+    if (int rc = conversion_scratch(pf, used)) return rc;
+    if (!pf->conv_tmp) return SLAM_OK;
     // stream-ordered: pages -> scratch rows -> the first half of the store (the scratch is read before anything else writes it)
     SLAM_HIP_TRY(e, launch_rows_from_pages(e->stream, pf->pool, pf->pt[pf->pt_cur], pf->nb, nullptr, nrows, pf->conv_tmp,
                                            5 * (int64_t)pf->Lp, pf->Lp, pf->L));
@@ -421,8 +453,6 @@ void place_split(slam_pf* pf, int base)
     pf->covx = pf->mean[1] + 2 * unit;
 }
 
-int32_t* split_h_live(slam_pf* pf) { return reinterpret_cast<int32_t*>(pf->d_hres) + 22; }   // {classes in use, epoch}
-
 // ---- SPLIT PAGES (paged && split): the means on copy-on-write pages of two planes (256 bytes), the covariances per class as
 // on the split layout.  The pages live in the session's two mean buffers (2 x cap x nb pages, exactly their size), which are
 // not neighbours in the store: pages below cap x nb in the buffer at the lower address, the others in the other one.
@@ -436,7 +466,6 @@ PageGeom split_geom(const slam_pf* pf)
     g.gap = (hi - lo) - g.half_pages * 2 * kPageLandmarks;
     return g;
 }
-bool split_pages(const slam_pf* pf) { return pf->paged && pf->split; }
 
 // a new set of classes is about to be made (set_map, reset, rows -> split): lists and counters start afresh
 void split_new_epoch(slam_pf* pf)
@@ -456,7 +485,7 @@ int split_from_rows(slam_pf* pf, const float* d_rows, int64_t row_stride, int pl
     split_new_epoch(pf);
     SLAM_HIP_TRY(e, launch_split_from_rows(e->stream, d_rows, row_stride, plane_stride, pf->L, nrows, pf->Lp, pf->mean[pf->sp_cur], pf->cov,
                                            pf->covx, pf->cfg.meas_var, pf->cls[pf->sp_cur], pf->live[0], pf->cov_cnt, 0, pf->cstamp,
-                                           pf->cstamp_now, split_h_live(pf), pf->cls_epoch, pf->split_scratch));
+                                           pf->cstamp_now, dev_word(pf, RES_LIVE), pf->cls_epoch, pf->split_scratch));
     return SLAM_OK;
 }
 
@@ -475,7 +504,7 @@ int convert_rows_to_split(slam_pf* pf)
 
 // split -> split pages: the means of the current buffer become pages in the OTHER mean buffer (identity tables, shifted),
 // the buffer they came from becomes free pages; classes and covariances stay where they are.  One stream-ordered launch.
-int convert_split_to_split_pages(slam_pf* pf)
+int split_means_to_pages(slam_pf* pf)
 {
     slam_engine* e = pf->e;
     const float* src = pf->mean[pf->sp_cur];
@@ -486,6 +515,12 @@ int convert_split_to_split_pages(slam_pf* pf)
     SLAM_HIP_TRY(e, launch_pages_from_rows(e->stream, src, 2 * (int64_t)pf->Lp, pf->Lp, pf->L, pf->nb, rows_to_convert(pf), split_pool(pf),
                                            pf->pt[0], pf->freelist, pf->npages, pf->page_scratch, page_base, split_geom(pf)));
     pf->paged = true;
+    return SLAM_OK;
+}
+
+int convert_split_to_split_pages(slam_pf* pf)
+{
+    if (int rc = split_means_to_pages(pf)) return rc;
     pf->conversions++;
     return SLAM_OK;
 }
@@ -497,25 +532,8 @@ int convert_split_pages_to_split(slam_pf* pf)
     slam_engine* e = pf->e;
     const int nrows = rows_to_convert(pf);
     const size_t used = 2 * (size_t)pf->Lp * (size_t)nrows;
-    if (pf->conv_floats < used) {
-        if (pf->conv_tmp) {
-            if (pf->comm) {
-                if (int rc = comm_wait_stream(pf->comm)) return rc;
-            } else {
-                SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
-            }
-            (void)hipFree(pf->conv_tmp);
-        }
-        pf->conv_tmp = nullptr;
-        pf->conv_floats = 0;
-        if (hipMalloc((void**)&pf->conv_tmp, used * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            pf->conv_tmp = nullptr;
-            pf->auto_stuck = true;
-            return SLAM_OK;
-        }
-        pf->conv_floats = used;
-    }
+    if (int rc = conversion_scratch(pf, used)) return rc;
+    if (!pf->conv_tmp) return SLAM_OK;
     SLAM_HIP_TRY(e, launch_rows_from_pages(e->stream, split_pool(pf), pf->pt[pf->pt_cur], pf->nb, nullptr, nrows, pf->conv_tmp,
                                            2 * (int64_t)pf->Lp, pf->Lp, pf->L, split_geom(pf)));
     SLAM_HIP_TRY(e, hipMemcpyAsync(pf->mean[0], pf->conv_tmp, used * 4, hipMemcpyDeviceToDevice, e->stream));
@@ -533,23 +551,21 @@ int convert_split_pages_to_split(slam_pf* pf)
 int auto_layout(slam_pf* pf)
 {
     if (pf->layout_cfg != SLAM_MAP_AUTO || pf->L == 0 || pf->auto_stuck) return SLAM_OK;
-    const int32_t* h = reinterpret_cast<const int32_t*>(pf->h_res) + 24;   // {observed, L, seq, votes_pages, votes_rows}
-    const volatile uint32_t* h_seq = reinterpret_cast<const volatile uint32_t*>(h) + 2;
+    const volatile uint32_t* h_seq = reinterpret_cast<const volatile uint32_t*>(host_word(pf, RES_OBS_SEQ));
     // The first frames of a session WAIT for the sample of the frame before (it is taken early in that frame: the wait is
     // about one motion + score launch), so that a session settles on its layout within its first four frames however far
     // the host runs ahead of the device; later looks never wait.
     if (pf->frame <= 3 && pf->obs_seq_issued != pf->obs_seq_seen) {
         if (pf->comm) {
             if (int rc = comm_wait_flag(pf->comm, h_seq, pf->obs_seq_issued)) return rc;
-        } else {
-            for (long spin = 0; spin < 400000000L && __atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != pf->obs_seq_issued; ++spin) {}
-        }
+        } else
+            (void)spin_flag(h_seq, pf->obs_seq_issued);   // (never showed up: this look finds nothing new, that is all)
     }
     const uint32_t seq = __atomic_load_n(h_seq, __ATOMIC_ACQUIRE);
     if (seq == pf->obs_seq_seen) return SLAM_OK;
     pf->obs_seq_seen = seq;
-    pf->votes_pages = h[3];   // samples in a row (counted on the device, so none is missed however far the host runs ahead)
-    pf->votes_rows = h[4];
+    pf->votes_pages = *host_word(pf, RES_VOTES_PAGES);   // samples in a row (counted on the device, so none is missed however far the host runs ahead)
+    pf->votes_rows = *host_word(pf, RES_VOTES_ROWS);
     if (!pf->paged && pf->votes_pages >= 3) {
         if (pf->split) return convert_split_to_split_pages(pf);   // the means go onto pages, the classes stay
         return convert_to_pages(pf);
@@ -680,6 +696,575 @@ int create_common(slam_engine* e, const slam_pf_config* cfg, slam_comm* comm, in
     return SLAM_OK;
 }
 
+// ---- one frame (pf_step_impl): the arguments its launches take, then its stages in the order they are issued
+// The classes' update of a frame (cov_update_body.h), in place, once per class still in use; nlandmarks = 0: only the list of
+// classes in use is brought up to date (a frame without observations).  The launch is as wide as the host knows the list to
+// be at most: its length as of some earlier launch (mapped memory, read without waiting) plus the classes that arrived since
+// (sharded sessions) — the second word is the running count of arrivals as of that launch; it is read FIRST and written
+// last, so a torn pair only over-estimates; before anything of this epoch has arrived: every class there can be.
+// Gives the arguments and the width, and moves the bookkeeping on as if it had been launched: the weights' launch carries it.
+void split_class_prepare(slam_pf* pf, int nlandmarks, CovArgs& ca, int& bound)
+{
+    const uint64_t hm = __atomic_load_n(reinterpret_cast<const uint64_t*>(host_word(pf, RES_CLS_MARK)), __ATOMIC_ACQUIRE),
+                   hl = __atomic_load_n(reinterpret_cast<const uint64_t*>(host_word(pf, RES_LIVE)), __ATOMIC_ACQUIRE);
+    const bool fresh = (uint32_t)(hl >> 32) == pf->cls_epoch && (uint32_t)hl > 0;
+    const uint32_t mark = (uint32_t)(hm >> 32) == pf->cls_epoch ? (uint32_t)hm : 0u;   // (no launch of this epoch has said yet: 0)
+    const int64_t upper = fresh ? (int64_t)(uint32_t)hl + (int64_t)(pf->cls_appended - mark) : (int64_t)pf->cap;
+    bound = upper < pf->cap ? (int)upper : pf->cap;
+    ca.cov = pf->cov;
+    ca.cov_stride = 3 * (int64_t)pf->Lp;
+    ca.covx = pf->covx;
+    ca.covx_stride = 2 * (int64_t)pf->Lp;
+    ca.plane_stride = pf->Lp;
+    ca.nlandmarks = nlandmarks;
+    ca.obs_zx = pf->e->d_obs_zx;
+    ca.obs_zy = pf->e->d_obs_zy;
+    ca.meas_var = pf->cfg.meas_var;
+    ca.live_in = pf->live[pf->live_cur];
+    ca.live_out = pf->live[1 - pf->live_cur];
+    ca.cnt = pf->cov_cnt;
+    ca.phase = pf->cov_phase;
+    ca.cstamp = pf->cstamp;
+    ca.stamp_now = pf->cstamp_now;
+    ca.h_live = dev_word(pf, RES_LIVE);
+    ca.h_mark = dev_word(pf, RES_CLS_MARK);
+    ca.epoch = pf->cls_epoch;
+    ca.mark = pf->cls_appended;
+    pf->live_cur = 1 - pf->live_cur;
+    pf->cov_phase = (pf->cov_phase + 1) % 3;
+}
+
+// the classes' update of the frame + the weights: ONE launch
+int weights_with_classes(slam_pf* pf, int nlandmarks, bool use_ekf)
+{
+    CovArgs ca;
+    int bound = 0;
+    split_class_prepare(pf, nlandmarks, ca, bound);
+    return slam_logweight_cov_dev(pf->e, pf->score, use_ekf, pf->cfg.score_gain, pf->n, pf->logw, nullptr, &ca, bound);
+}
+
+// the particles' side of a split update: the classes follow their particles through it; it stamps the ones still in use
+SplitIO split_io(const slam_pf* pf, int group_filter, const int32_t* map_anc)
+{
+    SplitIO sio{};
+    sio.group_filter = group_filter;
+    sio.map_anc = map_anc;
+    sio.cov = pf->cov;
+    sio.cov_stride = 3 * (int64_t)pf->Lp;
+    sio.covx = pf->covx;
+    sio.covx_stride = 2 * (int64_t)pf->Lp;
+    sio.cls_in = pf->cls[pf->sp_cur];
+    sio.cls_out = pf->cls[1 - pf->sp_cur];
+    sio.cstamp = pf->cstamp;
+    sio.stamp_now = pf->cstamp_now + 1;
+    return sio;
+}
+
+// What a frame is, decided once behind auto_layout (nothing later changes the layout), and what its stages leave for the next
+struct FrameFacts {
+    bool ekf;          // the host asks for the landmark update ...
+    bool observing;    // ... and the engine holds an observation table for these landmarks
+    bool sample_obs;   // SLAM_MAP_AUTO takes its sample of the number of observed landmarks in this frame
+    const int32_t* anc;   // the pending gather of the last resample (nullptr: none)
+    const float* src;     // poses: current -> next
+    float* dst;
+    int64_t first_id;
+    // page_scratch: the free list's bookkeeping | count | tpage[nb] | tindex[nb] | tmask[nb] | tbase[nb + 1] | the observation list
+    int32_t *count, *tpage, *tindex, *tmask, *tbase;
+    ObsListOut lo;     // the list form of the paged update (one lane per observation) whenever a list can be made
+    // ---- left by the stages
+    bool paged_listed;   // front: the page list is out, the free list rides with the scorer
+    bool fused;          // front: the landmark update went out with the score
+    bool in_place;       // gate: the last frame kept its population, the maps have not moved
+};
+
+FrameFacts frame_facts(const slam_pf* pf, int use_observations)
+{
+    FrameFacts f{};
+    f.ekf = pf->L > 0 && use_observations;
+    f.observing = f.ekf && pf->e->obs_nlandmarks == pf->L;
+    // SLAM_MAP_AUTO samples the number of observed landmarks: every frame at the start and while the counts speak against
+    // the current layout, every 8th frame otherwise
+    f.sample_obs = pf->layout_cfg == SLAM_MAP_AUTO && !pf->auto_stuck && f.observing &&
+                   (pf->frame < 8 || (pf->frame & 7u) == 0 || (pf->paged ? pf->votes_rows : pf->votes_pages) > 0);
+    f.anc = pf->has_anc ? pf->anc[pf->cur] : nullptr;
+    f.src = pf->pose[pf->cur];
+    f.dst = pf->pose[1 - pf->cur];
+    f.first_id = (int64_t)pf->rank * pf->n;
+    f.count = pf->page_scratch + pool_state_words();
+    f.tpage = f.count + 1;
+    f.tindex = f.tpage + pf->nb;
+    f.tmask = f.tindex + pf->nb;
+    f.tbase = f.tmask + pf->nb;
+    int32_t* lst = f.tbase + pf->nb + 1;
+    if (pf->paged && pf->L <= kObsListMaxLandmarks)   // id[Lp] | zx[Lp] | zy[Lp] | round[Lp] | {count, highest round}
+        f.lo = ObsListOut{ lst, reinterpret_cast<float*>(lst + pf->Lp), reinterpret_cast<float*>(lst + 2 * pf->Lp), lst + 3 * pf->Lp,
+                           lst + 4 * pf->Lp };
+    return f;
+}
+
+// the paged update into fresh pages; split pages: mean pages of two planes, the covariances per class
+PagedEkfArgs paged_ekf_args(const slam_pf* pf, const FrameFacts& f)
+{
+    slam_engine* e = pf->e;
+    const size_t sn = (size_t)pf->n;
+    PagedEkfArgs a;
+    a.ol = ObsListView{ f.lo.id, f.lo.zx, f.lo.zy, f.lo.round, f.lo.count };
+    a.tmask = f.tmask;
+    a.tbase = f.tbase;
+    a.pool = pf->pool;
+    if (pf->split) {
+        a.geom = split_geom(pf);
+        a.pool = split_pool(pf);
+        a.cov = pf->cov;
+        a.covx = pf->covx;
+        a.plane_stride = pf->Lp;
+        a.cls_in = pf->cls[pf->sp_cur];
+        a.cls_out = pf->cls[1 - pf->sp_cur];
+        a.cstamp = pf->cstamp;
+        a.cstamp_now = pf->cstamp_now + 1;
+    }
+    a.pt_in = pf->pt[pf->pt_cur];
+    a.pt_out = pf->pt[1 - pf->pt_cur];
+    a.nb = pf->nb;
+    a.anc = f.anc;
+    a.n = pf->n;
+    a.nlandmarks = pf->L;
+    a.x = f.dst;
+    a.y = f.dst + sn;
+    a.th = f.dst + 2 * sn;
+    a.obs_zx = e->d_obs_zx;
+    a.obs_zy = e->d_obs_zy;
+    a.meas_var = pf->cfg.meas_var;
+    a.loglik = e->ll_buf.as<float>();
+    a.loglik_user = nullptr;
+    a.tpage = f.tpage;
+    a.tindex = f.tindex;
+    a.count = f.count;
+    a.freelist = pf->freelist;
+    a.pool_state = pf->page_scratch;
+    a.stamp = pf->stamp;
+    a.stamp_now = pf->stamp_now + 1;   // the stamp of the tables this update writes
+    return a;
+}
+
+// Paged maps: the frame's page list (touched pages, observation list, where the fresh pages come from)
+int issue_page_list(slam_pf* pf, const FrameFacts& f)
+{
+    slam_engine* e = pf->e;
+    const ProfScope prof(e, SLAM_PROF_PAGES);
+    SLAM_HIP_TRY(e, launch_page_list(e->stream, e->d_obs_zx, e->d_obs_zy, pf->L, pf->nb, f.tpage, f.tindex, f.tmask, f.tbase, f.count, pf->n,
+                                     pf->page_scratch, f.sample_obs ? dev_word(pf, RES_OBS) : nullptr, f.sample_obs ? ++pf->obs_seq_issued : 0,
+                                     f.sample_obs ? pf->votes : nullptr, dev_word(pf, RES_PAGE_HINT), f.lo));
+    return SLAM_OK;
+}
+
+// 1 + 2. motion (+ the fused gather of the previous resample) and scan-match score, one launch.  Sharded: the ancestors' poses come
+// out of the array of every rank's poses: it needs nothing from the exchange and keeps the GPU busy while the host picks up the plan.
+int front_stage(slam_pf* pf, FrameFacts& f, int slot, const float dp[3])
+{
+    slam_engine* e = pf->e;
+    slam_comm* comm = pf->comm;
+    const int n = pf->n, cur = pf->cur;
+    const size_t sn = (size_t)n;
+    float* dst = f.dst;
+    // Paged maps on one GPU: the page list goes out first and the free list it may ask for travels in workgroups of the scorer's
+    // launch (free_list_body.h).  A sharded session issues both behind its exchange, which takes pages from the same list first.
+    FreeListRider rider;
+    if (!comm && pf->paged && f.observing) {
+        if (int rc = issue_page_list(pf, f)) return rc;
+        rider = FreeListRider{ pf->stamp, pf->npages, pf->stamp_now, pf->freelist, pf->page_scratch, dev_word(pf, RES_SHORT_LIST) };
+        f.paged_listed = true;
+    }
+    // 1 + 2 + 3 in ONE launch when the frame allows it (landmarks observed, long rows, enough particles): motion + score and the
+    // out-of-place landmark update side by side (slam_frame_front_dev; the same bits).  One GPU, rows or split: a gated session
+    // on rows is left out (its frames that keep their population update in place; on split they go through the identity index).
+    // Sharded, split, ungated: the launch scores every particle (poses out of the all-gathered array) and updates the groups
+    // whose ancestors are all rows of this rank; the groups with an ancestor in the staging tail follow behind the exchange
+    // (update_split).  Like the motion + score launch it replaces, it goes out before the host has looked at the plan.
+    const bool front = comm ? pf->split && !pf->paged && pf->has_anc && !pf->gated : !pf->paged && (!pf->gated || pf->split);
+    if (front && f.anc && f.observing) {
+        const float* ps = f.src;
+        const int32_t* pose_anc = f.anc;
+        if (comm) {
+            if (int rc = comm_all_gather_finish(comm)) return rc;
+            ps = pf->pose_all;
+            pose_anc = pf->pose_idx[cur];
+        }
+        const SplitIO sio = pf->split ? split_io(pf, comm ? 1 : 0, comm ? f.anc : nullptr) : SplitIO{};
+        const float* map_in = pf->split ? pf->mean[pf->sp_cur] : pf->map[pf->map_cur];
+        float* map_out = pf->split ? pf->mean[1 - pf->sp_cur] : pf->map[1 - pf->map_cur];
+        if (int rc = slam_frame_front_dev(e, slot, ps, ps + sn, ps + 2 * sn, pose_anc, dst, dst + sn, dst + 2 * sn, n, f.first_id, dp,
+                                          pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->score, pf->count, map_in, map_out,
+                                          (pf->split ? 2 : 5) * (int64_t)pf->Lp, pf->Lp, pf->L, pf->cfg.meas_var, &f.fused,
+                                          pf->split ? &sio : nullptr))
+            return rc;
+    }
+    if (f.fused) return SLAM_OK;
+    if (comm && pf->has_anc) {
+        if (int rc = comm_all_gather_finish(comm)) return rc;
+        const float* pa = pf->pose_all;
+        return slam_motion_score_dev(e, slot, pa, pa + sn, pa + 2 * sn, pf->pose_idx[cur], dst, dst + sn, dst + 2 * sn, n, f.first_id,
+                                     dp, pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->score, pf->count);
+    }
+    bool rode = false;
+    if (int rc = slam_motion_score_rider_dev(e, slot, f.src, f.src + sn, f.src + 2 * sn, f.anc, dst, dst + sn, dst + 2 * sn, n, f.first_id,
+                                             dp, pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->score, pf->count,
+                                             f.paged_listed ? &rider : nullptr, &rode))
+        return rc;
+    if (f.paged_listed && !rode) {   // (a small population: its scorer has no room for a rider)
+        const ProfScope prof(e, SLAM_PROF_PAGES);
+        return issue_free_list(pf);
+    }
+    return SLAM_OK;
+}
+
+// Resample gate: did the previous frame keep its population?  (Its verdict was made on the device; the host looks at it
+// only now, behind the front launch — a flag in mapped memory.)  Then the maps have not moved: on rows the EKF runs IN PLACE.
+// Sharded: then map rows of remote ancestors -> staging tail; issued behind the front launch, which does not need them.
+int gate_and_exchange(slam_pf* pf, FrameFacts& f, bool* collective_verdict)
+{
+    if (pf->gated && pf->has_anc) {
+        int resampled = 1;
+        if (int rc = slam_resample_happened_host(pf->e, &resampled)) return rc;
+        f.in_place = !resampled;
+        pf->frames_resampled += resampled ? 1 : 0;
+    }
+    if (pf->comm)
+        if (int rc = finish_exchange(pf)) {
+            *collective_verdict = rc == SLAM_ERR_CAPACITY;
+            return rc;
+        }
+    return SLAM_OK;
+}
+
+// 3. per-landmark EKF (+ fused gather) and the weights, one function per storage form.  Rows: in place, out of place, gather only
+int update_rows(slam_pf* pf, const FrameFacts& f)
+{
+    slam_engine* e = pf->e;
+    const int n = pf->n, L = pf->L, mc = pf->map_cur, mn = 1 - mc;
+    const size_t sn = (size_t)n;
+    const int64_t stride = 5 * (int64_t)pf->Lp;
+    float* dst = f.dst;
+    if (f.ekf) {
+        if (f.sample_obs) SLAM_HIP_TRY(e, launch_obs_count(e->stream, e->d_obs_zx, e->d_obs_zy, L, dev_word(pf, RES_OBS), ++pf->obs_seq_issued, pf->votes));
+        if (!f.fused)   // (fused: the update went out with the score; in place: no gather, the buffers do not flip)
+            if (int rc = slam_ekf_update_dev(e, pf->map[mc], pf->map[f.in_place ? mc : mn], stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn,
+                                             f.in_place ? nullptr : f.anc, n, pf->cfg.meas_var, nullptr))
+                return rc;
+        if (!f.in_place) pf->map_cur = mn;
+        return slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
+    }
+    if (L > 0 && f.anc && !f.in_place) {   // the maps follow their particles even without an observation
+        if (int rc = slam_gather_map_dev(e, pf->map[mc], pf->map[mn], stride, stride, pf->Lp, pf->Lp, L, f.anc, n)) return rc;
+        pf->map_cur = mn;
+    }
+    return slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
+}
+
+int update_split(slam_pf* pf, const FrameFacts& f)
+{
+    slam_engine* e = pf->e;
+    const int n = pf->n, L = pf->L, sc = pf->sp_cur;
+    const size_t sn = (size_t)n;
+    float* dst = f.dst;
+    if (f.ekf) {
+        if (!f.observing) return SLAM_ERR_NOT_READY;
+        if (f.sample_obs) SLAM_HIP_TRY(e, launch_obs_count(e->stream, e->d_obs_zx, e->d_obs_zy, L, dev_word(pf, RES_OBS), ++pf->obs_seq_issued, pf->votes));
+        // the particles' update (a frame that kept its population: out of place all the same, through the identity index); behind
+        // a sharded fused front: the groups that waited for the exchange — no rows received: the launch would find nothing to do ...
+        if (!f.fused || (pf->comm && pf->rows_received > 0)) {
+            const SplitIO sio = split_io(pf, f.fused ? 2 : 0, nullptr);
+            if (int rc = slam_ekf_split_dev(e, pf->mean[sc], pf->mean[1 - sc], 2 * (int64_t)pf->Lp, pf->Lp, L, dst, dst + sn, dst + 2 * sn,
+                                            f.anc, n, pf->cfg.meas_var, &sio))
+                return rc;
+        }
+        pf->cstamp_now++;
+        pf->sp_cur = 1 - sc;
+        // ... then the classes' update, in place, once per class still in use
+        return weights_with_classes(pf, L, true);
+    }
+    if (f.anc) {   // means and classes follow their particles
+        const ProfScope prof(e, SLAM_PROF_PAGES);
+        SLAM_HIP_TRY(e, launch_split_gather(e->stream, pf->mean[sc], pf->mean[1 - sc], pf->cls[sc], pf->cls[1 - sc], pf->Lp, f.anc, n,
+                                            pf->cstamp, ++pf->cstamp_now));
+        pf->sp_cur = 1 - sc;
+        return weights_with_classes(pf, 0, false);   // no observations: the list of classes in use only
+    }
+    return slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
+}
+
+// pages and split pages: touched pages of this frame's observation table, the update into fresh pages, the next free list
+int update_paged(slam_pf* pf, const FrameFacts& f)
+{
+    slam_engine* e = pf->e;
+    const int n = pf->n, pc = pf->pt_cur;
+    if (f.ekf) {
+        if (!f.observing) return SLAM_ERR_NOT_READY;
+        SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
+        if (!f.paged_listed) {
+            if (int rc = issue_page_list(pf, f)) return rc;
+            const ProfScope prof(e, SLAM_PROF_PAGES);
+            if (int rc = issue_free_list(pf)) return rc;
+        }
+        const PagedEkfArgs a = paged_ekf_args(pf, f);
+        pf->stamp_now++;
+        // pages staged per pass = what the last frames touched (a hint in mapped memory, read without waiting)
+        SLAM_HIP_TRY(e, launch_ekf_paged(e->stream, a, e->prof_next(SLAM_PROF_EKF), f.lo.id ? 1 : 0,
+                                         __atomic_load_n(host_word(pf, RES_PAGE_HINT), __ATOMIC_RELAXED)));
+        e->ll_n = n;
+        pf->pt_cur = 1 - pc;
+        if (!pf->split) return slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
+        // the classes went with their particles; their covariances, once per class, with the weights
+        pf->cstamp_now++;
+        pf->sp_cur = 1 - pf->sp_cur;
+        return weights_with_classes(pf, pf->L, true);
+    }
+    if (!f.anc) return slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
+    {   // the tables follow their particles ...
+        const ProfScope prof(e, SLAM_PROF_PAGES);
+        SLAM_HIP_TRY(e, launch_page_table_gather(e->stream, pf->pt[pc], pf->pt[1 - pc], pf->nb, f.anc, n, pf->stamp, ++pf->stamp_now));
+        pf->pt_cur = 1 - pc;
+        if (pf->split) {   // ... and so do the classes
+            SLAM_HIP_TRY(e, launch_class_gather(e->stream, pf->cls[pf->sp_cur], pf->cls[1 - pf->sp_cur], f.anc, n, pf->cstamp,
+                                                ++pf->cstamp_now));
+            pf->sp_cur = 1 - pf->sp_cur;
+        }
+    }
+    return pf->split ? weights_with_classes(pf, 0, false)
+                     : slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
+}
+
+// 4. weights: the maximum over all ranks, then fixed-point weights scanned as they are produced
+// Sharded: the ranks all-reduce the BLOCK maxima the weights' launch leaves in the engine (element by element: a few hundred
+// floats cost the wire what one costs) and the scan takes their maximum itself, as it does on one GPU — the maximum of the
+// same set of values, and one single-workgroup launch less per frame than reducing them to one float first.
+int scan_stage(slam_pf* pf)
+{
+    slam_engine* e = pf->e;
+    if (pf->comm) {
+        if (e->bmax_n != pf->n || e->bmax_count <= 0) return SLAM_ERR_NOT_READY;
+        if (int rc = comm_all_reduce_max_f32(pf->comm, e->bmax_buf.as<float>(), e->bmax_count)) return rc;
+    }
+    return slam_quantise_scan_dev(e, pf->logw, nullptr, pf->n, pf->comm ? pf->d_sum : nullptr);
+}
+
+// 5. resample on the integer CDF
+int resample_stage(slam_pf* pf, const float* poses)
+{
+    slam_engine* e = pf->e;
+    slam_comm* comm = pf->comm;
+    const int n = pf->n, nxt = 1 - pf->cur;
+    const size_t sn = (size_t)n;
+    if (!comm) return slam_ancestors_from_scan_dev(e, n, pf->cfg.seed, pf->frame, pf->anc[nxt]);
+    // shard totals (with the gate: total, sum v, sum v^2 per rank)
+    if (int rc = comm_all_gather(comm, pf->d_sum, pf->totals, (pf->gated ? 3 : 1) * sizeof(uint64_t))) return rc;
+    if (int rc = slam_offspring_from_scan_sharded_dev(e, n, pf->totals, pf->rank, pf->world, pf->cfg.seed, pf->frame, pf->n_total,
+                                                      pf->first))
+        return rc;
+    // the "all-gather of surviving indices" (4 B x N_total) and, grouped into the same RCCL launch, this frame's poses
+    // to every rank (12 B x N_total) for the next frame's motion + score — that launch then needs nothing from the exchange
+    if (int rc = comm_all_gather2(comm, pf->first, pf->first_all, sn * sizeof(int32_t), poses, pf->pose_all, 3 * sn * sizeof(float)))
+        return rc;
+    // 6. gather index of every slot (remote ancestors -> rows of the staging tail) and the exchange plan, on the
+    // device; the exchange itself happens at the start of the next frame, behind its motion + score launch
+    if (int rc = slam_ancestors_sharded_dev(e, pf->first_all, pf->n_total, n, pf->rank, pf->world, pf->anc[nxt], pf->d_plan,
+                                            pf->pose_idx[nxt]))
+        return rc;
+    pf->exchange_pending = true;
+    return SLAM_OK;
+}
+
+int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations, bool* collective_verdict)
+{
+    slam_engine* e = pf->e;
+    if (pf->paged && __atomic_load_n(host_word(pf, RES_SHORT_LIST), __ATOMIC_ACQUIRE) != 0) {
+        snprintf(e->err, sizeof e->err, "paged maps: a free list was shorter than the pages reserved from it (pool invariant broken)");
+        return SLAM_ERR_CAPACITY;
+    }
+    if (int rc = auto_layout(pf)) return rc;   // may move the maps to another layout (never changes a result)
+    FrameFacts f = frame_facts(pf, use_observations);
+    if (int rc = front_stage(pf, f, slot, dp)) return rc;
+    if (int rc = gate_and_exchange(pf, f, collective_verdict)) return rc;
+    if (int rc = pf->paged ? update_paged(pf, f) : pf->split ? update_split(pf, f) : update_rows(pf, f)) return rc;
+    if (int rc = scan_stage(pf)) return rc;
+    if (int rc = resample_stage(pf, f.dst)) return rc;
+    pf->cur = 1 - pf->cur;
+    pf->has_anc = true;
+    pf->last_ekf = f.ekf;
+    pf->frame++;
+    return SLAM_OK;
+}
+
+int pf_best(slam_pf* pf, float pose[3], float* logw, int32_t* index)
+{
+    if (!pf || !pose) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    // the log-weights of the last frame belong to pose[cur] BEFORE the pending gather
+    const float* p = pf->pose[pf->cur];
+    const size_t sn = (size_t)pf->n;
+    float r[5];
+    if (!pf->comm) {   // one launch, the result lands in mapped host memory: no copy, no stream synchronisation
+        const uint32_t seq = ++pf->res_seq;
+        SLAM_HIP_TRY(e, launch_best_particle(e->stream, pf->logw, pf->n, p, p + sn, p + 2 * sn, 0, pf->res_dev, pf->d_hres,
+                                             reinterpret_cast<uint32_t*>(dev_word(pf, RES_SEQ)), seq));
+        if (int rc = wait_result(pf, seq)) return rc;
+        memcpy(r, pf->h_res, sizeof r);
+    } else {   // every rank's candidate to every rank; the first maximum = the lowest rank = the lowest id
+        SLAM_HIP_TRY(e, launch_best_particle(e->stream, pf->logw, pf->n, p, p + sn, p + 2 * sn, (int64_t)pf->rank * pf->n,
+                                             pf->res_dev, nullptr, nullptr, 0));
+        if (int rc = comm_all_gather(pf->comm, pf->res_dev, pf->res_all, 5 * sizeof(float))) return rc;
+        std::vector<float> all(5 * (size_t)pf->world);
+        SLAM_HIP_TRY(e, hipMemcpyAsync(all.data(), pf->res_all, all.size() * 4, hipMemcpyDeviceToHost, e->stream));
+        if (int rc = comm_wait_stream(pf->comm)) return rc;
+        int best = 0;
+        for (int q = 1; q < pf->world; ++q)
+            if (all[5 * q] > all[5 * best]) best = q;
+        memcpy(r, &all[5 * best], sizeof r);
+    }
+    int32_t gid;
+    memcpy(&gid, &r[1], 4);
+    for (int k = 0; k < 3; ++k) pose[k] = r[2 + k];
+    if (logw) *logw = r[0];
+    if (index) *index = gid;
+    return SLAM_OK;
+}
+
+int pf_mean(slam_pf* pf, float ref_theta, float pose[3])
+{
+    if (!pf || !pose) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    const size_t sn = (size_t)pf->n;
+    const float *x = pf->pose[pf->cur], *y = x + sn, *th = x + 2 * sn;
+    const int32_t* idx = pf->has_anc ? pf->anc[pf->cur] : nullptr;
+    if (pf->comm && pf->has_anc) {   // the ancestors' poses are in the all-gathered array
+        if (int rc = comm_all_gather_finish(pf->comm)) return rc;
+        x = pf->pose_all;
+        y = x + sn;
+        th = x + 2 * sn;
+        idx = pf->pose_idx[pf->cur];
+    }
+    unsigned int* ticket = reinterpret_cast<unsigned int*>(pf->sums_acc + 4);
+    long long sums[4] = { 0, 0, 0, 0 };
+    if (!pf->comm) {
+        const uint32_t seq = ++pf->res_seq;
+        SLAM_HIP_TRY(e, launch_pose_sums(e->stream, x, y, th, idx, pf->n, ref_theta, pf->sums_acc, ticket,
+                                         reinterpret_cast<long long*>(pf->res_dev), reinterpret_cast<long long*>(pf->d_hres),
+                                         reinterpret_cast<uint32_t*>(dev_word(pf, RES_SEQ)), seq));
+        if (int rc = wait_result(pf, seq)) return rc;
+        memcpy(sums, pf->h_res, sizeof sums);
+    } else {   // integer sums: adding the ranks' shares in any order gives the single-GPU bits
+        SLAM_HIP_TRY(e, launch_pose_sums(e->stream, x, y, th, idx, pf->n, ref_theta, pf->sums_acc, ticket,
+                                         reinterpret_cast<long long*>(pf->res_dev), nullptr, nullptr, 0));
+        if (int rc = comm_all_gather(pf->comm, pf->res_dev, pf->res_all, 4 * sizeof(long long))) return rc;
+        std::vector<long long> all(4 * (size_t)pf->world);
+        SLAM_HIP_TRY(e, hipMemcpyAsync(all.data(), pf->res_all, all.size() * 8, hipMemcpyDeviceToHost, e->stream));
+        if (int rc = comm_wait_stream(pf->comm)) return rc;
+        for (int q = 0; q < pf->world; ++q)
+            for (int k = 0; k < 4; ++k) sums[k] += all[4 * (size_t)q + k];
+    }
+    const double nt = (double)pf->n_total;
+    pose[0] = (float)((double)sums[0] / 4294967296.0 / nt);
+    pose[1] = (float)((double)sums[1] / 4294967296.0 / nt);
+    pose[2] = (float)((double)ref_theta + atan2((double)sums[2], (double)sums[3]));
+    return SLAM_OK;
+}
+
+int pf_get_poses_host(slam_pf* pf, float* x, float* y, float* theta)
+{
+    if (!pf || !x || !y || !theta) return SLAM_ERR_INVALID_ARG;
+    const size_t n = (size_t)pf->n;
+    float* tmp = pf->pose[1 - pf->cur];   // the other buffer is free between frames
+    float* out[3] = { x, y, theta };
+    if (pf->comm && pf->has_anc) {   // the ancestors' poses are in the all-gathered array
+        if (int rc = comm_all_gather_finish(pf->comm)) return rc;
+        for (int k = 0; k < 3; ++k)
+            if (int rc = gathered_copy_out(pf, pf->pose_all + k * n, pf->pose_idx[pf->cur], out[k], tmp)) return rc;
+        return SLAM_OK;
+    }
+    const float* p = pf->pose[pf->cur];
+    for (int k = 0; k < 3; ++k)
+        if (int rc = gathered_copy_out(pf, p + k * n, pf->has_anc ? pf->anc[pf->cur] : nullptr, out[k], tmp)) return rc;
+    return SLAM_OK;
+}
+
+// dense rows [count][5][Lp] of the particles idx[0 .. count) (nullptr: 0 .. count - 1) of a session on pages, split or split pages
+hipError_t rows_of(const slam_pf* pf, const int32_t* idx, int count, float* dense)
+{
+    hipStream_t s = pf->e->stream;
+    const int64_t stride = 5 * (int64_t)pf->Lp;
+    if (pf->paged && pf->split)
+        return launch_rows_from_split_pages(s, split_pool(pf), split_geom(pf), pf->pt[pf->pt_cur], pf->nb, pf->cov, pf->cls[pf->sp_cur],
+                                            pf->Lp, idx, count, dense, stride, pf->Lp, pf->L);
+    if (pf->split) return launch_rows_from_split(s, pf->mean[pf->sp_cur], pf->cov, pf->cls[pf->sp_cur], pf->Lp, idx, count, dense, stride, pf->Lp, pf->L);
+    return launch_rows_from_pages(s, pf->pool, pf->pt[pf->pt_cur], pf->nb, idx, count, dense, stride, pf->Lp, pf->L);
+}
+
+int pf_get_map_host(slam_pf* pf, float* rows)
+{
+    if (!pf || !rows || !pf->L) return SLAM_ERR_INVALID_ARG;
+    const size_t n = (size_t)pf->n, L = (size_t)pf->L, Lp = (size_t)pf->Lp;
+    if (pf->comm)
+        if (int rc = finish_exchange(pf)) return rc;   // collective: remote ancestors' rows into the staging tail
+    const int32_t* idx = pf->has_anc ? pf->anc[pf->cur] : nullptr;   // the pending gather is applied on the way
+    float* dense = nullptr;
+    const float* src = pf->map[pf->map_cur];
+    int rc = SLAM_OK;
+    if (pf->paged || pf->split) {   // -> rows in a scratch buffer
+        if (hipMalloc((void**)&dense, 5 * Lp * n * 4) != hipSuccess) return SLAM_ERR_HIP;
+        if (rows_of(pf, idx, pf->n, dense) != hipSuccess) rc = SLAM_ERR_HIP;
+        src = dense;
+    } else if (idx) {               // -> the spare row buffer
+        rc = slam_gather_map_dev(pf->e, src, pf->map[1 - pf->map_cur], 5 * (int64_t)Lp, 5 * (int64_t)Lp, pf->Lp, pf->Lp, pf->L, idx, pf->n);
+        src = pf->map[1 - pf->map_cur];
+    }
+    if (rc == SLAM_OK) rc = slam_engine_sync(pf->e);
+    if (rc == SLAM_OK && hipMemcpy2D(rows, L * 4, src, Lp * 4, L * 4, 5 * n, hipMemcpyDeviceToHost) != hipSuccess) rc = SLAM_ERR_HIP;
+    (void)hipFree(dense);
+    return rc;
+}
+
+int pf_get_map_rows_host(slam_pf* pf, const int32_t* particle, int count, float* rows)
+{
+    if (!pf || !pf->L || count < 0 || (count > 0 && (!particle || !rows))) return SLAM_ERR_INVALID_ARG;
+    for (int k = 0; k < count; ++k)
+        if (particle[k] < 0 || particle[k] >= pf->n) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (pf->comm)
+        if (int rc = finish_exchange(pf)) return rc;   // collective: remote ancestors' rows into the staging tail
+    if (count == 0) return SLAM_OK;
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    if (pf->sel_cap < count) {
+        pf->sel_cap = 0;
+        if (int rc = replace_scratch(pf, (void**)&pf->sel, 2 * sizeof(int32_t) * (size_t)count, true)) return rc;
+        if (!pf->sel) return slam_engine_fail_hip(e, hipErrorOutOfMemory, "particle list");
+        pf->sel_cap = count;
+    }
+    const size_t L = (size_t)pf->L, Lp = (size_t)pf->Lp;
+    float* dense = nullptr;
+    SLAM_HIP_TRY(e, hipMalloc((void**)&dense, 5 * Lp * (size_t)count * 4));
+    int32_t *sel = pf->sel, *src = pf->sel + pf->sel_cap;
+    int rc = SLAM_OK;
+    auto ok = [&](hipError_t err, const char* what) {
+        if (err != hipSuccess && rc == SLAM_OK) rc = slam_engine_fail_hip(e, err, what);
+        return err == hipSuccess;
+    };
+    if (ok(hipMemcpyAsync(sel, particle, sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, e->stream), "copy of the particle list") &&
+        ok(launch_compose_index(e->stream, sel, pf->has_anc ? pf->anc[pf->cur] : nullptr, count, src), "compose_index")) {
+        if (pf->paged || pf->split)
+            ok(rows_of(pf, src, count, dense), "rows_of");
+        else
+            ok(launch_gather_map(e->stream, pf->map[pf->map_cur], dense, 5 * (int64_t)Lp, 5 * (int64_t)Lp, pf->Lp, pf->Lp, pf->L, src,
+                                 count), "gather_map");
+    }
+    if (rc == SLAM_OK) ok(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
+    if (rc == SLAM_OK) ok(hipMemcpy2D(rows, L * 4, dense, Lp * 4, L * 4, 5 * (size_t)count, hipMemcpyDeviceToHost), "hipMemcpy2D");
+    (void)hipFree(dense);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -737,7 +1322,7 @@ int slam_pf_reset(slam_pf* pf, const float pose[3])
     if (pf->split) {   // every landmark of every particle "not seen yet": one class
         split_new_epoch(pf);
         SLAM_HIP_TRY(pf->e, launch_split_reset(pf->e->stream, pf->mean[pf->sp_cur], pf->cov, pf->covx, pf->cls[pf->sp_cur], pf->Lp, pf->n,
-                                               pf->live[0], pf->cov_cnt, 0, pf->cstamp, pf->cstamp_now, split_h_live(pf), pf->cls_epoch));
+                                               pf->live[0], pf->cov_cnt, 0, pf->cstamp, pf->cstamp_now, dev_word(pf, RES_LIVE), pf->cls_epoch));
         if (pf->paged)   // split pages: every particle names ONE shared page of zero means, the rest of the pool is free
             SLAM_HIP_TRY(pf->e, launch_pages_reset(pf->e->stream, split_pool(pf), pf->pt[pf->pt_cur], (int64_t)pf->n * pf->nb, pf->freelist,
                                                    pf->npages, pf->page_scratch, split_geom(pf)));
@@ -809,9 +1394,7 @@ int slam_pf_set_map_dev(slam_pf* pf, const float* d_rows, int64_t row_stride, in
         pf->paged = false;
         pf->sp_cur = 0;
         if (int rc = split_from_rows(pf, d_rows, row_stride, plane_stride, pf->n)) return rc;
-        if (int rc = convert_split_to_split_pages(pf)) return rc;
-        pf->conversions--;
-        return SLAM_OK;
+        return split_means_to_pages(pf);
     }
     if (pf->split) return split_from_rows(pf, d_rows, row_stride, plane_stride, pf->n);
     if (pf->paged) {
@@ -828,57 +1411,6 @@ int slam_pf_set_map_dev(slam_pf* pf, const float* d_rows, int64_t row_stride, in
 
 int slam_pf_is_paged(const slam_pf* pf) { return pf && pf->paged ? 1 : 0; }
 
-// The classes' update of a frame (cov_update_body.h), in place, once per class still in use; nlandmarks = 0: only the list of
-// classes in use is brought up to date (a frame without observations).  The launch is as wide as the host knows the list to
-// be at most: its length as of some earlier launch (mapped memory, read without waiting) plus the classes that arrived since
-// (sharded sessions) — the second word is the running count of arrivals as of that launch; it is read FIRST and written
-// last, so a torn pair only over-estimates; before anything of this epoch has arrived: every class there can be.
-// the arguments and the width of the classes' update of this frame (and the session's bookkeeping moved on as if it had been
-// launched: the launch of the weights carries it)
-static void split_class_prepare(slam_pf* pf, int nlandmarks, CovArgs& ca, int& bound)
-{
-    slam_engine* e = pf->e;
-    const int32_t* hw = reinterpret_cast<const int32_t*>(pf->h_res);   // words 22-23: {count, epoch}; 18-19: {mark, epoch}
-    const uint64_t hm = __atomic_load_n(reinterpret_cast<const uint64_t*>(hw + 18), __ATOMIC_ACQUIRE),
-                   hl = __atomic_load_n(reinterpret_cast<const uint64_t*>(hw + 22), __ATOMIC_ACQUIRE);
-    const bool fresh = (uint32_t)(hl >> 32) == pf->cls_epoch && (uint32_t)hl > 0;
-    const uint32_t mark = (uint32_t)(hm >> 32) == pf->cls_epoch ? (uint32_t)hm : 0u;   // (no launch of this epoch has said yet: 0)
-    const int64_t upper = fresh ? (int64_t)(uint32_t)hl + (int64_t)(pf->cls_appended - mark) : (int64_t)pf->cap;
-    bound = upper < pf->cap ? (int)upper : pf->cap;
-    ca.cov = pf->cov;
-    ca.cov_stride = 3 * (int64_t)pf->Lp;
-    ca.covx = pf->covx;
-    ca.covx_stride = 2 * (int64_t)pf->Lp;
-    ca.plane_stride = pf->Lp;
-    ca.nlandmarks = nlandmarks;
-    ca.obs_zx = e->d_obs_zx;
-    ca.obs_zy = e->d_obs_zy;
-    ca.meas_var = pf->cfg.meas_var;
-    ca.live_in = pf->live[pf->live_cur];
-    ca.live_out = pf->live[1 - pf->live_cur];
-    ca.cnt = pf->cov_cnt;
-    ca.phase = pf->cov_phase;
-    ca.cstamp = pf->cstamp;
-    ca.stamp_now = pf->cstamp_now;
-    ca.h_live = split_h_live(pf);
-    ca.h_mark = reinterpret_cast<int32_t*>(pf->d_hres) + 18;
-    ca.epoch = pf->cls_epoch;
-    ca.mark = pf->cls_appended;
-    pf->live_cur = 1 - pf->live_cur;
-    pf->cov_phase = (pf->cov_phase + 1) % 3;
-}
-
-// the classes' update of the frame + the weights: ONE launch
-static int weights_with_classes(slam_pf* pf, int nlandmarks, bool use_ekf)
-{
-    CovArgs ca;
-    int bound = 0;
-    split_class_prepare(pf, nlandmarks, ca, bound);
-    return slam_logweight_cov_dev(pf->e, pf->score, use_ekf, pf->cfg.score_gain, pf->n, pf->logw, nullptr, &ca, bound);
-}
-
-static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations, bool* collective_verdict);
-
 int slam_pf_step(slam_pf* pf, int slot, const float dp[3], int use_observations)
 {
     if (!pf || !dp) return SLAM_ERR_INVALID_ARG;
@@ -891,322 +1423,8 @@ int slam_pf_step(slam_pf* pf, int slot, const float dp[3], int use_observations)
     return rc;
 }
 
-static int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations, bool* collective_verdict)
-{
-    slam_engine* e = pf->e;
-    slam_comm* comm = pf->comm;
-    if (pf->paged && __atomic_load_n(reinterpret_cast<int32_t*>(pf->h_res) + 20, __ATOMIC_ACQUIRE) != 0) {
-        snprintf(e->err, sizeof e->err, "paged maps: a free list was shorter than the pages reserved from it (pool invariant broken)");
-        return SLAM_ERR_CAPACITY;
-    }
-    if (int rc0 = auto_layout(pf)) return rc0;   // may move the maps between rows and pages (never changes a result)
-    const int n = pf->n, L = pf->L, cur = pf->cur, nxt = 1 - cur;
-    const size_t sn = (size_t)n;
-    // SLAM_MAP_AUTO samples the number of observed landmarks: every frame at the start and while the counts speak against
-    // the current layout, every 8th frame otherwise
-    const bool sample_obs = pf->layout_cfg == SLAM_MAP_AUTO && !pf->auto_stuck && L > 0 && use_observations &&
-                            e->obs_nlandmarks == L &&
-                            (pf->frame < 8 || (pf->frame & 7u) == 0 || (pf->paged ? pf->votes_rows : pf->votes_pages) > 0);
-    int32_t* d_hobs = reinterpret_cast<int32_t*>(pf->d_hres) + 24;
-    const float* src = pf->pose[cur];
-    float* dst = pf->pose[nxt];
-    const int32_t* anc = pf->has_anc ? pf->anc[cur] : nullptr;
-    const int64_t first_id = (int64_t)pf->rank * n;
-    int rc;
-    // 1 + 2 + 3 in ONE launch when the frame allows it (a single-GPU session on rows that resamples every frame, landmarks
-    // observed, long rows, enough particles): motion sample + scan-match score and the out-of-place landmark update side by
-    // side, the scorer's gathers in the shadow of the update's row stores (slam_frame_front_dev; the same bits)
-    bool fused = false;
-    SplitIO sio{};
-    auto make_sio = [&]() {   // the classes follow their particles through the update; it stamps the ones still in use
-        sio.group_filter = 0;
-        sio.map_anc = nullptr;
-        sio.cov = pf->cov;
-        sio.cov_stride = 3 * (int64_t)pf->Lp;
-        sio.covx = pf->covx;
-        sio.covx_stride = 2 * (int64_t)pf->Lp;
-        sio.cls_in = pf->cls[pf->sp_cur];
-        sio.cls_out = pf->cls[1 - pf->sp_cur];
-        sio.cstamp = pf->cstamp;
-        sio.stamp_now = pf->cstamp_now + 1;
-    };
-    if (pf->split) make_sio();
-    // Paged maps: the frame's page list (touched pages, observation list, where the fresh pages come from) and, when that asked
-    // for one, a new free list.  Neither needs anything from the motion + score launch nor the other way round: on one GPU the
-    // page list goes out first and the free list travels in workgroups of the scorer's launch (free_list_body.h); a sharded
-    // session issues both behind its exchange, which takes pages from the same list first.
-    int32_t *pstate = pf->page_scratch, *count = pstate + pool_state_words(), *tpage = count + 1, *tindex = tpage + pf->nb,
-            *tmask = tindex + pf->nb, *tbase = tmask + pf->nb, *lst = tbase + pf->nb + 1;
-    // the list form (one lane per observation) whenever a list can be made
-    const int form = L <= kObsListMaxLandmarks ? 1 : 0;
-    ObsListOut lo;
-    if (form && pf->paged) {
-        lo.id = lst;
-        lo.zx = reinterpret_cast<float*>(lst + pf->Lp);
-        lo.zy = reinterpret_cast<float*>(lst + 2 * pf->Lp);
-        lo.round = lst + 3 * pf->Lp;
-        lo.count = lst + 4 * pf->Lp;
-    }
-    auto issue_page_list = [&]() -> int {
-        const ProfScope prof(e, SLAM_PROF_PAGES);
-        SLAM_HIP_TRY(e, launch_page_list(e->stream, e->d_obs_zx, e->d_obs_zy, L, pf->nb, tpage, tindex, tmask, tbase, count, n, pstate,
-                                         sample_obs ? d_hobs : nullptr, sample_obs ? ++pf->obs_seq_issued : 0,
-                                         sample_obs ? pf->votes : nullptr, reinterpret_cast<int32_t*>(pf->d_hres) + 30, lo));
-        return SLAM_OK;
-    };
-    bool paged_listed = false;
-    FreeListRider rider;
-    if (!comm && pf->paged && L > 0 && use_observations && e->obs_nlandmarks == L) {
-        if (int rc1 = issue_page_list()) return rc1;
-        rider.stamp = pf->stamp;
-        rider.npages = pf->npages;
-        rider.live = pf->stamp_now;
-        rider.freelist = pf->freelist;
-        rider.pool_state = pstate;
-        rider.h_short = reinterpret_cast<int32_t*>(pf->d_hres) + 20;
-        paged_listed = true;
-    }
-    if (comm && pf->split && !pf->paged && pf->has_anc && !pf->gated && anc && L > 0 && use_observations && e->obs_nlandmarks == L) {
-        // Sharded, split maps: the front launch scores every particle (its ancestor's pose comes out of the all-gathered poses)
-        // and updates the groups of particles whose ancestors are all rows of this rank; the groups with an ancestor in the
-        // staging tail follow behind the exchange (below).  Like the motion + score launch it replaces, it needs nothing from
-        // the exchange and goes out before the host has looked at the plan.
-        if ((rc = comm_all_gather_finish(comm)) != SLAM_OK) return rc;
-        const float* pa = pf->pose_all;
-        sio.group_filter = 1;
-        sio.map_anc = anc;
-        rc = slam_frame_front_dev(e, slot, pa, pa + sn, pa + 2 * sn, pf->pose_idx[cur], dst, dst + sn, dst + 2 * sn, n, first_id, dp,
-                                  pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->score, pf->count, pf->mean[pf->sp_cur],
-                                  pf->mean[1 - pf->sp_cur], 2 * (int64_t)pf->Lp, pf->Lp, L, pf->cfg.meas_var, &fused, &sio);
-        if (rc != SLAM_OK) return rc;
-    }
-    // (a gated session on rows is left out: its frames that keep their population update in place; on the split layout they
-    // go through the identity index the resample stage leaves, like any other frame)
-    if (!comm && !pf->paged && (!pf->gated || pf->split) && anc && L > 0 && use_observations && e->obs_nlandmarks == L) {
-        if (pf->split)
-            rc = slam_frame_front_dev(e, slot, src, src + sn, src + 2 * sn, anc, dst, dst + sn, dst + 2 * sn, n, first_id, dp,
-                                      pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->score, pf->count, pf->mean[pf->sp_cur],
-                                      pf->mean[1 - pf->sp_cur], 2 * (int64_t)pf->Lp, pf->Lp, L, pf->cfg.meas_var, &fused, &sio);
-        else
-            rc = slam_frame_front_dev(e, slot, src, src + sn, src + 2 * sn, anc, dst, dst + sn, dst + 2 * sn, n, first_id, dp,
-                                      pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->score, pf->count, pf->map[pf->map_cur],
-                                      pf->map[1 - pf->map_cur], 5 * (int64_t)pf->Lp, pf->Lp, L, pf->cfg.meas_var, &fused);
-        if (rc != SLAM_OK) return rc;
-    }
-    // 1 + 2. motion (+ the fused gather of the previous resample) and scan-match score, one launch.  Sharded: the
-    // ancestors' poses come out of the array of every rank's poses, so this launch needs nothing from the exchange
-    // below and keeps the GPU busy while the host picks up the exchange plan.
-    if (fused) {
-        rc = SLAM_OK;
-    } else if (comm && pf->has_anc) {
-        if ((rc = comm_all_gather_finish(comm)) != SLAM_OK) return rc;
-        const float* pa = pf->pose_all;
-        rc = slam_motion_score_dev(e, slot, pa, pa + sn, pa + 2 * sn, pf->pose_idx[cur], dst, dst + sn, dst + 2 * sn, n,
-                                   first_id, dp, pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->score, pf->count);
-    } else {
-        bool rode = false;
-        rc = slam_motion_score_rider_dev(e, slot, src, src + sn, src + 2 * sn, anc, dst, dst + sn, dst + 2 * sn, n, first_id, dp,
-                                         pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->score, pf->count, paged_listed ? &rider : nullptr,
-                                         &rode);
-        if (rc == SLAM_OK && paged_listed && !rode) {   // (a small population: its scorer has no room for a rider)
-            const ProfScope prof(e, SLAM_PROF_PAGES);
-            SLAM_HIP_TRY(e, launch_free_list(e->stream, rider.stamp, rider.npages, rider.live, rider.freelist, rider.pool_state, rider.h_short));
-        }
-    }
-    if (rc != SLAM_OK) return rc;
-    // Resample gate: did the previous frame keep its population?  (Its verdict was made on the device; the host looks at it
-    // only now, behind the launch above — a flag in mapped memory.)  Then the maps have not moved: the EKF runs IN PLACE on
-    // the observed landmarks only, nothing is copied, the buffers do not flip.
-    bool in_place = false;
-    if (pf->gated && pf->has_anc) {
-        int resampled = 1;
-        if ((rc = slam_resample_happened_host(e, &resampled)) != SLAM_OK) return rc;
-        in_place = !resampled;
-        pf->frames_resampled += resampled ? 1 : 0;
-    }
-    if (comm) {
-        // map rows of remote ancestors -> staging tail; issued behind the launch above, which does not need them
-        if ((rc = finish_exchange(pf)) != SLAM_OK) {
-            *collective_verdict = rc == SLAM_ERR_CAPACITY;
-            return rc;
-        }
-    }
-    // 3. per-landmark EKF (+ fused gather); the log-likelihood stays inside the engine for step 4
-    const bool ekf = L > 0 && use_observations;
-    const int mc = pf->map_cur, mn = 1 - mc;
-    if (pf->split && !pf->paged && L > 0) {
-        const int sc = pf->sp_cur;
-        make_sio();   // (again: a layout move in front of the frame leaves other buffers than the ones the first look saw)
-        if (ekf) {
-            if (e->obs_nlandmarks != L) return SLAM_ERR_NOT_READY;
-            if (sample_obs) SLAM_HIP_TRY(e, launch_obs_count(e->stream, e->d_obs_zx, e->d_obs_zy, L, d_hobs, ++pf->obs_seq_issued, pf->votes));
-            // the particles' update (a frame that kept its population runs it out of place all the same: its gather index is
-            // the identity) ...
-            if (fused && comm) sio.group_filter = 2;   // the groups that waited for the exchange
-            // (no rows received this frame: no group has an ancestor in the staging tail, the launch would find nothing to do)
-            if (!fused || (comm && pf->rows_received > 0))
-                if ((rc = slam_ekf_split_dev(e, pf->mean[sc], pf->mean[1 - sc], 2 * (int64_t)pf->Lp, pf->Lp, L, dst, dst + sn, dst + 2 * sn,
-                                             anc, n, pf->cfg.meas_var, &sio)) != SLAM_OK)
-                    return rc;
-            pf->cstamp_now++;
-            pf->sp_cur = 1 - sc;
-            // ... then the classes' update, in place, once per class still in use
-            rc = weights_with_classes(pf, L, true);
-        } else {
-            if (anc) {   // means and classes follow their particles
-                const ProfScope prof(e, SLAM_PROF_PAGES);
-                SLAM_HIP_TRY(e, launch_split_gather(e->stream, pf->mean[sc], pf->mean[1 - sc], pf->cls[sc], pf->cls[1 - sc], pf->Lp, anc, n,
-                                                    pf->cstamp, ++pf->cstamp_now));
-                pf->sp_cur = 1 - sc;
-                rc = weights_with_classes(pf, 0, false);   // no observations: the list of classes in use only
-            } else
-                rc = slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
-        }
-    } else if (pf->paged) {
-        const int pc = pf->pt_cur;
-        if (ekf) {
-            // touched pages of this frame's observation table, the update into fresh pages, the next frame's free list
-            if (e->obs_nlandmarks != L) return SLAM_ERR_NOT_READY;
-            SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * sn));
-            if (!paged_listed) {
-                if (int rc1 = issue_page_list()) return rc1;
-                // a new free list when the old one runs short (decided on the device; the pages in use carry the last stamp)
-                const ProfScope prof(e, SLAM_PROF_PAGES);
-                SLAM_HIP_TRY(e, launch_free_list(e->stream, pf->stamp, pf->npages, pf->stamp_now, pf->freelist, pstate,
-                                                 reinterpret_cast<int32_t*>(pf->d_hres) + 20));
-            }
-            PagedEkfArgs a;
-            a.ol.id = lo.id;
-            a.ol.zx = lo.zx;
-            a.ol.zy = lo.zy;
-            a.ol.round = lo.round;
-            a.ol.count = lo.count;
-            a.tmask = tmask;
-            a.tbase = tbase;
-            a.pool = pf->pool;
-            if (pf->split) {   // split pages: mean pages of two planes, the covariances per class
-                a.geom = split_geom(pf);
-                a.pool = split_pool(pf);
-                a.cov = pf->cov;
-                a.covx = pf->covx;
-                a.plane_stride = pf->Lp;
-                a.cls_in = pf->cls[pf->sp_cur];
-                a.cls_out = pf->cls[1 - pf->sp_cur];
-                a.cstamp = pf->cstamp;
-                a.cstamp_now = pf->cstamp_now + 1;
-            }
-            a.pt_in = pf->pt[pc];
-            a.pt_out = pf->pt[1 - pc];
-            a.nb = pf->nb;
-            a.anc = anc;
-            a.n = n;
-            a.nlandmarks = L;
-            a.x = dst;
-            a.y = dst + sn;
-            a.th = dst + 2 * sn;
-            a.obs_zx = e->d_obs_zx;
-            a.obs_zy = e->d_obs_zy;
-            a.meas_var = pf->cfg.meas_var;
-            a.loglik = e->ll_buf.as<float>();
-            a.loglik_user = nullptr;
-            a.tpage = tpage;
-            a.tindex = tindex;
-            a.count = count;
-            a.freelist = pf->freelist;
-            a.pool_state = pstate;
-            a.stamp = pf->stamp;
-            a.stamp_now = ++pf->stamp_now;
-            // pages staged per pass = what the last frames touched (a hint in mapped memory, read without waiting)
-            SLAM_HIP_TRY(e, launch_ekf_paged(e->stream, a, e->prof_next(SLAM_PROF_EKF), form,
-                                             __atomic_load_n(reinterpret_cast<int32_t*>(pf->h_res) + 30, __ATOMIC_RELAXED)));
-            e->ll_n = n;
-            pf->pt_cur = 1 - pc;
-            if (pf->split) {   // the classes went with their particles; their covariances, once per class, with the weights
-                pf->cstamp_now++;
-                pf->sp_cur = 1 - pf->sp_cur;
-                rc = weights_with_classes(pf, L, true);
-            } else
-                rc = slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
-        } else {
-            if (anc) {   // the tables follow their particles
-                const ProfScope prof(e, SLAM_PROF_PAGES);
-                SLAM_HIP_TRY(e, launch_page_table_gather(e->stream, pf->pt[pc], pf->pt[1 - pc], pf->nb, anc, n, pf->stamp,
-                                                         ++pf->stamp_now));
-                pf->pt_cur = 1 - pc;
-                if (pf->split) {   // ... and so do the classes
-                    SLAM_HIP_TRY(e, launch_class_gather(e->stream, pf->cls[pf->sp_cur], pf->cls[1 - pf->sp_cur], anc, n, pf->cstamp,
-                                                        ++pf->cstamp_now));
-                    pf->sp_cur = 1 - pf->sp_cur;
-                }
-            }
-            rc = anc && pf->split ? weights_with_classes(pf, 0, false)
-                                  : slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
-        }
-    } else if (ekf && in_place) {
-        if (sample_obs) SLAM_HIP_TRY(e, launch_obs_count(e->stream, e->d_obs_zx, e->d_obs_zy, L, d_hobs, ++pf->obs_seq_issued, pf->votes));
-        rc = slam_ekf_update_dev(e, pf->map[mc], pf->map[mc], 5 * (int64_t)pf->Lp, pf->Lp, L, dst, dst + sn, dst + 2 * sn, nullptr, n,
-                                 pf->cfg.meas_var, nullptr);
-        if (rc != SLAM_OK) return rc;
-        rc = slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
-    } else if (ekf) {
-        if (sample_obs) SLAM_HIP_TRY(e, launch_obs_count(e->stream, e->d_obs_zx, e->d_obs_zy, L, d_hobs, ++pf->obs_seq_issued, pf->votes));
-        rc = fused ? SLAM_OK   // the update went out with the score
-                   : slam_ekf_update_dev(e, pf->map[mc], pf->map[mn], 5 * (int64_t)pf->Lp, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc,
-                                         n, pf->cfg.meas_var, nullptr);
-        if (rc != SLAM_OK) return rc;
-        pf->map_cur = mn;
-        rc = slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
-    } else {
-        if (L > 0 && anc && !in_place) {   // the maps follow their particles even without an observation
-            rc = slam_gather_map_dev(e, pf->map[mc], pf->map[mn], 5 * (int64_t)pf->Lp, 5 * (int64_t)pf->Lp, pf->Lp, pf->Lp, L,
-                                     anc, n);
-            if (rc != SLAM_OK) return rc;
-            pf->map_cur = mn;
-        }
-        rc = slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
-    }
-    if (rc != SLAM_OK) return rc;
-    // 4. weights: the maximum over all ranks, then fixed-point weights scanned as they are produced
-    // Sharded: the ranks all-reduce the BLOCK maxima the weights' launch leaves in the engine (element by element: a few hundred
-    // floats cost the wire what one costs) and the scan takes their maximum itself, as it does on one GPU — the maximum of the
-    // same set of values, and one single-workgroup launch less per frame than reducing them to one float first.
-    if (comm) {
-        if (e->bmax_n != n || e->bmax_count <= 0) return SLAM_ERR_NOT_READY;
-        if ((rc = comm_all_reduce_max_f32(comm, e->bmax_buf.as<float>(), e->bmax_count)) != SLAM_OK) return rc;
-    }
-    if ((rc = slam_quantise_scan_dev(e, pf->logw, nullptr, n, comm ? pf->d_sum : nullptr)) != SLAM_OK) return rc;
-    // 5. resample on the integer CDF
-    if (!comm) {
-        if ((rc = slam_ancestors_from_scan_dev(e, n, pf->cfg.seed, pf->frame, pf->anc[nxt])) != SLAM_OK) return rc;
-    } else {
-        // shard totals (with the gate: total, sum v, sum v^2 per rank)
-        if ((rc = comm_all_gather(comm, pf->d_sum, pf->totals, (pf->gated ? 3 : 1) * sizeof(uint64_t))) != SLAM_OK) return rc;
-        if ((rc = slam_offspring_from_scan_sharded_dev(e, n, pf->totals, pf->rank, pf->world, pf->cfg.seed, pf->frame,
-                                                       pf->n_total, pf->first)) != SLAM_OK)
-            return rc;
-        // the "all-gather of surviving indices" (4 B x N_total) and, grouped into the same RCCL launch, this frame's poses
-        // to every rank (12 B x N_total) for the next frame's motion + score — that launch then needs nothing from the exchange
-        if ((rc = comm_all_gather2(comm, pf->first, pf->first_all, sn * sizeof(int32_t), dst, pf->pose_all,
-                                   3 * sn * sizeof(float))) != SLAM_OK)
-            return rc;
-        // 6. gather index of every slot (remote ancestors -> rows of the staging tail) and the exchange plan, on the
-        // device; the exchange itself happens at the start of the next frame, behind its motion + score launch
-        if ((rc = slam_ancestors_sharded_dev(e, pf->first_all, pf->n_total, n, pf->rank, pf->world, pf->anc[nxt], pf->d_plan,
-                                             pf->pose_idx[nxt])) != SLAM_OK)
-            return rc;
-        pf->exchange_pending = true;
-    }
-    pf->cur = nxt;
-    pf->has_anc = true;
-    pf->last_ekf = ekf;
-    pf->frame++;
-    return SLAM_OK;
-}
-
 int slam_pf_rows_received(const slam_pf* pf) { return pf ? pf->rows_received : 0; }
-
 int64_t slam_pf_frames_resampled(const slam_pf* pf) { return pf ? pf->frames_resampled : 0; }
-
 int64_t slam_pf_layout_changes(const slam_pf* pf) { return pf ? pf->conversions : 0; }
 
 int slam_pf_device_view(slam_pf* pf, slam_pf_view* out)
@@ -1269,216 +1487,9 @@ int slam_pf_paged_device_view(slam_pf* pf, slam_pf_paged_view* out)
     return SLAM_OK;
 }
 
-static int slam_pf_best_impl(slam_pf* pf, float pose[3], float* logw, int32_t* index);
-
-int slam_pf_best(slam_pf* pf, float pose[3], float* logw, int32_t* index)
-{
-    return collective_result(pf, slam_pf_best_impl(pf, pose, logw, index));
-}
-
-static int slam_pf_best_impl(slam_pf* pf, float pose[3], float* logw, int32_t* index)
-{
-    if (!pf || !pose) return SLAM_ERR_INVALID_ARG;
-    slam_engine* e = pf->e;
-    SLAM_HIP_TRY(e, hipSetDevice(e->device));
-    // the log-weights of the last frame belong to pose[cur] BEFORE the pending gather
-    const float* p = pf->pose[pf->cur];
-    const size_t sn = (size_t)pf->n;
-    float r[5];
-    if (!pf->comm) {   // one launch, the result lands in mapped host memory: no copy, no stream synchronisation
-        const uint32_t seq = ++pf->res_seq;
-        SLAM_HIP_TRY(e, launch_best_particle(e->stream, pf->logw, pf->n, p, p + sn, p + 2 * sn, 0, pf->res_dev, pf->d_hres,
-                                             reinterpret_cast<uint32_t*>(pf->d_hres + 16), seq));
-        if (int rc = wait_result(pf, seq)) return rc;
-        memcpy(r, pf->h_res, sizeof r);
-    } else {   // every rank's candidate to every rank; the first maximum = the lowest rank = the lowest id
-        SLAM_HIP_TRY(e, launch_best_particle(e->stream, pf->logw, pf->n, p, p + sn, p + 2 * sn, (int64_t)pf->rank * pf->n,
-                                             pf->res_dev, nullptr, nullptr, 0));
-        if (int rc = comm_all_gather(pf->comm, pf->res_dev, pf->res_all, 5 * sizeof(float))) return rc;
-        std::vector<float> all(5 * (size_t)pf->world);
-        SLAM_HIP_TRY(e, hipMemcpyAsync(all.data(), pf->res_all, all.size() * 4, hipMemcpyDeviceToHost, e->stream));
-        if (int rc = comm_wait_stream(pf->comm)) return rc;
-        int best = 0;
-        for (int q = 1; q < pf->world; ++q)
-            if (all[5 * q] > all[5 * best]) best = q;
-        memcpy(r, &all[5 * best], sizeof r);
-    }
-    int32_t gid;
-    memcpy(&gid, &r[1], 4);
-    for (int k = 0; k < 3; ++k) pose[k] = r[2 + k];
-    if (logw) *logw = r[0];
-    if (index) *index = gid;
-    return SLAM_OK;
-}
-
-static int slam_pf_mean_impl(slam_pf* pf, float ref_theta, float pose[3]);
-
-int slam_pf_mean(slam_pf* pf, float ref_theta, float pose[3])
-{
-    return collective_result(pf, slam_pf_mean_impl(pf, ref_theta, pose));
-}
-
-static int slam_pf_mean_impl(slam_pf* pf, float ref_theta, float pose[3])
-{
-    if (!pf || !pose) return SLAM_ERR_INVALID_ARG;
-    slam_engine* e = pf->e;
-    SLAM_HIP_TRY(e, hipSetDevice(e->device));
-    const size_t sn = (size_t)pf->n;
-    const float *x = pf->pose[pf->cur], *y = x + sn, *th = x + 2 * sn;
-    const int32_t* idx = pf->has_anc ? pf->anc[pf->cur] : nullptr;
-    if (pf->comm && pf->has_anc) {   // the ancestors' poses are in the all-gathered array
-        if (int rc = comm_all_gather_finish(pf->comm)) return rc;
-        x = pf->pose_all;
-        y = x + sn;
-        th = x + 2 * sn;
-        idx = pf->pose_idx[pf->cur];
-    }
-    unsigned int* ticket = reinterpret_cast<unsigned int*>(pf->sums_acc + 4);
-    long long sums[4] = { 0, 0, 0, 0 };
-    if (!pf->comm) {
-        const uint32_t seq = ++pf->res_seq;
-        SLAM_HIP_TRY(e, launch_pose_sums(e->stream, x, y, th, idx, pf->n, ref_theta, pf->sums_acc, ticket,
-                                         reinterpret_cast<long long*>(pf->res_dev), reinterpret_cast<long long*>(pf->d_hres),
-                                         reinterpret_cast<uint32_t*>(pf->d_hres + 16), seq));
-        if (int rc = wait_result(pf, seq)) return rc;
-        memcpy(sums, pf->h_res, sizeof sums);
-    } else {   // integer sums: adding the ranks' shares in any order gives the single-GPU bits
-        SLAM_HIP_TRY(e, launch_pose_sums(e->stream, x, y, th, idx, pf->n, ref_theta, pf->sums_acc, ticket,
-                                         reinterpret_cast<long long*>(pf->res_dev), nullptr, nullptr, 0));
-        if (int rc = comm_all_gather(pf->comm, pf->res_dev, pf->res_all, 4 * sizeof(long long))) return rc;
-        std::vector<long long> all(4 * (size_t)pf->world);
-        SLAM_HIP_TRY(e, hipMemcpyAsync(all.data(), pf->res_all, all.size() * 8, hipMemcpyDeviceToHost, e->stream));
-        if (int rc = comm_wait_stream(pf->comm)) return rc;
-        for (int q = 0; q < pf->world; ++q)
-            for (int k = 0; k < 4; ++k) sums[k] += all[4 * (size_t)q + k];
-    }
-    const double nt = (double)pf->n_total;
-    pose[0] = (float)((double)sums[0] / 4294967296.0 / nt);
-    pose[1] = (float)((double)sums[1] / 4294967296.0 / nt);
-    pose[2] = (float)((double)ref_theta + atan2((double)sums[2], (double)sums[3]));
-    return SLAM_OK;
-}
-
-static int slam_pf_get_poses_host_impl(slam_pf* pf, float* x, float* y, float* theta);
-
-int slam_pf_get_poses_host(slam_pf* pf, float* x, float* y, float* theta)
-{
-    return collective_result(pf, slam_pf_get_poses_host_impl(pf, x, y, theta));
-}
-
-static int slam_pf_get_poses_host_impl(slam_pf* pf, float* x, float* y, float* theta)
-{
-    if (!pf || !x || !y || !theta) return SLAM_ERR_INVALID_ARG;
-    const size_t n = (size_t)pf->n;
-    float* tmp = pf->pose[1 - pf->cur];   // the other buffer is free between frames
-    float* out[3] = { x, y, theta };
-    if (pf->comm && pf->has_anc) {   // the ancestors' poses are in the all-gathered array
-        if (int rc = comm_all_gather_finish(pf->comm)) return rc;
-        for (int k = 0; k < 3; ++k)
-            if (int rc = gathered_copy_out(pf, pf->pose_all + k * n, pf->pose_idx[pf->cur], out[k], tmp)) return rc;
-        return SLAM_OK;
-    }
-    const float* p = pf->pose[pf->cur];
-    for (int k = 0; k < 3; ++k)
-        if (int rc = gathered_copy_out(pf, p + k * n, pf->has_anc ? pf->anc[pf->cur] : nullptr, out[k], tmp)) return rc;
-    return SLAM_OK;
-}
-
-static int slam_pf_get_map_host_impl(slam_pf* pf, float* rows);
-
-int slam_pf_get_map_host(slam_pf* pf, float* rows)
-{
-    return collective_result(pf, slam_pf_get_map_host_impl(pf, rows));
-}
-
-static int slam_pf_get_map_host_impl(slam_pf* pf, float* rows)
-{
-    if (!pf || !rows || !pf->L) return SLAM_ERR_INVALID_ARG;
-    const size_t n = (size_t)pf->n, L = (size_t)pf->L, Lp = (size_t)pf->Lp;
-    if (pf->comm)
-        if (int rc = finish_exchange(pf)) return rc;   // collective: remote ancestors' rows into the staging tail
-    if (pf->paged || pf->split) {   // -> rows in a scratch buffer (the pending gather applied on the way), then the copy
-        float* dense = nullptr;
-        if (hipMalloc((void**)&dense, 5 * Lp * n * 4) != hipSuccess) return SLAM_ERR_HIP;
-        int rc = SLAM_OK;
-        const int32_t* idx = pf->has_anc ? pf->anc[pf->cur] : nullptr;
-        if ((split_pages(pf) ? launch_rows_from_split_pages(pf->e->stream, split_pool(pf), split_geom(pf), pf->pt[pf->pt_cur], pf->nb, pf->cov,
-                                                            pf->cls[pf->sp_cur], pf->Lp, idx, pf->n, dense, 5 * (int64_t)Lp, pf->Lp, pf->L)
-             : pf->split ? launch_rows_from_split(pf->e->stream, pf->mean[pf->sp_cur], pf->cov, pf->cls[pf->sp_cur], pf->Lp, idx, pf->n, dense,
-                                                5 * (int64_t)Lp, pf->Lp, pf->L)
-                       : launch_rows_from_pages(pf->e->stream, pf->pool, pf->pt[pf->pt_cur], pf->nb, idx, pf->n, dense, 5 * (int64_t)Lp,
-                                                pf->Lp, pf->L)) != hipSuccess)
-            rc = SLAM_ERR_HIP;
-        if (rc == SLAM_OK) rc = slam_engine_sync(pf->e);
-        if (rc == SLAM_OK && hipMemcpy2D(rows, L * 4, dense, Lp * 4, L * 4, 5 * n, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = SLAM_ERR_HIP;
-        (void)hipFree(dense);
-        return rc;
-    }
-    const float* src = pf->map[pf->map_cur];
-    if (pf->has_anc) {
-        int rc = slam_gather_map_dev(pf->e, pf->map[pf->map_cur], pf->map[1 - pf->map_cur], 5 * (int64_t)Lp,
-                                     5 * (int64_t)Lp, pf->Lp, pf->Lp, pf->L, pf->anc[pf->cur], pf->n);
-        if (rc != SLAM_OK) return rc;
-        src = pf->map[1 - pf->map_cur];
-    }
-    if (int rc = slam_engine_sync(pf->e)) return rc;
-    return hipMemcpy2D(rows, L * 4, src, Lp * 4, L * 4, 5 * n, hipMemcpyDeviceToHost) == hipSuccess ? SLAM_OK : SLAM_ERR_HIP;
-}
-
-static int slam_pf_get_map_rows_host_impl(slam_pf* pf, const int32_t* particle, int count, float* rows);
-
-int slam_pf_get_map_rows_host(slam_pf* pf, const int32_t* particle, int count, float* rows)
-{
-    return collective_result(pf, slam_pf_get_map_rows_host_impl(pf, particle, count, rows));
-}
-
-static int slam_pf_get_map_rows_host_impl(slam_pf* pf, const int32_t* particle, int count, float* rows)
-{
-    if (!pf || !pf->L || count < 0 || (count > 0 && (!particle || !rows))) return SLAM_ERR_INVALID_ARG;
-    for (int k = 0; k < count; ++k)
-        if (particle[k] < 0 || particle[k] >= pf->n) return SLAM_ERR_INVALID_ARG;
-    slam_engine* e = pf->e;
-    if (pf->comm)
-        if (int rc = finish_exchange(pf)) return rc;   // collective: remote ancestors' rows into the staging tail
-    if (count == 0) return SLAM_OK;
-    SLAM_HIP_TRY(e, hipSetDevice(e->device));
-    if (pf->sel_cap < count) {
-        SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
-        if (pf->sel) (void)hipFree(pf->sel);
-        pf->sel = nullptr;
-        pf->sel_cap = 0;
-        SLAM_HIP_TRY(e, hipMalloc((void**)&pf->sel, 2 * sizeof(int32_t) * (size_t)count));
-        pf->sel_cap = count;
-    }
-    const size_t L = (size_t)pf->L, Lp = (size_t)pf->Lp;
-    float* dense = nullptr;
-    SLAM_HIP_TRY(e, hipMalloc((void**)&dense, 5 * Lp * (size_t)count * 4));
-    int32_t *sel = pf->sel, *src = pf->sel + pf->sel_cap;
-    int rc = SLAM_OK;
-    auto ok = [&](hipError_t err, const char* what) {
-        if (err != hipSuccess && rc == SLAM_OK) rc = slam_engine_fail_hip(e, err, what);
-        return err == hipSuccess;
-    };
-    if (ok(hipMemcpyAsync(sel, particle, sizeof(int32_t) * (size_t)count, hipMemcpyHostToDevice, e->stream), "copy of the particle list") &&
-        ok(launch_compose_index(e->stream, sel, pf->has_anc ? pf->anc[pf->cur] : nullptr, count, src), "compose_index")) {
-        if (split_pages(pf))
-            ok(launch_rows_from_split_pages(e->stream, split_pool(pf), split_geom(pf), pf->pt[pf->pt_cur], pf->nb, pf->cov, pf->cls[pf->sp_cur],
-                                            pf->Lp, src, count, dense, 5 * (int64_t)Lp, pf->Lp, pf->L), "rows_from_split_pages");
-        else if (pf->split)
-            ok(launch_rows_from_split(e->stream, pf->mean[pf->sp_cur], pf->cov, pf->cls[pf->sp_cur], pf->Lp, src, count, dense,
-                                      5 * (int64_t)Lp, pf->Lp, pf->L), "rows_from_split");
-        else if (pf->paged)
-            ok(launch_rows_from_pages(e->stream, pf->pool, pf->pt[pf->pt_cur], pf->nb, src, count, dense, 5 * (int64_t)Lp, pf->Lp, pf->L),
-               "rows_from_pages");
-        else
-            ok(launch_gather_map(e->stream, pf->map[pf->map_cur], dense, 5 * (int64_t)Lp, 5 * (int64_t)Lp, pf->Lp, pf->Lp, pf->L, src,
-                                 count), "gather_map");
-    }
-    if (rc == SLAM_OK) ok(hipStreamSynchronize(e->stream), "hipStreamSynchronize");
-    if (rc == SLAM_OK) ok(hipMemcpy2D(rows, L * 4, dense, Lp * 4, L * 4, 5 * (size_t)count, hipMemcpyDeviceToHost), "hipMemcpy2D");
-    (void)hipFree(dense);
-    return rc;
-}
-
+int slam_pf_best(slam_pf* pf, float pose[3], float* logw, int32_t* index) { return collective_result(pf, pf_best(pf, pose, logw, index)); }
+int slam_pf_mean(slam_pf* pf, float ref_theta, float pose[3]) { return collective_result(pf, pf_mean(pf, ref_theta, pose)); }
+int slam_pf_get_poses_host(slam_pf* pf, float* x, float* y, float* theta) { return collective_result(pf, pf_get_poses_host(pf, x, y, theta)); }
+int slam_pf_get_map_host(slam_pf* pf, float* rows) { return collective_result(pf, pf_get_map_host(pf, rows)); }
+int slam_pf_get_map_rows_host(slam_pf* pf, const int32_t* particle, int count, float* rows) { return collective_result(pf, pf_get_map_rows_host(pf, particle, count, rows)); }
 }  // extern "C"
