@@ -1,5 +1,5 @@
 // engine_internal.h — the engine object shared by the translation units that implement the C ABI
-// (engine.hip, mapper.hip).  Not part of the public interface.
+// (engine.hip and the engine_*.hip units by stage, pf_session.hip, comm.hip, mapper.hip).  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -83,7 +83,7 @@ struct slam_engine {
     const float *d_obs_zx = nullptr, *d_obs_zy = nullptr;
 
     DevBuf fm_buf;             // kFmIn + kFmOut floats
-    DevBuf fm_work;            // 27 x SLAM_MAX_BEAMS floats: per-candidate hit rows of the lattice kernel
+    DevBuf fm_work;            // 2 x 27 x SLAM_MAX_BEAMS floats: per-candidate hit rows of the lattice kernel, two sweeps (the chained pair)
     float* h_fm = nullptr;     // pinned + mapped: lattice candidates in, results out, then one uint32 arrival flag
     float* d_hfm = nullptr;    // the same memory as the device sees it (zero-copy FastMatch I/O)
     uint32_t fm_seq = 0;
@@ -186,7 +186,7 @@ struct slam_engine {
     // pinned staging ring for the per-frame sensor uploads: one host-to-device copy per upload, and the
     // host only waits if kStageSlots uploads are still in flight
     float* h_stage = nullptr;
-    hipEvent_t stage_ev[8] = {};
+    hipEvent_t stage_ev[kStageSlots] = {};
     unsigned stage_next = 0;
 
     float* stage_acquire()
@@ -242,12 +242,34 @@ struct ProfScope {
     ProfScope& operator=(const ProfScope&) = delete;
 };
 
-// helpers implemented in engine.hip
+// ---- helpers shared between the translation units, by the unit that implements them
+// engine.hip: what a failed HIP call leaves in slam_last_error ("what: hipGetErrorString") and returns
+int slam_engine_fail_hip(slam_engine* e, hipError_t err, const char* what);
+// bounded spin on a word in mapped host memory (a few seconds at most); false: it never showed `want`
+inline bool slam_spin_flag(const volatile uint32_t* flag, uint32_t want)
+{
+    for (long spin = 0; spin < 400000000L; ++spin)
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == want) return true;
+    return false;
+}
+// engine.hip: wait until `flag` shows `seq`.  With a communicator: comm_wait_flag (polls it, bounded in time).  Without: the
+// bounded spin, then a stream synchronisation and one more look; SLAM_ERR_HIP naming `what` if it still is not there.
+int slam_engine_wait_flag(slam_engine* e, slam_comm* comm, const volatile uint32_t* flag, uint32_t seq, const char* what);
+
+// engine_match.hip
+namespace slam_detail {
+// slot in range, its grid and a scan present
+__attribute__((visibility("hidden"))) int check_score_inputs(slam_engine* e, int slot);
+// the grid of `slot` as the scorers of `nposes` poses want it (with the byte-per-cell copy when there are many)
+__attribute__((visibility("hidden"))) int many_pose_grid(slam_engine* e, int slot, int nposes, slam::ScoreGrid* out);
+}  // namespace slam_detail
+// engine_resample.hip:
 // slam_logweight_dev / slam_logweight_ekf_dev (use_ekf) with, optionally, a split session's covariance classes brought up to
 // date by workgroups of the same launch (launch_logweight)
 extern "C" int slam_logweight_cov_dev(slam_engine* e, const float* d_score, bool use_ekf, float score_gain, int n, float* d_logw, float* d_max,
                            const slam::CovArgs* cov, int cov_bound);
-// slam_motion_score_dev with a rider (defined in engine.hip next to it)
+// engine_ekf.hip:
+// slam_motion_score_dev with a rider
 extern "C" int slam_motion_score_rider_dev(slam_engine* e, int slot, const float* d_src_x, const float* d_src_y, const float* d_src_th,
                                            const int32_t* d_anc, float* d_x, float* d_y, float* d_th, int n, int64_t first_id,
                                            const float dp[3], const float sigma[3], uint64_t seed, uint32_t frame, float* d_score,
@@ -265,19 +287,19 @@ extern "C" int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src
 extern "C" int slam_ekf_split_dev(slam_engine* e, const float* d_mean_in, float* d_mean_out, int64_t row_stride, int plane_stride,
                        int nlandmarks, const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc, int n,
                        float meas_var, const slam::SplitIO* split);
-int slam_engine_fail_hip(slam_engine* e, hipError_t err, const char* what);
+// engine_match.hip:
 slam::ScoreGrid slam_engine_score_grid(const slam_engine* e, int slot);
 // FastMatch on grid `slot` with the beam count read from device memory (d_nbeams, at most nbeams_max) and the
 // scan at d_bx/d_by; optionally mirrors the hit scratch into d_hits_persist.  Synchronises.
 int slam_engine_fastmatch(slam_engine* e, int slot, const float* d_bx, const float* d_by, int nbeams_max,
                           const int32_t* d_nbeams, const float pose[3], const float res[3], float out_pose[3],
                           float* best_hits, int32_t* best_hits_size, float* best_score, float* d_hits_persist);
-// ... and FastMatch(pose, res1) on slot1 followed by FastMatch2(its result, res2) on slot2 as ONE round trip (engine.hip)
+// ... and FastMatch(pose, res1) on slot1 followed by FastMatch2(its result, res2) on slot2 as ONE round trip
 int slam_engine_fastmatch_pair(slam_engine* e, int slot1, int slot2, const float* d_bx, const float* d_by, int nbeams_max,
                                const int32_t* d_nbeams, const float pose[3], const float res1[3], const float res2[3],
                                float out_pose[3], int32_t* best_hits_size, float* d_hits_persist);
 
-// slam_migrate_pack_dev for a session with paged maps (d_pt: page tables of nb entries, d_map: the page pool)
+// engine_resample.hip: slam_migrate_pack_dev for a session with paged maps (d_pt: page tables of nb entries, d_map: the page pool)
 extern "C" int slam_migrate_pack_paged(slam_engine* e, int n_local, int rank, int world, const int32_t* plan, const float* d_pose,
                             int64_t pose_ld, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks,
                             float* d_out, const int32_t* d_pt, int nb, const float* d_split_cov = nullptr,
@@ -288,4 +310,11 @@ extern "C" int slam_migrate_pack_paged(slam_engine* e, int n_local, int rank, in
     do {                                                                          \
         hipError_t err__ = (call);                                                \
         if (err__ != hipSuccess) return slam_engine_fail_hip((e), err__, #call); \
+    } while (0)
+
+// first line of every entry point that takes the engine
+#define SLAM_ENTER(e)                                  \
+    do {                                               \
+        if (!(e)) return SLAM_ERR_INVALID_ARG;         \
+        SLAM_HIP_TRY((e), hipSetDevice((e)->device)); \
     } while (0)

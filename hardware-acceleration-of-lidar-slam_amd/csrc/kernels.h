@@ -1,5 +1,5 @@
 // kernels.h — launchers of the gfx950 kernels, one section per kernel file in the Makefile's order; called by the C-ABI layer
-// (engine.hip), the particle-filter session (pf_session.hip) and the mapper (mapper.hip).
+// (engine.hip and engine_match / engine_ekf / engine_resample.hip by stage), the particle-filter session (pf_session.hip) and the mapper (mapper.hip).
 // Every launcher enqueues on `stream` and returns the hipError_t of the launch; none synchronises.
 #pragma once
 
@@ -86,7 +86,7 @@ hipError_t launch_pose_hits(hipStream_t stream, const ScoreGrid& g, const float*
 hipError_t launch_lattice(hipStream_t stream, const ScoreGrid& g, const float* bx, const float* by, int nbeams,
                           const int32_t* d_nbeams, const float* cand_xycs /* X[27] Y[27] CT[27] ST[27] */, float* work,
                           float* out, float* persist, float* host_out, uint32_t* host_flag, uint32_t seq);
-// FastMatch on g1 followed by FastMatch2 on g2 around its winner, THREE launches and no host in between (engine.hip:
+// FastMatch on g1 followed by FastMatch2 on g2 around its winner, THREE launches and no host in between (engine_match.hip:
 // slam_engine_fastmatch_pair): the first lattice from cand1 as above; the second lattice's wavefronts work out the first call's
 // winner themselves (strict '<' from +inf over out1's 27 scores, the first of equals; none: the middle candidate = the input
 // pose) and lay their own candidate around it — x, y = the winner's -/+ pair_in[18], heading (cos, sin) = pair_in[3 a + b],

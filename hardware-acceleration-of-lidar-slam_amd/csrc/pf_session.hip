@@ -294,24 +294,11 @@ int drop_resample(slam_pf* pf)
     return SLAM_OK;
 }
 
-// bounded spin on a word in mapped host memory; false: it never showed `want`
-bool spin_flag(const volatile uint32_t* flag, uint32_t want)
-{
-    for (long spin = 0; spin < 400000000L; ++spin)
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == want) return true;
-    return false;
-}
-
-// wait for a result kernel's sequence number in mapped host memory (bounded spin, then let the runtime tell us)
+// wait for a result kernel's sequence number in mapped host memory
 int wait_result(slam_pf* pf, uint32_t seq)
 {
-    slam_engine* e = pf->e;
     const volatile uint32_t* h_seq = reinterpret_cast<const volatile uint32_t*>(host_word(pf, RES_SEQ));
-    if (pf->comm) return comm_wait_flag(pf->comm, h_seq, seq);
-    if (spin_flag(h_seq, seq)) return SLAM_OK;
-    SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
-    if (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != seq) return slam_engine_fail_hip(e, hipErrorUnknown, "result flag");
-    return SLAM_OK;
+    return slam_engine_wait_flag(pf->e, pf->comm, h_seq, seq, "result flag");
 }
 
 int gathered_copy_out(slam_pf* pf, const float* d_src, const int32_t* idx, float* h_dst, float* d_tmp)
@@ -559,7 +546,7 @@ int auto_layout(slam_pf* pf)
         if (pf->comm) {
             if (int rc = comm_wait_flag(pf->comm, h_seq, pf->obs_seq_issued)) return rc;
         } else
-            (void)spin_flag(h_seq, pf->obs_seq_issued);   // (never showed up: this look finds nothing new, that is all)
+            (void)slam_spin_flag(h_seq, pf->obs_seq_issued);   // (never showed up: this look finds nothing new, that is all)
     }
     const uint32_t seq = __atomic_load_n(h_seq, __ATOMIC_ACQUIRE);
     if (seq == pf->obs_seq_seen) return SLAM_OK;
