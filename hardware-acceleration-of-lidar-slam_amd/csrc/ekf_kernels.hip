@@ -17,6 +17,7 @@
 #include "ekf_math.h"
 #include "score_body.h"
 #include "pf_common.h"
+#include "storage_bodies.h"
 
 namespace slam {
 
@@ -858,9 +859,7 @@ struct ObsList {
 // one workgroup: table (NaN = not observed) -> list in landmark order, rounds, counts (also to mapped host memory).
 // L <= kObsListMaxLandmarks (the bitmap of observed landmarks lives in LDS).
 __global__ __launch_bounds__(1024) void build_obs_list_kernel(const float* __restrict__ tzx, const float* __restrict__ tzy,
-                                                              int L, int32_t* __restrict__ id, float* __restrict__ zx,
-                                                              float* __restrict__ zy, int32_t* __restrict__ round,
-                                                              int32_t* __restrict__ count, int32_t* __restrict__ h_count)
+                                                              int L, ObsListOut ol, int32_t* __restrict__ h_count)
 {
     __shared__ unsigned s_bits[kObsListMaxLandmarks / 32];
     __shared__ int s_wave[16];
@@ -868,29 +867,14 @@ __global__ __launch_bounds__(1024) void build_obs_list_kernel(const float* __res
     __shared__ int s_max_round;
     if (threadIdx.x == 0) { s_base = 0; s_max_round = 0; }
     __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int l0 = 0; l0 < L; l0 += 1024) {   // ordered compaction, 1024 landmarks per step
+    for (int l0 = 0; l0 < L; l0 += 1024) {   // ordered compaction, 1024 landmarks per step (storage_bodies.h)
         const int l = l0 + (int)threadIdx.x;
         const float vx = l < L ? tzx[l] : __builtin_nanf(""), vy = l < L ? tzy[l] : __builtin_nanf("");
         const bool ob = vx == vx && vy == vy;
         const unsigned long long m = __ballot(ob);
-        if (lane == 0) s_wave[wave] = __popcll(m);
-        if (lane == 0) s_bits[(l0 >> 5) + 2 * wave] = (unsigned)m;
-        if (lane == 32) s_bits[(l0 >> 5) + 2 * wave + 1] = (unsigned)(m >> 32);
+        obs_list_mark(m, l0, s_wave, s_bits);
         __syncthreads();
-        int off = s_base;
-        for (int w = 0; w < wave; ++w) off += s_wave[w];
-        if (ob) {
-            const int k = off + __popcll(m & ((1ull << lane) - 1ull));
-            id[k] = l;
-            zx[k] = vx;
-            zy[k] = vy;
-            // round: earlier observed landmarks with the same l mod 128 = the same bit of every fourth word below
-            int r = 0;
-            for (int b = l - 128; b >= 0; b -= 128) r += (int)((s_bits[b >> 5] >> (b & 31)) & 1u);
-            round[k] = r;
-            if (r > 0) atomicMax(&s_max_round, r);
-        }
+        obs_list_step(m, ob, l, vx, vy, s_wave, s_base, s_bits, ol, &s_max_round);
         __syncthreads();
         if (threadIdx.x == 0) {
             int tot = 0;
@@ -902,8 +886,8 @@ __global__ __launch_bounds__(1024) void build_obs_list_kernel(const float* __res
     const int nobs = s_base;
     __syncthreads();
     if (threadIdx.x == 0) {
-        count[0] = nobs;
-        count[1] = s_max_round;
+        ol.count[0] = nobs;
+        ol.count[1] = s_max_round;
         if (h_count) {
             h_count[0] = nobs;
             h_count[1] = L;
@@ -1167,10 +1151,9 @@ hipError_t launch_selftest_reciprocal(hipStream_t stream, unsigned long long* ou
     return hipGetLastError();
 }
 
-hipError_t launch_build_obs_list(hipStream_t stream, const float* tzx, const float* tzy, int L, int32_t* id, float* zx,
-                                 float* zy, int32_t* round, int32_t* count, int32_t* h_count)
+hipError_t launch_build_obs_list(hipStream_t stream, const float* tzx, const float* tzy, int L, const ObsListOut& ol, int32_t* h_count)
 {
-    build_obs_list_kernel<<<1, 1024, 0, stream>>>(tzx, tzy, L, id, zx, zy, round, count, h_count);
+    build_obs_list_kernel<<<1, 1024, 0, stream>>>(tzx, tzy, L, ol, h_count);
     return hipGetLastError();
 }
 

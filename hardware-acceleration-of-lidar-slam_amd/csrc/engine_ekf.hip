@@ -186,8 +186,8 @@ int slam_ekf_update_dev(slam_engine* e, const float* d_map_in, float* d_map_out,
         }
         auto build_list = [&]() -> hipError_t {
             e->obs_list_valid = true;
-            return launch_build_obs_list(e->stream, e->d_obs_zx, e->d_obs_zy, nlandmarks, li, (float*)(li + L),
-                                         (float*)(li + 2 * L), li + 3 * L, li + 4 * L, e->d_hobs);
+            const ObsListOut ol{ li, (float*)(li + L), (float*)(li + 2 * L), li + 3 * L, li + 4 * L };
+            return launch_build_obs_list(e->stream, e->d_obs_zx, e->d_obs_zy, nlandmarks, ol, e->d_hobs);
         };
         if (sparse) {
             if (!e->obs_list_valid) SLAM_HIP_TRY(e, build_list());

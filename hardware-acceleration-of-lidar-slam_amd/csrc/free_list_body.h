@@ -15,10 +15,18 @@ enum { kPoolFree = 0,    // entries in the free list
        kPoolUsed = 1,    // ... of which handed out already
        kPoolRenew = 2,   // this frame: the list is made anew before the update takes from it
        kPoolBase = 3,    // this frame: first entry the update takes
-       kPoolTicket = 4,  // (unused since round 4)
+                         // word 4: unused, always zero — it stays where it is because callers see the words by number
+                         // (slam_pf_paged_device_view)
        kPoolShort = 5,   // set (and never cleared) when a list made anew was shorter than what had been reserved from it
-       kPoolAcc = 6 };   // words 6-7, one 64-bit word: free_list_kernel's running {entries (high), workgroups done (low)}; left at zero
+       kPoolAcc = 6,     // words 6-7, one 64-bit word: free_list_kernel's running {entries (high), workgroups done (low)}; left at zero
+       kPoolStateWords = 8 };
 
+// a list of free_count entries, nothing handed out (one thread)
+__device__ __forceinline__ void pool_state_clear(int32_t* __restrict__ pool_state, int free_count)
+{
+    pool_state[kPoolFree] = free_count;
+    for (int w = kPoolUsed; w < kPoolStateWords; ++w) pool_state[w] = 0;
+}
 
 // ---- free list = pages without the latest stamp (every update stamps every page its new tables name, so at any time the
 // pages in use are exactly those with the stamp of the last update).  Run every frame behind page_list_kernel, it does

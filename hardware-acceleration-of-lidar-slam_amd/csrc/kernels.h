@@ -172,8 +172,19 @@ hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const floa
 // compacted into a list in landmark order (ids, measurements, accumulator rounds; count[2] = {nobs, highest round} on the
 // device, {nobs, L} optionally in mapped host memory), then one lane per observation gathers, updates and scatters.
 constexpr int kObsListMaxLandmarks = 65536;   // the list form keeps a bitmap of the observed landmarks in LDS
-hipError_t launch_build_obs_list(hipStream_t stream, const float* tzx, const float* tzy, int L, int32_t* id, float* zx,
-                                 float* zy, int32_t* round, int32_t* count, int32_t* h_count);
+// the list: ids ascending, measurements, accumulator rounds, {nobs, highest round}
+struct ObsListView {
+    const int32_t* id = nullptr;
+    const float *zx = nullptr, *zy = nullptr;
+    const int32_t* round = nullptr;
+    const int32_t* count = nullptr;
+};
+struct ObsListOut {   // where launch_build_obs_list and launch_page_list leave it (id == nullptr: none wanted)
+    int32_t* id = nullptr;
+    float *zx = nullptr, *zy = nullptr;
+    int32_t *round = nullptr, *count = nullptr;
+};
+hipError_t launch_build_obs_list(hipStream_t stream, const float* tzx, const float* tzy, int L, const ObsListOut& ol, int32_t* h_count);
 hipError_t launch_ekf_sparse(hipStream_t stream, const EkfArgs& a, const int32_t* id, const float* zx, const float* zy,
                              const int32_t* round, const int32_t* count, const EventPair* ev = nullptr);
 // measurement support: rows of 5 x plane_stride floats copied with the update's access shape (slam_profile_copy_ceiling)
@@ -183,18 +194,6 @@ hipError_t launch_selftest_reciprocal(hipStream_t stream, unsigned long long* ou
 
 // ---- paged_kernels.hip: landmark maps as copy-on-write pages of kPageLandmarks landmarks (5 planes x 32 floats = 640 B)
 constexpr int kPageLandmarks = 32;   // 16- and 8-landmark pages measured no faster: profiles/r03_page_sizes.md
-// the compact observation list launch_build_obs_list makes: ids ascending, measurements, accumulator rounds, {nobs, highest round}
-struct ObsListView {
-    const int32_t* id = nullptr;
-    const float *zx = nullptr, *zy = nullptr;
-    const int32_t* round = nullptr;
-    const int32_t* count = nullptr;
-};
-struct ObsListOut {   // where launch_page_list leaves the same list (id == nullptr: none wanted)
-    int32_t* id = nullptr;
-    float *zx = nullptr, *zy = nullptr;
-    int32_t *round = nullptr, *count = nullptr;
-};
 // Where a page lies.  The pages of a session on joint pages are one array of [5][32] floats; the pages of a SPLIT session on
 // pages hold the two planes of MEANS only ([2][32] floats, 256 bytes) and lie in the session's two mean buffers, which are
 // not neighbours in the store: pages below `half_pages` in the first, the others `gap` floats further on.
@@ -202,6 +201,30 @@ struct PageGeom {
     int planes = 5;                          // planes per page (5: means + covariances; 2: means)
     int64_t half_pages = (int64_t)1 << 62;   // pages at or beyond this index lie `gap` floats further on
     int64_t gap = 0;
+};
+// A session's page pool as the launchers off the frame path take it (pf_session.hip: page_pool): by const reference to a
+// launcher, by value to its kernel.  pt is ONE table (the session's current one unless the caller says otherwise).
+struct PagePool {
+    float* pool;           // [npages][geom.planes][32]
+    PageGeom geom;
+    int32_t* pt;           // [rows][nb]
+    int nb;                // pages per particle
+    int32_t* freelist;     // [npages]
+    int npages;
+    int32_t* pool_state;   // pool_state_words() int32, see below
+    uint32_t* stamp;       // [npages]
+    uint32_t stamp_now;    // the stamp of the last update: pages that carry it are in use
+};
+// ... and the covariance classes of a session on the split layout or on split pages (split_kernels.hip; class_store)
+struct ClassStore {
+    float* cov;           // [classes][3][Lp], see EkfArgs
+    float* covx;          // [classes][2][Lp]
+    int32_t* cls;         // [rows] class of every particle (the current buffer)
+    int Lp;               // floats between the planes of a class row
+    uint32_t* cstamp;     // [classes]
+    uint32_t stamp_now;   // the stamp of the last update: classes that carry it are in use
+    int32_t* live;        // the current list of classes in use ...
+    int32_t* cnt;         // ... and its length, one of three rotating words (CovArgs); at the start of an epoch the first of them
 };
 struct PagedEkfArgs {
     PageGeom geom;
@@ -259,31 +282,27 @@ hipError_t launch_free_list(hipStream_t stream, const uint32_t* stamp, int npage
 // out[k] = anc[sel[k]] (anc == nullptr: sel[k])
 hipError_t launch_compose_index(hipStream_t stream, const int32_t* sel, const int32_t* anc, int count, int32_t* out);
 // rows -> pages page_base + j * nb + b behind identity tables; every other page of the pool goes on the free list
-hipError_t launch_pages_from_rows(hipStream_t stream, const float* rows, int64_t row_stride, int plane_stride, int nlandmarks,
-                                  int nb, int n, float* pool, int32_t* pt, int32_t* freelist, int npages, int32_t* pool_state,
-                                  int page_base = 0, const PageGeom& geom = PageGeom());
-hipError_t launch_rows_from_pages(hipStream_t stream, const float* pool, const int32_t* pt, int nb, const int32_t* anc, int n,
-                                  float* rows, int64_t row_stride, int plane_stride, int nlandmarks, const PageGeom& geom = PageGeom());
-hipError_t launch_pages_reset(hipStream_t stream, float* pool, int32_t* pt, int64_t nentries, int32_t* freelist, int npages,
-                              int32_t* pool_state, const PageGeom& geom = PageGeom());
+hipError_t launch_pages_from_rows(hipStream_t stream, const float* rows, int64_t row_stride, int plane_stride, int nlandmarks, int n,
+                                  const PagePool& pp, int page_base = 0);
+// pages of particle anc[i] (or i) -> row i of geom.planes planes
+hipError_t launch_rows_from_pages(hipStream_t stream, const PagePool& pp, const int32_t* anc, int n, float* rows, int64_t row_stride,
+                                  int plane_stride, int nlandmarks);
+// the first nentries table entries name ONE shared page of landmarks "not seen yet" (page 0), the rest of the pool is free
+hipError_t launch_pages_reset(hipStream_t stream, const PagePool& pp, int64_t nentries);
 // split pages -> dense rows of 5 planes (means from the particle's pages of two planes, covariances from its class's rows)
-hipError_t launch_rows_from_split_pages(hipStream_t stream, const float* pool, const PageGeom& geom, const int32_t* pt, int nb,
-                                        const float* cov, const int32_t* cls, int Lp, const int32_t* idx, int count, float* rows,
-                                        int64_t row_stride, int plane_stride, int nlandmarks);
+hipError_t launch_rows_from_split_pages(hipStream_t stream, const PagePool& pp, const ClassStore& cs, const int32_t* idx, int count,
+                                        float* rows, int64_t row_stride, int plane_stride, int nlandmarks);
 // Sharded sessions: `want` pages for the rows about to be unpacked (pool_state then says where in the list they start and
 // whether launch_free_list, to be called behind it, has to make a new list first), and the unpack itself: record p of
-// `in` (pose + 5 x nlandmarks floats, as launch_migrate_pack writes them) -> table row n + p on fresh pages, stamped `live`
+// `in` (pose + 5 x nlandmarks floats, as launch_migrate_pack writes them) -> table row n + p on fresh pages, stamped pp.stamp_now
 hipError_t launch_pool_reserve(hipStream_t stream, int32_t* pool_state, int64_t want);
 // ... for a session on SPLIT PAGES: record p -> its means on fresh pages of two planes behind table row n + p, its covariances (and
 // their determinant terms, meas_var) as class cls_free[cls_first + p] of its own, appended to the list of classes in use
 hipError_t launch_migrate_unpack_split_pages(hipStream_t stream, const float* in, int total, int n, float* pose, int64_t pose_ld,
-                                             float* pool, const PageGeom& geom, int32_t* pt, int nb, int nlandmarks,
-                                             const int32_t* freelist, const int32_t* pool_state, uint32_t* stamp, uint32_t live,
-                                             float* cov, float* covx, int32_t* cls, int Lp, float meas_var, const int32_t* cls_free,
-                                             int cls_first, uint32_t* cstamp, uint32_t cstamp_now, int32_t* live_list, int32_t* live_cnt);
+                                             const PagePool& pp, const ClassStore& cs, int nlandmarks, float meas_var,
+                                             const int32_t* cls_free, int cls_first);
 hipError_t launch_migrate_unpack_paged(hipStream_t stream, const float* in, int total, int n, float* pose, int64_t pose_ld,
-                                       float* pool, int32_t* pt, int nb, int nlandmarks, const int32_t* freelist,
-                                       const int32_t* pool_state, uint32_t* stamp, uint32_t live);
+                                       const PagePool& pp, int nlandmarks);
 
 // ---- split_kernels.hip: the covariance classes of the split layout (see EkfArgs)
 // The posterior covariance of every class that is still in use, in place, once per class: P' = (I - W) P for an observed
@@ -314,20 +333,19 @@ struct CovArgs {
 // rows [n][5][plane_stride_in] (row_stride_in floats apart) -> means [n][2][Lp], classes, class rows [..][3][Lp]: neighbouring
 // particles whose three covariance planes are equal bit for bit share a class (classes are numbered 0, 1, .. in particle
 // order; all particles alike -> one class).  scratch: split_scratch_words(n) int32 words.  live[k] = k, cnt[phase] = number
-// of classes (cnt[other] = 0), every class stamped stamp_now; h_live = {classes, epoch}.
+// of classes (cnt[other] = 0), every class stamped stamp_now; h_live = {classes, epoch}.  A new epoch: cs.live and cs.cnt are
+// the first list and the first of the three counts.
 size_t split_scratch_words(int n);
 // covx (written by a second launch, so that it may lie where the rows came from): the determinant terms of every class.
 hipError_t launch_split_from_rows(hipStream_t stream, const float* rows, int64_t row_stride_in, int plane_stride_in, int nlandmarks,
-                                  int n, int Lp, float* mean, float* cov, float* covx, float meas_var, int32_t* cls, int32_t* live,
-                                  int32_t* cnt, int phase, uint32_t* cstamp, uint32_t stamp_now, int32_t* h_live, uint32_t epoch,
-                                  void* scratch);
+                                  int n, float* mean, const ClassStore& cs, float meas_var, int32_t* h_live, uint32_t epoch, void* scratch);
 // out row k = [means of particle idx[k] (or k) | the covariance planes of its class], nlandmarks columns of each plane
-hipError_t launch_rows_from_split(hipStream_t stream, const float* mean, const float* cov, const int32_t* cls, int Lp,
-                                  const int32_t* idx, int count, float* rows, int64_t row_stride, int plane_stride, int nlandmarks);
+hipError_t launch_rows_from_split(hipStream_t stream, const float* mean, const ClassStore& cs, const int32_t* idx, int count,
+                                  float* rows, int64_t row_stride, int plane_stride, int nlandmarks);
 // Sharded sessions on the split layout.  A migrating particle travels as the same record whatever the layouts of the two ranks
 // (pose, then five planes of nlandmarks values): launch_migrate_pack(.., split_cov, split_cls) reads it from the means and the
 // class's covariance row, and this launch puts record p of `in` into staging row n + p of the means, with a class of its own —
-// first_class + p, covariance planes and determinant terms filled in, appended to the list of classes in use (live[*cnt ..)).
+// freelist[first + p], covariance planes and determinant terms filled in, appended to the list of classes in use (live[*cnt ..)).
 // Class numbers for the arrivals come from a free list on the device: the classes no current particle belongs to, i.e. whose
 // stamp is older than `min_live` — the stamp of the last update whose particles are the current ones.  At most n classes are in
 // use and there are n + staging rows of them, so a list made anew holds at least as many numbers as a rank has staging rows,
@@ -336,20 +354,17 @@ hipError_t launch_rows_from_split(hipStream_t stream, const float* mean, const f
 //   fs: two int32 words on the device, zero before the first launch and zero again behind every launch.
 hipError_t launch_class_free_list(hipStream_t stream, const uint32_t* cstamp, int nclasses, uint32_t min_live, int32_t* freelist,
                                   int32_t* fs);
-// the arrivals' classes are stamped `stamp` (= min_live: in use until the next update has said which of them have offspring)
+// the arrivals' classes are stamped cs.stamp_now (= min_live: in use until the next update has said which of them have offspring)
 hipError_t launch_migrate_unpack_split(hipStream_t stream, const float* in, int total, int n, float* pose, int64_t pose_ld, float* mean,
-                                       float* cov, float* covx, int32_t* cls, int Lp, int nlandmarks, float meas_var,
-                                       const int32_t* freelist, int first, uint32_t* cstamp, uint32_t stamp, int32_t* live,
-                                       int32_t* cnt);
+                                       const ClassStore& cs, int nlandmarks, float meas_var, const int32_t* freelist, int first);
 // a frame without a landmark update: means and classes follow their particles (out[i] = in[anc[i]])
 hipError_t launch_split_gather(hipStream_t stream, const float* mean_in, float* mean_out, const int32_t* cls_in, int32_t* cls_out,
                                int Lp, const int32_t* anc, int n, uint32_t* cstamp, uint32_t stamp_now);
 // the classes alone follow their particles (split pages: the means follow through the page tables)
 hipError_t launch_class_gather(hipStream_t stream, const int32_t* cls_in, int32_t* cls_out, const int32_t* anc, int n, uint32_t* cstamp,
                                uint32_t stamp_now);
-// every particle: all landmarks "not seen yet", one class
-hipError_t launch_split_reset(hipStream_t stream, float* mean, float* cov, float* covx, int32_t* cls, int Lp, int n, int32_t* live,
-                              int32_t* cnt, int phase, uint32_t* cstamp, uint32_t stamp_now, int32_t* h_live, uint32_t epoch);
+// every particle: all landmarks "not seen yet", one class (a new epoch, as launch_split_from_rows)
+hipError_t launch_split_reset(hipStream_t stream, float* mean, const ClassStore& cs, int n, int32_t* h_live, uint32_t epoch);
 
 // ---- resample_kernels.hip (rows A11-A12; no reference counterpart): weights, resampling on one GPU, results and gathers
 // carry / prev_resampled (optional): see logweight_kernel — the weights a frame without resample left behind

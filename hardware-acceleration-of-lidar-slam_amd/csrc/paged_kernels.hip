@@ -22,7 +22,8 @@
 #include "det_math.h"
 #include "ekf_math.h"
 #include "free_list_body.h"
-#include "kernels.h"
+#include "pf_common.h"
+#include "storage_bodies.h"
 
 namespace slam {
 
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(1024) void page_list_kernel(const float* __restrict
                                                          int32_t* __restrict__ h_touched, ObsListOut ol)
 {
     // ol.id != nullptr (L <= kObsListMaxLandmarks): the same pass also makes the compact observation list of
-    // build_obs_list_kernel (ekf_kernels.hip) — ids ascending, measurements, accumulator rounds, {count, highest round}
+    // build_obs_list_kernel (ekf_kernels.hip) with the same step (storage_bodies.h)
     __shared__ unsigned s_bits[kObsListMaxLandmarks / 32];
     __shared__ int s_wave[16], s_wobs[16];
     __shared__ int s_base, s_obase, s_max_round;
@@ -117,10 +118,7 @@ __global__ __launch_bounds__(1024) void page_list_kernel(const float* __restrict
             vy = zy[l];
         }
         const unsigned long long m = __ballot(ob);
-        if (ol.id) {
-            if (lane == 0) s_bits[(l0 >> 5) + 2 * wave] = (unsigned)m;
-            if (lane == 32) s_bits[(l0 >> 5) + 2 * wave + 1] = (unsigned)(m >> 32);
-        }
+        obs_list_mark(m, l0, s_wobs, ol.id ? s_bits : nullptr);
         int touched_before = 0, touched_mine = 0, touched_all = 0;   // pages of this wavefront: below mine / mine / all
 #pragma unroll
         for (int g = 0; g < kPerWave; ++g) {
@@ -129,16 +127,11 @@ __global__ __launch_bounds__(1024) void page_list_kernel(const float* __restrict
             if (g < lane / kPage) touched_before += tg;
             if (g == lane / kPage) touched_mine = tg;
         }
-        if (lane == 0) {
-            s_wave[wave] = touched_all;
-            s_wobs[wave] = __popcll(m);
-        }
+        if (lane == 0) s_wave[wave] = touched_all;
         __syncthreads();
-        int off = s_base, ooff = s_obase;
-        for (int w = 0; w < wave; ++w) {
-            off += s_wave[w];
-            ooff += s_wobs[w];
-        }
+        const int ooff = obs_list_step(m, ob, l, vx, vy, s_wobs, s_obase, s_bits, ol, &s_max_round);
+        int off = s_base;
+        for (int w = 0; w < wave; ++w) off += s_wave[w];
         const int b = l0 / kPage + kPerWave * wave + lane / kPage;
         if (lane % kPage == 0 && b < nb) {
             const int t = off + touched_before;
@@ -149,17 +142,6 @@ __global__ __launch_bounds__(1024) void page_list_kernel(const float* __restrict
                 tmask[t] = (int32_t)(uint32_t)(m >> (g * kPage) & kMask);
                 tbase[t] = ooff + __popcll(m & ((1ull << (g * kPage)) - 1ull));   // observations in the pages before this one
             }
-        }
-        if (ol.id && ob) {
-            const int k = ooff + __popcll(m & ((1ull << lane) - 1ull));
-            ol.id[k] = l;
-            ol.zx[k] = vx;
-            ol.zy[k] = vy;
-            // round: earlier observed landmarks with the same l mod 128 = the same bit of every fourth word below
-            int r = 0;
-            for (int b2 = l - 128; b2 >= 0; b2 -= 128) r += (int)((s_bits[b2 >> 5] >> (b2 & 31)) & 1u);
-            ol.round[k] = r;
-            if (r > 0) atomicMax(&s_max_round, r);
         }
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -208,126 +190,162 @@ __global__ __launch_bounds__(1024) void obs_count_kernel(const float* __restrict
 
 __global__ void pool_reserve_kernel(int32_t* __restrict__ pool_state, int64_t want) { pool_reserve(pool_state, want); }
 
-// Received rows -> fresh pages behind table rows n .. n + total - 1 (one workgroup per record).  The pages get the stamp
-// of the last update: they are in use from now on, whatever a free list made before the next update finds.
+// A received record's pose -> staging slot n + p, and table row n + p: nb fresh pages from the reserved part of the free
+// list, stamped like those of the last update — in use from now on, whatever a free list made before the next update
+// finds.  One workgroup of 256 threads; returns the row's pages.
+__device__ __forceinline__ const int32_t* unpack_pose_and_table(const float* __restrict__ rec, int p, int n, float* __restrict__ pose,
+                                                                int64_t pose_ld, const PagePool& pp)
+{
+    if (threadIdx.x < 3) pose[threadIdx.x * pose_ld + n + p] = rec[threadIdx.x];
+    const int32_t* __restrict__ mine = pp.freelist + pp.pool_state[kPoolBase] + (int64_t)p * pp.nb;
+    for (int b = threadIdx.x; b < pp.nb; b += 256) {
+        pp.pt[(int64_t)(n + p) * pp.nb + b] = mine[b];
+        pp.stamp[mine[b]] = pp.stamp_now;
+    }
+    return mine;
+}
+
+// Received rows -> fresh pages behind table rows n .. n + total - 1 (one workgroup per record)
 __global__ __launch_bounds__(256) void migrate_unpack_paged_kernel(const float* __restrict__ in, int total, int n,
-                                                                   float* __restrict__ pose, int64_t pose_ld,
-                                                                   float* __restrict__ pool, int32_t* __restrict__ pt, int nb,
-                                                                   int nlandmarks, const int32_t* __restrict__ freelist,
-                                                                   const int32_t* __restrict__ pool_state,
-                                                                   uint32_t* __restrict__ stamp, uint32_t live)
+                                                                   float* __restrict__ pose, int64_t pose_ld, PagePool pp, int nlandmarks)
 {
     const int p = blockIdx.x;
     if (p >= total) return;
     const float* __restrict__ rec = in + (int64_t)(3 + 5 * nlandmarks) * p;
-    if (threadIdx.x < 3) pose[threadIdx.x * pose_ld + n + p] = rec[threadIdx.x];
-    const int32_t* __restrict__ mine = freelist + pool_state[kPoolBase] + (int64_t)p * nb;
-    for (int b = threadIdx.x; b < nb; b += 256) {
-        pt[(int64_t)(n + p) * nb + b] = mine[b];
-        stamp[mine[b]] = live;
-    }
+    const int32_t* __restrict__ mine = unpack_pose_and_table(rec, p, n, pose, pose_ld, pp);
     for (int pl = 0; pl < 5; ++pl)
-        for (int l = threadIdx.x; l < nb * kPage; l += 256)   // the tail of the last page: landmarks that do not exist
-            pool[(int64_t)mine[l / kPage] * kPageFloats + pl * kPage + l % kPage] =
+        for (int l = threadIdx.x; l < pp.nb * kPage; l += 256)   // the tail of the last page: landmarks that do not exist
+            pp.pool[(int64_t)mine[l / kPage] * kPageFloats + pl * kPage + l % kPage] =
                 l < nlandmarks ? rec[3 + pl * nlandmarks + l] : (pl == 2 ? -1.0f : 0.0f);
 }
 
 // ... on split pages: the means on fresh pages of two planes, the covariances as a class of its own (what
 // migrate_unpack_split_kernel of split_kernels.hip does with them)
 __global__ __launch_bounds__(256) void migrate_unpack_split_pages_kernel(const float* __restrict__ in, int total, int n,
-                                                                         float* __restrict__ pose, int64_t pose_ld,
-                                                                         float* __restrict__ pool, PageGeom geom, int32_t* __restrict__ pt,
-                                                                         int nb, int nlandmarks, const int32_t* __restrict__ freelist,
-                                                                         const int32_t* __restrict__ pool_state,
-                                                                         uint32_t* __restrict__ stamp, uint32_t live, float* __restrict__ cov,
-                                                                         float* __restrict__ covx, int32_t* __restrict__ cls, int Lp, float q,
-                                                                         const int32_t* __restrict__ cls_free, int cls_first,
-                                                                         uint32_t* __restrict__ cstamp, uint32_t cstamp_now,
-                                                                         int32_t* __restrict__ live_list, int32_t* __restrict__ live_cnt)
+                                                                         float* __restrict__ pose, int64_t pose_ld, PagePool pp,
+                                                                         ClassStore cs, int nlandmarks, float q,
+                                                                         const int32_t* __restrict__ cls_free, int cls_first)
 {
     const int p = blockIdx.x;
     if (p >= total) return;
     const float* __restrict__ rec = in + (int64_t)(3 + 5 * nlandmarks) * p;
-    if (threadIdx.x < 3) pose[threadIdx.x * pose_ld + n + p] = rec[threadIdx.x];
-    const int32_t* __restrict__ mine = freelist + pool_state[kPoolBase] + (int64_t)p * nb;
-    for (int b = threadIdx.x; b < nb; b += 256) {
-        pt[(int64_t)(n + p) * nb + b] = mine[b];
-        stamp[mine[b]] = live;
+    const int32_t* __restrict__ mine = unpack_pose_and_table(rec, p, n, pose, pose_ld, pp);
+    for (int l = threadIdx.x; l < pp.nb * kPage; l += 256) {   // (nb * kPage = Lp; the tail of the last page: landmarks that do not exist)
+        float* __restrict__ pg = pp.pool + page_off(pp.geom, mine[l / kPage]) + l % kPage;
+        pg[0] = l < nlandmarks ? rec[3 + l] : 0.0f;
+        pg[kPage] = l < nlandmarks ? rec[3 + nlandmarks + l] : 0.0f;
     }
-    const int c = cls_free[cls_first + p];
-    float* __restrict__ cr = cov + (int64_t)c * 3 * Lp;
-    float* __restrict__ xr = covx + (int64_t)c * 2 * Lp;
-    for (int l = threadIdx.x; l < nb * kPage; l += 256) {   // (nb * kPage = Lp; the tail of the last page: landmarks that do not exist)
-        const bool in_row = l < nlandmarks;
-        float* __restrict__ pg = pool + page_off(geom, mine[l / kPage]) + l % kPage;
-        pg[0] = in_row ? rec[3 + l] : 0.0f;
-        pg[kPage] = in_row ? rec[3 + nlandmarks + l] : 0.0f;
-        const float pxx = in_row ? rec[3 + 2 * nlandmarks + l] : 1.0f, pxy = in_row ? rec[3 + 3 * nlandmarks + l] : 0.0f,
-                    pyy = in_row ? rec[3 + 4 * nlandmarks + l] : 1.0f;
-        cr[l] = pxx;
-        cr[Lp + l] = pxy;
-        cr[2 * Lp + l] = pyy;
-        float idet = 1.0f, hl = 0.0f;
-        if (in_row && !(pxx < 0.0f)) ekf_det_terms<float>(pxx, pxy, pyy, q, idet, hl);
-        xr[l] = idet;
-        xr[Lp + l] = hl;
+    unpack_class(rec, nlandmarks, q, cls_free[cls_first + p], n + p, cs);
+}
+
+// ---- What both forms of the paged update do around their page loop.  HALF a wavefront = one particle (kPage lanes = the
+// landmarks of a page); before the loop a lane knows:
+struct PagedLane {
+    int lane, wave, half, slot;   // `half`: this lane's particle of the wavefront, `slot`: its landmark of a page
+    bool alive;                   // the upper half of the last wavefront may have no particle: it stores nothing
+    int i, src, T;                // particle (clamped), its ancestor, touched pages of the frame
+    const int32_t* row_in;        // the ancestor's table row
+    int32_t* row_out;             // this particle's
+    const int32_t* fresh;         // this particle's T fresh pages
+    int cls;                      // SPLIT: the class, and its rows
+    const float *crow, *xrow;
+    float s, c, px, py, q;        // the pose, meas_var
+    float* acc;                   // the particle's 128 log-likelihood accumulators, zeroed
+};
+
+// Fills p; false: the wavefront has no particle at all.  Also (1) the particle's new table row — the ancestor's entries, fresh
+// pages for the touched ones, every named page stamped — and (2) SPLIT: a page holds the means only; the covariances are the
+// class's (split_kernels.hip), which follows the particle and is still in use.
+template <bool SPLIT>
+__device__ __forceinline__ bool paged_begin(const PagedEkfArgs& a, float (*s_acc)[64 / kPage][128], PagedLane& p)
+{
+    constexpr int kGroups = 64 / kPage;   // particles per wavefront
+    p.lane = threadIdx.x & 63;
+    p.wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    p.half = p.lane / kPage;
+    p.slot = p.lane % kPage;
+    const int first_of_wave = ((int)blockIdx.x * kWaves + p.wave) * kGroups;
+    const int i_raw = first_of_wave + p.half;
+    if (first_of_wave >= a.n) return false;
+    p.alive = i_raw < a.n;
+    p.i = p.alive ? i_raw : a.n - 1;
+    p.src = a.anc ? a.anc[p.i] : p.i;
+    p.T = __builtin_amdgcn_readfirstlane(a.count[0]);
+    p.row_in = a.pt_in + (int64_t)p.src * a.nb;
+    p.row_out = a.pt_out + (int64_t)p.i * a.nb;
+    const int fbase = __builtin_amdgcn_readfirstlane(a.pool_state[kPoolBase]);
+    p.fresh = a.freelist + fbase + (int64_t)p.i * p.T;
+    if (p.alive)
+        for (int b = p.slot; b < a.nb; b += kPage) {
+            const int t = a.tindex[b];
+            const int32_t page = t < 0 ? p.row_in[b] : p.fresh[t];
+            p.row_out[b] = page;
+            a.stamp[page] = a.stamp_now;   // named by a table of this frame (same value from every writer)
+        }
+    p.cls = 0;
+    if constexpr (SPLIT) {
+        p.cls = a.cls_in[p.src];
+        if (p.alive && p.slot == 0) {
+            a.cls_out[p.i] = p.cls;
+            a.cstamp[p.cls] = a.cstamp_now;
+        }
     }
-    if (threadIdx.x == 0) {
-        cls[n + p] = c;
-        cstamp[c] = cstamp_now;
-        live_list[atomicAdd(live_cnt, 1)] = c;
+    p.crow = SPLIT ? a.cov + (int64_t)p.cls * 3 * a.plane_stride : nullptr;
+    p.xrow = SPLIT ? a.covx + (int64_t)p.cls * 2 * a.plane_stride : nullptr;
+    float st, ct;
+    det_sincosf(a.th[p.i], st, ct);
+    p.s = st;
+    p.c = ct;
+    p.px = a.x[p.i];
+    p.py = a.y[p.i];
+    p.q = a.meas_var;
+    p.acc = s_acc[p.wave][p.half];
+#pragma unroll
+    for (int k = 0; k < 128 / kPage; ++k) p.acc[p.slot + kPage * k] = 0.0f;
+    return true;
+}
+
+// The specification's reduction — t[j] = acc[j] + acc[j + 64], then t[j] += t[j ^ s] for s = 1 .. 32 — on kPage lanes: a
+// lane holds t[slot + kPage m]; the steps s < kPage run across the lanes on each of them, the steps s >= kPage pair
+// them inside the lane (a + b is the same float either way round).  Then the particle's log-likelihood goes out.
+__device__ __forceinline__ void page_sum_store(const PagedEkfArgs& a, const PagedLane& p)
+{
+    float u[64 / kPage];
+#pragma unroll
+    for (int m = 0; m < 64 / kPage; ++m) u[m] = p.acc[p.slot + kPage * m] + p.acc[p.slot + kPage * m + 64];
+#pragma unroll
+    for (int sft = 1; sft < kPage; sft <<= 1)
+#pragma unroll
+        for (int m = 0; m < 64 / kPage; ++m) u[m] = u[m] + __shfl_xor(u[m], sft, 64);
+#pragma unroll
+    for (int w = 1; w < 64 / kPage; w <<= 1)
+#pragma unroll
+        for (int m = 0; m < 64 / kPage; m += 2 * w) u[m] = u[m] + u[m + w];
+    if (p.slot == 0 && p.alive) {
+        a.loglik[p.i] = u[0];
+        if (a.loglik_user) a.loglik_user[p.i] = u[0];
     }
 }
 
-// HALF a wavefront = one particle (32 lanes = the 32 landmarks of a page).  (1) its new page-table row: the ancestor's
-// entries, fresh pages for the touched ones, every named page stamped; (2) the touched pages one after the other.  A
+// The page-wide form: the touched pages one after the other, every lane of a page runs the update.  A
 // particle's work is a handful of dependent round trips (ancestor -> table -> page -> store) and little else, so the
 // kernel's time is the number of wavefronts times those round trips: two particles per wavefront halve it (one particle
 // per wavefront, two pages per pass: 91 us at 64k x 500 with 32 observed).
 template <bool SPLIT>
 __global__ __launch_bounds__(kWaves * 64) void ekf_paged_kernel(PagedEkfArgs a)
 {
-    constexpr int kGroups = 64 / kPage;          // particles per wavefront: kPage lanes = the landmarks of a page
     constexpr int kAccPages = 128 / kPage;       // pages per round of the 128 log-likelihood accumulators
-    __shared__ float s_acc[kWaves][kGroups][128];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int half = lane / kPage, slot = lane % kPage;   // `half`: this lane's particle of the wavefront
-    const int first_of_wave = ((int)blockIdx.x * kWaves + wave) * kGroups;
-    const int i_raw = first_of_wave + half;
-    if (first_of_wave >= a.n) return;
-    const bool alive = i_raw < a.n;            // the upper half of the last wavefront may have no particle: it stores nothing
-    const int i = alive ? i_raw : a.n - 1;
-    const int src = a.anc ? a.anc[i] : i;
-    const int T = __builtin_amdgcn_readfirstlane(a.count[0]);
-    const int32_t* __restrict__ row_in = a.pt_in + (int64_t)src * a.nb;
-    int32_t* __restrict__ row_out = a.pt_out + (int64_t)i * a.nb;
-    const int fbase = __builtin_amdgcn_readfirstlane(a.pool_state[kPoolBase]);
-    const int32_t* __restrict__ fresh = a.freelist + fbase + (int64_t)i * T;   // this particle's T fresh pages
-    if (alive)
-        for (int b = slot; b < a.nb; b += kPage) {
-            const int t = a.tindex[b];
-            const int32_t page = t < 0 ? row_in[b] : fresh[t];
-            row_out[b] = page;
-            a.stamp[page] = a.stamp_now;   // named by a table of this frame (same value from every writer)
-        }
-    // SPLIT: a page holds the means only; the covariances are the class's (split_kernels.hip), which follows the particle
-    int cls = 0;
-    if constexpr (SPLIT) {
-        cls = a.cls_in[src];
-        if (alive && slot == 0) {
-            a.cls_out[i] = cls;
-            a.cstamp[cls] = a.cstamp_now;
-        }
-    }
-    const float* __restrict__ crow = SPLIT ? a.cov + (int64_t)cls * 3 * a.plane_stride : nullptr;
-    const float* __restrict__ xrow = SPLIT ? a.covx + (int64_t)cls * 2 * a.plane_stride : nullptr;
-    float st, ct;
-    det_sincosf(a.th[i], st, ct);
-    const float s = st, c = ct, px = a.x[i], py = a.y[i], q = a.meas_var;
-    float* acc = s_acc[wave][half];
-#pragma unroll
-    for (int k = 0; k < kAccPages; ++k) acc[slot + kPage * k] = 0.0f;
+    __shared__ float s_acc[kWaves][64 / kPage][128];
+    PagedLane p;
+    if (!paged_begin<SPLIT>(a, s_acc, p)) return;
+    const int half = p.half, slot = p.slot, T = p.T;
+    const bool alive = p.alive;
+    const int32_t* __restrict__ row_in = p.row_in;
+    const int32_t* __restrict__ fresh = p.fresh;
+    const float* __restrict__ crow = p.crow;
+    const float* __restrict__ xrow = p.xrow;
+    const float s = p.s, c = p.c, px = p.px, py = p.py, q = p.q;
+    float* acc = p.acc;
     for (int c0 = 0; c0 < T; c0 += kPage) {   // kPage touched pages at a time: lane t of the group holds what page c0 + t needs
         const int tl = c0 + slot < T ? c0 + slot : T - 1;
         const int my_b = a.tpage[tl];
@@ -382,25 +400,7 @@ __global__ __launch_bounds__(kWaves * 64) void ekf_paged_kernel(PagedEkfArgs a)
             if (ob) acc[k] = acc[k] + term;
         }
     }
-    // the specification's reduction — t[j] = acc[j] + acc[j + 64], then t[j] += t[j ^ s] for s = 1 .. 32 — on kPage lanes: a
-    // lane holds t[slot + kPage m]; the steps s < kPage run across the lanes on each of them, the steps s >= kPage pair
-    // them inside the lane (a + b is the same float either way round)
-    float u[64 / kPage];
-#pragma unroll
-    for (int m = 0; m < 64 / kPage; ++m) u[m] = acc[slot + kPage * m] + acc[slot + kPage * m + 64];
-#pragma unroll
-    for (int sft = 1; sft < kPage; sft <<= 1)
-#pragma unroll
-        for (int m = 0; m < 64 / kPage; ++m) u[m] = u[m] + __shfl_xor(u[m], sft, 64);
-#pragma unroll
-    for (int w = 1; w < 64 / kPage; w <<= 1)
-#pragma unroll
-        for (int m = 0; m < 64 / kPage; m += 2 * w) u[m] = u[m] + u[m + w];
-    const float total = u[0];
-    if (slot == 0 && alive) {
-        a.loglik[i] = total;
-        if (a.loglik_user) a.loglik_user[i] = total;
-    }
+    page_sum_store(a, p);
 }
 
 // ---- the list form of the paged update, touched pages staged in LDS (same bits): (a) the table row; then, PG touched pages
@@ -414,52 +414,23 @@ __global__ __launch_bounds__(kWaves * 64) void ekf_paged_kernel(PagedEkfArgs a)
 template <int PG, bool SPLIT>
 __global__ __launch_bounds__(kWaves * 64) void ekf_paged_lds_kernel(PagedEkfArgs a)
 {
-    constexpr int kGroups = 64 / kPage;
     constexpr int PL = SPLIT ? 2 : 5;                // planes per page
     __shared__ float s_img[kWaves][PG][PL][64];      // [page of the chunk][plane][lane]: lane = particle of the wavefront x slot
-    __shared__ float s_acc[kWaves][kGroups][128];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int half = lane / kPage, slot = lane % kPage;
-    const int first_of_wave = ((int)blockIdx.x * kWaves + wave) * kGroups;
-    const int i_raw = first_of_wave + half;
-    if (first_of_wave >= a.n) return;
-    const bool alive = i_raw < a.n;
-    const int i = alive ? i_raw : a.n - 1;
-    const int src = a.anc ? a.anc[i] : i;
-    const int T = __builtin_amdgcn_readfirstlane(a.count[0]);
+    __shared__ float s_acc[kWaves][64 / kPage][128];
+    PagedLane p;
+    if (!paged_begin<SPLIT>(a, s_acc, p)) return;
+    const int lane = p.lane, half = p.half, slot = p.slot, T = p.T;
+    const bool alive = p.alive;
+    const int32_t* __restrict__ row_in = p.row_in;
+    const int32_t* __restrict__ fresh = p.fresh;
+    const float* __restrict__ crow = p.crow;
+    const float* __restrict__ xrow = p.xrow;
+    const float s = p.s, c = p.c, px = p.px, py = p.py, q = p.q;
+    float* acc = p.acc;
     const int max_round = __builtin_amdgcn_readfirstlane(a.ol.count[1]);
-    const int32_t* __restrict__ row_in = a.pt_in + (int64_t)src * a.nb;
-    int32_t* __restrict__ row_out = a.pt_out + (int64_t)i * a.nb;
-    const int fbase = __builtin_amdgcn_readfirstlane(a.pool_state[kPoolBase]);
-    const int32_t* __restrict__ fresh = a.freelist + fbase + (int64_t)i * T;
     const float* __restrict__ pool_in = a.pool;   // pages named by the ancestors' tables: read only
     float* __restrict__ pool_out = a.pool;        // fresh pages: written only (never one of the above)
-    float(*img)[PL][64] = s_img[wave];
-
-    if (alive)
-        for (int b = slot; b < a.nb; b += kPage) {
-            const int t = a.tindex[b];
-            const int32_t page = t < 0 ? row_in[b] : fresh[t];
-            row_out[b] = page;
-            a.stamp[page] = a.stamp_now;
-        }
-    int cls = 0;
-    if constexpr (SPLIT) {   // the class follows the particle and is still in use
-        cls = a.cls_in[src];
-        if (alive && slot == 0) {
-            a.cls_out[i] = cls;
-            a.cstamp[cls] = a.cstamp_now;
-        }
-    }
-    const float* __restrict__ crow = SPLIT ? a.cov + (int64_t)cls * 3 * a.plane_stride : nullptr;
-    const float* __restrict__ xrow = SPLIT ? a.covx + (int64_t)cls * 2 * a.plane_stride : nullptr;
-    float st, ct;
-    det_sincosf(a.th[i], st, ct);
-    const float s = st, c = ct, px = a.x[i], py = a.y[i], q = a.meas_var;
-    float* acc = s_acc[wave][half];
-#pragma unroll
-    for (int k = 0; k < 128 / kPage; ++k) acc[slot + kPage * k] = 0.0f;
+    float(*img)[PL][64] = s_img[p.wave];
 
     for (int c0 = 0; c0 < T; c0 += PG) {
         const int tc = T - c0 < PG ? T - c0 : PG;   // wave-uniform
@@ -533,22 +504,7 @@ __global__ __launch_bounds__(kWaves * 64) void ekf_paged_lds_kernel(PagedEkfArgs
             }
         __builtin_amdgcn_wave_barrier();
     }
-    float u2[64 / kPage];
-#pragma unroll
-    for (int m = 0; m < 64 / kPage; ++m) u2[m] = acc[slot + kPage * m] + acc[slot + kPage * m + 64];
-#pragma unroll
-    for (int sft = 1; sft < kPage; sft <<= 1)
-#pragma unroll
-        for (int m = 0; m < 64 / kPage; ++m) u2[m] = u2[m] + __shfl_xor(u2[m], sft, 64);
-#pragma unroll
-    for (int w = 1; w < 64 / kPage; w <<= 1)
-#pragma unroll
-        for (int m = 0; m < 64 / kPage; m += 2 * w) u2[m] = u2[m] + u2[m + w];
-    const float total = u2[0];
-    if (slot == 0 && alive) {
-        a.loglik[i] = total;
-        if (a.loglik_user) a.loglik_user[i] = total;
-    }
+    page_sum_store(a, p);
 }
 
 // A frame without observations: the tables follow their particles, nothing else moves.  Every page the new tables name
@@ -579,83 +535,68 @@ __global__ __launch_bounds__(256) void free_list_kernel(const uint32_t* __restri
 }
 
 // ---- rows <-> pages (set / get of whole maps; not on the frame path)
-// rows [n][5][plane_stride] -> pages page_base + j * nb + b (the identity table, shifted)
+// rows [n][planes][plane_stride] -> pages page_base + j * nb + b (the identity table, shifted)
 __global__ __launch_bounds__(256) void pages_from_rows_kernel(const float* __restrict__ rows, int64_t row_stride, int plane_stride,
-                                                              int nlandmarks, int nb, int n, float* __restrict__ pool,
-                                                              int32_t* __restrict__ pt, int page_base, PageGeom geom)
+                                                              int nlandmarks, int n, PagePool pp, int page_base)
 {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;   // one thread per (particle, page, slot)
-    if (idx >= (int64_t)n * nb * kPage) return;
+    if (idx >= (int64_t)n * pp.nb * kPage) return;
     const int slot = (int)(idx % kPage);
     const int64_t pb = idx / kPage;
-    const int b = (int)(pb % nb), i = (int)(pb / nb);
+    const int b = (int)(pb % pp.nb), i = (int)(pb / pp.nb);
     const int l = b * kPage + slot;
     const float* r = rows + (int64_t)i * row_stride;
-    float* pg = pool + page_off(geom, pb + page_base) + slot;
-    for (int p = 0; p < geom.planes; ++p) pg[p * kPage] = l < nlandmarks ? r[(int64_t)p * plane_stride + l] : (p == 2 ? -1.0f : 0.0f);
-    if (slot == 0) pt[pb] = (int32_t)pb + page_base;
+    float* pg = pp.pool + page_off(pp.geom, pb + page_base) + slot;
+    for (int p = 0; p < pp.geom.planes; ++p) pg[p * kPage] = l < nlandmarks ? r[(int64_t)p * plane_stride + l] : (p == 2 ? -1.0f : 0.0f);
+    if (slot == 0) pp.pt[pb] = (int32_t)pb + page_base;
 }
 
 // pages of particle anc[i] (or i) -> row i
-__global__ __launch_bounds__(256) void rows_from_pages_kernel(const float* __restrict__ pool, const int32_t* __restrict__ pt,
-                                                              int nb, const int32_t* __restrict__ anc, int n,
-                                                              float* __restrict__ rows, int64_t row_stride, int plane_stride,
-                                                              int nlandmarks, PageGeom geom)
+__global__ __launch_bounds__(256) void rows_from_pages_kernel(PagePool pp, const int32_t* __restrict__ anc, int n, float* __restrict__ rows,
+                                                              int64_t row_stride, int plane_stride, int nlandmarks)
 {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (int64_t)n * nb * kPage) return;
+    if (idx >= (int64_t)n * pp.nb * kPage) return;
     const int slot = (int)(idx % kPage);
     const int64_t pb = idx / kPage;
-    const int b = (int)(pb % nb), i = (int)(pb / nb);
+    const int b = (int)(pb % pp.nb), i = (int)(pb / pp.nb);
     const int l = b * kPage + slot;
     if (l >= nlandmarks) return;
     const int src = anc ? anc[i] : i;
-    const float* pg = pool + page_off(geom, pt[(int64_t)src * nb + b]) + slot;
+    const float* pg = pp.pool + page_off(pp.geom, pp.pt[(int64_t)src * pp.nb + b]) + slot;
     float* r = rows + (int64_t)i * row_stride;
-    for (int p = 0; p < geom.planes; ++p) r[(int64_t)p * plane_stride + l] = pg[p * kPage];
+    for (int p = 0; p < pp.geom.planes; ++p) r[(int64_t)p * plane_stride + l] = pg[p * kPage];
 }
 
 // split session on pages -> rows of five planes (one workgroup per output row)
-__global__ __launch_bounds__(256) void rows_from_split_pages_kernel(const float* __restrict__ pool, PageGeom geom,
-                                                                    const int32_t* __restrict__ pt, int nb, const float* __restrict__ cov,
-                                                                    const int32_t* __restrict__ cls, int Lp, const int32_t* __restrict__ idx,
-                                                                    int count, float* __restrict__ rows, int64_t row_stride,
-                                                                    int plane_stride, int nlandmarks)
+__global__ __launch_bounds__(256) void rows_from_split_pages_kernel(PagePool pp, ClassStore cs, const int32_t* __restrict__ idx, int count,
+                                                                    float* __restrict__ rows, int64_t row_stride, int plane_stride,
+                                                                    int nlandmarks)
 {
     const int k = blockIdx.x;
     if (k >= count) return;
     const int src = idx ? idx[k] : k;
-    const int32_t* tab = pt + (int64_t)src * nb;
-    const float* cr = cov + (int64_t)cls[src] * 3 * Lp;
+    const int32_t* tab = pp.pt + (int64_t)src * pp.nb;
+    const float* cr = cs.cov + (int64_t)cs.cls[src] * 3 * cs.Lp;
     float* r = rows + (int64_t)k * row_stride;
     for (int l = threadIdx.x; l < nlandmarks; l += 256) {
-        const float* pg = pool + page_off(geom, tab[l / kPage]) + l % kPage;
+        const float* pg = pp.pool + page_off(pp.geom, tab[l / kPage]) + l % kPage;
         r[l] = pg[0];
         r[(int64_t)plane_stride + l] = pg[kPage];
         r[2 * (int64_t)plane_stride + l] = cr[l];
-        r[3 * (int64_t)plane_stride + l] = cr[Lp + l];
-        r[4 * (int64_t)plane_stride + l] = cr[2 * Lp + l];
+        r[3 * (int64_t)plane_stride + l] = cr[cs.Lp + l];
+        r[4 * (int64_t)plane_stride + l] = cr[2 * cs.Lp + l];
     }
 }
 
 // every particle starts on ONE shared page of landmarks "not seen yet" (page 0), the rest of the pool is free
-__global__ __launch_bounds__(256) void pages_reset_kernel(float* __restrict__ pool, int32_t* __restrict__ pt, int64_t nentries,
-                                                          int32_t* __restrict__ freelist, int npages,
-                                                          int32_t* __restrict__ pool_state, int planes)
+__global__ __launch_bounds__(256) void pages_reset_kernel(PagePool pp, int64_t nentries)
 {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx < planes * kPage) pool[idx] = (idx / kPage == 2) ? -1.0f : 0.0f;
-    if (idx < nentries) pt[idx] = 0;
-    if (idx < npages - 1) freelist[idx] = (int32_t)idx + 1;
-    if (idx == 0) {
-        pool_state[kPoolFree] = npages - 1;
-        pool_state[kPoolUsed] = 0;
-        pool_state[kPoolRenew] = 0;
-        pool_state[kPoolBase] = 0;
-        pool_state[kPoolTicket] = 0;
-        pool_state[kPoolShort] = 0;
-        pool_state[kPoolAcc] = pool_state[kPoolAcc + 1] = 0;
-    }
+    if (idx < pp.geom.planes * kPage) pp.pool[idx] = (idx / kPage == 2) ? -1.0f : 0.0f;
+    if (idx < nentries) pp.pt[idx] = 0;
+    if (idx < pp.npages - 1) pp.freelist[idx] = (int32_t)idx + 1;
+    if (idx == 0) pool_state_clear(pp.pool_state, pp.npages - 1);
 }
 
 // free list = pages 0 .. count0 - 1, then first1 .. first1 + count1 - 1; nothing handed out
@@ -665,16 +606,7 @@ __global__ __launch_bounds__(256) void free_iota_kernel(int32_t* __restrict__ ou
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx < count0) out[idx] = idx;
     else if (idx < count0 + count1) out[idx] = first1 + (idx - count0);
-    if (idx == 0) {
-        const int count = count0 + count1;
-        pool_state[kPoolFree] = count;
-        pool_state[kPoolUsed] = 0;
-        pool_state[kPoolRenew] = 0;
-        pool_state[kPoolBase] = 0;
-        pool_state[kPoolTicket] = 0;
-        pool_state[kPoolShort] = 0;
-        pool_state[kPoolAcc] = pool_state[kPoolAcc + 1] = 0;
-    }
+    if (idx == 0) pool_state_clear(pool_state, count0 + count1);
 }
 
 // out[k] = anc[sel[k]] (or sel[k]): the source rows of a few chosen particles with the pending gather applied
@@ -684,8 +616,6 @@ __global__ __launch_bounds__(256) void compose_index_kernel(const int32_t* __res
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k < count) out[k] = anc ? anc[sel[k]] : sel[k];
 }
-
-inline int blocks256(int64_t n) { return (int)((n + 255) / 256); }
 
 }  // namespace
 
@@ -744,7 +674,7 @@ hipError_t launch_page_table_gather(hipStream_t stream, const int32_t* pt_in, in
     return hipGetLastError();
 }
 
-int pool_state_words() { return 8; }
+int pool_state_words() { return kPoolStateWords; }
 int free_list_blocks(int npages) { return (npages + kFreeTile - 1) / kFreeTile; }
 
 hipError_t launch_compose_index(hipStream_t stream, const int32_t* sel, const int32_t* anc, int count, int32_t* out)
@@ -757,7 +687,7 @@ hipError_t launch_compose_index(hipStream_t stream, const int32_t* sel, const in
 hipError_t launch_free_list(hipStream_t stream, const uint32_t* stamp, int npages, uint32_t live, int32_t* freelist,
                             int32_t* pool_state, int32_t* h_short)
 {
-    free_list_kernel<<<(npages + kFreeTile - 1) / kFreeTile, 256, 0, stream>>>(stamp, npages, live, freelist, pool_state, h_short);
+    free_list_kernel<<<free_list_blocks(npages), 256, 0, stream>>>(stamp, npages, live, freelist, pool_state, h_short);
     return hipGetLastError();
 }
 
@@ -768,65 +698,54 @@ hipError_t launch_pool_reserve(hipStream_t stream, int32_t* pool_state, int64_t 
 }
 
 hipError_t launch_migrate_unpack_paged(hipStream_t stream, const float* in, int total, int n, float* pose, int64_t pose_ld,
-                                       float* pool, int32_t* pt, int nb, int nlandmarks, const int32_t* freelist,
-                                       const int32_t* pool_state, uint32_t* stamp, uint32_t live)
+                                       const PagePool& pp, int nlandmarks)
 {
     if (total <= 0) return hipSuccess;
-    migrate_unpack_paged_kernel<<<total, 256, 0, stream>>>(in, total, n, pose, pose_ld, pool, pt, nb, nlandmarks, freelist,
-                                                          pool_state, stamp, live);
+    migrate_unpack_paged_kernel<<<total, 256, 0, stream>>>(in, total, n, pose, pose_ld, pp, nlandmarks);
     return hipGetLastError();
 }
 
 hipError_t launch_migrate_unpack_split_pages(hipStream_t stream, const float* in, int total, int n, float* pose, int64_t pose_ld,
-                                             float* pool, const PageGeom& geom, int32_t* pt, int nb, int nlandmarks,
-                                             const int32_t* freelist, const int32_t* pool_state, uint32_t* stamp, uint32_t live,
-                                             float* cov, float* covx, int32_t* cls, int Lp, float meas_var, const int32_t* cls_free,
-                                             int cls_first, uint32_t* cstamp, uint32_t cstamp_now, int32_t* live_list, int32_t* live_cnt)
+                                             const PagePool& pp, const ClassStore& cs, int nlandmarks, float meas_var,
+                                             const int32_t* cls_free, int cls_first)
 {
     if (total <= 0) return hipSuccess;
-    migrate_unpack_split_pages_kernel<<<total, 256, 0, stream>>>(in, total, n, pose, pose_ld, pool, geom, pt, nb, nlandmarks, freelist,
-                                                                 pool_state, stamp, live, cov, covx, cls, Lp, meas_var, cls_free, cls_first,
-                                                                 cstamp, cstamp_now, live_list, live_cnt);
+    migrate_unpack_split_pages_kernel<<<total, 256, 0, stream>>>(in, total, n, pose, pose_ld, pp, cs, nlandmarks, meas_var, cls_free,
+                                                                 cls_first);
     return hipGetLastError();
 }
 
-hipError_t launch_pages_from_rows(hipStream_t stream, const float* rows, int64_t row_stride, int plane_stride, int nlandmarks,
-                                  int nb, int n, float* pool, int32_t* pt, int32_t* freelist, int npages, int32_t* pool_state,
-                                  int page_base, const PageGeom& geom)
+hipError_t launch_pages_from_rows(hipStream_t stream, const float* rows, int64_t row_stride, int plane_stride, int nlandmarks, int n,
+                                  const PagePool& pp, int page_base)
 {
-    pages_from_rows_kernel<<<blocks256((int64_t)n * nb * kPage), 256, 0, stream>>>(rows, row_stride, plane_stride, nlandmarks, nb, n,
-                                                                                  pool, pt, page_base, geom);
-    const int used = n * nb;   // the tables name pages page_base .. page_base + n * nb - 1: the rest is free
+    pages_from_rows_kernel<<<blocks256((int64_t)n * pp.nb * kPage), 256, 0, stream>>>(rows, row_stride, plane_stride, nlandmarks, n, pp,
+                                                                                     page_base);
+    const int used = n * pp.nb;   // the tables name pages page_base .. page_base + n * nb - 1: the rest is free
     const int after = page_base + used;
-    free_iota_kernel<<<blocks256(npages > used ? npages - used : 1), 256, 0, stream>>>(freelist, page_base, after, npages - after,
-                                                                                     pool_state);
+    free_iota_kernel<<<blocks256(pp.npages > used ? pp.npages - used : 1), 256, 0, stream>>>(pp.freelist, page_base, after,
+                                                                                           pp.npages - after, pp.pool_state);
     return hipGetLastError();
 }
 
-hipError_t launch_rows_from_pages(hipStream_t stream, const float* pool, const int32_t* pt, int nb, const int32_t* anc, int n,
-                                  float* rows, int64_t row_stride, int plane_stride, int nlandmarks, const PageGeom& geom)
+hipError_t launch_rows_from_pages(hipStream_t stream, const PagePool& pp, const int32_t* anc, int n, float* rows, int64_t row_stride,
+                                  int plane_stride, int nlandmarks)
 {
-    rows_from_pages_kernel<<<blocks256((int64_t)n * nb * kPage), 256, 0, stream>>>(pool, pt, nb, anc, n, rows, row_stride,
-                                                                                  plane_stride, nlandmarks, geom);
+    rows_from_pages_kernel<<<blocks256((int64_t)n * pp.nb * kPage), 256, 0, stream>>>(pp, anc, n, rows, row_stride, plane_stride, nlandmarks);
     return hipGetLastError();
 }
 
-hipError_t launch_rows_from_split_pages(hipStream_t stream, const float* pool, const PageGeom& geom, const int32_t* pt, int nb,
-                                        const float* cov, const int32_t* cls, int Lp, const int32_t* idx, int count, float* rows,
-                                        int64_t row_stride, int plane_stride, int nlandmarks)
+hipError_t launch_rows_from_split_pages(hipStream_t stream, const PagePool& pp, const ClassStore& cs, const int32_t* idx, int count,
+                                        float* rows, int64_t row_stride, int plane_stride, int nlandmarks)
 {
     if (count <= 0) return hipSuccess;
-    rows_from_split_pages_kernel<<<count, 256, 0, stream>>>(pool, geom, pt, nb, cov, cls, Lp, idx, count, rows, row_stride, plane_stride,
-                                                           nlandmarks);
+    rows_from_split_pages_kernel<<<count, 256, 0, stream>>>(pp, cs, idx, count, rows, row_stride, plane_stride, nlandmarks);
     return hipGetLastError();
 }
 
-hipError_t launch_pages_reset(hipStream_t stream, float* pool, int32_t* pt, int64_t nentries, int32_t* freelist, int npages,
-                              int32_t* pool_state, const PageGeom& geom)
+hipError_t launch_pages_reset(hipStream_t stream, const PagePool& pp, int64_t nentries)
 {
-    const int64_t m = nentries > npages ? nentries : npages;
-    pages_reset_kernel<<<blocks256(m > kPageFloats ? m : kPageFloats), 256, 0, stream>>>(pool, pt, nentries, freelist, npages,
-                                                                                     pool_state, geom.planes);
+    const int64_t m = nentries > pp.npages ? nentries : pp.npages;
+    pages_reset_kernel<<<blocks256(m > kPageFloats ? m : kPageFloats), 256, 0, stream>>>(pp, nentries);
     return hipGetLastError();
 }
 

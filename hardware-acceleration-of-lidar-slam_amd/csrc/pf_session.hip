@@ -185,6 +185,8 @@ int issue_free_list(slam_pf* pf)
 
 float* split_pool(const slam_pf* pf);
 PageGeom split_geom(const slam_pf* pf);
+PagePool page_pool(const slam_pf* pf);
+ClassStore class_store(const slam_pf* pf);
 
 // Map rows (and poses) of ancestors that live on another rank -> the staging tail of the current buffers, where
 // the next EKF's fused gather picks them up.  pack (one launch) -> one grouped send/recv -> unpack (one launch).
@@ -238,16 +240,11 @@ int migrate(slam_pf* pf)
         if (spages) {   // the means onto fresh pages (a new free list first if the old one runs short), table rows n .. n + rtot - 1
             SLAM_HIP_TRY(e, launch_pool_reserve(e->stream, pf->page_scratch, rtot * pf->nb));
             if (int rc = issue_free_list(pf)) return rc;
-            SLAM_HIP_TRY(e, launch_migrate_unpack_split_pages(e->stream, pf->rbuf, (int)rtot, n, pf->pose_stage, pf->cap, split_pool(pf), geom,
-                                                              pf->pt[pf->pt_cur], pf->nb, L, pf->freelist, pf->page_scratch, pf->stamp, pf->stamp_now,
-                                                              pf->cov, pf->covx, pf->cls[pf->sp_cur], pf->Lp, pf->cfg.meas_var, pf->cls_free,
-                                                              (int)pf->cls_cursor, pf->cstamp, pf->cstamp_now, pf->live[pf->live_cur],
-                                                              pf->cov_cnt + pf->cov_phase));
+            SLAM_HIP_TRY(e, launch_migrate_unpack_split_pages(e->stream, pf->rbuf, (int)rtot, n, pf->pose_stage, pf->cap, page_pool(pf),
+                                                              class_store(pf), L, pf->cfg.meas_var, pf->cls_free, (int)pf->cls_cursor));
         } else
-            SLAM_HIP_TRY(e, launch_migrate_unpack_split(e->stream, pf->rbuf, (int)rtot, n, pf->pose_stage, pf->cap, pf->mean[pf->sp_cur], pf->cov,
-                                                        pf->covx, pf->cls[pf->sp_cur], pf->Lp, L, pf->cfg.meas_var, pf->cls_free,
-                                                        (int)pf->cls_cursor, pf->cstamp, pf->cstamp_now, pf->live[pf->live_cur],
-                                                        pf->cov_cnt + pf->cov_phase));
+            SLAM_HIP_TRY(e, launch_migrate_unpack_split(e->stream, pf->rbuf, (int)rtot, n, pf->pose_stage, pf->cap, pf->mean[pf->sp_cur],
+                                                        class_store(pf), L, pf->cfg.meas_var, pf->cls_free, (int)pf->cls_cursor));
         pf->cls_cursor += rtot;
         pf->cls_appended += (uint32_t)rtot;
     } else if (rtot && pf->paged) {
@@ -255,9 +252,7 @@ int migrate(slam_pf* pf)
         const ProfScope prof(e, SLAM_PROF_UNPACK);
         SLAM_HIP_TRY(e, launch_pool_reserve(e->stream, pf->page_scratch, rtot * pf->nb));
         if (int rc = issue_free_list(pf)) return rc;
-        SLAM_HIP_TRY(e, launch_migrate_unpack_paged(e->stream, pf->rbuf, (int)rtot, n, pf->pose_stage, pf->cap, pf->pool,
-                                                    pf->pt[pf->pt_cur], pf->nb, L, pf->freelist, pf->page_scratch, pf->stamp,
-                                                    pf->stamp_now));
+        SLAM_HIP_TRY(e, launch_migrate_unpack_paged(e->stream, pf->rbuf, (int)rtot, n, pf->pose_stage, pf->cap, page_pool(pf), L));
     } else if (rtot) {
         if (int rc = slam_migrate_unpack_dev(e, pf->rbuf, G, rcnt, n, pf->pose_stage, pf->cap,
                                              L ? pf->map[pf->map_cur] : nullptr, 5 * (int64_t)pf->Lp, pf->Lp, L))
@@ -373,8 +368,8 @@ int convert_to_pages(slam_pf* pf)
     const int mc = pf->map_cur;
     const int page_base = (1 - mc) * pf->cap * pf->nb;
     pf->pt_cur = 0;
-    SLAM_HIP_TRY(e, launch_pages_from_rows(e->stream, pf->map[mc], 5 * (int64_t)pf->Lp, pf->Lp, pf->L, pf->nb, rows_to_convert(pf),
-                                           pf->pool, pf->pt[0], pf->freelist, pf->npages, pf->page_scratch, page_base));
+    SLAM_HIP_TRY(e, launch_pages_from_rows(e->stream, pf->map[mc], 5 * (int64_t)pf->Lp, pf->Lp, pf->L, rows_to_convert(pf), page_pool(pf),
+                                           page_base));
     pf->paged = true;
     pf->conversions++;
     return SLAM_OK;
@@ -392,8 +387,7 @@ int convert_to_rows(slam_pf* pf)
     if (int rc = conversion_scratch(pf, used)) return rc;
     if (!pf->conv_tmp) return SLAM_OK;
     // stream-ordered: pages -> scratch rows -> the first half of the store (the scratch is read before anything else writes it)
-    SLAM_HIP_TRY(e, launch_rows_from_pages(e->stream, pf->pool, pf->pt[pf->pt_cur], pf->nb, nullptr, nrows, pf->conv_tmp,
-                                           5 * (int64_t)pf->Lp, pf->Lp, pf->L));
+    SLAM_HIP_TRY(e, launch_rows_from_pages(e->stream, page_pool(pf), nullptr, nrows, pf->conv_tmp, 5 * (int64_t)pf->Lp, pf->Lp, pf->L));
     SLAM_HIP_TRY(e, hipMemcpyAsync(pf->map[0], pf->conv_tmp, used * 4, hipMemcpyDeviceToDevice, e->stream));
     pf->map_cur = 0;
     pf->paged = false;
@@ -454,6 +448,19 @@ PageGeom split_geom(const slam_pf* pf)
     return g;
 }
 
+// the page pool and the class store as the launchers off the frame path take them (kernels.h): the current table, the current
+// class buffer and list, the stamps of the last update
+PagePool page_pool(const slam_pf* pf)
+{
+    return PagePool{ pf->split ? split_pool(pf) : pf->pool, pf->split ? split_geom(pf) : PageGeom(), pf->pt[pf->pt_cur], pf->nb,
+                     pf->freelist, pf->npages, pf->page_scratch, pf->stamp, pf->stamp_now };
+}
+ClassStore class_store(const slam_pf* pf)
+{
+    return ClassStore{ pf->cov, pf->covx, pf->cls[pf->sp_cur], pf->Lp, pf->cstamp, pf->cstamp_now, pf->live[pf->live_cur],
+                       pf->cov_cnt + pf->cov_phase };
+}
+
 // a new set of classes is about to be made (set_map, reset, rows -> split): lists and counters start afresh
 void split_new_epoch(slam_pf* pf)
 {
@@ -470,9 +477,8 @@ int split_from_rows(slam_pf* pf, const float* d_rows, int64_t row_stride, int pl
 {
     slam_engine* e = pf->e;
     split_new_epoch(pf);
-    SLAM_HIP_TRY(e, launch_split_from_rows(e->stream, d_rows, row_stride, plane_stride, pf->L, nrows, pf->Lp, pf->mean[pf->sp_cur], pf->cov,
-                                           pf->covx, pf->cfg.meas_var, pf->cls[pf->sp_cur], pf->live[0], pf->cov_cnt, 0, pf->cstamp,
-                                           pf->cstamp_now, dev_word(pf, RES_LIVE), pf->cls_epoch, pf->split_scratch));
+    SLAM_HIP_TRY(e, launch_split_from_rows(e->stream, d_rows, row_stride, plane_stride, pf->L, nrows, pf->mean[pf->sp_cur], class_store(pf),
+                                           pf->cfg.meas_var, dev_word(pf, RES_LIVE), pf->cls_epoch, pf->split_scratch));
     return SLAM_OK;
 }
 
@@ -499,8 +505,7 @@ int split_means_to_pages(slam_pf* pf)
     const int page_base = dst == split_pool(pf) ? 0 : pf->cap * pf->nb;
     pf->pt_cur = 0;
     // (sharded: rows_to_convert takes the staging tail along when the exchange of the last frame has been completed already)
-    SLAM_HIP_TRY(e, launch_pages_from_rows(e->stream, src, 2 * (int64_t)pf->Lp, pf->Lp, pf->L, pf->nb, rows_to_convert(pf), split_pool(pf),
-                                           pf->pt[0], pf->freelist, pf->npages, pf->page_scratch, page_base, split_geom(pf)));
+    SLAM_HIP_TRY(e, launch_pages_from_rows(e->stream, src, 2 * (int64_t)pf->Lp, pf->Lp, pf->L, rows_to_convert(pf), page_pool(pf), page_base));
     pf->paged = true;
     return SLAM_OK;
 }
@@ -521,8 +526,7 @@ int convert_split_pages_to_split(slam_pf* pf)
     const size_t used = 2 * (size_t)pf->Lp * (size_t)nrows;
     if (int rc = conversion_scratch(pf, used)) return rc;
     if (!pf->conv_tmp) return SLAM_OK;
-    SLAM_HIP_TRY(e, launch_rows_from_pages(e->stream, split_pool(pf), pf->pt[pf->pt_cur], pf->nb, nullptr, nrows, pf->conv_tmp,
-                                           2 * (int64_t)pf->Lp, pf->Lp, pf->L, split_geom(pf)));
+    SLAM_HIP_TRY(e, launch_rows_from_pages(e->stream, page_pool(pf), nullptr, nrows, pf->conv_tmp, 2 * (int64_t)pf->Lp, pf->Lp, pf->L));
     SLAM_HIP_TRY(e, hipMemcpyAsync(pf->mean[0], pf->conv_tmp, used * 4, hipMemcpyDeviceToDevice, e->stream));
     if (pf->sp_cur == 1) SLAM_HIP_TRY(e, hipMemcpyAsync(pf->cls[0], pf->cls[1], (size_t)nrows * 4, hipMemcpyDeviceToDevice, e->stream));
     pf->sp_cur = 0;
@@ -1182,11 +1186,9 @@ hipError_t rows_of(const slam_pf* pf, const int32_t* idx, int count, float* dens
 {
     hipStream_t s = pf->e->stream;
     const int64_t stride = 5 * (int64_t)pf->Lp;
-    if (pf->paged && pf->split)
-        return launch_rows_from_split_pages(s, split_pool(pf), split_geom(pf), pf->pt[pf->pt_cur], pf->nb, pf->cov, pf->cls[pf->sp_cur],
-                                            pf->Lp, idx, count, dense, stride, pf->Lp, pf->L);
-    if (pf->split) return launch_rows_from_split(s, pf->mean[pf->sp_cur], pf->cov, pf->cls[pf->sp_cur], pf->Lp, idx, count, dense, stride, pf->Lp, pf->L);
-    return launch_rows_from_pages(s, pf->pool, pf->pt[pf->pt_cur], pf->nb, idx, count, dense, stride, pf->Lp, pf->L);
+    if (pf->paged && pf->split) return launch_rows_from_split_pages(s, page_pool(pf), class_store(pf), idx, count, dense, stride, pf->Lp, pf->L);
+    if (pf->split) return launch_rows_from_split(s, pf->mean[pf->sp_cur], class_store(pf), idx, count, dense, stride, pf->Lp, pf->L);
+    return launch_rows_from_pages(s, page_pool(pf), idx, count, dense, stride, pf->Lp, pf->L);
 }
 
 int pf_get_map_host(slam_pf* pf, float* rows)
@@ -1308,15 +1310,13 @@ int slam_pf_reset(slam_pf* pf, const float pose[3])
     if (hipMemcpy(pf->pose[pf->cur], h.data(), 3 * n * 4, hipMemcpyHostToDevice) != hipSuccess) return SLAM_ERR_HIP;
     if (pf->split) {   // every landmark of every particle "not seen yet": one class
         split_new_epoch(pf);
-        SLAM_HIP_TRY(pf->e, launch_split_reset(pf->e->stream, pf->mean[pf->sp_cur], pf->cov, pf->covx, pf->cls[pf->sp_cur], pf->Lp, pf->n,
-                                               pf->live[0], pf->cov_cnt, 0, pf->cstamp, pf->cstamp_now, dev_word(pf, RES_LIVE), pf->cls_epoch));
+        SLAM_HIP_TRY(pf->e, launch_split_reset(pf->e->stream, pf->mean[pf->sp_cur], class_store(pf), pf->n, dev_word(pf, RES_LIVE),
+                                               pf->cls_epoch));
         if (pf->paged)   // split pages: every particle names ONE shared page of zero means, the rest of the pool is free
-            SLAM_HIP_TRY(pf->e, launch_pages_reset(pf->e->stream, split_pool(pf), pf->pt[pf->pt_cur], (int64_t)pf->n * pf->nb, pf->freelist,
-                                                   pf->npages, pf->page_scratch, split_geom(pf)));
+            SLAM_HIP_TRY(pf->e, launch_pages_reset(pf->e->stream, page_pool(pf), (int64_t)pf->n * pf->nb));
         if (int rc = slam_engine_sync(pf->e)) return rc;
     } else if (pf->paged) {   // every particle names ONE shared page of landmarks not seen yet
-        SLAM_HIP_TRY(pf->e, launch_pages_reset(pf->e->stream, pf->pool, pf->pt[pf->pt_cur], (int64_t)pf->n * pf->nb, pf->freelist,
-                                               pf->npages, pf->page_scratch));
+        SLAM_HIP_TRY(pf->e, launch_pages_reset(pf->e->stream, page_pool(pf), (int64_t)pf->n * pf->nb));
         if (int rc = slam_engine_sync(pf->e)) return rc;
     } else if (pf->L) {   // P_xx = -1: "not seen yet"
         const size_t Lp = (size_t)pf->Lp;
@@ -1385,8 +1385,7 @@ int slam_pf_set_map_dev(slam_pf* pf, const float* d_rows, int64_t row_stride, in
     }
     if (pf->split) return split_from_rows(pf, d_rows, row_stride, plane_stride, pf->n);
     if (pf->paged) {
-        SLAM_HIP_TRY(e, launch_pages_from_rows(e->stream, d_rows, row_stride, plane_stride, pf->L, pf->nb, pf->n, pf->pool,
-                                               pf->pt[pf->pt_cur], pf->freelist, pf->npages, pf->page_scratch));
+        SLAM_HIP_TRY(e, launch_pages_from_rows(e->stream, d_rows, row_stride, plane_stride, pf->L, pf->n, page_pool(pf)));
         return SLAM_OK;
     }
     for (int pl = 0; pl < 5; ++pl)   // plane by plane: one 2-D copy each whatever the caller's row stride is

@@ -25,15 +25,13 @@
 // This file: the conversions rows <-> split, the gather of a frame without an update.  The particles'
 // update on this layout is ekf_split_body in ekf_kernels.hip (it shares the grouped row kernel's machinery).
 
-#include "ekf_math.h"
 #include "cov_update_body.h"
-#include "kernels.h"
+#include "pf_common.h"
+#include "storage_bodies.h"
 
 namespace slam {
 
 namespace {
-
-inline int blocks256(int64_t n) { return (int)((n + 255) / 256); }
 
 // the determinant terms of classes 0 .. *count - 1 from their covariance planes (after a conversion or a reset)
 __global__ __launch_bounds__(256) void cov_terms_kernel(const float* __restrict__ cov, float* __restrict__ covx, int Lp, int nlandmarks,
@@ -77,16 +75,13 @@ __global__ __launch_bounds__(256) void cov_heads_kernel(const float* __restrict_
 // class, and — when it starts a class — the class's covariance row, list entry and stamp.  Padding columns [L, Lp): means 0,
 // covariances (1, 0, 1) — "seen, never observed again": harmless operands that nobody reads back.
 __global__ __launch_bounds__(256) void split_from_rows_kernel(const float* __restrict__ rows, int64_t row_stride, int plane_stride,
-                                                              int nlandmarks, int n, int Lp, const uint64_t* __restrict__ flag,
-                                                              const uint64_t* __restrict__ sum, float* __restrict__ mean,
-                                                              float* __restrict__ cov, int32_t* __restrict__ cls,
-                                                              int32_t* __restrict__ live, int32_t* __restrict__ cnt, int phase,
-                                                              uint32_t* __restrict__ cstamp, uint32_t stamp_now,
+                                                              int nlandmarks, int n, const uint64_t* __restrict__ flag,
+                                                              const uint64_t* __restrict__ sum, float* __restrict__ mean, ClassStore cs,
                                                               int32_t* __restrict__ h_live, uint32_t epoch)
 {
     const int i = blockIdx.x;
     if (i >= n) return;
-    const int c = (int)sum[i] - 1;
+    const int c = (int)sum[i] - 1, Lp = cs.Lp;
     const bool head = flag[i] != 0;
     const float* r = rows + (int64_t)i * row_stride;
     float* m = mean + (int64_t)i * 2 * Lp;
@@ -96,7 +91,7 @@ __global__ __launch_bounds__(256) void split_from_rows_kernel(const float* __res
         m[Lp + l] = in ? r[(int64_t)plane_stride + l] : 0.0f;
     }
     if (head) {
-        float* cr = cov + (int64_t)c * 3 * Lp;
+        float* cr = cs.cov + (int64_t)c * 3 * Lp;
         for (int l = threadIdx.x; l < Lp; l += 256) {
             const bool in = l < nlandmarks;
             cr[l] = in ? r[2 * (int64_t)plane_stride + l] : 1.0f;
@@ -105,31 +100,30 @@ __global__ __launch_bounds__(256) void split_from_rows_kernel(const float* __res
         }
     }
     if (threadIdx.x == 0) {
-        cls[i] = c;
+        cs.cls[i] = c;
         if (head) {
-            live[c] = c;
-            cstamp[c] = stamp_now;
+            cs.live[c] = c;
+            cs.cstamp[c] = cs.stamp_now;
         }
         if (i == n - 1) {
-            cnt[phase] = c + 1;
-            cnt[(phase + 1) % 3] = 0;
-            cnt[(phase + 2) % 3] = 0;
+            cs.cnt[0] = c + 1;
+            cs.cnt[1] = 0;
+            cs.cnt[2] = 0;
             if (h_live) publish_live(h_live, c + 1, epoch);
         }
     }
 }
 
 // ---- split -> rows: out row k = [means of particle src | covariances of its class], src = idx[k] or k
-__global__ __launch_bounds__(256) void rows_from_split_kernel(const float* __restrict__ mean, const float* __restrict__ cov,
-                                                              const int32_t* __restrict__ cls, int Lp, const int32_t* __restrict__ idx,
+__global__ __launch_bounds__(256) void rows_from_split_kernel(const float* __restrict__ mean, ClassStore cs, const int32_t* __restrict__ idx,
                                                               int count, float* __restrict__ rows, int64_t row_stride,
                                                               int plane_stride, int nlandmarks)
 {
     const int k = blockIdx.x;
     if (k >= count) return;
-    const int src = idx ? idx[k] : k;
+    const int src = idx ? idx[k] : k, Lp = cs.Lp;
     const float* m = mean + (int64_t)src * 2 * Lp;
-    const float* cr = cov + (int64_t)cls[src] * 3 * Lp;
+    const float* cr = cs.cov + (int64_t)cs.cls[src] * 3 * Lp;
     float* r = rows + (int64_t)k * row_stride;
     for (int l = threadIdx.x; l < nlandmarks; l += 256) {
         r[l] = m[l];
@@ -184,39 +178,19 @@ __global__ __launch_bounds__(256) void class_free_list_kernel(const uint32_t* __
 
 // ---- a received record (sharded sessions) -> staging row n + p of the means and a class of its own
 __global__ __launch_bounds__(256) void migrate_unpack_split_kernel(const float* __restrict__ in, int total, int n, float* __restrict__ pose,
-                                                                   int64_t pose_ld, float* __restrict__ mean, float* __restrict__ cov,
-                                                                   float* __restrict__ covx, int32_t* __restrict__ cls, int Lp,
-                                                                   int nlandmarks, float q, const int32_t* __restrict__ freelist,
-                                                                   int first, uint32_t* __restrict__ cstamp, uint32_t stamp,
-                                                                   int32_t* __restrict__ live, int32_t* __restrict__ cnt)
+                                                                   int64_t pose_ld, float* __restrict__ mean, ClassStore cs, int nlandmarks,
+                                                                   float q, const int32_t* __restrict__ freelist, int first)
 {
     const int p = blockIdx.x;
     if (p >= total) return;
     const float* __restrict__ rec = in + (int64_t)(3 + 5 * nlandmarks) * p;
-    const int c = freelist[first + p];
     if (threadIdx.x < 3) pose[threadIdx.x * pose_ld + n + p] = rec[threadIdx.x];
-    float* m = mean + (int64_t)(n + p) * 2 * Lp;
-    float* cr = cov + (int64_t)c * 3 * Lp;
-    float* xr = covx + (int64_t)c * 2 * Lp;
-    for (int l = threadIdx.x; l < Lp; l += 256) {
-        const bool in_row = l < nlandmarks;
-        m[l] = in_row ? rec[3 + l] : 0.0f;
-        m[Lp + l] = in_row ? rec[3 + nlandmarks + l] : 0.0f;
-        const float pxx = in_row ? rec[3 + 2 * nlandmarks + l] : 1.0f, pxy = in_row ? rec[3 + 3 * nlandmarks + l] : 0.0f,
-                    pyy = in_row ? rec[3 + 4 * nlandmarks + l] : 1.0f;
-        cr[l] = pxx;
-        cr[Lp + l] = pxy;
-        cr[2 * Lp + l] = pyy;
-        float idet = 1.0f, hl = 0.0f;
-        if (in_row && !(pxx < 0.0f)) ekf_det_terms<float>(pxx, pxy, pyy, q, idet, hl);
-        xr[l] = idet;
-        xr[Lp + l] = hl;
+    float* m = mean + (int64_t)(n + p) * 2 * cs.Lp;
+    for (int l = threadIdx.x; l < cs.Lp; l += 256) {
+        m[l] = l < nlandmarks ? rec[3 + l] : 0.0f;
+        m[cs.Lp + l] = l < nlandmarks ? rec[3 + nlandmarks + l] : 0.0f;
     }
-    if (threadIdx.x == 0) {
-        cls[n + p] = c;
-        cstamp[c] = stamp;
-        live[atomicAdd(cnt, 1)] = c;
-    }
+    unpack_class(rec, nlandmarks, q, freelist[first + p], n + p, cs);
 }
 
 __global__ __launch_bounds__(256) void class_gather_kernel(const int32_t* __restrict__ cls_in, int32_t* __restrict__ cls_out,
@@ -231,21 +205,19 @@ __global__ __launch_bounds__(256) void class_gather_kernel(const int32_t* __rest
 }
 
 // ---- reset: every landmark of every particle "not seen yet" (P_xx = -1), one class
-__global__ __launch_bounds__(256) void split_reset_kernel(float* __restrict__ mean, float* __restrict__ cov, int32_t* __restrict__ cls,
-                                                          int Lp, int n, int32_t* __restrict__ live, int32_t* __restrict__ cnt, int phase,
-                                                          uint32_t* __restrict__ cstamp, uint32_t stamp_now, int32_t* __restrict__ h_live,
+__global__ __launch_bounds__(256) void split_reset_kernel(float* __restrict__ mean, ClassStore cs, int n, int32_t* __restrict__ h_live,
                                                           uint32_t epoch)
 {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx < (int64_t)n * 2 * Lp) mean[idx] = 0.0f;
-    if (idx < 3 * (int64_t)Lp) cov[idx] = idx < Lp ? -1.0f : 0.0f;
-    if (idx < n) cls[idx] = 0;
+    if (idx < (int64_t)n * 2 * cs.Lp) mean[idx] = 0.0f;
+    if (idx < 3 * (int64_t)cs.Lp) cs.cov[idx] = idx < cs.Lp ? -1.0f : 0.0f;
+    if (idx < n) cs.cls[idx] = 0;
     if (idx == 0) {
-        live[0] = 0;
-        cstamp[0] = stamp_now;
-        cnt[phase] = 1;
-        cnt[(phase + 1) % 3] = 0;
-        cnt[(phase + 2) % 3] = 0;
+        cs.live[0] = 0;
+        cs.cstamp[0] = cs.stamp_now;
+        cs.cnt[0] = 1;
+        cs.cnt[1] = 0;
+        cs.cnt[2] = 0;
         if (h_live) publish_live(h_live, 1, epoch);
     }
 }
@@ -256,9 +228,7 @@ __global__ __launch_bounds__(256) void split_reset_kernel(float* __restrict__ me
 size_t split_scratch_words(int n) { return 2 * (2 * (size_t)n + (size_t)prefix_sum_scratch_elems(n)) + 4; }
 
 hipError_t launch_split_from_rows(hipStream_t stream, const float* rows, int64_t row_stride_in, int plane_stride_in, int nlandmarks,
-                                  int n, int Lp, float* mean, float* cov, float* covx, float meas_var, int32_t* cls, int32_t* live,
-                                  int32_t* cnt, int phase, uint32_t* cstamp, uint32_t stamp_now, int32_t* h_live, uint32_t epoch,
-                                  void* scratch)
+                                  int n, float* mean, const ClassStore& cs, float meas_var, int32_t* h_live, uint32_t epoch, void* scratch)
 {
     if (n <= 0) return hipSuccess;
     uint64_t* flag = static_cast<uint64_t*>(scratch);
@@ -267,18 +237,17 @@ hipError_t launch_split_from_rows(hipStream_t stream, const float* rows, int64_t
     cov_heads_kernel<<<n, 256, 0, stream>>>(rows, row_stride_in, plane_stride_in, nlandmarks, n, flag);
     hipError_t err = launch_prefix_sum(stream, flag, n, sum, ps);
     if (err != hipSuccess) return err;
-    split_from_rows_kernel<<<n, 256, 0, stream>>>(rows, row_stride_in, plane_stride_in, nlandmarks, n, Lp, flag, sum, mean, cov, cls,
-                                                  live, cnt, phase, cstamp, stamp_now, h_live, epoch);
+    split_from_rows_kernel<<<n, 256, 0, stream>>>(rows, row_stride_in, plane_stride_in, nlandmarks, n, flag, sum, mean, cs, h_live, epoch);
     // at most n classes: the launch is as wide as that, workgroups beyond the count leave at once
-    cov_terms_kernel<<<dim3((unsigned)n, (unsigned)((Lp + 255) / 256)), 256, 0, stream>>>(cov, covx, Lp, nlandmarks, meas_var, cnt + phase);
+    cov_terms_kernel<<<dim3((unsigned)n, (unsigned)((cs.Lp + 255) / 256)), 256, 0, stream>>>(cs.cov, cs.covx, cs.Lp, nlandmarks, meas_var, cs.cnt);
     return hipGetLastError();
 }
 
-hipError_t launch_rows_from_split(hipStream_t stream, const float* mean, const float* cov, const int32_t* cls, int Lp,
-                                  const int32_t* idx, int count, float* rows, int64_t row_stride, int plane_stride, int nlandmarks)
+hipError_t launch_rows_from_split(hipStream_t stream, const float* mean, const ClassStore& cs, const int32_t* idx, int count,
+                                  float* rows, int64_t row_stride, int plane_stride, int nlandmarks)
 {
     if (count <= 0) return hipSuccess;
-    rows_from_split_kernel<<<count, 256, 0, stream>>>(mean, cov, cls, Lp, idx, count, rows, row_stride, plane_stride, nlandmarks);
+    rows_from_split_kernel<<<count, 256, 0, stream>>>(mean, cs, idx, count, rows, row_stride, plane_stride, nlandmarks);
     return hipGetLastError();
 }
 
@@ -290,13 +259,10 @@ hipError_t launch_class_free_list(hipStream_t stream, const uint32_t* cstamp, in
 }
 
 hipError_t launch_migrate_unpack_split(hipStream_t stream, const float* in, int total, int n, float* pose, int64_t pose_ld, float* mean,
-                                       float* cov, float* covx, int32_t* cls, int Lp, int nlandmarks, float meas_var,
-                                       const int32_t* freelist, int first, uint32_t* cstamp, uint32_t stamp, int32_t* live,
-                                       int32_t* cnt)
+                                       const ClassStore& cs, int nlandmarks, float meas_var, const int32_t* freelist, int first)
 {
     if (total <= 0) return hipSuccess;
-    migrate_unpack_split_kernel<<<total, 256, 0, stream>>>(in, total, n, pose, pose_ld, mean, cov, covx, cls, Lp, nlandmarks, meas_var,
-                                                          freelist, first, cstamp, stamp, live, cnt);
+    migrate_unpack_split_kernel<<<total, 256, 0, stream>>>(in, total, n, pose, pose_ld, mean, cs, nlandmarks, meas_var, freelist, first);
     return hipGetLastError();
 }
 
@@ -316,13 +282,11 @@ hipError_t launch_class_gather(hipStream_t stream, const int32_t* cls_in, int32_
     return hipGetLastError();
 }
 
-hipError_t launch_split_reset(hipStream_t stream, float* mean, float* cov, float* covx, int32_t* cls, int Lp, int n, int32_t* live,
-                              int32_t* cnt, int phase, uint32_t* cstamp, uint32_t stamp_now, int32_t* h_live, uint32_t epoch)
+hipError_t launch_split_reset(hipStream_t stream, float* mean, const ClassStore& cs, int n, int32_t* h_live, uint32_t epoch)
 {
-    const int64_t m = (int64_t)n * 2 * Lp;
-    split_reset_kernel<<<blocks256(m > 3 * (int64_t)Lp ? m : 3 * (int64_t)Lp), 256, 0, stream>>>(mean, cov, cls, Lp, n, live, cnt, phase,
-                                                                                              cstamp, stamp_now, h_live, epoch);
-    cov_terms_kernel<<<dim3(1, (unsigned)((Lp + 255) / 256)), 256, 0, stream>>>(cov, covx, Lp, 0, 1.0f, cnt + phase);   // nothing seen yet
+    const int64_t m = (int64_t)n * 2 * cs.Lp;
+    split_reset_kernel<<<blocks256(m > 3 * (int64_t)cs.Lp ? m : 3 * (int64_t)cs.Lp), 256, 0, stream>>>(mean, cs, n, h_live, epoch);
+    cov_terms_kernel<<<dim3(1, (unsigned)((cs.Lp + 255) / 256)), 256, 0, stream>>>(cs.cov, cs.covx, cs.Lp, 0, 1.0f, cs.cnt);   // nothing seen yet
     return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@ DEV = torch.device("cuda", 0)
 
 
 def _run(paged, n, L, frames, ess, obs_of, start):
+    """paged: False / True (rows / pages) or the name of a layout."""
     import _shard_worker as W
 
     pkg = load_package()
@@ -24,8 +25,8 @@ def _run(paged, n, L, frames, ess, obs_of, start):
     eng.grid_set_dev(0, torch.from_numpy(edt).to(DEV), pkg.grid_meta(meta.rows, meta.cols, meta.ld, meta.pixel, meta.min_x, meta.min_y))
     eng.scan_upload(bx, by)
     ses = pkg.PfSession(eng, n, L, seed=77, sigma=(0.02, 0.02, 0.004), meas_var=0.02, score_gain=0.05, resample_ess_frac=ess,
-                        map_layout="pages" if paged else "rows")
-    assert ses.is_paged() == bool(paged)
+                        map_layout=paged if isinstance(paged, str) else "pages" if paged else "rows")
+    assert ses.is_paged() == (paged in (True, "pages", "split_pages"))
     if start == "empty":
         ses.reset([0.0, 0.0, 0.0])
         ses.set_poses(x, y, th)
@@ -93,6 +94,40 @@ def test_paged_session_equals_row_session(n, L, obs, start, ess):
         assert np.array_equal(bits(a), bits(b))
     if ess:
         assert 0 < rows["resampled"] < frames - 1, rows["resampled"]
+
+
+# landmarks 114, 242, 1010 and 1138 share log-likelihood accumulator 114 (l mod 128): accumulator rounds 0 .. 3, two of them on
+# either side of landmark 1024, where the list kernels start their second 1024-landmark step; with 1016 .. 1030 the set
+# touches pages 3, 7, 31, 32 and 35 — few enough for the list form of the paged update
+STEP_IDS = np.array([114, 242, 1010, 1138] + list(range(1016, 1031)), np.int32)
+
+
+def _across_the_step(frame, lm):
+    if frame == 2:
+        return None
+    ids = np.sort(STEP_IDS)
+    z = lm[ids] + 0.01 * np.float32(frame)
+    return ids, z[:, 0].copy(), z[:, 1].copy()
+
+
+@pytest.fixture(scope="module")
+def step_rows():
+    return _run("rows", 512, 1200, 6, 0.0, _across_the_step, "map")
+
+
+@pytest.mark.parametrize("layout", ["pages", "split_pages"])
+def test_observation_list_crosses_a_1024_landmark_step(step_rows, layout):
+    """L = 1200: the compaction of the observation table runs two steps, and observations of ONE accumulator lie in both
+    (their rounds count on across the step).  Five touched pages: the paged update runs its list form.  Poses, maps in the
+    middle and at the end, heaviest particle and posterior mean equal the row session's, bit for bit."""
+    assert sorted(set(STEP_IDS // 32)) == [3, 7, 31, 32, 35] and set(STEP_IDS[:4] % 128) == {114}
+    rows, got = step_rows, _run(layout, 512, 1200, 6, 0.0, _across_the_step, "map")
+    for k in ("pose", "map_mid", "map"):
+        assert np.array_equal(bits(got[k]), bits(rows[k])), k
+    for a, b in zip(got["best"], rows["best"]):
+        assert a[2] == b[2] and a[1] == b[1] and np.array_equal(bits(a[0]), bits(b[0]))
+    for a, b in zip(got["mean"], rows["mean"]):
+        assert np.array_equal(bits(a), bits(b))
 
 
 def test_paged_session_many_frames_of_free_list_turnover():

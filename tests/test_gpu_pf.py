@@ -214,6 +214,56 @@ def test_ekf_in_place_forms(eng, orc, form):
         assert d0 > 0 and d1 > 0   # the feedback chose each of them at some point
 
 
+def test_ekf_in_place_forms_in_a_session_across_a_1024_landmark_step(eng):
+    """The two in-place forms inside a gated row session at L = 1200 (the list kernel's second 1024-landmark step): the
+    observations of tests/test_gpu_paged.py's STEP_IDS — four of one accumulator, on both sides of landmark 1024 — in every
+    frame but frame 2.  resample_ess_frac = 0.2: on the CPU specification (oracle, the loop of test_gpu_configs.
+    _gated_reference on this scenario) the frames' ESS / n is 0.022, 0.82, 0.70, 0.31, 0.12, 0.66, so frames 0 and 4
+    resample and frames 3 and 4 — observing, behind a frame that kept its population — update in place.  Form 0 (whole
+    rows) and form 1 (the compact list) give the same bits, and the list form really ran."""
+    import _shard_worker as W
+    from test_gpu_paged import _across_the_step
+
+    pkg = load_package()
+    n, L, frames = 512, 1200, 6
+    meta, edt, bx, by, lm = W.make_world(L=L)
+    keep = dev(edt)
+    eng.grid_set_dev(1, keep, pkg.grid_meta(meta.rows, meta.cols, meta.ld, meta.pixel, meta.min_x, meta.min_y))
+    eng.scan_upload(bx, by)
+    x, y, th, mp = W.init_state(n, L, lm)
+    outs = []
+    for form in (0, 1):
+        eng.ekf_inplace_form_set(form)
+        before = eng.ekf_inplace_form_counts()
+        ses = pkg.PfSession(eng, n, L, seed=77, sigma=(0.02, 0.02, 0.004), meas_var=0.02, score_gain=0.05, resample_ess_frac=0.2,
+                            map_layout="rows")
+        ses.set_poses(x, y, th)
+        ses.set_map(mp)
+        best, mean = [], []
+        for f in range(frames):
+            obs = _across_the_step(f, lm)
+            if obs is not None:
+                eng.obs_upload(*obs, L)
+            ses.step(1, [0.01, -0.005, 0.002], obs is not None)
+            best.append(ses.best())
+            mean.append(ses.mean(0.05))
+        out = (ses.poses(), ses.maps(), best, mean, ses.frames_resampled())
+        ses.close()
+        after = eng.ekf_inplace_form_counts()
+        eng.ekf_inplace_form_set(-1)
+        assert after[1 - form] == before[1 - form] and after[form] - before[form] >= 1, (form, before, after)
+        # the host has looked at frames 0 .. 4: two resampled, three kept — at most one of those is frame 2, the only one
+        # without observations, so the gate kept the population in an observing frame
+        assert out[4] == 2, out[4]
+        outs.append(out)
+    a, b = outs
+    assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1]))
+    for u, v in zip(a[2], b[2]):
+        assert u[2] == v[2] and u[1] == v[1] and np.array_equal(bits(u[0]), bits(v[0]))
+    for u, v in zip(a[3], b[3]):
+        assert np.array_equal(bits(u), bits(v))
+
+
 @pytest.mark.parametrize("form", [0, 1])
 def test_ekf_in_place_sees_a_rewritten_device_table(eng, orc, form):
     """slam_obs_set_dev adopts the caller's arrays: when the caller rewrites them between two launches (same pointers,
