@@ -1,6 +1,6 @@
 // ekf_math.h — the arithmetic of ONE landmark update (no counterpart in the reference, specification:
 // oracle/slam_oracle_pf.c orc_ekf_update), written once for every kernel that applies it: the row walk, the grouped row
-// walk, the compact observation list (ekf_kernels.hip) and the paged update (paged_kernels.hip).  T = float (one landmark per
+// walk, the compact observation list (ekf_sparse_kernels.hip) and the paged update (paged_kernels.hip).  T = float (one landmark per
 // lane) or v2f (two landmarks per lane on packed arithmetic: v_pk_mul_f32 / v_pk_add_f32 are IEEE per component, so both
 // give the same bits).  Every multiply and add is rounded separately, in this order (-ffp-contract=off).
 #pragma once

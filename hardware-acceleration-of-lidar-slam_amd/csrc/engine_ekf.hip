@@ -175,24 +175,25 @@ int slam_ekf_update_dev(slam_engine* e, const float* d_map_in, float* d_map_out,
                                                                   : e->h_obs[1] == nlandmarks && 4 * (int64_t)e->h_obs[0] <= nlandmarks);
         const bool build = can_list && !e->obs_list_valid && (sparse || e->ekf_inplace_form < 0);
         const size_t L = (size_t)nlandmarks;
-        int32_t* li = nullptr;
+        ObsListOut ol;     // where the list is built ...
+        ObsListView olv;   // ... and read
         if (build || sparse) {
             if (e->obs_list.cap < 4 * (4 * L + 2)) {
                 SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
                 SLAM_HIP_TRY(e, e->obs_list.ensure(4 * (4 * L + 2)));
                 e->obs_list_valid = false;
             }
-            li = e->obs_list.as<int32_t>();
+            int32_t* li = e->obs_list.as<int32_t>();
+            ol = ObsListOut{ li, (float*)(li + L), (float*)(li + 2 * L), li + 3 * L, li + 4 * L };
+            olv = ObsListView{ ol.id, ol.zx, ol.zy, ol.round, ol.count };
         }
         auto build_list = [&]() -> hipError_t {
             e->obs_list_valid = true;
-            const ObsListOut ol{ li, (float*)(li + L), (float*)(li + 2 * L), li + 3 * L, li + 4 * L };
             return launch_build_obs_list(e->stream, e->d_obs_zx, e->d_obs_zy, nlandmarks, ol, e->d_hobs);
         };
         if (sparse) {
             if (!e->obs_list_valid) SLAM_HIP_TRY(e, build_list());
-            SLAM_HIP_TRY(e, launch_ekf_sparse(e->stream, a, li, (const float*)(li + L), (const float*)(li + 2 * L), li + 3 * L,
-                                              li + 4 * L, e->prof_next(SLAM_PROF_EKF)));
+            SLAM_HIP_TRY(e, launch_ekf_sparse(e->stream, a, olv, e->prof_next(SLAM_PROF_EKF)));
         } else {
             SLAM_HIP_TRY(e, launch_ekf_update(e->stream, a, e->prof_next(SLAM_PROF_EKF), 0));
             if (build) SLAM_HIP_TRY(e, build_list());   // after the update: only the count for the next frames is wanted

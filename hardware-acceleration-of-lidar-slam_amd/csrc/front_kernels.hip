@@ -1,0 +1,121 @@
+// front_kernels.hip — the landmark update fused with the scorer into the front of a frame.
+// ---- the FRONT of a single-GPU frame in one launch: motion sample + scan-match score (score_body.h) and the grouped
+// out-of-place landmark update side by side.  The two are bound by different units — the scorer by the texture addresser
+// (gathers out of L2), the update by HBM writes — and neither needs the other's output: both start from the resample
+// indices and the previous poses (the update works out its particles' motion samples itself).  As two launches they run one
+// after the other (a second stream with an event fork and join costs more than it wins: DESIGN.md section 11.5); here the
+// workgroups of both kinds are dealt out interleaved — of every `score_octets + ekf_octets` consecutive octets of workgroups
+// (an octet = one workgroup per XCD) the scoring ones are spread evenly — so the gathers run in the shadow of the row
+// stores.  Same bits as the two launches (same device functions).
+
+#include "ekf_group_body.h"
+#include "ekf_split_body.h"
+#include "score_body.h"
+
+namespace slam {
+
+namespace {
+
+struct FrontArgs {
+    ScoreGrid g;
+    const float *bx, *by;
+    int nbeams;
+    float* score;
+    int32_t* count;
+    MotionIO mio;
+    MotionParams mpar;
+    EkfArgs a;
+    int score_blocks;    // 256-thread slices of poses to score
+    int score_octets;    // ceil(score_blocks / 8)
+    int ekf_octets;      // update workgroups per XCD (the xcd_chunk of ekf_update_group_kernel)
+    int score_span;      // the scoring octets lie among the first score_span octets of the grid
+};
+
+template <int NB, int G, int LPP, int DEPTH, bool SPLIT = false, bool PACKED = false>
+__global__ __launch_bounds__(kEkfWaves * 64) __attribute__((amdgpu_waves_per_eu(SPLIT ? kEkfSplitWpe : kEkfGroupWpe, SPLIT ? kEkfSplitWpe : kEkfGroupWpe)))
+void frame_front_kernel(FrontArgs f)
+{
+    static_assert(kScoreBlock == kEkfWaves * 64, "both kinds of workgroup have 256 threads");
+    extern __shared__ float4 s_pair[];
+    __shared__ float s_acc[kEkfWaves][G][128];
+    const int o = (int)blockIdx.x >> 3, xcd = (int)blockIdx.x & 7;
+    // the scoring octets are spread evenly over the first `span` octets of the grid: the whole grid (against the first part of it
+    // only — 64k x 500, 4 / 2 particles per updating wavefront: 100 % 130.7 / 158.5 us, 75 % 134.0 / 156.3, 50 % 155.1 / 154.8,
+    // 25 % 141.2 / 157.9)
+    const int64_t span = f.score_span;
+    const int before = o < span ? (int)((int64_t)o * f.score_octets / span) : f.score_octets;             // scoring octets among 0 .. o - 1
+    const int upto = o + 1 < span ? (int)((int64_t)(o + 1) * f.score_octets / span) : f.score_octets;    // ... among 0 .. o
+    if (upto > before) {   // a scoring octet (wave-uniform, workgroup-uniform)
+        const int sb = before * 8 + xcd;
+        if (sb >= f.score_blocks) return;
+        score_poses_body<false, LPP, DEPTH, true, PACKED>(f.g, f.bx, f.by, f.nbeams, f.mio.x, f.mio.y, f.mio.th, nullptr, f.a.n,
+                                                          f.score, f.count, f.mio, f.mpar, sb, s_pair);
+    } else if constexpr (SPLIT) {
+        ekf_split_body<NB, G, true>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar);
+    } else {
+        ekf_group_body<NB, G, true>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar);
+    }
+}
+
+int update_blocks(int n, int group_size) { return (n + kEkfWaves * group_size - 1) / (kEkfWaves * group_size); }
+}  // namespace
+
+bool frame_front_fits(int n, int nlandmarks, int group_size)
+{
+    if (n < kWaveMaxPoses || nlandmarks <= 128 || (group_size != 2 && group_size != 4 && group_size != 8)) return false;
+    return update_blocks(n, group_size) >= 64;
+}
+
+// The front of a single-GPU frame in one launch (frame_front_kernel).  *launched = false when the shapes do not fit it (few
+// particles: the one-wavefront-per-pose scorer; short rows; too few update workgroups for the XCD-contiguous numbering): the
+// caller then issues the two launches.
+hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const float* bx, const float* by, int nbeams,
+                              const MotionIO& io, int64_t first_id, const float dp[3], const float sigma[3], uint64_t seed,
+                              uint32_t frame, float* score, int32_t* count, const EkfArgs& a_in, int group_size,
+                              const EventPair* ev, bool* launched, int* lanes_per_pose)
+{
+    *launched = false;
+    const int n = a_in.n;
+    if (!a_in.cov && group_size == 8) group_size = 4;   // rows: 2 or 4 particles per updating wavefront
+    if (a_in.map_in == a_in.map_out || !frame_front_fits(n, a_in.nlandmarks, group_size)) return hipSuccess;
+    const int G = group_size;
+    const bool quad = n < kQuadMaxPoses;
+    FrontArgs f;
+    f.g = g;
+    f.bx = bx;
+    f.by = by;
+    f.nbeams = nbeams;
+    f.score = score;
+    f.count = count;
+    f.mio = io;
+    f.mpar = make_motion_params(first_id, dp, sigma, seed, frame);
+    f.a = a_in;
+    f.ekf_octets = (update_blocks(n, G) + 7) / 8;
+    f.a.xcd_chunk = f.ekf_octets;
+    f.score_blocks = (int)(((quad ? 4L : 1L) * n + kScoreBlock - 1) / kScoreBlock);
+    f.score_octets = (f.score_blocks + 7) / 8;
+    f.score_span = f.score_octets + f.ekf_octets;
+    const int grid = 8 * f.score_span;
+    const size_t lds = sizeof(float2) * (size_t)(nbeams + (quad ? 4 * kQuadDepth : kLaneDepth)) + (g.packed ? 1024 : 0);
+    if (ev) (void)hipEventRecord(ev->start, stream);
+    // the instantiation: particles per updating wavefront (8: split only) x scorer's lane mapping x map layout x grid copy read
+#define SLAM_FRONT(G_, SP_, PK_)                                                                                                  \
+    do {                                                                                                                          \
+        constexpr int NB_ = (SP_) ? kEkfSplitNb : kEkfGroupNb;                                                                    \
+        if (quad) frame_front_kernel<NB_, G_, 4, kQuadDepth, SP_, PK_><<<grid, kEkfWaves * 64, lds, stream>>>(f);                 \
+        else frame_front_kernel<NB_, G_, 1, kLaneDepth, SP_, PK_><<<grid, kEkfWaves * 64, lds, stream>>>(f);                      \
+    } while (0)
+#define SLAM_FRONT_PK(G_, SP_) do { if (f.g.packed) SLAM_FRONT(G_, SP_, true); else SLAM_FRONT(G_, SP_, false); } while (0)
+    if (G == 2) { if (f.a.cov) SLAM_FRONT_PK(2, true); else SLAM_FRONT_PK(2, false); }
+    else if (G == 8 && f.a.cov) SLAM_FRONT_PK(8, true);
+    else if (f.a.cov) SLAM_FRONT_PK(4, true);
+    else SLAM_FRONT_PK(4, false);
+#undef SLAM_FRONT_PK
+#undef SLAM_FRONT
+    if (ev) (void)hipEventRecord(ev->stop, stream);
+    *launched = true;
+    if (lanes_per_pose) *lanes_per_pose = quad ? 4 : 1;
+    return hipGetLastError();
+}
+
+}  // namespace slam

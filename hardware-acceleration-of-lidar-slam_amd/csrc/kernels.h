@@ -102,7 +102,7 @@ enum { EDT_MAX_RADIUS = 32 };
 hipError_t launch_edt(hipStream_t stream, const int32_t* occ, int ld, int rows, int cols, float cap, float* out,
                       const EventPair* ev = nullptr);
 
-// ---- ekf_kernels.hip (rows A9-A10; no reference counterpart): motion sample and landmark update
+// ---- ekf_kernels.hip, front_kernels.hip, ekf_sparse_kernels.hip (rows A9-A10; no reference counterpart): motion sample and landmark update
 hipError_t launch_motion_sample(hipStream_t stream, const float* sx, const float* sy, const float* sth,
                                 const int32_t* anc, float* x, float* y, float* th, int n, int64_t first_id,
                                 const float dp[3], const float sigma[3], uint64_t seed, uint32_t frame);
@@ -185,8 +185,7 @@ struct ObsListOut {   // where launch_build_obs_list and launch_page_list leave 
     int32_t *round = nullptr, *count = nullptr;
 };
 hipError_t launch_build_obs_list(hipStream_t stream, const float* tzx, const float* tzy, int L, const ObsListOut& ol, int32_t* h_count);
-hipError_t launch_ekf_sparse(hipStream_t stream, const EkfArgs& a, const int32_t* id, const float* zx, const float* zy,
-                             const int32_t* round, const int32_t* count, const EventPair* ev = nullptr);
+hipError_t launch_ekf_sparse(hipStream_t stream, const EkfArgs& a, const ObsListView& ol, const EventPair* ev = nullptr);
 // measurement support: rows of 5 x plane_stride floats copied with the update's access shape (slam_profile_copy_ceiling)
 hipError_t launch_copy_rows(hipStream_t stream, const float* in, float* out, int n, int plane_stride);
 // every float in the fast reciprocal's range, ekf_rcp_core against IEEE division

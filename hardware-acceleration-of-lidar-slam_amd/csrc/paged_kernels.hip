@@ -11,7 +11,7 @@
 // pages without this frame's stamp (a compaction: count, offsets, scatter).
 //
 // Arithmetic, its order and the log-likelihood summation order (landmark l adds to accumulator l mod 128 in order of l,
-// then j + (j + 64), then the xor butterfly) are those of ekf_batches in ekf_kernels.hip: a paged and a row-per-particle
+// then j + (j + 64), then the xor butterfly) are those of ekf_batches in ekf_row_body.h: a paged and a row-per-particle
 // session give the same bits (tests/test_gpu_paged.py).
 // No counterpart in the reference (it has no particles or landmarks).
 
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(1024) void page_list_kernel(const float* __restrict
                                                          int32_t* __restrict__ h_touched, ObsListOut ol)
 {
     // ol.id != nullptr (L <= kObsListMaxLandmarks): the same pass also makes the compact observation list of
-    // build_obs_list_kernel (ekf_kernels.hip) with the same step (storage_bodies.h)
+    // build_obs_list_kernel (ekf_sparse_kernels.hip) with the same step (storage_bodies.h)
     __shared__ unsigned s_bits[kObsListMaxLandmarks / 32];
     __shared__ int s_wave[16], s_wobs[16];
     __shared__ int s_base, s_obase, s_max_round;

@@ -1,4 +1,4 @@
-// pf_common.h — what the particle-filter units (ekf_kernels.hip, paged_kernels.hip, split_kernels.hip, resample_kernels.hip, shard_kernels.hip) share.
+// pf_common.h — what the particle-filter units (ekf_kernels.hip, front_kernels.hip, ekf_sparse_kernels.hip, paged_kernels.hip, split_kernels.hip, resample_kernels.hip, shard_kernels.hip) share.
 #pragma once
 #include "kernels.h"
 

@@ -1,6 +1,6 @@
 // score_body.h — the scan-match score of a slice of poses as a device function (semantics restated from
 // Subsystem_1/main.c:381-596, see score_kernels.hip): the body of score_poses_kernel, shared with the fused front kernel of
-// a particle-filter frame (ekf_kernels.hip: scoring workgroups and landmark-update workgroups in ONE launch).
+// a particle-filter frame (front_kernels.hip: scoring workgroups and landmark-update workgroups in ONE launch).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,7 +54,7 @@ __device__ __forceinline__ float quad_bcast(float v)
 // MOTION: the pose is not read but produced — pose' = motion_sample(src[anc[i]]) (row A9) — written to
 // (px,py,p2) by the pose's first lane and scored in the same launch (saves a launch and a pose round trip).
 // `block`: which 256-thread slice of the poses this workgroup takes (blockIdx.x of score_poses_kernel; the fused front kernel
-// of a frame, ekf_kernels.hip, hands its scoring workgroups their slice); s_pair: nb_pad / 2 float4 of LDS.
+// of a frame, front_kernels.hip, hands its scoring workgroups their slice); s_pair: nb_pad / 2 float4 of LDS.
 template <bool HAS_CS, int LPP, int DEPTH, bool MOTION, bool PACKED = false>
 __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float* __restrict__ bx, const float* __restrict__ by,
                                                  int nbeams, float* __restrict__ px, float* __restrict__ py,

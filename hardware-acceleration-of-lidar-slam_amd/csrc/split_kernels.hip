@@ -23,7 +23,7 @@
 // in use, landmark), against 20 + 20.
 //
 // This file: the conversions rows <-> split, the gather of a frame without an update.  The particles'
-// update on this layout is ekf_split_body in ekf_kernels.hip (it shares the grouped row kernel's machinery).
+// update on this layout is ekf_split_body in ekf_split_body.h (it shares the grouped row kernel's machinery).
 
 #include "cov_update_body.h"
 #include "pf_common.h"

@@ -1,5 +1,5 @@
 // Device bodies that the map-storage kernels of more than one unit run, each written once: the ordered compaction of the
-// observation table (build_obs_list_kernel of ekf_kernels.hip and page_list_kernel of paged_kernels.hip feed the same
+// observation table (build_obs_list_kernel of ekf_sparse_kernels.hip and page_list_kernel of paged_kernels.hip feed the same
 // list-form updates, so their lists must agree bit for bit) and a migrated record's covariances as a class of its own
 // (the unpackers of split_kernels.hip and paged_kernels.hip).
 // No counterpart in the reference (it has no particles or landmarks).

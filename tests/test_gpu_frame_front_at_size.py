@@ -1,4 +1,4 @@
-"""frame_front_kernel (csrc/ekf_kernels.hip: motion sample + scan-match score + grouped landmark update in ONE launch — the
+"""frame_front_kernel (csrc/front_kernels.hip: motion sample + scan-match score + grouped landmark update in ONE launch — the
 kernel every headline number of bench.py runs) against the CPU specification DIRECTLY, at the shapes those numbers are
 quoted on: 65 536 x 500 (BASELINE configs[1], all landmarks observed and the 32 nearest), 1 048 576 x 1 000 (the north-star
 workload) and 524 288 x 5 000 (configs[4]'s per-GPU share) — bench.py's own world (1024 x 1024 EDT, 360 beams, its room,

@@ -84,6 +84,9 @@ def _rand_map(rng, L, rows, Lp=None):
     (300, 700, 704, 641, True),      # accumulators reused across batches, partial last batch, 59 copied through
     (1, 3, 3, 3, False), (4097, 33, 64, 33, True), (256, 10, 32, 0, True), (130, 128, 128, 128, False),
     (77, 129, 160, 129, True), (64, 300, 320, 1, True), (50, 257, 257, 200, True), (9, 1, 1, 1, False),
+    (3, 300, 320, 150, True),        # fewer particles than a group of either size; two full passes of 128 plus a tail
+    (5, 257, 384, 257, True),        # a full group + a partly filled one at 4 per wavefront, odd n at 2; one landmark in the last batch
+    (1, 129, 256, 129, False),       # a single particle, no gather index
 ])
 @pytest.mark.parametrize("form", [0, 1, 2])
 def test_ekf_update(eng, orc, n, L, Lp, nobs, with_anc, form):

@@ -1,4 +1,4 @@
-"""The SPLIT layout of the landmark maps (csrc/split_kernels.hip, ekf_split_body in csrc/ekf_kernels.hip): means per particle,
+"""The SPLIT layout of the landmark maps (csrc/split_kernels.hip, ekf_split_body in csrc/ekf_split_body.h): means per particle,
 covariances per covariance class.  The layout is not part of the specification: a split session must give the bits of a row
 session — poses, maps, heaviest particle, frame after frame — whatever the classes look like (one for the whole population;
 one per particle; anything between), for every row length (whole passes, tails, rows shorter than a batch), fused with the
@@ -121,7 +121,8 @@ def _same(a, b):
     (16384, 300, "own", -1, None), (16384, 300, "shared", -1, None), (16384, 300, "families", 1, None),
     (5000, 513, "families", -1, None), (6001, 700, "own", 2, None), (140000, 200, "families", -1, None),
     (3073, 130, "own", -1, 37), (4099, 129, "shared", 1, 1), (4096, 100, "families", -1, None), (2048, 300, "own", -1, None),
-    (3000, 31, "families", -1, None), (1500, 5000, "families", -1, None)])
+    (3000, 31, "families", -1, None), (1500, 5000, "families", -1, None),
+    (5, 300, "own", -1, None), (13, 257, "families", 2, None)])   # a wavefront with fewer particles than its group; a partly filled last group
 def test_split_gives_the_bits_of_rows(n, L, cov, form, nbeams):
     frames = 7
     rows = _run("rows", n, L, frames, cov, True, form, nbeams)
