@@ -77,6 +77,9 @@ SIGNATURES = {
     "slam_fastmatch_host": (_i, [_vp, _i, _fp, _fp, _fp, _vp, C.POINTER(C.c_int32), _fp]),
     "slam_motion_sample_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _fp, _fp, _u64, _u32]),
     "slam_motion_score_dev": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _fp, _fp, _u64, _u32, _vp, _vp]),
+    "slam_refine_poses_dev": (_i, [_vp, _i, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _vp]),
+    "slam_motion_refine_dev": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _fp, _fp, _u64, _u32, _f, _f, _i, _vp,
+                               _vp]),
     "slam_obs_upload_host": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
     "slam_obs_set_dev": (_i, [_vp, _vp, _vp, _i]),
     "slam_logweight_ekf_dev": (_i, [_vp, _vp, _f, _i, _vp, _vp]),
@@ -140,6 +143,7 @@ SIGNATURES = {
     "slam_pf_set_poses_host": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_set_map_host": (_i, [_vp, _vp]),
     "slam_pf_step": (_i, [_vp, _i, _fp, _i]),
+    "slam_pf_refine_set": (_i, [_vp, _f, _f, _i]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
     "slam_pf_get_poses_host": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_map_host": (_i, [_vp, _vp]),
@@ -347,6 +351,18 @@ class Engine:
         self._ck(self.lib.slam_motion_score_dev(self.h, slot, _ptr(src[0]), _ptr(src[1]), _ptr(src[2]), _ptr(anc),
                                                 _ptr(dst[0]), _ptr(dst[1]), _ptr(dst[2]), n, first_id, _f3(dp),
                                                 _f3(sigma), seed, frame, _ptr(d_score), _ptr(d_count)), "motion_score_dev")
+
+    def refine_poses_dev(self, slot, d_x, d_y, d_th, n, step_xy, step_theta, sweeps, d_score, d_count):
+        """`sweeps` sweeps of the 27-pose lattice around every pose, in place; d_score / d_count: those of the final pose."""
+        self._ck(self.lib.slam_refine_poses_dev(self.h, slot, _ptr(d_x), _ptr(d_y), _ptr(d_th), n, step_xy, step_theta, sweeps,
+                                                _ptr(d_score), _ptr(d_count)), "refine_poses_dev")
+
+    def motion_refine_dev(self, slot, src, anc, dst, n, first_id, dp, sigma, seed, frame, step_xy, step_theta, sweeps, d_score,
+                          d_count):
+        self._ck(self.lib.slam_motion_refine_dev(self.h, slot, _ptr(src[0]), _ptr(src[1]), _ptr(src[2]), _ptr(anc),
+                                                 _ptr(dst[0]), _ptr(dst[1]), _ptr(dst[2]), n, first_id, _f3(dp), _f3(sigma),
+                                                 seed, frame, step_xy, step_theta, sweeps, _ptr(d_score), _ptr(d_count)),
+                 "motion_refine_dev")
 
     def obs_set_dev(self, d_zx_by_landmark, d_zy_by_landmark, nlandmarks):
         """Observation table on the device: entry l = observation of landmark l, NaN in zx = not observed."""
@@ -726,6 +742,10 @@ class PfSession:
 
     def step(self, slot, dp, use_observations=False):
         self.e._ck(self.e.lib.slam_pf_step(self.h, slot, _f3(dp), 1 if use_observations else 0), "pf_step")
+
+    def refine_set(self, step_xy: float, step_theta: float, sweeps: int):
+        """sweeps in 1..16: every frame refines its motion samples on the 27-pose lattice; 0 switches it off."""
+        self.e._ck(self.e.lib.slam_pf_refine_set(self.h, step_xy, step_theta, sweeps), "pf_refine_set")
 
     def best(self):
         pose = (C.c_float * 3)()

@@ -59,6 +59,45 @@ int slam_motion_score_rider_dev(slam_engine* e, int slot, const float* d_src_x, 
     return SLAM_OK;
 }
 
+static bool refine_args_ok(float step_xy, float step_theta, int sweeps)
+{
+    return sweeps >= 1 && sweeps <= 16 && step_xy >= 0.0f && step_theta >= 0.0f && step_xy <= std::numeric_limits<float>::max() &&
+           step_theta <= std::numeric_limits<float>::max();   // (NaN fails every comparison)
+}
+
+int slam_refine_poses_dev(slam_engine* e, int slot, float* d_x, float* d_y, float* d_th, int n, float step_xy, float step_theta,
+                          int sweeps, float* d_score, int32_t* d_count)
+{
+    SLAM_ENTER(e);
+    if (n < 0 || !refine_args_ok(step_xy, step_theta, sweeps) || (n > 0 && (!d_x || !d_y || !d_th || !d_score || !d_count)))
+        return SLAM_ERR_INVALID_ARG;
+    if (int rc = check_score_inputs(e, slot)) return rc;
+    ScoreGrid sg;
+    if (int rc = many_pose_grid(e, slot, n, &sg)) return rc;
+    SLAM_HIP_TRY(e, launch_refine_poses(e->stream, sg, e->d_bx, e->d_by, e->nbeams, d_x, d_y, d_th, n, step_xy, step_theta, sweeps,
+                                        d_score, d_count, e->prof_next(SLAM_PROF_SCORE)));
+    return SLAM_OK;
+}
+
+int slam_motion_refine_dev(slam_engine* e, int slot, const float* d_src_x, const float* d_src_y, const float* d_src_th,
+                           const int32_t* d_anc, float* d_x, float* d_y, float* d_th, int n, int64_t first_id, const float dp[3],
+                           const float sigma[3], uint64_t seed, uint32_t frame, float step_xy, float step_theta, int sweeps,
+                           float* d_score, int32_t* d_count)
+{
+    SLAM_ENTER(e);
+    if (n < 0 || first_id < 0 || !dp || !sigma || !refine_args_ok(step_xy, step_theta, sweeps) ||
+        (n > 0 && (!d_src_x || !d_src_y || !d_src_th || !d_x || !d_y || !d_th || !d_score || !d_count)))
+        return SLAM_ERR_INVALID_ARG;
+    if (n > 0 && (d_src_x == d_x || d_src_y == d_y || d_src_th == d_th)) return SLAM_ERR_INVALID_ARG;   // several lanes re-read src
+    if (int rc = check_score_inputs(e, slot)) return rc;
+    const MotionIO io{ d_src_x, d_src_y, d_src_th, d_anc, d_x, d_y, d_th, FreeListRider() };
+    ScoreGrid sg;
+    if (int rc = many_pose_grid(e, slot, n, &sg)) return rc;
+    SLAM_HIP_TRY(e, launch_motion_refine(e->stream, sg, e->d_bx, e->d_by, e->nbeams, io, n, first_id, dp, sigma, seed, frame, step_xy,
+                                         step_theta, sweeps, d_score, d_count, e->prof_next(SLAM_PROF_SCORE)));
+    return SLAM_OK;
+}
+
 int slam_obs_upload_host(slam_engine* e, const int32_t* landmark_id, const float* zx, const float* zy, int nobs,
                          int nlandmarks)
 {

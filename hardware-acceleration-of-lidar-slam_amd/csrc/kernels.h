@@ -97,6 +97,19 @@ hipError_t launch_lattice_pair(hipStream_t stream, const ScoreGrid& g1, const Sc
                                const int32_t* d_nbeams, const float* cand1, const float* pair_in, float* work1, float* work2, float* out1,
                                float* out2, float* persist, float* host_out1, float* host_out2, uint32_t* host_flag, uint32_t seq);
 
+// ---- refine_kernels.hip (DESIGN.md §7 "Refinement"; no reference counterpart: FastMatch's lattice around every pose)
+// `sweeps` sweeps of the 3 x 3 x 3 lattice (steps step_xy on x and y, step_theta on the heading; headings through det_sincosf)
+// around each of nposes poses, the centre as incumbent; x / y / th are read and overwritten with the final pose, score / count
+// are those of that pose as launch_score_poses gives them.  Uses g.packed when present, at any pose count.
+hipError_t launch_refine_poses(hipStream_t stream, const ScoreGrid& g, const float* bx, const float* by, int nbeams, float* x, float* y,
+                               float* th, int nposes, float step_xy, float step_theta, int sweeps, float* score, int32_t* count,
+                               const EventPair* ev = nullptr);
+// ... around pose' = motion(src[anc]) (launch_motion_sample's bits); io.x / io.y / io.th receive the refined pose only
+hipError_t launch_motion_refine(hipStream_t stream, const ScoreGrid& g, const float* bx, const float* by, int nbeams, const MotionIO& io,
+                                int nposes, int64_t first_id, const float dp[3], const float sigma[3], uint64_t seed, uint32_t frame,
+                                float step_xy, float step_theta, int sweeps, float* score, int32_t* count,
+                                const EventPair* ev = nullptr);
+
 // ---- edt_kernels.hip (row A6; reference: main.c:223-269, main_accelerated.c:215-283)
 enum { EDT_MAX_RADIUS = 32 };
 hipError_t launch_edt(hipStream_t stream, const int32_t* occ, int ld, int rows, int cols, float cap, float* out,

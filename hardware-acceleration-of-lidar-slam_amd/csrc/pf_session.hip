@@ -9,6 +9,7 @@
 // "handle created once in main and threaded through" is the reference's (Hadrware_acclereated.cpp:842-845, 284).
 
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -111,6 +112,9 @@ struct slam_pf {
     void* split_scratch = nullptr;  // flags, prefix sums of a rows -> split move
     bool gated = false;             // cfg.resample_ess_frac in (0, 1): a frame resamples only when its ESS is low
     int64_t frames_resampled = 0;   // (as far as the host has looked: one frame behind)
+    // slam_pf_refine_set: sweeps > 0: the front launch of a frame is motion + refine (refine_kernels.hip), never the fused front
+    float refine_step_xy = 0.0f, refine_step_theta = 0.0f;
+    int refine_sweeps = 0;
     // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe (RES_OBS) and moves between split and
     // split pages while it runs (between rows and pages when it could not have the split layout's tables)
     int layout_cfg = SLAM_MAP_AUTO;
@@ -873,6 +877,26 @@ int front_stage(slam_pf* pf, FrameFacts& f, int slot, const float dp[3])
     // Sharded, split, ungated: the launch scores every particle (poses out of the all-gathered array) and updates the groups
     // whose ancestors are all rows of this rank; the groups with an ancestor in the staging tail follow behind the exchange
     // (update_split).  Like the motion + score launch it replaces, it goes out before the host has looked at the plan.
+    // Refining session: motion + refine, the frame as it runs while SLAM_PROF_SCORE is timed — no fused front (its update would
+    // work out the UNREFINED sample again): the update stages read the refined poses from dst.
+    if (pf->refine_sweeps > 0) {
+        const float* ps = f.src;
+        const int32_t* pose_anc = f.anc;
+        if (comm && pf->has_anc) {
+            if (int rc = comm_all_gather_finish(comm)) return rc;
+            ps = pf->pose_all;
+            pose_anc = pf->pose_idx[cur];
+        }
+        if (int rc = slam_motion_refine_dev(e, slot, ps, ps + sn, ps + 2 * sn, pose_anc, dst, dst + sn, dst + 2 * sn, n, f.first_id, dp,
+                                            pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->refine_step_xy, pf->refine_step_theta,
+                                            pf->refine_sweeps, pf->score, pf->count))
+            return rc;
+        if (f.paged_listed) {
+            const ProfScope prof(e, SLAM_PROF_PAGES);
+            return issue_free_list(pf);
+        }
+        return SLAM_OK;
+    }
     const bool front = comm ? pf->split && !pf->paged && pf->has_anc && !pf->gated : !pf->paged && (!pf->gated || pf->split);
     if (front && f.anc && f.observing) {
         const float* ps = f.src;
@@ -1407,6 +1431,16 @@ int slam_pf_step(slam_pf* pf, int slot, const float dp[3], int use_observations)
     // staging area might overflow: bit 1 of the plan) is not such a failure.
     if (rc != SLAM_OK && pf->comm && !collective_verdict) (void)comm_abort(pf->comm);
     return rc;
+}
+
+int slam_pf_refine_set(slam_pf* pf, float step_xy, float step_theta, int sweeps)
+{
+    if (!pf || sweeps < 0 || sweeps > 16) return SLAM_ERR_INVALID_ARG;
+    if (sweeps > 0 && !(step_xy >= 0.0f && step_theta >= 0.0f && step_xy <= FLT_MAX && step_theta <= FLT_MAX)) return SLAM_ERR_INVALID_ARG;
+    pf->refine_step_xy = sweeps ? step_xy : 0.0f;
+    pf->refine_step_theta = sweeps ? step_theta : 0.0f;
+    pf->refine_sweeps = sweeps;
+    return SLAM_OK;
 }
 
 int slam_pf_rows_received(const slam_pf* pf) { return pf ? pf->rows_received : 0; }

@@ -19,9 +19,12 @@
  * the number of GPUs (bit for bit: pose log and map file).
  *
  * usage: slam_pf_main dataset.csv frames beams map_out.csv particles [seed [mean|best]]
- *                     [--gpus N] [--transport rccl|local] [--same-device] [--ess F]
+ *                     [--gpus N] [--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]]
  *   particles      the whole population (a multiple of N)
  *   --ess F        ESS-gated resampling: resample only in frames whose effective sample size is below F * N
+ *   --refine SWEEPS  scan-match refinement of every particle (slam_pf_refine_set): SWEEPS (1..16) sweeps of the reference's
+ *                  27-pose lattice around each motion sample, the particle weighted at the pose it ends on
+ *   --refine-res T R  its steps in metres and radians (default: the reference's fastResolution2, 0.025 0.004363; main.c:833)
  *   --transport    rccl (default when N > 1): RCCL, one GPU per rank.  local: the in-process transport.
  *   --same-device  every rank on device 0 (only with the local transport; RCCL refuses two ranks on one GPU)
  */
@@ -48,6 +51,8 @@ typedef struct {
     int frames, beams, particles_total, use_mean;
     unsigned long long seed;
     float ess_frac;        /* --ess F: resample only when the effective sample size is below F * N (0: every frame) */
+    int refine_sweeps;     /* --refine SWEEPS (0: off) */
+    float refine_res[2];   /* --refine-res T R */
     /* the ranks */
     int world, use_rccl, same_device;
     uint8_t comm_id[SLAM_COMM_ID_BYTES];
@@ -107,6 +112,7 @@ static void *rank_main(void *arg)
     } else {
         CHECK(slam_pf_create(eng, &cfg, &pf));
     }
+    if (run->refine_sweeps) CHECK(slam_pf_refine_set(pf, run->refine_res[0], run->refine_res[1], run->refine_sweeps));
     if (fe_scan_init(&scan, beams, -2.351831f, 0.004363f) || fe_points_init(&map, FE_MAP_CAPACITY + beams) ||
         fe_points_init(&local, FE_LOCAL_CAPACITY) || fe_grid_init(&coarse, FE_COARSE_LD) || fe_grid_init(&fine, FE_FINE_LD) ||
         !(hits = (float *)calloc((size_t)beams + 1, sizeof(float)))) {
@@ -214,6 +220,8 @@ int main(int argc, char **argv)
     run.world = 1;
     run.use_mean = 1;
     run.seed = 1;
+    run.refine_res[0] = 0.025f;   /* fastResolution2 (main.c:833) */
+    run.refine_res[1] = 0.004363f;
     const char *pos[8];
     int npos = 0, transport_given = 0, use_local = 0;
     for (int a = 1; a < argc; ++a) {
@@ -221,11 +229,16 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[a], "--transport") && a + 1 < argc) { use_local = !strcmp(argv[++a], "local"); transport_given = 1; }
         else if (!strcmp(argv[a], "--same-device")) run.same_device = 1;
         else if (!strcmp(argv[a], "--ess") && a + 1 < argc) run.ess_frac = (float)atof(argv[++a]);
+        else if (!strcmp(argv[a], "--refine") && a + 1 < argc) run.refine_sweeps = atoi(argv[++a]);
+        else if (!strcmp(argv[a], "--refine-res") && a + 2 < argc) {
+            run.refine_res[0] = (float)atof(argv[++a]);
+            run.refine_res[1] = (float)atof(argv[++a]);
+        }
         else if (npos < 8) pos[npos++] = argv[a];
     }
-    if (npos < 5 || run.world < 1 || run.world > 16) {
+    if (npos < 5 || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
-                        "[--transport rccl|local] [--same-device] [--ess F]\n", argv[0]);
+                        "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]]\n", argv[0]);
         return 2;
     }
     run.dataset = pos[0];

@@ -215,6 +215,25 @@ int slam_motion_score_dev(slam_engine *e, int slot, const float *d_src_x, const 
                           int64_t first_id, const float dp[3], const float sigma[3], uint64_t seed, uint32_t frame,
                           float *d_score, int32_t *d_count);
 
+/* Scan-match refinement of every pose ("Refinement"): `sweeps` (1..16) sweeps of the reference's
+ * 3 x 3 x 3 lattice (FastMatch, main.c:424-563) around EACH pose, in one launch.  One sweep: candidates theta -/+ step_theta,
+ * x -/+ step_xy, y -/+ step_xy (one binary32 subtract or add each), every candidate scored exactly as slam_score_poses_dev
+ * scores that pose (headings through the particle path's deterministic sincos, not libm), the centre as the incumbent:
+ * the candidates are visited heading-major, x, y-minor like the reference's, and one replaces the incumbent only with a
+ * strictly lower score — unlike FastMatch, which starts from +inf and walks to candidate 0 when all 27 tie, a pose in free
+ * space or off the grid stays where it is.  The pose becomes the winner and the next sweep is laid around it.  Like the
+ * weights, the comparison is on the raw sum: a candidate with fewer in-bounds beams can win (the reference's behaviour,
+ * SURVEY Q-list).  d_x / d_y / d_th are read and overwritten with the final pose, d_score / d_count receive its score and
+ * in-bounds count.  Steps must be finite and >= 0; n == 0 launches nothing.  Bracketed as SLAM_PROF_SCORE. */
+int slam_refine_poses_dev(slam_engine *e, int slot, float *d_x, float *d_y, float *d_th, int n, float step_xy,
+                          float step_theta, int sweeps, float *d_score, int32_t *d_count);
+/* slam_motion_sample_dev followed by the above, one launch (the unrefined sample is never stored); source and destination
+ * arrays must differ */
+int slam_motion_refine_dev(slam_engine *e, int slot, const float *d_src_x, const float *d_src_y, const float *d_src_th,
+                           const int32_t *d_anc, float *d_x, float *d_y, float *d_th, int n, int64_t first_id,
+                           const float dp[3], const float sigma[3], uint64_t seed, uint32_t frame, float step_xy,
+                           float step_theta, int sweeps, float *d_score, int32_t *d_count);
+
 /* A10: per-particle x per-landmark 2x2 EKF correction (FastSLAM 1.0, known correspondences,
  * cartesian sensor-frame observations z = H (m - t), H = [[ct,-st],[st,ct]], noise R = meas_var * I).  H being a rotation
  * and R isotropic, the update is carried out in the world frame: w = t + H^T z, S = P + R, W = P S^-1, mu' = mu + W (w - mu),
@@ -269,7 +288,9 @@ int slam_ekf_form_counts(slam_engine *e, int64_t counts[2]);
  * measurements).  Paged sessions, gated sessions on rows, sharded sessions
  * on rows, short rows and small populations always take the two launches (a sharded session on the split layout fuses the
  * score with the update of the groups whose ancestors are local), and so does every frame while SLAM_PROF_SCORE is being timed
- * (slam_profile_enable: a fused launch is bracketed as SLAM_PROF_EKF).  slam_frame_fusion_count: fused launches of this engine so far. */
+ * (slam_profile_enable: a fused launch is bracketed as SLAM_PROF_EKF), and every frame of a session that refines its poses
+ * (slam_pf_refine_set: the update must read the REFINED poses, the fused launch would work out the unrefined sample again).
+ * slam_frame_fusion_count: fused launches of this engine so far. */
 int slam_frame_fusion_set(slam_engine *e, int on);
 int slam_frame_fusion_count(slam_engine *e, int64_t *launches);
 /* Which instantiation the LAST fused front launch of this engine was (tests pin the kernel at the shapes its numbers are
@@ -530,6 +551,12 @@ int slam_pf_is_paged(const slam_pf *pf);
 int slam_pf_layout(const slam_pf *pf);
 /* one frame against grid `slot`; asynchronous */
 int slam_pf_step(slam_pf *pf, int slot, const float dp[3], int use_observations);
+/* Scan-match refinement inside the session: with sweeps in 1..16 the first launch of every frame is motion + refine
+ * (slam_motion_refine_dev) instead of motion + score, on every layout, gated or not, sharded or not; the landmark update is a
+ * launch of its own that reads the refined poses, and slam_pf_view.score / count, the weights, slam_pf_best and slam_pf_mean
+ * all see the refined poses and their scores.  sweeps = 0 (the initial state; the steps are then ignored) switches it off.
+ * Sharded: every rank must make the same call. */
+int slam_pf_refine_set(slam_pf *pf, float step_xy, float step_theta, int sweeps);
 /* heaviest particle of the last frame (lowest index on ties): its pose, log-weight and index; synchronises.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
 int slam_pf_best(slam_pf *pf, float pose[3], float *logw, int32_t *index);
