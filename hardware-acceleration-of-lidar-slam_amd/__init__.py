@@ -108,6 +108,7 @@ SIGNATURES = {
     "slam_mapper_first_frame": (_i, [_vp, _vp]),
     "slam_mapper_next_frame": (_i, [_vp, _vp, _fp]),
     "slam_mapper_get_map_host": (_i, [_vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32)]),
+    "slam_mapper_device_view": (_i, [_vp, _vp]),
     "slam_exchange_set_capacity": (_i, [_vp, _i]),
     "slam_ekf_form_set": (_i, [_vp, _i]),
     "slam_ekf_form_counts": (_i, [_vp, _vp]),
@@ -524,6 +525,83 @@ class MapperParams(C.Structure):
     def as_list(self):
         return list(self.fast_res) + list(self.fast_res2) + [self.border, self.pixel, self.pixel2, self.key_dt, self.key_dr,
                                                              self.range_min, self.usable_range, self.edt_cap, self.new_point_threshold]
+
+
+class MapperView(C.Structure):
+    """``slam_mapper_view``"""
+
+    _fields_ = [("bx", C.c_void_p), ("by", C.c_void_p), ("tx", C.c_void_p), ("ty", C.c_void_p), ("mx", C.c_void_p),
+                ("my", C.c_void_p), ("lx", C.c_void_p), ("ly", C.c_void_p), ("counts", C.c_void_p), ("occ", C.c_void_p * 2),
+                ("edt", C.c_void_p * 2), ("ld", C.c_int32 * 2), ("meta", C.c_void_p), ("hits", C.c_void_p),
+                ("nhits", C.c_int32), ("pose", C.c_float * 3), ("prev", C.c_float * 3), ("map_pose", C.c_float * 3),
+                ("mini_updated", C.c_int32), ("frame", C.c_int32), ("map_cap", C.c_int32), ("nbeams", C.c_int32)]
+
+
+LOCAL_MAP_CAP = 25000   # the reference's local-map capacity (main.c:148)
+
+
+class Mapper:
+    """``slam_mapper`` — the reference's frame loop with the map, the scan and the grids resident on the device."""
+
+    def __init__(self, engine: "Engine", nbeams: int, angle_min: float, angle_inc: float, params: MapperParams | None = None):
+        self.e, self.nbeams = engine, int(nbeams)
+        h = C.c_void_p()
+        if params is None:
+            rc = engine.lib.slam_mapper_create(engine.h, nbeams, angle_min, angle_inc, C.byref(h))
+        else:
+            rc = engine.lib.slam_mapper_create_ex(engine.h, nbeams, angle_min, angle_inc, C.byref(params), C.byref(h))
+        engine._ck(rc, "mapper_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.e.lib.slam_mapper_destroy(self.h)
+            self.h = None
+
+    def _ranges(self, ranges):
+        r = _np(ranges, np.float32)
+        assert r.shape == (self.nbeams,)
+        return r
+
+    def first_frame(self, ranges):
+        self.e._ck(self.e.lib.slam_mapper_first_frame(self.h, _ptr(self._ranges(ranges))), "mapper_first_frame")
+
+    def next_frame(self, ranges):
+        """-> the matched pose [3]; raises SlamError (``.status``) when the frame fails."""
+        pose = (C.c_float * 3)()
+        self.e._ck(self.e.lib.slam_mapper_next_frame(self.h, _ptr(self._ranges(ranges)), pose), "mapper_next_frame")
+        return np.array(list(pose), np.float32)
+
+    def map(self, capacity: int | None = None, want_points: bool = True):
+        """``slam_mapper_get_map_host``: -> (size, x, y).  x / y hold min(size, capacity) points; capacity None = all of
+        them (two calls), want_points False = the size alone (x, y are None)."""
+        n = C.c_int32(-1)
+        if not want_points:
+            self.e._ck(self.e.lib.slam_mapper_get_map_host(self.h, None, None, 0, C.byref(n)), "mapper_get_map")
+            return n.value, None, None
+        if capacity is None:
+            capacity = self.map(want_points=False)[0]
+        x, y = np.zeros(max(capacity, 1), np.float32), np.zeros(max(capacity, 1), np.float32)
+        self.e._ck(self.e.lib.slam_mapper_get_map_host(self.h, _ptr(x), _ptr(y), capacity, C.byref(n)), "mapper_get_map")
+        return n.value, x[:capacity], y[:capacity]
+
+    def view(self):
+        """dict of DeviceArray views of the mapper's own buffers and a copy of its host state (``slam_mapper_device_view``).
+        Valid until the next call on the mapper; synchronise (``Engine.sync``) first."""
+        v = MapperView()
+        self.e._ck(self.e.lib.slam_mapper_device_view(self.h, C.byref(v)), "mapper_device_view")
+        nb, cap = v.nbeams, v.map_cap
+        d = {k: DeviceArray(getattr(v, k), (n,), "<f4", self)
+             for k, n in (("bx", nb), ("by", nb), ("tx", nb), ("ty", nb), ("hits", nb), ("mx", cap), ("my", cap),
+                          ("lx", LOCAL_MAP_CAP), ("ly", LOCAL_MAP_CAP))}
+        d["counts"] = DeviceArray(v.counts, (3,), "<i4", self)
+        d["occ"] = [DeviceArray(v.occ[k], (v.ld[k], v.ld[k]), "<i4", self) for k in (0, 1)]
+        d["edt"] = [DeviceArray(v.edt[k], (v.ld[k], v.ld[k]), "<f4", self) for k in (0, 1)]
+        d["meta"] = DeviceArray(v.meta, (2, 6), "<i4", self)   # two slam_grid_meta records as raw words
+        d.update(ld=[v.ld[0], v.ld[1]], nhits=v.nhits, pose=np.array(list(v.pose), np.float32),
+                 prev=np.array(list(v.prev), np.float32), map_pose=np.array(list(v.map_pose), np.float32),
+                 mini_updated=v.mini_updated, frame=v.frame, map_cap=cap, nbeams=nb)
+        return d
 
 
 class PfConfig(C.Structure):

@@ -274,4 +274,30 @@ int slam_mapper_get_map_host(slam_mapper* m, float* x, float* y, int32_t capacit
     return SLAM_OK;
 }
 
+int slam_mapper_device_view(const slam_mapper* m, slam_mapper_view* out)
+{
+    if (!m || !out) return SLAM_ERR_INVALID_ARG;
+    slam_mapper_view v{};
+    v.bx = m->d_bx; v.by = m->d_by; v.tx = m->d_tx; v.ty = m->d_ty;
+    v.mx = m->d_mx; v.my = m->d_my; v.lx = m->d_lx; v.ly = m->d_ly;
+    v.counts = m->d_counts;
+    for (int k = 0; k < 2; ++k) {
+        v.occ[k] = m->d_occ[k];
+        v.edt[k] = m->d_edt[k];
+    }
+    v.ld[0] = kCoarseLd; v.ld[1] = kFineLd;
+    v.meta = m->d_meta;
+    v.hits = m->d_hits;
+    v.nhits = m->nhits;
+    memcpy(v.pose, m->pose, sizeof v.pose);
+    memcpy(v.prev, m->prev, sizeof v.prev);
+    memcpy(v.map_pose, m->map_pose, sizeof v.map_pose);
+    v.mini_updated = m->mini_updated;
+    v.frame = m->frame;
+    v.map_cap = m->map_cap;
+    v.nbeams = m->nbeams;
+    *out = v;
+    return SLAM_OK;
+}
+
 }  // extern "C"

@@ -669,6 +669,29 @@ int slam_mapper_next_frame(slam_mapper *m, const float *ranges, float pose_out[3
 /* map points (main.c:982-985 writes them as "%f,%f" lines); x/y may be NULL to query the size only */
 int slam_mapper_get_map_host(slam_mapper *m, float *x, float *y, int32_t capacity, int32_t *n);
 
+/* Inspection of a mapper (tests, debugging).  Device pointers into the mapper's own state, valid until the next
+ * slam_mapper_* call, and a copy of its host state.  Synchronises nothing: call slam_engine_sync first.
+ *   bx/by[0 .. counts[0])  the cleaned scan, sensor frame;  tx/ty: its world points as of the last frame that made them
+ *   mx/my[0 .. counts[1])  the map (map_cap floats each);   lx/ly[0 .. counts[2]): the local map of the last rebuild
+ *   counts                 {nscan, msize, lsize}
+ *   occ[k], edt[k]         coarse (k = 0) and fine (k = 1) occupancy grid and distance transform, ld[k] x ld[k] storage
+ *   meta[2]                the two grids' records as the rasteriser wrote them
+ *   hits[0 .. nbeams)      the matcher's persistent hit scratch;  nhits: the best candidate's count (host)
+ *   pose, prev, map_pose, mini_updated, frame: the reference's loop locals (main.c:844-969) */
+typedef struct {
+    const float *bx, *by, *tx, *ty, *mx, *my, *lx, *ly;
+    const int32_t *counts;
+    const int32_t *occ[2];
+    const float *edt[2];
+    int32_t ld[2];
+    const slam_grid_meta *meta;
+    const float *hits;
+    int32_t nhits;
+    float pose[3], prev[3], map_pose[3];
+    int32_t mini_updated, frame, map_cap, nbeams;
+} slam_mapper_view;
+int slam_mapper_device_view(const slam_mapper *m, slam_mapper_view *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,26 @@ class GridMeta(C.Structure):
     ]
 
 
+class SlamParams(C.Structure):
+    """Mirror of ``orc_slam_params`` (slam_oracle.h); same fields, same order as ``slam_mapper_params``."""
+
+    _fields_ = [("fast_res", C.c_float * 3), ("fast_res2", C.c_float * 3), ("border", C.c_float), ("pixel", C.c_float),
+                ("pixel2", C.c_float), ("key_dt", C.c_float), ("key_dr", C.c_float), ("range_min", C.c_float),
+                ("usable_range", C.c_float), ("edt_cap", C.c_float), ("new_point_threshold", C.c_float)]
+
+    @classmethod
+    def default(cls, **changes):
+        p = cls()
+        lib().orc_slam_params_default(C.byref(p))
+        for k, v in changes.items():
+            if k in ("fast_res", "fast_res2"):
+                v = (C.c_float * 3)(*v)
+            elif not hasattr(p, k):
+                raise AttributeError(k)
+            setattr(p, k, v)
+        return p
+
+
 def build(ref: bool = True) -> None:
     """Compile the oracle (and, when /root/reference exists, the reference harness)."""
     targets = ["all"] + (["ref"] if ref else [])
@@ -73,6 +93,21 @@ def lib() -> C.CDLL:
     L.orc_score_poses.argtypes = [P(GridMeta), _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p, C.c_int, _f32p, _i32p]
     L.orc_fastmatch.argtypes = [P(GridMeta), _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p, P(C.c_int),
                                 P(C.c_float)]
+    L.orc_slam_create.argtypes = [C.c_int, C.c_float, C.c_float]
+    L.orc_slam_create.restype = C.c_void_p
+    L.orc_slam_destroy.argtypes = [C.c_void_p]
+    L.orc_slam_params_default.argtypes = [P(SlamParams)]
+    L.orc_slam_set_params.argtypes = [C.c_void_p, P(SlamParams)]
+    L.orc_slam_set_edt_variant.argtypes = [C.c_void_p, C.c_int]
+    L.orc_slam_first_frame.argtypes = [C.c_void_p, _f32p]
+    L.orc_slam_next_frame.argtypes = [C.c_void_p, _f32p, _f32p]
+    L.orc_slam_map_size.argtypes = [C.c_void_p]
+    L.orc_slam_map_size.restype = C.c_int
+    for name in ("orc_slam_map_x", "orc_slam_map_y"):
+        getattr(L, name).argtypes = [C.c_void_p]
+        getattr(L, name).restype = P(C.c_float)
+    L.orc_slam_partial_frames.argtypes = [C.c_void_p]
+    L.orc_slam_partial_frames.restype = C.c_long
     # ---- particle-filter specification (slam_oracle_pf.c)
     _i64, _u64, _u32 = C.c_int64, C.c_uint64, C.c_uint32
     L.orc_det_sincosf_array.argtypes = [_f32p, C.c_int, _f32p, _f32p]
@@ -178,16 +213,72 @@ def score_poses(m: GridMeta, edt_grid, bx, by, x, y, theta):
     return score, count
 
 
-def fastmatch(m: GridMeta, edt_grid, bx, by, pose, res):
-    """-> (pose[3], best_hits (full scratch, nbeams long), best_hits_size, best_score)"""
+def fastmatch(m: GridMeta, edt_grid, bx, by, pose, res, hits=None, hits_size=0):
+    """-> (pose[3], best_hits (full scratch, nbeams long), best_hits_size, best_score).  `hits` (float32, C-contiguous,
+    >= len(bx)) is the reference's persistent scratch, written in place; a zeroed one is made when omitted.  `hits_size`
+    is what best_hits_size keeps when no candidate beats +inf."""
     out = np.empty(3, np.float32)
-    hits = np.zeros(max(len(bx), 1), np.float32)
-    n = C.c_int(0)
+    if hits is None:
+        hits = np.zeros(max(len(bx), 1), np.float32)
+    assert hits.dtype == np.float32 and hits.flags.c_contiguous and len(hits) >= len(bx)
+    n = C.c_int(hits_size)
     sc = C.c_float(0)
     lib().orc_fastmatch(C.byref(m), np.ascontiguousarray(edt_grid, np.float32), np.ascontiguousarray(bx, np.float32),
                         np.ascontiguousarray(by, np.float32), len(bx), np.ascontiguousarray(pose, np.float32),
                         np.ascontiguousarray(res, np.float32), out, hits, C.byref(n), C.byref(sc))
     return out, hits, n.value, np.float32(sc.value)
+
+
+EDT_VARIANTS = {"gather": 0, "scatter": 1, "window": 2}
+
+
+class Slam:
+    """``orc_slam`` — the whole frame loop of the restatement (main.c:844-969)."""
+
+    def __init__(self, nbeams, angle_min, angle_inc, params: SlamParams | None = None, edt_variant="window"):
+        self.nbeams = int(nbeams)
+        self.h = lib().orc_slam_create(nbeams, angle_min, angle_inc)
+        if params is not None:
+            self.set_params(params)
+        self.set_edt_variant(edt_variant)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().orc_slam_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def set_params(self, params: SlamParams):
+        lib().orc_slam_set_params(self.h, C.byref(params))
+
+    def set_edt_variant(self, variant):
+        lib().orc_slam_set_edt_variant(self.h, EDT_VARIANTS.get(variant, variant))
+
+    def _ranges(self, ranges):
+        r = np.ascontiguousarray(ranges, np.float32)
+        assert r.shape == (self.nbeams,)
+        return r
+
+    def first_frame(self, ranges):
+        lib().orc_slam_first_frame(self.h, self._ranges(ranges))
+
+    def next_frame(self, ranges):
+        pose = np.empty(3, np.float32)
+        lib().orc_slam_next_frame(self.h, self._ranges(ranges), pose)
+        return pose
+
+    def map_size(self):
+        return lib().orc_slam_map_size(self.h)
+
+    def map_x(self):
+        return np.ctypeslib.as_array(lib().orc_slam_map_x(self.h), (max(self.map_size(), 1),))[: self.map_size()].copy()
+
+    def map_y(self):
+        return np.ctypeslib.as_array(lib().orc_slam_map_y(self.h), (max(self.map_size(), 1),))[: self.map_size()].copy()
+
+    def partial_frames(self):
+        return int(lib().orc_slam_partial_frames(self.h))
 
 
 def libm_cos_sin(theta):
