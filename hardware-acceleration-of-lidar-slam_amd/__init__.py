@@ -115,6 +115,7 @@ SIGNATURES = {
     "slam_selftest_reciprocal": (_i, [_vp, _vp, _vp]),
     "slam_frame_fusion_set": (_i, [_vp, _i]),
     "slam_frame_fusion_count": (_i, [_vp, _vp]),
+    "slam_survivor_rows_set": (_i, [_vp, _i]),
     "slam_frame_front_last": (_i, [_vp, _vp]),
     "slam_ekf_inplace_form_set": (_i, [_vp, _i]),
     "slam_pf_paged_set": (_i, [_vp, _i]),
@@ -152,6 +153,7 @@ SIGNATURES = {
     "slam_pf_paged_device_view": (_i, [_vp, _vp]),
     "slam_pf_layout": (_i, [_vp]),
     "slam_pf_split_device_view": (_i, [_vp, _vp]),
+    "slam_pf_split_covx_view": (_i, [_vp, _vp]),
 }
 
 _LIB = None
@@ -230,8 +232,9 @@ class Engine:
         self._ck(self.lib.slam_engine_sync(self.h), "sync")
 
     PROF_SCORE, PROF_EDT, PROF_EKF, PROF_WEIGHTS, PROF_SCAN, PROF_ANCESTORS, PROF_PLAN, PROF_PACK, PROF_UNPACK = range(9)
-    PROF_COLLECTIVES, PROF_PAGES, PROF_EKF_TAIL, PROF_COUNT = 9, 10, 11, 12
-    PROF_NAMES = ("score", "edt", "ekf", "weights", "scan", "ancestors", "plan", "pack", "unpack", "collectives", "pages", "ekf_tail")
+    PROF_COLLECTIVES, PROF_PAGES, PROF_EKF_TAIL, PROF_MATERIALISE, PROF_COUNT = 9, 10, 11, 12, 13
+    PROF_NAMES = ("score", "edt", "ekf", "weights", "scan", "ancestors", "plan", "pack", "unpack", "collectives", "pages", "ekf_tail",
+                  "materialise")
 
     def profile_enable(self, *kernels):
         """profile_enable(PROF_EKF, ...) times those kernels; profile_enable() switches timing off."""
@@ -444,6 +447,11 @@ class Engine:
     def frame_fusion_set(self, on: bool):
         """The front of a single-GPU frame on rows (motion + score and the landmark update) as one launch (default) or two."""
         self._ck(self.lib.slam_frame_fusion_set(self.h, 1 if on else 0), "frame_fusion_set")
+
+    def survivor_rows_set(self, on: bool):
+        """Survivor rows (``slam_survivor_rows_set``; default on): a dense split frame writes mean rows only for the particles its
+        resample keeps.  Off: every frame writes every row.  Results are the same bits either way."""
+        self._ck(self.lib.slam_survivor_rows_set(self.h, 1 if on else 0), "survivor_rows_set")
 
     def frame_front_last(self):
         """(particles per updating wavefront, lanes per pose) of the last fused front launch; (0, 0) before the first."""
@@ -774,8 +782,14 @@ class PfSession:
         self.e._ck(self.e.lib.slam_pf_split_device_view(self.h, C.byref(v)), "pf_split_device_view")
         return {"mean": DeviceArray(v.mean, (v.rows, 2, v.plane_stride), "<f4", self) if v.mean else None,   # None: split pages
                 "cov": DeviceArray(v.cov, (v.rows, 3, v.plane_stride), "<f4", self),
+                "covx": DeviceArray(self._split_covx(), (v.rows, 2, v.plane_stride), "<f4", self),
                 "cls": DeviceArray(v.cls, (v.rows,), "<i4", self), "live": DeviceArray(v.live, (v.rows,), "<i4", self),
                 "live_count": DeviceArray(v.live_count, (1,), "<i4", self), "plane_stride": v.plane_stride}
+
+    def _split_covx(self):
+        p = C.c_void_p()
+        self.e._ck(self.e.lib.slam_pf_split_covx_view(self.h, C.byref(p)), "pf_split_covx_view")
+        return p.value
 
     def paged_view(self):
         """``slam_pf_paged_device_view``: the page pool, tables, stamps and free list of a session that is on pages."""

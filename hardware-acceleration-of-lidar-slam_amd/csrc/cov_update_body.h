@@ -38,9 +38,19 @@ __device__ __forceinline__ void cov_update_body(const CovArgs& a, int k, int y)
     if (y == 0 && threadIdx.x == 0) a.live_out[atomicAdd(&a.cnt[(a.phase + 1) % 3], 1)] = c;
     const int l = y * 256 + threadIdx.x;
     if (l >= a.nlandmarks) return;   // (the padding of a row is never observed: it stays as it is)
+    float* row = a.cov + (int64_t)c * a.cov_stride + l;
+    if (a.save_cov) {   // survivor rows: what the particles' update of this frame started from, kept for the launch that repeats it
+        float* sr = a.save_cov + (int64_t)c * a.cov_stride + l;
+        const float* xr = a.covx + (int64_t)c * a.covx_stride + l;
+        float* sx = a.save_covx + (int64_t)c * a.covx_stride + l;
+        sr[0] = row[0];
+        sr[a.plane_stride] = row[a.plane_stride];
+        sr[2 * (int64_t)a.plane_stride] = row[2 * (int64_t)a.plane_stride];
+        sx[0] = xr[0];
+        sx[a.plane_stride] = xr[a.plane_stride];
+    }
     const float zx = a.obs_zx[l], zy = a.obs_zy[l];
     if (!(zx == zx && zy == zy)) return;   // not observed: the prior stays
-    float* row = a.cov + (int64_t)c * a.cov_stride + l;
     const float pxx = row[0], pxy = row[a.plane_stride], pyy = row[2 * (int64_t)a.plane_stride];
     float o2 = a.meas_var, o3 = 0.0f, o4 = a.meas_var;   // a first sighting: q I
     if (!(pxx < 0.0f)) {

@@ -86,6 +86,14 @@ void ekf_split_kernel(EkfArgs a)
     ekf_split_body<NB, G, false>(a, xcd_block(a.xcd_chunk), s_acc, MotionIO{}, MotionParams{});
 }
 
+// the mean rows of the split update alone (ekf_split_body, TALLY = false): survivor rows, launch_ekf_materialise
+template <int NB, int G>
+__global__ __launch_bounds__(kEkfWaves * 64) __attribute__((amdgpu_waves_per_eu(kEkfSplitWpe, kEkfSplitWpe)))
+void ekf_materialise_kernel(EkfArgs a)
+{
+    ekf_split_body<NB, G, false, true, false>(a, xcd_block(a.xcd_chunk), nullptr, MotionIO{}, MotionParams{});
+}
+
 // ---- measurement support (slam_profile_copy_ceiling): the access shape of ekf_update_kernel without its arithmetic
 __global__ __launch_bounds__(kEkfWaves * 64) void copy_rows_kernel(const float* __restrict__ in, float* __restrict__ out, int n,
                                                                    int plane_stride, int xcd_chunk)
@@ -185,6 +193,20 @@ hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const Even
         else kernel = ekf_update_kernel<2, true>;
     }
     const int blocks = xcd_grid(a.n, per_block, a.xcd_chunk);
+    if (ev) (void)hipEventRecord(ev->start, stream);
+    kernel<<<blocks, kEkfWaves * 64, 0, stream>>>(a);
+    if (ev) (void)hipEventRecord(ev->stop, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_ekf_materialise(hipStream_t stream, const EkfArgs& a_in, const EventPair* ev, int group_size)
+{
+    if (a_in.n <= 0) return hipSuccess;
+    EkfArgs a = a_in;
+    const int G = group_size == 4 || group_size == 8 ? group_size : 2;
+    void (*kernel)(EkfArgs) = G == 8 ? ekf_materialise_kernel<kEkfSplitNb, 8>
+                              : G == 4 ? ekf_materialise_kernel<kEkfSplitNb, 4> : ekf_materialise_kernel<kEkfSplitNb, 2>;
+    const int blocks = xcd_grid(a.n, kEkfWaves * G, a.xcd_chunk);
     if (ev) (void)hipEventRecord(ev->start, stream);
     kernel<<<blocks, kEkfWaves * 64, 0, stream>>>(a);
     if (ev) (void)hipEventRecord(ev->stop, stream);

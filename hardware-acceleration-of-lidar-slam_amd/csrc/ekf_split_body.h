@@ -18,6 +18,8 @@ namespace slam {
 // the same two for the kernels of the split layout (a batch costs fewer registers there: no covariance planes to carry)
 constexpr int kEkfSplitWpe = 5;   // 64k x 500, fused front: 4 waves 97.7 us, 5 waves 94.8 us, 6 waves 99.4 us, 8 waves (spills) 149 us
 constexpr int kEkfSplitNb = 2;
+// ... of the front launch that writes no mean row (survivor rows; 69 VGPRs): profiles/r05_survivor_rows.md
+constexpr int kEkfSplitWpeNoStore = 5;
 
 template <int NB>
 struct SplitBatch {
@@ -37,14 +39,16 @@ struct SplitBatch {
 // tests around the special cases into 26 v_cndmask per batch (as many instructions as the update's arithmetic: counted in
 // the ISA of round 3's kernel): hence two copies of the batch, chosen by a REAL branch (the asm statement keeps the copies
 // from being merged back into one).
-template <int NB, bool SPECIAL>
+// MEANS = false (a survivor-rows frame's front launch): no mean is stored, the log-likelihood terms are all that is left — the
+// same terms: the new means are dead values then and go, with the pins that would keep them alive.
+template <int NB, bool SPECIAL, bool MEANS>
 __device__ __forceinline__ void split_apply_one(const SplitBatch<NB>& b, int g, const EkfPose& w, int pl, v2f& term)
 {
     v2f zx = b.zx[g];
     if constexpr (SPECIAL) asm volatile("" : "+v"(zx));
     const EkfParticle<v2f> u = ekf_particle<v2f>(b.sh[g], b.mx[g], b.my[g], zx, b.zy[g], w.s, w.c, w.px, w.py);
     v2f r0 = u.o0, r1 = u.o1, ll = u.ll;
-    if constexpr (!SPECIAL) {
+    if constexpr (!SPECIAL && MEANS) {
         // The two landmarks of a lane are stored one by one, and left to itself the compiler pushes the two extracts up through
         // the whole expression and then packs each landmark's w00 * dx + w01 * dy as ONE product pair + a horizontal add — with
         // two register moves per pair to line the operands up: 20 instructions for the four new means where 8 packed ones do
@@ -57,50 +61,57 @@ __device__ __forceinline__ void split_apply_one(const SplitBatch<NB>& b, int g, 
     if constexpr (SPECIAL) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {   // obs ? (first ? the observed point : the update) : the prior
-            r0[t] = b.keep[g][t] ? b.mx[g][t] : (b.first[g][t] ? u.wx[t] : r0[t]);
-            r1[t] = b.keep[g][t] ? b.my[g][t] : (b.first[g][t] ? u.wy[t] : r1[t]);
+            if constexpr (MEANS) r0[t] = b.keep[g][t] ? b.mx[g][t] : (b.first[g][t] ? u.wx[t] : r0[t]);
+            if constexpr (MEANS) r1[t] = b.keep[g][t] ? b.my[g][t] : (b.first[g][t] ? u.wy[t] : r1[t]);
             ll[t] = (b.keep[g][t] || b.first[g][t]) ? 0.0f : ll[t];
         }
     }
     term = ll;
+    if constexpr (MEANS) {
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        row_store(w.rout, b.off[g][t], 0, r0[t]);
-        row_store(w.rout, b.off[g][t], pl, r1[t]);
+        for (int t = 0; t < 2; ++t) {
+            row_store(w.rout, b.off[g][t], 0, r0[t]);
+            row_store(w.rout, b.off[g][t], pl, r1[t]);
+        }
     }
 }
 
 // one particle, the NB batches of a pass: term[g] = the batch's log-likelihood terms (+0 where there is none)
-template <int NB>
+template <int NB, bool MEANS>
 __device__ __forceinline__ void split_apply_terms(const SplitBatch<NB>& b, const EkfPose& w, int pl, v2f (&term)[NB])
 {
 #pragma unroll
     for (int g = 0; g < NB; ++g) {
         term[g] = bc2(0.0f);
         if (!b.any_obs[g]) {   // nothing observed among these 128 landmarks: the means are copied
+            if constexpr (MEANS) {
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                row_store(w.rout, b.off[g][t], 0, b.mx[g][t]);
-                row_store(w.rout, b.off[g][t], pl, b.my[g][t]);
+                for (int t = 0; t < 2; ++t) {
+                    row_store(w.rout, b.off[g][t], 0, b.mx[g][t]);
+                    row_store(w.rout, b.off[g][t], pl, b.my[g][t]);
+                }
             }
         } else if (b.special[g]) {
-            split_apply_one<NB, true>(b, g, w, pl, term[g]);
+            split_apply_one<NB, true, MEANS>(b, g, w, pl, term[g]);
         } else {
-            split_apply_one<NB, false>(b, g, w, pl, term[g]);
+            split_apply_one<NB, false, MEANS>(b, g, w, pl, term[g]);
         }
     }
 }
 
-template <int NB>
+template <int NB, bool MEANS>
 __device__ __forceinline__ void split_apply(const SplitBatch<NB>& b, const EkfPose& w, int pl, v2f& acc)
 {
     v2f term[NB];
-    split_apply_terms<NB>(b, w, pl, term);
+    split_apply_terms<NB, MEANS>(b, w, pl, term);
 #pragma unroll
     for (int g = 0; g < NB; ++g) acc = acc + term[g];   // (a batch without observations adds +0: the bits stay)
 }
 
-template <int NB, int G, bool OWN_MOTION>
+// MEANS / TALLY: the two halves of what the update leaves, for a survivor-rows frame.  Its front launch runs
+// MEANS = false — classes, stamps and log-likelihoods, no mean row —, and the launch behind its resample (ekf_materialise_kernel)
+// TALLY = false — mean rows and nothing else, for the particles EkfArgs::survivor names.  The same device functions either way.
+template <int NB, int G, bool OWN_MOTION, bool MEANS = true, bool TALLY = true>
 __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float (*s_acc)[G][128], const MotionIO& mio,
                                                const MotionParams& mpar)
 {
@@ -111,6 +122,12 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
     const int nslots = a.n - g0 < G ? a.n - g0 : G;
     // lane k prepares particle g0 + k: source row, class, pose; read back with v_readlane below
     const int mine = g0 + ((int)lane < nslots ? (int)lane : 0);
+    unsigned long long alive = ~0ull;   // (TALLY = false) the group's particles that get a row
+    if constexpr (!TALLY) {
+        if (a.survivor) alive = __ballot((int)lane < nslots && a.survivor[mine] == a.survivor_stamp);
+        if (alive == 0) return;   // nobody here survived the resample
+    }
+    const int k0 = TALLY ? 0 : __builtin_amdgcn_readfirstlane(__builtin_ctzll(alive));   // the first particle worked on
     const int src_l = a.anc ? a.anc[mine] : mine;
     if (a.group_filter) {   // sharded: this launch takes the groups fed from local rows only (1) or the others (2)
         const bool remote = __ballot(src_l >= a.n) != 0;
@@ -130,12 +147,14 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
         px_l = a.x[mine];
         py_l = a.y[mine];
     }
-    if ((int)lane < nslots) {   // the class follows the particle and is still in use
-        a.cls_out[mine] = cls_l;
-        a.cstamp[cls_l] = a.stamp_now;
-    }
+    if constexpr (TALLY) {
+        if ((int)lane < nslots) {   // the class follows the particle and is still in use
+            a.cls_out[mine] = cls_l;
+            a.cstamp[cls_l] = a.stamp_now;
+        }
 #pragma unroll
-    for (int k = 0; k < G; ++k) acc_store<G>(s_acc, wave, k, lane, bc2(0.0f));
+        for (int k = 0; k < G; ++k) acc_store<G>(s_acc, wave, k, lane, bc2(0.0f));
+    }
     const int pl = __builtin_amdgcn_readfirstlane(a.plane_stride * 4);
     const int mean_bytes = 2 * pl, cov_bytes = 3 * pl;
     const gchar* ozx = uniform_gptr(a.obs_zx);
@@ -164,7 +183,7 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
         unsigned off[NB][2];
         bool in[NB][2];
     };
-    const int src0 = __builtin_amdgcn_readlane(src_l, 0), cls0 = __builtin_amdgcn_readlane(cls_l, 0);
+    const int src0 = __builtin_amdgcn_readlane(src_l, k0), cls0 = __builtin_amdgcn_readlane(cls_l, k0);
     auto load_means = [&](int src, const unsigned (&off)[NB][2], v2f (&mx)[NB], v2f (&my)[NB]) {
         const __amdgpu_buffer_rsrc_t rin = row_rsrc(a.map_in, src, a.row_stride, mean_bytes);
 #pragma unroll
@@ -237,7 +256,9 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
         }
         prepare(b, cur.pr);
         int prev = src0, prev_cls = cls0;
-        for (int k = 0; k < nslots; ++k) {
+        for (int k = k0; k < nslots; ++k) {
+            if constexpr (!TALLY)
+                if (!((alive >> k) & 1ull)) continue;
             const int src = __builtin_amdgcn_readlane(src_l, k);
             const int cls = __builtin_amdgcn_readlane(cls_l, k);
             if (src != prev) {   // another ancestor: its means into registers (wave-uniform branch)
@@ -251,11 +272,17 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
                 prev_cls = cls;
             }
             const EkfPose w = pose_of(k);
-            v2f acc = acc_load<G>(s_acc, wave, k, lane);
-            split_apply<NB>(b, w, pl, acc);
-            acc_store<G>(s_acc, wave, k, lane, acc);
+            if constexpr (TALLY) {
+                v2f acc = acc_load<G>(s_acc, wave, k, lane);
+                split_apply<NB, MEANS>(b, w, pl, acc);
+                acc_store<G>(s_acc, wave, k, lane, acc);
+            } else {
+                v2f term[NB];
+                split_apply_terms<NB, true>(b, w, pl, term);
+            }
         }
     }
+    if constexpr (!TALLY) return;
     // the G sums side by side (wave_xor_tree_sum for every particle, the steps interleaved: one after the other they were 6 G
     // dependent cross-lane round trips at the end of every wavefront's life); slots beyond nslots hold zeros
     float tot[G];

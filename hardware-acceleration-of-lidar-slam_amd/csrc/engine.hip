@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <new>
@@ -116,6 +117,7 @@ int slam_engine_create(int device, slam_engine** out)
     slam_engine* e = new (std::nothrow) slam_engine();
     if (!e) return SLAM_ERR_HIP;
     e->device = device;
+    if (const char* sr = getenv("SLAM_SURVIVOR_ROWS")) e->survivor_rows = atoi(sr) != 0;
     if (hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking) != hipSuccess ||
         e->fm_buf.ensure(sizeof(float) * (kFmIn + kFmOut)) != hipSuccess ||
         e->fm_work.ensure(sizeof(float) * 2 * kLattice * SLAM_MAX_BEAMS) != hipSuccess ||   // (the hits of two sweeps: the chained pair)

@@ -251,7 +251,7 @@ int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src_x, const f
                          const int32_t* d_anc, float* d_x, float* d_y, float* d_th, int n, int64_t first_id, const float dp[3],
                          const float sigma[3], uint64_t seed, uint32_t frame, float* d_score, int32_t* d_count,
                          const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride, int nlandmarks,
-                         float meas_var, bool* launched, const slam::SplitIO* split)
+                         float meas_var, bool* launched, const slam::SplitIO* split, float* d_obs_save)
 {
     SLAM_ENTER(e);
     *launched = false;
@@ -266,6 +266,7 @@ int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src_x, const f
         return SLAM_OK;
     if (int rc = check_score_inputs(e, slot)) return rc;
     if (e->obs_nlandmarks < 0 || e->obs_nlandmarks != nlandmarks) return SLAM_ERR_NOT_READY;
+    if (d_obs_save && !split) return SLAM_ERR_INVALID_ARG;
     const int group = e->ekf_group_size(n, true, plane_stride, true, split != nullptr);
     if (!frame_front_fits(n, nlandmarks, group)) return SLAM_OK;
     SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
@@ -279,7 +280,7 @@ int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src_x, const f
     ScoreGrid sg;
     if (int rc = many_pose_grid(e, slot, n, &sg)) return rc;
     SLAM_HIP_TRY(e, launch_frame_front(e->stream, sg, e->d_bx, e->d_by, e->nbeams, io, first_id, dp, sigma, seed,
-                                       frame, d_score, d_count, a, group, e->prof_next(SLAM_PROF_EKF), launched, &lanes));
+                                       frame, d_score, d_count, a, group, e->prof_next(SLAM_PROF_EKF), launched, &lanes, d_obs_save));
     if (*launched) {
         e->front_last[0] = group;
         e->front_last[1] = lanes;
@@ -308,6 +309,38 @@ int slam_ekf_split_dev(slam_engine* e, const float* d_mean_in, float* d_mean_out
     SLAM_HIP_TRY(e, launch_ekf_update(e->stream, a, e->prof_next(split->group_filter == 2 ? SLAM_PROF_EKF_TAIL : SLAM_PROF_EKF), group));
     if (split->group_filter != 2) e->ekf_form_launches[1]++;
     e->ll_n = n;
+    return SLAM_OK;
+}
+
+int slam_ekf_materialise_dev(slam_engine* e, const float* d_mean_in, float* d_mean_out, int64_t row_stride, int plane_stride,
+                             int nlandmarks, const float* d_obs_save, const float* d_x, const float* d_y, const float* d_th,
+                             const int32_t* d_anc, int n, float meas_var, const slam::SplitIO* split, const uint32_t* d_survivor,
+                             uint32_t stamp, int group)
+{
+    SLAM_ENTER(e);
+    if (n <= 0 || nlandmarks <= 0 || plane_stride < nlandmarks || row_stride < 2 * (int64_t)plane_stride || !(meas_var > 0.0f) ||
+        !d_mean_in || !d_mean_out || d_mean_in == d_mean_out || !d_obs_save || !d_x || !d_y || !d_th || !split || !split->cov ||
+        !split->covx || !split->cls_in)
+        return SLAM_ERR_INVALID_ARG;
+    EkfArgs a = ekf_args(e, d_mean_in, d_mean_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, meas_var, nullptr);
+    apply_split(a, *split);
+    a.obs_zx = d_obs_save;   // the table as the frame's own update saw it
+    a.obs_zy = d_obs_save + plane_stride;
+    a.loglik = nullptr;      // (nothing but mean rows is written)
+    a.cls_out = nullptr;
+    a.cstamp = nullptr;
+    a.group_filter = 0;
+    a.survivor = d_survivor;
+    a.survivor_stamp = stamp;
+    SLAM_HIP_TRY(e, launch_ekf_materialise(e->stream, a, e->prof_next(SLAM_PROF_MATERIALISE), group));
+    return SLAM_OK;
+}
+
+int slam_survivor_rows_set(slam_engine* e, int on)
+{
+    SLAM_ENTER(e);
+    if (on < 0 || on > 1) return SLAM_ERR_INVALID_ARG;
+    e->survivor_rows = on != 0;
     return SLAM_OK;
 }
 

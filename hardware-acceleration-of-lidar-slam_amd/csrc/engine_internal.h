@@ -142,6 +142,7 @@ struct slam_engine {
     void* h_pf_res = nullptr;
     void* d_hpf_res = nullptr;
     bool frame_fusion = true;       // slam_frame_fusion_set
+    bool survivor_rows = true;      // slam_survivor_rows_set
     int64_t front_launches = 0;
     int32_t front_last[2] = { 0, 0 };   // slam_frame_front_last: particles per updating wavefront, lanes per pose
     int ekf_inplace_form = -1;   // slam_ekf_inplace_form_set: -1 by the feedback, 0 whole rows, 1 observed landmarks only
@@ -281,7 +282,19 @@ extern "C" int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src
                          const int32_t* d_anc, float* d_x, float* d_y, float* d_th, int n, int64_t first_id, const float dp[3],
                          const float sigma[3], uint64_t seed, uint32_t frame, float* d_score, int32_t* d_count,
                          const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride, int nlandmarks,
-                         float meas_var, bool* launched, const slam::SplitIO* split = nullptr);
+                         float meas_var, bool* launched, const slam::SplitIO* split = nullptr, float* d_obs_save = nullptr);
+// survivor rows: d_obs_save != nullptr asks slam_frame_front_dev for the launch that writes no mean row (split only) and keeps
+// the observation table there ([2][plane_stride]); this is the launch that writes them later, from the same inputs — the mean
+// rows of slam_ekf_split_dev bit for bit and nothing else (the stored poses; split->cov / covx: the PRIOR class rows; cls_out,
+// cstamp unused).  d_survivor: only particles i with d_survivor[i] == stamp (nullptr: all).  Counts in no form counter.
+extern "C" int slam_ekf_materialise_dev(slam_engine* e, const float* d_mean_in, float* d_mean_out, int64_t row_stride, int plane_stride,
+                             int nlandmarks, const float* d_obs_save, const float* d_x, const float* d_y, const float* d_th,
+                             const int32_t* d_anc, int n, float meas_var, const slam::SplitIO* split, const uint32_t* d_survivor,
+                             uint32_t stamp, int group);
+// engine_resample.hip: slam_ancestors_from_scan_dev that also marks the particles it kept (kernels.h: SurvivorOut); needs
+// ancestors_from_scan_fits(n)
+extern "C" int slam_ancestors_survivors_dev(slam_engine* e, int n, uint64_t seed, uint32_t frame, int32_t* d_anc,
+                                            const slam::SurvivorOut* survivors);
 // the out-of-place landmark update on the SPLIT layout (kernels.h: EkfArgs): d_mean_in / d_mean_out are rows of two planes
 // (row_stride >= 2 * plane_stride), the covariances come per class through `split`; otherwise slam_ekf_update_dev
 extern "C" int slam_ekf_split_dev(slam_engine* e, const float* d_mean_in, float* d_mean_out, int64_t row_stride, int plane_stride,

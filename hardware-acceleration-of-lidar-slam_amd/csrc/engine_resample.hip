@@ -106,8 +106,13 @@ int slam_offspring_from_scan_dev(slam_engine* e, int n, const uint64_t* d_base, 
 
 int slam_ancestors_from_scan_dev(slam_engine* e, int n, uint64_t seed, uint32_t frame, int32_t* d_anc)
 {
+    return slam_ancestors_survivors_dev(e, n, seed, frame, d_anc, nullptr);
+}
+
+int slam_ancestors_survivors_dev(slam_engine* e, int n, uint64_t seed, uint32_t frame, int32_t* d_anc, const SurvivorOut* survivors)
+{
     SLAM_ENTER(e);
-    if (n <= 0 || !d_anc) return SLAM_ERR_INVALID_ARG;
+    if (n <= 0 || !d_anc || (survivors && !ancestors_from_scan_fits(n))) return SLAM_ERR_INVALID_ARG;
     if (e->scan_n != n) return SLAM_ERR_NOT_READY;
     const uint64_t* cdf = e->scan_state.as<uint64_t>();
     const uint32_t frac = e->carry_n == n ? e->gate_frac_q16 : 0;   // the gate needs the sums of a gated quantise_scan
@@ -116,7 +121,7 @@ int slam_ancestors_from_scan_dev(slam_engine* e, int n, uint64_t seed, uint32_t 
     if (ancestors_from_scan_fits(n)) {
         // the distinct-ancestor count only steers the EKF's kernel choice: made only for populations that have maps
         SLAM_HIP_TRY(e, launch_ancestors_from_scan(e->stream, cdf, cdf + n, n, seed, frame, d_anc, frac, gate,
-                                                   e->ll_n == n ? e->heads_out() : HeadsOut()));
+                                                   e->ll_n == n ? e->heads_out() : HeadsOut(), survivors ? *survivors : SurvivorOut()));
         return SLAM_OK;
     }
     // more tiles than the one-launch form keeps in LDS: the two-launch form through a scratch `first` array

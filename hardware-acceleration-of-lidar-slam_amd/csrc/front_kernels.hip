@@ -29,15 +29,31 @@ struct FrontArgs {
     int score_octets;    // ceil(score_blocks / 8)
     int ekf_octets;      // update workgroups per XCD (the xcd_chunk of ekf_update_group_kernel)
     int score_span;      // the scoring octets lie among the first score_span octets of the grid
+    float* obs_save;     // MEANS = false: [2][plane_stride], the observation table as this frame's update saw it
 };
 
-template <int NB, int G, int LPP, int DEPTH, bool SPLIT = false, bool PACKED = false>
-__global__ __launch_bounds__(kEkfWaves * 64) __attribute__((amdgpu_waves_per_eu(SPLIT ? kEkfSplitWpe : kEkfGroupWpe, SPLIT ? kEkfSplitWpe : kEkfGroupWpe)))
+// MEANS = false (split only): a survivor-rows frame — the updating workgroups write no mean row (ekf_split_body), and one workgroup
+// behind the grid keeps a copy of the observation table for the launch that writes the survivors' rows later
+constexpr int front_wpe(bool split, bool means) { return !split ? kEkfGroupWpe : means ? kEkfSplitWpe : kEkfSplitWpeNoStore; }
+
+template <int NB, int G, int LPP, int DEPTH, bool SPLIT = false, bool PACKED = false, bool MEANS = true>
+__global__ __launch_bounds__(kEkfWaves * 64) __attribute__((amdgpu_waves_per_eu(front_wpe(SPLIT, MEANS), front_wpe(SPLIT, MEANS))))
 void frame_front_kernel(FrontArgs f)
 {
     static_assert(kScoreBlock == kEkfWaves * 64, "both kinds of workgroup have 256 threads");
     extern __shared__ float4 s_pair[];
     __shared__ float s_acc[kEkfWaves][G][128];
+    if constexpr (!MEANS) {
+        if (blockIdx.x == gridDim.x - 1) {   // (the caller's table may be rewritten as soon as the frame is issued)
+            const int L = f.a.nlandmarks, Lp = f.a.plane_stride;
+            const float nan = __uint_as_float(0x7fc00000u);
+            for (int l = (int)threadIdx.x; l < Lp; l += kEkfWaves * 64) {
+                f.obs_save[l] = l < L ? f.a.obs_zx[l] : nan;
+                f.obs_save[Lp + l] = l < L ? f.a.obs_zy[l] : nan;
+            }
+            return;
+        }
+    }
     const int o = (int)blockIdx.x >> 3, xcd = (int)blockIdx.x & 7;
     // the scoring octets are spread evenly over the first `span` octets of the grid: the whole grid (against the first part of it
     // only — 64k x 500, 4 / 2 particles per updating wavefront: 100 % 130.7 / 158.5 us, 75 % 134.0 / 156.3, 50 % 155.1 / 154.8,
@@ -51,7 +67,7 @@ void frame_front_kernel(FrontArgs f)
         score_poses_body<false, LPP, DEPTH, true, PACKED>(f.g, f.bx, f.by, f.nbeams, f.mio.x, f.mio.y, f.mio.th, nullptr, f.a.n,
                                                           f.score, f.count, f.mio, f.mpar, sb, s_pair);
     } else if constexpr (SPLIT) {
-        ekf_split_body<NB, G, true>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar);
+        ekf_split_body<NB, G, true, MEANS>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar);
     } else {
         ekf_group_body<NB, G, true>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar);
     }
@@ -72,12 +88,13 @@ bool frame_front_fits(int n, int nlandmarks, int group_size)
 hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const float* bx, const float* by, int nbeams,
                               const MotionIO& io, int64_t first_id, const float dp[3], const float sigma[3], uint64_t seed,
                               uint32_t frame, float* score, int32_t* count, const EkfArgs& a_in, int group_size,
-                              const EventPair* ev, bool* launched, int* lanes_per_pose)
+                              const EventPair* ev, bool* launched, int* lanes_per_pose, float* obs_save)
 {
     *launched = false;
     const int n = a_in.n;
     if (!a_in.cov && group_size == 8) group_size = 4;   // rows: 2 or 4 particles per updating wavefront
     if (a_in.map_in == a_in.map_out || !frame_front_fits(n, a_in.nlandmarks, group_size)) return hipSuccess;
+    if (obs_save && !a_in.cov) return hipErrorInvalidValue;   // survivor rows are a mode of the split layout
     const int G = group_size;
     const bool quad = n < kQuadMaxPoses;
     FrontArgs f;
@@ -95,21 +112,25 @@ hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const floa
     f.score_blocks = (int)(((quad ? 4L : 1L) * n + kScoreBlock - 1) / kScoreBlock);
     f.score_octets = (f.score_blocks + 7) / 8;
     f.score_span = f.score_octets + f.ekf_octets;
-    const int grid = 8 * f.score_span;
+    f.obs_save = obs_save;
+    const int grid = 8 * f.score_span + (obs_save ? 1 : 0);
     const size_t lds = sizeof(float2) * (size_t)(nbeams + (quad ? 4 * kQuadDepth : kLaneDepth)) + (g.packed ? 1024 : 0);
     if (ev) (void)hipEventRecord(ev->start, stream);
     // the instantiation: particles per updating wavefront (8: split only) x scorer's lane mapping x map layout x grid copy read
-#define SLAM_FRONT(G_, SP_, PK_)                                                                                                  \
+    // ... x mean rows written or not (split only)
+#define SLAM_FRONT(G_, SP_, PK_, MN_)                                                                                             \
     do {                                                                                                                          \
         constexpr int NB_ = (SP_) ? kEkfSplitNb : kEkfGroupNb;                                                                    \
-        if (quad) frame_front_kernel<NB_, G_, 4, kQuadDepth, SP_, PK_><<<grid, kEkfWaves * 64, lds, stream>>>(f);                 \
-        else frame_front_kernel<NB_, G_, 1, kLaneDepth, SP_, PK_><<<grid, kEkfWaves * 64, lds, stream>>>(f);                      \
+        if (quad) frame_front_kernel<NB_, G_, 4, kQuadDepth, SP_, PK_, MN_><<<grid, kEkfWaves * 64, lds, stream>>>(f);            \
+        else frame_front_kernel<NB_, G_, 1, kLaneDepth, SP_, PK_, MN_><<<grid, kEkfWaves * 64, lds, stream>>>(f);                 \
     } while (0)
-#define SLAM_FRONT_PK(G_, SP_) do { if (f.g.packed) SLAM_FRONT(G_, SP_, true); else SLAM_FRONT(G_, SP_, false); } while (0)
-    if (G == 2) { if (f.a.cov) SLAM_FRONT_PK(2, true); else SLAM_FRONT_PK(2, false); }
-    else if (G == 8 && f.a.cov) SLAM_FRONT_PK(8, true);
-    else if (f.a.cov) SLAM_FRONT_PK(4, true);
-    else SLAM_FRONT_PK(4, false);
+#define SLAM_FRONT_PK(G_, SP_, MN_) do { if (f.g.packed) SLAM_FRONT(G_, SP_, true, MN_); else SLAM_FRONT(G_, SP_, false, MN_); } while (0)
+#define SLAM_FRONT_SPLIT(G_) do { if (obs_save) SLAM_FRONT_PK(G_, true, false); else SLAM_FRONT_PK(G_, true, true); } while (0)
+    if (G == 2) { if (f.a.cov) SLAM_FRONT_SPLIT(2); else SLAM_FRONT_PK(2, false, true); }
+    else if (G == 8 && f.a.cov) SLAM_FRONT_SPLIT(8);
+    else if (f.a.cov) SLAM_FRONT_SPLIT(4);
+    else SLAM_FRONT_PK(4, false, true);
+#undef SLAM_FRONT_SPLIT
 #undef SLAM_FRONT_PK
 #undef SLAM_FRONT
     if (ev) (void)hipEventRecord(ev->stop, stream);

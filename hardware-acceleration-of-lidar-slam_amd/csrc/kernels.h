@@ -154,6 +154,11 @@ struct EkfArgs {
     // fused front launch, before the host has even looked at the exchange plan; 2: only the other groups, behind the unpack.
     // 0: every group.
     int group_filter = 0;
+    // Survivor rows (launch_ekf_materialise): the mean rows of a frame whose front launch wrote none, from the inputs that frame
+    // started from.  survivor != nullptr: only particles i with survivor[i] == survivor_stamp (the ones the frame's resample
+    // kept) get their row; a wavefront without one leaves before it loads anything else.  nullptr: every particle.
+    const uint32_t* survivor = nullptr;
+    uint32_t survivor_stamp = 0;
 };
 // the split layout's part of EkfArgs, as the session hands it to the engine's stage functions
 struct SplitIO {
@@ -172,15 +177,20 @@ struct SplitIO {
 // group_size: 0 = one wavefront per particle; 2 / 4 / 8 = the grouped out-of-place form (that many neighbouring particles
 // per wavefront share their source rows in registers) — a speed choice only, every form gives the same bits
 hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a, const EventPair* ev = nullptr, int group_size = 0);
+// split layout: the MEAN ROWS of launch_ekf_update alone, bit for bit — no log-likelihood, no class, no stamp is written; reads
+// the stored poses a.x / a.y / a.th; optionally for the survivors only (EkfArgs::survivor).  group_size as above.
+hipError_t launch_ekf_materialise(hipStream_t stream, const EkfArgs& a, const EventPair* ev, int group_size);
 bool frame_front_fits(int n, int nlandmarks, int group_size);   // the shapes launch_frame_front takes
 // motion sample + scan-match score AND the grouped out-of-place landmark update in ONE launch (single-GPU frames on rows): the
 // gathers of the scorer run in the shadow of the update's row stores.  `a.x / a.y / a.th` are not read (the update works out
 // its particles' motion samples itself, the same bits the scorer writes to io.x / io.y / io.th).  *launched = false: shapes
 // that this kernel does not take; nothing was issued.
+// obs_save (split layout only; nullptr: none): the launch writes NO mean row — everything else as ever, the same bits — and one
+// more workgroup copies the observation table to obs_save [2][plane_stride] (zx | zy), for launch_ekf_materialise to start from.
 hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const float* bx, const float* by, int nbeams,
                               const MotionIO& io, int64_t first_id, const float dp[3], const float sigma[3], uint64_t seed,
                               uint32_t frame, float* score, int32_t* count, const EkfArgs& a, int group_size,
-                              const EventPair* ev, bool* launched, int* lanes_per_pose = nullptr);
+                              const EventPair* ev, bool* launched, int* lanes_per_pose = nullptr, float* obs_save = nullptr);
 // In-place update of the OBSERVED landmarks only (frames that keep their population): the observation table is first
 // compacted into a list in landmark order (ids, measurements, accumulator rounds; count[2] = {nobs, highest round} on the
 // device, {nobs, L} optionally in mapped host memory), then one lane per observation gathers, updates and scatters.
@@ -341,6 +351,9 @@ struct CovArgs {
     int32_t* h_mark;       // ... and, written behind a system-scope fence, {mark, epoch}
     uint32_t epoch;
     uint32_t mark;         // the host's running count of classes appended to the list so far (sharded sessions: rows received)
+    // survivor rows: the PRIOR rows of every class that is updated are first copied here (same strides; nullptr: not wanted)
+    float* save_cov = nullptr;
+    float* save_covx = nullptr;
 };
 // rows [n][5][plane_stride_in] (row_stride_in floats apart) -> means [n][2][Lp], classes, class rows [..][3][Lp]: neighbouring
 // particles whose three covariance planes are equal bit for bit share a class (classes are numbered 0, 1, .. in particle
@@ -429,9 +442,15 @@ hipError_t launch_ancestors(hipStream_t stream, const int32_t* first_all, int64_
                             int32_t* anc);
 // single GPU: offspring offsets + ancestors in one launch (n up to 8M; beyond that use the two launches above)
 bool ancestors_from_scan_fits(int n);
+// survivors (optional): mark[anc[j]] = stamp for every slot j — the particles the resample kept
+struct SurvivorOut {
+    uint32_t* mark = nullptr;   // [n]
+    uint32_t stamp = 0;
+};
 hipError_t launch_ancestors_from_scan(hipStream_t stream, const uint64_t* cdf_local, const uint64_t* tile_total, int n,
                                       uint64_t seed, uint32_t frame, int32_t* anc, uint32_t frac_q16 = 0,
-                                      const GateOut& gate = GateOut(), const HeadsOut& heads = HeadsOut());
+                                      const GateOut& gate = GateOut(), const HeadsOut& heads = HeadsOut(),
+                                      const SurvivorOut& survivors = SurvivorOut());
 hipError_t launch_argmax(hipStream_t stream, const float* v, int n, int32_t* idx_out, float* val_out);
 // heaviest particle {logw, global id (int bits), x, y, theta} -> out5 (device) and optionally mapped host memory + seq
 hipError_t launch_best_particle(hipStream_t stream, const float* v, int n, const float* px, const float* py,

@@ -110,6 +110,27 @@ struct slam_pf {
     int64_t cls_cursor = 0;         // entries of the current list handed out so far (beyond its guaranteed length: make a new one)
     uint32_t cls_appended = 0;      // classes appended to the list so far in this epoch (what cov_update_body's `mark` carries)
     void* split_scratch = nullptr;  // flags, prefix sums of a rows -> split move
+    // ---- survivor rows (one GPU, split, resampling every frame): the fused front launch of a frame writes
+    // no mean row, a launch behind the resample writes the rows of the particles it kept (materialise).  Until the next step the
+    // session keeps what the frame's update started from — the previous mean rows, gather index, classes and the frame's poses
+    // are intact anyway; the observation table and the prior rows of the classes it updates are copied — so that settle_means
+    // can still write every row when something other than the next eligible frame wants to look.
+    bool surv_can = false;          // the session can have such frames; the buffers are made when the first one comes up
+    bool surv_failed = false;       // ... and could not be had: it writes every row, as ever
+    float* surv_store = nullptr;    // the one allocation behind the next four
+    float* save_cov = nullptr;      // [cap][3][Lp] prior rows of the classes the last frame updated (cov_update_body)
+    float* save_covx = nullptr;     // [cap][2][Lp]
+    float* obs_save = nullptr;      // [2][Lp] the last frame's observation table
+    uint32_t* survivor = nullptr;   // [n] == surv_stamp: the last resample kept the particle
+    uint32_t surv_stamp = 0;
+    struct {                        // the frame whose rows are not all written yet (pending)
+        bool pending = false;
+        const float* mean_in = nullptr;
+        float* mean_out = nullptr;
+        const int32_t *anc = nullptr, *cls_in = nullptr;
+        const float* pose = nullptr;
+        int group = 0;
+    } surv;
     bool gated = false;             // cfg.resample_ess_frac in (0, 1): a frame resamples only when its ESS is low
     int64_t frames_resampled = 0;   // (as far as the host has looked: one frame behind)
     // slam_pf_refine_set: sweeps > 0: the front launch of a frame is motion + refine (refine_kernels.hip), never the fused front
@@ -191,6 +212,54 @@ float* split_pool(const slam_pf* pf);
 PageGeom split_geom(const slam_pf* pf);
 PagePool page_pool(const slam_pf* pf);
 ClassStore class_store(const slam_pf* pf);
+
+// Survivor rows: the mean rows of the pending frame, from the inputs it started from (the same device functions as its front
+// launch: the same bits) — for the particles the resample kept (filtered), or all of them.
+int materialise(slam_pf* pf, bool filtered)
+{
+    const size_t sn = (size_t)pf->n;
+    SplitIO sio{};
+    sio.cov = pf->save_cov;
+    sio.cov_stride = 3 * (int64_t)pf->Lp;
+    sio.covx = pf->save_covx;
+    sio.covx_stride = 2 * (int64_t)pf->Lp;
+    sio.cls_in = pf->surv.cls_in;
+    return slam_ekf_materialise_dev(pf->e, pf->surv.mean_in, pf->surv.mean_out, 2 * (int64_t)pf->Lp, pf->Lp, pf->L, pf->obs_save,
+                                    pf->surv.pose, pf->surv.pose + sn, pf->surv.pose + 2 * sn, pf->surv.anc, pf->n, pf->cfg.meas_var, &sio,
+                                    filtered ? pf->survivor : nullptr, pf->surv_stamp, pf->surv.group);
+}
+
+// The buffers of the mode, made in front of the first frame that wants them (a session whose switch stays off, or that never
+// has such a frame, does not pay for them): one allocation, zeroed on the stream.
+bool survivor_buffers(slam_pf* pf)
+{
+    if (pf->surv_store) return true;
+    if (!pf->surv_can || pf->surv_failed) return false;
+    const size_t unit = (size_t)pf->Lp * (size_t)pf->cap, words = 5 * unit + 2 * (size_t)pf->Lp + (size_t)pf->n;
+    if (hipMalloc((void**)&pf->surv_store, words * 4) != hipSuccess ||
+        hipMemsetAsync(pf->surv_store, 0, words * 4, pf->e->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        if (pf->surv_store) (void)hipFree(pf->surv_store);
+        pf->surv_store = nullptr;
+        pf->surv_failed = true;
+        return false;
+    }
+    pf->save_cov = pf->surv_store;
+    pf->save_covx = pf->save_cov + 3 * unit;
+    pf->obs_save = pf->save_covx + 2 * unit;
+    pf->survivor = reinterpret_cast<uint32_t*>(pf->obs_save + 2 * (size_t)pf->Lp);
+    return true;
+}
+
+// Before anything but the next eligible frame sees a mean row: after this the buffers hold what a frame that wrote every row
+// leaves.  Called by every entry that reads or moves mean rows or hands out their address (slam_pf_get_map_rows_host reads
+// through the pending gather — survivors only — and does not need it).
+int settle_means(slam_pf* pf)
+{
+    if (!pf->surv.pending) return SLAM_OK;
+    pf->surv.pending = false;
+    return materialise(pf, false);
+}
 
 // Map rows (and poses) of ancestors that live on another rank -> the staging tail of the current buffers, where
 // the next EKF's fused gather picks them up.  pack (one launch) -> one grouped send/recv -> unpack (one launch).
@@ -285,6 +354,7 @@ int finish_exchange(slam_pf* pf)
 // set_poses / set_map / reset discard the pending resample gather: nothing of it may run later
 int drop_resample(slam_pf* pf)
 {
+    if (int rc = settle_means(pf)) return rc;   // without the gather every row is a current particle's
     pf->has_anc = false;
     pf->exchange_pending = false;
     if (pf->gated)   // ... and no weight is carried into the next frame
@@ -561,6 +631,8 @@ int auto_layout(slam_pf* pf)
     pf->obs_seq_seen = seq;
     pf->votes_pages = *host_word(pf, RES_VOTES_PAGES);   // samples in a row (counted on the device, so none is missed however far the host runs ahead)
     pf->votes_rows = *host_word(pf, RES_VOTES_ROWS);
+    if ((!pf->paged && pf->votes_pages >= 3) || (pf->paged && pf->votes_rows >= 3))
+        if (int rc = settle_means(pf)) return rc;   // a move reads every row
     if (!pf->paged && pf->votes_pages >= 3) {
         if (pf->split) return convert_split_to_split_pages(pf);   // the means go onto pages, the classes stay
         return convert_to_pages(pf);
@@ -638,6 +710,10 @@ int create_common(slam_engine* e, const slam_pf_config* cfg, slam_comm* comm, in
         pf->split = have;
         if (have) place_split(pf, 0);
     }
+    // survivor rows: a session that can have such frames (split — not pinned to split pages — on one GPU, resampling every frame,
+    // the one-launch ancestor search); its buffers are made in front of the first such frame (survivor_buffers)
+    pf->surv_can = L && ok && pf->split && !pf->paged && !comm && !pf->gated && cfg->resample_ess_frac <= 0.0f &&
+                   ancestors_from_scan_fits(pf->n);
     if (L && ok && (pf->paged || (pf->layout_cfg == SLAM_MAP_AUTO && !pf->auto_stuck))) {
         ok = alloc_page_tables(pf);
         if (!ok && !pf->paged) {   // AUTO can live without them: it stays on rows
@@ -698,8 +774,10 @@ int create_common(slam_engine* e, const slam_pf_config* cfg, slam_comm* comm, in
 // (sharded sessions) — the second word is the running count of arrivals as of that launch; it is read FIRST and written
 // last, so a torn pair only over-estimates; before anything of this epoch has arrived: every class there can be.
 // Gives the arguments and the width, and moves the bookkeeping on as if it had been launched: the weights' launch carries it.
-void split_class_prepare(slam_pf* pf, int nlandmarks, CovArgs& ca, int& bound)
+void split_class_prepare(slam_pf* pf, int nlandmarks, bool save_prior, CovArgs& ca, int& bound)
 {
+    ca.save_cov = save_prior ? pf->save_cov : nullptr;
+    ca.save_covx = save_prior ? pf->save_covx : nullptr;
     const uint64_t hm = __atomic_load_n(reinterpret_cast<const uint64_t*>(host_word(pf, RES_CLS_MARK)), __ATOMIC_ACQUIRE),
                    hl = __atomic_load_n(reinterpret_cast<const uint64_t*>(host_word(pf, RES_LIVE)), __ATOMIC_ACQUIRE);
     const bool fresh = (uint32_t)(hl >> 32) == pf->cls_epoch && (uint32_t)hl > 0;
@@ -730,11 +808,11 @@ void split_class_prepare(slam_pf* pf, int nlandmarks, CovArgs& ca, int& bound)
 }
 
 // the classes' update of the frame + the weights: ONE launch
-int weights_with_classes(slam_pf* pf, int nlandmarks, bool use_ekf)
+int weights_with_classes(slam_pf* pf, int nlandmarks, bool use_ekf, bool save_prior = false)
 {
     CovArgs ca;
     int bound = 0;
-    split_class_prepare(pf, nlandmarks, ca, bound);
+    split_class_prepare(pf, nlandmarks, save_prior, ca, bound);
     return slam_logweight_cov_dev(pf->e, pf->score, use_ekf, pf->cfg.score_gain, pf->n, pf->logw, nullptr, &ca, bound);
 }
 
@@ -770,6 +848,7 @@ struct FrameFacts {
     // ---- left by the stages
     bool paged_listed;   // front: the page list is out, the free list rides with the scorer
     bool fused;          // front: the landmark update went out with the score
+    bool survivors;      // front: ... and wrote no mean row (survivor rows): the resample marks whom it keeps, a launch behind it writes their rows
     bool in_place;       // gate: the last frame kept its population, the maps have not moved
 };
 
@@ -871,6 +950,14 @@ int front_stage(slam_pf* pf, FrameFacts& f, int slot, const float dp[3])
         rider = FreeListRider{ pf->stamp, pf->npages, pf->stamp_now, pf->freelist, pf->page_scratch, dev_word(pf, RES_SHORT_LIST) };
         f.paged_listed = true;
     }
+    // Survivor rows: the switch is on, the frame goes to the fused front launch and the session has (or now gets) the buffers;
+    // whether the launch takes the frame is known for good once it has been asked.  A frame that cannot be one reads,
+    // gathers or overwrites whole mean buffers: the rows the frame before left unwritten come first.
+    const bool want_survivors = e->survivor_rows && pf->split && !pf->paged && !comm && pf->refine_sweeps == 0 && f.anc &&
+                                f.observing && e->frame_fusion && !(e->prof_mask & (1 << SLAM_PROF_SCORE)) &&
+                                frame_front_fits(pf->n, pf->L, 4) && survivor_buffers(pf);
+    if (!want_survivors)
+        if (int rc = settle_means(pf)) return rc;
     // 1 + 2 + 3 in ONE launch when the frame allows it (landmarks observed, long rows, enough particles): motion + score and the
     // out-of-place landmark update side by side (slam_frame_front_dev; the same bits).  One GPU, rows or split: a gated session
     // on rows is left out (its frames that keep their population update in place; on split they go through the identity index).
@@ -912,9 +999,23 @@ int front_stage(slam_pf* pf, FrameFacts& f, int slot, const float dp[3])
         if (int rc = slam_frame_front_dev(e, slot, ps, ps + sn, ps + 2 * sn, pose_anc, dst, dst + sn, dst + 2 * sn, n, f.first_id, dp,
                                           pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->score, pf->count, map_in, map_out,
                                           (pf->split ? 2 : 5) * (int64_t)pf->Lp, pf->Lp, pf->L, pf->cfg.meas_var, &f.fused,
-                                          pf->split ? &sio : nullptr))
+                                          pf->split ? &sio : nullptr, want_survivors ? pf->obs_save : nullptr))
             return rc;
+        f.survivors = f.fused && want_survivors;
+        if (f.survivors) {   // (the rows of the frame before are read through its gather index only: no settle)  What this frame starts from:
+            pf->surv.mean_in = map_in;
+            pf->surv.mean_out = map_out;
+            pf->surv.anc = f.anc;
+            pf->surv.cls_in = sio.cls_in;
+            pf->surv.pose = dst;
+            int32_t info[2];
+            if (int rc = slam_frame_front_last(e, info)) return rc;
+            pf->surv.group = info[0];
+            pf->surv.pending = false;   // (its own rows become pending behind the resample)
+        }
     }
+    if (f.survivors) return SLAM_OK;
+    if (int rc = settle_means(pf)) return rc;   // (the launch did not take the shapes: nothing was issued yet)
     if (f.fused) return SLAM_OK;
     if (comm && pf->has_anc) {
         if (int rc = comm_all_gather_finish(comm)) return rc;
@@ -997,7 +1098,7 @@ int update_split(slam_pf* pf, const FrameFacts& f)
         pf->cstamp_now++;
         pf->sp_cur = 1 - sc;
         // ... then the classes' update, in place, once per class still in use
-        return weights_with_classes(pf, L, true);
+        return weights_with_classes(pf, L, true, f.survivors);
     }
     if (f.anc) {   // means and classes follow their particles
         const ProfScope prof(e, SLAM_PROF_PAGES);
@@ -1065,12 +1166,18 @@ int scan_stage(slam_pf* pf)
 }
 
 // 5. resample on the integer CDF
-int resample_stage(slam_pf* pf, const float* poses)
+int resample_stage(slam_pf* pf, const float* poses, bool survivors)
 {
     slam_engine* e = pf->e;
     slam_comm* comm = pf->comm;
     const int n = pf->n, nxt = 1 - pf->cur;
     const size_t sn = (size_t)n;
+    if (survivors) {   // one GPU: the search also marks the particles it keeps, and one launch behind it writes their mean rows
+        const SurvivorOut so{ pf->survivor, ++pf->surv_stamp };
+        if (int rc = slam_ancestors_survivors_dev(e, n, pf->cfg.seed, pf->frame, pf->anc[nxt], &so)) return rc;
+        pf->surv.pending = true;
+        return materialise(pf, true);
+    }
     if (!comm) return slam_ancestors_from_scan_dev(e, n, pf->cfg.seed, pf->frame, pf->anc[nxt]);
     // shard totals (with the gate: total, sum v, sum v^2 per rank)
     if (int rc = comm_all_gather(comm, pf->d_sum, pf->totals, (pf->gated ? 3 : 1) * sizeof(uint64_t))) return rc;
@@ -1103,7 +1210,7 @@ int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations,
     if (int rc = gate_and_exchange(pf, f, collective_verdict)) return rc;
     if (int rc = pf->paged ? update_paged(pf, f) : pf->split ? update_split(pf, f) : update_rows(pf, f)) return rc;
     if (int rc = scan_stage(pf)) return rc;
-    if (int rc = resample_stage(pf, f.dst)) return rc;
+    if (int rc = resample_stage(pf, f.dst, f.survivors)) return rc;
     pf->cur = 1 - pf->cur;
     pf->has_anc = true;
     pf->last_ekf = f.ekf;
@@ -1221,6 +1328,7 @@ int pf_get_map_host(slam_pf* pf, float* rows)
     const size_t n = (size_t)pf->n, L = (size_t)pf->L, Lp = (size_t)pf->Lp;
     if (pf->comm)
         if (int rc = finish_exchange(pf)) return rc;   // collective: remote ancestors' rows into the staging tail
+    if (int rc = settle_means(pf)) return rc;
     const int32_t* idx = pf->has_anc ? pf->anc[pf->cur] : nullptr;   // the pending gather is applied on the way
     float* dense = nullptr;
     const float* src = pf->map[pf->map_cur];
@@ -1310,6 +1418,7 @@ int slam_pf_destroy(slam_pf* pf)
         (void)hipFree(pf->pose_idx[b]);
     }
     if (pf->store) (void)hipFree(pf->store);
+    if (pf->surv_store) (void)hipFree(pf->surv_store);
     free_page_tables(pf);
     free_split_tables(pf);
     for (void* p : { (void*)pf->score, (void*)pf->logw, (void*)pf->count, (void*)pf->first, (void*)pf->pose_all, (void*)pf->pose_stage, (void*)pf->first_all,
@@ -1377,6 +1486,7 @@ int slam_pf_set_poses_host(slam_pf* pf, const float* x, const float* y, const fl
 int slam_pf_set_map_host(slam_pf* pf, const float* rows)
 {
     if (!pf || !rows || !pf->L) return SLAM_ERR_INVALID_ARG;
+    if (int rc = settle_means(pf)) return rc;
     if (int rc = slam_engine_sync(pf->e)) return rc;
     if (pf->has_anc) return SLAM_ERR_NOT_READY;   // set poses / reset first: a gather is pending
     // host [n][5][L] -> device [n][5][Lp]: 5n planes of L floats each
@@ -1398,6 +1508,7 @@ int slam_pf_set_map_host(slam_pf* pf, const float* rows)
 int slam_pf_set_map_dev(slam_pf* pf, const float* d_rows, int64_t row_stride, int plane_stride)
 {
     if (!pf || !d_rows || !pf->L || plane_stride < pf->L || row_stride < 5 * (int64_t)plane_stride) return SLAM_ERR_INVALID_ARG;
+    if (int rc = settle_means(pf)) return rc;
     if (pf->has_anc) return SLAM_ERR_NOT_READY;   // set poses / reset first: a gather is pending
     slam_engine* e = pf->e;
     SLAM_HIP_TRY(e, hipSetDevice(e->device));
@@ -1450,6 +1561,7 @@ int64_t slam_pf_layout_changes(const slam_pf* pf) { return pf ? pf->conversions 
 int slam_pf_device_view(slam_pf* pf, slam_pf_view* out)
 {
     if (!pf || !out) return SLAM_ERR_INVALID_ARG;
+    if (int rc = settle_means(pf)) return rc;
     out->pose = pf->pose[pf->cur];
     const bool rows = pf->L && !pf->paged && !pf->split;   // pages and split maps have no rows to look at: slam_pf_set_map_dev
     out->map = rows ? pf->map[pf->map_cur] : nullptr;
@@ -1475,6 +1587,7 @@ int slam_pf_split_device_view(slam_pf* pf, slam_pf_split_view* out)
 {
     if (!pf || !out) return SLAM_ERR_INVALID_ARG;
     if (!pf->split || !pf->L) return SLAM_ERR_NOT_READY;
+    if (int rc = settle_means(pf)) return rc;
     out->mean = pf->paged ? nullptr : pf->mean[pf->sp_cur];   // split pages: the means are on pages (slam_pf_paged_device_view)
     out->cov = pf->cov;
     out->cls = pf->cls[pf->sp_cur];
@@ -1485,10 +1598,19 @@ int slam_pf_split_device_view(slam_pf* pf, slam_pf_split_view* out)
     return SLAM_OK;
 }
 
+int slam_pf_split_covx_view(slam_pf* pf, const float** covx)
+{
+    if (!pf || !covx) return SLAM_ERR_INVALID_ARG;
+    if (!pf->split || !pf->L) return SLAM_ERR_NOT_READY;
+    *covx = pf->covx;
+    return SLAM_OK;
+}
+
 int slam_pf_paged_device_view(slam_pf* pf, slam_pf_paged_view* out)
 {
     if (!pf || !out) return SLAM_ERR_INVALID_ARG;
     if (!pf->paged) return SLAM_ERR_NOT_READY;
+    if (int rc = settle_means(pf)) return rc;
     const PageGeom g = pf->split ? split_geom(pf) : PageGeom();
     out->pool = pf->split ? split_pool(pf) : pf->pool;
     out->planes = g.planes;

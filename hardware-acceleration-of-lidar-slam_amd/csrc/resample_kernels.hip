@@ -523,7 +523,8 @@ __global__ __launch_bounds__(kBlock) void ancestors_from_scan_kernel(const uint6
                                                                      uint32_t frame, int32_t* __restrict__ anc,
                                                                      const uint64_t* __restrict__ tile_s16,
                                                                      const uint64_t* __restrict__ tile_q16,
-                                                                     uint32_t frac_q16, GateOut gate, HeadsOut heads)
+                                                                     uint32_t frac_q16, GateOut gate, HeadsOut heads,
+                                                                     SurvivorOut survivors)
 {
     __shared__ uint64_t s_off[kPer * kBlock];
     __shared__ uint64_t s_wave[kBlock / 64];
@@ -629,6 +630,8 @@ __global__ __launch_bounds__(kBlock) void ancestors_from_scan_kernel(const uint6
         }
     }
     if (j < n) anc[j] = val;
+    // survivor rows: the particles this resample kept (val in [0, n); slots of one ancestor store the same word: no atomics)
+    if (j < n && survivors.mark) survivors.mark[val] = survivors.stamp;
     count_heads(heads, val, j < n, n);
 }
 
@@ -875,7 +878,7 @@ bool ancestors_from_scan_fits(int n) { return n > 0 && scan_tile_count(n) <= kMa
 
 hipError_t launch_ancestors_from_scan(hipStream_t stream, const uint64_t* cdf_local, const uint64_t* tile_total, int n,
                                       uint64_t seed, uint32_t frame, int32_t* anc, uint32_t frac_q16, const GateOut& gate,
-                                      const HeadsOut& heads)
+                                      const HeadsOut& heads, const SurvivorOut& survivors)
 {
     if (n <= 0) return hipSuccess;
     const int ntiles = scan_tile_count(n);
@@ -883,11 +886,11 @@ hipError_t launch_ancestors_from_scan(hipStream_t stream, const uint64_t* cdf_lo
     if (ntiles <= kBlock)
         ancestors_from_scan_kernel<1><<<blocks_for(n), kBlock, 0, stream>>>(cdf_local, tile_total, ntiles, n, (uint32_t)seed,
                                                                             (uint32_t)(seed >> 32), frame, anc, ts, tq,
-                                                                            frac_q16, gate, heads);
+                                                                            frac_q16, gate, heads, survivors);
     else
         ancestors_from_scan_kernel<kMaxLdsTiles / kBlock><<<blocks_for(n), kBlock, 0, stream>>>(
             cdf_local, tile_total, ntiles, n, (uint32_t)seed, (uint32_t)(seed >> 32), frame, anc, ts, tq, frac_q16, gate,
-            heads);
+            heads, survivors);
     return hipGetLastError();
 }
 

@@ -107,7 +107,9 @@ typedef enum {
                                    its own (one GPU: it travels in the scorer's launch); split maps' gathers on frames without observations */
     SLAM_PROF_EKF_TAIL = 11,    /* several GPUs, split maps: the part of the landmark update that waits for the exchange (the
                                    groups with an ancestor in the staging tail); the rest went out with the score (SLAM_PROF_EKF) */
-    SLAM_PROF_COUNT = 12
+    SLAM_PROF_MATERIALISE = 12, /* survivor rows (slam_survivor_rows_set): the launch behind the resample that writes the mean rows of
+                                   the particles it kept, and the launch that writes all of them when something asks (settle) */
+    SLAM_PROF_COUNT = 13
 } slam_prof_kernel;
 int slam_profile_enable(slam_engine *e, int mask);
 int slam_profile_read(slam_engine *e, int kernel, double *total_ms, int64_t *launches);
@@ -293,6 +295,15 @@ int slam_ekf_form_counts(slam_engine *e, int64_t counts[2]);
  * slam_frame_fusion_count: fused launches of this engine so far. */
 int slam_frame_fusion_set(slam_engine *e, int on);
 int slam_frame_fusion_count(slam_engine *e, int64_t *launches);
+/* SURVIVOR ROWS.  On the split layout the fused front launch of a single-GPU session that resamples every frame
+ * (resample_ess_frac == 0) writes no mean row: the next frame reads a row only through the resample index, and most
+ * particles leave no offspring.  One launch behind the resample writes the rows of the particles it kept, from the inputs
+ * the frame started from, bit for bit what the front launch would have written.  Whatever else looks at mean rows
+ * (slam_pf_device_view and its kin, slam_pf_get_map_host, a change of layout, a frame that does not qualify) first gets
+ * them all written by one more launch, so no result depends on the switch.  on = 1 (the initial state; the environment
+ * variable SLAM_SURVIVOR_ROWS=0 makes 0 the initial state of engines created afterwards) / 0: every frame writes every row.
+ * Neither launch counts in slam_ekf_form_counts or slam_frame_fusion_count; both are bracketed as SLAM_PROF_MATERIALISE. */
+int slam_survivor_rows_set(slam_engine *e, int on);
 /* Which instantiation the LAST fused front launch of this engine was (tests pin the kernel at the shapes its numbers are
  * quoted on and say which one they pinned): info[0] = particles per updating wavefront (2 or 4; 2, 4 or 8 on the split
  * layout), info[1] = lanes per pose of its scoring workgroups (4 below 131 072 particles, else 1); both 0 before the first
@@ -580,7 +591,10 @@ int64_t slam_pf_layout_changes(const slam_pf *pf);
  * n_particles floats each; map = one row per particle, row_stride floats apart, five planes of plane_stride floats
  * (layout of slam_ekf_update_dev); anc = the pending resample gather (slot i descends from particle anc[i] of
  * these buffers; NULL when none is pending: right after create / reset / set_*).  The pointers move with every
- * slam_pf_step; synchronise (slam_engine_sync) before touching the memory from another stream. */
+ * slam_pf_step; synchronise (slam_engine_sync) before touching the memory from another stream.
+ * This call and the two *_device_view calls below may ISSUE A LAUNCH on the engine's stream: after a survivor-rows frame
+ * (slam_survivor_rows_set) they first have every mean row of that frame written.  Ask for the view again after every
+ * slam_pf_step: a view kept across a step may show rows that nobody has written yet. */
 typedef struct {
     float *pose, *map;
     float *map_spare;                 /* the other map buffer: free between frames (the next EKF writes it) */
@@ -635,6 +649,9 @@ typedef struct {
     int32_t plane_stride, rows;
 } slam_pf_split_view;
 int slam_pf_split_device_view(slam_pf *pf, slam_pf_split_view *out);
+/* ... and covx[..][2][plane_stride]: row c = the determinant terms of class c's covariances, 1 / det (P + q I) and
+ * 0.5 log det (P + q I), as the next landmark update will read them (same validity as the view's pointers). */
+int slam_pf_split_covx_view(slam_pf *pf, const float **covx);
 
 /* ------------------------------------------------------------------ mapper: the reference's frame loop in one call
  * (SURVEY.md §8f rows N1 + N2).  One slam_mapper_next_frame = one iteration of the reference's loop
