@@ -846,7 +846,8 @@ class PfSession:
         return np.array(list(pose), np.float32), np.float32(lw.value), idx.value
 
     def mean(self, ref_theta: float):
-        """``slam_pf_mean``: posterior mean of the current population (heading averaged on the circle around ref_theta)."""
+        """``slam_pf_mean``: posterior mean of the current population (heading averaged on the circle around ref_theta):
+        the plain mean of equally weighted particles, the weighted mean after a frame the resample gate kept."""
         pose = (C.c_float * 3)()
         self.e._ck(self.e.lib.slam_pf_mean(self.h, float(ref_theta), pose), "pf_mean")
         return np.array(list(pose), np.float32)

@@ -456,11 +456,14 @@ hipError_t launch_argmax(hipStream_t stream, const float* v, int n, int32_t* idx
 hipError_t launch_best_particle(hipStream_t stream, const float* v, int n, const float* px, const float* py,
                                 const float* pth, int64_t first_id, float* out5, float* h_out5, uint32_t* h_seq,
                                 uint32_t seq);
-// exact fixed-point sums of the population {x, y: 2^-32; sin, cos of (theta - ref): 2^-30} -> out4 (device), optionally
-// mapped host memory + seq; acc[4] / ticket: zero-initialised device scratch the kernel leaves zeroed
+// exact fixed-point sums of the population {x, y: 2^-32; sin, cos of (theta - ref): 2^-30} -> out[4] (device), optionally
+// mapped host memory + seq; acc[9] / ticket: zero-initialised device scratch the kernel leaves zeroed.
+// carry != nullptr (a frame the resample gate kept): the weighted sums, out[9] = each of the four as two limbs
+// (w16 * (V >> 21), w16 * (V & 0x1fffff)) and sum w16, with w16 = quantise(det_exp(carry[i])) >> 16
+constexpr int kPoseSumsPlain = 4, kPoseSumsWeighted = 9;
 hipError_t launch_pose_sums(hipStream_t stream, const float* x, const float* y, const float* th, const int32_t* idx,
-                            int n, float ref_th, unsigned long long* acc, unsigned int* ticket, long long* out4,
-                            long long* h_out4, uint32_t* h_seq, uint32_t seq);
+                            int n, float ref_th, unsigned long long* acc, unsigned int* ticket, long long* out,
+                            long long* h_out, uint32_t* h_seq, uint32_t seq, const float* carry = nullptr);
 hipError_t launch_gather_f32(hipStream_t stream, const float* src, const int32_t* idx, int n, float* dst);
 hipError_t launch_gather_map(hipStream_t stream, const float* in, float* out, int64_t in_row_stride,
                              int64_t out_row_stride, int in_plane_stride, int out_plane_stride, int nlandmarks,

@@ -72,7 +72,7 @@ struct slam_pf {
     float* d_hres = nullptr;        // the same memory as the device sees it
     uint32_t res_seq = 0;
     float* res_dev = nullptr;       // device copy of the payload (what the ranks all-gather)
-    unsigned long long* sums_acc = nullptr;   // 4 accumulators + ticket of pose_sums_kernel (kept zeroed by the kernel)
+    unsigned long long* sums_acc = nullptr;   // 9 accumulators + ticket of pose_sums_kernel (kept zeroed by the kernel)
     void* res_all = nullptr;        // [world] payloads
     // ---- paged maps (slam_pf_paged_set before the session is made; one GPU): copy-on-write pages behind a page table
     // per particle instead of one row per particle (paged_kernels.hip); map[] stays unallocated
@@ -728,9 +728,9 @@ int create_common(slam_engine* e, const slam_pf_config* cfg, slam_comm* comm, in
     }
     ok = ok && dev_alloc((void**)&pf->score, n * 4) == hipSuccess && dev_alloc((void**)&pf->logw, n * 4) == hipSuccess &&
          dev_alloc((void**)&pf->count, n * 4) == hipSuccess && dev_alloc((void**)&pf->first, n * 4) == hipSuccess &&
-         dev_alloc((void**)&pf->res_dev, 64) == hipSuccess && dev_alloc((void**)&pf->sums_acc, 64) == hipSuccess &&
-         dev_alloc(&pf->res_all, 64 * G) == hipSuccess &&
-         hipMemset(pf->sums_acc, 0, 64) == hipSuccess;
+         dev_alloc((void**)&pf->res_dev, 128) == hipSuccess && dev_alloc((void**)&pf->sums_acc, 128) == hipSuccess &&
+         dev_alloc(&pf->res_all, 128 * G) == hipSuccess &&
+         hipMemset(pf->sums_acc, 0, 128) == hipSuccess;
     // results come back through the engine's mapped buffer (one session per engine; see engine_internal.h for why the
     // session does not allocate its own); the engine was drained above, so nothing of an earlier session writes to it any more
     pf->h_res = static_cast<decltype(pf->h_res)>(e->h_pf_res);
@@ -1268,7 +1268,38 @@ int pf_mean(slam_pf* pf, float ref_theta, float pose[3])
         th = x + 2 * sn;
         idx = pf->pose_idx[pf->cur];
     }
-    unsigned int* ticket = reinterpret_cast<unsigned int*>(pf->sums_acc + 4);
+    unsigned int* ticket = reinterpret_cast<unsigned int*>(pf->sums_acc + kPoseSumsWeighted);
+    // A frame the resample gate kept (its verdict is on its way to mapped host memory: wait for it) left unequal weights:
+    // the weighted mean of DESIGN.md section 7.  Nine sums, so they come back by a copy, not through the mapped payload.
+    int resampled = 1;
+    if (pf->gated && pf->has_anc)
+        if (int rc = slam_resample_happened_host(e, &resampled)) return rc;
+    if (!resampled) {
+        constexpr int K = kPoseSumsWeighted;
+        long long* out = reinterpret_cast<long long*>(pf->res_dev);
+        SLAM_HIP_TRY(e, launch_pose_sums(e->stream, x, y, th, idx, pf->n, ref_theta, pf->sums_acc, ticket, out, nullptr, nullptr, 0,
+                                         e->carry_buf.as<float>()));
+        const void* src = out;
+        if (pf->comm) {
+            if (int rc = comm_all_gather(pf->comm, pf->res_dev, pf->res_all, K * sizeof(long long))) return rc;
+            src = pf->res_all;
+        }
+        std::vector<long long> all(K * (size_t)pf->world);
+        SLAM_HIP_TRY(e, hipMemcpyAsync(all.data(), src, all.size() * 8, hipMemcpyDeviceToHost, e->stream));
+        if (int rc = wait_stream(pf)) return rc;
+        long long w[K] = { 0 };
+        for (int q = 0; q < pf->world; ++q)
+            for (int k = 0; k < K; ++k) w[k] += all[K * (size_t)q + k];   // every limb sum of the whole population fits 64 bits
+        if (w[8] > 0) {   // (no weight at all: log-weights that are not numbers — the plain mean below)
+            double v[4];
+            for (int k = 0; k < 4; ++k)   // trunc(sum w16 V / sum w16): C's division truncates
+                v[k] = (double)(long long)(((__int128)w[2 * k] * 2097152 + w[2 * k + 1]) / w[8]);
+            pose[0] = (float)(v[0] / 4294967296.0);
+            pose[1] = (float)(v[1] / 4294967296.0);
+            pose[2] = (float)((double)ref_theta + atan2(v[2], v[3]));
+            return SLAM_OK;
+        }
+    }
     long long sums[4] = { 0, 0, 0, 0 };
     if (!pf->comm) {
         const uint32_t seq = ++pf->res_seq;

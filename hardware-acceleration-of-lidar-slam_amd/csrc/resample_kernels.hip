@@ -672,7 +672,7 @@ __global__ __launch_bounds__(kBlock) void gather_map_kernel(const float* __restr
         for (int l = threadIdx.x; l < nlandmarks; l += kBlock) dst[pl * out_plane_stride + l] = src[pl * in_plane_stride + l];
 }
 
-// index of the largest value, lowest index on ties (the heaviest particle); one workgroup
+// index of the largest value, lowest index on ties, NaN never wins (the heaviest particle); one workgroup
 __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ v, int n, int32_t* __restrict__ idx_out,
                                                       float* __restrict__ val_out)
 {
@@ -695,7 +695,7 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
     if (threadIdx.x == 0) {
         for (int w = 1; w < 16; ++w)
             if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
-        *idx_out = bi == 0x7fffffff ? 0 : bi;
+        *idx_out = bv > -INFINITY ? bi : 0;   // nothing but -inf and NaN: particle 0
         *val_out = bv;
     }
 }
@@ -727,7 +727,7 @@ __global__ __launch_bounds__(1024) void best_particle_kernel(const float* __rest
     if (threadIdx.x != 0) return;
     for (int w = 1; w < 16; ++w)
         if (s_v[w] > bv || (s_v[w] == bv && s_i[w] < bi)) { bv = s_v[w]; bi = s_i[w]; }
-    if (bi == 0x7fffffff) bi = 0;
+    if (!(bv > -INFINITY)) bi = 0;   // nothing but -inf and NaN: particle 0
     const float r[5] = { bv, __int_as_float((int32_t)(first_id + bi)), px[bi], py[bi], pth[bi] };
     for (int k = 0; k < 5; ++k) out5[k] = r[k];
     if (h_out5) {
@@ -740,44 +740,59 @@ __global__ __launch_bounds__(1024) void best_particle_kernel(const float* __rest
 // Exact, order-independent sums over the population for the posterior mean: x and y as 2^-32 fixed point, the heading
 // as sin / cos of (theta - ref) in 2^-30 fixed point (det_sincosf: the specified polynomial), accumulated with 64-bit
 // integer atomics — the same bits for any summation order, workgroup count or sharding.  idx (optional): the pending
-// resample gather.  The last workgroup to finish (a ticket) hands the four sums over — to device memory and,
+// resample gather.  The last workgroup to finish (a ticket) hands the sums over — to device memory and,
 // optionally, mapped host memory behind a sequence number — and clears the accumulators for the next call.
+// WEIGHTED (a frame the resample gate kept): slot i counts with the 16-bit weight the gate's S is made
+// of, w16 = quantise(det_exp(carry[i])) >> 16 <= 2^16.  The products pass 64 bits, so every value V goes in as two limbs,
+// w16 * (V >> 21) and w16 * (V & 0x1fffff): nine sums {x hi, x lo, y hi, y lo, sin hi, sin lo, cos hi, cos lo, sum w16}.
+// |V| <= 2^42 (|x|, |y| <= 1024 m) keeps a limb product below 2^37, and 2^23 of them below 2^60.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(kBlock) void pose_sums_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                            const float* __restrict__ th, const int32_t* __restrict__ idx,
-                                                           int n, float ref_th, unsigned long long* __restrict__ acc,
-                                                           unsigned int* __restrict__ ticket, long long* __restrict__ out4,
-                                                           long long* __restrict__ h_out4, uint32_t* __restrict__ h_seq,
+                                                           const float* __restrict__ carry, int n, float ref_th,
+                                                           unsigned long long* __restrict__ acc,
+                                                           unsigned int* __restrict__ ticket, long long* __restrict__ out,
+                                                           long long* __restrict__ h_out, uint32_t* __restrict__ h_seq,
                                                            uint32_t seq)
 {
+    constexpr int kSums = WEIGHTED ? kPoseSumsWeighted : kPoseSumsPlain;
     __shared__ uint64_t s_red[kBlock / 64];
-    uint64_t sx = 0, sy = 0, ss = 0, sc = 0;   // two's complement: signed sums through unsigned adds
+    uint64_t sum[kSums];   // two's complement: signed sums through unsigned adds
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) sum[k] = 0;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         const int j = idx ? idx[i] : i;
         float s, c;
         det_sincosf(th[j] - ref_th, s, c);
-        sx += (uint64_t)(long long)(x[j] * 4294967296.0f);
-        sy += (uint64_t)(long long)(y[j] * 4294967296.0f);
-        ss += (uint64_t)(long long)(s * 1073741824.0f);
-        sc += (uint64_t)(long long)(c * 1073741824.0f);
+        const long long v[4] = { (long long)(x[j] * 4294967296.0f), (long long)(y[j] * 4294967296.0f),
+                                 (long long)(s * 1073741824.0f), (long long)(c * 1073741824.0f) };
+        if (WEIGHTED) {
+            const long long w = (long long)((uint64_t)(det_expf(carry[i]) * 4294967296.0f) >> 16);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                sum[2 * k] += (uint64_t)(w * (v[k] >> 21));
+                sum[2 * k + 1] += (uint64_t)(w * (v[k] & 0x1fffffll));
+            }
+            sum[8] += (uint64_t)w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sum[k] += (uint64_t)v[k];
+        }
     }
-    sx = block_sum_u64(sx, s_red);
-    sy = block_sum_u64(sy, s_red);
-    ss = block_sum_u64(ss, s_red);
-    sc = block_sum_u64(sc, s_red);
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) sum[k] = block_sum_u64(sum[k], s_red);
     if (threadIdx.x != 0) return;
-    atomicAdd(&acc[0], (unsigned long long)sx);
-    atomicAdd(&acc[1], (unsigned long long)sy);
-    atomicAdd(&acc[2], (unsigned long long)ss);
-    atomicAdd(&acc[3], (unsigned long long)sc);
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) atomicAdd(&acc[k], (unsigned long long)sum[k]);
     __threadfence();
     if (atomicAdd(ticket, 1u) != gridDim.x - 1) return;
     __threadfence();
-    long long r[4];
-    for (int k = 0; k < 4; ++k) r[k] = (long long)atomicExch(&acc[k], 0ull);   // read and clear for the next call
+    long long r[kSums];
+    for (int k = 0; k < kSums; ++k) r[k] = (long long)atomicExch(&acc[k], 0ull);   // read and clear for the next call
     *ticket = 0;
-    for (int k = 0; k < 4; ++k) out4[k] = r[k];
-    if (h_out4) {
-        for (int k = 0; k < 4; ++k) h_out4[k] = r[k];
+    for (int k = 0; k < kSums; ++k) out[k] = r[k];
+    if (h_out) {
+        for (int k = 0; k < kSums; ++k) h_out[k] = r[k];
         __threadfence_system();
         __hip_atomic_store(h_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -919,12 +934,15 @@ hipError_t launch_best_particle(hipStream_t stream, const float* v, int n, const
 }
 
 hipError_t launch_pose_sums(hipStream_t stream, const float* x, const float* y, const float* th, const int32_t* idx,
-                            int n, float ref_th, unsigned long long* acc, unsigned int* ticket, long long* out4,
-                            long long* h_out4, uint32_t* h_seq, uint32_t seq)
+                            int n, float ref_th, unsigned long long* acc, unsigned int* ticket, long long* out,
+                            long long* h_out, uint32_t* h_seq, uint32_t seq, const float* carry)
 {
     if (n <= 0) return hipSuccess;
     const int nb = blocks_for(n) < 256 ? blocks_for(n) : 256;
-    pose_sums_kernel<<<nb, kBlock, 0, stream>>>(x, y, th, idx, n, ref_th, acc, ticket, out4, h_out4, h_seq, seq);
+    if (carry)
+        pose_sums_kernel<true><<<nb, kBlock, 0, stream>>>(x, y, th, idx, carry, n, ref_th, acc, ticket, out, h_out, h_seq, seq);
+    else
+        pose_sums_kernel<false><<<nb, kBlock, 0, stream>>>(x, y, th, idx, nullptr, n, ref_th, acc, ticket, out, h_out, h_seq, seq);
     return hipGetLastError();
 }
 

@@ -7,9 +7,9 @@
  * is the pose search: instead of the reference's two 27-pose lattice sweeps (main.c:901-918) every frame
  * runs one particle-filter step on the GPU — N particles are moved by the constant-velocity increment of
  * main.c:875-898 plus noise, each is scored against the fine EDT with the reference's own score function,
- * weights are normalised and the population is resampled; the frame's pose is the mean of the resampled
- * (hence equally weighted) population (exact fixed-point sums on the device) — or, with estimator "best", the
- * heaviest particle.
+ * weights are normalised and the population is resampled; the frame's pose is the posterior mean of the
+ * population (exact fixed-point sums on the device: the plain mean of a resampled, hence equally weighted population,
+ * the weighted mean of a frame that --ess kept) — or, with estimator "best", the heaviest particle.
  * All of it goes through the C ABI (slam_pf_* in include/slam_hip.h); no HIP or RCCL type appears here.
  *
  * Several GPUs: the accelerator handle is created once per GPU and threaded through, the shape of the reference's
@@ -158,8 +158,9 @@ static void *rank_main(void *arg)
         CHECK(slam_pf_step(pf, 1, dp, 0));
         float best[3];
         if (run->use_mean) {
-            /* posterior mean = plain mean of the resampled population, over ALL ranks' particles: exact integer sums made on
-             * the device (slam_pf_mean), so the result does not depend on the number of GPUs.  Headings are averaged on the
+            /* posterior mean over ALL ranks' particles = plain mean of a resampled population, weighted mean of one that the
+             * resample gate (--ess) kept: exact integer sums made on the device (slam_pf_mean), so the result does not depend
+             * on the number of GPUs.  Headings are averaged on the
              * circle, around the predicted heading, so that a population straddling +-pi does not average to nonsense and
              * theta stays unwrapped (the reference never normalises angles). */
             CHECK(slam_pf_mean(pf, pose[2] + dp[2], best));

@@ -568,15 +568,29 @@ int slam_pf_step(slam_pf *pf, int slot, const float dp[3], int use_observations)
  * all see the refined poses and their scores.  sweeps = 0 (the initial state; the steps are then ignored) switches it off.
  * Sharded: every rank must make the same call. */
 int slam_pf_refine_set(slam_pf *pf, float step_xy, float step_theta, int sweeps);
-/* heaviest particle of the last frame (lowest index on ties): its pose, log-weight and index; synchronises.
+/* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
+ * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
 int slam_pf_best(slam_pf *pf, float pose[3], float *logw, int32_t *index);
-/* Posterior mean of the current (resampled, hence equally weighted) population: x and y are averaged, the heading is
- * averaged on the circle around `ref_theta` (theta = ref + atan2(sum sin(theta_i - ref), sum cos(theta_i - ref)), so a
- * population straddling +-pi does not average to nonsense and theta stays unwrapped — the reference never normalises
- * angles; pass the predicted heading).  The sums are exact fixed-point integer sums made on the device (x, y
- * in 2^-32, sin / cos in 2^-30 units), so the result is bit-identical for any workgroup count and any number of GPUs;
- * one launch, the four sums land in mapped host memory (no copy of the population, no stream synchronisation).
+/* Posterior mean of the current population: x and y are averaged, the heading is averaged on the circle around
+ * `ref_theta` (theta = ref + atan2(sum sin(theta_i - ref), sum cos(theta_i - ref)), so a population straddling +-pi does
+ * not average to nonsense and theta stays unwrapped — the reference never normalises angles; pass the
+ * predicted heading).  The sums are exact fixed-point integer sums made on the device, X_i = trunc(x_i * 2^32) and Y_i
+ * likewise, S_i / C_i = trunc(sin / cos(theta_i - ref) * 2^30) (the cast of C: towards zero), so the result is
+ * bit-identical for any workgroup count and any number of GPUs.
+ *   Frames that resampled, sessions without a gate and sessions before their first step (equal weights): the plain mean,
+ *     x = float(double(sum X) / 2^32 / n_total), theta = float(ref + atan2(double(sum S), double(sum C)));
+ *   one launch, the four sums land in mapped host memory (no copy of the population, no stream synchronisation).
+ *   Domain: the sums are 64-bit, |sum X| <= n_total * max|x| * 2^32 must stay below 2^63: n_total * max|x| < 2^31 metres
+ *   (256 m at 2^23 particles; |S|, |C| <= 2^30 never get there with n_total < 2^31).
+ *   Frames the resample gate kept (cfg.resample_ess_frac in (0, 1), the last frame did not resample): the particles carry
+ *   unequal weights, and particle i counts with the 16-bit weight the gate's own sums are made of,
+ *     w16_i = (uint64)(det_exp(logw_i - max logw) * 2^32) >> 16,    D = sum w16 (the gate's S),
+ *     Qx = trunc(sum w16_i X_i / D) (Qy, Qs, Qc alike),  x = float(double(Qx) / 2^32),  theta = float(ref + atan2(Qs, Qc)).
+ *   The device sums every product as two limbs, w16 * (V >> 21) and w16 * (V & 0x1fffff), the host joins them in 128 bits.
+ *   Domain: w16 <= 2^16 and |V >> 21| <= 2^21 for |x|, |y| <= 1024 m, so a limb product is at most 2^37 and the sum of
+ *   n_total <= 2^23 of them at most 2^60 < 2^63; the call waits for the gate's verdict and for the nine sums (a copy).
+ *   set_poses / reset discard the carried weights: the mean after them is the plain one again.
  * Sharded: collective, the same answer on every rank. */
 int slam_pf_mean(slam_pf *pf, float ref_theta, float pose[3]);
 /* rows this rank received in the exchange of the last completed frame (0 on a single GPU) */
