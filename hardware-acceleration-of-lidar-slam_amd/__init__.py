@@ -112,6 +112,8 @@ SIGNATURES = {
     "slam_exchange_set_capacity": (_i, [_vp, _i]),
     "slam_ekf_form_set": (_i, [_vp, _i]),
     "slam_ekf_form_counts": (_i, [_vp, _vp]),
+    "slam_ekf_update_aniso_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "slam_ekf_aniso_count": (_i, [_vp, _vp]),
     "slam_selftest_reciprocal": (_i, [_vp, _vp, _vp]),
     "slam_frame_fusion_set": (_i, [_vp, _i]),
     "slam_frame_fusion_count": (_i, [_vp, _vp]),
@@ -146,6 +148,7 @@ SIGNATURES = {
     "slam_pf_set_map_host": (_i, [_vp, _vp]),
     "slam_pf_step": (_i, [_vp, _i, _fp, _i]),
     "slam_pf_refine_set": (_i, [_vp, _f, _f, _i]),
+    "slam_pf_meas_cov_set": (_i, [_vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
     "slam_pf_get_poses_host": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_map_host": (_i, [_vp, _vp]),
@@ -389,6 +392,18 @@ class Engine:
         self._ck(self.lib.slam_ekf_update_dev(self.h, _ptr(d_map_in), _ptr(d_map_out), row_stride, plane_stride, nlandmarks,
                                               _ptr(d_x), _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, meas_var,
                                               _ptr(d_loglik)), "ekf_update_dev")
+
+    def ekf_update_aniso_dev(self, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, meas_cov,
+                             d_loglik):
+        """``slam_ekf_update_aniso_dev``: ekf_update_dev with a 2x2 sensor-frame measurement covariance, meas_cov = (qxx, qxy, qyy)."""
+        self._ck(self.lib.slam_ekf_update_aniso_dev(self.h, _ptr(d_map_in), _ptr(d_map_out), row_stride, plane_stride, nlandmarks,
+                                                    _ptr(d_x), _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, _f3(meas_cov),
+                                                    _ptr(d_loglik)), "ekf_update_aniso_dev")
+
+    def ekf_aniso_count(self) -> int:
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_ekf_aniso_count(self.h, C.byref(c)), "ekf_aniso_count")
+        return int(c.value)
 
     def logweight_dev(self, d_score, d_loglik, gain, n, d_logw, d_max):
         self._ck(self.lib.slam_logweight_dev(self.h, _ptr(d_score), _ptr(d_loglik), gain, n, _ptr(d_logw), _ptr(d_max)),
@@ -838,6 +853,11 @@ class PfSession:
     def refine_set(self, step_xy: float, step_theta: float, sweeps: int):
         """sweeps in 1..16: every frame refines its motion samples on the 27-pose lattice; 0 switches it off."""
         self.e._ck(self.e.lib.slam_pf_refine_set(self.h, step_xy, step_theta, sweeps), "pf_refine_set")
+
+    def meas_cov_set(self, meas_cov):
+        """``slam_pf_meas_cov_set``: (qxx, qxy, qyy) of the sensor-frame measurement covariance; rows sessions only;
+        (meas_var, 0, meas_var) switches back to the isotropic update."""
+        self.e._ck(self.e.lib.slam_pf_meas_cov_set(self.h, _f3(meas_cov)), "pf_meas_cov_set")
 
     def best(self):
         pose = (C.c_float * 3)()

@@ -53,20 +53,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void ekf_update_kernel(EkfArgs a)
     w.L = (unsigned)a.nlandmarks;
     w.p.s = bc2(st_); w.p.c = bc2(ct_); w.p.px = bc2(a.x[i]); w.p.py = bc2(a.y[i]); w.q = bc2(a.meas_var);
 
-    v2f acc = bc2(0.0f);   // lane j: .x = accumulator j, .y = accumulator j + 64 of the spec (landmark l -> l mod 128)
-    unsigned lb = 0;
-    if (COPY) {   // whole batches that fit into the row, padding included: nothing predicated
-        const unsigned room = (unsigned)a.plane_stride;
-        for (; lb < w.L && lb + 128u * NB <= room; lb += 128u * NB) ekf_batches<NB, true, COPY>(w, lb, lane, acc);
-        if (NB > 1)
-            for (; lb < w.L && lb + 128u <= room; lb += 128u) ekf_batches<1, true, COPY>(w, lb, lane, acc);
-    }
-    // the general form (row tails; in-place updates).  In place only observed landmarks are touched, so a wavefront's
-    // time is round trips, not bytes: NB batches go through one round trip together (batches beyond L load nothing).
-    constexpr int NBT = COPY ? 1 : NB;
-    for (; lb < w.L; lb += 128u * NBT) ekf_batches<NBT, false, COPY>(w, lb, lane, acc);
-
-    const float total = wave_xor_tree_sum(acc[0] + acc[1]);
+    const float total = ekf_row_walk<NB, COPY>(w, (unsigned)a.plane_stride, lane);
     if (lane == 0) store_loglik(a, i, total);
 }
 

@@ -15,26 +15,17 @@
 
 namespace slam {
 
-struct EkfLane {   // per-wavefront constants of one particle
-    // source row and destination row (p.rout) as buffer resources (wave-uniform descriptors in SGPRs): an access is
-    // "descriptor + 32-bit lane offset + scalar plane offset", no 64-bit vector arithmetic for loads or stores
-    __amdgpu_buffer_rsrc_t rin;
-    EkfPose p;
-    int pl;   // plane stride in bytes
-    const gchar *ozx, *ozy;
-    unsigned L;
-    v2f q;
-};
-
 // What goes into the row for the two landmarks of a lane, given the update's result in r0 .. r4 / ll: a first sighting
-// (prior P_xx < 0) takes the observed point and P = q I and adds no likelihood term; a landmark without an observation keeps
+// (prior P_xx < 0) takes the observed point and P = (fxx, fxy, fyy) — q I, or the particle's R_w when the measurement covariance
+// is a full 2x2 (ekf_aniso_kernels.hip) — and adds no likelihood term; a landmark without an observation keeps
 // its prior values.  Both cases are decided for the WAVEFRONT first (a ballot each): in a running filter most batches of
 // 128 landmarks hold neither — every landmark seen before, every one observed, or none — and then the selects (and the
 // arithmetic of the first sighting) are skipped altogether.  The values are those of
-//     ob ? (first ? {f0, f1, q, 0, q; 0} : {o0 .. o4; ll}) : {prior; 0}
+//     ob ? (first ? {f0, f1, fxx, fxy, fyy; 0} : {o0 .. o4; ll}) : {prior; 0}
 // in every case.
 __device__ __forceinline__ void ekf_select(v2f& r0, v2f& r1, v2f& r2, v2f& r3, v2f& r4, v2f& ll, v2f mx, v2f my, v2f pxx, v2f pxy,
-                                           v2f pyy, v2f zx, v2f zy, v2f s, v2f c, v2f px, v2f py, v2f q, bool ob0, bool ob1)
+                                           v2f pyy, v2f zx, v2f zy, v2f s, v2f c, v2f px, v2f py, v2f fxx, v2f fxy, v2f fyy, bool ob0,
+                                           bool ob1)
 {
     if (__ballot(pxx[0] < 0.0f || pxx[1] < 0.0f) != 0) {
         v2f f0, f1;
@@ -44,9 +35,9 @@ __device__ __forceinline__ void ekf_select(v2f& r0, v2f& r1, v2f& r2, v2f& r3, v
             const bool first = pxx[t] < 0.0f;
             r0[t] = first ? f0[t] : r0[t];
             r1[t] = first ? f1[t] : r1[t];
-            r2[t] = first ? q[t] : r2[t];
-            r3[t] = first ? 0.0f : r3[t];
-            r4[t] = first ? q[t] : r4[t];
+            r2[t] = first ? fxx[t] : r2[t];
+            r3[t] = first ? fxy[t] : r3[t];
+            r4[t] = first ? fyy[t] : r4[t];
             ll[t] = first ? 0.0f : ll[t];
         }
     }
@@ -64,14 +55,34 @@ __device__ __forceinline__ void ekf_select(v2f& r0, v2f& r1, v2f& r2, v2f& r3, v
     }
 }
 
+struct EkfLane {   // per-wavefront constants of one particle
+    // source row and destination row (p.rout) as buffer resources (wave-uniform descriptors in SGPRs): an access is
+    // "descriptor + 32-bit lane offset + scalar plane offset", no 64-bit vector arithmetic for loads or stores
+    __amdgpu_buffer_rsrc_t rin;
+    EkfPose p;
+    int pl;   // plane stride in bytes
+    const gchar *ozx, *ozy;
+    unsigned L;
+    v2f q;
+    // what goes into the row for the two landmarks of a lane (ob0 / ob1: they have an observation) and their likelihood terms
+    __device__ __forceinline__ void update(v2f mx, v2f my, v2f pxx, v2f pxy, v2f pyy, v2f zx, v2f zy, bool ob0, bool ob1, v2f& r0, v2f& r1,
+                                           v2f& r2, v2f& r3, v2f& r4, v2f& ll) const
+    {
+        const EkfResult<v2f> u = ekf_update_one<v2f, false>(mx, my, pxx, pxy, pyy, zx, zy, p.s, p.c, p.px, p.py, q);
+        r0 = u.o0; r1 = u.o1; r2 = u.o2; r3 = u.o3; r4 = u.o4; ll = u.ll;
+        ekf_select(r0, r1, r2, r3, r4, ll, mx, my, pxx, pxy, pyy, zx, zy, p.s, p.c, p.px, p.py, q, bc2(0.0f), q, ob0, ob1);
+    }
+};
+
 // NB batches of 128 landmarks starting at lb: all loads first, then the arithmetic, then the stores.  A lane owns
 // landmarks l and l + 64 of each batch, so every access is one 256-byte dword access per wavefront (8-byte
 // accesses, a lane owning neighbours, were measured ~20 % slower whenever the source rows come out of L2).
 // FULL: every lane's landmarks lie inside the row (lb + 128*NB <= plane_stride) and the update is out of place,
 // so nothing is predicated; landmarks at or beyond L (row padding) then simply count as "not observed" and their
 // padding values are copied along.  !FULL: the general form (row tails, in-place updates).
-template <int NB, bool FULL, bool COPY>
-__device__ __forceinline__ void ekf_batches(const EkfLane& w, unsigned lb, unsigned lane, v2f& acc)
+// W: the wavefront's constants and its arithmetic (EkfLane; EkfAnisoLane of ekf_aniso_kernels.hip).
+template <int NB, bool FULL, bool COPY, class W>
+__device__ __forceinline__ void ekf_batches(const W& w, unsigned lb, unsigned lane, v2f& acc)
 {
     const float nan = __uint_as_float(0x7fc00000u);
     v2f m[NB][5], zx[NB], zy[NB];
@@ -114,10 +125,8 @@ __device__ __forceinline__ void ekf_batches(const EkfLane& w, unsigned lb, unsig
                 }
             continue;
         }
-        const v2f q = w.q;
-        const EkfResult<v2f> u = ekf_update_one<v2f, false>(mx, my, pxx, pxy, pyy, zx[g], zy[g], w.p.s, w.p.c, w.p.px, w.p.py, q);
-        v2f r0 = u.o0, r1 = u.o1, r2 = u.o2, r3 = u.o3, r4 = u.o4, ll = u.ll;
-        ekf_select(r0, r1, r2, r3, r4, ll, mx, my, pxx, pxy, pyy, zx[g], zy[g], w.p.s, w.p.c, w.p.px, w.p.py, q, obs[g][0], obs[g][1]);
+        v2f r0, r1, r2, r3, r4, ll;
+        w.update(mx, my, pxx, pxy, pyy, zx[g], zy[g], obs[g][0], obs[g][1], r0, r1, r2, r3, r4, ll);
 #pragma unroll
         for (int t = 0; t < 2; ++t)
             if (FULL || use[g][t]) {
@@ -129,6 +138,25 @@ __device__ __forceinline__ void ekf_batches(const EkfLane& w, unsigned lb, unsig
             }
         acc = acc + ll;
     }
+}
+
+// One particle's whole row, NB batches per pass of the fast path (ekf_update_kernel; ekf_aniso_kernel) -> its log-likelihood,
+// in every lane.  room: the plane stride in floats.
+template <int NB, bool COPY, class W>
+__device__ __forceinline__ float ekf_row_walk(const W& w, unsigned room, unsigned lane)
+{
+    v2f acc = bc2(0.0f);   // lane j: .x = accumulator j, .y = accumulator j + 64 of the spec (landmark l -> l mod 128)
+    unsigned lb = 0;
+    if (COPY) {   // whole batches that fit into the row, padding included: nothing predicated
+        for (; lb < w.L && lb + 128u * NB <= room; lb += 128u * NB) ekf_batches<NB, true, COPY>(w, lb, lane, acc);
+        if (NB > 1)
+            for (; lb < w.L && lb + 128u <= room; lb += 128u) ekf_batches<1, true, COPY>(w, lb, lane, acc);
+    }
+    // the general form (row tails; in-place updates).  In place only observed landmarks are touched, so a wavefront's
+    // time is round trips, not bytes: NB batches go through one round trip together (batches beyond L load nothing).
+    constexpr int NBT = COPY ? 1 : NB;
+    for (; lb < w.L; lb += 128u * NBT) ekf_batches<NBT, false, COPY>(w, lb, lane, acc);
+    return wave_xor_tree_sum(acc[0] + acc[1]);
 }
 
 }  // namespace slam

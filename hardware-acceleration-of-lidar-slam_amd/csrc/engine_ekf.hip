@@ -3,6 +3,7 @@
 // with motion + score as the frame's front launch), and the switches and counters of those forms.
 
 #include <hip/hip_runtime.h>
+#include <stdio.h>
 
 #include <limits>
 
@@ -244,6 +245,39 @@ int slam_ekf_update_dev(slam_engine* e, const float* d_map_in, float* d_map_out,
         e->ekf_form_launches[group ? 1 : 0]++;
     }
     e->ll_n = n;
+    return SLAM_OK;
+}
+
+int slam_ekf_update_aniso_dev(slam_engine* e, const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride,
+                              int nlandmarks, const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc, int n,
+                              const float meas_cov[3], float* d_loglik)
+{
+    SLAM_ENTER(e);
+    if (n < 0 || nlandmarks < 0 || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride || !meas_cov ||
+        (n > 0 && (!d_map_in || !d_map_out || !d_x || !d_y || !d_th)))
+        return SLAM_ERR_INVALID_ARG;
+    const EkfAnisoCov q = ekf_aniso_cov(meas_cov);
+    if (!ekf_aniso_cov_ok(q)) {
+        snprintf(e->err, sizeof e->err, "meas_cov must be finite with qxx > 0, qyy > 0 and qxx * qyy - qxy * qxy > 0 in float32");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (d_anc && d_map_in == d_map_out) return SLAM_ERR_INVALID_ARG;
+    if (e->obs_nlandmarks < 0 || e->obs_nlandmarks != nlandmarks) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
+    // (meas_var of the arguments is not read by this form)
+    const EkfArgs a = ekf_args(e, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, 0.0f, d_loglik);
+    SLAM_HIP_TRY(e, launch_ekf_aniso(e->stream, a, q, e->prof_next(SLAM_PROF_EKF)));
+    e->ekf_aniso_launches++;
+    e->ll_n = n;
+    return SLAM_OK;
+}
+
+int slam_ekf_aniso_count(slam_engine* e, int64_t* launches)
+{
+    SLAM_ENTER(e);
+    if (!launches) return SLAM_ERR_INVALID_ARG;
+    *launches = e->ekf_aniso_launches;
     return SLAM_OK;
 }
 

@@ -152,6 +152,7 @@ struct slam_engine {
     bool pf_paged = false;     // slam_pf_paged_set: sessions made from now on keep their maps as copy-on-write pages
     int ekf_form = -1;         // slam_ekf_form_set: -1 choose by the feedback, 0 row per wavefront, 1 / 2 grouped by 4 / 2
     int64_t ekf_form_launches[2] = { 0, 0 };   // out-of-place launches so far: [0] one wavefront per particle, [1] grouped
+    int64_t ekf_aniso_launches = 0;            // slam_ekf_update_aniso_dev launches so far (they count in neither form counter)
     // particles per wavefront of an out-of-place update that gathers through `anc` (0 = one wavefront per particle).  With the
     // covariance part of the update hoisted (ekf_prepare) the kernel is memory-bound and behaves like the grouped pure copy of
     // profiles/copy_ceiling.hip: 2 rows per wavefront beat 4 and 8 (update alone at 64k x 500: 133 | 145 | 155 us; fused

@@ -180,6 +180,28 @@ hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a, const EventPa
 // split layout: the MEAN ROWS of launch_ekf_update alone, bit for bit — no log-likelihood, no class, no stamp is written; reads
 // the stored poses a.x / a.y / a.th; optionally for the survivors only (EkfArgs::survivor).  group_size as above.
 hipError_t launch_ekf_materialise(hipStream_t stream, const EkfArgs& a, const EventPair* ev, int group_size);
+// ---- ekf_aniso_kernels.hip: the same update with a full 2x2 measurement covariance Q in the sensor frame (ekf_aniso_math.h;
+// rows only: the posterior covariance then depends on the particle's heading).  Q and its float32 determinant:
+struct EkfAnisoCov {
+    float qxx, qxy, qyy, detq;
+};
+// detq = qxx * qyy - qxy * qxy: two products and one subtraction, each rounded to float32 (-ffp-contract=off)
+inline EkfAnisoCov ekf_aniso_cov(const float meas_cov[3])
+{
+    EkfAnisoCov q{ meas_cov[0], meas_cov[1], meas_cov[2], 0.0f };
+    const float xx = q.qxx * q.qyy, xy = q.qxy * q.qxy;
+    q.detq = xx - xy;
+    return q;
+}
+// every value finite, qxx > 0, qyy > 0 and the float32 determinant > 0 (NaN fails every comparison)
+inline bool ekf_aniso_cov_ok(const EkfAnisoCov& q)
+{
+    const float big = 3.402823466e+38f;
+    return q.qxx > 0.0f && q.qyy > 0.0f && q.detq > 0.0f && q.qxx <= big && q.qyy <= big && q.qxy >= -big && q.qxy <= big;
+}
+// one wavefront per particle, out of place (through a.anc, unobserved landmarks copied) or in place (a.map_in == a.map_out:
+// only observed landmarks touched); a.meas_var is not read, a.cov must be null
+hipError_t launch_ekf_aniso(hipStream_t stream, const EkfArgs& a, const EkfAnisoCov& q, const EventPair* ev = nullptr);
 bool frame_front_fits(int n, int nlandmarks, int group_size);   // the shapes launch_frame_front takes
 // motion sample + scan-match score AND the grouped out-of-place landmark update in ONE launch (single-GPU frames on rows): the
 // gathers of the scorer run in the shadow of the update's row stores.  `a.x / a.y / a.th` are not read (the update works out

@@ -136,6 +136,10 @@ struct slam_pf {
     // slam_pf_refine_set: sweeps > 0: the front launch of a frame is motion + refine (refine_kernels.hip), never the fused front
     float refine_step_xy = 0.0f, refine_step_theta = 0.0f;
     int refine_sweeps = 0;
+    // slam_pf_meas_cov_set (rows only): a full 2x2 measurement covariance — the landmark update of every frame is
+    // slam_ekf_update_aniso_dev, a launch of its own (never the fused front)
+    bool aniso = false;
+    float meas_cov[3] = { 0.0f, 0.0f, 0.0f };
     // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe (RES_OBS) and moves between split and
     // split pages while it runs (between rows and pages when it could not have the split layout's tables)
     int layout_cfg = SLAM_MAP_AUTO;
@@ -984,7 +988,8 @@ int front_stage(slam_pf* pf, FrameFacts& f, int slot, const float dp[3])
         }
         return SLAM_OK;
     }
-    const bool front = comm ? pf->split && !pf->paged && pf->has_anc && !pf->gated : !pf->paged && (!pf->gated || pf->split);
+    // General measurement covariance (rows only): its update exists as a launch of its own alone.
+    const bool front = !pf->aniso && (comm ? pf->split && !pf->paged && pf->has_anc && !pf->gated : !pf->paged && (!pf->gated || pf->split));
     if (front && f.anc && f.observing) {
         const float* ps = f.src;
         const int32_t* pose_anc = f.anc;
@@ -1064,10 +1069,15 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
     float* dst = f.dst;
     if (f.ekf) {
         if (f.sample_obs) SLAM_HIP_TRY(e, launch_obs_count(e->stream, e->d_obs_zx, e->d_obs_zy, L, dev_word(pf, RES_OBS), ++pf->obs_seq_issued, pf->votes));
-        if (!f.fused)   // (fused: the update went out with the score; in place: no gather, the buffers do not flip)
-            if (int rc = slam_ekf_update_dev(e, pf->map[mc], pf->map[f.in_place ? mc : mn], stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn,
-                                             f.in_place ? nullptr : f.anc, n, pf->cfg.meas_var, nullptr))
+        if (!f.fused) {   // (fused: the update went out with the score; in place: no gather, the buffers do not flip)
+            float* out = pf->map[f.in_place ? mc : mn];
+            const int32_t* anc = f.in_place ? nullptr : f.anc;
+            if (int rc = pf->aniso ? slam_ekf_update_aniso_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n,
+                                                               pf->meas_cov, nullptr)
+                                   : slam_ekf_update_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n,
+                                                         pf->cfg.meas_var, nullptr))
                 return rc;
+        }
         if (!f.in_place) pf->map_cur = mn;
         return slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
     }
@@ -1582,6 +1592,24 @@ int slam_pf_refine_set(slam_pf* pf, float step_xy, float step_theta, int sweeps)
     pf->refine_step_xy = sweeps ? step_xy : 0.0f;
     pf->refine_step_theta = sweeps ? step_theta : 0.0f;
     pf->refine_sweeps = sweeps;
+    return SLAM_OK;
+}
+
+int slam_pf_meas_cov_set(slam_pf* pf, const float meas_cov[3])
+{
+    if (!pf || !meas_cov) return SLAM_ERR_INVALID_ARG;
+    if (pf->layout_cfg != SLAM_MAP_ROWS || pf->L == 0) {
+        snprintf(pf->e->err, sizeof pf->e->err, "a 2x2 measurement covariance makes the landmark covariances per particle: that needs the "
+                                                "row layout (map_layout = SLAM_MAP_ROWS, n_landmarks > 0)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (!ekf_aniso_cov_ok(ekf_aniso_cov(meas_cov))) {
+        snprintf(pf->e->err, sizeof pf->e->err, "meas_cov must be finite with qxx > 0, qyy > 0 and qxx * qyy - qxy * qxy > 0 in float32");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    for (int k = 0; k < 3; ++k) pf->meas_cov[k] = meas_cov[k];
+    // {meas_var, 0, meas_var}: the session's own isotropic update again, exactly as without this call
+    pf->aniso = !(meas_cov[0] == pf->cfg.meas_var && meas_cov[1] == 0.0f && meas_cov[2] == pf->cfg.meas_var);
     return SLAM_OK;
 }
 

@@ -53,6 +53,8 @@ typedef struct {
     float ess_frac;        /* --ess F: resample only when the effective sample size is below F * N (0: every frame) */
     int refine_sweeps;     /* --refine SWEEPS (0: off) */
     float refine_res[2];   /* --refine-res T R */
+    int use_meas_cov;      /* --meas-cov qxx qxy qyy: the session is made on rows and given this measurement covariance */
+    float meas_cov[3];
     /* the ranks */
     int world, use_rccl, same_device;
     uint8_t comm_id[SLAM_COMM_ID_BYTES];
@@ -104,7 +106,8 @@ static void *rank_main(void *arg)
         }
     }
     /* motion noise of the order of the reference's fine lattice step (0.025 m, 0.004363 rad; main.c:833) */
-    const slam_pf_config cfg = { n, 0, { 0.01f, 0.01f, 0.002f }, 1.0f, 0.25f, run->seed, run->ess_frac, SLAM_MAP_AUTO };
+    const slam_pf_config cfg = { n, 0, { 0.01f, 0.01f, 0.002f }, 1.0f, 0.25f, run->seed, run->ess_frac,
+                                 run->use_meas_cov ? SLAM_MAP_ROWS : SLAM_MAP_AUTO };
     if (world > 1 || run->use_rccl || run->group) {
         if (run->group) CHECK(slam_comm_create_local(eng, run->group, rank, &comm));
         else CHECK(slam_comm_create_rccl(eng, rank, world, run->comm_id, &comm));
@@ -113,6 +116,14 @@ static void *rank_main(void *arg)
         CHECK(slam_pf_create(eng, &cfg, &pf));
     }
     if (run->refine_sweeps) CHECK(slam_pf_refine_set(pf, run->refine_res[0], run->refine_res[1], run->refine_sweeps));
+    if (run->use_meas_cov) {
+        /* This program's filter keeps no landmarks (n_landmarks = 0): a session without them has no covariance to apply the
+         * matrix to and says so (the values themselves were checked in main).  That is reported, not fatal: the run goes on as
+         * it would on rows.  A program that sets n_landmarks makes the same call and checks its result. */
+        const int rc = slam_pf_meas_cov_set(pf, run->meas_cov);
+        if (cfg.n_landmarks > 0) CHECK(rc);
+        else if (rank == 0) fprintf(stderr, "--meas-cov has no effect here: %s\n", slam_last_error(eng));
+    }
     if (fe_scan_init(&scan, beams, -2.351831f, 0.004363f) || fe_points_init(&map, FE_MAP_CAPACITY + beams) ||
         fe_points_init(&local, FE_LOCAL_CAPACITY) || fe_grid_init(&coarse, FE_COARSE_LD) || fe_grid_init(&fine, FE_FINE_LD) ||
         !(hits = (float *)calloc((size_t)beams + 1, sizeof(float)))) {
@@ -235,12 +246,27 @@ int main(int argc, char **argv)
             run.refine_res[0] = (float)atof(argv[++a]);
             run.refine_res[1] = (float)atof(argv[++a]);
         }
+        else if (!strcmp(argv[a], "--meas-cov") && a + 3 < argc) {
+            run.use_meas_cov = 1;
+            for (int k = 0; k < 3; ++k) run.meas_cov[k] = (float)atof(argv[++a]);
+        }
         else if (npos < 8) pos[npos++] = argv[a];
     }
     if (npos < 5 || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
-                        "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]]\n", argv[0]);
+                        "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
+                        "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
+                        "              while this program keeps no landmarks\n", argv[0]);
         return 2;
+    }
+    if (run.use_meas_cov) {   /* the conditions of slam_pf_meas_cov_set: finite, qxx > 0, qyy > 0, float determinant > 0 */
+        const float *q = run.meas_cov;
+        const float xx = q[0] * q[2], xy = q[1] * q[1];
+        if (!(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]) && q[0] > 0.0f && q[2] > 0.0f && xx - xy > 0.0f)) {
+            fprintf(stderr, "--meas-cov %g %g %g: the values must be finite with QXX > 0, QYY > 0 and QXX * QYY - QXY * QXY > 0\n",
+                    (double)q[0], (double)q[1], (double)q[2]);
+            return 2;
+        }
     }
     run.dataset = pos[0];
     run.frames = atoi(pos[1]);

@@ -283,6 +283,23 @@ int slam_ekf_form_set(slam_engine *e, int form);
 /* out-of-place EKF launches of this engine so far: counts[0] one wavefront per particle, counts[1] the grouped kernel
  * (by itself or inside the fused front launch below) */
 int slam_ekf_form_counts(slam_engine *e, int64_t counts[2]);
+/* GENERAL MEASUREMENT COVARIANCE.  slam_ekf_update_dev is the update for R = meas_var * I.  This is the same stage for a full
+ * 2x2 covariance Q = [[qxx, qxy], [qxy, qyy]] of the observation IN THE SENSOR FRAME (meas_cov = {qxx, qxy, qyy}): a lidar's
+ * range and bearing noise differ by orders of magnitude.  In the world frame the noise is R_w = H^T Q H, H^T = [[c, s],
+ * [-s, c]] with (s, c) the deterministic sine / cosine of the particle's heading, so the posterior covariance depends on
+ * the particle: the stage exists on the row layout only.  With S = P + R_w, d = w - mu and w the observed point in the world
+ * frame:  mu' = w - R_w S^-1 d,  P' = (det P * R_w + det Q * P) / det S,  log-likelihood -1/2 d^T S^-1 d - 1/2 log det S
+ * - log 2 pi; a first sighting stores w and P = R_w.  Operation order: tests/_aniso_spec.py, csrc/ekf_aniso_math.h.
+ * Arguments, argument checks, observation table, forms (d_anc with d_map_in != d_map_out: out of place, unobserved landmarks
+ * copied; d_map_in == d_map_out and d_anc == NULL: in place, only observed landmarks touched), the log-likelihood's
+ * summation order and where it stays (slam_logweight_ekf_dev), padding columns and the SLAM_PROF_EKF bracket are those of
+ * slam_ekf_update_dev.  SLAM_ERR_INVALID_ARG unless every value of meas_cov is finite, qxx > 0, qyy > 0 and
+ * qxx * qyy - qxy * qxy, worked out in float32, is > 0.  One kernel (a wavefront per particle); its launches are counted
+ * by slam_ekf_aniso_count and in neither slam_ekf_form_counts nor slam_ekf_inplace_form_counts. */
+int slam_ekf_update_aniso_dev(slam_engine *e, const float *d_map_in, float *d_map_out, int64_t row_stride, int plane_stride,
+                              int nlandmarks, const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc,
+                              int n, const float meas_cov[3] /* qxx, qxy, qyy */, float *d_loglik);
+int slam_ekf_aniso_count(slam_engine *e, int64_t *launches);
 /* The FRONT of a frame of a single-GPU slam_pf session on rows — motion sample + scan-match score (FastMatch's inner loop,
  * main.c:459-518, for every particle) and the out-of-place landmark update — goes out as ONE launch whose scoring and
  * updating workgroups are dealt out interleaved: the scorer's gathers (texture addresser, L2) run in the shadow of the
@@ -568,6 +585,14 @@ int slam_pf_step(slam_pf *pf, int slot, const float dp[3], int use_observations)
  * all see the refined poses and their scores.  sweeps = 0 (the initial state; the steps are then ignored) switches it off.
  * Sharded: every rank must make the same call. */
 int slam_pf_refine_set(slam_pf *pf, float step_xy, float step_theta, int sweeps);
+/* A full 2x2 measurement covariance for the session's landmark update (slam_ekf_update_aniso_dev; meas_cov = {qxx, qxy,
+ * qyy}, the same conditions).  Legal between frames; sharded: every rank must make the same call.  Only a session created
+ * with map_layout = SLAM_MAP_ROWS and n_landmarks > 0 stores a covariance per particle: any other session returns
+ * SLAM_ERR_INVALID_ARG (slam_last_error says so) and goes on as before.  From then on every frame's update is that stage as a
+ * launch of its own — out of place, in place on the frames a gated session kept its population, through the staging tail
+ * when sharded — and no frame goes out as a fused front launch.  meas_cov = {cfg.meas_var, 0, cfg.meas_var} switches back:
+ * the session then runs exactly what it ran before the first call. */
+int slam_pf_meas_cov_set(slam_pf *pf, const float meas_cov[3]);
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
  * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
