@@ -114,6 +114,11 @@ SIGNATURES = {
     "slam_ekf_form_counts": (_i, [_vp, _vp]),
     "slam_ekf_update_aniso_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "slam_ekf_aniso_count": (_i, [_vp, _vp]),
+    "slam_detections_upload_host": (_i, [_vp, _vp, _vp, _i]),
+    "slam_detections_set_dev": (_i, [_vp, _vp, _vp, _i]),
+    "slam_associate_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _vp, _i, _vp]),
+    "slam_ekf_update_assoc_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _i, _vp]),
+    "slam_assoc_counts": (_i, [_vp, _vp]),
     "slam_selftest_reciprocal": (_i, [_vp, _vp, _vp]),
     "slam_frame_fusion_set": (_i, [_vp, _i]),
     "slam_frame_fusion_count": (_i, [_vp, _vp]),
@@ -149,6 +154,8 @@ SIGNATURES = {
     "slam_pf_step": (_i, [_vp, _i, _fp, _i]),
     "slam_pf_refine_set": (_i, [_vp, _f, _f, _i]),
     "slam_pf_meas_cov_set": (_i, [_vp, _vp]),
+    "slam_pf_assoc_set": (_i, [_vp, _f, _f, _i]),
+    "slam_pf_assoc_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
     "slam_pf_get_poses_host": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_map_host": (_i, [_vp, _vp]),
@@ -404,6 +411,37 @@ class Engine:
         c = C.c_int64(0)
         self._ck(self.lib.slam_ekf_aniso_count(self.h, C.byref(c)), "ekf_aniso_count")
         return int(c.value)
+
+    def detections_upload(self, zx, zy):
+        """``slam_detections_upload_host``: the frame's detections, sensor-frame points without identity (at most 64, finite)."""
+        zx, zy = _np(zx, np.float32), _np(zy, np.float32)
+        assert len(zx) == len(zy)
+        self._ck(self.lib.slam_detections_upload_host(self.h, _ptr(zx), _ptr(zy), len(zx)), "detections_upload")
+
+    def detections_set_dev(self, d_zx, d_zy, ndet):
+        """``slam_detections_set_dev``: the same from two device arrays, adopted and read afresh by every launch."""
+        self._ck(self.lib.slam_detections_set_dev(self.h, _ptr(d_zx), _ptr(d_zy), ndet), "detections_set_dev")
+        self.__dict__.setdefault("_adopted", {})["det"] = (d_zx, d_zy)
+
+    def associate_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, meas_var, gate, new_gate, create,
+                      d_assoc, assoc_stride, d_stats):
+        """``slam_associate_dev``: every particle's table uint8 [n][assoc_stride] (255 = none) and stats int32 [n][3]."""
+        self._ck(self.lib.slam_associate_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x), _ptr(d_y), _ptr(d_th),
+                                             _ptr(d_anc), n, meas_var, gate, new_gate, int(create), _ptr(d_assoc), assoc_stride,
+                                             _ptr(d_stats)), "associate_dev")
+
+    def ekf_update_assoc_dev(self, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, meas_var,
+                             d_assoc, assoc_stride, d_loglik):
+        """``slam_ekf_update_assoc_dev``: ekf_update_dev with particle i's observations read through its table row."""
+        self._ck(self.lib.slam_ekf_update_assoc_dev(self.h, _ptr(d_map_in), _ptr(d_map_out), row_stride, plane_stride, nlandmarks,
+                                                    _ptr(d_x), _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, meas_var, _ptr(d_assoc),
+                                                    assoc_stride, _ptr(d_loglik)), "ekf_update_assoc_dev")
+
+    def assoc_counts(self):
+        """-> (associate launches, assoc-update launches) of this engine so far."""
+        c = (C.c_int64 * 2)()
+        self._ck(self.lib.slam_assoc_counts(self.h, c), "assoc_counts")
+        return int(c[0]), int(c[1])
 
     def logweight_dev(self, d_score, d_loglik, gain, n, d_logw, d_max):
         self._ck(self.lib.slam_logweight_dev(self.h, _ptr(d_score), _ptr(d_loglik), gain, n, _ptr(d_logw), _ptr(d_max)),
@@ -858,6 +896,18 @@ class PfSession:
         """``slam_pf_meas_cov_set``: (qxx, qxy, qyy) of the sensor-frame measurement covariance; rows sessions only;
         (meas_var, 0, meas_var) switches back to the isotropic update."""
         self.e._ck(self.e.lib.slam_pf_meas_cov_set(self.h, _f3(meas_cov)), "pf_meas_cov_set")
+
+    def assoc_set(self, gate: float, new_gate: float = 0.0, create: bool = True):
+        """``slam_pf_assoc_set``: gate > 0: frames associate the engine's detections themselves (single-GPU rows sessions only);
+        gate = 0 switches it off."""
+        self.e._ck(self.e.lib.slam_pf_assoc_set(self.h, gate, new_gate, 1 if create else 0), "pf_assoc_set")
+
+    def assoc_view(self):
+        """``slam_pf_assoc_device_view``: the last frame's table uint8 [n][stride] and stats int32 [n][3], indexed like score."""
+        a, st, stride = C.c_void_p(), C.c_void_p(), C.c_int32(0)
+        self.e._ck(self.e.lib.slam_pf_assoc_device_view(self.h, C.byref(a), C.byref(stride), C.byref(st)), "pf_assoc_device_view")
+        return {"assoc": DeviceArray(a.value, (self.n, stride.value), "|u1", self), "stats": DeviceArray(st.value, (self.n, 3), "<i4", self),
+                "assoc_stride": stride.value}
 
     def best(self):
         pose = (C.c_float * 3)()

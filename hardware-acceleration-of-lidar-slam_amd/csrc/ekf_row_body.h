@@ -74,13 +74,24 @@ struct EkfLane {   // per-wavefront constants of one particle
     }
 };
 
+// The observation of landmark l as a wavefront's lane type supplies it (in: l < L; NaN = none).  This one: the frame's table
+// indexed by landmark, w.ozx / w.ozy (EkfLane, EkfAnisoLane).  A lane type with another source overloads it (assoc_kernels.hip:
+// the particle's own association table).
+template <class W> __device__ __forceinline__ void ekf_obs(const W& w, unsigned l, bool in, float& vx, float& vy)
+{
+    const unsigned zo = (in ? l : 0u) * 4u;   // clamped index + select instead of a predicated load
+    vx = *(const gfloat*)(w.ozx + zo);
+    vy = *(const gfloat*)(w.ozy + zo);
+}
+
 // NB batches of 128 landmarks starting at lb: all loads first, then the arithmetic, then the stores.  A lane owns
 // landmarks l and l + 64 of each batch, so every access is one 256-byte dword access per wavefront (8-byte
 // accesses, a lane owning neighbours, were measured ~20 % slower whenever the source rows come out of L2).
 // FULL: every lane's landmarks lie inside the row (lb + 128*NB <= plane_stride) and the update is out of place,
 // so nothing is predicated; landmarks at or beyond L (row padding) then simply count as "not observed" and their
 // padding values are copied along.  !FULL: the general form (row tails, in-place updates).
-// W: the wavefront's constants and its arithmetic (EkfLane; EkfAnisoLane of ekf_aniso_kernels.hip).
+// W: the wavefront's constants, its arithmetic and where its observations come from (EkfLane; EkfAnisoLane of
+// ekf_aniso_kernels.hip; EkfAssocLane of assoc_kernels.hip).
 template <int NB, bool FULL, bool COPY, class W>
 __device__ __forceinline__ void ekf_batches(const W& w, unsigned lb, unsigned lane, v2f& acc)
 {
@@ -95,8 +106,8 @@ __device__ __forceinline__ void ekf_batches(const W& w, unsigned lb, unsigned la
             const unsigned l = lb + (unsigned)g * 128u + 64u * t + lane;
             const bool in = l < w.L;
             off[g][t] = ((FULL || in) ? l : 0u) * 4u;
-            const unsigned zo = (in ? l : 0u) * 4u;   // clamped index + select instead of a predicated load
-            const float vx = *(const gfloat*)(w.ozx + zo), vy = *(const gfloat*)(w.ozy + zo);
+            float vx, vy;
+            ekf_obs(w, l, in, vx, vy);
             zx[g][t] = in ? vx : nan;
             zy[g][t] = in ? vy : nan;
             // NaN = no observation (also what lanes beyond L were given).  Testing zy as well keeps its load up here

@@ -1,6 +1,7 @@
 // engine_ekf.hip — the landmark side of a particle-filter frame behind the C ABI: motion sample (alone, or with the score of
 // the sampled poses), the observation table, the landmark update in every form (in place, out of place, split layout, fused
-// with motion + score as the frame's front launch), and the switches and counters of those forms.
+// with motion + score as the frame's front launch), the switches and counters of those forms, and data association (the frame's
+// detections, the association stage and the update under a per-particle table).
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -278,6 +279,109 @@ int slam_ekf_aniso_count(slam_engine* e, int64_t* launches)
     SLAM_ENTER(e);
     if (!launches) return SLAM_ERR_INVALID_ARG;
     *launches = e->ekf_aniso_launches;
+    return SLAM_OK;
+}
+
+/* ------------------------------------------------------------------ data association (assoc_kernels.hip) */
+
+int slam_detections_upload_host(slam_engine* e, const float* zx, const float* zy, int ndet)
+{
+    SLAM_ENTER(e);
+    if (ndet < 0 || ndet > SLAM_MAX_DETECTIONS || (ndet > 0 && (!zx || !zy))) return SLAM_ERR_INVALID_ARG;
+    const float big = std::numeric_limits<float>::max();
+    for (int k = 0; k < ndet; ++k)
+        if (!(zx[k] >= -big && zx[k] <= big && zy[k] >= -big && zy[k] <= big)) return SLAM_ERR_INVALID_ARG;   // (NaN fails every comparison)
+    if (!e->det_buf.p) SLAM_HIP_TRY(e, e->det_buf.ensure(sizeof(float) * 2 * SLAM_MAX_DETECTIONS));
+    if (ndet > 0) {
+        float* h = e->stage_acquire();
+        for (int k = 0; k < SLAM_MAX_DETECTIONS; ++k) {   // zx[64] | zy[ndet]: one copy
+            h[k] = k < ndet ? zx[k] : 0.0f;
+            if (k < ndet) h[SLAM_MAX_DETECTIONS + k] = zy[k];
+        }
+        const hipError_t err = hipMemcpyAsync(e->det_buf.as<float>(), h, sizeof(float) * (SLAM_MAX_DETECTIONS + (size_t)ndet),
+                                              hipMemcpyHostToDevice, e->stream);
+        SLAM_HIP_TRY(e, e->stage_release(h));
+        SLAM_HIP_TRY(e, err);
+    }
+    e->d_det_zx = e->det_buf.as<float>();
+    e->d_det_zy = e->det_buf.as<float>() + SLAM_MAX_DETECTIONS;
+    e->ndet = ndet;
+    return SLAM_OK;
+}
+
+int slam_detections_set_dev(slam_engine* e, const float* d_zx, const float* d_zy, int ndet)
+{
+    SLAM_ENTER(e);
+    if (ndet < 0 || ndet > SLAM_MAX_DETECTIONS || (ndet > 0 && (!d_zx || !d_zy))) return SLAM_ERR_INVALID_ARG;
+    e->d_det_zx = d_zx;
+    e->d_det_zy = d_zy;
+    e->ndet = ndet;
+    return SLAM_OK;
+}
+
+int slam_associate_dev(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                       const float* d_y, const float* d_th, const int32_t* d_anc, int n, float meas_var, float gate, float new_gate,
+                       int create, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
+{
+    SLAM_ENTER(e);
+    if (n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
+        assoc_stride < nlandmarks || !(meas_var > 0.0f) || !(gate > 0.0f && gate <= std::numeric_limits<float>::max()) ||
+        !(new_gate >= gate) || (create != 0 && create != 1) || (n > 0 && (!d_map || !d_x || !d_y || !d_th || !d_assoc)))
+        return SLAM_ERR_INVALID_ARG;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    AssocArgs a;
+    a.map = d_map;
+    a.row_stride = row_stride;
+    a.plane_stride = plane_stride;
+    a.nlandmarks = nlandmarks;
+    a.x = d_x;
+    a.y = d_y;
+    a.th = d_th;
+    a.anc = d_anc;
+    a.n = n;
+    a.det_zx = e->d_det_zx;
+    a.det_zy = e->d_det_zy;
+    a.ndet = e->ndet;
+    a.meas_var = meas_var;
+    a.gate = gate;
+    a.new_gate = new_gate;
+    a.assoc = d_assoc;
+    a.assoc_stride = assoc_stride;
+    a.stats = d_stats;
+    a.xcd_chunk = 0;
+    SLAM_HIP_TRY(e, launch_associate(e->stream, a, create != 0, e->prof_next(SLAM_PROF_PAGES)));
+    e->assoc_launches[0]++;
+    return SLAM_OK;
+}
+
+int slam_ekf_update_assoc_dev(slam_engine* e, const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride,
+                              int nlandmarks, const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc, int n,
+                              float meas_var, const uint8_t* d_assoc, int assoc_stride, float* d_loglik)
+{
+    SLAM_ENTER(e);
+    if (n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
+        assoc_stride < nlandmarks || !(meas_var > 0.0f) || (n > 0 && (!d_map_in || !d_map_out || !d_x || !d_y || !d_th || !d_assoc)))
+        return SLAM_ERR_INVALID_ARG;
+    if (d_anc && d_map_in == d_map_out) return SLAM_ERR_INVALID_ARG;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
+    // (the observation table of the arguments is not read by this form)
+    const EkfArgs a = ekf_args(e, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, meas_var, d_loglik);
+    const EkfAssocTable tab{ d_assoc, assoc_stride, e->d_det_zx, e->d_det_zy, e->ndet };
+    SLAM_HIP_TRY(e, launch_ekf_assoc(e->stream, a, tab, e->prof_next(SLAM_PROF_EKF)));
+    e->assoc_launches[1]++;
+    e->ll_n = n;
+    return SLAM_OK;
+}
+
+int slam_assoc_counts(slam_engine* e, int64_t counts[2])
+{
+    SLAM_ENTER(e);
+    if (!counts) return SLAM_ERR_INVALID_ARG;
+    counts[0] = e->assoc_launches[0];
+    counts[1] = e->assoc_launches[1];
     return SLAM_OK;
 }
 

@@ -82,6 +82,13 @@ struct slam_engine {
     int obs_nlandmarks = -1;
     const float *d_obs_zx = nullptr, *d_obs_zy = nullptr;
 
+    // detections of the current frame: sensor-frame points without identity (slam_detections_upload_host / _set_dev), what
+    // slam_associate_dev and slam_ekf_update_assoc_dev read
+    DevBuf det_buf;   // zx[SLAM_MAX_DETECTIONS] zy[SLAM_MAX_DETECTIONS] when uploaded from the host
+    int ndet = -1;
+    const float *d_det_zx = nullptr, *d_det_zy = nullptr;
+    int64_t assoc_launches[2] = { 0, 0 };   // slam_assoc_counts: associate launches, assoc-update launches (in no form counter)
+
     DevBuf fm_buf;             // kFmIn + kFmOut floats
     DevBuf fm_work;            // 2 x 27 x SLAM_MAX_BEAMS floats: per-candidate hit rows of the lattice kernel, two sweeps (the chained pair)
     float* h_fm = nullptr;     // pinned + mapped: lattice candidates in, results out, then one uint32 arrival flag

@@ -202,6 +202,37 @@ inline bool ekf_aniso_cov_ok(const EkfAnisoCov& q)
 // one wavefront per particle, out of place (through a.anc, unobserved landmarks copied) or in place (a.map_in == a.map_out:
 // only observed landmarks touched); a.meas_var is not read, a.cov must be null
 hipError_t launch_ekf_aniso(hipStream_t stream, const EkfArgs& a, const EkfAnisoCov& q, const EventPair* ev = nullptr);
+// ---- assoc_kernels.hip: data association (specification: tests/_assoc_spec.py).  The detections of a frame
+// are sensor-frame points WITHOUT identity; every particle decides for itself which of its landmarks each one belongs to and
+// which ones start a new landmark.  Rows only: the table is per particle, so "which landmarks a frame observes" is too.
+struct AssocArgs {
+    const float* map;      // rows as in EkfArgs (read only)
+    int64_t row_stride;
+    int plane_stride;
+    int nlandmarks;        // <= SLAM_MAX_OBS
+    const float *x, *y, *th;
+    const int32_t* anc;    // particle i reads row anc[i] (nullptr: i)
+    int n;
+    const float *det_zx, *det_zy;   // [ndet] finite sensor-frame points
+    int ndet;                       // <= SLAM_MAX_DETECTIONS
+    float meas_var, gate, new_gate;
+    uint8_t* assoc;        // [n][assoc_stride]: entry l = the detection landmark l takes, SLAM_ASSOC_NONE = none
+    int assoc_stride;      // >= nlandmarks; the columns from nlandmarks on are written SLAM_ASSOC_NONE
+    int32_t* stats;        // [n][3] matched, created, dropped; may be nullptr
+    int xcd_chunk;         // set by the launcher
+};
+// one wavefront per particle; create: unmatched detections far from every seen landmark take the unseen slots
+hipError_t launch_associate(hipStream_t stream, const AssocArgs& a, bool create, const EventPair* ev = nullptr);
+// the table a landmark update reads its observations through: z of landmark l of particle i = det[assoc[i][l]]
+struct EkfAssocTable {
+    const uint8_t* assoc;
+    int assoc_stride;
+    const float *det_zx, *det_zy;
+    int ndet;
+};
+// the row update of launch_ekf_update's one-wavefront-per-particle form under such a table (a.obs_zx / a.obs_zy are not read;
+// a.cov must be null): out of place through a.anc, or in place (only landmarks with an association touched)
+hipError_t launch_ekf_assoc(hipStream_t stream, const EkfArgs& a, const EkfAssocTable& t, const EventPair* ev = nullptr);
 bool frame_front_fits(int n, int nlandmarks, int group_size);   // the shapes launch_frame_front takes
 // motion sample + scan-match score AND the grouped out-of-place landmark update in ONE launch (single-GPU frames on rows): the
 // gathers of the scorer run in the shadow of the update's row stores.  `a.x / a.y / a.th` are not read (the update works out

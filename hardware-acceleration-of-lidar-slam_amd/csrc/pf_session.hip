@@ -140,6 +140,13 @@ struct slam_pf {
     // slam_ekf_update_aniso_dev, a launch of its own (never the fused front)
     bool aniso = false;
     float meas_cov[3] = { 0.0f, 0.0f, 0.0f };
+    // slam_pf_assoc_set (rows only, one GPU): the frame's observations are detections without identity — every frame that uses
+    // observations runs slam_associate_dev and then slam_ekf_update_assoc_dev, two launches of their own (never the fused front)
+    bool assoc_on = false;
+    float assoc_gate = 0.0f, assoc_new_gate = 0.0f;
+    int assoc_create = 0;
+    uint8_t* assoc_tab = nullptr;     // [n][Lp] the last frame's table, indexed like `score`; made by the first slam_pf_assoc_set
+    int32_t* assoc_stats = nullptr;   // [n][3], behind the table in the same allocation
     // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe (RES_OBS) and moves between split and
     // split pages while it runs (between rows and pages when it could not have the split layout's tables)
     int layout_cfg = SLAM_MAP_AUTO;
@@ -989,7 +996,8 @@ int front_stage(slam_pf* pf, FrameFacts& f, int slot, const float dp[3])
         return SLAM_OK;
     }
     // General measurement covariance (rows only): its update exists as a launch of its own alone.
-    const bool front = !pf->aniso && (comm ? pf->split && !pf->paged && pf->has_anc && !pf->gated : !pf->paged && (!pf->gated || pf->split));
+    // Data association likewise: associate + update, two launches that read the poses this one writes.
+    const bool front = !pf->aniso && !pf->assoc_on && (comm ? pf->split && !pf->paged && pf->has_anc && !pf->gated : !pf->paged && (!pf->gated || pf->split));
     if (front && f.anc && f.observing) {
         const float* ps = f.src;
         const int32_t* pose_anc = f.anc;
@@ -1069,7 +1077,16 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
     float* dst = f.dst;
     if (f.ekf) {
         if (f.sample_obs) SLAM_HIP_TRY(e, launch_obs_count(e->stream, e->d_obs_zx, e->d_obs_zy, L, dev_word(pf, RES_OBS), ++pf->obs_seq_issued, pf->votes));
-        if (!f.fused) {   // (fused: the update went out with the score; in place: no gather, the buffers do not flip)
+        if (pf->assoc_on) {   // detections without identity: the observation table is not read
+            float* out = pf->map[f.in_place ? mc : mn];
+            const int32_t* anc = f.in_place ? nullptr : f.anc;
+            if (int rc = slam_associate_dev(e, pf->map[mc], stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->cfg.meas_var,
+                                            pf->assoc_gate, pf->assoc_new_gate, pf->assoc_create, pf->assoc_tab, pf->Lp, pf->assoc_stats))
+                return rc;
+            if (int rc = slam_ekf_update_assoc_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n,
+                                                   pf->cfg.meas_var, pf->assoc_tab, pf->Lp, nullptr))
+                return rc;
+        } else if (!f.fused) {   // (fused: the update went out with the score; in place: no gather, the buffers do not flip)
             float* out = pf->map[f.in_place ? mc : mn];
             const int32_t* anc = f.in_place ? nullptr : f.anc;
             if (int rc = pf->aniso ? slam_ekf_update_aniso_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n,
@@ -1460,6 +1477,7 @@ int slam_pf_destroy(slam_pf* pf)
     }
     if (pf->store) (void)hipFree(pf->store);
     if (pf->surv_store) (void)hipFree(pf->surv_store);
+    if (pf->assoc_tab) (void)hipFree(pf->assoc_tab);   // (the stats live behind the table)
     free_page_tables(pf);
     free_split_tables(pf);
     for (void* p : { (void*)pf->score, (void*)pf->logw, (void*)pf->count, (void*)pf->first, (void*)pf->pose_all, (void*)pf->pose_stage, (void*)pf->first_all,
@@ -1607,9 +1625,63 @@ int slam_pf_meas_cov_set(slam_pf* pf, const float meas_cov[3])
         snprintf(pf->e->err, sizeof pf->e->err, "meas_cov must be finite with qxx > 0, qyy > 0 and qxx * qyy - qxy * qxy > 0 in float32");
         return SLAM_ERR_INVALID_ARG;
     }
+    const bool iso = meas_cov[0] == pf->cfg.meas_var && meas_cov[1] == 0.0f && meas_cov[2] == pf->cfg.meas_var;
+    if (pf->assoc_on && !iso) {
+        snprintf(pf->e->err, sizeof pf->e->err, "data association is on (slam_pf_assoc_set): it gates with meas_var * I, a 2x2 "
+                                                "measurement covariance cannot be set");
+        return SLAM_ERR_INVALID_ARG;
+    }
     for (int k = 0; k < 3; ++k) pf->meas_cov[k] = meas_cov[k];
     // {meas_var, 0, meas_var}: the session's own isotropic update again, exactly as without this call
-    pf->aniso = !(meas_cov[0] == pf->cfg.meas_var && meas_cov[1] == 0.0f && meas_cov[2] == pf->cfg.meas_var);
+    pf->aniso = !iso;
+    return SLAM_OK;
+}
+
+int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (gate == 0.0f) {   // off: the session runs exactly what it ran before the first call
+        pf->assoc_on = false;
+        return SLAM_OK;
+    }
+    if (pf->layout_cfg != SLAM_MAP_ROWS || pf->L == 0 || pf->comm) {
+        snprintf(e->err, sizeof e->err, "data association gives every particle its own observed landmarks: that needs the row "
+                                        "layout on one GPU (map_layout = SLAM_MAP_ROWS, n_landmarks > 0, not sharded)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (pf->aniso) {
+        snprintf(e->err, sizeof e->err, "data association gates with meas_var * I: not while a 2x2 measurement covariance is in "
+                                        "force (slam_pf_meas_cov_set)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (!(gate > 0.0f && gate <= FLT_MAX) || !(new_gate >= gate) || (create != 0 && create != 1) || pf->L > SLAM_MAX_OBS) {
+        snprintf(e->err, sizeof e->err, "association needs a finite gate > 0, new_gate >= gate, create in {0, 1} and at most %d landmarks",
+                 (int)SLAM_MAX_OBS);
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (!pf->assoc_tab) {
+        SLAM_HIP_TRY(e, hipSetDevice(e->device));
+        const size_t tab = ((size_t)pf->n * (size_t)pf->Lp + 15) & ~(size_t)15, st = (size_t)pf->n * 3 * sizeof(int32_t);
+        SLAM_HIP_TRY(e, dev_alloc((void**)&pf->assoc_tab, tab + st));   // one allocation: the table, then the stats
+        pf->assoc_stats = reinterpret_cast<int32_t*>(pf->assoc_tab + tab);
+        SLAM_HIP_TRY(e, hipMemsetAsync(pf->assoc_tab, SLAM_ASSOC_NONE, tab, e->stream));
+        SLAM_HIP_TRY(e, hipMemsetAsync(pf->assoc_stats, 0, st, e->stream));
+    }
+    pf->assoc_on = true;
+    pf->assoc_gate = gate;
+    pf->assoc_new_gate = new_gate;
+    pf->assoc_create = create;
+    return SLAM_OK;
+}
+
+int slam_pf_assoc_device_view(slam_pf* pf, const uint8_t** assoc, int32_t* assoc_stride, const int32_t** stats)
+{
+    if (!pf || !assoc || !assoc_stride || !stats) return SLAM_ERR_INVALID_ARG;
+    if (!pf->assoc_tab) return SLAM_ERR_NOT_READY;   // slam_pf_assoc_set never switched association on
+    *assoc = pf->assoc_tab;
+    *assoc_stride = pf->Lp;
+    *stats = pf->assoc_stats;
     return SLAM_OK;
 }
 

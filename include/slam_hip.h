@@ -103,7 +103,7 @@ typedef enum {
     SLAM_PROF_PACK = 7,         /* several GPUs: migrating rows into the send buffer */
     SLAM_PROF_UNPACK = 8,       /* several GPUs: received rows into the staging tail */
     SLAM_PROF_COLLECTIVES = 9,  /* every exchange between ranks (all-reduce, all-gathers, send/recv), as the stream sees them */
-    SLAM_PROF_PAGES = 10,       /* map bookkeeping: paged maps' touched-page list, table gathers, the free list where it is a launch of
+    SLAM_PROF_PAGES = 10,       /* map bookkeeping: data association (slam_associate_dev), paged maps' touched-page list, table gathers, the free list where it is a launch of
                                    its own (one GPU: it travels in the scorer's launch); split maps' gathers on frames without observations */
     SLAM_PROF_EKF_TAIL = 11,    /* several GPUs, split maps: the part of the landmark update that waits for the exchange (the
                                    groups with an ancestor in the staging tail); the rest went out with the score (SLAM_PROF_EKF) */
@@ -300,6 +300,45 @@ int slam_ekf_update_aniso_dev(slam_engine *e, const float *d_map_in, float *d_ma
                               int nlandmarks, const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc,
                               int n, const float meas_cov[3] /* qxx, qxy, qyy */, float *d_loglik);
 int slam_ekf_aniso_count(slam_engine *e, int64_t *launches);
+/* DATA ASSOCIATION.  slam_ekf_update_dev needs to be told which landmark every observation belongs to; a feature detector
+ * delivers points in the sensor frame with no identity attached.  These stages let every particle decide for itself (rows
+ * only: a table per particle means that the landmarks a frame observes differ between particles).  The DETECTIONS of a frame
+ * are handed over once, like the observation table: from the host (finite values; copied) or as two device arrays (adopted,
+ * read afresh by every launch), 0 <= ndet <= SLAM_MAX_DETECTIONS.
+ * slam_associate_dev, for particle i with row src = d_anc[i] (NULL: i) of d_map, pose (x, y, th)_i, q = meas_var:
+ *   a. w_k = the observed point of detection k in the world frame (the update's own: t + H^T z);
+ *   b. a landmark l < nlandmarks is SEEN unless P_xx < 0 (the update's first-sighting test); for a seen one and every k,
+ *      m(l, k) = d^T (P + q I)^-1 d with d = w_k - mu: the very Mahalanobis term of the update's likelihood, same operations;
+ *   c. the landmark chooses k*(l) = argmin_k m(l, k) (lowest k on ties) and is a candidate iff 0 <= m(l, k*) <= gate (float
+ *      comparisons: NaN never passes);
+ *   d. the detection chooses: of the candidates with k*(l) = k the one with the smallest m (lowest l on ties) gets
+ *      assoc[l] = k, the others get nothing this frame — no landmark holds two detections, no detection serves two landmarks;
+ *   e. create != 0: a detection that is unmatched and has no seen landmark with m(l, k) <= new_gate is NEW; the new
+ *      detections in ascending k take the unseen landmarks (P_xx < 0) in ascending l, and once those run out the rest is
+ *      dropped.  The update's first-sighting path then initialises such a landmark (mean = w_k, P = q I, no likelihood term).
+ * d_assoc is uint8 [n][assoc_stride]: entry l = k or SLAM_ASSOC_NONE, the columns [nlandmarks, assoc_stride) are
+ * SLAM_ASSOC_NONE.  d_stats (may be NULL) is int32 [n][3] = matched, created, dropped (every detection that is neither).
+ * The rows are not written.  Operation order: tests/_assoc_spec.py.
+ * slam_ekf_update_assoc_dev is slam_ekf_update_dev with particle i's own observation list {(l, z[d_assoc[i][l]]) :
+ * d_assoc[i][l] != SLAM_ASSOC_NONE} (an entry that names no detection counts as SLAM_ASSOC_NONE): forms (out of place through
+ * d_anc, unassociated landmarks copied; in place with d_anc == NULL, only associated landmarks touched), first sightings,
+ * padding columns, the log-likelihood's summation order and where it stays (slam_logweight_ekf_dev) are unchanged.
+ * SLAM_ERR_INVALID_ARG, nothing launched: gate not finite or <= 0, new_gate < gate or NaN, meas_var <= 0, nlandmarks >
+ * SLAM_MAX_OBS, assoc_stride < nlandmarks, create not 0 or 1, a gather index with d_map_in == d_map_out.  SLAM_ERR_NOT_READY:
+ * no detections were handed over.  ndet == 0 is legal: the table is all SLAM_ASSOC_NONE and the update copies.
+ * Timing: the update is bracketed as SLAM_PROF_EKF, the association as SLAM_PROF_PAGES (map bookkeeping).  The launches are
+ * counted by slam_assoc_counts (counts[0] associate, counts[1] update) and in none of the form counters. */
+enum { SLAM_MAX_DETECTIONS = 64, SLAM_ASSOC_NONE = 255 };
+int slam_detections_upload_host(slam_engine *e, const float *zx, const float *zy, int ndet);
+int slam_detections_set_dev(slam_engine *e, const float *d_zx, const float *d_zy, int ndet);
+int slam_associate_dev(slam_engine *e, const float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                       const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc, int n,
+                       float meas_var, float gate, float new_gate, int create,
+                       uint8_t *d_assoc, int assoc_stride, int32_t *d_stats /* may be NULL */);
+int slam_ekf_update_assoc_dev(slam_engine *e, const float *d_map_in, float *d_map_out, int64_t row_stride, int plane_stride,
+                              int nlandmarks, const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc,
+                              int n, float meas_var, const uint8_t *d_assoc, int assoc_stride, float *d_loglik);
+int slam_assoc_counts(slam_engine *e, int64_t counts[2]);
 /* The FRONT of a frame of a single-GPU slam_pf session on rows — motion sample + scan-match score (FastMatch's inner loop,
  * main.c:459-518, for every particle) and the out-of-place landmark update — goes out as ONE launch whose scoring and
  * updating workgroups are dealt out interleaved: the scorer's gathers (texture addresser, L2) run in the shadow of the
@@ -593,6 +632,18 @@ int slam_pf_refine_set(slam_pf *pf, float step_xy, float step_theta, int sweeps)
  * when sharded — and no frame goes out as a fused front launch.  meas_cov = {cfg.meas_var, 0, cfg.meas_var} switches back:
  * the session then runs exactly what it ran before the first call. */
 int slam_pf_meas_cov_set(slam_pf *pf, const float meas_cov[3]);
+/* Data association inside the session (slam_associate_dev + slam_ekf_update_assoc_dev with cfg.meas_var).  After a call with
+ * gate > 0 a frame with use_observations ignores the observation table and reads the engine's DETECTIONS
+ * (slam_detections_upload_host / _set_dev; none handed over: SLAM_ERR_NOT_READY): it runs associate and then update, two
+ * launches that read the refined poses when refinement is on and work in place on the frames a gated session kept; no frame
+ * goes out as a fused front launch.  Only a single-GPU session created with map_layout = SLAM_MAP_ROWS and n_landmarks > 0
+ * accepts the switch: any other layout, a sharded session, and a session with a non-isotropic slam_pf_meas_cov_set in force
+ * return SLAM_ERR_INVALID_ARG (slam_last_error says why) and go on as before; setting a 2x2 covariance while association is
+ * on is refused likewise.  gate == 0 (new_gate and create are then ignored) returns the session to exactly what it ran before.
+ * slam_pf_assoc_device_view: the table ([n_particles][*assoc_stride] bytes) and stats ([n_particles][3]) of the last such
+ * frame, indexed like slam_pf_view.score (BEFORE the pending gather); SLAM_ERR_NOT_READY until association was switched on. */
+int slam_pf_assoc_set(slam_pf *pf, float gate, float new_gate, int create);
+int slam_pf_assoc_device_view(slam_pf *pf, const uint8_t **assoc, int32_t *assoc_stride, const int32_t **stats);
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
  * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
