@@ -119,6 +119,9 @@ SIGNATURES = {
     "slam_associate_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _vp, _i, _vp]),
     "slam_ekf_update_assoc_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _i, _vp]),
     "slam_assoc_counts": (_i, [_vp, _vp]),
+    "slam_landmark_evidence_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "slam_evidence_init_dev": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _i]),
+    "slam_evidence_counts": (_i, [_vp, _vp]),
     "slam_selftest_reciprocal": (_i, [_vp, _vp, _vp]),
     "slam_frame_fusion_set": (_i, [_vp, _i]),
     "slam_frame_fusion_count": (_i, [_vp, _vp]),
@@ -156,6 +159,9 @@ SIGNATURES = {
     "slam_pf_meas_cov_set": (_i, [_vp, _vp]),
     "slam_pf_assoc_set": (_i, [_vp, _f, _f, _i]),
     "slam_pf_assoc_device_view": (_i, [_vp, _vp, _vp, _vp]),
+    "slam_pf_prune_set": (_i, [_vp, _i, _i, _i, _f]),
+    "slam_pf_evidence_device_view": (_i, [_vp, _vp, _vp, _vp]),
+    "slam_pf_get_evidence_host": (_i, [_vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
     "slam_pf_get_poses_host": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_map_host": (_i, [_vp, _vp]),
@@ -441,6 +447,26 @@ class Engine:
         """-> (associate launches, assoc-update launches) of this engine so far."""
         c = (C.c_int64 * 2)()
         self._ck(self.lib.slam_assoc_counts(self.h, c), "assoc_counts")
+        return int(c[0]), int(c[1])
+
+    def landmark_evidence_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_anc, n, d_assoc, assoc_stride, d_ev_in,
+                              d_ev_out, ev_stride, hit, miss, cmax, view_range, d_stats):
+        """``slam_landmark_evidence_dev``: the evidence bytes uint8 [n][ev_stride] behind a frame's associating update; pruned
+        landmarks' slots in d_map become unused ones; stats int32 [n][2] = pruned, seen after pruning."""
+        self._ck(self.lib.slam_landmark_evidence_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x), _ptr(d_y),
+                                                     _ptr(d_anc), n, _ptr(d_assoc), assoc_stride, _ptr(d_ev_in), _ptr(d_ev_out),
+                                                     ev_stride, int(hit), int(miss), int(cmax), view_range, _ptr(d_stats)),
+                 "landmark_evidence_dev")
+
+    def evidence_init_dev(self, d_map, row_stride, plane_stride, nlandmarks, nrows, d_ev, ev_stride, value):
+        """``slam_evidence_init_dev``: evidence = seen ? value : 0 for the nrows rows of d_map."""
+        self._ck(self.lib.slam_evidence_init_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, nrows, _ptr(d_ev), ev_stride,
+                                                 int(value)), "evidence_init_dev")
+
+    def evidence_counts(self):
+        """-> (evidence launches, evidence-init launches) of this engine so far."""
+        c = (C.c_int64 * 2)()
+        self._ck(self.lib.slam_evidence_counts(self.h, c), "evidence_counts")
         return int(c[0]), int(c[1])
 
     def logweight_dev(self, d_score, d_loglik, gain, n, d_logw, d_max):
@@ -908,6 +934,25 @@ class PfSession:
         self.e._ck(self.e.lib.slam_pf_assoc_device_view(self.h, C.byref(a), C.byref(stride), C.byref(st)), "pf_assoc_device_view")
         return {"assoc": DeviceArray(a.value, (self.n, stride.value), "|u1", self), "stats": DeviceArray(st.value, (self.n, 3), "<i4", self),
                 "assoc_stride": stride.value}
+
+    def prune_set(self, hit: int, miss: int = 1, cmax: int = 1, view_range: float = 1.0):
+        """``slam_pf_prune_set``: existence evidence and pruning of clutter landmarks behind every associating update (only while
+        association is on); hit = 0 switches it off."""
+        self.e._ck(self.e.lib.slam_pf_prune_set(self.h, int(hit), int(miss), int(cmax), view_range), "pf_prune_set")
+
+    def evidence_view(self):
+        """``slam_pf_evidence_device_view``: the current evidence uint8 [n][stride] (indexed like the maps: before the pending
+        gather) and the last stage's stats int32 [n][2]."""
+        a, st, stride = C.c_void_p(), C.c_void_p(), C.c_int32(0)
+        self.e._ck(self.e.lib.slam_pf_evidence_device_view(self.h, C.byref(a), C.byref(stride), C.byref(st)), "pf_evidence_device_view")
+        return {"ev": DeviceArray(a.value, (self.n, stride.value), "|u1", self), "stats": DeviceArray(st.value, (self.n, 2), "<i4", self),
+                "ev_stride": stride.value}
+
+    def evidence(self):
+        """``slam_pf_get_evidence_host``: uint8 [n][n_landmarks], the pending gather applied."""
+        ev = np.empty((self.n, self.L), np.uint8)
+        self.e._ck(self.e.lib.slam_pf_get_evidence_host(self.h, _ptr(ev)), "pf_get_evidence")
+        return ev
 
     def best(self):
         pose = (C.c_float * 3)()

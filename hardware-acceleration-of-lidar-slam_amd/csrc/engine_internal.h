@@ -88,6 +88,7 @@ struct slam_engine {
     int ndet = -1;
     const float *d_det_zx = nullptr, *d_det_zy = nullptr;
     int64_t assoc_launches[2] = { 0, 0 };   // slam_assoc_counts: associate launches, assoc-update launches (in no form counter)
+    int64_t evidence_launches[2] = { 0, 0 };   // slam_evidence_counts: evidence launches, init launches (in no other counter)
 
     DevBuf fm_buf;             // kFmIn + kFmOut floats
     DevBuf fm_work;            // 2 x 27 x SLAM_MAX_BEAMS floats: per-candidate hit rows of the lattice kernel, two sweeps (the chained pair)
@@ -299,6 +300,9 @@ extern "C" int slam_ekf_materialise_dev(slam_engine* e, const float* d_mean_in, 
                              int nlandmarks, const float* d_obs_save, const float* d_x, const float* d_y, const float* d_th,
                              const int32_t* d_anc, int n, float meas_var, const slam::SplitIO* split, const uint32_t* d_survivor,
                              uint32_t stamp, int group);
+// a frame of a pruning session without a landmark update: the evidence follows its particles, d_out[i] = d_in[d_anc[i]] (rows of
+// ev_stride bytes; bracketed as SLAM_PROF_PAGES like slam_gather_map_dev's table gathers; counted nowhere)
+extern "C" int slam_evidence_gather_dev(slam_engine* e, const uint8_t* d_in, uint8_t* d_out, int ev_stride, const int32_t* d_anc, int n);
 // engine_resample.hip: slam_ancestors_from_scan_dev that also marks the particles it kept (kernels.h: SurvivorOut); needs
 // ancestors_from_scan_fits(n)
 extern "C" int slam_ancestors_survivors_dev(slam_engine* e, int n, uint64_t seed, uint32_t frame, int32_t* d_anc,

@@ -233,6 +233,44 @@ struct EkfAssocTable {
 // the row update of launch_ekf_update's one-wavefront-per-particle form under such a table (a.obs_zx / a.obs_zy are not read;
 // a.cov must be null): out of place through a.anc, or in place (only landmarks with an association touched)
 hipError_t launch_ekf_assoc(hipStream_t stream, const EkfArgs& a, const EkfAssocTable& t, const EventPair* ev = nullptr);
+// ---- evidence_kernels.hip: landmark existence evidence (specification: tests/_evidence_spec.py).  One byte
+// c in [0, cmax] per (particle, landmark slot) beside the rows; behind the update of a frame a matched landmark gains `hit`, a
+// visible unmatched one loses `miss`, and one that cannot pay is pruned: its slot gets the bits of a slot that was never used.
+struct EvidenceArgs {
+    float* map;            // rows as in EkfArgs, AFTER the frame's update: read, and written where a landmark is pruned
+    int64_t row_stride;
+    int plane_stride;
+    int nlandmarks;        // <= SLAM_MAX_OBS
+    const float *x, *y;    // the poses the update used
+    const int32_t* anc;    // particle i reads evidence row anc[i] (nullptr: i; the MAP row is always i)
+    int n;
+    const uint8_t* assoc;  // [n][assoc_stride] the frame's table
+    int assoc_stride;      // >= nlandmarks
+    int ndet;              // K: a table byte < K is a hit
+    const uint8_t* ev_in;  // [rows][ev_stride]
+    uint8_t* ev_out;       // [n][ev_stride]; == ev_in: in place (anc must be nullptr), the padding columns are left alone — else written 0
+    int ev_stride;         // >= nlandmarks
+    int hit, miss, cmax;   // 1 .. 255
+    float range2;          // view_range * view_range, one float32 product made on the host
+    int32_t* stats;        // [n][2] pruned, seen after pruning; may be nullptr
+    int xcd_chunk;         // set by the launcher
+};
+// one wavefront per particle; byte traffic as dwords when every row of the three byte arrays starts on a dword, else as bytes
+hipError_t launch_landmark_evidence(hipStream_t stream, const EvidenceArgs& a, const EventPair* ev = nullptr);
+struct EvidenceInitArgs {
+    const float* map;      // [nrows] rows as above (read only)
+    int64_t row_stride;
+    int plane_stride;
+    int nlandmarks;
+    int nrows;
+    uint8_t* ev;           // [nrows][ev_stride] <- seen ? value : 0, the padding columns 0
+    int ev_stride;
+    int value;             // 0 .. 255
+    int xcd_chunk;         // set by the launcher
+};
+hipError_t launch_evidence_init(hipStream_t stream, const EvidenceInitArgs& a, const EventPair* ev = nullptr);
+// a frame without a landmark update: the evidence follows its particles, out[i] = in[anc[i]] (whole rows of `stride` bytes)
+hipError_t launch_evidence_gather(hipStream_t stream, const uint8_t* in, uint8_t* out, int stride, const int32_t* anc, int n);
 bool frame_front_fits(int n, int nlandmarks, int group_size);   // the shapes launch_frame_front takes
 // motion sample + scan-match score AND the grouped out-of-place landmark update in ONE launch (single-GPU frames on rows): the
 // gathers of the scorer run in the shadow of the update's row stores.  `a.x / a.y / a.th` are not read (the update works out

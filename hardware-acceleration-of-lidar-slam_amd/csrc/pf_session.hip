@@ -147,6 +147,13 @@ struct slam_pf {
     int assoc_create = 0;
     uint8_t* assoc_tab = nullptr;     // [n][Lp] the last frame's table, indexed like `score`; made by the first slam_pf_assoc_set
     int32_t* assoc_stats = nullptr;   // [n][3], behind the table in the same allocation
+    // slam_pf_prune_set (only while association is on): one evidence byte per (particle, landmark slot) beside the rows, brought up
+    // to date behind every associating update (slam_landmark_evidence_dev); ev[map_cur] belongs to map[map_cur] — the two flip together
+    bool prune_on = false;
+    int prune_hit = 0, prune_miss = 0, prune_cmax = 0;
+    float prune_range = 0.0f;
+    uint8_t* ev[2] = { nullptr, nullptr };   // [n][Lp] each, one allocation made by the first slam_pf_prune_set that switches on
+    int32_t* ev_stats = nullptr;             // [n][2] pruned, seen after pruning (the last frame that ran the stage), behind them
     // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe (RES_OBS) and moves between split and
     // split pages while it runs (between rows and pages when it could not have the split layout's tables)
     int layout_cfg = SLAM_MAP_AUTO;
@@ -270,6 +277,15 @@ int settle_means(slam_pf* pf)
     if (!pf->surv.pending) return SLAM_OK;
     pf->surv.pending = false;
     return materialise(pf, false);
+}
+
+// Pruning: the evidence of the current maps, from scratch — a map that is there is trusted (seen: cmax, else 0).  At the switch,
+// and whenever the session's maps are replaced wholesale while pruning is on.
+int evidence_from_maps(slam_pf* pf)
+{
+    if (!pf->prune_on) return SLAM_OK;
+    return slam_evidence_init_dev(pf->e, pf->map[pf->map_cur], 5 * (int64_t)pf->Lp, pf->Lp, pf->L, pf->n, pf->ev[pf->map_cur], pf->Lp,
+                                  pf->prune_cmax);
 }
 
 // Map rows (and poses) of ancestors that live on another rank -> the staging tail of the current buffers, where
@@ -1086,6 +1102,12 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
             if (int rc = slam_ekf_update_assoc_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n,
                                                    pf->cfg.meas_var, pf->assoc_tab, pf->Lp, nullptr))
                 return rc;
+            // existence evidence, on the row the update wrote: through the frame's gather into the other buffer, or in place
+            if (pf->prune_on)
+                if (int rc = slam_landmark_evidence_dev(e, out, stride, pf->Lp, L, dst, dst + sn, anc, n, pf->assoc_tab, pf->Lp, pf->ev[mc],
+                                                        pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit, pf->prune_miss,
+                                                        pf->prune_cmax, pf->prune_range, pf->ev_stats))
+                    return rc;
         } else if (!f.fused) {   // (fused: the update went out with the score; in place: no gather, the buffers do not flip)
             float* out = pf->map[f.in_place ? mc : mn];
             const int32_t* anc = f.in_place ? nullptr : f.anc;
@@ -1100,6 +1122,8 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
     }
     if (L > 0 && f.anc && !f.in_place) {   // the maps follow their particles even without an observation
         if (int rc = slam_gather_map_dev(e, pf->map[mc], pf->map[mn], stride, stride, pf->Lp, pf->Lp, L, f.anc, n)) return rc;
+        if (pf->prune_on)   // ... and so does their evidence
+            if (int rc = slam_evidence_gather_dev(e, pf->ev[mc], pf->ev[mn], pf->Lp, f.anc, n)) return rc;
         pf->map_cur = mn;
     }
     return slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
@@ -1478,6 +1502,7 @@ int slam_pf_destroy(slam_pf* pf)
     if (pf->store) (void)hipFree(pf->store);
     if (pf->surv_store) (void)hipFree(pf->surv_store);
     if (pf->assoc_tab) (void)hipFree(pf->assoc_tab);   // (the stats live behind the table)
+    if (pf->ev[0]) (void)hipFree(pf->ev[0]);           // (the second buffer and the stats live behind the first)
     free_page_tables(pf);
     free_split_tables(pf);
     for (void* p : { (void*)pf->score, (void*)pf->logw, (void*)pf->count, (void*)pf->first, (void*)pf->pose_all, (void*)pf->pose_stage, (void*)pf->first_all,
@@ -1525,7 +1550,7 @@ int slam_pf_reset(slam_pf* pf, const float pose[3])
         }
     }
     pf->frame = 0;
-    return SLAM_OK;
+    return evidence_from_maps(pf);   // (pruning: every slot unseen, every evidence byte 0)
 }
 
 int slam_pf_set_poses_host(slam_pf* pf, const float* x, const float* y, const float* theta)
@@ -1560,6 +1585,8 @@ int slam_pf_set_map_host(slam_pf* pf, const float* rows)
         if (rc == SLAM_OK) rc = slam_pf_set_map_dev(pf, dense, 5 * (int64_t)pf->Lp, pf->Lp);
         if (rc == SLAM_OK) rc = slam_engine_sync(pf->e);
         (void)hipFree(dense);
+    } else if (rc == SLAM_OK) {
+        rc = evidence_from_maps(pf);   // (pruning: the loaded maps are trusted)
     }
     return rc;
 }
@@ -1586,7 +1613,7 @@ int slam_pf_set_map_dev(slam_pf* pf, const float* d_rows, int64_t row_stride, in
         SLAM_HIP_TRY(e, hipMemcpy2DAsync(pf->map[pf->map_cur] + (size_t)pl * pf->Lp, 5 * (size_t)pf->Lp * 4,
                                          d_rows + (size_t)pl * plane_stride, (size_t)row_stride * 4, (size_t)pf->L * 4,
                                          (size_t)pf->n, hipMemcpyDeviceToDevice, e->stream));
-    return SLAM_OK;
+    return evidence_from_maps(pf);   // (pruning: the loaded maps are trusted)
 }
 
 int slam_pf_is_paged(const slam_pf* pf) { return pf && pf->paged ? 1 : 0; }
@@ -1641,8 +1668,9 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
 {
     if (!pf) return SLAM_ERR_INVALID_ARG;
     slam_engine* e = pf->e;
-    if (gate == 0.0f) {   // off: the session runs exactly what it ran before the first call
+    if (gate == 0.0f) {   // off: the session runs exactly what it ran before the first call (pruning goes off with it)
         pf->assoc_on = false;
+        pf->prune_on = false;
         return SLAM_OK;
     }
     if (pf->layout_cfg != SLAM_MAP_ROWS || pf->L == 0 || pf->comm) {
@@ -1682,6 +1710,65 @@ int slam_pf_assoc_device_view(slam_pf* pf, const uint8_t** assoc, int32_t* assoc
     *assoc = pf->assoc_tab;
     *assoc_stride = pf->Lp;
     *stats = pf->assoc_stats;
+    return SLAM_OK;
+}
+
+int slam_pf_prune_set(slam_pf* pf, int hit, int miss, int cmax, float view_range)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (hit == 0) {   // off: the session runs exactly what it ran before the first call
+        pf->prune_on = false;
+        return SLAM_OK;
+    }
+    if (!pf->assoc_on) {   // (which is what every layout but rows, a sharded session and a 2x2 covariance come down to)
+        snprintf(e->err, sizeof e->err, "pruning reads the frame's association table: it needs data association switched on "
+                                        "(slam_pf_assoc_set: the row layout on one GPU, not sharded, meas_var * I)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (hit < 1 || hit > 255 || miss < 1 || miss > 255 || cmax < 1 || cmax > 255 || !(view_range > 0.0f && view_range <= FLT_MAX)) {
+        snprintf(e->err, sizeof e->err, "pruning needs hit, miss and cmax in 1 .. 255 and a finite view_range > 0");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    if (!pf->ev[0]) {   // once, at the switch: two evidence buffers, then the stats — device memory only
+        const size_t buf = ((size_t)pf->n * (size_t)pf->Lp + 15) & ~(size_t)15, st = (size_t)pf->n * 2 * sizeof(int32_t);
+        SLAM_HIP_TRY(e, dev_alloc((void**)&pf->ev[0], 2 * buf + st));
+        pf->ev[1] = pf->ev[0] + buf;
+        pf->ev_stats = reinterpret_cast<int32_t*>(pf->ev[1] + buf);
+        SLAM_HIP_TRY(e, hipMemsetAsync(pf->ev[0], 0, 2 * buf + st, e->stream));
+    }
+    pf->prune_on = true;
+    pf->prune_hit = hit;
+    pf->prune_miss = miss;
+    pf->prune_cmax = cmax;
+    pf->prune_range = view_range;
+    return evidence_from_maps(pf);   // the current maps are trusted (indexed like them: before the pending gather)
+}
+
+int slam_pf_evidence_device_view(slam_pf* pf, const uint8_t** ev, int32_t* ev_stride, const int32_t** stats)
+{
+    if (!pf || !ev || !ev_stride || !stats) return SLAM_ERR_INVALID_ARG;
+    if (!pf->ev[0]) return SLAM_ERR_NOT_READY;   // slam_pf_prune_set never switched pruning on
+    *ev = pf->ev[pf->map_cur];
+    *ev_stride = pf->Lp;
+    *stats = pf->ev_stats;
+    return SLAM_OK;
+}
+
+int slam_pf_get_evidence_host(slam_pf* pf, uint8_t* ev)
+{
+    if (!pf || !ev) return SLAM_ERR_INVALID_ARG;
+    if (!pf->ev[0]) return SLAM_ERR_NOT_READY;
+    slam_engine* e = pf->e;
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    const uint8_t* src = pf->ev[pf->map_cur];
+    if (pf->has_anc) {   // the pending gather is applied on the way, into the spare buffer
+        if (int rc = slam_evidence_gather_dev(e, src, pf->ev[1 - pf->map_cur], pf->Lp, pf->anc[pf->cur], pf->n)) return rc;
+        src = pf->ev[1 - pf->map_cur];
+    }
+    if (int rc = slam_engine_sync(e)) return rc;
+    SLAM_HIP_TRY(e, hipMemcpy2D(ev, (size_t)pf->L, src, (size_t)pf->Lp, (size_t)pf->L, (size_t)pf->n, hipMemcpyDeviceToHost));
     return SLAM_OK;
 }
 

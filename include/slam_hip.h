@@ -103,7 +103,7 @@ typedef enum {
     SLAM_PROF_PACK = 7,         /* several GPUs: migrating rows into the send buffer */
     SLAM_PROF_UNPACK = 8,       /* several GPUs: received rows into the staging tail */
     SLAM_PROF_COLLECTIVES = 9,  /* every exchange between ranks (all-reduce, all-gathers, send/recv), as the stream sees them */
-    SLAM_PROF_PAGES = 10,       /* map bookkeeping: data association (slam_associate_dev), paged maps' touched-page list, table gathers, the free list where it is a launch of
+    SLAM_PROF_PAGES = 10,       /* map bookkeeping: data association (slam_associate_dev), existence evidence (slam_landmark_evidence_dev), paged maps' touched-page list, table gathers, the free list where it is a launch of
                                    its own (one GPU: it travels in the scorer's launch); split maps' gathers on frames without observations */
     SLAM_PROF_EKF_TAIL = 11,    /* several GPUs, split maps: the part of the landmark update that waits for the exchange (the
                                    groups with an ancestor in the staging tail); the rest went out with the score (SLAM_PROF_EKF) */
@@ -339,6 +339,43 @@ int slam_ekf_update_assoc_dev(slam_engine *e, const float *d_map_in, float *d_ma
                               int nlandmarks, const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc,
                               int n, float meas_var, const uint8_t *d_assoc, int assoc_stride, float *d_loglik);
 int slam_assoc_counts(slam_engine *e, int64_t counts[2]);
+/* EXISTENCE EVIDENCE.  A detector produces false detections; with association alone each one that lies far from every landmark
+ * takes an unseen slot and keeps it for good.  Every particle therefore keeps one EVIDENCE byte c in [0, cmax] per landmark slot
+ * beside its row (uint8 [rows][ev_stride]); the counter goes up when the landmark is matched, down when it should have been
+ * seen and was not, and a landmark that runs out is removed.  slam_landmark_evidence_dev runs AFTER the update of the frame
+ * (slam_ekf_update_assoc_dev), for particle i and landmark l < nlandmarks, with
+ *   (mu_x, mu_y, P_xx) of row i of d_map as the update left it, (px, py) = (d_x[i], d_y[i]) the pose the update used,
+ *   c = d_ev_in[src][l] as an integer with src = d_anc[i] (NULL: i), a = d_assoc[i][l], K = the ndet of the engine's current
+ *   detections, hit / miss / cmax integers in 1 .. 255 and range2 = view_range * view_range rounded once to float32:
+ *   seen     = !(P_xx < 0)          (the update's own test: -0.0 counts as seen)
+ *   hit_now  = a < K                (a byte that names no detection of this frame, K <= a <= 255, is no hit — as in the update)
+ *   visible  = r2 <= range2 with dx = mu_x - px, dy = mu_y - py, t = dx * dx, u = dy * dy, r2 = t + u: six separately rounded
+ *              float32 operations, no fused multiply-add; a NaN mean is not visible.  (A 360-degree sensor: no bearing test.)
+ *   not seen:                              c' = 0
+ *   seen, hit_now:                         c' = min(c + hit, cmax), in integers (c = 200, hit = 255 does not wrap)
+ *   seen, no hit, visible, c >= miss:      c' = c - miss
+ *   seen, no hit, visible, c <  miss:      PRUNED — the five planes of slot l of row i become 0, 0, -1.0f, 0, 0, the bits of a slot
+ *                                          that was never used (slam_associate_dev hands it out again), and c' = 0
+ *   seen, no hit, not visible:             c' = c
+ * d_ev_out[i][l] = c'.  Out of place (d_ev_in != d_ev_out) the padding columns [nlandmarks, ev_stride) of d_ev_out are written
+ * 0; in place (d_anc must be NULL) they are left alone.  The padding columns of the map rows, and every plane of a landmark
+ * that is not pruned, are never written.  d_stats (may be NULL) is int32 [n][2] = landmarks pruned this frame, landmarks seen
+ * after pruning.  Operation order: tests/_evidence_spec.py.
+ * slam_evidence_init_dev: d_ev[r][l] = seen ? value : 0 for the nrows rows of d_map (0 <= value <= 255), padding columns 0.
+ * SLAM_ERR_INVALID_ARG, nothing launched: hit, miss or cmax outside 1 .. 255, view_range not finite or <= 0, nlandmarks >
+ * SLAM_MAX_OBS, assoc_stride, ev_stride or plane_stride < nlandmarks, a gather index with d_ev_in == d_ev_out, a null pointer
+ * other than d_anc and d_stats.  SLAM_ERR_NOT_READY: no detections were handed over (ndet == 0 is legal: an observing frame in
+ * which every visible seen landmark takes a miss).
+ * Timing: both launches are bracketed as SLAM_PROF_PAGES (map bookkeeping), as the association is.  They are counted by
+ * slam_evidence_counts (counts[0] evidence launches, counts[1] init launches) and in none of the other counters. */
+int slam_landmark_evidence_dev(slam_engine *e, float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                               const float *d_x, const float *d_y, const int32_t *d_anc, int n,
+                               const uint8_t *d_assoc, int assoc_stride,
+                               const uint8_t *d_ev_in, uint8_t *d_ev_out, int ev_stride,
+                               int hit, int miss, int cmax, float view_range, int32_t *d_stats /* [n][2], may be NULL */);
+int slam_evidence_init_dev(slam_engine *e, const float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                           int nrows, uint8_t *d_ev, int ev_stride, int value);
+int slam_evidence_counts(slam_engine *e, int64_t counts[2]);   /* evidence launches, init launches */
 /* The FRONT of a frame of a single-GPU slam_pf session on rows — motion sample + scan-match score (FastMatch's inner loop,
  * main.c:459-518, for every particle) and the out-of-place landmark update — goes out as ONE launch whose scoring and
  * updating workgroups are dealt out interleaved: the scorer's gathers (texture addresser, L2) run in the shadow of the
@@ -644,6 +681,23 @@ int slam_pf_meas_cov_set(slam_pf *pf, const float meas_cov[3]);
  * frame, indexed like slam_pf_view.score (BEFORE the pending gather); SLAM_ERR_NOT_READY until association was switched on. */
 int slam_pf_assoc_set(slam_pf *pf, float gate, float new_gate, int create);
 int slam_pf_assoc_device_view(slam_pf *pf, const uint8_t **assoc, int32_t *assoc_stride, const int32_t **stats);
+/* Pruning of clutter landmarks inside the session (slam_landmark_evidence_dev behind every associating update).  Accepted only
+ * while association is on — so never off single-GPU rows: otherwise SLAM_ERR_INVALID_ARG (slam_last_error says why) and the
+ * session goes on as before; likewise for hit, miss or cmax outside 1 .. 255 or a view_range that is not finite and > 0.
+ * hit == 0 switches pruning off (the other arguments are then ignored), and so does slam_pf_assoc_set(gate = 0); with pruning
+ * off the session runs exactly what it ran before the first call.  Switching on allocates (once) two evidence buffers
+ * [n_particles][ev_stride] and the stats, and initialises the evidence of the CURRENT maps with value = cmax: a map that is
+ * there is trusted.  The same initialisation runs whenever the maps are replaced wholesale while pruning is on
+ * (slam_pf_set_map_host / _dev, slam_pf_reset).  Frames: the stage runs behind the associating update on the row it wrote —
+ * through the frame's gather into the other evidence buffer, or in place on the frames a gated session kept; a frame without
+ * observations gathers the evidence as it gathers the maps.
+ * slam_pf_evidence_device_view: the current evidence ([n_particles][*ev_stride] bytes, indexed like slam_pf_view.map: BEFORE the
+ * pending gather) and the stats ([n_particles][2], indexed like slam_pf_view.score) of the last frame that ran the stage.
+ * slam_pf_get_evidence_host: [n_particles][n_landmarks] with the pending gather applied, like slam_pf_get_map_host;
+ * synchronises.  Both: SLAM_ERR_NOT_READY until pruning was switched on. */
+int slam_pf_prune_set(slam_pf *pf, int hit, int miss, int cmax, float view_range);   /* hit == 0: off */
+int slam_pf_evidence_device_view(slam_pf *pf, const uint8_t **ev, int32_t *ev_stride, const int32_t **stats);
+int slam_pf_get_evidence_host(slam_pf *pf, uint8_t *ev /* [n][nlandmarks] */);       /* pending gather applied, like slam_pf_get_map_host */
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
  * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
