@@ -18,8 +18,10 @@ namespace slam {
 // the same two for the kernels of the split layout (a batch costs fewer registers there: no covariance planes to carry)
 constexpr int kEkfSplitWpe = 5;   // 64k x 500, fused front: 4 waves 97.7 us, 5 waves 94.8 us, 6 waves 99.4 us, 8 waves (spills) 149 us
 constexpr int kEkfSplitNb = 2;
-// ... of the front launch that writes no mean row (survivor rows; 69 VGPRs): profiles/r05_survivor_rows.md
-constexpr int kEkfSplitWpeNoStore = 5;
+// ... of the front launch that writes no mean row (survivor rows; 69 VGPRs, no scratch at 5, 6 and 7): ms per frame, medians of four
+// interleaved runs, 64k x 500: 5 waves 0.0809, 6 waves 0.0790, 7 waves 0.0808; 1M x 1000: 5 waves 1.031, 6 waves 1.000, 7 waves 1.007
+// (profiles/r06_survivor_ride.md)
+constexpr int kEkfSplitWpeNoStore = 6;
 
 template <int NB>
 struct SplitBatch {
