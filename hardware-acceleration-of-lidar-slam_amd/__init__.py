@@ -122,6 +122,10 @@ SIGNATURES = {
     "slam_landmark_evidence_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "slam_evidence_init_dev": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _i]),
     "slam_evidence_counts": (_i, [_vp, _vp]),
+    "slam_detect_params_default": (None, [_vp]),
+    "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
+    "slam_detect_count": (_i, [_vp, _vp]),
+    "slam_detections_get_host": (_i, [_vp, _vp, _vp, _vp]),
     "slam_selftest_reciprocal": (_i, [_vp, _vp, _vp]),
     "slam_frame_fusion_set": (_i, [_vp, _i]),
     "slam_frame_fusion_count": (_i, [_vp, _vp]),
@@ -162,6 +166,7 @@ SIGNATURES = {
     "slam_pf_prune_set": (_i, [_vp, _i, _i, _i, _f]),
     "slam_pf_evidence_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_evidence_host": (_i, [_vp, _vp]),
+    "slam_pf_detect_set": (_i, [_vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
     "slam_pf_get_poses_host": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_map_host": (_i, [_vp, _vp]),
@@ -463,6 +468,25 @@ class Engine:
         self._ck(self.lib.slam_evidence_init_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, nrows, _ptr(d_ev), ev_stride,
                                                  int(value)), "evidence_init_dev")
 
+    def detect_scan_dev(self, params: "DetectParams | None" = None, d_stats=None, **kw):
+        """``slam_detect_scan_dev``: the engine's current scan -> its current detections (asynchronous; the count is picked up by
+        the next associating stage or by detections()).  params: a DetectParams, or the defaults with the keywords applied."""
+        p = params if params is not None else DetectParams.default(**kw)
+        self._ck(self.lib.slam_detect_scan_dev(self.h, C.byref(p), _ptr(d_stats)), "detect_scan_dev")
+
+    def detect_count(self) -> int:
+        """Detector launches of this engine so far."""
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_detect_count(self.h, C.byref(c)), "detect_count")
+        return c.value
+
+    def detections(self, full: bool = False):
+        """``slam_detections_get_host``: the current detections, whatever their origin -> (zx, zy) float32 [ndet]; synchronises.
+        full: -> (zx [64], zy [64], ndet), the entries from ndet on as the call returns them (0)."""
+        zx, zy, k = np.full(64, np.nan, np.float32), np.full(64, np.nan, np.float32), C.c_int32(-1)
+        self._ck(self.lib.slam_detections_get_host(self.h, _ptr(zx), _ptr(zy), C.byref(k)), "detections_get_host")
+        return (zx, zy, k.value) if full else (zx[:k.value].copy(), zy[:k.value].copy())
+
     def evidence_counts(self):
         """-> (evidence launches, evidence-init launches) of this engine so far."""
         c = (C.c_int64 * 2)()
@@ -594,6 +618,23 @@ class Engine:
         self._ck(self.lib.slam_gather_map_dev(self.h, _ptr(d_in), _ptr(d_out), in_row_stride, out_row_stride,
                                               in_plane_stride, out_plane_stride, nlandmarks, _ptr(d_idx), n),
                  "gather_map_dev")
+
+
+class DetectParams(C.Structure):
+    """``slam_detect_params``: the detector's rule (include/slam_hip.h: slam_detect_scan_dev)."""
+
+    _fields_ = [("jump", C.c_float), ("guard", C.c_float), ("max_width", C.c_float), ("max_range", C.c_float),
+                ("min_points", C.c_int32), ("max_points", C.c_int32), ("wrap", C.c_int32)]
+
+    @classmethod
+    def default(cls, **kw):
+        p = cls()
+        load_library().slam_detect_params_default(C.byref(p))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"slam_detect_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
 
 
 class MapperParams(C.Structure):
@@ -939,6 +980,15 @@ class PfSession:
         """``slam_pf_prune_set``: existence evidence and pruning of clutter landmarks behind every associating update (only while
         association is on); hit = 0 switches it off."""
         self.e._ck(self.e.lib.slam_pf_prune_set(self.h, int(hit), int(miss), int(cmax), view_range), "pf_prune_set")
+
+    def detect_set(self, params: "DetectParams | None | bool" = True, **kw):
+        """``slam_pf_detect_set``: observing frames make their detections from the engine's scan (only while association is on).
+        params: a DetectParams; True: the defaults with the keywords applied; None / False: off."""
+        if params is None or params is False:
+            self.e._ck(self.e.lib.slam_pf_detect_set(self.h, None), "pf_detect_set")
+            return
+        p = DetectParams.default(**kw) if params is True else params
+        self.e._ck(self.e.lib.slam_pf_detect_set(self.h, C.byref(p)), "pf_detect_set")
 
     def evidence_view(self):
         """``slam_pf_evidence_device_view``: the current evidence uint8 [n][stride] (indexed like the maps: before the pending

@@ -46,7 +46,7 @@ static hipError_t engine_host_block(slam_engine* e)
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t b_fm = up(sizeof(float) * (kFmIn + kFmOut + 4 + kFmPair)), b_plan = up(sizeof(int32_t) * (SLAM_PLAN_WORDS(kMaxRanks) + 1)),
                  b_small = 256, b_res = 256, b_stage = up(sizeof(float) * kStageSlots * kStageFloats);
-    const size_t total = b_fm + b_plan + 3 * b_small + b_res + b_stage;
+    const size_t total = b_fm + b_plan + 4 * b_small + b_res + b_stage;
     hipError_t err = hipHostMalloc(&e->h_block, total, hipHostMallocMapped);
     if (err != hipSuccess) return err;
     void* dblock = nullptr;
@@ -63,6 +63,7 @@ static hipError_t engine_host_block(slam_engine* e)
     take(b_small, e->h_gate, e->d_hgate);
     take(b_small, e->h_heads, e->d_hheads);
     take(b_small, e->h_obs, e->d_hobs);
+    take(b_small, e->h_det, e->d_hdet);
     take(b_res, e->h_pf_res, e->d_hpf_res);
     e->h_stage = reinterpret_cast<float*>(h + off);
     memset(e->h_block, 0, total);

@@ -1,7 +1,8 @@
 // engine_ekf.hip — the landmark side of a particle-filter frame behind the C ABI: motion sample (alone, or with the score of
 // the sampled poses), the observation table, the landmark update in every form (in place, out of place, split layout, fused
 // with motion + score as the frame's front launch), the switches and counters of those forms, data association (the frame's
-// detections, the association stage and the update under a per-particle table) and the landmarks' existence evidence.
+// detections, the association stage and the update under a per-particle table), the detector that makes the detections from
+// the scan, and the landmarks' existence evidence.
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -11,6 +12,18 @@
 #include "engine_internal.h"
 
 using namespace slam;
+
+int slam_engine_resolve_detections(slam_engine* e)
+{
+    if (!e->det_pending) return SLAM_OK;
+    const volatile uint32_t* flag = reinterpret_cast<const volatile uint32_t*>(e->h_det + 1);
+    if (int rc = slam_engine_wait_flag(e, nullptr, flag, e->det_seq, "detection count flag")) return rc;
+    const int ndet = e->h_det[0];
+    if (ndet < 0 || ndet > SLAM_MAX_DETECTIONS) return slam_engine_fail_hip(e, hipErrorUnknown, "detection count");
+    e->ndet = ndet;
+    e->det_pending = false;
+    return SLAM_OK;
+}
 
 extern "C" {
 
@@ -306,6 +319,8 @@ int slam_detections_upload_host(slam_engine* e, const float* zx, const float* zy
     e->d_det_zx = e->det_buf.as<float>();
     e->d_det_zy = e->det_buf.as<float>() + SLAM_MAX_DETECTIONS;
     e->ndet = ndet;
+    e->det_pending = false;   // (a detector launch still in flight wrote the buffer in front of this copy, in stream order)
+    e->det_from_scan = false;
     return SLAM_OK;
 }
 
@@ -316,6 +331,8 @@ int slam_detections_set_dev(slam_engine* e, const float* d_zx, const float* d_zy
     e->d_det_zx = d_zx;
     e->d_det_zy = d_zy;
     e->ndet = ndet;
+    e->det_pending = false;
+    e->det_from_scan = false;
     return SLAM_OK;
 }
 
@@ -324,6 +341,7 @@ int slam_associate_dev(slam_engine* e, const float* d_map, int64_t row_stride, i
                        int create, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
 {
     SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
     if (n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
         assoc_stride < nlandmarks || !(meas_var > 0.0f) || !(gate > 0.0f && gate <= std::numeric_limits<float>::max()) ||
         !(new_gate >= gate) || (create != 0 && create != 1) || (n > 0 && (!d_map || !d_x || !d_y || !d_th || !d_assoc)))
@@ -360,6 +378,7 @@ int slam_ekf_update_assoc_dev(slam_engine* e, const float* d_map_in, float* d_ma
                               float meas_var, const uint8_t* d_assoc, int assoc_stride, float* d_loglik)
 {
     SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
     if (n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
         assoc_stride < nlandmarks || !(meas_var > 0.0f) || (n > 0 && (!d_map_in || !d_map_out || !d_x || !d_y || !d_th || !d_assoc)))
         return SLAM_ERR_INVALID_ARG;
@@ -385,6 +404,83 @@ int slam_assoc_counts(slam_engine* e, int64_t counts[2])
     return SLAM_OK;
 }
 
+/* ------------------------------------------------------------------ the detector (detect_kernels.hip) */
+
+void slam_detect_params_default(slam_detect_params* p)
+{
+    if (!p) return;
+    p->jump = 0.3f;
+    p->guard = 1.0f;
+    p->max_width = 0.5f;
+    p->max_range = 20.0f;
+    p->min_points = 3;
+    p->max_points = 40;
+    p->wrap = 1;
+}
+
+int slam_detect_scan_dev(slam_engine* e, const slam_detect_params* params, int32_t* d_stats)
+{
+    SLAM_ENTER(e);
+    if (!params) return SLAM_ERR_INVALID_ARG;
+    if (!slam_detect_params_ok(params)) {
+        snprintf(e->err, sizeof e->err, "the detector needs finite jump, guard, max_width and max_range > 0, guard >= jump, "
+                                        "1 <= min_points <= max_points <= %d and wrap in {0, 1}", (int)SLAM_DETECT_MAX_POINTS);
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (e->nbeams < 0) return SLAM_ERR_NOT_READY;
+    if (!e->det_buf.p) SLAM_HIP_TRY(e, e->det_buf.ensure(sizeof(float) * 2 * SLAM_MAX_DETECTIONS));
+    DetectArgs a;
+    a.bx = e->d_bx;
+    a.by = e->d_by;
+    a.nbeams = e->nbeams;
+    a.jump2 = params->jump * params->jump;   // one float32 product each (-ffp-contract=off)
+    a.guard2 = params->guard * params->guard;
+    a.width2 = params->max_width * params->max_width;
+    a.range2 = params->max_range * params->max_range;
+    a.min_points = params->min_points;
+    a.max_points = params->max_points;
+    a.wrap = params->wrap;
+    a.det = e->det_buf.as<float>();
+    a.stats = d_stats;
+    a.h_out = e->d_hdet;
+    a.seq = e->det_seq + 1;
+    SLAM_HIP_TRY(e, launch_detect_scan(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
+    e->det_seq = a.seq;
+    e->d_det_zx = e->det_buf.as<float>();
+    e->d_det_zy = e->det_buf.as<float>() + SLAM_MAX_DETECTIONS;
+    e->ndet = 0;   // until the count is picked up
+    e->det_pending = true;
+    e->det_from_scan = true;
+    e->detect_launches++;
+    return SLAM_OK;
+}
+
+int slam_detect_count(slam_engine* e, int64_t* launches)
+{
+    SLAM_ENTER(e);
+    if (!launches) return SLAM_ERR_INVALID_ARG;
+    *launches = e->detect_launches;
+    return SLAM_OK;
+}
+
+int slam_detections_get_host(slam_engine* e, float* zx, float* zy, int32_t* ndet)
+{
+    SLAM_ENTER(e);
+    if (!zx || !zy || !ndet) return SLAM_ERR_INVALID_ARG;
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    // the detector's output: the whole block as its kernel left it (0 from ndet on); anything else: ndet values, 0 behind them
+    const size_t count = e->det_from_scan ? (size_t)SLAM_MAX_DETECTIONS : (size_t)e->ndet;
+    for (size_t k = count; k < SLAM_MAX_DETECTIONS; ++k) zx[k] = zy[k] = 0.0f;
+    if (count > 0) {
+        SLAM_HIP_TRY(e, hipMemcpyAsync(zx, e->d_det_zx, sizeof(float) * count, hipMemcpyDeviceToHost, e->stream));
+        SLAM_HIP_TRY(e, hipMemcpyAsync(zy, e->d_det_zy, sizeof(float) * count, hipMemcpyDeviceToHost, e->stream));
+    }
+    SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
+    *ndet = e->ndet;
+    return SLAM_OK;
+}
+
 /* ------------------------------------------------------------------ landmark existence evidence (evidence_kernels.hip) */
 
 int slam_landmark_evidence_dev(slam_engine* e, float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
@@ -393,6 +489,7 @@ int slam_landmark_evidence_dev(slam_engine* e, float* d_map, int64_t row_stride,
                                int32_t* d_stats)
 {
     SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
     if (n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
         assoc_stride < nlandmarks || ev_stride < nlandmarks || hit < 1 || hit > 255 || miss < 1 || miss > 255 || cmax < 1 || cmax > 255 ||
         !(view_range > 0.0f && view_range <= std::numeric_limits<float>::max()) ||   // (NaN fails every comparison)

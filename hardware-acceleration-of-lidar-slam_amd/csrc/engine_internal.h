@@ -89,6 +89,14 @@ struct slam_engine {
     const float *d_det_zx = nullptr, *d_det_zy = nullptr;
     int64_t assoc_launches[2] = { 0, 0 };   // slam_assoc_counts: associate launches, assoc-update launches (in no form counter)
     int64_t evidence_launches[2] = { 0, 0 };   // slam_evidence_counts: evidence launches, init launches (in no other counter)
+    // the detector (slam_detect_scan_dev): its kernel writes det_buf and leaves {ndet, sequence} in mapped host memory; until the
+    // next stage that needs the count on the host has picked it up (slam_engine_resolve_detections) it is PENDING
+    int32_t* h_det = nullptr;
+    int32_t* d_hdet = nullptr;
+    uint32_t det_seq = 0;
+    bool det_pending = false;
+    bool det_from_scan = false;   // the current detections are the detector's: det_buf holds 0 from ndet on
+    int64_t detect_launches = 0;   // slam_detect_count (in no other counter)
 
     DevBuf fm_buf;             // kFmIn + kFmOut floats
     DevBuf fm_work;            // 2 x 27 x SLAM_MAX_BEAMS floats: per-candidate hit rows of the lattice kernel, two sweeps (the chained pair)
@@ -265,6 +273,20 @@ inline bool slam_spin_flag(const volatile uint32_t* flag, uint32_t want)
 // engine.hip: wait until `flag` shows `seq`.  With a communicator: comm_wait_flag (polls it, bounded in time).  Without: the
 // bounded spin, then a stream synchronisation and one more look; SLAM_ERR_HIP naming `what` if it still is not there.
 int slam_engine_wait_flag(slam_engine* e, slam_comm* comm, const volatile uint32_t* flag, uint32_t seq, const char* what);
+
+// engine_ekf.hip: a pending detection count (slam_detect_scan_dev) becomes e->ndet — a flag wait, no copy, no stream
+// synchronisation; nothing pending: nothing happens
+int slam_engine_resolve_detections(slam_engine* e);
+// the conditions of slam_detect_scan_dev on its parameters (NaN fails every comparison)
+inline bool slam_detect_params_ok(const slam_detect_params* p)
+{
+    const float big = 3.402823466e+38f;
+    const float len[4] = { p->jump, p->guard, p->max_width, p->max_range };
+    for (float v : len)
+        if (!(v > 0.0f && v <= big)) return false;
+    return p->guard >= p->jump && p->min_points >= 1 && p->min_points <= p->max_points && p->max_points <= SLAM_DETECT_MAX_POINTS &&
+           (p->wrap == 0 || p->wrap == 1);
+}
 
 // engine_match.hip
 namespace slam_detail {

@@ -154,6 +154,10 @@ struct slam_pf {
     float prune_range = 0.0f;
     uint8_t* ev[2] = { nullptr, nullptr };   // [n][Lp] each, one allocation made by the first slam_pf_prune_set that switches on
     int32_t* ev_stats = nullptr;             // [n][2] pruned, seen after pruning (the last frame that ran the stage), behind them
+    // slam_pf_detect_set (only while association is on): every observing frame makes its detections from the engine's scan
+    // (slam_detect_scan_dev), issued in front of the frame's first launch
+    bool detect_on = false;
+    slam_detect_params detect_params{};
     // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe (RES_OBS) and moves between split and
     // split pages while it runs (between rows and pages when it could not have the split layout's tables)
     int layout_cfg = SLAM_MAP_AUTO;
@@ -1257,6 +1261,9 @@ int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations,
     }
     if (int rc = auto_layout(pf)) return rc;   // may move the maps to another layout (never changes a result)
     FrameFacts f = frame_facts(pf, use_observations);
+    // the detector: in front of the frame's first launch, so that its count has arrived when update_rows' association asks for it
+    if (pf->detect_on && pf->assoc_on && f.ekf)
+        if (int rc = slam_detect_scan_dev(e, &pf->detect_params, nullptr)) return rc;
     if (int rc = front_stage(pf, f, slot, dp)) return rc;
     if (int rc = gate_and_exchange(pf, f, collective_verdict)) return rc;
     if (int rc = pf->paged ? update_paged(pf, f) : pf->split ? update_split(pf, f) : update_rows(pf, f)) return rc;
@@ -1668,9 +1675,10 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
 {
     if (!pf) return SLAM_ERR_INVALID_ARG;
     slam_engine* e = pf->e;
-    if (gate == 0.0f) {   // off: the session runs exactly what it ran before the first call (pruning goes off with it)
+    if (gate == 0.0f) {   // off: the session runs exactly what it ran before the first call (pruning and the detector go off with it)
         pf->assoc_on = false;
         pf->prune_on = false;
+        pf->detect_on = false;
         return SLAM_OK;
     }
     if (pf->layout_cfg != SLAM_MAP_ROWS || pf->L == 0 || pf->comm) {
@@ -1744,6 +1752,29 @@ int slam_pf_prune_set(slam_pf* pf, int hit, int miss, int cmax, float view_range
     pf->prune_cmax = cmax;
     pf->prune_range = view_range;
     return evidence_from_maps(pf);   // the current maps are trusted (indexed like them: before the pending gather)
+}
+
+int slam_pf_detect_set(slam_pf* pf, const slam_detect_params* params)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (!params) {   // off: the session runs exactly what it ran before the first call
+        pf->detect_on = false;
+        return SLAM_OK;
+    }
+    if (!pf->assoc_on) {   // (which is what every layout but rows, a sharded session and a 2x2 covariance come down to)
+        snprintf(e->err, sizeof e->err, "the detector makes the detections the association reads: it needs data association switched "
+                                        "on (slam_pf_assoc_set: the row layout on one GPU, not sharded, meas_var * I)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (!slam_detect_params_ok(params)) {
+        snprintf(e->err, sizeof e->err, "the detector needs finite jump, guard, max_width and max_range > 0, guard >= jump, "
+                                        "1 <= min_points <= max_points <= %d and wrap in {0, 1}", (int)SLAM_DETECT_MAX_POINTS);
+        return SLAM_ERR_INVALID_ARG;
+    }
+    pf->detect_on = true;
+    pf->detect_params = *params;
+    return SLAM_OK;
 }
 
 int slam_pf_evidence_device_view(slam_pf* pf, const uint8_t** ev, int32_t* ev_stride, const int32_t** stats)

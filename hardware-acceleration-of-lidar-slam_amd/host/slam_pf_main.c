@@ -20,6 +20,8 @@
  *
  * usage: slam_pf_main dataset.csv frames beams map_out.csv particles [seed [mean|best]]
  *                     [--gpus N] [--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]]
+ *                     [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE]
+ *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]]] [--landmarks-out FILE]]
  *   particles      the whole population (a multiple of N)
  *   --ess F        ESS-gated resampling: resample only in frames whose effective sample size is below F * N
  *   --refine SWEEPS  scan-match refinement of every particle (slam_pf_refine_set): SWEEPS (1..16) sweeps of the reference's
@@ -27,6 +29,13 @@
  *   --refine-res T R  its steps in metres and radians (default: the reference's fastResolution2, 0.025 0.004363; main.c:833)
  *   --transport    rccl (default when N > 1): RCCL, one GPU per rank.  local: the in-process transport.
  *   --same-device  every rank on device 0 (only with the local transport; RCCL refuses two ranks on one GPU)
+ *   --landmarks L  the session is made on rows (SLAM_MAP_ROWS) with L landmark slots per particle; one GPU.  Without it the
+ *                  filter keeps no landmarks and the options below are refused
+ *   --assoc GATE NEW_GATE  data association (slam_pf_assoc_set, create = 1): frames read the engine's detections
+ *   --prune HIT MISS CMAX RANGE  existence evidence and pruning of clutter landmarks (slam_pf_prune_set)
+ *   --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]  the detector (slam_pf_detect_set; no values: slam_detect_params_default):
+ *                  every frame makes its detections from its own scan, so the landmark map grows from nothing but lidar frames
+ *   --landmarks-out FILE  at the end, the seen landmarks (P_xx >= 0) of the heaviest particle as "%f,%f" lines
  */
 #define _POSIX_C_SOURCE 200809L
 #include <math.h>
@@ -55,6 +64,15 @@ typedef struct {
     float refine_res[2];   /* --refine-res T R */
     int use_meas_cov;      /* --meas-cov qxx qxy qyy: the session is made on rows and given this measurement covariance */
     float meas_cov[3];
+    int landmarks;         /* --landmarks L (0: the filter keeps no landmarks) */
+    int use_assoc;         /* --assoc GATE NEW_GATE */
+    float assoc_gate[2];
+    int use_prune;         /* --prune HIT MISS CMAX RANGE */
+    int prune[3];
+    float prune_range;
+    int use_detect;        /* --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] */
+    slam_detect_params detect;
+    const char *landmarks_out;   /* --landmarks-out FILE */
     /* the ranks */
     int world, use_rccl, same_device;
     uint8_t comm_id[SLAM_COMM_ID_BYTES];
@@ -106,8 +124,9 @@ static void *rank_main(void *arg)
         }
     }
     /* motion noise of the order of the reference's fine lattice step (0.025 m, 0.004363 rad; main.c:833) */
-    const slam_pf_config cfg = { n, 0, { 0.01f, 0.01f, 0.002f }, 1.0f, 0.25f, run->seed, run->ess_frac,
-                                 run->use_meas_cov ? SLAM_MAP_ROWS : SLAM_MAP_AUTO };
+    /* ... and, with landmarks, a detection noise of the order of a pole's radius (0.1 m); without them meas_var is not read */
+    const slam_pf_config cfg = { n, run->landmarks, { 0.01f, 0.01f, 0.002f }, run->landmarks > 0 ? 0.01f : 1.0f, 0.25f, run->seed, run->ess_frac,
+                                 run->use_meas_cov || run->landmarks > 0 ? SLAM_MAP_ROWS : SLAM_MAP_AUTO };
     if (world > 1 || run->use_rccl || run->group) {
         if (run->group) CHECK(slam_comm_create_local(eng, run->group, rank, &comm));
         else CHECK(slam_comm_create_rccl(eng, rank, world, run->comm_id, &comm));
@@ -117,13 +136,18 @@ static void *rank_main(void *arg)
     }
     if (run->refine_sweeps) CHECK(slam_pf_refine_set(pf, run->refine_res[0], run->refine_res[1], run->refine_sweeps));
     if (run->use_meas_cov) {
-        /* This program's filter keeps no landmarks (n_landmarks = 0): a session without them has no covariance to apply the
-         * matrix to and says so (the values themselves were checked in main).  That is reported, not fatal: the run goes on as
-         * it would on rows.  A program that sets n_landmarks makes the same call and checks its result. */
+        /* Without --landmarks this program's filter keeps none (n_landmarks = 0): a session without them has no covariance to
+         * apply the matrix to and says so (the values themselves were checked in main).  That is reported, not fatal: the run
+         * goes on as it would on rows.  With landmarks the call's result is checked. */
         const int rc = slam_pf_meas_cov_set(pf, run->meas_cov);
         if (cfg.n_landmarks > 0) CHECK(rc);
         else if (rank == 0) fprintf(stderr, "--meas-cov has no effect here: %s\n", slam_last_error(eng));
     }
+    /* the landmark pipeline: association reads detections, the detector makes them from each frame's scan */
+    if (run->use_assoc) CHECK(slam_pf_assoc_set(pf, run->assoc_gate[0], run->assoc_gate[1], 1));
+    if (run->use_prune) CHECK(slam_pf_prune_set(pf, run->prune[0], run->prune[1], run->prune[2], run->prune_range));
+    if (run->use_detect) CHECK(slam_pf_detect_set(pf, &run->detect));
+    const int observe = run->landmarks > 0 && run->use_assoc && run->use_detect;   /* else: no frame has observations */
     if (fe_scan_init(&scan, beams, -2.351831f, 0.004363f) || fe_points_init(&map, FE_MAP_CAPACITY + beams) ||
         fe_points_init(&local, FE_LOCAL_CAPACITY) || fe_grid_init(&coarse, FE_COARSE_LD) || fe_grid_init(&fine, FE_FINE_LD) ||
         !(hits = (float *)calloc((size_t)beams + 1, sizeof(float)))) {
@@ -166,7 +190,7 @@ static void *rank_main(void *arg)
         float dp[3];
         for (int a = 0; a < 3; ++a) dp[a] = k > 1 ? pose[a] - prev[a] : 0.0f;
         const double t0 = now_s();
-        CHECK(slam_pf_step(pf, 1, dp, 0));
+        CHECK(slam_pf_step(pf, 1, dp, observe));
         float best[3];
         if (run->use_mean) {
             /* posterior mean over ALL ranks' particles = plain mean of a resampled population, weighted mean of one that the
@@ -211,6 +235,35 @@ static void *rank_main(void *arg)
         for (int j = 0; j < map.size; ++j) fprintf(out, "%f,%f\n", map.x[j], map.y[j]);
         fclose(out);
     }
+    if (rank == 0 && run->landmarks_out) {
+        /* the heaviest particle of the last frame is named by its index BEFORE that frame's resample; the rows that can be
+         * asked for are those of the CURRENT particles: take the first one that carries its pose (an offspring of it) */
+        const int L = run->landmarks;
+        float bp[3], *px = (float *)malloc(sizeof(float) * 3 * (size_t)n), *row = (float *)malloc(sizeof(float) * 5 * (size_t)L);
+        int32_t sel = 0;
+        int rc_out = px && row ? SLAM_OK : SLAM_ERR_CAPACITY;
+        if (rc_out == SLAM_OK) rc_out = slam_pf_best(pf, bp, NULL, NULL);
+        if (rc_out == SLAM_OK) rc_out = slam_pf_get_poses_host(pf, px, px + n, px + 2 * (size_t)n);
+        if (rc_out == SLAM_OK) {
+            int found = 0;
+            for (int j = 0; j < n && !found; ++j)
+                if (px[j] == bp[0] && px[n + j] == bp[1] && px[2 * (size_t)n + j] == bp[2]) { sel = j; found = 1; }
+            if (!found) fprintf(stderr, "--landmarks-out: the heaviest particle left no offspring; writing particle 0's map\n");
+            rc_out = slam_pf_get_map_rows_host(pf, &sel, 1, row);
+        }
+        FILE *out = rc_out == SLAM_OK ? fopen(run->landmarks_out, "w") : NULL;
+        if (out) {
+            int seen = 0;
+            for (int l = 0; l < L; ++l)
+                if (!(row[2 * L + l] < 0.0f)) { fprintf(out, "%f,%f\n", row[l], row[L + l]); ++seen; }
+            fclose(out);
+            fprintf(stderr, "landmarks %d of %d slots\n", seen, L);
+        }
+        free(px);
+        free(row);
+        if (rc_out != SLAM_OK) CHECK(rc_out);
+        if (!out) { perror(run->landmarks_out); goto fail; }
+    }
     me->rc = 0;
 fail:
     if (me->rc && comm) slam_comm_abort(comm);   /* the other ranks must not wait for this one: their calls fail with SLAM_ERR_COMM */
@@ -250,13 +303,48 @@ int main(int argc, char **argv)
             run.use_meas_cov = 1;
             for (int k = 0; k < 3; ++k) run.meas_cov[k] = (float)atof(argv[++a]);
         }
+        else if (!strcmp(argv[a], "--landmarks") && a + 1 < argc) run.landmarks = atoi(argv[++a]);
+        else if (!strcmp(argv[a], "--assoc") && a + 2 < argc) {
+            run.use_assoc = 1;
+            for (int k = 0; k < 2; ++k) run.assoc_gate[k] = (float)atof(argv[++a]);
+        }
+        else if (!strcmp(argv[a], "--prune") && a + 4 < argc) {
+            run.use_prune = 1;
+            for (int k = 0; k < 3; ++k) run.prune[k] = atoi(argv[++a]);
+            run.prune_range = (float)atof(argv[++a]);
+        }
+        else if (!strcmp(argv[a], "--detect")) {
+            run.use_detect = 1;
+            slam_detect_params_default(&run.detect);
+            /* seven values follow, or none: a value is whatever starts like a number */
+            int have = 0;
+            while (have < 7 && a + 1 + have < argc && strchr("0123456789.+-", argv[a + 1 + have][0]) && strncmp(argv[a + 1 + have], "--", 2))
+                ++have;
+            if (have == 7) {
+                run.detect.jump = (float)atof(argv[a + 1]);
+                run.detect.guard = (float)atof(argv[a + 2]);
+                run.detect.max_width = (float)atof(argv[a + 3]);
+                run.detect.max_range = (float)atof(argv[a + 4]);
+                run.detect.min_points = atoi(argv[a + 5]);
+                run.detect.max_points = atoi(argv[a + 6]);
+                run.detect.wrap = atoi(argv[a + 7]);
+                a += 7;
+            }
+        }
+        else if (!strcmp(argv[a], "--landmarks-out") && a + 1 < argc) run.landmarks_out = argv[++a];
         else if (npos < 8) pos[npos++] = argv[a];
     }
-    if (npos < 5 || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16) {
+    const int landmark_options = run.use_assoc || run.use_prune || run.use_detect || run.landmarks_out != NULL;
+    if (npos < 5 || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
+        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1)) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
+                        "  [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]]] "
+                        "[--landmarks-out FILE]]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
-                        "              while this program keeps no landmarks\n", argv[0]);
+                        "              without --landmarks\n"
+                        "  --landmarks: L landmark slots per particle on rows, one GPU; --assoc, --prune, --detect and --landmarks-out need it.\n"
+                        "              With --assoc and --detect every frame makes its detections from its own scan\n", argv[0]);
         return 2;
     }
     if (run.use_meas_cov) {   /* the conditions of slam_pf_meas_cov_set: finite, qxx > 0, qyy > 0, float determinant > 0 */

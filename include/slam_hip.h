@@ -376,6 +376,47 @@ int slam_landmark_evidence_dev(slam_engine *e, float *d_map, int64_t row_stride,
 int slam_evidence_init_dev(slam_engine *e, const float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
                            int nrows, uint8_t *d_ev, int ev_stride, int value);
 int slam_evidence_counts(slam_engine *e, int64_t counts[2]);   /* evidence launches, init launches */
+/* THE DETECTOR: the detections of a frame made on the device from the engine's current scan (slam_scan_upload_host / _set_dev),
+ * P = nbeams points in scan order — what fe_clean left, so a removed beam leaves no hole and the rule uses distances only, never
+ * beam angles.  With jump2 = jump * jump, guard2, width2 and range2 likewise (each rounded once to float32), and every step below
+ * one separately rounded float32 operation:
+ *   1. per point b: r2_b = x*x + y*y; g_b = dx*dx + dy*dy against point b - 1 (g_0: against point P - 1 with wrap, else +inf);
+ *      break_b = !(g_b <= jump2) (a NaN breaks);
+ *   2. every break f starts a SEGMENT: the points from f up to, excluding, the next break — cyclic through P - 1 into 0 with
+ *      wrap; without it the walk ends at P - 1, and a segment that holds point 0 or point P - 1 is rejected (cut by the field of
+ *      view).  m = its point count, e = its last point.  A scan without a break has no segment;
+ *   3. a segment is ACCEPTED iff (a) min_points <= m <= max_points, (b) dx = x_e - x_f, dy alike, dx*dx + dy*dy <= width2, (c) it
+ *      is occluded at neither end — left, with p the point before f: g_f <= guard2 && r2_p < r2_f; right, with q the point after
+ *      e: g_q <= guard2 && r2_q < r2_e (something close to an end and in front of it may hide part of the object) — and (d) its
+ *      centroid zx = sx / (float)m, zy alike (sx = x_f, then + x over the other points in segment order; IEEE division) has
+ *      zx*zx + zy*zy <= range2.  NaN and inf pass none of the tests: every detection is finite;
+ *   4. the accepted segments in ascending f, the first SLAM_MAX_DETECTIONS of them, are the engine's current detections:
+ *      zx[k] | zy[k] in the engine's own buffer, no copy through the host.  d_stats (may be NULL) is int32 [4] = segments,
+ *      accepted, written (= ndet), 0.  Operation order: tests/_detect_spec.py.
+ * slam_detect_scan_dev is asynchronous: the count of the detections is PENDING afterwards — the kernel leaves it in mapped host
+ * memory, and slam_associate_dev, slam_ekf_update_assoc_dev and slam_landmark_evidence_dev pick it up first thing (a wait on a
+ * flag word: no copy, no stream synchronisation); with nothing pending they do what they did.  slam_detections_upload_host /
+ * _set_dev replace the detections and end the pending state.  SLAM_ERR_INVALID_ARG, nothing launched: a length that is not
+ * finite and > 0, guard < jump, not 1 <= min_points <= max_points <= SLAM_DETECT_MAX_POINTS, wrap not 0 or 1, a null pointer other
+ * than d_stats.  SLAM_ERR_NOT_READY: no scan.  Timing: bracketed as SLAM_PROF_PAGES, as the association is.  Counted by
+ * slam_detect_count, and in no other counter.
+ * slam_detections_get_host: the engine's current detections whatever their origin — zx and zy hold SLAM_MAX_DETECTIONS values
+ * each, the first *ndet the detections, the rest 0 (after slam_detect_scan_dev: the block as the kernel left it); synchronises.
+ * SLAM_ERR_NOT_READY: none were handed over or made. */
+enum { SLAM_DETECT_MAX_POINTS = 64 };
+typedef struct {
+    float jump;          /* a gap between neighbouring points above this breaks the scan [m] */
+    float guard;         /* a nearer neighbour within this of a segment's end occludes it [m]; >= jump */
+    float max_width;     /* first to last point of a segment [m] */
+    float max_range;     /* of the centroid [m] */
+    int32_t min_points;  /* 1 <= min_points <= max_points <= SLAM_DETECT_MAX_POINTS */
+    int32_t max_points;
+    int32_t wrap;        /* 1: a 360-degree scan, point 0 follows point P - 1; 0: the ends are the edge of the field of view */
+} slam_detect_params;
+void slam_detect_params_default(slam_detect_params *p);   /* 0.3, 1.0, 0.5, 20.0, 3, 40, 1 */
+int slam_detect_scan_dev(slam_engine *e, const slam_detect_params *params, int32_t *d_stats /* [4], may be NULL */);
+int slam_detect_count(slam_engine *e, int64_t *launches);
+int slam_detections_get_host(slam_engine *e, float *zx, float *zy, int32_t *ndet);
 /* The FRONT of a frame of a single-GPU slam_pf session on rows — motion sample + scan-match score (FastMatch's inner loop,
  * main.c:459-518, for every particle) and the out-of-place landmark update — goes out as ONE launch whose scoring and
  * updating workgroups are dealt out interleaved: the scorer's gathers (texture addresser, L2) run in the shadow of the
@@ -698,6 +739,13 @@ int slam_pf_assoc_device_view(slam_pf *pf, const uint8_t **assoc, int32_t *assoc
 int slam_pf_prune_set(slam_pf *pf, int hit, int miss, int cmax, float view_range);   /* hit == 0: off */
 int slam_pf_evidence_device_view(slam_pf *pf, const uint8_t **ev, int32_t *ev_stride, const int32_t **stats);
 int slam_pf_get_evidence_host(slam_pf *pf, uint8_t *ev /* [n][nlandmarks] */);       /* pending gather applied, like slam_pf_get_map_host */
+/* The detector inside the session (slam_detect_scan_dev with these parameters; NULL: off).  Accepted only while association is on
+ * — otherwise SLAM_ERR_INVALID_ARG (slam_last_error says why) and the session goes on as before; likewise for parameters that
+ * slam_detect_scan_dev refuses.  slam_pf_assoc_set(gate = 0) switches it off too.  With it on, every frame with use_observations
+ * makes its detections from the engine's current scan — the launch goes out in front of the frame's first launch, so its count
+ * has long arrived when the association asks for it — and then runs associate -> update (-> evidence) on them; whatever
+ * detections were handed over are replaced.  With it off the session runs exactly what it ran before the first call. */
+int slam_pf_detect_set(slam_pf *pf, const slam_detect_params *params /* NULL: off */);
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
  * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
