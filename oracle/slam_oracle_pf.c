@@ -377,7 +377,15 @@ void orc_offspring_offsets(const uint64_t *cdf, int n, uint64_t base, uint64_t t
                            int64_t n_total, int32_t *first)
 {
     /* comb tooth j sits at j*total + u on an axis where particle i spans [N*C(i-1), N*C(i));
-     * first[i] = number of teeth strictly below N*C(i-1) = ceil((N*C(i-1) - u) / total), clamped at 0 */
+     * first[i] = number of teeth strictly below N*C(i-1) = ceil((N*C(i-1) - u) / total), clamped at 0.
+     * A grand total of 0 (every log-weight -inf or NaN, or one of them +inf: every difference to the maximum is -inf or NaN
+     * and quantises to 0) or of 2^63 and more has no comb: first[i] = 0 for every particle, without a division, whatever cdf,
+     * base and comb_u hold; orc_ancestors then gives every slot the LAST particle, n_total - 1.  Under the resample gate the
+     * case never gets here: S = Q = 0 is "0 < 0", no resample, the population keeps its slots (orc_ess_resample). */
+    if (total == 0 || (total >> 63)) {
+        for (int i = 0; i < n; ++i) first[i] = 0;
+        return;
+    }
     for (int i = 0; i < n; ++i) {
         const uint64_t c_excl = base + (i ? cdf[i - 1] : 0);
         const unsigned __int128 X = (unsigned __int128)c_excl * (uint64_t)n_total;
