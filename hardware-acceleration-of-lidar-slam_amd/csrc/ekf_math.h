@@ -180,7 +180,12 @@ __device__ __forceinline__ EkfParticle<T> ekf_particle(const EkfShared<T>& h, T 
     r.o0 = r.wx - h.q * t0;
     r.o1 = r.wy - h.q * t1;
     const T maha = dx * t0 + dy * t1;
-    r.ll = ((ekf_splat<T>(0.0f) - ekf_splat<T>(0.5f) * maha) - h.hl) - ekf_splat<T>(1.8378770664f);
+    // The specification says ((0 - 0.5 maha) - hl) - 1.8378770664.  0 - x and -x differ in one case only, the sign of a zero
+    // result (0 - (+0) = +0, -(+0) = -0), and the two subtractions behind it erase that sign: a zero of either sign minus a
+    // non-zero hl is -hl exactly, and minus a zero hl it is a zero again, from which the non-zero constant gives the same bits.
+    // A NaN maha gives a NaN term either way.  Without nsz the compiler may not take this step itself; written as the negated
+    // product, the subtraction from zero goes (one packed instruction per particle and batch).
+    r.ll = (-(ekf_splat<T>(0.5f) * maha) - h.hl) - ekf_splat<T>(1.8378770664f);
     return r;
 }
 

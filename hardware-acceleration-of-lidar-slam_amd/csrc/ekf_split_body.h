@@ -113,17 +113,29 @@ __device__ __forceinline__ void split_apply(const SplitBatch<NB>& b, const EkfPo
 // MEANS / TALLY: the two halves of what the update leaves, for a survivor-rows frame.  Its front launch runs
 // MEANS = false — classes, stamps and log-likelihoods, no mean row —, and the launch behind its resample (ekf_materialise_kernel)
 // TALLY = false — mean rows and nothing else, for the particles EkfArgs::survivor names.  The same device functions either way.
+// OWN_MOTION (the fused front of a frame): the poses are not read but worked out here, as ekf_group_body does — but ONCE per
+// workgroup: one wavefront makes the motion samples and the sines and cosines of the workgroup's kEkfWaves * G particles in its
+// low lanes and hands them over in LDS (s_motion: one float4 (x, y, sine, cosine) per particle), where every wavefront for
+// itself ran Philox, Box-Muller and det_sincosf in 64 lanes to use G of them.  A particle's sample is a function of its index
+// and its ancestor's pose alone: the same bits.  The one barrier this costs stands behind everything a wavefront can issue
+// without its poses — the gather indices, the classes, the loads of its first pass —, so the round trips of those run while
+// the samples are made; every wavefront of a workgroup with a particle reaches it, also one that has no particle of its own
+// or whose group this launch leaves out (group_filter).
 template <int NB, int G, bool OWN_MOTION, bool MEANS = true, bool TALLY = true>
 __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float (*s_acc)[G][128], const MotionIO& mio,
-                                               const MotionParams& mpar)
+                                               const MotionParams& mpar, float4* s_motion = nullptr)
 {
     const unsigned lane = threadIdx.x & 63u;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int g0 = (bid * kEkfWaves + wave) * G;
-    if (g0 >= a.n) return;
-    const int nslots = a.n - g0 < G ? a.n - g0 : G;
+    const int first = bid * kEkfWaves * G;   // the workgroup's first particle
+    const int g0 = first + wave * G;
+    if (first >= a.n) return;   // (a surplus workgroup of the padded grid: all its wavefronts leave)
+    bool skip = g0 >= a.n;      // wave-uniform: nothing to update here
+    if constexpr (!OWN_MOTION)
+        if (skip) return;
+    const int nslots = skip ? 0 : a.n - g0 < G ? a.n - g0 : G;
     // lane k prepares particle g0 + k: source row, class, pose; read back with v_readlane below
-    const int mine = g0 + ((int)lane < nslots ? (int)lane : 0);
+    const int mine = skip ? first : g0 + ((int)lane < nslots ? (int)lane : 0);
     unsigned long long alive = ~0ull;   // (TALLY = false) the group's particles that get a row
     if constexpr (!TALLY) {
         if (a.survivor) alive = __ballot((int)lane < nslots && a.survivor[mine] == a.survivor_stamp);
@@ -133,30 +145,12 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
     const int src_l = a.anc ? a.anc[mine] : mine;
     if (a.group_filter) {   // sharded: this launch takes the groups fed from local rows only (1) or the others (2)
         const bool remote = __ballot(src_l >= a.n) != 0;
-        if (remote != (a.group_filter == 2)) return;
-    }
-    const int cls_l = a.cls_in[src_l];
-    float st_l, ct_l, px_l, py_l;
-    if constexpr (OWN_MOTION) {
-        // the ancestor's POSE comes through the scorer's index (a sharded session reads it out of the all-gathered poses of
-        // every rank; on one GPU the two indices are the same array)
-        const int psrc = mio.anc ? mio.anc[mine] : mine;
-        float th_l;
-        motion_sample_one(mpar, (uint64_t)mine, mio.sx[psrc], mio.sy[psrc], mio.sth[psrc], px_l, py_l, th_l);
-        det_sincosf(th_l, st_l, ct_l);
-    } else {
-        det_sincosf(a.th[mine], st_l, ct_l);
-        px_l = a.x[mine];
-        py_l = a.y[mine];
-    }
-    if constexpr (TALLY) {
-        if ((int)lane < nslots) {   // the class follows the particle and is still in use
-            a.cls_out[mine] = cls_l;
-            a.cstamp[cls_l] = a.stamp_now;
+        if (remote != (a.group_filter == 2)) {
+            if constexpr (!OWN_MOTION) return;
+            skip = true;
         }
-#pragma unroll
-        for (int k = 0; k < G; ++k) acc_store<G>(s_acc, wave, k, lane, bc2(0.0f));
     }
+    const int cls_l = a.cls_in[OWN_MOTION && skip ? mine : src_l];   // (a group left out may have its source rows elsewhere)
     const int pl = __builtin_amdgcn_readfirstlane(a.plane_stride * 4);
     const int mean_bytes = 2 * pl, cov_bytes = 3 * pl;
     const gchar* ozx = uniform_gptr(a.obs_zx);
@@ -165,6 +159,7 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
     const v2f q2 = bc2(a.meas_var);
     const float nan = __uint_as_float(0x7fc00000u);
 
+    float st_l, ct_l, px_l, py_l;   // lane k: the pose of particle g0 + k (set below)
     auto pose_of = [&](int k) {
         EkfPose w;
         w.rout = row_rsrc(a.map_out, g0 + k, a.row_stride, mean_bytes);
@@ -236,9 +231,45 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
     };
 
     constexpr unsigned kStep = 128u * NB;
-    for (unsigned lb = 0; lb < L; lb += kStep) {
-        Raw cur;
-        issue(lb, cur);
+    Raw cur;   // the loads of a pass are issued at the end of the pass before it; those of the first one ahead of the poses
+    if constexpr (OWN_MOTION) {
+        if (wave == 0) {   // particle first + lane in lane < kEkfWaves * G: the whole workgroup's samples in one wavefront
+            const int i = first + (int)lane;
+            if ((int)lane < kEkfWaves * G && i < a.n) {
+                // the ancestor's POSE comes through the scorer's index (a sharded session reads it out of the all-gathered poses
+                // of every rank; on one GPU the two indices are the same array)
+                const int psrc = mio.anc ? mio.anc[i] : i;
+                float x, y, th, st, ct;
+                motion_sample_one(mpar, (uint64_t)i, mio.sx[psrc], mio.sy[psrc], mio.sth[psrc], x, y, th);
+                det_sincosf(th, st, ct);
+                s_motion[lane] = make_float4(x, y, st, ct);
+            }
+        }
+        // (behind the samples in wavefront 0: in front of them the 40 registers the loads land in stay reserved through
+        // Philox — 73 VGPRs and a stack object instead of 72 and none; its gather index and class are on their way meanwhile)
+        if (!skip && L > 0) issue(0, cur);
+        __syncthreads();
+        if (skip) return;
+        const float4 m = s_motion[wave * G + ((int)lane < nslots ? (int)lane : 0)];
+        px_l = m.x;
+        py_l = m.y;
+        st_l = m.z;
+        ct_l = m.w;
+    } else {
+        if (L > 0) issue(0, cur);
+        det_sincosf(a.th[mine], st_l, ct_l);
+        px_l = a.x[mine];
+        py_l = a.y[mine];
+    }
+    if constexpr (TALLY) {
+        if ((int)lane < nslots) {   // the class follows the particle and is still in use
+            a.cls_out[mine] = cls_l;
+            a.cstamp[cls_l] = a.stamp_now;
+        }
+#pragma unroll
+        for (int k = 0; k < G; ++k) acc_store<G>(s_acc, wave, k, lane, bc2(0.0f));
+    }
+    for (unsigned lb = 0; lb < L;) {
         SplitBatch<NB> b;
 #pragma unroll
         for (int g = 0; g < NB; ++g)
@@ -283,23 +314,20 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
                 split_apply_terms<NB, true>(b, w, pl, term);
             }
         }
+        lb += kStep;
+        if (lb < L) issue(lb, cur);
     }
     if constexpr (!TALLY) return;
-    // the G sums side by side (wave_xor_tree_sum for every particle, the steps interleaved: one after the other they were 6 G
-    // dependent cross-lane round trips at the end of every wavefront's life); slots beyond nslots hold zeros
+    // the G sums side by side (wave_xor_tree_sum's bits for every particle, on the halving schedule of ekf_wave.h: one after the
+    // other the butterflies were 6 G dependent cross-lane round trips at the end of every wavefront's life, interleaved still
+    // 6 G exchanges and additions, half of them made twice); slots beyond nslots hold zeros
     float tot[G];
 #pragma unroll
     for (int k = 0; k < G; ++k) {
         const v2f acc = acc_load<G>(s_acc, wave, k, lane);
         tot[k] = acc[0] + acc[1];
     }
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1)
-#pragma unroll
-        for (int k = 0; k < G; ++k) tot[k] = tot[k] + __shfl_xor(tot[k], s, 64);
-    float total = 0.0f;   // lane k: the sum of particle g0 + k (every lane holds all of them)
-#pragma unroll
-    for (int k = 0; k < G; ++k) total = (int)lane == k ? tot[k] : total;
+    const float total = wave_halving_tree_sums<G>(tot, lane);   // lane k < G: the sum of particle g0 + k
     if ((int)lane < nslots) store_loglik(a, g0 + (int)lane, total);
 }
 

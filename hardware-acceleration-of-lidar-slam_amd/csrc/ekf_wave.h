@@ -27,6 +27,37 @@ __device__ __forceinline__ float wave_xor_tree_sum(float v)   // t[j] = t[j] + t
     return v;
 }
 
+// wave_xor_tree_sum of G values per lane (the sums of a group's G particles) without doing every addition twice.  In a step
+// of the butterfly lanes j and j ^ s add the same two values; here, while a lane still holds more than one particle, the
+// two share the work: of each pair of neighbouring values lane j keeps the one whose particle has the bit of s as j has it and
+// hands the other to lane j ^ s, which keeps exactly that one.  After log2 G steps a lane holds ONE particle, j & (G - 1),
+// and the remaining steps run on it as in the butterfly: G - 1 + 6 - log2 G exchanges and additions instead of 6 G.  What lane
+// j adds for the particle it ends up with is, step by step, what the butterfly adds in lane j for that particle — own value
+// first, the partner's second —, so the value returned in lane j is the butterfly's t[j & (G - 1)] of lane j bit for bit: lane
+// k < G holds particle k's total (tests/test_reduce_schedule_cpu.py walks the schedule lane by lane).
+template <int G>
+__device__ __forceinline__ float wave_halving_tree_sums(const float (&t)[G], unsigned lane)
+{
+    static_assert(G == 2 || G == 4 || G == 8, "a power of two below the wavefront's size");
+    float v[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) v[k] = t[k];
+    int s = 1;
+#pragma unroll
+    for (int m = G; m > 1; m >>= 1, s <<= 1) {
+        const bool up = (lane & (unsigned)s) != 0;
+#pragma unroll
+        for (int i = 0; i < m / 2; ++i) {
+            const float keep = up ? v[2 * i + 1] : v[2 * i];
+            const float send = up ? v[2 * i] : v[2 * i + 1];
+            v[i] = keep + __shfl_xor(send, s, 64);
+        }
+    }
+#pragma unroll
+    for (; s < 64; s <<= 1) v[0] = v[0] + __shfl_xor(v[0], s, 64);
+    return v[0];
+}
+
 constexpr int kEkfWaves = 4;   // particles per workgroup
 
 // global-address-space pointers: "scalar base + 32-bit lane offset" is an addressing mode of global_load/store only

@@ -43,6 +43,10 @@ void frame_front_kernel(FrontArgs f)
     static_assert(kScoreBlock == kEkfWaves * 64, "both kinds of workgroup have 256 threads");
     extern __shared__ float4 s_pair[];
     __shared__ float s_acc[kEkfWaves][G][128];
+    // a workgroup's motion samples, made once by one of its wavefronts: (x, y, sine, cosine) of the kScoreBlock / 4 poses of a
+    // scoring workgroup with four lanes per pose, of the kEkfWaves * G particles of an updating one (1 KB)
+    __shared__ float4 s_motion[kScoreBlock / 4];
+    static_assert(kEkfWaves * G <= kScoreBlock / 4, "s_motion holds an updating workgroup's particles");
     if constexpr (!MEANS) {
         if (blockIdx.x == gridDim.x - 1) {   // (the caller's table may be rewritten as soon as the frame is issued)
             const int L = f.a.nlandmarks, Lp = f.a.plane_stride;
@@ -65,9 +69,9 @@ void frame_front_kernel(FrontArgs f)
         const int sb = before * 8 + xcd;
         if (sb >= f.score_blocks) return;
         score_poses_body<false, LPP, DEPTH, true, PACKED>(f.g, f.bx, f.by, f.nbeams, f.mio.x, f.mio.y, f.mio.th, nullptr, f.a.n,
-                                                          f.score, f.count, f.mio, f.mpar, sb, s_pair);
+                                                          f.score, f.count, f.mio, f.mpar, sb, s_pair, s_motion);
     } else if constexpr (SPLIT) {
-        ekf_split_body<NB, G, true, MEANS>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar);
+        ekf_split_body<NB, G, true, MEANS>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar, s_motion);
     } else {
         ekf_group_body<NB, G, true>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar);
     }

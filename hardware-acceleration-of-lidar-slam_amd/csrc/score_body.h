@@ -60,7 +60,7 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
                                                  int nbeams, float* __restrict__ px, float* __restrict__ py,
                                                  float* __restrict__ p2, const float* __restrict__ p3, int nposes,
                                                  float* __restrict__ score, int32_t* __restrict__ count, const MotionIO& mio,
-                                                 const MotionParams& mpar, int block, float4* s_pair)
+                                                 const MotionParams& mpar, int block, float4* s_pair, float4* s_motion = nullptr)
 {
     // beams padded with NaN to a whole number of pipeline rounds: a NaN beam is out of bounds and adds +0
     // (at least one round, so that an empty scan still runs the pipeline prologue on NaN beams)
@@ -84,6 +84,30 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
         static_assert(kScoreBlock == 256, "one table entry per thread");
         s_table[threadIdx.x] = g.table[threadIdx.x];
     }
+    // MOTION with four lanes per pose: the kScoreBlock / 4 poses of the workgroup fill ONE wavefront, which makes their samples
+    // with their sines and cosines once — lane l that of the workgroup's pose l — and hands them to the quads through LDS
+    // (s_motion: (x, y, sine, cosine) per pose) behind the barrier the beams need anyway, where all four lanes of every quad
+    // ran Philox, Box-Muller and det_sincosf for the same pose.  The same function of the pose's index and its ancestor's pose:
+    // the same bits.  The LAST wavefront does it: with 360 beams it has no beam pair to stage above.
+    constexpr bool kSharedMotion = MOTION && LPP == 4;
+    if constexpr (kSharedMotion) {
+        static_assert(kScoreBlock / LPP == 64, "the workgroup's poses fill one wavefront");
+        if (threadIdx.x >= kScoreBlock - 64) {
+            const int l = (int)threadIdx.x - (kScoreBlock - 64);
+            const int pose_l = block * (kScoreBlock / LPP) + l;
+            const int i_l = pose_l < nposes ? pose_l : nposes - 1;   // (a quad beyond the poses scores the last one, as below)
+            const int j = mio.anc ? mio.anc[i_l] : i_l;
+            float x, y, th, sn, cs;
+            motion_sample_one(mpar, (uint64_t)i_l, mio.sx[j], mio.sy[j], mio.sth[j], x, y, th);
+            if (pose_l < nposes) {
+                px[i_l] = x;
+                py[i_l] = y;
+                p2[i_l] = th;
+            }
+            det_sincosf(th, sn, cs);
+            s_motion[l] = make_float4(x, y, sn, cs);
+        }
+    }
     __syncthreads();
 
     const int t = block * kScoreBlock + threadIdx.x;
@@ -92,7 +116,13 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
     const int i = pose < nposes ? pose : nposes - 1;   // LPP > 1: keep whole quads active for the DPP broadcasts
 
     float ct, st, pose_x, pose_y;
-    if constexpr (MOTION) {
+    if constexpr (kSharedMotion) {
+        const float4 m = s_motion[threadIdx.x / LPP];
+        pose_x = m.x;
+        pose_y = m.y;
+        st = m.z;
+        ct = m.w;
+    } else if constexpr (MOTION) {
         const int j = mio.anc ? mio.anc[i] : i;
         float pose_t;
         motion_sample_one(mpar, (uint64_t)i, mio.sx[j], mio.sy[j], mio.sth[j], pose_x, pose_y, pose_t);

@@ -47,8 +47,9 @@ __global__ __launch_bounds__(kScoreBlock) void score_poses_kernel(ScoreGrid g, c
             return;
         }
     }
+    __shared__ float4 s_motion[kScoreBlock / 4];   // MOTION, four lanes per pose: the workgroup's samples (unused otherwise: no LDS)
     score_poses_body<HAS_CS, LPP, DEPTH, MOTION, PACKED>(g, bx, by, nbeams, px, py, p2, p3, nposes, score, count, mio, mpar,
-                                                         (int)blockIdx.x, s_pair);
+                                                         (int)blockIdx.x, s_pair, s_motion);
 }
 
 // Small batches (< ~8k poses): ONE WAVEFRONT PER POSE.  The 64 lanes gather 64 beams at a time (8 x 64 in flight),
