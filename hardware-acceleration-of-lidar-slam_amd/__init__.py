@@ -119,6 +119,9 @@ SIGNATURES = {
     "slam_associate_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _i, _vp, _i, _vp]),
     "slam_ekf_update_assoc_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _i, _vp]),
     "slam_assoc_counts": (_i, [_vp, _vp]),
+    "slam_associate_aniso_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _i, _vp, _i, _vp]),
+    "slam_ekf_update_assoc_aniso_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "slam_assoc_aniso_counts": (_i, [_vp, _vp]),
     "slam_landmark_evidence_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "slam_evidence_init_dev": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _i]),
     "slam_evidence_counts": (_i, [_vp, _vp]),
@@ -163,6 +166,7 @@ SIGNATURES = {
     "slam_pf_meas_cov_set": (_i, [_vp, _vp]),
     "slam_pf_assoc_set": (_i, [_vp, _f, _f, _i]),
     "slam_pf_assoc_device_view": (_i, [_vp, _vp, _vp, _vp]),
+    "slam_pf_assoc_cov_set": (_i, [_vp, _vp, _f, _f, _i]),
     "slam_pf_prune_set": (_i, [_vp, _i, _i, _i, _f]),
     "slam_pf_evidence_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_evidence_host": (_i, [_vp, _vp]),
@@ -452,6 +456,26 @@ class Engine:
         """-> (associate launches, assoc-update launches) of this engine so far."""
         c = (C.c_int64 * 2)()
         self._ck(self.lib.slam_assoc_counts(self.h, c), "assoc_counts")
+        return int(c[0]), int(c[1])
+
+    def associate_aniso_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, meas_cov, gate, new_gate, create,
+                            d_assoc, assoc_stride, d_stats):
+        """``slam_associate_aniso_dev``: associate_dev under a 2x2 sensor-frame measurement covariance, meas_cov = (qxx, qxy, qyy)."""
+        self._ck(self.lib.slam_associate_aniso_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x), _ptr(d_y),
+                                                   _ptr(d_th), _ptr(d_anc), n, _f3(meas_cov), gate, new_gate, int(create), _ptr(d_assoc),
+                                                   assoc_stride, _ptr(d_stats)), "associate_aniso_dev")
+
+    def ekf_update_assoc_aniso_dev(self, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, meas_cov,
+                                   d_assoc, assoc_stride, d_loglik):
+        """``slam_ekf_update_assoc_aniso_dev``: ekf_update_aniso_dev with particle i's observations read through its table row."""
+        self._ck(self.lib.slam_ekf_update_assoc_aniso_dev(self.h, _ptr(d_map_in), _ptr(d_map_out), row_stride, plane_stride, nlandmarks,
+                                                          _ptr(d_x), _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, _f3(meas_cov), _ptr(d_assoc),
+                                                          assoc_stride, _ptr(d_loglik)), "ekf_update_assoc_aniso_dev")
+
+    def assoc_aniso_counts(self):
+        """-> (associate launches, assoc-update launches) under a 2x2 covariance of this engine so far."""
+        c = (C.c_int64 * 2)()
+        self._ck(self.lib.slam_assoc_aniso_counts(self.h, c), "assoc_aniso_counts")
         return int(c[0]), int(c[1])
 
     def landmark_evidence_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_anc, n, d_assoc, assoc_stride, d_ev_in,
@@ -968,6 +992,11 @@ class PfSession:
         """``slam_pf_assoc_set``: gate > 0: frames associate the engine's detections themselves (single-GPU rows sessions only);
         gate = 0 switches it off."""
         self.e._ck(self.e.lib.slam_pf_assoc_set(self.h, gate, new_gate, 1 if create else 0), "pf_assoc_set")
+
+    def assoc_cov_set(self, meas_cov, gate: float, new_gate: float = 0.0, create: bool = True):
+        """``slam_pf_assoc_cov_set``: association under the 2x2 sensor-frame covariance (qxx, qxy, qyy) — covariance and gates in one
+        switch; (meas_var, 0, meas_var) is exactly assoc_set(gate, new_gate, create)."""
+        self.e._ck(self.e.lib.slam_pf_assoc_cov_set(self.h, _f3(meas_cov), gate, new_gate, 1 if create else 0), "pf_assoc_cov_set")
 
     def assoc_view(self):
         """``slam_pf_assoc_device_view``: the last frame's table uint8 [n][stride] and stats int32 [n][3], indexed like score."""

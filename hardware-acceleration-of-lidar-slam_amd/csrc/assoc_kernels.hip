@@ -15,8 +15,13 @@
 //   e. a detection that matched nothing and lies within new_gate of no seen landmark (a flag per detection, from a ballot, kept by lane k)
 //      takes the next unseen slot: the ranks come from popcounts over a 64-bit "unseen" mask per 64 landmarks.
 // The particle's table row is assembled in LDS and written out as whole dwords.
+//
+// Under a full 2x2 sensor-frame measurement covariance Q (specification: tests/_assoc_aniso_spec.py) the same two kernels run with
+// S = P + R_w(theta_i): associate_body takes the noise as a policy (AssocNoiseIso: the lines above; AssocNoiseAniso: R_w once per
+// wavefront, S^-1 with the operations of ekf_aniso_update_one), and the update's lane type is EkfAnisoLane with the table as
+// its source of z.
 
-#include "ekf_row_body.h"
+#include "ekf_aniso_lane.h"
 
 namespace slam {
 
@@ -49,8 +54,43 @@ __device__ __forceinline__ void wave_lds_sync()
 
 __device__ __forceinline__ u64 below(unsigned lane) { return (1ull << lane) - 1ull; }   // the lanes in front of this one
 
-template <bool CREATE>
-__global__ __launch_bounds__(kEkfWaves * 64) void associate_kernel(AssocArgs a)
+// The measurement noise of one particle as the association sees it: S^-1 = (P + noise)^-1 of the two landmarks of a lane, in
+// EkfShared's i00 / i01 / i11.
+struct AssocNoiseIso {   // q I: ekf_det_terms without the logarithm, then ekf_shared_from
+    v2f q;
+    __device__ __forceinline__ AssocNoiseIso(float meas_var, float, float) : q(bc2(meas_var)) {}
+    __device__ __forceinline__ EkfShared<v2f> inverse(v2f pxx, v2f pxy, v2f pyy) const
+    {
+        const v2f aa = pxx + q, cc = pyy + q;
+        const v2f det = aa * cc - pxy * pxy;
+        return ekf_shared_from<v2f, false>(pxx, pxy, pyy, q, ekf_rcp(det), bc2(0.0f));
+    }
+};
+struct AssocNoiseAniso {   // R_w = H^T Q H of the particle's heading: the operations of ekf_aniso_update_one, the update's own reciprocal
+    float rxx, rxy, ryy;   // wave-uniform, held in scalar registers
+    __device__ __forceinline__ AssocNoiseAniso(const EkfAnisoCov& q, float s, float c)
+    {
+        float xx, xy, yy;
+        ekf_aniso_world_noise(q, s, c, xx, xy, yy);
+        rxx = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(xx)));
+        rxy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(xy)));
+        ryy = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(yy)));
+    }
+    __device__ __forceinline__ EkfShared<v2f> inverse(v2f pxx, v2f pxy, v2f pyy) const
+    {
+        EkfShared<v2f> h;   // (only S^-1 is filled in)
+        const v2f a = pxx + bc2(rxx), b = pxy + bc2(rxy), cc = pyy + bc2(ryy);
+        const v2f det = a * cc - b * b;
+        const v2f idet = ekf_rcp(det);
+        h.i00 = cc * idet;
+        h.i01 = -b * idet;
+        h.i11 = a * idet;
+        return h;
+    }
+};
+
+// NOISE(qp, sine, cosine): one of the two above; qp: meas_var, or Q
+template <bool CREATE, class NOISE, class QP> __device__ __forceinline__ void associate_body(const AssocArgs& a, const QP& qp)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const unsigned lane = threadIdx.x & 63u;
@@ -81,7 +121,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void associate_kernel(AssocArgs a)
     float wxk, wyk;
     ekf_first_sighting<float>(zxk, zyk, st, ct, px, py, wxk, wyk);
 
-    const v2f q = bc2(a.meas_var);
+    const NOISE noise(qp, st, ct);
     const float inf = __uint_as_float(0x7f800000u);
     bool near = false;   // lane k: some seen landmark lies within new_gate of detection k
     for (unsigned b = 0; b < lds.batches; ++b) {
@@ -106,10 +146,8 @@ __global__ __launch_bounds__(kEkfWaves * 64) void associate_kernel(AssocArgs a)
             // a landmark that takes no part: NaN in its mean makes every m NaN, and NaN passes none of the comparisons below
             mx[t] = seen[t] ? mx[t] : __uint_as_float(0x7fc00000u);
         }
-        // b. (P + q I)^-1: ekf_det_terms without the logarithm, then ekf_shared_from
-        const v2f aa = pxx + q, cc = pyy + q;
-        const v2f det = aa * cc - pxy * pxy;
-        const EkfShared<v2f> h = ekf_shared_from<v2f, false>(pxx, pxy, pyy, q, ekf_rcp(det), bc2(0.0f));
+        // b. S^-1, once per landmark
+        const EkfShared<v2f> h = noise.inverse(pxx, pxy, pyy);
         // c. the cheapest detection of each landmark
         v2f best = bc2(inf);
         unsigned bk[2] = { 0u, 0u };
@@ -179,15 +217,27 @@ __global__ __launch_bounds__(kEkfWaves * 64) void associate_kernel(AssocArgs a)
     }
 }
 
+template <bool CREATE> __global__ __launch_bounds__(kEkfWaves * 64) void associate_kernel(AssocArgs a)
+{
+    associate_body<CREATE, AssocNoiseIso>(a, a.meas_var);
+}
+
+// ... under S = P + R_w (a.meas_var is not read)
+template <bool CREATE> __global__ __launch_bounds__(kEkfWaves * 64) void associate_aniso_kernel(AssocArgs a, EkfAnisoCov q)
+{
+    associate_body<CREATE, AssocNoiseAniso>(a, q);
+}
+
 // ------------------------------------------------------------------ the landmark update under a per-particle table
-// EkfLane whose observation of landmark l is det[assoc[i][l]]: lane k of the wavefront holds detection k (NaN from ndet on), the
+// A lane type (EkfLane; EkfAnisoLane) whose observation of landmark l is det[assoc[i][l]]: lane k of the wavefront holds detection k (NaN from ndet on), the
 // table byte is read alongside the row and the detection comes from a lane read — no second trip to memory.
-struct EkfAssocLane : EkfLane {
+template <class BASE> struct EkfAssocLaneT : BASE {
     const gchar* arow;   // the particle's table row (wave-uniform)
     float detx, dety;    // THIS lane's detection
 };
+typedef EkfAssocLaneT<EkfLane> EkfAssocLane;
 
-__device__ __forceinline__ void ekf_obs(const EkfAssocLane& w, unsigned l, bool in, float& vx, float& vy)
+template <class BASE> __device__ __forceinline__ void ekf_obs(const EkfAssocLaneT<BASE>& w, unsigned l, bool in, float& vx, float& vy)
 {
     const float nan = __uint_as_float(0x7fc00000u);
     const unsigned k = *(const guchar*)(w.arow + (in ? l : 0u));   // clamped index: the caller discards what lanes beyond L get
@@ -226,14 +276,55 @@ __global__ __launch_bounds__(kEkfWaves * 64) void ekf_assoc_kernel(EkfArgs a, Ek
     if (lane == 0) store_loglik(a, i, total);
 }
 
+// ... with R_w and det Q in the place of q: EkfAnisoLane's arithmetic (a first sighting stores P = R_w), the table's observations
+template <int NB, bool COPY>
+__global__ __launch_bounds__(kEkfWaves * 64) void ekf_assoc_aniso_kernel(EkfArgs a, EkfAssocTable tab, EkfAnisoCov q)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int i = xcd_block(a.xcd_chunk) * kEkfWaves + wave;
+    if (i >= a.n) return;
+    const int src = a.anc ? a.anc[i] : i;
+    float st_, ct_, rxx, rxy, ryy;
+    det_sincosf(a.th[i], st_, ct_);
+    ekf_aniso_world_noise(q, st_, ct_, rxx, rxy, ryy);
+    const float nan = __uint_as_float(0x7fc00000u);
+    EkfAssocLaneT<EkfAnisoLane> w;
+    const int row_bytes = __builtin_amdgcn_readfirstlane(5 * a.plane_stride * 4);
+    w.rin = row_rsrc(a.map_in, src, a.row_stride, row_bytes);
+    w.p.rout = row_rsrc(a.map_out, i, a.row_stride, row_bytes);
+    w.pl = __builtin_amdgcn_readfirstlane(a.plane_stride * 4);
+    w.ozx = nullptr;
+    w.ozy = nullptr;
+    w.L = (unsigned)a.nlandmarks;
+    w.p.s = bc2(st_); w.p.c = bc2(ct_); w.p.px = bc2(a.x[i]); w.p.py = bc2(a.y[i]);
+    w.rxx = bc2(rxx); w.rxy = bc2(rxy); w.ryy = bc2(ryy); w.detq = bc2(q.detq);
+    w.arow = uniform_gptr(tab.assoc + (size_t)i * (size_t)tab.assoc_stride);
+    w.detx = (int)lane < tab.ndet ? tab.det_zx[lane] : nan;
+    w.dety = (int)lane < tab.ndet ? tab.det_zy[lane] : nan;
+
+    const float total = ekf_row_walk<NB, COPY>(w, (unsigned)a.plane_stride, lane);
+    if (lane == 0) store_loglik(a, i, total);
+}
+
+// the shapes the LDS carve and the row accesses of the associating kernels are sized by
+bool assoc_args_ok(const AssocArgs& a)
+{
+    return !(a.nlandmarks < 0 || a.nlandmarks > SLAM_MAX_OBS || a.ndet < 0 || a.ndet > SLAM_MAX_DETECTIONS ||
+             a.assoc_stride < a.nlandmarks || a.plane_stride < a.nlandmarks);
+}
+
+bool ekf_assoc_args_ok(const EkfArgs& a, const EkfAssocTable& tab)   // rows only
+{
+    return !(a.cov || tab.assoc_stride < a.nlandmarks || tab.ndet < 0 || tab.ndet > SLAM_MAX_DETECTIONS);
+}
+
 }  // namespace
 
 hipError_t launch_associate(hipStream_t stream, const AssocArgs& a_in, bool create, const EventPair* ev)
 {
     if (a_in.n <= 0) return hipSuccess;
-    if (a_in.nlandmarks < 0 || a_in.nlandmarks > SLAM_MAX_OBS || a_in.ndet < 0 || a_in.ndet > SLAM_MAX_DETECTIONS ||
-        a_in.assoc_stride < a_in.nlandmarks || a_in.plane_stride < a_in.nlandmarks)
-        return hipErrorInvalidValue;   // what the LDS carve and the row accesses are sized by
+    if (!assoc_args_ok(a_in)) return hipErrorInvalidValue;
     AssocArgs a = a_in;
     const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
     const size_t lds = (size_t)kEkfWaves * assoc_lds((unsigned)a.nlandmarks).per_wave;   // at most 4 x 9 792 bytes
@@ -247,7 +338,7 @@ hipError_t launch_associate(hipStream_t stream, const AssocArgs& a_in, bool crea
 hipError_t launch_ekf_assoc(hipStream_t stream, const EkfArgs& a_in, const EkfAssocTable& tab, const EventPair* ev)
 {
     if (a_in.n <= 0) return hipSuccess;
-    if (a_in.cov || tab.assoc_stride < a_in.nlandmarks || tab.ndet < 0 || tab.ndet > SLAM_MAX_DETECTIONS) return hipErrorInvalidValue;   // rows only
+    if (!ekf_assoc_args_ok(a_in, tab)) return hipErrorInvalidValue;
     EkfArgs a = a_in;
     const bool copy = a.map_in != a.map_out;   // in place: rows without an association stay as they are
     // batches per pass: those of ekf_update_kernel (launch_ekf_update, its form 0) at the same shapes
@@ -257,6 +348,38 @@ hipError_t launch_ekf_assoc(hipStream_t stream, const EkfArgs& a_in, const EkfAs
     const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
     if (ev) (void)hipEventRecord(ev->start, stream);
     kernel<<<blocks, kEkfWaves * 64, 0, stream>>>(a, tab);
+    if (ev) (void)hipEventRecord(ev->stop, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_associate_aniso(hipStream_t stream, const AssocArgs& a_in, const EkfAnisoCov& q, bool create, const EventPair* ev)
+{
+    if (a_in.n <= 0) return hipSuccess;
+    if (!assoc_args_ok(a_in) || !ekf_aniso_cov_ok(q)) return hipErrorInvalidValue;
+    AssocArgs a = a_in;
+    const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
+    const size_t lds = (size_t)kEkfWaves * assoc_lds((unsigned)a.nlandmarks).per_wave;
+    if (ev) (void)hipEventRecord(ev->start, stream);
+    if (create) associate_aniso_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
+    else associate_aniso_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
+    if (ev) (void)hipEventRecord(ev->stop, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_ekf_assoc_aniso(hipStream_t stream, const EkfArgs& a_in, const EkfAssocTable& tab, const EkfAnisoCov& q,
+                                  const EventPair* ev)
+{
+    if (a_in.n <= 0) return hipSuccess;
+    if (!ekf_assoc_args_ok(a_in, tab) || !ekf_aniso_cov_ok(q)) return hipErrorInvalidValue;
+    EkfArgs a = a_in;
+    const bool copy = a.map_in != a.map_out;
+    // batches per pass: launch_ekf_assoc's
+    void (*kernel)(EkfArgs, EkfAssocTable, EkfAnisoCov);
+    if (!copy) kernel = a.nlandmarks > 128 ? ekf_assoc_aniso_kernel<4, false> : ekf_assoc_aniso_kernel<1, false>;
+    else kernel = a.nlandmarks > 128 ? ekf_assoc_aniso_kernel<2, true> : ekf_assoc_aniso_kernel<1, true>;
+    const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
+    if (ev) (void)hipEventRecord(ev->start, stream);
+    kernel<<<blocks, kEkfWaves * 64, 0, stream>>>(a, tab, q);
     if (ev) (void)hipEventRecord(ev->stop, stream);
     return hipGetLastError();
 }

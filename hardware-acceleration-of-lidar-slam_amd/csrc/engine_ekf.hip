@@ -1,7 +1,7 @@
 // engine_ekf.hip — the landmark side of a particle-filter frame behind the C ABI: motion sample (alone, or with the score of
 // the sampled poses), the observation table, the landmark update in every form (in place, out of place, split layout, fused
 // with motion + score as the frame's front launch), the switches and counters of those forms, data association (the frame's
-// detections, the association stage and the update under a per-particle table), the detector that makes the detections from
+// detections, the association stage and the update under a per-particle table, with meas_var * I or a 2x2 Q), the detector that makes the detections from
 // the scan, and the landmarks' existence evidence.
 
 #include <hip/hip_runtime.h>
@@ -262,6 +262,15 @@ int slam_ekf_update_dev(slam_engine* e, const float* d_map_in, float* d_map_out,
     return SLAM_OK;
 }
 
+// meas_cov as the 2x2 stages accept it; leaves the reason behind otherwise
+static bool aniso_cov_from(slam_engine* e, const float meas_cov[3], EkfAnisoCov* q)
+{
+    *q = ekf_aniso_cov(meas_cov);
+    if (ekf_aniso_cov_ok(*q)) return true;
+    snprintf(e->err, sizeof e->err, "meas_cov must be finite with qxx > 0, qyy > 0 and qxx * qyy - qxy * qxy > 0 in float32");
+    return false;
+}
+
 int slam_ekf_update_aniso_dev(slam_engine* e, const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride,
                               int nlandmarks, const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc, int n,
                               const float meas_cov[3], float* d_loglik)
@@ -270,11 +279,8 @@ int slam_ekf_update_aniso_dev(slam_engine* e, const float* d_map_in, float* d_ma
     if (n < 0 || nlandmarks < 0 || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride || !meas_cov ||
         (n > 0 && (!d_map_in || !d_map_out || !d_x || !d_y || !d_th)))
         return SLAM_ERR_INVALID_ARG;
-    const EkfAnisoCov q = ekf_aniso_cov(meas_cov);
-    if (!ekf_aniso_cov_ok(q)) {
-        snprintf(e->err, sizeof e->err, "meas_cov must be finite with qxx > 0, qyy > 0 and qxx * qyy - qxy * qxy > 0 in float32");
-        return SLAM_ERR_INVALID_ARG;
-    }
+    EkfAnisoCov q;
+    if (!aniso_cov_from(e, meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
     if (d_anc && d_map_in == d_map_out) return SLAM_ERR_INVALID_ARG;
     if (e->obs_nlandmarks < 0 || e->obs_nlandmarks != nlandmarks) return SLAM_ERR_NOT_READY;
     if (n == 0) return SLAM_OK;
@@ -336,18 +342,20 @@ int slam_detections_set_dev(slam_engine* e, const float* d_zx, const float* d_zy
     return SLAM_OK;
 }
 
-int slam_associate_dev(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
-                       const float* d_y, const float* d_th, const int32_t* d_anc, int n, float meas_var, float gate, float new_gate,
-                       int create, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
+// the argument checks the two associating stages share (everything but the measurement noise)
+static bool associate_args_ok(const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x, const float* d_y,
+                              const float* d_th, int n, float gate, float new_gate, int create, const uint8_t* d_assoc, int assoc_stride)
 {
-    SLAM_ENTER(e);
-    if (int rc = slam_engine_resolve_detections(e)) return rc;
-    if (n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
-        assoc_stride < nlandmarks || !(meas_var > 0.0f) || !(gate > 0.0f && gate <= std::numeric_limits<float>::max()) ||
-        !(new_gate >= gate) || (create != 0 && create != 1) || (n > 0 && (!d_map || !d_x || !d_y || !d_th || !d_assoc)))
-        return SLAM_ERR_INVALID_ARG;
-    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
-    if (n == 0) return SLAM_OK;
+    return !(n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
+             assoc_stride < nlandmarks || !(gate > 0.0f && gate <= std::numeric_limits<float>::max()) || !(new_gate >= gate) ||
+             (create != 0 && create != 1) || (n > 0 && (!d_map || !d_x || !d_y || !d_th || !d_assoc)));
+}
+
+// ... and what they put into an AssocArgs alike: the caller's rows, poses, gather index and table, the engine's detections
+static AssocArgs assoc_args(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                            const float* d_y, const float* d_th, const int32_t* d_anc, int n, float meas_var, float gate, float new_gate,
+                            uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
+{
     AssocArgs a;
     a.map = d_map;
     a.row_stride = row_stride;
@@ -368,8 +376,45 @@ int slam_associate_dev(slam_engine* e, const float* d_map, int64_t row_stride, i
     a.assoc_stride = assoc_stride;
     a.stats = d_stats;
     a.xcd_chunk = 0;
+    return a;
+}
+
+int slam_associate_dev(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                       const float* d_y, const float* d_th, const int32_t* d_anc, int n, float meas_var, float gate, float new_gate,
+                       int create, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
+{
+    SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (!associate_args_ok(d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, n, gate, new_gate, create, d_assoc, assoc_stride) ||
+        !(meas_var > 0.0f))
+        return SLAM_ERR_INVALID_ARG;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    const AssocArgs a = assoc_args(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, meas_var, gate, new_gate,
+                                   d_assoc, assoc_stride, d_stats);
     SLAM_HIP_TRY(e, launch_associate(e->stream, a, create != 0, e->prof_next(SLAM_PROF_PAGES)));
     e->assoc_launches[0]++;
+    return SLAM_OK;
+}
+
+int slam_associate_aniso_dev(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                             const float* d_y, const float* d_th, const int32_t* d_anc, int n, const float meas_cov[3], float gate,
+                             float new_gate, int create, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
+{
+    SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (!associate_args_ok(d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, n, gate, new_gate, create, d_assoc, assoc_stride) ||
+        !meas_cov)
+        return SLAM_ERR_INVALID_ARG;
+    EkfAnisoCov q;
+    if (!aniso_cov_from(e, meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    // (meas_var of the arguments is not read by this form)
+    const AssocArgs a = assoc_args(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, 0.0f, gate, new_gate, d_assoc,
+                                   assoc_stride, d_stats);
+    SLAM_HIP_TRY(e, launch_associate_aniso(e->stream, a, q, create != 0, e->prof_next(SLAM_PROF_PAGES)));
+    e->assoc_aniso_launches[0]++;
     return SLAM_OK;
 }
 
@@ -392,6 +437,39 @@ int slam_ekf_update_assoc_dev(slam_engine* e, const float* d_map_in, float* d_ma
     SLAM_HIP_TRY(e, launch_ekf_assoc(e->stream, a, tab, e->prof_next(SLAM_PROF_EKF)));
     e->assoc_launches[1]++;
     e->ll_n = n;
+    return SLAM_OK;
+}
+
+int slam_ekf_update_assoc_aniso_dev(slam_engine* e, const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride,
+                                    int nlandmarks, const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc, int n,
+                                    const float meas_cov[3], const uint8_t* d_assoc, int assoc_stride, float* d_loglik)
+{
+    SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
+        assoc_stride < nlandmarks || !meas_cov || (n > 0 && (!d_map_in || !d_map_out || !d_x || !d_y || !d_th || !d_assoc)))
+        return SLAM_ERR_INVALID_ARG;
+    EkfAnisoCov q;
+    if (!aniso_cov_from(e, meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
+    if (d_anc && d_map_in == d_map_out) return SLAM_ERR_INVALID_ARG;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
+    // (neither the observation table nor meas_var of the arguments is read by this form)
+    const EkfArgs a = ekf_args(e, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, 0.0f, d_loglik);
+    const EkfAssocTable tab{ d_assoc, assoc_stride, e->d_det_zx, e->d_det_zy, e->ndet };
+    SLAM_HIP_TRY(e, launch_ekf_assoc_aniso(e->stream, a, tab, q, e->prof_next(SLAM_PROF_EKF)));
+    e->assoc_aniso_launches[1]++;
+    e->ll_n = n;
+    return SLAM_OK;
+}
+
+int slam_assoc_aniso_counts(slam_engine* e, int64_t counts[2])
+{
+    SLAM_ENTER(e);
+    if (!counts) return SLAM_ERR_INVALID_ARG;
+    counts[0] = e->assoc_aniso_launches[0];
+    counts[1] = e->assoc_aniso_launches[1];
     return SLAM_OK;
 }
 

@@ -88,6 +88,7 @@ struct slam_engine {
     int ndet = -1;
     const float *d_det_zx = nullptr, *d_det_zy = nullptr;
     int64_t assoc_launches[2] = { 0, 0 };   // slam_assoc_counts: associate launches, assoc-update launches (in no form counter)
+    int64_t assoc_aniso_launches[2] = { 0, 0 };   // slam_assoc_aniso_counts: the same two under a 2x2 Q (in no other counter)
     int64_t evidence_launches[2] = { 0, 0 };   // slam_evidence_counts: evidence launches, init launches (in no other counter)
     // the detector (slam_detect_scan_dev): its kernel writes det_buf and leaves {ndet, sequence} in mapped host memory; until the
     // next stage that needs the count on the host has picked it up (slam_engine_resolve_detections) it is PENDING

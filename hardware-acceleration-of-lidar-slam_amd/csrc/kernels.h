@@ -233,6 +233,12 @@ struct EkfAssocTable {
 // the row update of launch_ekf_update's one-wavefront-per-particle form under such a table (a.obs_zx / a.obs_zy are not read;
 // a.cov must be null): out of place through a.anc, or in place (only landmarks with an association touched)
 hipError_t launch_ekf_assoc(hipStream_t stream, const EkfArgs& a, const EkfAssocTable& t, const EventPair* ev = nullptr);
+// Both under a full 2x2 sensor-frame measurement covariance (specification: tests/_assoc_aniso_spec.py): every particle gates,
+// matches, creates and updates with S = P + R_w(theta_i); a.meas_var is not read.  The argument checks of the two above and
+// ekf_aniso_cov_ok(q).
+hipError_t launch_associate_aniso(hipStream_t stream, const AssocArgs& a, const EkfAnisoCov& q, bool create, const EventPair* ev = nullptr);
+hipError_t launch_ekf_assoc_aniso(hipStream_t stream, const EkfArgs& a, const EkfAssocTable& t, const EkfAnisoCov& q,
+                                  const EventPair* ev = nullptr);
 // ---- evidence_kernels.hip: landmark existence evidence (specification: tests/_evidence_spec.py).  One byte
 // c in [0, cmax] per (particle, landmark slot) beside the rows; behind the update of a frame a matched landmark gains `hit`, a
 // visible unmatched one loses `miss`, and one that cannot pay is pruned: its slot gets the bits of a slot that was never used.

@@ -145,6 +145,10 @@ struct slam_pf {
     bool assoc_on = false;
     float assoc_gate = 0.0f, assoc_new_gate = 0.0f;
     int assoc_create = 0;
+    // slam_pf_assoc_cov_set: association under a full 2x2 Q — the same frames with slam_associate_aniso_dev and
+    // slam_ekf_update_assoc_aniso_dev as the two launches (assoc_cov is read only while assoc_aniso is set; `aniso` above stays false)
+    bool assoc_aniso = false;
+    float assoc_cov[3] = { 0.0f, 0.0f, 0.0f };
     uint8_t* assoc_tab = nullptr;     // [n][Lp] the last frame's table, indexed like `score`; made by the first slam_pf_assoc_set
     int32_t* assoc_stats = nullptr;   // [n][3], behind the table in the same allocation
     // slam_pf_prune_set (only while association is on): one evidence byte per (particle, landmark slot) beside the rows, brought up
@@ -1100,11 +1104,17 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
         if (pf->assoc_on) {   // detections without identity: the observation table is not read
             float* out = pf->map[f.in_place ? mc : mn];
             const int32_t* anc = f.in_place ? nullptr : f.anc;
-            if (int rc = slam_associate_dev(e, pf->map[mc], stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->cfg.meas_var,
-                                            pf->assoc_gate, pf->assoc_new_gate, pf->assoc_create, pf->assoc_tab, pf->Lp, pf->assoc_stats))
+            if (int rc = pf->assoc_aniso
+                             ? slam_associate_aniso_dev(e, pf->map[mc], stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->assoc_cov,
+                                                        pf->assoc_gate, pf->assoc_new_gate, pf->assoc_create, pf->assoc_tab, pf->Lp,
+                                                        pf->assoc_stats)
+                             : slam_associate_dev(e, pf->map[mc], stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->cfg.meas_var,
+                                                  pf->assoc_gate, pf->assoc_new_gate, pf->assoc_create, pf->assoc_tab, pf->Lp, pf->assoc_stats))
                 return rc;
-            if (int rc = slam_ekf_update_assoc_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n,
-                                                   pf->cfg.meas_var, pf->assoc_tab, pf->Lp, nullptr))
+            if (int rc = pf->assoc_aniso ? slam_ekf_update_assoc_aniso_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn,
+                                                                           anc, n, pf->assoc_cov, pf->assoc_tab, pf->Lp, nullptr)
+                                         : slam_ekf_update_assoc_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n,
+                                                                     pf->cfg.meas_var, pf->assoc_tab, pf->Lp, nullptr))
                 return rc;
             // existence evidence, on the row the update wrote: through the frame's gather into the other buffer, or in place
             if (pf->prune_on)
@@ -1662,7 +1672,8 @@ int slam_pf_meas_cov_set(slam_pf* pf, const float meas_cov[3])
     const bool iso = meas_cov[0] == pf->cfg.meas_var && meas_cov[1] == 0.0f && meas_cov[2] == pf->cfg.meas_var;
     if (pf->assoc_on && !iso) {
         snprintf(pf->e->err, sizeof pf->e->err, "data association is on (slam_pf_assoc_set): it gates with meas_var * I, a 2x2 "
-                                                "measurement covariance cannot be set");
+                                                "measurement covariance cannot be set (slam_pf_assoc_cov_set sets covariance and "
+                                                "gates together)");
         return SLAM_ERR_INVALID_ARG;
     }
     for (int k = 0; k < 3; ++k) pf->meas_cov[k] = meas_cov[k];
@@ -1677,6 +1688,7 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
     slam_engine* e = pf->e;
     if (gate == 0.0f) {   // off: the session runs exactly what it ran before the first call (pruning and the detector go off with it)
         pf->assoc_on = false;
+        pf->assoc_aniso = false;
         pf->prune_on = false;
         pf->detect_on = false;
         return SLAM_OK;
@@ -1705,9 +1717,30 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
         SLAM_HIP_TRY(e, hipMemsetAsync(pf->assoc_stats, 0, st, e->stream));
     }
     pf->assoc_on = true;
+    pf->assoc_aniso = false;   // (slam_pf_assoc_cov_set behind this call says otherwise)
     pf->assoc_gate = gate;
     pf->assoc_new_gate = new_gate;
     pf->assoc_create = create;
+    return SLAM_OK;
+}
+
+int slam_pf_assoc_cov_set(slam_pf* pf, const float meas_cov[3], float gate, float new_gate, int create)
+{
+    if (!pf || !meas_cov) return SLAM_ERR_INVALID_ARG;
+    if (!ekf_aniso_cov_ok(ekf_aniso_cov(meas_cov))) {
+        snprintf(pf->e->err, sizeof pf->e->err, "meas_cov must be finite with qxx > 0, qyy > 0 and qxx * qyy - qxy * qxy > 0 in float32");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (gate == 0.0f) {   // slam_pf_assoc_set(0, ..) is the switch-off: here a gate has to be given
+        snprintf(pf->e->err, sizeof pf->e->err, "association needs a finite gate > 0 (slam_pf_assoc_set(0, ..) switches it off)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    // the conditions, the refusals and the table of the isotropic switch; a refused call leaves the session as it was
+    if (int rc = slam_pf_assoc_set(pf, gate, new_gate, create)) return rc;
+    // {meas_var, 0, meas_var}: exactly slam_pf_assoc_set — the isotropic kernels, the same bits
+    const bool iso = meas_cov[0] == pf->cfg.meas_var && meas_cov[1] == 0.0f && meas_cov[2] == pf->cfg.meas_var;
+    for (int k = 0; k < 3; ++k) pf->assoc_cov[k] = meas_cov[k];
+    pf->assoc_aniso = !iso;
     return SLAM_OK;
 }
 

@@ -31,7 +31,8 @@
  *   --same-device  every rank on device 0 (only with the local transport; RCCL refuses two ranks on one GPU)
  *   --landmarks L  the session is made on rows (SLAM_MAP_ROWS) with L landmark slots per particle; one GPU.  Without it the
  *                  filter keeps no landmarks and the options below are refused
- *   --assoc GATE NEW_GATE  data association (slam_pf_assoc_set, create = 1): frames read the engine's detections
+ *   --assoc GATE NEW_GATE  data association (slam_pf_assoc_set, create = 1): frames read the engine's detections.  Together
+ *                  with --meas-cov and --landmarks: association under that covariance (slam_pf_assoc_cov_set, one call for both)
  *   --prune HIT MISS CMAX RANGE  existence evidence and pruning of clutter landmarks (slam_pf_prune_set)
  *   --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]  the detector (slam_pf_detect_set; no values: slam_detect_params_default):
  *                  every frame makes its detections from its own scan, so the landmark map grows from nothing but lidar frames
@@ -135,7 +136,11 @@ static void *rank_main(void *arg)
         CHECK(slam_pf_create(eng, &cfg, &pf));
     }
     if (run->refine_sweeps) CHECK(slam_pf_refine_set(pf, run->refine_res[0], run->refine_res[1], run->refine_sweeps));
-    if (run->use_meas_cov) {
+    /* --assoc and --meas-cov with landmarks: one switch sets covariance and gates together (each of the two separate switches
+     * refuses the other) */
+    const int assoc_cov = run->use_assoc && run->use_meas_cov && run->landmarks > 0;
+    if (assoc_cov) CHECK(slam_pf_assoc_cov_set(pf, run->meas_cov, run->assoc_gate[0], run->assoc_gate[1], 1));
+    if (run->use_meas_cov && !assoc_cov) {
         /* Without --landmarks this program's filter keeps none (n_landmarks = 0): a session without them has no covariance to
          * apply the matrix to and says so (the values themselves were checked in main).  That is reported, not fatal: the run
          * goes on as it would on rows.  With landmarks the call's result is checked. */
@@ -144,7 +149,7 @@ static void *rank_main(void *arg)
         else if (rank == 0) fprintf(stderr, "--meas-cov has no effect here: %s\n", slam_last_error(eng));
     }
     /* the landmark pipeline: association reads detections, the detector makes them from each frame's scan */
-    if (run->use_assoc) CHECK(slam_pf_assoc_set(pf, run->assoc_gate[0], run->assoc_gate[1], 1));
+    if (run->use_assoc && !assoc_cov) CHECK(slam_pf_assoc_set(pf, run->assoc_gate[0], run->assoc_gate[1], 1));
     if (run->use_prune) CHECK(slam_pf_prune_set(pf, run->prune[0], run->prune[1], run->prune[2], run->prune_range));
     if (run->use_detect) CHECK(slam_pf_detect_set(pf, &run->detect));
     const int observe = run->landmarks > 0 && run->use_assoc && run->use_detect;   /* else: no frame has observations */
@@ -342,7 +347,7 @@ int main(int argc, char **argv)
                         "  [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]]] "
                         "[--landmarks-out FILE]]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
-                        "              without --landmarks\n"
+                        "              without --landmarks; with --landmarks and --assoc the association gates and updates under it\n"
                         "  --landmarks: L landmark slots per particle on rows, one GPU; --assoc, --prune, --detect and --landmarks-out need it.\n"
                         "              With --assoc and --detect every frame makes its detections from its own scan\n", argv[0]);
         return 2;

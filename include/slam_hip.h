@@ -339,6 +339,29 @@ int slam_ekf_update_assoc_dev(slam_engine *e, const float *d_map_in, float *d_ma
                               int nlandmarks, const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc,
                               int n, float meas_var, const uint8_t *d_assoc, int assoc_stride, float *d_loglik);
 int slam_assoc_counts(slam_engine *e, int64_t counts[2]);
+/* DATA ASSOCIATION UNDER A 2x2 MEASUREMENT COVARIANCE.  The two stages above gate and update with meas_var * I; these are the
+ * same two stages for the Q of slam_ekf_update_aniso_dev (meas_cov = {qxx, qxy, qyy} in the sensor frame, the same conditions):
+ * every particle gates, matches, creates and updates with S = P + R_w(theta_i), R_w = H^T Q H of its own heading.
+ * slam_associate_aniso_dev is slam_associate_dev with step b reading m(l, k) = d^T (P + R_w)^-1 d — the very Mahalanobis term of
+ * slam_ekf_update_aniso_dev's likelihood, same operations, the same reciprocal; steps a and c .. e, the table, the stats and the
+ * rows (not written) are unchanged.  slam_ekf_update_assoc_aniso_dev is slam_ekf_update_aniso_dev with particle i's own
+ * observation list read through its table row, as slam_ekf_update_assoc_dev reads it: a landmark the association created starts
+ * with mean = w_k and P = R_w(theta_i) of the particle that created it, no likelihood term.  Operation order:
+ * tests/_assoc_aniso_spec.py.
+ * Errors: the union of the parents'.  SLAM_ERR_INVALID_ARG, nothing launched: a meas_cov that slam_ekf_update_aniso_dev refuses
+ * (slam_last_error: "meas_cov must be finite ..."), and whatever slam_associate_dev / slam_ekf_update_assoc_dev refuse.
+ * SLAM_ERR_NOT_READY: no detections were handed over; a detector's pending count is picked up first, as there.
+ * Timing: the association is bracketed as SLAM_PROF_PAGES, the update as SLAM_PROF_EKF.  The launches are counted by
+ * slam_assoc_aniso_counts (counts[0] associate, counts[1] update) and by no other counter — not slam_assoc_counts, not
+ * slam_ekf_aniso_count, none of the form counters. */
+int slam_associate_aniso_dev(slam_engine *e, const float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                             const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc, int n,
+                             const float meas_cov[3] /* qxx, qxy, qyy */, float gate, float new_gate, int create,
+                             uint8_t *d_assoc, int assoc_stride, int32_t *d_stats /* may be NULL */);
+int slam_ekf_update_assoc_aniso_dev(slam_engine *e, const float *d_map_in, float *d_map_out, int64_t row_stride, int plane_stride,
+                                    int nlandmarks, const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc,
+                                    int n, const float meas_cov[3], const uint8_t *d_assoc, int assoc_stride, float *d_loglik);
+int slam_assoc_aniso_counts(slam_engine *e, int64_t counts[2]);
 /* EXISTENCE EVIDENCE.  A detector produces false detections; with association alone each one that lies far from every landmark
  * takes an unseen slot and keeps it for good.  Every particle therefore keeps one EVIDENCE byte c in [0, cmax] per landmark slot
  * beside its row (uint8 [rows][ev_stride]); the counter goes up when the landmark is matched, down when it should have been
@@ -722,6 +745,19 @@ int slam_pf_meas_cov_set(slam_pf *pf, const float meas_cov[3]);
  * frame, indexed like slam_pf_view.score (BEFORE the pending gather); SLAM_ERR_NOT_READY until association was switched on. */
 int slam_pf_assoc_set(slam_pf *pf, float gate, float new_gate, int create);
 int slam_pf_assoc_device_view(slam_pf *pf, const uint8_t **assoc, int32_t *assoc_stride, const int32_t **stats);
+/* Data association under a 2x2 measurement covariance inside the session: ONE switch that sets covariance and gates together
+ * (slam_associate_aniso_dev + slam_ekf_update_assoc_aniso_dev with meas_cov in every observing frame).  The conditions of
+ * slam_pf_assoc_set (single-GPU rows, n_landmarks > 0 and <= SLAM_MAX_OBS, the gates' rules; gate == 0 is refused here: off is
+ * slam_pf_assoc_set(0, ..)) and those of slam_pf_meas_cov_set on meas_cov; refused, like slam_pf_assoc_set, while a non-isotropic
+ * slam_pf_meas_cov_set is in force — there is one way in, and the session never holds two matrices that could disagree.  It
+ * allocates the table as slam_pf_assoc_set does, and everything that accepts an associating session accepts this one
+ * (slam_pf_prune_set, slam_pf_detect_set, slam_pf_assoc_device_view, refinement, the resample gate's in-place frames); no frame
+ * goes out as a fused front launch.  meas_cov = {cfg.meas_var, 0, cfg.meas_var} is exactly slam_pf_assoc_set(gate, new_gate,
+ * create): the isotropic kernels, the same bits.  While it is on, slam_pf_meas_cov_set(non-isotropic) stays refused (association
+ * is on), slam_pf_assoc_set(gate > 0, ..) returns the session to isotropic association and slam_pf_assoc_set(0, ..) switches
+ * association off.  Not implemented: the split, paged, AUTO and sharded forms, an evidence stage fused into the update, more than
+ * SLAM_MAX_DETECTIONS detections. */
+int slam_pf_assoc_cov_set(slam_pf *pf, const float meas_cov[3], float gate, float new_gate, int create);
 /* Pruning of clutter landmarks inside the session (slam_landmark_evidence_dev behind every associating update).  Accepted only
  * while association is on — so never off single-GPU rows: otherwise SLAM_ERR_INVALID_ARG (slam_last_error says why) and the
  * session goes on as before; likewise for hit, miss or cmax outside 1 .. 255 or a view_range that is not finite and > 0.
