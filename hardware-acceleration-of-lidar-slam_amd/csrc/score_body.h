@@ -17,8 +17,16 @@ constexpr int kScoreBlock = 256;
 //  LPP 1: one lane walks all beams of its pose.  Best when there are enough poses to fill the chip (>= ~128k).
 //  LPP 4: a quad of lanes shares a pose, lane q takes beams 4j+q.  The reference's sequential float sum
 //         is kept exactly: after each step every lane of the quad adds the four hits in beam order,
-//         fetched with DPP quad broadcasts (v_add_f32 ... quad_perm:[k,k,k,k]) — no LDS, no extra
-//         rounding.  4x the wavefronts and 4x the gathers in flight: 1.5x faster at 64k poses, where
+//         fetched with DPP quad broadcasts — no LDS, no extra rounding.  The broadcast rides inside the
+//         add (v_add_f32_dpp ... quad_perm:[k,k,k,k]: four vector instructions per hit) only where the
+//         compiler's DPP combiner finds the v_mov_b32_dpp and the add that consumes it in ONE basic block;
+//         the moves are convergent and stay where they are written, the adds are not.  Two things used
+//         to part them (eight instructions per hit: profiles/r08_score_sum.md): a cell offset computed
+//         under a branch cut the round into a dozen blocks and the adds sank to its last one, and the
+//         adds of the epilogue sank into the `sub == 0` block of the final store.  Hence the branch-free
+//         offset in beam2, the scheduling barrier behind every pipeline step and the opaque `total` in
+//         front of the store.
+//         4x the wavefronts and 4x the gathers in flight: 1.5x faster at 64k poses, where
 //         LPP 1 has a single wave per SIMD and is latency-bound; slower beyond ~128k poses (each wave
 //         gather then touches 4 beam neighbourhoods instead of 1).
 // Both forms run the same software pipeline: DEPTH gathers stay in flight per lane and the hits of step s are summed
@@ -182,10 +190,13 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
             asm("v_cvt_i32_f32 %0, %1" : "=v"(iy) : "v"(fy[e]));
             const bool in = (unsigned)(ix - 1) < lim_x && (unsigned)(iy - 1) < lim_y;
             if constexpr (PACKED) {
-                const unsigned off = in ? __umul24((unsigned)ix >> 4, strip) + (((unsigned)iy << 4) | ((unsigned)ix & 15u)) : 0xffffffffu;
+                // (the offset worked out on both sides and selected: as `in ? f(ix, iy) : ~0u` it is a branch)
+                const unsigned cell = __umul24((unsigned)ix >> 4, strip) + (((unsigned)iy << 4) | ((unsigned)ix & 15u));
+                const unsigned off = in ? cell : 0xffffffffu;
                 h[e] = __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b8(edt, (int)off, 0, 0));   // out of range: code 0
             } else {
-                const unsigned off = in ? __umul24((unsigned)iy, ld4) + ((unsigned)ix << 2) : 0xffffffffu;
+                const unsigned cell = __umul24((unsigned)iy, ld4) + ((unsigned)ix << 2);
+                const unsigned off = in ? cell : 0xffffffffu;
                 h[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(edt, (int)off, 0, 0));   // out of range: +0.0f
             }
             n_in += in ? 1 : 0;
@@ -206,6 +217,10 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
             total = total + h;
         }
     };
+    // Behind every step of a round.  The round is one basic block now; scheduled as a whole, its loads gather at its end and
+    // its waits at its start, and the registers of all its steps are live at once (LPP 1, MOTION, PACKED: 114 VGPRs and 4
+    // waves per SIMD against 61 and 8 with the steps kept apart, as the blocks of the branchy offset used to keep them).
+    auto pin_step = [] { __builtin_amdgcn_sched_barrier(0); };
     constexpr int kPairs = DEPTH / 2;
     v2f hq[kPairs];
 #pragma unroll
@@ -223,6 +238,7 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
                 add_hit(hprev[0]);
                 add_hit(hprev[1]);
                 hprev = h;
+                pin_step();
             }
         }
 #pragma unroll
@@ -242,6 +258,7 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
                 hq[m] = beam2(r * kPairs + m);
                 add_hit(h[0]);
                 add_hit(h[1]);
+                pin_step();
             }
         }
 #pragma unroll
@@ -251,6 +268,7 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
         }
     }
     if (LPP == 4) {
+        asm volatile("" : "+v"(total));   // no instruction: keeps the epilogue's adds out of the store's block, beside their moves
         n_in += __builtin_amdgcn_mov_dpp(n_in, 0xB1, 0xf, 0xf, true);   // quad_perm [1,0,3,2]
         n_in += __builtin_amdgcn_mov_dpp(n_in, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
     }
