@@ -1,7 +1,7 @@
 // assoc_kernels.hip — data association (no counterpart in the reference; specification: tests/_assoc_spec.py, DESIGN.md
 // section 7): the detections of a frame are sensor-frame points without identity, and every particle decides for itself which of
 // its landmarks each one belongs to and which ones start a new landmark (associate_kernel); the landmark update then reads its
-// observations through the particle's table (ekf_assoc_kernel: the row walk of ekf_update_kernel with another source of z).
+// observations through the particle's table (ekf_update_kernel of ekf_kernels.hip with EkfObsTable as its source of z).
 // Rows only: a table per particle means "which landmarks a frame observes" differs between particles, which the split, paged
 // and grouped forms rely on being the same.
 //
@@ -16,18 +16,17 @@
 //      takes the next unseen slot: the ranks come from popcounts over a 64-bit "unseen" mask per 64 landmarks.
 // The particle's table row is assembled in LDS and written out as whole dwords.
 //
-// Under a full 2x2 sensor-frame measurement covariance Q (specification: tests/_assoc_aniso_spec.py) the same two kernels run with
-// S = P + R_w(theta_i): associate_body takes the noise as a policy (AssocNoiseIso: the lines above; AssocNoiseAniso: R_w once per
-// wavefront, S^-1 with the operations of ekf_aniso_update_one), and the update's lane type is EkfAnisoLane with the table as
-// its source of z.
+// Under a full 2x2 sensor-frame measurement covariance Q (specification: tests/_assoc_aniso_spec.py) association and update run
+// with S = P + R_w(theta_i): associate_body takes the noise as a policy (AssocNoiseIso: the lines above; AssocNoiseAniso: R_w once
+// per wavefront, S^-1 with the operations of ekf_aniso_update_one), and the update's noise policy is EkfNoiseAniso.
 
-#include "ekf_aniso_lane.h"
+#include "ekf_aniso_math.h"
+#include "ekf_wave.h"
 
 namespace slam {
 
 namespace {
 
-typedef __attribute__((address_space(1))) unsigned char guchar;
 typedef unsigned long long u64;
 
 // LDS of one wavefront, carved out of the dynamic region in multiples of 16 bytes:
@@ -228,85 +227,6 @@ template <bool CREATE> __global__ __launch_bounds__(kEkfWaves * 64) void associa
     associate_body<CREATE, AssocNoiseAniso>(a, q);
 }
 
-// ------------------------------------------------------------------ the landmark update under a per-particle table
-// A lane type (EkfLane; EkfAnisoLane) whose observation of landmark l is det[assoc[i][l]]: lane k of the wavefront holds detection k (NaN from ndet on), the
-// table byte is read alongside the row and the detection comes from a lane read — no second trip to memory.
-template <class BASE> struct EkfAssocLaneT : BASE {
-    const gchar* arow;   // the particle's table row (wave-uniform)
-    float detx, dety;    // THIS lane's detection
-};
-typedef EkfAssocLaneT<EkfLane> EkfAssocLane;
-
-template <class BASE> __device__ __forceinline__ void ekf_obs(const EkfAssocLaneT<BASE>& w, unsigned l, bool in, float& vx, float& vy)
-{
-    const float nan = __uint_as_float(0x7fc00000u);
-    const unsigned k = *(const guchar*)(w.arow + (in ? l : 0u));   // clamped index: the caller discards what lanes beyond L get
-    const float dx = __shfl(w.detx, (int)(k & 63u), 64), dy = __shfl(w.dety, (int)(k & 63u), 64);
-    const bool has = k < 64u;   // SLAM_ASSOC_NONE, and any value that is no detection
-    vx = has ? dx : nan;
-    vy = has ? dy : nan;
-}
-
-// NB: batches of 128 landmarks per pass of the fast path.  COPY: out of place.
-template <int NB, bool COPY>
-__global__ __launch_bounds__(kEkfWaves * 64) void ekf_assoc_kernel(EkfArgs a, EkfAssocTable tab)
-{
-    const unsigned lane = threadIdx.x & 63u;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int i = xcd_block(a.xcd_chunk) * kEkfWaves + wave;
-    if (i >= a.n) return;
-    const int src = a.anc ? a.anc[i] : i;
-    float st_, ct_;
-    det_sincosf(a.th[i], st_, ct_);
-    const float nan = __uint_as_float(0x7fc00000u);
-    EkfAssocLane w;
-    const int row_bytes = __builtin_amdgcn_readfirstlane(5 * a.plane_stride * 4);
-    w.rin = row_rsrc(a.map_in, src, a.row_stride, row_bytes);
-    w.p.rout = row_rsrc(a.map_out, i, a.row_stride, row_bytes);
-    w.pl = __builtin_amdgcn_readfirstlane(a.plane_stride * 4);
-    w.ozx = nullptr;
-    w.ozy = nullptr;
-    w.L = (unsigned)a.nlandmarks;
-    w.p.s = bc2(st_); w.p.c = bc2(ct_); w.p.px = bc2(a.x[i]); w.p.py = bc2(a.y[i]); w.q = bc2(a.meas_var);
-    w.arow = uniform_gptr(tab.assoc + (size_t)i * (size_t)tab.assoc_stride);
-    w.detx = (int)lane < tab.ndet ? tab.det_zx[lane] : nan;
-    w.dety = (int)lane < tab.ndet ? tab.det_zy[lane] : nan;
-
-    const float total = ekf_row_walk<NB, COPY>(w, (unsigned)a.plane_stride, lane);
-    if (lane == 0) store_loglik(a, i, total);
-}
-
-// ... with R_w and det Q in the place of q: EkfAnisoLane's arithmetic (a first sighting stores P = R_w), the table's observations
-template <int NB, bool COPY>
-__global__ __launch_bounds__(kEkfWaves * 64) void ekf_assoc_aniso_kernel(EkfArgs a, EkfAssocTable tab, EkfAnisoCov q)
-{
-    const unsigned lane = threadIdx.x & 63u;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int i = xcd_block(a.xcd_chunk) * kEkfWaves + wave;
-    if (i >= a.n) return;
-    const int src = a.anc ? a.anc[i] : i;
-    float st_, ct_, rxx, rxy, ryy;
-    det_sincosf(a.th[i], st_, ct_);
-    ekf_aniso_world_noise(q, st_, ct_, rxx, rxy, ryy);
-    const float nan = __uint_as_float(0x7fc00000u);
-    EkfAssocLaneT<EkfAnisoLane> w;
-    const int row_bytes = __builtin_amdgcn_readfirstlane(5 * a.plane_stride * 4);
-    w.rin = row_rsrc(a.map_in, src, a.row_stride, row_bytes);
-    w.p.rout = row_rsrc(a.map_out, i, a.row_stride, row_bytes);
-    w.pl = __builtin_amdgcn_readfirstlane(a.plane_stride * 4);
-    w.ozx = nullptr;
-    w.ozy = nullptr;
-    w.L = (unsigned)a.nlandmarks;
-    w.p.s = bc2(st_); w.p.c = bc2(ct_); w.p.px = bc2(a.x[i]); w.p.py = bc2(a.y[i]);
-    w.rxx = bc2(rxx); w.rxy = bc2(rxy); w.ryy = bc2(ryy); w.detq = bc2(q.detq);
-    w.arow = uniform_gptr(tab.assoc + (size_t)i * (size_t)tab.assoc_stride);
-    w.detx = (int)lane < tab.ndet ? tab.det_zx[lane] : nan;
-    w.dety = (int)lane < tab.ndet ? tab.det_zy[lane] : nan;
-
-    const float total = ekf_row_walk<NB, COPY>(w, (unsigned)a.plane_stride, lane);
-    if (lane == 0) store_loglik(a, i, total);
-}
-
 // the shapes the LDS carve and the row accesses of the associating kernels are sized by
 bool assoc_args_ok(const AssocArgs& a)
 {
@@ -314,72 +234,23 @@ bool assoc_args_ok(const AssocArgs& a)
              a.assoc_stride < a.nlandmarks || a.plane_stride < a.nlandmarks);
 }
 
-bool ekf_assoc_args_ok(const EkfArgs& a, const EkfAssocTable& tab)   // rows only
-{
-    return !(a.cov || tab.assoc_stride < a.nlandmarks || tab.ndet < 0 || tab.ndet > SLAM_MAX_DETECTIONS);
-}
-
 }  // namespace
 
-hipError_t launch_associate(hipStream_t stream, const AssocArgs& a_in, bool create, const EventPair* ev)
+hipError_t launch_associate(hipStream_t stream, const AssocArgs& a_in, const EkfAnisoCov* q, bool create, const EventPair* ev)
 {
     if (a_in.n <= 0) return hipSuccess;
-    if (!assoc_args_ok(a_in)) return hipErrorInvalidValue;
+    if (!assoc_args_ok(a_in) || (q && !ekf_aniso_cov_ok(*q))) return hipErrorInvalidValue;
     AssocArgs a = a_in;
     const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
     const size_t lds = (size_t)kEkfWaves * assoc_lds((unsigned)a.nlandmarks).per_wave;   // at most 4 x 9 792 bytes
     if (ev) (void)hipEventRecord(ev->start, stream);
-    if (create) associate_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
-    else associate_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
-    if (ev) (void)hipEventRecord(ev->stop, stream);
-    return hipGetLastError();
-}
-
-hipError_t launch_ekf_assoc(hipStream_t stream, const EkfArgs& a_in, const EkfAssocTable& tab, const EventPair* ev)
-{
-    if (a_in.n <= 0) return hipSuccess;
-    if (!ekf_assoc_args_ok(a_in, tab)) return hipErrorInvalidValue;
-    EkfArgs a = a_in;
-    const bool copy = a.map_in != a.map_out;   // in place: rows without an association stay as they are
-    // batches per pass: those of ekf_update_kernel (launch_ekf_update, its form 0) at the same shapes
-    void (*kernel)(EkfArgs, EkfAssocTable);
-    if (!copy) kernel = a.nlandmarks > 128 ? ekf_assoc_kernel<4, false> : ekf_assoc_kernel<1, false>;
-    else kernel = a.nlandmarks > 128 ? ekf_assoc_kernel<2, true> : ekf_assoc_kernel<1, true>;
-    const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
-    if (ev) (void)hipEventRecord(ev->start, stream);
-    kernel<<<blocks, kEkfWaves * 64, 0, stream>>>(a, tab);
-    if (ev) (void)hipEventRecord(ev->stop, stream);
-    return hipGetLastError();
-}
-
-hipError_t launch_associate_aniso(hipStream_t stream, const AssocArgs& a_in, const EkfAnisoCov& q, bool create, const EventPair* ev)
-{
-    if (a_in.n <= 0) return hipSuccess;
-    if (!assoc_args_ok(a_in) || !ekf_aniso_cov_ok(q)) return hipErrorInvalidValue;
-    AssocArgs a = a_in;
-    const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
-    const size_t lds = (size_t)kEkfWaves * assoc_lds((unsigned)a.nlandmarks).per_wave;
-    if (ev) (void)hipEventRecord(ev->start, stream);
-    if (create) associate_aniso_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
-    else associate_aniso_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
-    if (ev) (void)hipEventRecord(ev->stop, stream);
-    return hipGetLastError();
-}
-
-hipError_t launch_ekf_assoc_aniso(hipStream_t stream, const EkfArgs& a_in, const EkfAssocTable& tab, const EkfAnisoCov& q,
-                                  const EventPair* ev)
-{
-    if (a_in.n <= 0) return hipSuccess;
-    if (!ekf_assoc_args_ok(a_in, tab) || !ekf_aniso_cov_ok(q)) return hipErrorInvalidValue;
-    EkfArgs a = a_in;
-    const bool copy = a.map_in != a.map_out;
-    // batches per pass: launch_ekf_assoc's
-    void (*kernel)(EkfArgs, EkfAssocTable, EkfAnisoCov);
-    if (!copy) kernel = a.nlandmarks > 128 ? ekf_assoc_aniso_kernel<4, false> : ekf_assoc_aniso_kernel<1, false>;
-    else kernel = a.nlandmarks > 128 ? ekf_assoc_aniso_kernel<2, true> : ekf_assoc_aniso_kernel<1, true>;
-    const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
-    if (ev) (void)hipEventRecord(ev->start, stream);
-    kernel<<<blocks, kEkfWaves * 64, 0, stream>>>(a, tab, q);
+    if (q) {
+        if (create) associate_aniso_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a, *q);
+        else associate_aniso_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a, *q);
+    } else {
+        if (create) associate_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
+        else associate_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
+    }
     if (ev) (void)hipEventRecord(ev->stop, stream);
     return hipGetLastError();
 }

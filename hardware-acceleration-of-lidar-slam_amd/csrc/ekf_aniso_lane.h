@@ -1,5 +1,8 @@
-// ekf_aniso_lane.h — the lane type of the row walk (ekf_row_body.h) under a full 2x2 measurement covariance: what
-// ekf_aniso_kernel (ekf_aniso_kernels.hip) and the update under a per-particle table (assoc_kernels.hip) both walk their rows with.
+// ekf_aniso_lane.h — the noise policy of the row walk (ekf_row_body.h: EkfRowLane) under a full 2x2 measurement covariance in the
+// sensor frame (the arithmetic: ekf_aniso_math.h; specification: tests/_aniso_spec.py).  The world-frame noise
+// R_w = H^T Q H depends on the particle's heading, so the posterior covariance is per particle again: only the row layout stores
+// that, and this is a form of the one-wavefront-per-particle row update alone (ekf_update_kernel of ekf_kernels.hip) — no grouped
+// form, no observation-list form, no fused front.  R_w and the pose are wave-uniform.
 #pragma once
 
 #include "ekf_aniso_math.h"
@@ -7,15 +10,17 @@
 
 namespace slam {
 
-struct EkfAnisoLane {   // per-wavefront constants of one particle (EkfLane with R_w and det Q in the place of q)
-    __amdgpu_buffer_rsrc_t rin;
-    EkfPose p;
-    int pl;   // plane stride in bytes
-    const gchar *ozx, *ozy;
-    unsigned L;
+struct EkfNoiseAniso {   // EkfNoiseIso with R_w and det Q in the place of q (a.meas_var is not read; a first sighting stores P = R_w)
+    typedef EkfAnisoCov Args;
     v2f rxx, rxy, ryy, detq;
-    __device__ __forceinline__ void update(v2f mx, v2f my, v2f pxx, v2f pxy, v2f pyy, v2f zx, v2f zy, bool ob0, bool ob1, v2f& r0, v2f& r1,
-                                           v2f& r2, v2f& r3, v2f& r4, v2f& ll) const
+    __device__ __forceinline__ void init(const EkfArgs& a, const Args& q, float s, float c)
+    {
+        float xx, xy, yy;
+        ekf_aniso_world_noise(q, s, c, xx, xy, yy);
+        rxx = bc2(xx); rxy = bc2(xy); ryy = bc2(yy); detq = bc2(q.detq);
+    }
+    __device__ __forceinline__ void update(const EkfPose& p, v2f mx, v2f my, v2f pxx, v2f pxy, v2f pyy, v2f zx, v2f zy, bool ob0, bool ob1,
+                                           v2f& r0, v2f& r1, v2f& r2, v2f& r3, v2f& r4, v2f& ll) const
     {
         const EkfResult<v2f> u = ekf_aniso_update_one<v2f>(mx, my, pxx, pxy, pyy, zx, zy, p.s, p.c, p.px, p.py, rxx, rxy, ryy, detq);
         r0 = u.o0; r1 = u.o1; r2 = u.o2; r3 = u.o3; r4 = u.o4; ll = u.ll;

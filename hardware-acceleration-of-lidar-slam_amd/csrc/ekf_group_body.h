@@ -219,10 +219,10 @@ __device__ __forceinline__ void ekf_group_body(const EkfArgs& a, int bid, float 
         w.rin = row_rsrc(a.map_in, src, a.row_stride, row_bytes);
         w.p = pose_of(k);
         w.pl = pl;
-        w.ozx = ozx;
-        w.ozy = ozy;
         w.L = L;
-        w.q = q2;
+        w.noise.q = q2;
+        w.obs.ozx = ozx;
+        w.obs.ozy = ozy;
         v2f acc = acc_load<G>(s_acc, wave, k, lane);
         unsigned lt = lb;
         for (; lt < L && lt + 128u <= room; lt += 128u) ekf_batches<1, true, true>(w, lt, lane, acc);

@@ -1,11 +1,13 @@
 // ekf_kernels.hip — the motion sample and the landmark update of the particle filter: the 2x2 EKF
-// per (particle, landmark) with a row per wavefront, grouped and on the split layout (the bodies: ekf_row_body.h,
-// ekf_group_body.h, ekf_split_body.h; what they share and the data layout: ekf_wave.h), plus the copy ceiling and the
-// reciprocal self-test.  Fused with the scorer into the front of a frame: front_kernels.hip; sparse in place behind the compact
+// per (particle, landmark) with a row per wavefront (in its four forms: noise meas_var * I or a 2x2 Q, observations from the
+// frame's table or through a per-particle association table), grouped and on the split layout (the bodies: ekf_row_body.h,
+// ekf_aniso_lane.h, ekf_group_body.h, ekf_split_body.h; what they share and the data layout: ekf_wave.h), plus the copy ceiling
+// and the reciprocal self-test.  Fused with the scorer into the front of a frame: front_kernels.hip; sparse in place behind the compact
 // observation list: ekf_sparse_kernels.hip.  The only
 // reference anchor is the zero-noise motion step = the constant-velocity predict of
 // Subsystem_1/main.c:875-898.
 
+#include "ekf_aniso_lane.h"
 #include "ekf_group_body.h"
 #include "ekf_split_body.h"
 
@@ -32,9 +34,10 @@ __global__ __launch_bounds__(kBlock) void motion_sample_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------ A10: 2x2 EKF per (particle, landmark)
-// NB: batches of 128 landmarks per pass of the fast path.  COPY: out of place.
-template <int NB, bool COPY>
-__global__ __launch_bounds__(kEkfWaves * 64) void ekf_update_kernel(EkfArgs a)
+// One wavefront per particle walks its row.  NB: batches of 128 landmarks per pass of the fast path.  COPY: out of place.
+// NOISE, OBS: the two policies of ekf_row_body.h, each with the argument it needs beyond EkfArgs.
+template <int NB, bool COPY, class NOISE, class OBS>
+__global__ __launch_bounds__(kEkfWaves * 64) void ekf_update_kernel(EkfArgs a, typename NOISE::Args na, typename OBS::Args oa)
 {
     const unsigned lane = threadIdx.x & 63u;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -43,15 +46,15 @@ __global__ __launch_bounds__(kEkfWaves * 64) void ekf_update_kernel(EkfArgs a)
     const int src = a.anc ? a.anc[i] : i;
     float st_, ct_;
     det_sincosf(a.th[i], st_, ct_);
-    EkfLane w;
+    EkfRowLane<NOISE, OBS> w;
     const int row_bytes = __builtin_amdgcn_readfirstlane(5 * a.plane_stride * 4);
     w.rin = row_rsrc(a.map_in, src, a.row_stride, row_bytes);
     w.p.rout = row_rsrc(a.map_out, i, a.row_stride, row_bytes);
     w.pl = __builtin_amdgcn_readfirstlane(a.plane_stride * 4);
-    w.ozx = uniform_gptr(a.obs_zx);
-    w.ozy = uniform_gptr(a.obs_zy);
     w.L = (unsigned)a.nlandmarks;
-    w.p.s = bc2(st_); w.p.c = bc2(ct_); w.p.px = bc2(a.x[i]); w.p.py = bc2(a.y[i]); w.q = bc2(a.meas_var);
+    w.p.s = bc2(st_); w.p.c = bc2(ct_); w.p.px = bc2(a.x[i]); w.p.py = bc2(a.y[i]);
+    w.noise.init(a, na, st_, ct_);
+    w.obs.init(a, oa, i, lane);
 
     const float total = ekf_row_walk<NB, COPY>(w, (unsigned)a.plane_stride, lane);
     if (lane == 0) store_loglik(a, i, total);
@@ -141,12 +144,43 @@ hipError_t launch_motion_sample(hipStream_t stream, const float* sx, const float
     return hipGetLastError();
 }
 
+// one form of the row update: batches of 128 landmarks in flight per wavefront and the launch
+template <class NOISE, class OBS>
+static hipError_t launch_rows(hipStream_t stream, EkfArgs a, const typename NOISE::Args& na, const typename OBS::Args& oa, const EventPair* ev)
+{
+    const bool copy = a.map_in != a.map_out;   // in place: rows without an observation stay as they are
+    const bool big = a.nlandmarks > 128;
+    // out of place: 2 measured best at 64k x 500 (1: 178 us, 2: 166 us, 4: 180 us).  In place: 4 batches (512 landmarks) per round
+    // trip; measured at 64k x 500 with 32 landmarks observed: 1 batch at a time 91 us, because every batch is its own dependent
+    // chain obs table -> row -> store
+    void (*kernel)(EkfArgs, typename NOISE::Args, typename OBS::Args);
+    if (!copy) kernel = big ? ekf_update_kernel<4, false, NOISE, OBS> : ekf_update_kernel<1, false, NOISE, OBS>;
+    else kernel = big ? ekf_update_kernel<2, true, NOISE, OBS> : ekf_update_kernel<1, true, NOISE, OBS>;
+    const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
+    if (ev) (void)hipEventRecord(ev->start, stream);
+    kernel<<<blocks, kEkfWaves * 64, 0, stream>>>(a, na, oa);
+    if (ev) (void)hipEventRecord(ev->stop, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_ekf_rows(hipStream_t stream, const EkfArgs& a, const EkfAnisoCov* q, const EkfAssocTable* tab, const EventPair* ev)
+{
+    if (a.n <= 0) return hipSuccess;
+    if (a.cov) return hipErrorInvalidValue;   // rows only
+    if (tab && (tab->assoc_stride < a.nlandmarks || tab->ndet < 0 || tab->ndet > SLAM_MAX_DETECTIONS)) return hipErrorInvalidValue;
+    if (q && !ekf_aniso_cov_ok(*q)) return hipErrorInvalidValue;
+    if (q && tab) return launch_rows<EkfNoiseAniso, EkfObsTable>(stream, a, *q, *tab, ev);
+    if (q) return launch_rows<EkfNoiseAniso, EkfObsFrame>(stream, a, *q, {}, ev);
+    if (tab) return launch_rows<EkfNoiseIso, EkfObsTable>(stream, a, {}, *tab, ev);
+    return launch_rows<EkfNoiseIso, EkfObsFrame>(stream, a, {}, {}, ev);
+}
+
 hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const EventPair* ev, int group_size)
 {
     if (a_in.n <= 0) return hipSuccess;
     EkfArgs a = a_in;
     void (*kernel)(EkfArgs);   // the form, and how many particles a workgroup of it owns
-    int per_block = kEkfWaves;
+    int per_block;
     const bool copy = a.map_in != a.map_out;   // in place: rows without an observation stay as they are
     if (a.cov) {   // split layout: always the grouped form (2 particles per wavefront unless the caller asks for 4 or 8)
         const int G = group_size == 4 || group_size == 8 ? group_size : 2;
@@ -170,14 +204,7 @@ hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const Even
         if (G == 2) kernel = ekf_update_group_kernel<kEkfGroupNb, 2>;
         else kernel = ekf_update_group_kernel<kEkfGroupNb, 4>;
     } else {
-        // batches of 128 landmarks in flight per wavefront: 2 measured best at 64k x 500 (1: 178 us, 2: 166 us, 4: 180 us)
-        const int nb = a.nlandmarks <= 128 ? 1 : 2;
-        // in place: 4 batches (512 landmarks) per round trip; measured at 64k x 500 with 32 landmarks observed: 1 batch at a
-        // time 91 us, because every batch is its own dependent chain obs table -> row -> store
-        if (!copy && a.nlandmarks > 128) kernel = ekf_update_kernel<4, false>;
-        else if (!copy) kernel = ekf_update_kernel<1, false>;
-        else if (nb == 1) kernel = ekf_update_kernel<1, true>;
-        else kernel = ekf_update_kernel<2, true>;
+        return launch_ekf_rows(stream, a, nullptr, nullptr, ev);   // one wavefront per particle
     }
     const int blocks = xcd_grid(a.n, per_block, a.xcd_chunk);
     if (ev) (void)hipEventRecord(ev->start, stream);

@@ -17,7 +17,7 @@ namespace slam {
 
 // What goes into the row for the two landmarks of a lane, given the update's result in r0 .. r4 / ll: a first sighting
 // (prior P_xx < 0) takes the observed point and P = (fxx, fxy, fyy) — q I, or the particle's R_w when the measurement covariance
-// is a full 2x2 (ekf_aniso_kernels.hip) — and adds no likelihood term; a landmark without an observation keeps
+// is a full 2x2 (ekf_aniso_lane.h) — and adds no likelihood term; a landmark without an observation keeps
 // its prior values.  Both cases are decided for the WAVEFRONT first (a ballot each): in a running filter most batches of
 // 128 landmarks hold neither — every landmark seen before, every one observed, or none — and then the selects (and the
 // arithmetic of the first sighting) are skipped altogether.  The values are those of
@@ -55,18 +55,18 @@ __device__ __forceinline__ void ekf_select(v2f& r0, v2f& r1, v2f& r2, v2f& r3, v
     }
 }
 
-struct EkfLane {   // per-wavefront constants of one particle
-    // source row and destination row (p.rout) as buffer resources (wave-uniform descriptors in SGPRs): an access is
-    // "descriptor + 32-bit lane offset + scalar plane offset", no 64-bit vector arithmetic for loads or stores
-    __amdgpu_buffer_rsrc_t rin;
-    EkfPose p;
-    int pl;   // plane stride in bytes
-    const gchar *ozx, *ozy;
-    unsigned L;
+// A wavefront's lane type is made of two independent choices, each a policy with the kernel argument it needs beyond EkfArgs
+// (Args), an init() for one particle and the one operation ekf_batches asks of it.
+//
+// NOISE — the measurement noise and the arithmetic per landmark.  This one: meas_var * I (a first sighting stores P = q I);
+// EkfNoiseAniso of ekf_aniso_lane.h: the particle's R_w from a 2x2 sensor-frame Q.
+struct EkfNoiseIso {
+    struct Args {};   // a.meas_var is all it needs
     v2f q;
+    __device__ __forceinline__ void init(const EkfArgs& a, const Args&, float s, float c) { q = bc2(a.meas_var); }
     // what goes into the row for the two landmarks of a lane (ob0 / ob1: they have an observation) and their likelihood terms
-    __device__ __forceinline__ void update(v2f mx, v2f my, v2f pxx, v2f pxy, v2f pyy, v2f zx, v2f zy, bool ob0, bool ob1, v2f& r0, v2f& r1,
-                                           v2f& r2, v2f& r3, v2f& r4, v2f& ll) const
+    __device__ __forceinline__ void update(const EkfPose& p, v2f mx, v2f my, v2f pxx, v2f pxy, v2f pyy, v2f zx, v2f zy, bool ob0, bool ob1,
+                                           v2f& r0, v2f& r1, v2f& r2, v2f& r3, v2f& r4, v2f& ll) const
     {
         const EkfResult<v2f> u = ekf_update_one<v2f, false>(mx, my, pxx, pxy, pyy, zx, zy, p.s, p.c, p.px, p.py, q);
         r0 = u.o0; r1 = u.o1; r2 = u.o2; r3 = u.o3; r4 = u.o4; ll = u.ll;
@@ -74,15 +74,58 @@ struct EkfLane {   // per-wavefront constants of one particle
     }
 };
 
-// The observation of landmark l as a wavefront's lane type supplies it (in: l < L; NaN = none).  This one: the frame's table
-// indexed by landmark, w.ozx / w.ozy (EkfLane, EkfAnisoLane).  A lane type with another source overloads it (assoc_kernels.hip:
-// the particle's own association table).
-template <class W> __device__ __forceinline__ void ekf_obs(const W& w, unsigned l, bool in, float& vx, float& vy)
-{
-    const unsigned zo = (in ? l : 0u) * 4u;   // clamped index + select instead of a predicated load
-    vx = *(const gfloat*)(w.ozx + zo);
-    vy = *(const gfloat*)(w.ozy + zo);
-}
+// OBS — the observation of landmark l (in: l < L; NaN = none).  This one: the frame's table indexed by landmark, a.obs_zx / a.obs_zy.
+struct EkfObsFrame {
+    struct Args {};
+    const gchar *ozx, *ozy;
+    __device__ __forceinline__ void init(const EkfArgs& a, const Args&, int i, unsigned lane)
+    {
+        ozx = uniform_gptr(a.obs_zx);
+        ozy = uniform_gptr(a.obs_zy);
+    }
+    __device__ __forceinline__ void get(unsigned l, bool in, float& vx, float& vy) const
+    {
+        const unsigned zo = (in ? l : 0u) * 4u;   // clamped index + select instead of a predicated load
+        vx = *(const gfloat*)(ozx + zo);
+        vy = *(const gfloat*)(ozy + zo);
+    }
+};
+// ... and det[assoc[i][l]], the particle's own association table (data association: assoc_kernels.hip makes the table): lane k of
+// the wavefront holds detection k (NaN from ndet on), the table byte is read alongside the row and the detection comes from a
+// lane read — no second trip to memory.
+struct EkfObsTable {
+    typedef EkfAssocTable Args;
+    const gchar* arow;   // the particle's table row (wave-uniform)
+    float detx, dety;    // THIS lane's detection
+    __device__ __forceinline__ void init(const EkfArgs& a, const Args& tab, int i, unsigned lane)
+    {
+        const float nan = __uint_as_float(0x7fc00000u);
+        arow = uniform_gptr(tab.assoc + (size_t)i * (size_t)tab.assoc_stride);
+        detx = (int)lane < tab.ndet ? tab.det_zx[lane] : nan;
+        dety = (int)lane < tab.ndet ? tab.det_zy[lane] : nan;
+    }
+    __device__ __forceinline__ void get(unsigned l, bool in, float& vx, float& vy) const
+    {
+        const float nan = __uint_as_float(0x7fc00000u);
+        const unsigned k = *(const guchar*)(arow + (in ? l : 0u));   // clamped index: the caller discards what lanes beyond L get
+        const float dx = __shfl(detx, (int)(k & 63u), 64), dy = __shfl(dety, (int)(k & 63u), 64);
+        const bool has = k < 64u;   // SLAM_ASSOC_NONE, and any value that is no detection
+        vx = has ? dx : nan;
+        vy = has ? dy : nan;
+    }
+};
+
+template <class NOISE, class OBS> struct EkfRowLane {   // per-wavefront constants of one particle
+    // source row and destination row (p.rout) as buffer resources (wave-uniform descriptors in SGPRs): an access is
+    // "descriptor + 32-bit lane offset + scalar plane offset", no 64-bit vector arithmetic for loads or stores
+    __amdgpu_buffer_rsrc_t rin;
+    EkfPose p;
+    int pl;   // plane stride in bytes
+    unsigned L;
+    NOISE noise;
+    OBS obs;
+};
+typedef EkfRowLane<EkfNoiseIso, EkfObsFrame> EkfLane;   // the grouped form's row tails (ekf_group_body.h)
 
 // NB batches of 128 landmarks starting at lb: all loads first, then the arithmetic, then the stores.  A lane owns
 // landmarks l and l + 64 of each batch, so every access is one 256-byte dword access per wavefront (8-byte
@@ -90,8 +133,7 @@ template <class W> __device__ __forceinline__ void ekf_obs(const W& w, unsigned 
 // FULL: every lane's landmarks lie inside the row (lb + 128*NB <= plane_stride) and the update is out of place,
 // so nothing is predicated; landmarks at or beyond L (row padding) then simply count as "not observed" and their
 // padding values are copied along.  !FULL: the general form (row tails, in-place updates).
-// W: the wavefront's constants, its arithmetic and where its observations come from (EkfLane; EkfAnisoLane of
-// ekf_aniso_kernels.hip; EkfAssocLane of assoc_kernels.hip).
+// W: an EkfRowLane — the wavefront's constants, its arithmetic (W::noise) and where its observations come from (W::obs).
 template <int NB, bool FULL, bool COPY, class W>
 __device__ __forceinline__ void ekf_batches(const W& w, unsigned lb, unsigned lane, v2f& acc)
 {
@@ -107,7 +149,7 @@ __device__ __forceinline__ void ekf_batches(const W& w, unsigned lb, unsigned la
             const bool in = l < w.L;
             off[g][t] = ((FULL || in) ? l : 0u) * 4u;
             float vx, vy;
-            ekf_obs(w, l, in, vx, vy);
+            w.obs.get(l, in, vx, vy);
             zx[g][t] = in ? vx : nan;
             zy[g][t] = in ? vy : nan;
             // NaN = no observation (also what lanes beyond L were given).  Testing zy as well keeps its load up here
@@ -137,7 +179,7 @@ __device__ __forceinline__ void ekf_batches(const W& w, unsigned lb, unsigned la
             continue;
         }
         v2f r0, r1, r2, r3, r4, ll;
-        w.update(mx, my, pxx, pxy, pyy, zx[g], zy[g], obs[g][0], obs[g][1], r0, r1, r2, r3, r4, ll);
+        w.noise.update(w.p, mx, my, pxx, pxy, pyy, zx[g], zy[g], obs[g][0], obs[g][1], r0, r1, r2, r3, r4, ll);
 #pragma unroll
         for (int t = 0; t < 2; ++t)
             if (FULL || use[g][t]) {
@@ -151,7 +193,7 @@ __device__ __forceinline__ void ekf_batches(const W& w, unsigned lb, unsigned la
     }
 }
 
-// One particle's whole row, NB batches per pass of the fast path (ekf_update_kernel; ekf_aniso_kernel) -> its log-likelihood,
+// One particle's whole row, NB batches per pass of the fast path (ekf_update_kernel) -> its log-likelihood,
 // in every lane.  room: the plane stride in floats.
 template <int NB, bool COPY, class W>
 __device__ __forceinline__ float ekf_row_walk(const W& w, unsigned room, unsigned lane)

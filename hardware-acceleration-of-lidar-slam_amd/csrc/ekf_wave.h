@@ -63,6 +63,7 @@ constexpr int kEkfWaves = 4;   // particles per workgroup
 // global-address-space pointers: "scalar base + 32-bit lane offset" is an addressing mode of global_load/store only
 typedef __attribute__((address_space(1))) char gchar;
 typedef __attribute__((address_space(1))) float gfloat;
+typedef __attribute__((address_space(1))) unsigned char guchar;
 // cache policy of the row stores: 2 = nt (streaming; the written rows are next read a frame later, long after they
 // left the caches).  Measured at 64k x 500: default 170 us, nt 162 us, sc0 170 us, sc1 171 us in the filter;
 // 243 / 248 / 244 / 243 us for a sweep without shared ancestors.

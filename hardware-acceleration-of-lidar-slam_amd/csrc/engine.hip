@@ -1,6 +1,6 @@
 // engine.hip — the engine handle behind the C ABI declared in include/slam_hip.h: errors and status strings, its life cycle
 // and stream, HIP-event profiling, the self-test and the one bounded wait on a word in mapped host memory.  The stages are
-// implemented in engine_match.hip, engine_ekf.hip and engine_resample.hip.
+// implemented in engine_match.hip, engine_ekf.hip, engine_assoc.hip and engine_resample.hip.
 //
 // The engine owns what the reference keeps in file-scope globals — the two occupancy/EDT grids
 // (`occ_grid`, Subsystem_1/main.c:200-213), the current scan (`scan`, main.c:60-69) and the matcher

@@ -1,0 +1,320 @@
+// engine_assoc.hip — what a frame of detections without identity adds behind the C ABI: the detections themselves (uploaded, set,
+// or made from the scan by the detector), the association stage with meas_var * I or a 2x2 Q, and the landmarks' existence
+// evidence.  The landmark update under the table the association makes: engine_ekf.hip.
+
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+
+#include <limits>
+
+#include "engine_internal.h"
+
+using namespace slam;
+
+int slam_engine_resolve_detections(slam_engine* e)
+{
+    if (!e->det_pending) return SLAM_OK;
+    const volatile uint32_t* flag = reinterpret_cast<const volatile uint32_t*>(e->h_det + 1);
+    if (int rc = slam_engine_wait_flag(e, nullptr, flag, e->det_seq, "detection count flag")) return rc;
+    const int ndet = e->h_det[0];
+    if (ndet < 0 || ndet > SLAM_MAX_DETECTIONS) return slam_engine_fail_hip(e, hipErrorUnknown, "detection count");
+    e->ndet = ndet;
+    e->det_pending = false;
+    return SLAM_OK;
+}
+
+extern "C" {
+
+/* ------------------------------------------------------------------ data association (assoc_kernels.hip) */
+
+int slam_detections_upload_host(slam_engine* e, const float* zx, const float* zy, int ndet)
+{
+    SLAM_ENTER(e);
+    if (ndet < 0 || ndet > SLAM_MAX_DETECTIONS || (ndet > 0 && (!zx || !zy))) return SLAM_ERR_INVALID_ARG;
+    const float big = std::numeric_limits<float>::max();
+    for (int k = 0; k < ndet; ++k)
+        if (!(zx[k] >= -big && zx[k] <= big && zy[k] >= -big && zy[k] <= big)) return SLAM_ERR_INVALID_ARG;   // (NaN fails every comparison)
+    if (!e->det_buf.p) SLAM_HIP_TRY(e, e->det_buf.ensure(sizeof(float) * 2 * SLAM_MAX_DETECTIONS));
+    if (ndet > 0) {
+        float* h = e->stage_acquire();
+        for (int k = 0; k < SLAM_MAX_DETECTIONS; ++k) {   // zx[64] | zy[ndet]: one copy
+            h[k] = k < ndet ? zx[k] : 0.0f;
+            if (k < ndet) h[SLAM_MAX_DETECTIONS + k] = zy[k];
+        }
+        const hipError_t err = hipMemcpyAsync(e->det_buf.as<float>(), h, sizeof(float) * (SLAM_MAX_DETECTIONS + (size_t)ndet),
+                                              hipMemcpyHostToDevice, e->stream);
+        SLAM_HIP_TRY(e, e->stage_release(h));
+        SLAM_HIP_TRY(e, err);
+    }
+    e->d_det_zx = e->det_buf.as<float>();
+    e->d_det_zy = e->det_buf.as<float>() + SLAM_MAX_DETECTIONS;
+    e->ndet = ndet;
+    e->det_pending = false;   // (a detector launch still in flight wrote the buffer in front of this copy, in stream order)
+    e->det_from_scan = false;
+    return SLAM_OK;
+}
+
+int slam_detections_set_dev(slam_engine* e, const float* d_zx, const float* d_zy, int ndet)
+{
+    SLAM_ENTER(e);
+    if (ndet < 0 || ndet > SLAM_MAX_DETECTIONS || (ndet > 0 && (!d_zx || !d_zy))) return SLAM_ERR_INVALID_ARG;
+    e->d_det_zx = d_zx;
+    e->d_det_zy = d_zy;
+    e->ndet = ndet;
+    e->det_pending = false;
+    e->det_from_scan = false;
+    return SLAM_OK;
+}
+
+// the argument checks of the association stage (everything but the measurement noise)
+static bool associate_args_ok(const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x, const float* d_y,
+                              const float* d_th, int n, float gate, float new_gate, int create, const uint8_t* d_assoc, int assoc_stride)
+{
+    return !(n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
+             assoc_stride < nlandmarks || !(gate > 0.0f && gate <= std::numeric_limits<float>::max()) || !(new_gate >= gate) ||
+             (create != 0 && create != 1) || (n > 0 && (!d_map || !d_x || !d_y || !d_th || !d_assoc)));
+}
+
+// ... and what it puts into an AssocArgs: the caller's rows, poses, gather index and table, the engine's detections
+static AssocArgs assoc_args(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                            const float* d_y, const float* d_th, const int32_t* d_anc, int n, float meas_var, float gate, float new_gate,
+                            uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
+{
+    AssocArgs a;
+    a.map = d_map;
+    a.row_stride = row_stride;
+    a.plane_stride = plane_stride;
+    a.nlandmarks = nlandmarks;
+    a.x = d_x;
+    a.y = d_y;
+    a.th = d_th;
+    a.anc = d_anc;
+    a.n = n;
+    a.det_zx = e->d_det_zx;
+    a.det_zy = e->d_det_zy;
+    a.ndet = e->ndet;
+    a.meas_var = meas_var;
+    a.gate = gate;
+    a.new_gate = new_gate;
+    a.assoc = d_assoc;
+    a.assoc_stride = assoc_stride;
+    a.stats = d_stats;
+    a.xcd_chunk = 0;
+    return a;
+}
+
+int slam_engine_associate(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                          const float* d_y, const float* d_th, const int32_t* d_anc, int n, const slam_meas_noise& noise, float gate,
+                          float new_gate, int create, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
+{
+    SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (!associate_args_ok(d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, n, gate, new_gate, create, d_assoc, assoc_stride) ||
+        (noise.full ? !noise.meas_cov : !(noise.meas_var > 0.0f)))
+        return SLAM_ERR_INVALID_ARG;
+    EkfAnisoCov q;
+    if (noise.full && !slam_aniso_cov_from(e, noise.meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    // (meas_var of the arguments is not read under a 2x2 covariance)
+    const AssocArgs a = assoc_args(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, noise.full ? 0.0f : noise.meas_var,
+                                   gate, new_gate, d_assoc, assoc_stride, d_stats);
+    SLAM_HIP_TRY(e, launch_associate(e->stream, a, noise.full ? &q : nullptr, create != 0, e->prof_next(SLAM_PROF_PAGES)));
+    (noise.full ? e->assoc_aniso_launches : e->assoc_launches)[0]++;
+    return SLAM_OK;
+}
+
+int slam_associate_dev(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                       const float* d_y, const float* d_th, const int32_t* d_anc, int n, float meas_var, float gate, float new_gate,
+                       int create, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
+{
+    return slam_engine_associate(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, slam_meas_noise{ meas_var, nullptr, false },
+                                 gate, new_gate, create, d_assoc, assoc_stride, d_stats);
+}
+
+int slam_associate_aniso_dev(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                             const float* d_y, const float* d_th, const int32_t* d_anc, int n, const float meas_cov[3], float gate,
+                             float new_gate, int create, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
+{
+    return slam_engine_associate(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, slam_meas_noise{ 0.0f, meas_cov, true },
+                                 gate, new_gate, create, d_assoc, assoc_stride, d_stats);
+}
+
+int slam_assoc_aniso_counts(slam_engine* e, int64_t counts[2])
+{
+    SLAM_ENTER(e);
+    if (!counts) return SLAM_ERR_INVALID_ARG;
+    counts[0] = e->assoc_aniso_launches[0];
+    counts[1] = e->assoc_aniso_launches[1];
+    return SLAM_OK;
+}
+
+int slam_assoc_counts(slam_engine* e, int64_t counts[2])
+{
+    SLAM_ENTER(e);
+    if (!counts) return SLAM_ERR_INVALID_ARG;
+    counts[0] = e->assoc_launches[0];
+    counts[1] = e->assoc_launches[1];
+    return SLAM_OK;
+}
+
+/* ------------------------------------------------------------------ the detector (detect_kernels.hip) */
+
+void slam_detect_params_default(slam_detect_params* p)
+{
+    if (!p) return;
+    p->jump = 0.3f;
+    p->guard = 1.0f;
+    p->max_width = 0.5f;
+    p->max_range = 20.0f;
+    p->min_points = 3;
+    p->max_points = 40;
+    p->wrap = 1;
+}
+
+int slam_detect_scan_dev(slam_engine* e, const slam_detect_params* params, int32_t* d_stats)
+{
+    SLAM_ENTER(e);
+    if (!params) return SLAM_ERR_INVALID_ARG;
+    if (!slam_detect_params_ok(params)) {
+        slam_detect_params_error(e);
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (e->nbeams < 0) return SLAM_ERR_NOT_READY;
+    if (!e->det_buf.p) SLAM_HIP_TRY(e, e->det_buf.ensure(sizeof(float) * 2 * SLAM_MAX_DETECTIONS));
+    DetectArgs a;
+    a.bx = e->d_bx;
+    a.by = e->d_by;
+    a.nbeams = e->nbeams;
+    a.jump2 = params->jump * params->jump;   // one float32 product each (-ffp-contract=off)
+    a.guard2 = params->guard * params->guard;
+    a.width2 = params->max_width * params->max_width;
+    a.range2 = params->max_range * params->max_range;
+    a.min_points = params->min_points;
+    a.max_points = params->max_points;
+    a.wrap = params->wrap;
+    a.det = e->det_buf.as<float>();
+    a.stats = d_stats;
+    a.h_out = e->d_hdet;
+    a.seq = e->det_seq + 1;
+    SLAM_HIP_TRY(e, launch_detect_scan(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
+    e->det_seq = a.seq;
+    e->d_det_zx = e->det_buf.as<float>();
+    e->d_det_zy = e->det_buf.as<float>() + SLAM_MAX_DETECTIONS;
+    e->ndet = 0;   // until the count is picked up
+    e->det_pending = true;
+    e->det_from_scan = true;
+    e->detect_launches++;
+    return SLAM_OK;
+}
+
+int slam_detect_count(slam_engine* e, int64_t* launches)
+{
+    SLAM_ENTER(e);
+    if (!launches) return SLAM_ERR_INVALID_ARG;
+    *launches = e->detect_launches;
+    return SLAM_OK;
+}
+
+int slam_detections_get_host(slam_engine* e, float* zx, float* zy, int32_t* ndet)
+{
+    SLAM_ENTER(e);
+    if (!zx || !zy || !ndet) return SLAM_ERR_INVALID_ARG;
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    // the detector's output: the whole block as its kernel left it (0 from ndet on); anything else: ndet values, 0 behind them
+    const size_t count = e->det_from_scan ? (size_t)SLAM_MAX_DETECTIONS : (size_t)e->ndet;
+    for (size_t k = count; k < SLAM_MAX_DETECTIONS; ++k) zx[k] = zy[k] = 0.0f;
+    if (count > 0) {
+        SLAM_HIP_TRY(e, hipMemcpyAsync(zx, e->d_det_zx, sizeof(float) * count, hipMemcpyDeviceToHost, e->stream));
+        SLAM_HIP_TRY(e, hipMemcpyAsync(zy, e->d_det_zy, sizeof(float) * count, hipMemcpyDeviceToHost, e->stream));
+    }
+    SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
+    *ndet = e->ndet;
+    return SLAM_OK;
+}
+
+/* ------------------------------------------------------------------ landmark existence evidence (evidence_kernels.hip) */
+
+int slam_landmark_evidence_dev(slam_engine* e, float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                               const float* d_y, const int32_t* d_anc, int n, const uint8_t* d_assoc, int assoc_stride,
+                               const uint8_t* d_ev_in, uint8_t* d_ev_out, int ev_stride, int hit, int miss, int cmax, float view_range,
+                               int32_t* d_stats)
+{
+    SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
+        assoc_stride < nlandmarks || ev_stride < nlandmarks || hit < 1 || hit > 255 || miss < 1 || miss > 255 || cmax < 1 || cmax > 255 ||
+        !(view_range > 0.0f && view_range <= std::numeric_limits<float>::max()) ||   // (NaN fails every comparison)
+        !d_map || !d_x || !d_y || !d_assoc || !d_ev_in || !d_ev_out || (d_anc && d_ev_in == d_ev_out))
+        return SLAM_ERR_INVALID_ARG;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    EvidenceArgs a;
+    a.map = d_map;
+    a.row_stride = row_stride;
+    a.plane_stride = plane_stride;
+    a.nlandmarks = nlandmarks;
+    a.x = d_x;
+    a.y = d_y;
+    a.anc = d_anc;
+    a.n = n;
+    a.assoc = d_assoc;
+    a.assoc_stride = assoc_stride;
+    a.ndet = e->ndet;
+    a.ev_in = d_ev_in;
+    a.ev_out = d_ev_out;
+    a.ev_stride = ev_stride;
+    a.hit = hit;
+    a.miss = miss;
+    a.cmax = cmax;
+    a.range2 = view_range * view_range;   // one float32 product (-ffp-contract=off)
+    a.stats = d_stats;
+    a.xcd_chunk = 0;
+    SLAM_HIP_TRY(e, launch_landmark_evidence(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
+    e->evidence_launches[0]++;
+    return SLAM_OK;
+}
+
+int slam_evidence_init_dev(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, int nrows,
+                           uint8_t* d_ev, int ev_stride, int value)
+{
+    SLAM_ENTER(e);
+    if (nrows < 0 || nlandmarks < 0 || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride || ev_stride < nlandmarks ||
+        value < 0 || value > 255 || !d_map || !d_ev)
+        return SLAM_ERR_INVALID_ARG;
+    if (nrows == 0) return SLAM_OK;
+    EvidenceInitArgs a;
+    a.map = d_map;
+    a.row_stride = row_stride;
+    a.plane_stride = plane_stride;
+    a.nlandmarks = nlandmarks;
+    a.nrows = nrows;
+    a.ev = d_ev;
+    a.ev_stride = ev_stride;
+    a.value = value;
+    a.xcd_chunk = 0;
+    SLAM_HIP_TRY(e, launch_evidence_init(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
+    e->evidence_launches[1]++;
+    return SLAM_OK;
+}
+
+int slam_evidence_counts(slam_engine* e, int64_t counts[2])
+{
+    SLAM_ENTER(e);
+    if (!counts) return SLAM_ERR_INVALID_ARG;
+    counts[0] = e->evidence_launches[0];
+    counts[1] = e->evidence_launches[1];
+    return SLAM_OK;
+}
+
+int slam_evidence_gather_dev(slam_engine* e, const uint8_t* d_in, uint8_t* d_out, int ev_stride, const int32_t* d_anc, int n)
+{
+    SLAM_ENTER(e);
+    if (n < 0 || ev_stride < 0 || (n > 0 && ev_stride > 0 && (!d_in || !d_out || !d_anc || d_in == d_out))) return SLAM_ERR_INVALID_ARG;
+    const ProfScope prof(e, SLAM_PROF_PAGES);
+    SLAM_HIP_TRY(e, launch_evidence_gather(e->stream, d_in, d_out, ev_stride, d_anc, n));
+    return SLAM_OK;
+}
+
+}  // extern "C"

@@ -1,8 +1,9 @@
 // engine_internal.h — the engine object shared by the translation units that implement the C ABI
-// (engine.hip and the engine_*.hip units by stage, pf_session.hip, comm.hip, mapper.hip).  Not part of the public interface.
+// (engine.hip and the engine_*.hip units by stage — match, ekf, assoc, resample —, pf_session.hip, comm.hip, mapper.hip).  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stdio.h>
 
 #include <vector>
 
@@ -275,10 +276,10 @@ inline bool slam_spin_flag(const volatile uint32_t* flag, uint32_t want)
 // bounded spin, then a stream synchronisation and one more look; SLAM_ERR_HIP naming `what` if it still is not there.
 int slam_engine_wait_flag(slam_engine* e, slam_comm* comm, const volatile uint32_t* flag, uint32_t seq, const char* what);
 
-// engine_ekf.hip: a pending detection count (slam_detect_scan_dev) becomes e->ndet — a flag wait, no copy, no stream
+// engine_assoc.hip: a pending detection count (slam_detect_scan_dev) becomes e->ndet — a flag wait, no copy, no stream
 // synchronisation; nothing pending: nothing happens
 int slam_engine_resolve_detections(slam_engine* e);
-// the conditions of slam_detect_scan_dev on its parameters (NaN fails every comparison)
+// the conditions of slam_detect_scan_dev on its parameters (NaN fails every comparison) and what a refusal leaves in slam_last_error
 inline bool slam_detect_params_ok(const slam_detect_params* p)
 {
     const float big = 3.402823466e+38f;
@@ -288,6 +289,43 @@ inline bool slam_detect_params_ok(const slam_detect_params* p)
     return p->guard >= p->jump && p->min_points >= 1 && p->min_points <= p->max_points && p->max_points <= SLAM_DETECT_MAX_POINTS &&
            (p->wrap == 0 || p->wrap == 1);
 }
+inline void slam_detect_params_error(slam_engine* e)
+{
+    snprintf(e->err, sizeof e->err, "the detector needs finite jump, guard, max_width and max_range > 0, guard >= jump, "
+                                    "1 <= min_points <= max_points <= %d and wrap in {0, 1}", (int)SLAM_DETECT_MAX_POINTS);
+}
+
+// The two choices a landmark update on rows has (kernels.h: launch_ekf_rows), as the engine's stages take them.
+// The measurement noise: meas_var * I, or — full — the 2x2 sensor-frame covariance meas_cov[3] = {qxx, qxy, qyy}
+struct slam_meas_noise {
+    float meas_var;
+    const float* meas_cov;
+    bool full;
+};
+// ... and a per-particle association table as the source of the observations (no table: the engine's observation table)
+struct slam_assoc_view {
+    const uint8_t* d_assoc;
+    int assoc_stride;
+};
+// meas_cov as the 2x2 stages accept it; leaves the reason in slam_last_error otherwise
+inline bool slam_aniso_cov_from(slam_engine* e, const float meas_cov[3], slam::EkfAnisoCov* q)
+{
+    *q = slam::ekf_aniso_cov(meas_cov);
+    if (slam::ekf_aniso_cov_ok(*q)) return true;
+    snprintf(e->err, sizeof e->err, "meas_cov must be finite with qxx > 0, qyy > 0 and qxx * qyy - qxy * qxy > 0 in float32");
+    return false;
+}
+// engine_ekf.hip: slam_ekf_update_dev, _aniso_dev, _assoc_dev and _assoc_aniso_dev are this one function, their checks and status
+// codes in one order: the isotropic update from the observation table alone has the sparse in-place and the grouped kernels, a
+// table brings SLAM_MAX_OBS, the detections (resolved first; SLAM_ERR_NOT_READY without any) and d_assoc with it
+extern "C" int slam_engine_ekf_update(slam_engine* e, const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride,
+                                      int nlandmarks, const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc, int n,
+                                      const slam_meas_noise& noise, const slam_assoc_view* table, float* d_loglik);
+// engine_assoc.hip: slam_associate_dev and slam_associate_aniso_dev likewise
+extern "C" int slam_engine_associate(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                                     const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc, int n,
+                                     const slam_meas_noise& noise, float gate, float new_gate, int create, uint8_t* d_assoc,
+                                     int assoc_stride, int32_t* d_stats);
 
 // engine_match.hip
 namespace slam_detail {
@@ -323,7 +361,7 @@ extern "C" int slam_ekf_materialise_dev(slam_engine* e, const float* d_mean_in, 
                              int nlandmarks, const float* d_obs_save, const float* d_x, const float* d_y, const float* d_th,
                              const int32_t* d_anc, int n, float meas_var, const slam::SplitIO* split, const uint32_t* d_survivor,
                              uint32_t stamp, int group);
-// a frame of a pruning session without a landmark update: the evidence follows its particles, d_out[i] = d_in[d_anc[i]] (rows of
+// engine_assoc.hip: a frame of a pruning session without a landmark update: the evidence follows its particles, d_out[i] = d_in[d_anc[i]] (rows of
 // ev_stride bytes; bracketed as SLAM_PROF_PAGES like slam_gather_map_dev's table gathers; counted nowhere)
 extern "C" int slam_evidence_gather_dev(slam_engine* e, const uint8_t* d_in, uint8_t* d_out, int ev_stride, const int32_t* d_anc, int n);
 // engine_resample.hip: slam_ancestors_from_scan_dev that also marks the particles it kept (kernels.h: SurvivorOut); needs

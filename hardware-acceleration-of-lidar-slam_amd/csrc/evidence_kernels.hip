@@ -22,7 +22,6 @@ namespace slam {
 
 namespace {
 
-typedef __attribute__((address_space(1))) unsigned char guchar;
 typedef __attribute__((address_space(1))) unsigned int guint;
 
 // r2 of the visibility test: six separately rounded float32 operations (tests/_evidence_spec.py), never contracted

@@ -1,5 +1,5 @@
 // kernels.h — launchers of the gfx950 kernels, one section per kernel file in the Makefile's order; called by the C-ABI layer
-// (engine.hip and engine_match / engine_ekf / engine_resample.hip by stage), the particle-filter session (pf_session.hip) and the mapper (mapper.hip).
+// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_resample.hip by stage), the particle-filter session (pf_session.hip) and the mapper (mapper.hip).
 // Every launcher enqueues on `stream` and returns the hipError_t of the launch; none synchronises.
 #pragma once
 
@@ -180,8 +180,8 @@ hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a, const EventPa
 // split layout: the MEAN ROWS of launch_ekf_update alone, bit for bit — no log-likelihood, no class, no stamp is written; reads
 // the stored poses a.x / a.y / a.th; optionally for the survivors only (EkfArgs::survivor).  group_size as above.
 hipError_t launch_ekf_materialise(hipStream_t stream, const EkfArgs& a, const EventPair* ev, int group_size);
-// ---- ekf_aniso_kernels.hip: the same update with a full 2x2 measurement covariance Q in the sensor frame (ekf_aniso_math.h;
-// rows only: the posterior covariance then depends on the particle's heading).  Q and its float32 determinant:
+// The same update with a full 2x2 measurement covariance Q in the sensor frame (ekf_aniso_math.h, ekf_aniso_lane.h; rows
+// only: the posterior covariance then depends on the particle's heading).  Q and its float32 determinant:
 struct EkfAnisoCov {
     float qxx, qxy, qyy, detq;
 };
@@ -199,9 +199,19 @@ inline bool ekf_aniso_cov_ok(const EkfAnisoCov& q)
     const float big = 3.402823466e+38f;
     return q.qxx > 0.0f && q.qyy > 0.0f && q.detq > 0.0f && q.qxx <= big && q.qyy <= big && q.qxy >= -big && q.qxy <= big;
 }
-// one wavefront per particle, out of place (through a.anc, unobserved landmarks copied) or in place (a.map_in == a.map_out:
-// only observed landmarks touched); a.meas_var is not read, a.cov must be null
-hipError_t launch_ekf_aniso(hipStream_t stream, const EkfArgs& a, const EkfAnisoCov& q, const EventPair* ev = nullptr);
+// A per-particle table a landmark update reads its observations through: z of landmark l of particle i = det[assoc[i][l]]
+// (data association, assoc_kernels.hip below, makes it)
+struct EkfAssocTable {
+    const uint8_t* assoc;
+    int assoc_stride;
+    const float *det_zx, *det_zy;
+    int ndet;
+};
+// The one-wavefront-per-particle form of launch_ekf_update (which delegates to it) under either noise and either source of
+// observations: out of place (through a.anc, landmarks without an observation copied) or in place (a.map_in == a.map_out: only
+// landmarks with one touched); a.cov must be null. q == nullptr: noise a.meas_var * I, else R_w(theta_i) of *q (a.meas_var is not read; ekf_aniso_cov_ok(*q)).
+// tab == nullptr: observations a.obs_zx / a.obs_zy, else through *tab (a.obs_zx / a.obs_zy are not read).
+hipError_t launch_ekf_rows(hipStream_t stream, const EkfArgs& a, const EkfAnisoCov* q, const EkfAssocTable* tab, const EventPair* ev = nullptr);
 // ---- assoc_kernels.hip: data association (specification: tests/_assoc_spec.py).  The detections of a frame
 // are sensor-frame points WITHOUT identity; every particle decides for itself which of its landmarks each one belongs to and
 // which ones start a new landmark.  Rows only: the table is per particle, so "which landmarks a frame observes" is too.
@@ -221,24 +231,10 @@ struct AssocArgs {
     int32_t* stats;        // [n][3] matched, created, dropped; may be nullptr
     int xcd_chunk;         // set by the launcher
 };
-// one wavefront per particle; create: unmatched detections far from every seen landmark take the unseen slots
-hipError_t launch_associate(hipStream_t stream, const AssocArgs& a, bool create, const EventPair* ev = nullptr);
-// the table a landmark update reads its observations through: z of landmark l of particle i = det[assoc[i][l]]
-struct EkfAssocTable {
-    const uint8_t* assoc;
-    int assoc_stride;
-    const float *det_zx, *det_zy;
-    int ndet;
-};
-// the row update of launch_ekf_update's one-wavefront-per-particle form under such a table (a.obs_zx / a.obs_zy are not read;
-// a.cov must be null): out of place through a.anc, or in place (only landmarks with an association touched)
-hipError_t launch_ekf_assoc(hipStream_t stream, const EkfArgs& a, const EkfAssocTable& t, const EventPair* ev = nullptr);
-// Both under a full 2x2 sensor-frame measurement covariance (specification: tests/_assoc_aniso_spec.py): every particle gates,
-// matches, creates and updates with S = P + R_w(theta_i); a.meas_var is not read.  The argument checks of the two above and
-// ekf_aniso_cov_ok(q).
-hipError_t launch_associate_aniso(hipStream_t stream, const AssocArgs& a, const EkfAnisoCov& q, bool create, const EventPair* ev = nullptr);
-hipError_t launch_ekf_assoc_aniso(hipStream_t stream, const EkfArgs& a, const EkfAssocTable& t, const EkfAnisoCov& q,
-                                  const EventPair* ev = nullptr);
+// one wavefront per particle; create: unmatched detections far from every seen landmark take the unseen slots.  q (optional):
+// a full 2x2 sensor-frame measurement covariance (specification: tests/_assoc_aniso_spec.py) — every particle gates, matches and
+// creates with S = P + R_w(theta_i), a.meas_var is not read, ekf_aniso_cov_ok(*q) is checked; nullptr: a.meas_var * I
+hipError_t launch_associate(hipStream_t stream, const AssocArgs& a, const EkfAnisoCov* q, bool create, const EventPair* ev = nullptr);
 // ---- evidence_kernels.hip: landmark existence evidence (specification: tests/_evidence_spec.py).  One byte
 // c in [0, cmax] per (particle, landmark slot) beside the rows; behind the update of a frame a matched landmark gains `hit`, a
 // visible unmatched one loses `miss`, and one that cannot pay is pruned: its slot gets the bits of a slot that was never used.

@@ -136,17 +136,17 @@ struct slam_pf {
     // slam_pf_refine_set: sweeps > 0: the front launch of a frame is motion + refine (refine_kernels.hip), never the fused front
     float refine_step_xy = 0.0f, refine_step_theta = 0.0f;
     int refine_sweeps = 0;
-    // slam_pf_meas_cov_set (rows only): a full 2x2 measurement covariance — the landmark update of every frame is
-    // slam_ekf_update_aniso_dev, a launch of its own (never the fused front)
+    // slam_pf_meas_cov_set (rows only): a full 2x2 measurement covariance — the landmark update of every frame runs under it
+    // (update_noise), a launch of its own (never the fused front)
     bool aniso = false;
     float meas_cov[3] = { 0.0f, 0.0f, 0.0f };
     // slam_pf_assoc_set (rows only, one GPU): the frame's observations are detections without identity — every frame that uses
-    // observations runs slam_associate_dev and then slam_ekf_update_assoc_dev, two launches of their own (never the fused front)
+    // observations runs the association and then the update under its table, two launches of their own (never the fused front)
     bool assoc_on = false;
     float assoc_gate = 0.0f, assoc_new_gate = 0.0f;
     int assoc_create = 0;
-    // slam_pf_assoc_cov_set: association under a full 2x2 Q — the same frames with slam_associate_aniso_dev and
-    // slam_ekf_update_assoc_aniso_dev as the two launches (assoc_cov is read only while assoc_aniso is set; `aniso` above stays false)
+    // slam_pf_assoc_cov_set: association under a full 2x2 Q — the same two launches under it (update_noise; assoc_cov is read only
+    // while assoc_aniso is set; `aniso` above stays false)
     bool assoc_aniso = false;
     float assoc_cov[3] = { 0.0f, 0.0f, 0.0f };
     uint8_t* assoc_tab = nullptr;     // [n][Lp] the last frame's table, indexed like `score`; made by the first slam_pf_assoc_set
@@ -1091,6 +1091,14 @@ int gate_and_exchange(slam_pf* pf, FrameFacts& f, bool* collective_verdict)
     return SLAM_OK;
 }
 
+// which measurement noise this frame's landmark update (and its association) uses on rows: the 2x2 covariance in force — the
+// association's own while association is on (slam_pf_assoc_cov_set), else slam_pf_meas_cov_set's — or meas_var * I
+slam_meas_noise update_noise(const slam_pf* pf)
+{
+    if (pf->assoc_on ? pf->assoc_aniso : pf->aniso) return slam_meas_noise{ 0.0f, pf->assoc_on ? pf->assoc_cov : pf->meas_cov, true };
+    return slam_meas_noise{ pf->cfg.meas_var, nullptr, false };
+}
+
 // 3. per-landmark EKF (+ fused gather) and the weights, one function per storage form.  Rows: in place, out of place, gather only
 int update_rows(slam_pf* pf, const FrameFacts& f)
 {
@@ -1101,20 +1109,16 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
     float* dst = f.dst;
     if (f.ekf) {
         if (f.sample_obs) SLAM_HIP_TRY(e, launch_obs_count(e->stream, e->d_obs_zx, e->d_obs_zy, L, dev_word(pf, RES_OBS), ++pf->obs_seq_issued, pf->votes));
+        // (fused: the update went out with the score; in place: no gather, the buffers do not flip)
+        float* out = pf->map[f.in_place ? mc : mn];
+        const int32_t* anc = f.in_place ? nullptr : f.anc;
+        const slam_meas_noise noise = update_noise(pf);
         if (pf->assoc_on) {   // detections without identity: the observation table is not read
-            float* out = pf->map[f.in_place ? mc : mn];
-            const int32_t* anc = f.in_place ? nullptr : f.anc;
-            if (int rc = pf->assoc_aniso
-                             ? slam_associate_aniso_dev(e, pf->map[mc], stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->assoc_cov,
-                                                        pf->assoc_gate, pf->assoc_new_gate, pf->assoc_create, pf->assoc_tab, pf->Lp,
-                                                        pf->assoc_stats)
-                             : slam_associate_dev(e, pf->map[mc], stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->cfg.meas_var,
-                                                  pf->assoc_gate, pf->assoc_new_gate, pf->assoc_create, pf->assoc_tab, pf->Lp, pf->assoc_stats))
+            const slam_assoc_view table{ pf->assoc_tab, pf->Lp };
+            if (int rc = slam_engine_associate(e, pf->map[mc], stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, noise, pf->assoc_gate,
+                                               pf->assoc_new_gate, pf->assoc_create, pf->assoc_tab, pf->Lp, pf->assoc_stats))
                 return rc;
-            if (int rc = pf->assoc_aniso ? slam_ekf_update_assoc_aniso_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn,
-                                                                           anc, n, pf->assoc_cov, pf->assoc_tab, pf->Lp, nullptr)
-                                         : slam_ekf_update_assoc_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n,
-                                                                     pf->cfg.meas_var, pf->assoc_tab, pf->Lp, nullptr))
+            if (int rc = slam_engine_ekf_update(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, noise, &table, nullptr))
                 return rc;
             // existence evidence, on the row the update wrote: through the frame's gather into the other buffer, or in place
             if (pf->prune_on)
@@ -1122,13 +1126,8 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
                                                         pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit, pf->prune_miss,
                                                         pf->prune_cmax, pf->prune_range, pf->ev_stats))
                     return rc;
-        } else if (!f.fused) {   // (fused: the update went out with the score; in place: no gather, the buffers do not flip)
-            float* out = pf->map[f.in_place ? mc : mn];
-            const int32_t* anc = f.in_place ? nullptr : f.anc;
-            if (int rc = pf->aniso ? slam_ekf_update_aniso_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n,
-                                                               pf->meas_cov, nullptr)
-                                   : slam_ekf_update_dev(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n,
-                                                         pf->cfg.meas_var, nullptr))
+        } else if (!f.fused) {
+            if (int rc = slam_engine_ekf_update(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, noise, nullptr, nullptr))
                 return rc;
         }
         if (!f.in_place) pf->map_cur = mn;
@@ -1665,10 +1664,8 @@ int slam_pf_meas_cov_set(slam_pf* pf, const float meas_cov[3])
                                                 "row layout (map_layout = SLAM_MAP_ROWS, n_landmarks > 0)");
         return SLAM_ERR_INVALID_ARG;
     }
-    if (!ekf_aniso_cov_ok(ekf_aniso_cov(meas_cov))) {
-        snprintf(pf->e->err, sizeof pf->e->err, "meas_cov must be finite with qxx > 0, qyy > 0 and qxx * qyy - qxy * qxy > 0 in float32");
-        return SLAM_ERR_INVALID_ARG;
-    }
+    EkfAnisoCov q;
+    if (!slam_aniso_cov_from(pf->e, meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
     const bool iso = meas_cov[0] == pf->cfg.meas_var && meas_cov[1] == 0.0f && meas_cov[2] == pf->cfg.meas_var;
     if (pf->assoc_on && !iso) {
         snprintf(pf->e->err, sizeof pf->e->err, "data association is on (slam_pf_assoc_set): it gates with meas_var * I, a 2x2 "
@@ -1727,10 +1724,8 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
 int slam_pf_assoc_cov_set(slam_pf* pf, const float meas_cov[3], float gate, float new_gate, int create)
 {
     if (!pf || !meas_cov) return SLAM_ERR_INVALID_ARG;
-    if (!ekf_aniso_cov_ok(ekf_aniso_cov(meas_cov))) {
-        snprintf(pf->e->err, sizeof pf->e->err, "meas_cov must be finite with qxx > 0, qyy > 0 and qxx * qyy - qxy * qxy > 0 in float32");
-        return SLAM_ERR_INVALID_ARG;
-    }
+    EkfAnisoCov q;
+    if (!slam_aniso_cov_from(pf->e, meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
     if (gate == 0.0f) {   // slam_pf_assoc_set(0, ..) is the switch-off: here a gate has to be given
         snprintf(pf->e->err, sizeof pf->e->err, "association needs a finite gate > 0 (slam_pf_assoc_set(0, ..) switches it off)");
         return SLAM_ERR_INVALID_ARG;
@@ -1801,8 +1796,7 @@ int slam_pf_detect_set(slam_pf* pf, const slam_detect_params* params)
         return SLAM_ERR_INVALID_ARG;
     }
     if (!slam_detect_params_ok(params)) {
-        snprintf(e->err, sizeof e->err, "the detector needs finite jump, guard, max_width and max_range > 0, guard >= jump, "
-                                        "1 <= min_points <= max_points <= %d and wrap in {0, 1}", (int)SLAM_DETECT_MAX_POINTS);
+        slam_detect_params_error(e);
         return SLAM_ERR_INVALID_ARG;
     }
     pf->detect_on = true;

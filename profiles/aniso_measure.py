@@ -36,7 +36,7 @@ e.ekf_form_set(0)
 cov = (0.02, 0.012, 0.015)
 calls = {
     "isotropic, form 0 (ekf_update_kernel)": lambda: e.ekf_update_dev(d_in, d_out, 5 * Lp, Lp, L, x, y, th, anc, n, 0.02, None),
-    "2x2 Q (ekf_aniso_kernel)": lambda: e.ekf_update_aniso_dev(d_in, d_out, 5 * Lp, Lp, L, x, y, th, anc, n, cov, None),
+    "2x2 Q (ekf_update_kernel, EkfNoiseAniso)": lambda: e.ekf_update_aniso_dev(d_in, d_out, 5 * Lp, Lp, L, x, y, th, anc, n, cov, None),
 }
 for call in calls.values():
     for _ in range(5):

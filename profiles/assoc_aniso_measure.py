@@ -78,8 +78,8 @@ alternate({
 st = d_stats.sum(dim=0).cpu().numpy() / n
 print(f"      per particle (2x2): matched {st[0]:.2f}  created {st[1]:.2f}  dropped {st[2]:.2f}")
 alternate({
-    "ekf_assoc_kernel<2, out of place> (slam_ekf_update_assoc_dev)": lambda: e.ekf_update_assoc_dev(d_in, d_out, 5 * Lp, Lp, L, *pose, anc, n, Q, tabs["iso"], Lp, None),
-    "ekf_assoc_aniso_kernel<2, out of place> (.._assoc_aniso_dev)": lambda: e.ekf_update_assoc_aniso_dev(d_in, d_out, 5 * Lp, Lp, L, *pose, anc, n, COV, tabs["aniso"], Lp, None),
+    "table update, meas_var * I (slam_ekf_update_assoc_dev)": lambda: e.ekf_update_assoc_dev(d_in, d_out, 5 * Lp, Lp, L, *pose, anc, n, Q, tabs["iso"], Lp, None),
+    "table update, 2x2 Q (slam_ekf_update_assoc_aniso_dev)": lambda: e.ekf_update_assoc_aniso_dev(d_in, d_out, 5 * Lp, Lp, L, *pose, anc, n, COV, tabs["aniso"], Lp, None),
 }, pkg.Engine.PROF_EKF)
 e.close()
 del d_in, d_out, tabs

@@ -1,4 +1,4 @@
-"""slam_ekf_update_aniso_dev (the landmark update with a 2x2 sensor-frame measurement covariance, csrc/ekf_aniso_kernels.hip)
+"""slam_ekf_update_aniso_dev (the landmark update with a 2x2 sensor-frame measurement covariance, csrc/ekf_kernels.hip under EkfNoiseAniso)
 against its specification tests/_aniso_spec.py, bit for bit: rows, log-likelihoods, unobserved landmarks, and the columns
 below L whatever the padding holds.  Every (n, L) runs the three forms x four observation patterns x two covariances."""
 import numpy as np
