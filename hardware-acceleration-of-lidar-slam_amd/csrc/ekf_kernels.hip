@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) __attribute__((amdgpu_waves_per_eu(
 void ekf_split_kernel(EkfArgs a)
 {
     __shared__ float s_acc[kEkfWaves][G][128];
-    ekf_split_body<NB, G, false>(a, xcd_block(a.xcd_chunk), s_acc, MotionIO{}, MotionParams{});
+    ekf_split_body<NB, G, kPosesRead>(a, xcd_block(a.xcd_chunk), s_acc, MotionIO{}, MotionParams{});
 }
 
 // the mean rows of the split update alone (ekf_split_body, TALLY = false): survivor rows, launch_ekf_materialise
@@ -81,7 +81,7 @@ template <int NB, int G>
 __global__ __launch_bounds__(kEkfWaves * 64) __attribute__((amdgpu_waves_per_eu(kEkfSplitWpe, kEkfSplitWpe)))
 void ekf_materialise_kernel(EkfArgs a)
 {
-    ekf_split_body<NB, G, false, true, false>(a, xcd_block(a.xcd_chunk), nullptr, MotionIO{}, MotionParams{});
+    ekf_split_body<NB, G, kPosesRead, true, false>(a, xcd_block(a.xcd_chunk), nullptr, MotionIO{}, MotionParams{});
 }
 
 // ---- measurement support (slam_profile_copy_ceiling): the access shape of ekf_update_kernel without its arithmetic

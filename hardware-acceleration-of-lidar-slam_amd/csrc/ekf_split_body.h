@@ -121,17 +121,24 @@ __device__ __forceinline__ void split_apply(const SplitBatch<NB>& b, const EkfPo
 // without its poses — the gather indices, the classes, the loads of its first pass —, so the round trips of those run while
 // the samples are made; every wavefront of a workgroup with a particle reaches it, also one that has no particle of its own
 // or whose group this launch leaves out (group_filter).
-template <int NB, int G, bool OWN_MOTION, bool MEANS = true, bool TALLY = true>
-__device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float (*s_acc)[G][128], const MotionIO& mio,
-                                               const MotionParams& mpar, float4* s_motion = nullptr)
+// OWN_MOTION = kPosesStaged (frame_particle_kernel of front_kernels.hip, whose workgroups score their particles first): the samples
+// lie in s_motion already, behind a barrier of the caller's — nothing is made here and nothing waited for.
+// ekf_split_group is the update of ONE group: the G particles from `first + slot * G` on, `first` the first particle of the
+// workgroup, whose samples s_motion holds from particle `first` on; wavefront `wave` of the workgroup works on it, with
+// s_acc[wave].  A wavefront may take several groups one after the other (kPosesStaged, kPosesRead: no barrier inside).
+// s_ll (optional, TALLY): the group's log-likelihood totals are left in s_ll[slot * G ...] as well, for a later phase of the workgroup.
+enum : int { kPosesRead = 0, kPosesMade = 1, kPosesStaged = 2 };
+
+template <int NB, int G, int OWN_MOTION, bool MEANS = true, bool TALLY = true>
+__device__ __forceinline__ void ekf_split_group(const EkfArgs& a, int first, int slot, int wave, float (*s_acc)[G][128],
+                                                const MotionIO& mio, const MotionParams& mpar, float4* s_motion = nullptr,
+                                                float* s_ll = nullptr)
 {
     const unsigned lane = threadIdx.x & 63u;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int first = bid * kEkfWaves * G;   // the workgroup's first particle
-    const int g0 = first + wave * G;
+    const int g0 = first + slot * G;
     if (first >= a.n) return;   // (a surplus workgroup of the padded grid: all its wavefronts leave)
     bool skip = g0 >= a.n;      // wave-uniform: nothing to update here
-    if constexpr (!OWN_MOTION)
+    if constexpr (OWN_MOTION != kPosesMade)
         if (skip) return;
     const int nslots = skip ? 0 : a.n - g0 < G ? a.n - g0 : G;
     // lane k prepares particle g0 + k: source row, class, pose; read back with v_readlane below
@@ -146,11 +153,11 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
     if (a.group_filter) {   // sharded: this launch takes the groups fed from local rows only (1) or the others (2)
         const bool remote = __ballot(src_l >= a.n) != 0;
         if (remote != (a.group_filter == 2)) {
-            if constexpr (!OWN_MOTION) return;
+            if constexpr (OWN_MOTION != kPosesMade) return;
             skip = true;
         }
     }
-    const int cls_l = a.cls_in[OWN_MOTION && skip ? mine : src_l];   // (a group left out may have its source rows elsewhere)
+    const int cls_l = a.cls_in[OWN_MOTION == kPosesMade && skip ? mine : src_l];   // (a group left out may have its source rows elsewhere)
     const int pl = __builtin_amdgcn_readfirstlane(a.plane_stride * 4);
     const int mean_bytes = 2 * pl, cov_bytes = 3 * pl;
     const gchar* ozx = uniform_gptr(a.obs_zx);
@@ -232,7 +239,7 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
 
     constexpr unsigned kStep = 128u * NB;
     Raw cur;   // the loads of a pass are issued at the end of the pass before it; those of the first one ahead of the poses
-    if constexpr (OWN_MOTION) {
+    if constexpr (OWN_MOTION == kPosesMade) {
         if (wave == 0) {   // particle first + lane in lane < kEkfWaves * G: the whole workgroup's samples in one wavefront
             const int i = first + (int)lane;
             if ((int)lane < kEkfWaves * G && i < a.n) {
@@ -250,13 +257,16 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
         if (!skip && L > 0) issue(0, cur);
         __syncthreads();
         if (skip) return;
-        const float4 m = s_motion[wave * G + ((int)lane < nslots ? (int)lane : 0)];
+    } else {
+        if (L > 0) issue(0, cur);
+    }
+    if constexpr (OWN_MOTION != kPosesRead) {
+        const float4 m = s_motion[slot * G + ((int)lane < nslots ? (int)lane : 0)];
         px_l = m.x;
         py_l = m.y;
         st_l = m.z;
         ct_l = m.w;
     } else {
-        if (L > 0) issue(0, cur);
         det_sincosf(a.th[mine], st_l, ct_l);
         px_l = a.x[mine];
         py_l = a.y[mine];
@@ -328,7 +338,19 @@ __device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float 
         tot[k] = acc[0] + acc[1];
     }
     const float total = wave_halving_tree_sums<G>(tot, lane);   // lane k < G: the sum of particle g0 + k
-    if ((int)lane < nslots) store_loglik(a, g0 + (int)lane, total);
+    if ((int)lane < nslots) {
+        store_loglik(a, g0 + (int)lane, total);
+        if (s_ll) s_ll[slot * G + (int)lane] = total;
+    }
+}
+
+// a workgroup of kEkfWaves wavefronts with one group each: workgroup `bid` takes the particles from bid * kEkfWaves * G on
+template <int NB, int G, int OWN_MOTION, bool MEANS = true, bool TALLY = true>
+__device__ __forceinline__ void ekf_split_body(const EkfArgs& a, int bid, float (*s_acc)[G][128], const MotionIO& mio,
+                                               const MotionParams& mpar, float4* s_motion = nullptr)
+{
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    ekf_split_group<NB, G, OWN_MOTION, MEANS, TALLY>(a, bid * kEkfWaves * G, wave, wave, s_acc, mio, mpar, s_motion);
 }
 
 // (A second form of this update — ONE PASS PER WAVEFRONT: the four wavefronts of a workgroup take the passes of a row side by

@@ -318,10 +318,11 @@ int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src_x, const f
                          const int32_t* d_anc, float* d_x, float* d_y, float* d_th, int n, int64_t first_id, const float dp[3],
                          const float sigma[3], uint64_t seed, uint32_t frame, float* d_score, int32_t* d_count,
                          const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride, int nlandmarks,
-                         float meas_var, bool* launched, const slam::SplitIO* split, float* d_obs_save)
+                         float meas_var, bool* launched, const slam::SplitIO* split, float* d_obs_save, const slam_front_weights* weights)
 {
     SLAM_ENTER(e);
     *launched = false;
+    if (weights) *weights->made = false;
     if (!e->frame_fusion) return SLAM_OK;
     if (e->prof_mask & (1 << SLAM_PROF_SCORE)) return SLAM_OK;   // the score stage is being timed: it stays a launch of its own
     // the checks of slam_motion_score_dev and of slam_ekf_update_dev (out of place)
@@ -346,8 +347,25 @@ int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src_x, const f
     // one bracket for the whole launch: it counts as the frame's landmark update (the dominant stage)
     ScoreGrid sg;
     if (int rc = many_pose_grid(e, slot, n, &sg)) return rc;
+    // the weights too where one workgroup scores and updates the same particles (no resample gate: its carried weights and its
+    // scan stay with the weights' launch); the block maxima go where slam_logweight_dev leaves them
+    FrontWeights fw{};
+    bool weighted = false;
+    if (weights && weights->d_logw && e->gate_frac_q16 == 0) {
+        if (e->bmax_buf.cap < sizeof(float) * (size_t)logweight_scratch_floats()) {
+            SLAM_HIP_TRY(e, e->bmax_buf.ensure(sizeof(float) * (size_t)logweight_scratch_floats()));
+            SLAM_HIP_TRY(e, hipMemsetAsync(e->bmax_buf.p, 0, e->bmax_buf.cap, e->stream));
+        }
+        fw = FrontWeights{ weights->score_gain, weights->d_logw, e->bmax_buf.as<float>(), nullptr, nullptr, &weighted };
+    }
     SLAM_HIP_TRY(e, launch_frame_front(e->stream, sg, e->d_bx, e->d_by, e->nbeams, io, first_id, dp, sigma, seed,
-                                       frame, d_score, d_count, a, group, e->prof_next(SLAM_PROF_EKF), launched, &lanes, d_obs_save));
+                                       frame, d_score, d_count, a, group, e->prof_next(SLAM_PROF_EKF), launched, &lanes, d_obs_save,
+                                       fw.logw ? &fw : nullptr));
+    if (weighted) {
+        e->bmax_count = (n + 63) / 64;
+        e->bmax_n = n;
+        *weights->made = true;
+    }
     if (*launched) {
         e->front_last[0] = group;
         e->front_last[1] = lanes;

@@ -339,12 +339,23 @@ __attribute__((visibility("hidden"))) int many_pose_grid(slam_engine* e, int slo
 // date by workgroups of the same launch (launch_logweight)
 extern "C" int slam_logweight_cov_dev(slam_engine* e, const float* d_score, bool use_ekf, float score_gain, int n, float* d_logw, float* d_max,
                            const slam::CovArgs* cov, int cov_bound);
+// slam_quantise_scan_dev(d_max = nullptr) on one GPU with a split session's covariance classes brought up to date by workgroups
+// of the same launch (launch_quantise_scan): the form for a frame whose weights the front launch made
+extern "C" int slam_quantise_scan_cov_dev(slam_engine* e, const float* d_logw, int n, const slam::CovArgs* cov, int cov_bound);
 // engine_ekf.hip:
 // slam_motion_score_dev with a rider
 extern "C" int slam_motion_score_rider_dev(slam_engine* e, int slot, const float* d_src_x, const float* d_src_y, const float* d_src_th,
                                            const int32_t* d_anc, float* d_x, float* d_y, float* d_th, int n, int64_t first_id,
                                            const float dp[3], const float sigma[3], uint64_t seed, uint32_t frame, float* d_score,
                                            int32_t* d_count, const slam::FreeListRider* rider, bool* rode);
+// weights (optional): the frame's log-weights may come out of the front launch as well (kernels.h: FrontWeights) — score_gain
+// and d_logw as slam_logweight_cov_dev takes them; *made = true: they did, the block maxima are where slam_quantise_scan_dev
+// looks for them, and the frame needs no weights' launch (its classes' update: slam_quantise_scan_cov_dev)
+struct slam_front_weights {
+    float score_gain;
+    float* d_logw;
+    bool* made;
+};
 // slam_motion_score_dev + slam_ekf_update_dev (out of place, through the resample indices d_anc) as ONE launch
 // (launch_frame_front).  *launched = false: the shapes do not fit or fusion is off — nothing was issued, the caller makes
 // the two calls.  Used by the slam_pf session for single-GPU frames on rows.
@@ -352,7 +363,8 @@ extern "C" int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src
                          const int32_t* d_anc, float* d_x, float* d_y, float* d_th, int n, int64_t first_id, const float dp[3],
                          const float sigma[3], uint64_t seed, uint32_t frame, float* d_score, int32_t* d_count,
                          const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride, int nlandmarks,
-                         float meas_var, bool* launched, const slam::SplitIO* split = nullptr, float* d_obs_save = nullptr);
+                         float meas_var, bool* launched, const slam::SplitIO* split = nullptr, float* d_obs_save = nullptr,
+                         const slam_front_weights* weights = nullptr);
 // survivor rows: d_obs_save != nullptr asks slam_frame_front_dev for the launch that writes no mean row (split only) and keeps
 // the observation table there ([2][plane_stride]); this is the launch that writes them later, from the same inputs — the mean
 // rows of slam_ekf_split_dev bit for bit and nothing else (the stored poses; split->cov / covx: the PRIOR class rows; cls_out,

@@ -69,9 +69,9 @@ int slam_logweight_cov_dev(slam_engine* e, const float* d_score, bool use_ekf, f
     return logweight_common(e, d_score, use_ekf ? e->ll_buf.as<float>() : nullptr, score_gain, n, d_logw, d_max, cov, cov_bound);
 }
 
-int slam_quantise_scan_dev(slam_engine* e, const float* d_logw, const float* d_max, int n, uint64_t* d_sum)
+static int quantise_scan_common(slam_engine* e, const float* d_logw, const float* d_max, int n, uint64_t* d_sum, const CovArgs* cov,
+                                int cov_bound)
 {
-    SLAM_ENTER(e);
     if (n <= 0 || !d_logw) return SLAM_ERR_INVALID_ARG;
     if (!d_max && e->bmax_n != n) return SLAM_ERR_NOT_READY;   // needs the maxima of slam_logweight_dev(n)
     const size_t ntiles = (size_t)scan_tile_count(n);
@@ -85,10 +85,24 @@ int slam_quantise_scan_dev(slam_engine* e, const float* d_logw, const float* d_m
     }
     const ProfScope prof(e, SLAM_PROF_SCAN);
     SLAM_HIP_TRY(e, launch_quantise_scan(e->stream, d_logw, d_max, e->bmax_buf.as<float>(), e->bmax_count, n, cdf, tiles, d_sum,
-                                         carry, tiles + ntiles, tiles + 2 * ntiles, e->gate_buf.as<unsigned int>() + kGateTicketWord));
+                                         carry, tiles + ntiles, tiles + 2 * ntiles, e->gate_buf.as<unsigned int>() + kGateTicketWord, cov,
+                                         cov_bound));
     e->scan_n = n;
     e->carry_n = carry ? n : -1;
     return SLAM_OK;
+}
+
+int slam_quantise_scan_dev(slam_engine* e, const float* d_logw, const float* d_max, int n, uint64_t* d_sum)
+{
+    SLAM_ENTER(e);
+    return quantise_scan_common(e, d_logw, d_max, n, d_sum, nullptr, 0);
+}
+
+int slam_quantise_scan_cov_dev(slam_engine* e, const float* d_logw, int n, const CovArgs* cov, int cov_bound)
+{
+    SLAM_ENTER(e);
+    if (e->gate_frac_q16 != 0) return SLAM_ERR_INVALID_ARG;   // (the rider exists for the ungated scan alone)
+    return quantise_scan_common(e, d_logw, nullptr, n, nullptr, cov, cov_bound);
 }
 
 int slam_offspring_from_scan_dev(slam_engine* e, int n, const uint64_t* d_base, const uint64_t* d_total, uint64_t seed,

@@ -7,10 +7,12 @@
 // workgroups of both kinds are dealt out interleaved — of every `score_octets + ekf_octets` consecutive octets of workgroups
 // (an octet = one workgroup per XCD) the scoring ones are spread evenly — so the gathers run in the shadow of the row
 // stores.  Same bits as the two launches (same device functions).
+// A survivor-rows frame (no row stores) of the flagship shape goes to frame_particle_kernel below instead: one kind of workgroup.
 
 #include "ekf_group_body.h"
 #include "ekf_split_body.h"
 #include "score_body.h"
+#include "pf_common.h"
 
 namespace slam {
 
@@ -32,6 +34,18 @@ struct FrontArgs {
     float* obs_save;     // MEANS = false: [2][plane_stride], the observation table as this frame's update saw it
 };
 
+// the workgroup behind the grid of a survivor-rows frame's front launch: the observation table as this frame's update saw it, kept
+// for the launch that writes the survivors' rows later (the caller's table may be rewritten as soon as the frame is issued)
+__device__ __forceinline__ void obs_save_body(const FrontArgs& f, int threads)
+{
+    const int L = f.a.nlandmarks, Lp = f.a.plane_stride;
+    const float nan = __uint_as_float(0x7fc00000u);
+    for (int l = (int)threadIdx.x; l < Lp; l += threads) {
+        f.obs_save[l] = l < L ? f.a.obs_zx[l] : nan;
+        f.obs_save[Lp + l] = l < L ? f.a.obs_zy[l] : nan;
+    }
+}
+
 // MEANS = false (split only): a survivor-rows frame — the updating workgroups write no mean row (ekf_split_body), and one workgroup
 // behind the grid keeps a copy of the observation table for the launch that writes the survivors' rows later
 constexpr int front_wpe(bool split, bool means) { return !split ? kEkfGroupWpe : means ? kEkfSplitWpe : kEkfSplitWpeNoStore; }
@@ -48,13 +62,8 @@ void frame_front_kernel(FrontArgs f)
     __shared__ float4 s_motion[kScoreBlock / 4];
     static_assert(kEkfWaves * G <= kScoreBlock / 4, "s_motion holds an updating workgroup's particles");
     if constexpr (!MEANS) {
-        if (blockIdx.x == gridDim.x - 1) {   // (the caller's table may be rewritten as soon as the frame is issued)
-            const int L = f.a.nlandmarks, Lp = f.a.plane_stride;
-            const float nan = __uint_as_float(0x7fc00000u);
-            for (int l = (int)threadIdx.x; l < Lp; l += kEkfWaves * 64) {
-                f.obs_save[l] = l < L ? f.a.obs_zx[l] : nan;
-                f.obs_save[Lp + l] = l < L ? f.a.obs_zy[l] : nan;
-            }
+        if (blockIdx.x == gridDim.x - 1) {
+            obs_save_body(f, kEkfWaves * 64);
             return;
         }
     }
@@ -71,10 +80,80 @@ void frame_front_kernel(FrontArgs f)
         score_poses_body<false, LPP, DEPTH, true, PACKED>(f.g, f.bx, f.by, f.nbeams, f.mio.x, f.mio.y, f.mio.th, nullptr, f.a.n,
                                                           f.score, f.count, f.mio, f.mpar, sb, s_pair, s_motion);
     } else if constexpr (SPLIT) {
-        ekf_split_body<NB, G, true, MEANS>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar, s_motion);
+        ekf_split_body<NB, G, kPosesMade, MEANS>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar, s_motion);
     } else {
         ekf_group_body<NB, G, true>(f.a, xcd * f.ekf_octets + (o - before), s_acc, f.mio, f.mpar);
     }
+}
+
+// ---- A particle's score, its landmark update and its weight in ONE workgroup (a survivor-rows frame of the split layout, 8 particles
+// per wavefront, four lanes per pose): workgroup b owns particles [64 b, 64 b + 64), XCD-contiguous as the updating workgroups
+// above.  With MEANS = false the launch stores no rows, so there is no HBM traffic left for the gathers to hide behind (the
+// reason for the two kinds of workgroup above); and a score and a log-likelihood that come out of the same workgroup meet in LDS,
+// which saves the weights' launch and the second motion sample of every particle.
+//   stage: beams, decode table, the 64 motion samples by the last wavefront (score_stage), barrier;
+//   S: the scorer on the 64 poses (score_poses_body, STAGED), every quad's score also into s_score;
+//   U: each wavefront updates groups `wave` and `wave + 4` of the workgroup's eight groups of eight, one after the other, the
+//      poses from the staged samples (ekf_split_group, kPosesStaged), every particle's log-likelihood also into s_ll;
+//   barrier; W: thread t < 64 makes particle 64 b + t's log-weight (log_weight_of) and the first wavefront the block's maximum
+//      (the per-element rule of logweight_kernel, then fmaxf across the lanes: the maximum of a set, however it is blocked).
+// The workgroups whose blockIdx.x has bit 8 set run U before S, so that neighbours on a compute unit gather while the others compute:
+// an XCD's workgroups (blockIdx.x >> 3 = 0, 1, ..) are dealt to its 32 compute units in turn, so with all of the bench shape's 1 024
+// workgroups resident at once, 4 per unit, the four of a unit are 32 apart there and two of them run each order.  For other
+// populations (fewer than 4 per unit, or a second round) neighbours need not alternate: the results are the same bits either way,
+// the measured gain belongs to 65 536 particles.  (The same order in every workgroup was measured and dropped: figures below.)
+// The same device functions on the same inputs as the kernels above plus logweight_cov_kernel: the same bits.
+// Measured (profiles/r09_front_combined.md; ms per frame at 64k x 500, medians of four interleaved runs, the separate
+// launches 0.0752): S before U everywhere 0.0761 at 4 waves per SIMD (98 VGPRs), 0.0762 at 5 (95), 0.0785 at 6 (80);
+// alternating at 4 waves (99 VGPRs) 0.0728.  1 024 workgroups are 4 per compute unit, one wavefront per SIMD each.
+constexpr int kFrontParticleWpe = 4;
+constexpr int kFrontParticleG = 8;
+
+template <bool PACKED>
+__global__ __launch_bounds__(kScoreBlock) __attribute__((amdgpu_waves_per_eu(kFrontParticleWpe, kFrontParticleWpe)))
+void frame_particle_kernel(FrontArgs f, FrontWeights w)
+{
+    constexpr int G = kFrontParticleG, kOwn = kScoreBlock / 4;   // particles of a workgroup
+    static_assert(kOwn == 2 * kEkfWaves * G, "every wavefront takes two groups");
+    extern __shared__ float4 s_pair[];
+    __shared__ float s_acc[kEkfWaves][G][128];
+    __shared__ float4 s_motion[kOwn];
+    __shared__ float s_score[kOwn], s_ll[kOwn];
+    if (blockIdx.x == gridDim.x - 1) {
+        obs_save_body(f, kScoreBlock);
+        return;
+    }
+    const int n = f.a.n;
+    const int b = xcd_block(f.a.xcd_chunk), first = b * kOwn;
+    if (first >= n) return;   // (a surplus workgroup of the padded grid)
+    score_stage<4, kQuadDepth, true, PACKED>(f.g, f.bx, f.by, f.nbeams, f.mio.x, f.mio.y, f.mio.th, n, f.mio, f.mpar, b, s_pair, s_motion);
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int flip = ((int)blockIdx.x >> 8) & 1;
+#pragma nounroll
+    for (int step = 0; step < 2; ++step) {
+        if ((step ^ flip) == 0) {
+            score_poses_body<false, 4, kQuadDepth, true, PACKED, true>(f.g, f.bx, f.by, f.nbeams, f.mio.x, f.mio.y, f.mio.th, nullptr, n,
+                                                                       f.score, f.count, f.mio, f.mpar, b, s_pair, s_motion, s_score);
+        } else {
+#pragma nounroll
+            for (int r = 0; r < 2; ++r)
+                ekf_split_group<kEkfSplitNb, G, kPosesStaged, false>(f.a, first, wave + kEkfWaves * r, wave, s_acc, f.mio, f.mpar, s_motion,
+                                                                     s_ll);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;
+    const int t = (int)threadIdx.x, i = first + t;
+    const bool add_carry = w.carry && *w.prev_resampled == 0;
+    float m = -INFINITY;
+    if (i < n) {
+        const float lw = log_weight_of(s_ll[t], s_score[t] * w.gain, w.carry, add_carry, i);
+        w.logw[i] = lw;
+        m = lw > m ? lw : m;
+    }
+    m = wave_max(m);
+    if (t == 0) w.block_max[b] = m;
 }
 
 int update_blocks(int n, int group_size) { return (n + kEkfWaves * group_size - 1) / (kEkfWaves * group_size); }
@@ -92,9 +171,10 @@ bool frame_front_fits(int n, int nlandmarks, int group_size)
 hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const float* bx, const float* by, int nbeams,
                               const MotionIO& io, int64_t first_id, const float dp[3], const float sigma[3], uint64_t seed,
                               uint32_t frame, float* score, int32_t* count, const EkfArgs& a_in, int group_size,
-                              const EventPair* ev, bool* launched, int* lanes_per_pose, float* obs_save)
+                              const EventPair* ev, bool* launched, int* lanes_per_pose, float* obs_save, const FrontWeights* weights)
 {
     *launched = false;
+    if (weights) *weights->made = false;
     const int n = a_in.n;
     if (!a_in.cov && group_size == 8) group_size = 4;   // rows: 2 or 4 particles per updating wavefront
     if (a_in.map_in == a_in.map_out || !frame_front_fits(n, a_in.nlandmarks, group_size)) return hipSuccess;
@@ -120,6 +200,19 @@ hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const floa
     const int grid = 8 * f.score_span + (obs_save ? 1 : 0);
     const size_t lds = sizeof(float2) * (size_t)(nbeams + (quad ? 4 * kQuadDepth : kLaneDepth)) + (g.packed ? 1024 : 0);
     if (ev) (void)hipEventRecord(ev->start, stream);
+    // one workgroup per 64 particles, weights included (frame_particle_kernel), where the frame allows it
+    if (weights && weights->logw && weights->block_max && obs_save && f.a.cov && G == kFrontParticleG && quad && f.a.group_filter == 0 &&
+        (n + 63) / 64 <= kMaxWeightBlocks) {
+        f.a.xcd_chunk = ((n + 63) / 64 + 7) / 8;
+        const int pgrid = 8 * f.a.xcd_chunk + 1;
+        if (f.g.packed) frame_particle_kernel<true><<<pgrid, kScoreBlock, lds, stream>>>(f, *weights);
+        else frame_particle_kernel<false><<<pgrid, kScoreBlock, lds, stream>>>(f, *weights);
+        if (ev) (void)hipEventRecord(ev->stop, stream);
+        *launched = true;
+        *weights->made = true;
+        if (lanes_per_pose) *lanes_per_pose = 4;
+        return hipGetLastError();
+    }
     // the instantiation: particles per updating wavefront (8: split only) x scorer's lane mapping x map layout x grid copy read
     // ... x mean rows written or not (split only)
 #define SLAM_FRONT(G_, SP_, PK_, MN_)                                                                                             \

@@ -294,10 +294,24 @@ bool frame_front_fits(int n, int nlandmarks, int group_size);   // the shapes la
 // that this kernel does not take; nothing was issued.
 // obs_save (split layout only; nullptr: none): the launch writes NO mean row — everything else as ever, the same bits — and one
 // more workgroup copies the observation table to obs_save [2][plane_stride] (zx | zy), for launch_ekf_materialise to start from.
+// weights (optional): where the frame's log-weights and their block maxima go when ONE workgroup can both score and update
+// its particles (frame_particle_kernel: a survivor-rows frame of the split layout, 8 particles per wavefront, four lanes per
+// pose, one GPU, at most kMaxWeightBlocks workgroups of 64 particles); *weights->made says whether it did: then block_max
+// holds ceil(n / 64) maxima and no weights' launch is wanted.  Every other frame: the launch as ever, *made = false.
+constexpr int kMaxWeightBlocks = 2048;   // the block maxima a frame leaves at most, whichever launch makes them (logweight_scratch_floats)
+struct FrontWeights {
+    float gain;
+    float* logw;
+    float* block_max;
+    const float* carry;                // as launch_logweight's
+    const int32_t* prev_resampled;
+    bool* made;
+};
 hipError_t launch_frame_front(hipStream_t stream, const ScoreGrid& g, const float* bx, const float* by, int nbeams,
                               const MotionIO& io, int64_t first_id, const float dp[3], const float sigma[3], uint64_t seed,
                               uint32_t frame, float* score, int32_t* count, const EkfArgs& a, int group_size,
-                              const EventPair* ev, bool* launched, int* lanes_per_pose = nullptr, float* obs_save = nullptr);
+                              const EventPair* ev, bool* launched, int* lanes_per_pose = nullptr, float* obs_save = nullptr,
+                              const FrontWeights* weights = nullptr);
 // In-place update of the OBSERVED landmarks only (frames that keep their population): the observation table is first
 // compacted into a list in landmark order (ids, measurements, accumulator rounds; count[2] = {nobs, highest round} on the
 // device, {nobs, L} optionally in mapped host memory), then one lane per observation gathers, updates and scatters.
@@ -531,10 +545,12 @@ struct GateOut {
 // fused frame-loop form (quantise + tile scan; offsets straight from the tile-local scan).  The scan state is
 // cdf_local[n] followed by tile_total[ntiles] | tile_s16[ntiles] | tile_q16[ntiles] (the last two only with a gate:
 // carry != nullptr).  With a gate d_sum receives three values (total, S, Q) and d_shard_totals holds such triples.
+// cov (optional; ungated, block maxima): the launch carries the covariance classes' update as launch_logweight does — for a
+// frame whose front launch made the weights itself (launch_frame_front's FrontWeights), which has no weights' launch.
 hipError_t launch_quantise_scan(hipStream_t stream, const float* logw, const float* d_max, const float* block_max,
                                 int nblock_max, int n, uint64_t* cdf_local, uint64_t* tile_total, uint64_t* d_sum,
                                 float* carry = nullptr, uint64_t* tile_s16 = nullptr, uint64_t* tile_q16 = nullptr,
-                                unsigned int* ticket = nullptr);
+                                unsigned int* ticket = nullptr, const CovArgs* cov = nullptr, int cov_bound = 0);
 hipError_t launch_offspring_from_scan(hipStream_t stream, const uint64_t* cdf_local, const uint64_t* tile_total, int n,
                                       const uint64_t* d_base, const uint64_t* d_total, const uint64_t* d_shard_totals,
                                       int rank, int world, uint64_t seed, uint32_t frame, int64_t n_total,

@@ -808,7 +808,8 @@ int create_common(slam_engine* e, const slam_pf_config* cfg, slam_comm* comm, in
 // be at most: its length as of some earlier launch (mapped memory, read without waiting) plus the classes that arrived since
 // (sharded sessions) — the second word is the running count of arrivals as of that launch; it is read FIRST and written
 // last, so a torn pair only over-estimates; before anything of this epoch has arrived: every class there can be.
-// Gives the arguments and the width, and moves the bookkeeping on as if it had been launched: the weights' launch carries it.
+// Gives the arguments and the width, and moves the bookkeeping on as if it had been launched: the weights' launch carries it
+// (weights_with_classes), or the scan's on a frame whose front launch made the weights (update_split, scan_stage).
 void split_class_prepare(slam_pf* pf, int nlandmarks, bool save_prior, CovArgs& ca, int& bound)
 {
     ca.save_cov = save_prior ? pf->save_cov : nullptr;
@@ -884,6 +885,10 @@ struct FrameFacts {
     bool paged_listed;   // front: the page list is out, the free list rides with the scorer
     bool fused;          // front: the landmark update went out with the score
     bool survivors;      // front: ... and wrote no mean row (survivor rows): the resample marks whom it keeps, a launch behind it writes their rows
+    bool weighted;       // front: ... and made the log-weights and their block maxima as well: no weights' launch
+    bool classes_due;    // update: the classes' update (cov, cov_bound) has its arguments and still wants a launch to ride in: the scan's
+    CovArgs cov;
+    int cov_bound;
     bool in_place;       // gate: the last frame kept its population, the maps have not moved
 };
 
@@ -1033,10 +1038,13 @@ int front_stage(slam_pf* pf, FrameFacts& f, int slot, const float dp[3])
         const SplitIO sio = pf->split ? split_io(pf, comm ? 1 : 0, comm ? f.anc : nullptr) : SplitIO{};
         const float* map_in = pf->split ? pf->mean[pf->sp_cur] : pf->map[pf->map_cur];
         float* map_out = pf->split ? pf->mean[1 - pf->sp_cur] : pf->map[1 - pf->map_cur];
+        // (a survivor-rows frame may come back with its weights made as well: one workgroup scores and updates a particle)
+        const slam_front_weights fw{ pf->cfg.score_gain, pf->logw, &f.weighted };
         if (int rc = slam_frame_front_dev(e, slot, ps, ps + sn, ps + 2 * sn, pose_anc, dst, dst + sn, dst + 2 * sn, n, f.first_id, dp,
                                           pf->cfg.sigma, pf->cfg.seed, pf->frame, pf->score, pf->count, map_in, map_out,
                                           (pf->split ? 2 : 5) * (int64_t)pf->Lp, pf->Lp, pf->L, pf->cfg.meas_var, &f.fused,
-                                          pf->split ? &sio : nullptr, want_survivors ? pf->obs_save : nullptr))
+                                          pf->split ? &sio : nullptr, want_survivors ? pf->obs_save : nullptr,
+                                          want_survivors ? &fw : nullptr))
             return rc;
         f.survivors = f.fused && want_survivors;
         if (f.survivors) {   // (the rows of the frame before are read through its gather index only: no settle)  What this frame starts from:
@@ -1142,7 +1150,7 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
     return slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
 }
 
-int update_split(slam_pf* pf, const FrameFacts& f)
+int update_split(slam_pf* pf, FrameFacts& f)
 {
     slam_engine* e = pf->e;
     const int n = pf->n, L = pf->L, sc = pf->sp_cur;
@@ -1161,7 +1169,14 @@ int update_split(slam_pf* pf, const FrameFacts& f)
         }
         pf->cstamp_now++;
         pf->sp_cur = 1 - sc;
-        // ... then the classes' update, in place, once per class still in use
+        // ... then the classes' update, in place, once per class still in use: with the weights — or, when the front launch has
+        // made those, with the scan (scan_stage): it still runs behind the launch that stamped the classes and in front of the
+        // one that reads the saved priors
+        if (f.weighted) {
+            split_class_prepare(pf, L, f.survivors, f.cov, f.cov_bound);
+            f.classes_due = true;
+            return SLAM_OK;
+        }
         return weights_with_classes(pf, L, true, f.survivors);
     }
     if (f.anc) {   // means and classes follow their particles
@@ -1215,13 +1230,15 @@ int update_paged(slam_pf* pf, const FrameFacts& f)
                      : slam_logweight_dev(e, pf->score, nullptr, pf->cfg.score_gain, n, pf->logw, nullptr);
 }
 
-// 4. weights: the maximum over all ranks, then fixed-point weights scanned as they are produced
+// 4. weights: the maximum over all ranks, then fixed-point weights scanned as they are produced (a frame whose front launch made
+// the weights: the scan's launch carries the classes' update that the weights' launch would have carried)
 // Sharded: the ranks all-reduce the BLOCK maxima the weights' launch leaves in the engine (element by element: a few hundred
 // floats cost the wire what one costs) and the scan takes their maximum itself, as it does on one GPU — the maximum of the
 // same set of values, and one single-workgroup launch less per frame than reducing them to one float first.
-int scan_stage(slam_pf* pf)
+int scan_stage(slam_pf* pf, const FrameFacts& f)
 {
     slam_engine* e = pf->e;
+    if (f.classes_due) return slam_quantise_scan_cov_dev(e, pf->logw, pf->n, &f.cov, f.cov_bound);   // (one GPU, no gate)
     if (pf->comm) {
         if (e->bmax_n != pf->n || e->bmax_count <= 0) return SLAM_ERR_NOT_READY;
         if (int rc = comm_all_reduce_max_f32(pf->comm, e->bmax_buf.as<float>(), e->bmax_count)) return rc;
@@ -1276,7 +1293,7 @@ int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations,
     if (int rc = front_stage(pf, f, slot, dp)) return rc;
     if (int rc = gate_and_exchange(pf, f, collective_verdict)) return rc;
     if (int rc = pf->paged ? update_paged(pf, f) : pf->split ? update_split(pf, f) : update_rows(pf, f)) return rc;
-    if (int rc = scan_stage(pf)) return rc;
+    if (int rc = scan_stage(pf, f)) return rc;
     if (int rc = resample_stage(pf, f.dst, f.survivors)) return rc;
     pf->cur = 1 - pf->cur;
     pf->has_anc = true;

@@ -1,5 +1,5 @@
 // resample_kernels.hip — weights and resampling on one GPU: log-weights (with the covariance classes'
-// update riding along), maximum, quantise, tile scan, ESS gate, offspring offsets, ancestors; and the small result and gather
+// update riding along; behind the scan's tiles instead on a frame whose front launch made the weights), maximum, quantise, tile scan, ESS gate, offspring offsets, ancestors; and the small result and gather
 // kernels that use the same block reductions (arg-max, best particle, pose sums, gather_f32, gather_map).
 //
 // No reference counterpart: the specification is DESIGN.md + oracle/slam_oracle_pf.c, matched bit for bit.
@@ -13,13 +13,7 @@ namespace slam {
 namespace {
 
 // ------------------------------------------------------------------ A11: weights
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
+// (log_weight_of, wave_max: pf_common.h)
 // carry (optional): the normalised log-weights the previous frame left behind; they count only when that frame did
 // NOT resample (*prev_resampled == 0, a device flag written by the previous frame's resample kernel)
 __global__ __launch_bounds__(kBlock) void logweight_kernel(const float* __restrict__ score,
@@ -34,8 +28,7 @@ __global__ __launch_bounds__(kBlock) void logweight_kernel(const float* __restri
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
         const float ll = loglik ? loglik[i] : 0.0f;
         const float sc = score ? score[i] * gain : 0.0f;
-        float lw = ll - sc;
-        if (add_carry) lw = carry[i] + lw;
+        const float lw = log_weight_of(ll, sc, carry, add_carry, i);
         logw[i] = lw;
         m = lw > m ? lw : m;
     }
@@ -66,8 +59,7 @@ __global__ __launch_bounds__(kBlock) void logweight_cov_kernel(const float* __re
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += nw * kBlock) {
         const float ll = loglik ? loglik[i] : 0.0f;
         const float sc = score ? score[i] * gain : 0.0f;
-        float lw = ll - sc;
-        if (add_carry) lw = carry[i] + lw;
+        const float lw = log_weight_of(ll, sc, carry, add_carry, i);
         logw[i] = lw;
         m = lw > m ? lw : m;
     }
@@ -246,22 +238,19 @@ __device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t* s_red /*
 // GATED: also what the resample gate needs — the 16-bit weight sums S = sum(wq >> 16), Q = sum((wq >> 16)^2) of the
 // tile (exact integers, hence independent of order and sharding) and carry[i] = logw[i] - max, the weight a particle
 // takes into the next frame when this one does not resample (oracle: orc_ess_terms / orc_weight_carry).
+// tile `tile` of `ntiles`, by one workgroup (quantise_scan_kernel: the whole grid; quantise_scan_cov_kernel: its first part)
 template <bool GATED>
-__global__ __launch_bounds__(kBlock) void quantise_scan_kernel(const float* __restrict__ logw,
-                                                               const float* __restrict__ d_max,
-                                                               const float* __restrict__ block_max, int nblock_max,
-                                                               int n, uint64_t* __restrict__ cdf_local,
-                                                               uint64_t* __restrict__ tile_total,
-                                                               float* __restrict__ carry,
-                                                               uint64_t* __restrict__ tile_s16,
-                                                               uint64_t* __restrict__ tile_q16,
-                                                               uint64_t* __restrict__ d_sum,
-                                                               unsigned int* __restrict__ ticket)
+__device__ __forceinline__ void quantise_scan_body(const float* __restrict__ logw, const float* __restrict__ d_max,
+                                                   const float* __restrict__ block_max, int nblock_max, int n,
+                                                   uint64_t* __restrict__ cdf_local, uint64_t* __restrict__ tile_total,
+                                                   float* __restrict__ carry, uint64_t* __restrict__ tile_s16,
+                                                   uint64_t* __restrict__ tile_q16, uint64_t* __restrict__ d_sum,
+                                                   unsigned int* __restrict__ ticket, unsigned tile, unsigned ntiles)
 {
     __shared__ uint64_t s_wave[kBlock / 64];
     __shared__ float s_red[kBlock / 64];
     const float m = d_max ? *d_max : block_max_of(block_max, nblock_max, s_red);
-    const int base = blockIdx.x * kScanTile + threadIdx.x * kScanItems;
+    const int base = tile * kScanTile + threadIdx.x * kScanItems;
     uint64_t v[kScanItems];
     uint64_t run = 0, s16 = 0, q16 = 0;
 #pragma unroll
@@ -289,7 +278,7 @@ __global__ __launch_bounds__(kBlock) void quantise_scan_kernel(const float* __re
         const int i = base + k;
         if (i < n) cdf_local[i] = v[k] + excl;   // inclusive, local to this 2048-element tile
     }
-    if (threadIdx.x == 0) tile_total[blockIdx.x] = total;
+    if (threadIdx.x == 0) tile_total[tile] = total;
     if (GATED) {
         s16 = wave_sum_u64(s16);
         q16 = wave_sum_u64(q16);
@@ -306,8 +295,8 @@ __global__ __launch_bounds__(kBlock) void quantise_scan_kernel(const float* __re
 #pragma unroll
         for (int w = 0; w < kBlock / 64; ++w) b += s_wave[w];
         if (threadIdx.x == 0) {
-            tile_s16[blockIdx.x] = a;
-            tile_q16[blockIdx.x] = b;
+            tile_s16[tile] = a;
+            tile_q16[tile] = b;
         }
     }
     if (!d_sum || threadIdx.x != 0) return;
@@ -319,14 +308,47 @@ __global__ __launch_bounds__(kBlock) void quantise_scan_kernel(const float* __re
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(ticket + 2);   // 3 accumulators behind the ticket
     unsigned long long dep = atomicAdd(&acc[0], (unsigned long long)total);
     if (GATED) {
-        dep ^= atomicAdd(&acc[1], (unsigned long long)tile_s16[blockIdx.x]);
-        dep ^= atomicAdd(&acc[2], (unsigned long long)tile_q16[blockIdx.x]);
+        dep ^= atomicAdd(&acc[1], (unsigned long long)tile_s16[tile]);
+        dep ^= atomicAdd(&acc[2], (unsigned long long)tile_q16[tile]);
     }
     uint32_t one = 1u;
     asm volatile("" : "+v"(one) : "v"(dep));
-    if (atomicAdd(&ticket[0], one) != gridDim.x - 1) return;
+    if (atomicAdd(&ticket[0], one) != ntiles - 1) return;
     for (int a = 0; a < (GATED ? 3 : 1); ++a) d_sum[a] = atomicExch(&acc[a], 0ull);
     ticket[0] = 0;
+}
+
+template <bool GATED>
+__global__ __launch_bounds__(kBlock) void quantise_scan_kernel(const float* __restrict__ logw,
+                                                               const float* __restrict__ d_max,
+                                                               const float* __restrict__ block_max, int nblock_max,
+                                                               int n, uint64_t* __restrict__ cdf_local,
+                                                               uint64_t* __restrict__ tile_total,
+                                                               float* __restrict__ carry,
+                                                               uint64_t* __restrict__ tile_s16,
+                                                               uint64_t* __restrict__ tile_q16,
+                                                               uint64_t* __restrict__ d_sum,
+                                                               unsigned int* __restrict__ ticket)
+{
+    quantise_scan_body<GATED>(logw, d_max, block_max, nblock_max, n, cdf_local, tile_total, carry, tile_s16, tile_q16, d_sum, ticket,
+                              blockIdx.x, gridDim.x);
+}
+
+// The ungated scan with the covariance classes' update of a split session in workgroups of its own behind the `ntiles` tiles
+// (cov_update_body.h), as logweight_cov_kernel carries it: on a frame whose front launch has made the weights itself
+// (frame_particle_kernel, front_kernels.hip) there is no weights' launch for it to ride in.
+__global__ __launch_bounds__(kBlock) void quantise_scan_cov_kernel(const float* __restrict__ logw, const float* __restrict__ block_max,
+                                                                   int nblock_max, int n, uint64_t* __restrict__ cdf_local,
+                                                                   uint64_t* __restrict__ tile_total, uint64_t* __restrict__ d_sum,
+                                                                   unsigned int* __restrict__ ticket, int ntiles, int ly, CovArgs cov)
+{
+    if ((int)blockIdx.x >= ntiles) {
+        const int j = (int)blockIdx.x - ntiles;
+        cov_update_body(cov, j / ly, j % ly);
+        return;
+    }
+    quantise_scan_body<false>(logw, nullptr, block_max, nblock_max, n, cdf_local, tile_total, nullptr, nullptr, nullptr, d_sum, ticket,
+                              blockIdx.x, (unsigned)ntiles);
 }
 
 // The resample gate (oracle: orc_ess_resample): resample iff ESS < frac * N, i.e. S^2 * 65536 < frac_q16 * N * Q, in
@@ -800,7 +822,6 @@ __global__ __launch_bounds__(kBlock) void pose_sums_kernel(const float* __restri
 
 }  // namespace
 
-constexpr int kMaxWeightBlocks = 2048;
 static int capped_blocks(int n) { const int b = blocks_for(n); return b < kMaxWeightBlocks ? b : kMaxWeightBlocks; }
 int logweight_scratch_elems(int n) { return capped_blocks(n > 0 ? n : 1); }
 int logweight_scratch_floats() { return kMaxWeightBlocks + 2; }   // block maxima + {ticket, running maximum} (zero-initialise once)
@@ -849,10 +870,18 @@ hipError_t launch_prefix_sum(hipStream_t stream, const uint64_t* in, int n, uint
 
 hipError_t launch_quantise_scan(hipStream_t stream, const float* logw, const float* d_max, const float* block_max,
                                 int nblock_max, int n, uint64_t* cdf_local, uint64_t* tile_total, uint64_t* d_sum,
-                                float* carry, uint64_t* tile_s16, uint64_t* tile_q16, unsigned int* ticket)
+                                float* carry, uint64_t* tile_s16, uint64_t* tile_q16, unsigned int* ticket, const CovArgs* cov,
+                                int cov_bound)
 {
     if (n <= 0) return hipSuccess;
     const int ntiles = scan_tile_count(n);
+    if (cov && cov_bound > 0) {   // + the covariance classes' update (cov_bound x ly workgroups, flattened, as launch_logweight's)
+        if (carry || d_max) return hipErrorInvalidValue;   // the rider exists for the ungated scan over block maxima only
+        const int ly = cov->nlandmarks > 0 ? (cov->nlandmarks + 255) / 256 : 1;
+        quantise_scan_cov_kernel<<<ntiles + (int64_t)cov_bound * ly, kBlock, 0, stream>>>(logw, block_max, nblock_max, n, cdf_local,
+                                                                                        tile_total, d_sum, ticket, ntiles, ly, *cov);
+        return hipGetLastError();
+    }
     // `ticket`: {ticket, pad, three 64-bit accumulators} (8-byte aligned behind the pad), zero-initialised, left zeroed
     if (carry)
         quantise_scan_kernel<true><<<ntiles, kBlock, 0, stream>>>(logw, d_max, block_max, nblock_max, n, cdf_local, tile_total,

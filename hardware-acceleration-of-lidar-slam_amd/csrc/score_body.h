@@ -59,21 +59,26 @@ __device__ __forceinline__ float quad_bcast(float v)
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
 
-// MOTION: the pose is not read but produced — pose' = motion_sample(src[anc[i]]) (row A9) — written to
-// (px,py,p2) by the pose's first lane and scored in the same launch (saves a launch and a pose round trip).
-// `block`: which 256-thread slice of the poses this workgroup takes (blockIdx.x of score_poses_kernel; the fused front kernel
-// of a frame, front_kernels.hip, hands its scoring workgroups their slice); s_pair: nb_pad / 2 float4 of LDS.
-template <bool HAS_CS, int LPP, int DEPTH, bool MOTION, bool PACKED = false>
-__device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float* __restrict__ bx, const float* __restrict__ by,
-                                                 int nbeams, float* __restrict__ px, float* __restrict__ py,
-                                                 float* __restrict__ p2, const float* __restrict__ p3, int nposes,
-                                                 float* __restrict__ score, int32_t* __restrict__ count, const MotionIO& mio,
-                                                 const MotionParams& mpar, int block, float4* s_pair, float4* s_motion = nullptr)
+// What a scoring workgroup puts into LDS before its barrier: the beams, padded with NaN to a whole number of pipeline rounds
+// (score_pad_beams) and staged in pairs, the decode table of the packed grid behind them and — MOTION with four lanes per pose —
+// the workgroup's motion samples.  score_poses_body runs it itself; a kernel that gives a workgroup more to do with the same
+// samples (frame_particle_kernel, front_kernels.hip) runs it once, in front of a barrier of its own, and scores STAGED.
+template <int LPP, int DEPTH>
+__device__ __forceinline__ int score_pad_beams(int nbeams)
 {
     // beams padded with NaN to a whole number of pipeline rounds: a NaN beam is out of bounds and adds +0
     // (at least one round, so that an empty scan still runs the pipeline prologue on NaN beams)
     constexpr int kRound = LPP * DEPTH;
-    const int nb_pad = nbeams > 0 ? (nbeams + kRound - 1) / kRound * kRound : kRound;
+    return nbeams > 0 ? (nbeams + kRound - 1) / kRound * kRound : kRound;
+}
+
+template <int LPP, int DEPTH, bool MOTION, bool PACKED>
+__device__ __forceinline__ void score_stage(const ScoreGrid& g, const float* __restrict__ bx, const float* __restrict__ by,
+                                            int nbeams, float* __restrict__ px, float* __restrict__ py, float* __restrict__ p2,
+                                            int nposes, const MotionIO& mio, const MotionParams& mpar, int block, float4* s_pair,
+                                            float4* s_motion)
+{
+    const int nb_pad = score_pad_beams<LPP, DEPTH>(nbeams);
     {
         // LPP lanes per pose: lane `sub` takes beams sub + LPP*k and handles them two at a time (k = 2m, 2m+1) on
         // float2 arithmetic; the pair is staged side by side — slot sub + LPP*m = (x_k, x_k+1, y_k, y_k+1) — so one
@@ -97,8 +102,7 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
     // (s_motion: (x, y, sine, cosine) per pose) behind the barrier the beams need anyway, where all four lanes of every quad
     // ran Philox, Box-Muller and det_sincosf for the same pose.  The same function of the pose's index and its ancestor's pose:
     // the same bits.  The LAST wavefront does it: with 360 beams it has no beam pair to stage above.
-    constexpr bool kSharedMotion = MOTION && LPP == 4;
-    if constexpr (kSharedMotion) {
+    if constexpr (MOTION && LPP == 4) {
         static_assert(kScoreBlock / LPP == 64, "the workgroup's poses fill one wavefront");
         if (threadIdx.x >= kScoreBlock - 64) {
             const int l = (int)threadIdx.x - (kScoreBlock - 64);
@@ -116,7 +120,30 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
             s_motion[l] = make_float4(x, y, sn, cs);
         }
     }
-    __syncthreads();
+}
+
+// MOTION: the pose is not read but produced — pose' = motion_sample(src[anc[i]]) (row A9) — written to
+// (px,py,p2) by the pose's first lane and scored in the same launch (saves a launch and a pose round trip).
+// `block`: which 256-thread slice of the poses this workgroup takes (blockIdx.x of score_poses_kernel; the fused front kernel
+// of a frame, front_kernels.hip, hands its scoring workgroups their slice); s_pair: nb_pad / 2 float4 of LDS.
+// STAGED: score_stage and the barrier behind it have been run by the caller.  s_score (LPP 4, optional): kScoreBlock / 4 floats
+// of LDS in which every quad also leaves its score, for a later phase of the same workgroup.
+template <bool HAS_CS, int LPP, int DEPTH, bool MOTION, bool PACKED = false, bool STAGED = false>
+__device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float* __restrict__ bx, const float* __restrict__ by,
+                                                 int nbeams, float* __restrict__ px, float* __restrict__ py,
+                                                 float* __restrict__ p2, const float* __restrict__ p3, int nposes,
+                                                 float* __restrict__ score, int32_t* __restrict__ count, const MotionIO& mio,
+                                                 const MotionParams& mpar, int block, float4* s_pair, float4* s_motion = nullptr,
+                                                 float* s_score = nullptr)
+{
+    constexpr int kRound = LPP * DEPTH;
+    const int nb_pad = score_pad_beams<LPP, DEPTH>(nbeams);
+    float* s_table = reinterpret_cast<float*>(s_pair + nb_pad / 2);
+    constexpr bool kSharedMotion = MOTION && LPP == 4;
+    if constexpr (!STAGED) {
+        score_stage<LPP, DEPTH, MOTION, PACKED>(g, bx, by, nbeams, px, py, p2, nposes, mio, mpar, block, s_pair, s_motion);
+        __syncthreads();
+    }
 
     const int t = block * kScoreBlock + threadIdx.x;
     const int pose = t / LPP, sub = t % LPP;
@@ -276,6 +303,8 @@ __device__ __forceinline__ void score_poses_body(const ScoreGrid& g, const float
         score[pose] = total;
         count[pose] = n_in;
     }
+    if constexpr (LPP == 4)
+        if (s_score && sub == 0) s_score[threadIdx.x / LPP] = total;
 }
 
 }  // namespace slam

@@ -96,8 +96,9 @@ typedef enum {
     SLAM_PROF_EDT = 1,          /* edt kernels */
     SLAM_PROF_EKF = 2,          /* the landmark update of a frame, whichever kernel runs it (rows, grouped, list, pages) */
     SLAM_PROF_WEIGHTS = 3,      /* log-weights + block maxima (+ the maximum's finalize launch on several GPUs); a split session's
-                                   covariance classes are brought up to date by workgroups of the same launch */
-    SLAM_PROF_SCAN = 4,         /* quantise + prefix sum (+ ESS sums) */
+                                   covariance classes are brought up to date by workgroups of the same launch.  A survivor-rows frame
+                                   whose fused front launch made the weights itself has no launch in this bracket */
+    SLAM_PROF_SCAN = 4,         /* quantise + prefix sum (+ ESS sums); + the covariance classes' update on a frame without a weights' launch */
     SLAM_PROF_ANCESTORS = 5,    /* offspring offsets / ancestor search (single GPU: one launch) */
     SLAM_PROF_PLAN = 6,         /* several GPUs: global ancestor search, flag scans, exchange plan, local gather index */
     SLAM_PROF_PACK = 7,         /* several GPUs: migrating rows into the send buffer */
