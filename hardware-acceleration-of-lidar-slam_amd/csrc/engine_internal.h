@@ -1,5 +1,5 @@
 // engine_internal.h — the engine object shared by the translation units that implement the C ABI
-// (engine.hip and the engine_*.hip units by stage — match, ekf, assoc, resample —, pf_session.hip, comm.hip, mapper.hip).  Not part of the public interface.
+// (engine.hip and the engine_*.hip units by stage — match, ekf, assoc, resample —, the pf_session*.hip units, comm.hip, mapper.hip).  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>

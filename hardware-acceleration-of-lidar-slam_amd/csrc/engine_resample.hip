@@ -300,7 +300,7 @@ int slam_migrate_pack_dev(slam_engine* e, int n_local, int rank, int world, cons
                                    d_out, nullptr, 0, nullptr, nullptr, nullptr);
 }
 
-// d_pt != nullptr: d_map is a page pool and the particles' landmarks sit behind page tables of nb entries (pf_session.hip)
+// d_pt != nullptr: d_map is a page pool and the particles' landmarks sit behind page tables of nb entries (pf_session_store.hip)
 int slam_migrate_pack_paged(slam_engine* e, int n_local, int rank, int world, const int32_t* plan, const float* d_pose,
                             int64_t pose_ld, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks,
                             float* d_out, const int32_t* d_pt, int nb, const float* d_split_cov, const int32_t* d_split_cls,

@@ -1,5 +1,5 @@
 // kernels.h — launchers of the gfx950 kernels, one section per kernel file in the Makefile's order; called by the C-ABI layer
-// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_resample.hip by stage), the particle-filter session (pf_session.hip) and the mapper (mapper.hip).
+// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_resample.hip by stage), the particle-filter session (the pf_session*.hip units) and the mapper (mapper.hip).
 // Every launcher enqueues on `stream` and returns the hipError_t of the launch; none synchronises.
 #pragma once
 
@@ -345,7 +345,7 @@ struct PageGeom {
     int64_t half_pages = (int64_t)1 << 62;   // pages at or beyond this index lie `gap` floats further on
     int64_t gap = 0;
 };
-// A session's page pool as the launchers off the frame path take it (pf_session.hip: page_pool): by const reference to a
+// A session's page pool as the launchers off the frame path take it (pf_session_store.hip: page_pool): by const reference to a
 // launcher, by value to its kernel.  pt is ONE table (the session's current one unless the caller says otherwise).
 struct PagePool {
     float* pool;           // [npages][geom.planes][32]

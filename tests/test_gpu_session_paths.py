@@ -1,7 +1,7 @@
 """Every path a slam_pf frame can take, against one rank on rows, bit for bit.
 
 Five map layouts x {one GPU, three ranks sharing this card} x {ungated, ESS-gated} x {dense, sparse observations}: which
-launches a frame consists of is decided by the host code of csrc/pf_session.hip from exactly these four facts.  At 9 216
+launches a frame consists of is decided by the host code of csrc/pf_session_frame.hip from exactly these four facts.  At 9 216
 particles x 160 landmarks (3 072 per rank of three, rows of five pages) the fused front (one GPU and sharded), the staging
 tail, the free-list rider, both forms of the paged update, the gathers of the frame without observations and the exchange
 that a map read completes early all occur.  Results never depend on the layout, the number of ranks or the path taken.

@@ -1,4 +1,4 @@
-"""Survivor rows (slam_survivor_rows_set; csrc/ekf_split_body.h MEANS / TALLY, ekf_materialise_kernel, pf_session.hip: settle_means):
+"""Survivor rows (slam_survivor_rows_set; csrc/ekf_split_body.h MEANS / TALLY, ekf_materialise_kernel, pf_session_store.hip: settle_means):
 on the split layout the fused front launch of a single-GPU session that resamples every frame writes no mean row, a launch
 behind the resample writes the rows of the particles it kept, and anything else that looks at mean rows first has them all
 written.  No result may depend on the switch.
