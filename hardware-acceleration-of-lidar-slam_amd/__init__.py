@@ -128,6 +128,9 @@ SIGNATURES = {
     "slam_detect_params_default": (None, [_vp]),
     "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
     "slam_detect_count": (_i, [_vp, _vp]),
+    "slam_detect_fit_default": (None, [_vp]),
+    "slam_detect_scan_fit_dev": (_i, [_vp, _vp, _vp, _vp]),
+    "slam_detect_fit_count": (_i, [_vp, _vp]),
     "slam_detections_get_host": (_i, [_vp, _vp, _vp, _vp]),
     "slam_selftest_reciprocal": (_i, [_vp, _vp, _vp]),
     "slam_frame_fusion_set": (_i, [_vp, _i]),
@@ -171,6 +174,7 @@ SIGNATURES = {
     "slam_pf_evidence_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_evidence_host": (_i, [_vp, _vp]),
     "slam_pf_detect_set": (_i, [_vp, _vp]),
+    "slam_pf_detect_fit_set": (_i, [_vp, _vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
     "slam_pf_get_poses_host": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_map_host": (_i, [_vp, _vp]),
@@ -498,6 +502,20 @@ class Engine:
         p = params if params is not None else DetectParams.default(**kw)
         self._ck(self.lib.slam_detect_scan_dev(self.h, C.byref(p), _ptr(d_stats)), "detect_scan_dev")
 
+    def detect_scan_fit_dev(self, fit: "DetectFit | tuple | None", params: "DetectParams | None" = None, d_stats=None, **kw):
+        """``slam_detect_scan_fit_dev``: detect_scan_dev with every detection the centre of a circle of known radius fitted to
+        its segment, and the shape test.  fit: a DetectFit, (radius, spread_tol), or None (the centroid: detect_scan_dev)."""
+        p = params if params is not None else DetectParams.default(**kw)
+        f = DetectFit.of(fit)
+        self._ck(self.lib.slam_detect_scan_fit_dev(self.h, C.byref(p), C.byref(f) if f is not None else None, _ptr(d_stats)),
+                 "detect_scan_fit_dev")
+
+    def detect_fit_count(self) -> int:
+        """Detector launches of this engine so far that ran the fit."""
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_detect_fit_count(self.h, C.byref(c)), "detect_fit_count")
+        return c.value
+
     def detect_count(self) -> int:
         """Detector launches of this engine so far."""
         c = C.c_int64(0)
@@ -659,6 +677,30 @@ class DetectParams(C.Structure):
                 raise TypeError(f"slam_detect_params has no field {k!r}")
             setattr(p, k, v)
         return p
+
+
+class DetectFit(C.Structure):
+    """``slam_detect_fit``: the poles' nominal radius and what the shape test allows beyond it (slam_detect_scan_fit_dev)."""
+
+    _fields_ = [("radius", C.c_float), ("spread_tol", C.c_float)]
+
+    @classmethod
+    def default(cls, **kw):
+        f = cls()
+        load_library().slam_detect_fit_default(C.byref(f))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"slam_detect_fit has no field {k!r}")
+            setattr(f, k, v)
+        return f
+
+    @classmethod
+    def of(cls, fit):
+        """None, a DetectFit or (radius, spread_tol) -> None or a DetectFit."""
+        if fit is None or isinstance(fit, cls):
+            return fit
+        radius, tol = fit
+        return cls(radius, tol)
 
 
 class MapperParams(C.Structure):
@@ -1018,6 +1060,15 @@ class PfSession:
             return
         p = DetectParams.default(**kw) if params is True else params
         self.e._ck(self.e.lib.slam_pf_detect_set(self.h, C.byref(p)), "pf_detect_set")
+
+    def detect_fit_set(self, fit: "DetectFit | tuple | None", params: "DetectParams | None | bool" = True, **kw):
+        """``slam_pf_detect_fit_set``: detect_set with the fit (a DetectFit or (radius, spread_tol); None: detect_set)."""
+        if params is None or params is False:
+            self.e._ck(self.e.lib.slam_pf_detect_fit_set(self.h, None, None), "pf_detect_fit_set")
+            return
+        p = DetectParams.default(**kw) if params is True else params
+        f = DetectFit.of(fit)
+        self.e._ck(self.e.lib.slam_pf_detect_fit_set(self.h, C.byref(p), C.byref(f) if f is not None else None), "pf_detect_fit_set")
 
     def evidence_view(self):
         """``slam_pf_evidence_device_view``: the current evidence uint8 [n][stride] (indexed like the maps: before the pending

@@ -14,6 +14,11 @@
 //      the lanes in front) — no atomics, and nothing depends on the order in which lanes or wavefronts arrive;
 //   5. zx[64] | zy[64] (0 from ndet on), the stats and {ndet, sequence} in mapped host memory: plain vector stores, the sequence
 //      word released last.
+// THE FIT (kFit, a compile-time policy: the instantiation without it is the kernel as it was; specification:
+// tests/_detect_fit_spec.py): a pole of known radius rho.  Directly behind the centroid sum the owning lane walks its segment's
+// m <= 64 LDS points once more for their spread s2 about the centroid; s2 <= rho^2 + tol^2 or the segment is no pole (the shape
+// test: a third mask of the same shape, only counted), and the detection is the point sqrt(rho^2 - s2) behind the centroid on
+// its line of sight — the circle's centre.
 
 #include "kernels.h"
 
@@ -63,8 +68,10 @@ __device__ __forceinline__ float det_r2(const DetScan& s, int b)
     return xx + yy;
 }
 
-// the segment that starts at break f: accepted -> its centroid
-__device__ __forceinline__ bool det_segment(const DetScan& s, const DetectArgs& a, const u64* brk, int f, float& zx, float& zy)
+// the segment that starts at break f: accepted -> its centroid, with kFit the centre fitted to it (shape: the shape test rejected it)
+template <bool kFit>
+__device__ __forceinline__ bool det_segment(const DetScan& s, const DetectArgs& a, const u64* brk, int f, float& zx, float& zy,
+                                            bool& shape)
 {
     const int P = s.P, span = a.max_points + 1;   // an implementation may stop counting at max_points + 1
     int q = first_set(brk, f + 1, min(f + span + 1, P)), m = -1;
@@ -93,14 +100,42 @@ __device__ __forceinline__ bool det_segment(const DetScan& s, const DetectArgs& 
     zx = sx / fm;   // IEEE division (-fno-fast-math)
     zy = sy / fm;
     const float zxx = zx * zx, zyy = zy * zy;
-    return zxx + zyy <= a.range2;   // NaN and inf fail: what comes out is finite
+    if constexpr (!kFit) {
+        return zxx + zyy <= a.range2;   // NaN and inf fail: what comes out is finite
+    } else {
+        const float c2 = zxx + zyy;
+        if (!(c2 <= a.range2)) return false;   // ... so everything that enters the fit is finite
+        const float cx = zx, cy = zy;
+        float q = 0.0f;
+        for (int j = 0, i = f; j < m; ++j) {   // the same walk: the spread about the centroid, in segment order
+            const float du = s.x[i] - cx, dv = s.y[i] - cy;
+            const float du2 = du * du, dv2 = dv * dv;
+            q = q + (du2 + dv2);
+            i = i + 1 == P ? 0 : i + 1;
+        }
+        const float s2 = q / fm;
+        if (!(s2 <= a.lim) || !(c2 > 0.0f)) {   // not round enough for a pole / the centroid on the sensor: no line of sight
+            shape = true;
+            return false;
+        }
+        float t = a.rho2 - s2;
+        t = t > 0.0f ? t : 0.0f;
+        const float d = sqrtf(t), n = sqrtf(c2);   // correctly rounded (hipcc's default, like the divisions)
+        const float ux = cx / n, uy = cy / n;
+        const float ox = d * ux, oy = d * uy;
+        zx = cx + ox;
+        zy = cy + oy;
+        const float fxx = zx * zx, fyy = zy * zy;
+        return fxx + fyy <= a.range2;
+    }
 }
 
+template <bool kFit>
 __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs a)
 {
     __shared__ float s_x[SLAM_MAX_BEAMS], s_y[SLAM_MAX_BEAMS];
-    __shared__ u64 s_brk[kDetWords], s_acc[kDetWords];
-    __shared__ int s_pre[kDetWords], s_tot[2];
+    __shared__ u64 s_brk[kDetWords], s_acc[kDetWords], s_shp[kFit ? kDetWords : 1];
+    __shared__ int s_pre[kDetWords], s_tot[kFit ? 3 : 2];
     const int T = (int)blockDim.x, tid = (int)threadIdx.x, lane = tid & 63;
     const int P = a.nbeams, nwords = (kDetRounds * T) >> 6;   // the words the ballots below write (kDetRounds * T >= P)
     DetScan s;
@@ -137,10 +172,14 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
         const int b = k * T + tid;
         zx[k] = 0.0f;
         zy[k] = 0.0f;
-        bool acc = false;
-        if ((mine >> k) & 1u) acc = det_segment(s, a, s_brk, b, zx[k], zy[k]);
+        bool acc = false, shape = false;
+        if ((mine >> k) & 1u) acc = det_segment<kFit>(s, a, s_brk, b, zx[k], zy[k], shape);
         const u64 word = __ballot(acc);
         if (lane == 0) s_acc[b >> 6] = word;
+        if constexpr (kFit) {   // the third mask: rejected by the shape test
+            const u64 round = __ballot(shape);
+            if (lane == 0) s_shp[b >> 6] = round;
+        }
         kept |= acc ? 1u << k : 0u;
     }
     __syncthreads();
@@ -148,16 +187,21 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
     if (tid < 64) {   // wavefront 0, lane w: word w
         const int c = tid < nwords ? __popcll(s_acc[tid]) : 0;
         int segs = tid < nwords ? __popcll(s_brk[tid]) : 0;
+        int shp = 0;
+        if constexpr (kFit) shp = tid < nwords ? __popcll(s_shp[tid]) : 0;
         int inc = c;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const int up = __shfl_up(inc, d, 64), other = __shfl_xor(segs, d, 64);
             inc += lane >= d ? up : 0;
             segs += other;
+            if constexpr (kFit) shp += __shfl_xor(shp, d, 64);
         }
         s_pre[tid] = inc - c;
         if (tid == 63) s_tot[0] = inc;
         if (tid == 0) s_tot[1] = segs;
+        if constexpr (kFit)
+            if (tid == 0) s_tot[2] = shp;
     }
     __syncthreads();
 
@@ -181,7 +225,8 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
             a.stats[0] = s_tot[1];
             a.stats[1] = accepted;
             a.stats[2] = written;
-            a.stats[3] = 0;
+            if constexpr (kFit) a.stats[3] = s_tot[2];
+            else a.stats[3] = 0;
         }
         a.h_out[0] = written;
         __threadfence_system();
@@ -194,12 +239,13 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
 hipError_t launch_detect_scan(hipStream_t stream, const DetectArgs& a, const EventPair* ev)
 {
     if (a.nbeams < 0 || a.nbeams > SLAM_MAX_BEAMS || a.min_points < 1 || a.max_points > SLAM_DETECT_MAX_POINTS ||
-        a.min_points > a.max_points || !a.det || !a.h_out || (a.nbeams > 0 && (!a.bx || !a.by)))
+        a.min_points > a.max_points || !a.det || !a.h_out || (a.nbeams > 0 && (!a.bx || !a.by)) || (a.fit != 0 && a.fit != 1))
         return hipErrorInvalidValue;   // what the LDS arrays and the mask search are sized by
     int threads = ((a.nbeams + kDetRounds - 1) / kDetRounds + 63) & ~63;
     threads = threads < 64 ? 64 : threads;
     if (ev) (void)hipEventRecord(ev->start, stream);
-    detect_scan_kernel<<<1, threads, 0, stream>>>(a);
+    if (a.fit) detect_scan_kernel<true><<<1, threads, 0, stream>>>(a);
+    else detect_scan_kernel<false><<<1, threads, 0, stream>>>(a);
     if (ev) (void)hipEventRecord(ev->stop, stream);
     return hipGetLastError();
 }

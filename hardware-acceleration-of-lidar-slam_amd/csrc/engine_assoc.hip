@@ -172,12 +172,24 @@ void slam_detect_params_default(slam_detect_params* p)
     p->wrap = 1;
 }
 
-int slam_detect_scan_dev(slam_engine* e, const slam_detect_params* params, int32_t* d_stats)
+void slam_detect_fit_default(slam_detect_fit* f)
+{
+    if (!f) return;
+    f->radius = 0.1f;
+    f->spread_tol = 0.0f;
+}
+
+// the one checked path of both entry points (fit == nullptr: the centroid, the kernel instantiation without the fit)
+static int detect_scan(slam_engine* e, const slam_detect_params* params, const slam_detect_fit* fit, int32_t* d_stats)
 {
     SLAM_ENTER(e);
     if (!params) return SLAM_ERR_INVALID_ARG;
     if (!slam_detect_params_ok(params)) {
         slam_detect_params_error(e);
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (fit && !slam_detect_fit_ok(fit)) {
+        slam_detect_fit_error(e);
         return SLAM_ERR_INVALID_ARG;
     }
     if (e->nbeams < 0) return SLAM_ERR_NOT_READY;
@@ -197,6 +209,9 @@ int slam_detect_scan_dev(slam_engine* e, const slam_detect_params* params, int32
     a.stats = d_stats;
     a.h_out = e->d_hdet;
     a.seq = e->det_seq + 1;
+    a.fit = fit ? 1 : 0;
+    a.rho2 = fit ? fit->radius * fit->radius : 0.0f;
+    a.lim = fit ? a.rho2 + fit->spread_tol * fit->spread_tol : 0.0f;
     SLAM_HIP_TRY(e, launch_detect_scan(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
     e->det_seq = a.seq;
     e->d_det_zx = e->det_buf.as<float>();
@@ -205,7 +220,18 @@ int slam_detect_scan_dev(slam_engine* e, const slam_detect_params* params, int32
     e->det_pending = true;
     e->det_from_scan = true;
     e->detect_launches++;
+    if (fit) e->detect_fit_launches++;
     return SLAM_OK;
+}
+
+int slam_detect_scan_dev(slam_engine* e, const slam_detect_params* params, int32_t* d_stats)
+{
+    return detect_scan(e, params, nullptr, d_stats);
+}
+
+int slam_detect_scan_fit_dev(slam_engine* e, const slam_detect_params* params, const slam_detect_fit* fit, int32_t* d_stats)
+{
+    return detect_scan(e, params, fit, d_stats);
 }
 
 int slam_detect_count(slam_engine* e, int64_t* launches)
@@ -213,6 +239,14 @@ int slam_detect_count(slam_engine* e, int64_t* launches)
     SLAM_ENTER(e);
     if (!launches) return SLAM_ERR_INVALID_ARG;
     *launches = e->detect_launches;
+    return SLAM_OK;
+}
+
+int slam_detect_fit_count(slam_engine* e, int64_t* launches)
+{
+    SLAM_ENTER(e);
+    if (!launches) return SLAM_ERR_INVALID_ARG;
+    *launches = e->detect_fit_launches;
     return SLAM_OK;
 }
 

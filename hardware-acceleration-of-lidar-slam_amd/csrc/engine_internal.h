@@ -99,6 +99,7 @@ struct slam_engine {
     bool det_pending = false;
     bool det_from_scan = false;   // the current detections are the detector's: det_buf holds 0 from ndet on
     int64_t detect_launches = 0;   // slam_detect_count (in no other counter)
+    int64_t detect_fit_launches = 0;   // slam_detect_fit_count: those of them that ran the fit
 
     DevBuf fm_buf;             // kFmIn + kFmOut floats
     DevBuf fm_work;            // 2 x 27 x SLAM_MAX_BEAMS floats: per-candidate hit rows of the lattice kernel, two sweeps (the chained pair)
@@ -293,6 +294,17 @@ inline void slam_detect_params_error(slam_engine* e)
 {
     snprintf(e->err, sizeof e->err, "the detector needs finite jump, guard, max_width and max_range > 0, guard >= jump, "
                                     "1 <= min_points <= max_points <= %d and wrap in {0, 1}", (int)SLAM_DETECT_MAX_POINTS);
+}
+
+// ... and of slam_detect_scan_fit_dev on a fit
+inline bool slam_detect_fit_ok(const slam_detect_fit* f)
+{
+    const float big = 3.402823466e+38f;
+    return f->radius > 0.0f && f->radius <= big && f->spread_tol >= 0.0f && f->spread_tol <= big;
+}
+inline void slam_detect_fit_error(slam_engine* e)
+{
+    snprintf(e->err, sizeof e->err, "the detector's fit needs a finite radius > 0 and a finite spread_tol >= 0");
 }
 
 // The two choices a landmark update on rows has (kernels.h: launch_ekf_rows), as the engine's stages take them.

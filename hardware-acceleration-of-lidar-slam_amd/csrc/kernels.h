@@ -275,15 +275,20 @@ hipError_t launch_evidence_init(hipStream_t stream, const EvidenceInitArgs& a, c
 hipError_t launch_evidence_gather(hipStream_t stream, const uint8_t* in, uint8_t* out, int stride, const int32_t* anc, int n);
 // ---- detect_kernels.hip: the landmark detector (specification: tests/_detect_spec.py).  The scan's short,
 // narrow, unoccluded runs of points between two range jumps become the frame's detections: their centroids, in scan order.
+// fit (specification: tests/_detect_fit_spec.py): the runs that are no more spread out than a circle of the given radius, each
+// as that circle's centre.
 struct DetectArgs {
     const float *bx, *by;   // the scan, [nbeams] sensor-frame points in scan order
     int nbeams;             // 0 .. SLAM_MAX_BEAMS
     float jump2, guard2, width2, range2;   // the squares of slam_detect_params' lengths, one float32 product each, made on the host
     int min_points, max_points, wrap;      // 1 <= min_points <= max_points <= SLAM_DETECT_MAX_POINTS
     float* det;             // zx[SLAM_MAX_DETECTIONS] | zy[SLAM_MAX_DETECTIONS]: the first ndet by ascending start, then 0
-    int32_t* stats;         // [4] segments, accepted, written (= ndet), 0; may be nullptr
+    int32_t* stats;         // [4] segments, accepted, written (= ndet), rejected by the shape test (0 without fit); may be nullptr
     int32_t* h_out;         // mapped host memory {ndet, sequence}: plain stores, `seq` released last
     uint32_t seq;
+    // behind everything the kernel without the fit reads:
+    int fit;                // 0: the centroid; 1: the centre of a circle of squared radius rho2 through the segment
+    float rho2, lim;        // radius * radius; rho2 + spread_tol * spread_tol: one float32 operation each, made on the host
 };
 // one workgroup of 64 .. 1024 threads by the size of the scan
 hipError_t launch_detect_scan(hipStream_t stream, const DetectArgs& a, const EventPair* ev = nullptr);

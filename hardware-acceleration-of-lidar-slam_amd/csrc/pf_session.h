@@ -154,6 +154,10 @@ struct slam_pf {
     // (slam_detect_scan_dev), issued in front of the frame's first launch
     bool detect_on = false;
     slam_detect_params detect_params{};
+    // slam_pf_detect_fit_set: the detector's launch runs the fit (slam_detect_scan_fit_dev); cleared by slam_pf_detect_set and
+    // slam_pf_assoc_set(0)
+    bool detect_fit_on = false;
+    slam_detect_fit detect_fit{};
     // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe (RES_OBS) and moves between split and
     // split pages while it runs (between rows and pages when it could not have the split layout's tables)
     int layout_cfg = SLAM_MAP_AUTO;

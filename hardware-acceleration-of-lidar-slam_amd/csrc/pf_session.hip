@@ -349,6 +349,7 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
         pf->assoc_aniso = false;
         pf->prune_on = false;
         pf->detect_on = false;
+        pf->detect_fit_on = false;
         return SLAM_OK;
     }
     if (pf->layout_cfg != SLAM_MAP_ROWS || pf->L == 0 || pf->comm) {
@@ -432,12 +433,16 @@ int slam_pf_prune_set(slam_pf* pf, int hit, int miss, int cmax, float view_range
     return evidence_from_maps(pf);   // the current maps are trusted (indexed like them: before the pending gather)
 }
 
-int slam_pf_detect_set(slam_pf* pf, const slam_detect_params* params)
+int slam_pf_detect_set(slam_pf* pf, const slam_detect_params* params) { return slam_pf_detect_fit_set(pf, params, nullptr); }
+
+// fit == nullptr: the centroid detector (slam_pf_detect_set); a refused call leaves the session as it was
+int slam_pf_detect_fit_set(slam_pf* pf, const slam_detect_params* params, const slam_detect_fit* fit)
 {
     if (!pf) return SLAM_ERR_INVALID_ARG;
     slam_engine* e = pf->e;
     if (!params) {   // off: the session runs exactly what it ran before the first call
         pf->detect_on = false;
+        pf->detect_fit_on = false;
         return SLAM_OK;
     }
     if (!pf->assoc_on) {   // (which is what every layout but rows, a sharded session and a 2x2 covariance come down to)
@@ -449,8 +454,14 @@ int slam_pf_detect_set(slam_pf* pf, const slam_detect_params* params)
         slam_detect_params_error(e);
         return SLAM_ERR_INVALID_ARG;
     }
+    if (fit && !slam_detect_fit_ok(fit)) {
+        slam_detect_fit_error(e);
+        return SLAM_ERR_INVALID_ARG;
+    }
     pf->detect_on = true;
     pf->detect_params = *params;
+    pf->detect_fit_on = fit != nullptr;
+    if (fit) pf->detect_fit = *fit;
     return SLAM_OK;
 }
 

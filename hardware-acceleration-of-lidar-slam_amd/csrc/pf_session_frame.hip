@@ -557,7 +557,7 @@ int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations,
     FrameFacts f = frame_facts(pf, use_observations);
     // the detector: in front of the frame's first launch, so that its count has arrived when update_rows' association asks for it
     if (pf->detect_on && pf->assoc_on && f.ekf)
-        if (int rc = slam_detect_scan_dev(e, &pf->detect_params, nullptr)) return rc;
+        if (int rc = slam_detect_scan_fit_dev(e, &pf->detect_params, pf->detect_fit_on ? &pf->detect_fit : nullptr, nullptr)) return rc;
     if (int rc = front_stage(pf, f, slot, dp)) return rc;
     if (int rc = gate_and_exchange(pf, f, collective_verdict)) return rc;
     if (int rc = pf->paged ? update_paged(pf, f) : pf->split ? update_split(pf, f) : update_rows(pf, f)) return rc;

@@ -440,6 +440,28 @@ typedef struct {
 void slam_detect_params_default(slam_detect_params *p);   /* 0.3, 1.0, 0.5, 20.0, 3, 40, 1 */
 int slam_detect_scan_dev(slam_engine *e, const slam_detect_params *params, int32_t *d_stats /* [4], may be NULL */);
 int slam_detect_count(slam_engine *e, int64_t *launches);
+/* THE DETECTOR, FITTED: a pole has a known nominal radius, and with it the centre of the circle through a segment's points has a
+ * closed form that uses every point.  With c the centroid, s2 the mean squared distance of the m points to it and C the centre,
+ * sum (p_i - c) = 0 gives mean |p_i - C|^2 = s2 + |c - C|^2; on the circle the left side is radius^2, so C lies
+ * sqrt(radius^2 - s2) from c, along the line of sight through c.  slam_detect_scan_fit_dev is slam_detect_scan_dev (fit == NULL:
+ * exactly that, bit for bit and launch for launch) with, behind step 3(d) — whose test of the centroid stays — for every segment,
+ * rho2 = radius * radius, lim = rho2 + spread_tol * spread_tol and range2 rounded once, every step one float32 operation:
+ *   (e) q = 0, then for the points in segment order du = x - cx, dv = y - cy, q = q + (du*du + dv*dv); s2 = q / (float)m;
+ *       s2 <= lim and cx*cx + cy*cy > 0, or the segment is REJECTED BY THE SHAPE TEST: more spread out than a pole can be (a flat
+ *       piece of wall wider than about 3.46 radius), or its centroid on the sensor;
+ *   (f) t = max(rho2 - s2, 0); d = sqrt(t); n = sqrt(cx*cx + cy*cy); zx = cx + d * (cx / n), zy alike (correctly rounded sqrt and
+ *       division); accepted iff zx*zx + zy*zy <= range2.
+ * d_stats[3] counts the segments the shape test rejected (0 without a fit).  Operation order: tests/_detect_fit_spec.py.
+ * SLAM_ERR_INVALID_ARG, nothing launched: as slam_detect_scan_dev, or a radius that is not finite and > 0, a spread_tol that is
+ * not finite and >= 0.  Counted by slam_detect_count like every detector launch, and by slam_detect_fit_count when a fit ran. */
+typedef struct {
+    float radius;       /* the poles' nominal radius [m] */
+    float spread_tol;   /* what the shape test allows beyond it: s2 <= radius^2 + spread_tol^2 [m] */
+} slam_detect_fit;
+void slam_detect_fit_default(slam_detect_fit *f);   /* 0.1, 0.0 */
+int slam_detect_scan_fit_dev(slam_engine *e, const slam_detect_params *params, const slam_detect_fit *fit /* NULL: the centroid */,
+                             int32_t *d_stats /* [4], may be NULL */);
+int slam_detect_fit_count(slam_engine *e, int64_t *launches);   /* launches that ran the fit; slam_detect_count counts all */
 int slam_detections_get_host(slam_engine *e, float *zx, float *zy, int32_t *ndet);
 /* The FRONT of a frame of a single-GPU slam_pf session on rows — motion sample + scan-match score (FastMatch's inner loop,
  * main.c:459-518, for every particle) and the out-of-place landmark update — goes out as ONE launch whose scoring and
@@ -783,6 +805,10 @@ int slam_pf_get_evidence_host(slam_pf *pf, uint8_t *ev /* [n][nlandmarks] */);  
  * has long arrived when the association asks for it — and then runs associate -> update (-> evidence) on them; whatever
  * detections were handed over are replaced.  With it off the session runs exactly what it ran before the first call. */
 int slam_pf_detect_set(slam_pf *pf, const slam_detect_params *params /* NULL: off */);
+/* ... with the fit (slam_detect_scan_fit_dev): accepted and refused exactly where slam_pf_detect_set is, and for a fit that
+ * slam_detect_scan_fit_dev refuses.  params == NULL: the detector off; fit == NULL: slam_pf_detect_set(params).
+ * slam_pf_detect_set and slam_pf_assoc_set(gate = 0) clear the fit.  The frame's launches and their order are the same. */
+int slam_pf_detect_fit_set(slam_pf *pf, const slam_detect_params *params /* NULL: off */, const slam_detect_fit *fit /* NULL: the centroid */);
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
  * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
