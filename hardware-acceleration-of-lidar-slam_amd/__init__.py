@@ -144,6 +144,7 @@ SIGNATURES = {
     "slam_ekf_inplace_form_counts": (_i, [_vp, _vp]),
     "slam_resample_gate_set": (_i, [_vp, _f]),
     "slam_resample_happened_host": (_i, [_vp, C.POINTER(C.c_int)]),
+    "slam_resample_heads_host": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "slam_comm_unique_id": (_i, [_vp]),
     "slam_comm_create_rccl": (_i, [_vp, _i, _i, _vp, C.POINTER(_vp)]),
     "slam_local_group_create": (_i, [_i, C.POINTER(_vp)]),
@@ -629,6 +630,12 @@ class Engine:
         r = C.c_int(1)
         self._ck(self.lib.slam_resample_happened_host(self.h, C.byref(r)), "resample_happened")
         return bool(r.value)
+
+    def resample_heads(self):
+        """(about how many distinct ancestors the last resample stage of a population with maps left, that population's size or -1)"""
+        h, n = C.c_int32(0), C.c_int32(-1)
+        self._ck(self.lib.slam_resample_heads_host(self.h, C.byref(h), C.byref(n)), "resample_heads")
+        return h.value, n.value
 
     def exchange_set_capacity(self, rows: int):
         self._ck(self.lib.slam_exchange_set_capacity(self.h, int(rows)), "exchange_set_capacity")

@@ -188,6 +188,15 @@ int slam_resample_happened_host(slam_engine* e, int* resampled)
     return SLAM_OK;
 }
 
+int slam_resample_heads_host(slam_engine* e, int32_t* heads, int32_t* n)
+{
+    SLAM_ENTER(e);
+    if (!heads || !n) return SLAM_ERR_INVALID_ARG;
+    *heads = e->h_heads[0];   // mapped host memory, read as the engine's own heuristic reads it: no wait
+    *n = e->h_heads[1];
+    return SLAM_OK;
+}
+
 int slam_quantise_weights_dev(slam_engine* e, const float* d_logw, const float* d_max, int n, uint64_t* d_wq,
                               uint64_t* d_sum)
 {

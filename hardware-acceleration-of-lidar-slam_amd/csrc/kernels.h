@@ -568,9 +568,10 @@ hipError_t launch_offspring_offsets(hipStream_t stream, const uint64_t* cdf, int
                                     int32_t* first);
 hipError_t launch_ancestors(hipStream_t stream, const int32_t* first_all, int64_t n_total, int64_t slot0, int nslots,
                             int32_t* anc);
-// single GPU: offspring offsets + ancestors in one launch (n up to 8M; beyond that use the two launches above)
+// single GPU: offspring offsets + ancestors in one launch (n up to 8M; beyond that use the two launches above): every particle
+// fills the run of slots it owns, [first[i], first[i + 1]) (offspring_fill_kernel)
 bool ancestors_from_scan_fits(int n);
-// survivors (optional): mark[anc[j]] = stamp for every slot j — the particles the resample kept
+// survivors (optional): mark[i] = stamp for every particle i that is some slot's ancestor — the particles the resample kept
 struct SurvivorOut {
     uint32_t* mark = nullptr;   // [n]
     uint32_t stamp = 0;

@@ -5,6 +5,7 @@
 // No reference counterpart: the specification is DESIGN.md + oracle/slam_oracle_pf.c, matched bit for bit.
 
 #include "det_math.h"
+#include "comb_quotient.h"
 #include "cov_update_body.h"
 #include "pf_common.h"
 
@@ -249,8 +250,11 @@ __device__ __forceinline__ void quantise_scan_body(const float* __restrict__ log
 {
     __shared__ uint64_t s_wave[kBlock / 64];
     __shared__ float s_red[kBlock / 64];
-    const float m = d_max ? *d_max : block_max_of(block_max, nblock_max, s_red);
     const int base = tile * kScanTile + threadIdx.x * kScanItems;
+    float lw[kScanItems];   // asked for in front of the maximum's reduction and its two barriers, which they do not need
+#pragma unroll
+    for (int k = 0; k < kScanItems; ++k) lw[k] = base + k < n ? logw[base + k] : 0.0f;
+    const float m = d_max ? *d_max : block_max_of(block_max, nblock_max, s_red);
     uint64_t v[kScanItems];
     uint64_t run = 0, s16 = 0, q16 = 0;
 #pragma unroll
@@ -258,7 +262,7 @@ __device__ __forceinline__ void quantise_scan_body(const float* __restrict__ log
         const int i = base + k;
         uint64_t q = 0;
         if (i < n) {
-            const float rel = logw[i] - m;
+            const float rel = lw[k] - m;
             q = (uint64_t)(det_expf(rel) * 4294967296.0f);
             if (GATED) carry[i] = rel;
         }
@@ -503,18 +507,15 @@ __global__ __launch_bounds__(kBlock) void offspring_from_scan_kernel(const uint6
 }
 
 // Feedback for the host's choice between the two out-of-place EKF forms (it changes speed, never results): about how many
-// DISTINCT ancestors the resample left — a slot counts when its wavefront neighbour descends from another particle (so
-// wavefront boundaries count once too often: at most n / 64).  Summed with one atomic per workgroup; the workgroup that
-// finishes last hands {count, n} to mapped host memory and clears the counter (8-byte aligned pair of words).  The host
-// reads it without any synchronisation, a frame or two late.
-__device__ __forceinline__ void count_heads(const HeadsOut& h, int val, bool valid, int n)
+// DISTINCT ancestors the resample left — `head`: this thread's particle has offspring.  Summed with one atomic per workgroup;
+// the workgroup that finishes last hands {count, n} to mapped host memory and clears the counter (8-byte aligned pair of words).
+// The host reads it without any synchronisation, a frame or two late.
+__device__ __forceinline__ void count_heads(const HeadsOut& h, bool head, int n)
 {
     // a sample is enough for a heuristic: every 8th workgroup counts, the result is scaled (same-address atomics run at
     // ~88 per microsecond: one per workgroup cost 14 us at 4096 workgroups)
     if (!h.counter || (blockIdx.x & 7u) != 0) return;
     __shared__ int s_heads[kBlock / 64];
-    const int up = __shfl_up(val, 1, 64);
-    const bool head = valid && ((threadIdx.x & 63) == 0 || up != val);
     const int cnt = __popcll(__ballot(head));
     if ((threadIdx.x & 63) == 0) s_heads[threadIdx.x >> 6] = cnt;
     __syncthreads();
@@ -527,134 +528,116 @@ __device__ __forceinline__ void count_heads(const HeadsOut& h, int val, bool val
     const unsigned long long old = atomicAdd(acc, ((unsigned long long)(unsigned)sum << 32) | 1ull);
     const unsigned sampled = (gridDim.x + 7u) / 8u;
     if ((unsigned)(old & 0xffffffffu) != sampled - 1) return;
-    const long long slots = (long long)sampled * kBlock < n ? (long long)sampled * kBlock : n;   // slots the sample covered (about)
-    h.h_out[0] = (int32_t)(((long long)(old >> 32) + sum) * n / slots);
+    const long long owners = (long long)sampled * kBlock < n ? (long long)sampled * kBlock : n;   // particles the sample covered (about)
+    h.h_out[0] = (int32_t)(((long long)(old >> 32) + sum) * n / owners);
     h.h_out[1] = n;
     atomicExch(acc, 0ull);
 }
 
-// Single GPU: the ancestor of every slot straight from the tile-local scan, without materialising `first`.
-// first[i] <= j  <=>  N*C_excl(i) <= j*S + u  (first[i] = ceil((N*C_excl(i) - u)/S), clamped at 0), so the ancestor
-// of slot j — the last i with first[i] <= j — is the number of k in [0, n-1) with N*C_incl(k) <= j*S + u.
-// Both sides are 96-bit quantities, compared as (hi, lo) pairs.  Tile offsets live in LDS: n <= kMaxLdsTiles*2048.
-constexpr int kMaxLdsTiles = 4096;
-template <int kPer>   // tiles per thread: 1 covers n <= 512k with 2 KB of LDS, 16 covers n <= 8M with 32 KB
-__global__ __launch_bounds__(kBlock) void ancestors_from_scan_kernel(const uint64_t* __restrict__ cdf_local,
-                                                                     const uint64_t* __restrict__ tile_total,
-                                                                     int ntiles, int n, uint32_t key0, uint32_t key1,
-                                                                     uint32_t frame, int32_t* __restrict__ anc,
-                                                                     const uint64_t* __restrict__ tile_s16,
-                                                                     const uint64_t* __restrict__ tile_q16,
-                                                                     uint32_t frac_q16, GateOut gate, HeadsOut heads,
-                                                                     SurvivorOut survivors)
+// first[] of a particle whose exclusive CDF is c, with the comb offset already drawn and the total known to be sane
+// (comb_first() without its 64-step division: the offset sits on the one dependent chain of offspring_fill_kernel)
+__device__ __forceinline__ int32_t comb_first_quick(uint64_t c, uint64_t total, uint64_t n_total, uint64_t comb_u)
 {
-    __shared__ uint64_t s_off[kPer * kBlock];
-    __shared__ uint64_t s_wave[kBlock / 64];
-    uint64_t v[kPer], run = 0, s16 = 0, q16 = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        const int t = threadIdx.x * kPer + k;
-        v[k] = run;   // exclusive within the thread
-        run += t < ntiles ? tile_total[t] : 0ull;
-        if (frac_q16 != 0 && t < ntiles) {
+    uint64_t lo = c * n_total, hi = __umul64hi(c, n_total);
+    if (hi == 0 && lo <= comb_u) return 0;
+    const uint64_t sub = comb_u + 1ull;
+    hi -= lo < sub ? 1ull : 0ull;
+    lo -= sub;
+    return (int32_t)(quotient_below_2_32(hi, lo, total) + 1ull);   // c <= total: at most n_total
+}
+
+// Single GPU: the ancestor of every slot straight from the tile-local scan, without materialising `first` and without a
+// search: the OWNER fills its slots.  first[i] <= j  <=>  N*C_excl(i) <= j*S + u  (first[i] = ceil((N*C_excl(i) - u)/S),
+// clamped at 0), so the ancestor of slot j — the last i with first[i] <= j, the number of k in [0, n-1) with
+// N*C_incl(k) <= j*S + u — is i exactly for the slots of [first[i], first[i+1]), and for [first[n-1], n) with the last particle,
+// which takes what is left (k stops at n-1).  first[0] = 0 and first[] never falls: the runs tile [0, n).  first[i+1] comes from
+// C_incl(i), which IS the neighbour's C_excl (the same sum of the same integers, also across a tile edge: the tile's offset plus
+// its total is the next tile's offset), so both bounds come from this thread's own two coalesced loads and no value crosses
+// lanes or workgroups.  A total of 0 (or >= 2^63) has first[] = 0 everywhere: every run is empty but the last particle's, the pinned rule
+// by itself.  A gated frame that keeps its population: run i is [i, i+1).
+// The chain: loads (tile totals and the two CDF values, side by side) -> one block sum -> arithmetic -> stores.
+// The fill never loops over a run in one thread: a run of up to kOwnSlots slots is stored by its owner (neighbouring lanes own
+// neighbouring slots), a longer one by the whole wavefront, 64 slots per store — at most n/64 + 64 store instructions in a
+// wavefront however the weights lie (one particle with all the weight: n/64).
+constexpr int kMaxScanTiles = 4096;   // n <= 8M (beyond: the two-launch form)
+constexpr int kOwnSlots = 4;
+__global__ __launch_bounds__(kBlock) void offspring_fill_kernel(const uint64_t* __restrict__ cdf_local,
+                                                                const uint64_t* __restrict__ tile_total, int ntiles, int n,
+                                                                uint32_t key0, uint32_t key1, uint32_t frame,
+                                                                int32_t* __restrict__ anc, const uint64_t* __restrict__ tile_s16,
+                                                                const uint64_t* __restrict__ tile_q16, uint32_t frac_q16,
+                                                                GateOut gate, HeadsOut heads, SurvivorOut survivors)
+{
+    __shared__ uint64_t s_red[4][kBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * kBlock + threadIdx.x;      // the particle this thread owns
+    const int tile = (blockIdx.x * kBlock) / kScanTile;   // kScanTile is a multiple of kBlock
+    const bool in = i < n, gated = frac_q16 != 0;
+    const uint64_t c_own = in ? cdf_local[i] : 0ull;                           // inclusive, local to the tile
+    const uint64_t c_prev = in && (i % kScanTile) ? cdf_local[i - 1] : 0ull;   // exclusive: 0 at a tile's start
+    uint64_t before = 0, total = 0, s16 = 0, q16 = 0;
+    for (int t = threadIdx.x; t < ntiles; t += kBlock) {   // (one turn up to 512k particles)
+        const uint64_t v = tile_total[t];
+        total += v;
+        before += t < tile ? v : 0ull;
+        if (gated) {
             s16 += tile_s16[t];
             q16 += tile_q16[t];
         }
     }
-    uint64_t total;
-    const uint64_t excl = block_inclusive_scan(run, s_wave, total) - run;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) s_off[threadIdx.x * kPer + k] = v[k] + excl;
+    before = wave_sum_u64(before);
+    total = wave_sum_u64(total);
+    if (gated) {
+        s16 = wave_sum_u64(s16);
+        q16 = wave_sum_u64(q16);
+    }
+    if (lane == 0) {
+        s_red[0][wave] = before;
+        s_red[1][wave] = total;
+        s_red[2][wave] = s16;
+        s_red[3][wave] = q16;
+    }
     __syncthreads();
-    const int j = blockIdx.x * kBlock + threadIdx.x;
+    before = total = s16 = q16 = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) {
+        before += s_red[0][w];
+        total += s_red[1][w];
+        s16 += s_red[2][w];
+        q16 += s_red[3][w];
+    }
     bool resample = true;
-    if (frac_q16 != 0) {   // resample gate: the same verdict in every workgroup
-        s16 = block_sum_u64(s16, s_wave);
-        q16 = block_sum_u64(q16, s_wave);
+    if (gated) {   // resample gate: the same verdict in every workgroup
         resample = ess_wants_resample(s16, q16, (uint64_t)n, frac_q16);
         if (blockIdx.x == 0 && threadIdx.x == 0) publish_gate(gate, resample);
     }
-    int val = -1;   // this slot's ancestor (-1: no such slot)
-    const bool search = resample && !(total == 0 || (total >> 63));   // the same in every thread of every workgroup
-    if (j < n && !search) val = resample ? n - 1   // see offspring_offsets_kernel: every slot gets the last particle
-                                         : j;      // the frame keeps its population
-    if (search) {
-        const bool in = j < n;
-        const uint64_t N = (uint64_t)n;
-        uint64_t t_lo = 0, t_hi = 0;
-        int tlo = 0;
-        auto below = [&](uint64_t c) {   // N * c <= T, both sides 96-bit quantities compared as (hi, lo) pairs
-            const uint64_t x_lo = c * N, x_hi = __umul64hi(c, N);
-            return x_hi < t_hi || (x_hi == t_hi && x_lo <= t_lo);
-        };
-        if (in) {
+    int lo = i, hi = i + 1;   // the frame keeps its population: slot i descends from particle i
+    if (resample) {
+        lo = hi = 0;   // total 0 or >= 2^63 (see offspring_offsets_kernel): no division, first[] = 0
+        if (!(total == 0 || (total >> 63))) {
             const u32x4 r = philox4x32_10(0u, 0u, frame, 1u /* resample stream */, key0, key1);
             const uint64_t comb_u = __umul64hi((uint64_t)r.v[0] | ((uint64_t)r.v[1] << 32), total);
-            t_lo = (uint64_t)j * total;
-            t_hi = __umul64hi((uint64_t)j, total);
-            t_lo += comb_u;
-            t_hi += t_lo < comb_u ? 1ull : 0ull;
-            // number of k in [0, n-1) with N*C_incl(k) <= T.  First among the tiles, in LDS: the CDF at the end of tile t is
-            // the offset of tile t + 1 (the grand total for the last one), so whole tiles below T are counted without
-            // touching memory; then inside the one tile that holds the boundary.
-            int thi = ntiles - 1;   // first tile whose last element lies above T (the last tile if none does)
-            while (tlo < thi) {
-                const int mid = (tlo + thi) >> 1;
-                if (below(s_off[mid + 1])) tlo = mid + 1; else thi = mid;   // mid + 1 <= ntiles - 1
-            }
+            lo = comb_first_quick(before + c_prev, total, (uint64_t)n, comb_u);
+            hi = comb_first_quick(before + c_own, total, (uint64_t)n, comb_u);
         }
-        int lo = tlo * kScanTile, hi = (tlo + 1) * kScanTile < n - 1 ? (tlo + 1) * kScanTile : n - 1;
-        const uint64_t off = s_off[tlo];   // (every pivot below lies in tile tlo)
-        // kPer == 1 (n <= 512k): a second level in LDS.  The thresholds rise with the slot, so the workgroup's 256 slots fall
-        // into the tiles of its first and its last slot; when that is at most two tiles, the CDF at the END of each of their
-        // 32-element blocks (64 values per tile: one strided load per thread, one round trip) is staged in LDS, six LDS steps
-        // find the block, and five dependent L2 round trips remain of the eleven (measured: 7.6 -> 7.1 us at 64k slots; staging the
-        // whole window instead, 16-32 KB, was slower: 9.5 us).  The same comparisons on the same values: the block whose last element is the first above T holds the
-        // answer, and if none is, the search ends at the tile's upper bound as it does without the second level.
-        if constexpr (kPer == 1) {
-            constexpr int kSub = 32, kSubPerTile = kScanTile / kSub;
-            __shared__ uint64_t s_sub[2 * kSubPerTile];
-            __shared__ int s_t[2];
-            const int last = (n - 1 - (int)blockIdx.x * kBlock) < kBlock - 1 ? (n - 1 - (int)blockIdx.x * kBlock) : kBlock - 1;
-            if (threadIdx.x == 0) s_t[0] = tlo;
-            if ((int)threadIdx.x == last) s_t[1] = tlo;
-            __syncthreads();
-            const int tmin = s_t[0], tmax = s_t[1];
-            const bool staged = tmax - tmin <= 1;   // (workgroup-uniform)
-            if (staged) {
-                for (int q = threadIdx.x; q < (tmax - tmin + 1) * kSubPerTile; q += kBlock) {
-                    const int idx = tmin * kScanTile + q * kSub + kSub - 1;
-                    s_sub[q] = cdf_local[idx < n ? idx : n - 1];   // (beyond the data: never looked at below)
-                }
-                __syncthreads();
-                if (in) {
-                    // first block b of tile tlo whose last element is above T, among the blocks that end below `hi`
-                    const int nblk = (hi - lo) / kSub;   // whole blocks in [lo, hi): their last elements are < hi
-                    const uint64_t* sub = s_sub + (tlo - tmin) * kSubPerTile;
-                    int blo = 0, bhi = nblk;
-                    while (blo < bhi) {
-                        const int mid = (blo + bhi) >> 1;
-                        if (below(sub[mid] + off)) blo = mid + 1; else bhi = mid;
-                    }
-                    if (blo < nblk) hi = lo + blo * kSub + kSub - 1;   // that element is above T: the answer is at or below it
-                    lo += blo * kSub;
-                }
-            }
-        }
-        if (in) {
-            // (an 8-ary search — seven pivots per step side by side — was measured equal: 10.5 us at 64k slots, 62 us at 1M:
-            // fewer dependent round trips, but seven times the gathers)
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (below(cdf_local[mid] + off)) lo = mid + 1; else hi = mid;
-            }
-            val = lo;
-        }
+        if (i == n - 1) hi = n;   // the last particle takes every slot that is left
+        lo = lo < 0 ? 0 : lo > n ? n : lo;
+        hi = hi < 0 ? 0 : hi > n ? n : hi;
     }
-    if (j < n) anc[j] = val;
-    // survivor rows: the particles this resample kept (val in [0, n); slots of one ancestor store the same word: no atomics)
-    if (j < n && survivors.mark) survivors.mark[val] = survivors.stamp;
-    count_heads(heads, val, j < n, n);
+    if (!in) lo = hi = 0;
+    const int len = hi - lo;
+#pragma unroll
+    for (int k = 0; k < kOwnSlots; ++k)
+        if (len <= kOwnSlots && k < len) anc[lo + k] = i;
+    for (unsigned long long wide = __ballot(len > kOwnSlots); wide; wide &= wide - 1) {
+        const int src = __ffsll(wide) - 1;   // (wavefront-uniform: the run's bounds come through scalar registers)
+        const int r_lo = __builtin_amdgcn_readlane(lo, src), r_hi = __builtin_amdgcn_readlane(hi, src);
+        const int owner = i - lane + src;
+        for (int s = r_lo + lane; s < r_hi; s += 64) anc[s] = owner;
+    }
+    // survivor rows: the particles this resample kept mark themselves
+    if (len > 0 && survivors.mark) survivors.mark[i] = survivors.stamp;
+    count_heads(heads, len > 0, n);
 }
 
 __global__ __launch_bounds__(kBlock) void ancestors_kernel(const int32_t* __restrict__ first_all, int64_t n_total,
@@ -918,7 +901,7 @@ hipError_t launch_offspring_offsets(hipStream_t stream, const uint64_t* cdf, int
     return hipGetLastError();
 }
 
-bool ancestors_from_scan_fits(int n) { return n > 0 && scan_tile_count(n) <= kMaxLdsTiles; }
+bool ancestors_from_scan_fits(int n) { return n > 0 && scan_tile_count(n) <= kMaxScanTiles; }
 
 hipError_t launch_ancestors_from_scan(hipStream_t stream, const uint64_t* cdf_local, const uint64_t* tile_total, int n,
                                       uint64_t seed, uint32_t frame, int32_t* anc, uint32_t frac_q16, const GateOut& gate,
@@ -927,14 +910,8 @@ hipError_t launch_ancestors_from_scan(hipStream_t stream, const uint64_t* cdf_lo
     if (n <= 0) return hipSuccess;
     const int ntiles = scan_tile_count(n);
     const uint64_t *ts = tile_total + ntiles, *tq = tile_total + 2 * ntiles;   // layout of the engine's scan state
-    if (ntiles <= kBlock)
-        ancestors_from_scan_kernel<1><<<blocks_for(n), kBlock, 0, stream>>>(cdf_local, tile_total, ntiles, n, (uint32_t)seed,
-                                                                            (uint32_t)(seed >> 32), frame, anc, ts, tq,
-                                                                            frac_q16, gate, heads, survivors);
-    else
-        ancestors_from_scan_kernel<kMaxLdsTiles / kBlock><<<blocks_for(n), kBlock, 0, stream>>>(
-            cdf_local, tile_total, ntiles, n, (uint32_t)seed, (uint32_t)(seed >> 32), frame, anc, ts, tq, frac_q16, gate,
-            heads, survivors);
+    offspring_fill_kernel<<<blocks_for(n), kBlock, 0, stream>>>(cdf_local, tile_total, ntiles, n, (uint32_t)seed, (uint32_t)(seed >> 32),
+                                                                frame, anc, ts, tq, frac_q16, gate, heads, survivors);
     return hipGetLastError();
 }
 

@@ -545,6 +545,10 @@ int slam_offspring_from_scan_sharded_dev(slam_engine *e, int n, const uint64_t *
  *    can run the next EKF in place (map_in == map_out, no gather) instead of out of place. */
 int slam_resample_gate_set(slam_engine *e, float ess_frac);
 int slam_resample_happened_host(slam_engine *e, int *resampled);
+/* What the last resample stage of a population with maps reported, for looking at: about how many distinct ancestors it
+ * left, and the population that count belongs to (-1: nothing reported yet).  It steers the engine's choice between update
+ * forms, never a result; read without any synchronisation, so it may be a frame or two old. */
+int slam_resample_heads_host(slam_engine *e, int32_t *heads, int32_t *n);
 
 /* A12: systematic resampling on the exact integer CDF.
  *  step 1 (per shard): d_cdf[i] = inclusive prefix sum of wq within the shard.
