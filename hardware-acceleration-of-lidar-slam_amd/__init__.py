@@ -67,6 +67,7 @@ SIGNATURES = {
     "slam_grid_upload_host": (_i, [_vp, _i, _vp, C.POINTER(GridMeta), _f, _vp]),
     "slam_grid_set_dev": (_i, [_vp, _i, _vp, C.POINTER(GridMeta)]),
     "slam_grid_set_meta": (_i, [_vp, _i, C.POINTER(GridMeta)]),
+    "slam_grid_packed_state": (_i, [_vp, _i, C.POINTER(C.c_int)]),
     "slam_scan_upload_host": (_i, [_vp, _vp, _vp, _i]),
     "slam_scan_set_dev": (_i, [_vp, _vp, _vp, _i]),
     "slam_score_poses_cs_dev": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
@@ -317,6 +318,12 @@ class Engine:
 
     def grid_set_meta(self, slot: int, meta: GridMeta):
         self._ck(self.lib.slam_grid_set_meta(self.h, slot, C.byref(meta)), "grid_set_meta")
+
+    def grid_packed_state(self, slot: int) -> int:
+        """``slam_grid_packed_state``: 0 no verdict since the grid last changed, 1 the packed copy is in use, 2 the grid does not pack."""
+        s = C.c_int(-1)
+        self._ck(self.lib.slam_grid_packed_state(self.h, slot, C.byref(s)), "grid_packed_state")
+        return int(s.value)
 
     def scan_upload(self, bx, by):
         bx, by = _np(bx, np.float32), _np(by, np.float32)

@@ -203,6 +203,15 @@ int slam_grid_set_meta(slam_engine* e, int slot, const slam_grid_meta* meta)
     return SLAM_OK;
 }
 
+int slam_grid_packed_state(slam_engine* e, int slot, int* state)
+{
+    SLAM_ENTER(e);
+    if (!slot_ok(slot) || !state) return SLAM_ERR_INVALID_ARG;
+    if (!e->grid[slot].ready) return SLAM_ERR_NOT_READY;
+    *state = e->grid[slot].packed_state;
+    return SLAM_OK;
+}
+
 int slam_scan_upload_host(slam_engine* e, const float* bx, const float* by, int nbeams)
 {
     SLAM_ENTER(e);

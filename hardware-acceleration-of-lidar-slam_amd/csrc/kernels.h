@@ -32,8 +32,10 @@ struct ScoreGrid {
 // The capped EDT (main.c:223-269, Appendix A.4) holds few distinct values: 0 on an occupied cell, sqrtf(d2) of a small
 // integer d2 below the cap, and the cap itself.  launch_edt_pack writes code(cell) = d2 (255: the grid's largest value) into
 // `packed`, table[code] = the float it stands for, and flag[1] = 1 if some cell of the rows x cols rectangle is not table[its
-// code] bit for bit (a grid that did not come from the EDT kernels, or a cap above 15.9 cells): the caller then keeps the
-// float grid.  flag: two device words {largest value's bits (scratch), bad}, zeroed by the launcher.
+// code] bit for bit (a grid that did not come from the EDT kernels, or a cap above 16.0 cells with two different values of
+// 16.0 and more: at cap 16.0 the largest distance below the cap is sqrtf(250) — 251 .. 255 are no sums of two squares — and
+// 16.0 itself is the largest value): the caller then keeps the float grid.  flag: two device words {largest value's bits
+// (scratch), bad}, zeroed by the launcher.
 size_t edt_packed_bytes(int rows, int cols);
 hipError_t launch_edt_pack(hipStream_t stream, const float* edt, int ld, int rows, int cols, uint8_t* packed, float* table,
                            uint32_t* flag);

@@ -161,6 +161,14 @@ int slam_grid_set_meta(slam_engine *e, int slot, const slam_grid_meta *meta);
  * slam_grid_set_dev again after rewriting the cells of an adopted grid (slam_edt_dev into the adopted buffer is noticed
  * by itself).  Results are bit-identical either way. */
 int slam_grid_set_dev(slam_engine *e, int slot, const float *d_edt, const slam_grid_meta *meta);
+/* Where grid `slot` stands with its packed copy: *state = 0: no verdict since the grid last changed (upload, adoption,
+ * slam_edt_dev into the adopted buffer) — no scorer of >= 3 072 poses has read it since, or the grid has fewer than 8 rows or
+ * 16 columns; 1: the packed copy is in use; 2: the grid does not pack (a cell that is neither sqrtf of an integer 0 .. 254 nor
+ * the grid's largest value) and the scorers keep the float grid.  slam_grid_set_meta leaves the state as it is.  A capped EDT
+ * packs at every cap up to 16.0 (its distances below the cap are sqrtf of at most 250); with a larger cap it packs as long as
+ * its cells of 16.0 and more all hold one value.  Reads host bookkeeping only: no launch, no wait.  SLAM_ERR_NOT_READY:
+ * nothing in the slot. */
+int slam_grid_packed_state(slam_engine *e, int slot, int *state);
 /* Sensor-frame cartesian beams of the current scan = scan.x / scan.y (main.c:60-69). */
 int slam_scan_upload_host(slam_engine *e, const float *bx, const float *by, int nbeams);
 int slam_scan_set_dev(slam_engine *e, const float *d_bx, const float *d_by, int nbeams);
