@@ -123,6 +123,12 @@ SIGNATURES = {
     "slam_associate_aniso_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _i, _vp, _i, _vp]),
     "slam_ekf_update_assoc_aniso_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "slam_assoc_aniso_counts": (_i, [_vp, _vp]),
+    "slam_detections_cov_upload_host": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "slam_detections_cov_set_dev": (_i, [_vp, _vp, _vp, _vp, _i]),
+    "slam_detections_get_cov_host": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "slam_associate_detcov_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _vp, _i, _vp]),
+    "slam_ekf_update_assoc_detcov_dev": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "slam_assoc_detcov_counts": (_i, [_vp, _vp]),
     "slam_landmark_evidence_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "slam_evidence_init_dev": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _i]),
     "slam_evidence_counts": (_i, [_vp, _vp]),
@@ -172,6 +178,10 @@ SIGNATURES = {
     "slam_pf_assoc_set": (_i, [_vp, _f, _f, _i]),
     "slam_pf_assoc_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_assoc_cov_set": (_i, [_vp, _vp, _f, _f, _i]),
+    "slam_pf_assoc_detcov_set": (_i, [_vp, _f, _f, _i]),
+    "slam_pf_detect_noise_set": (_i, [_vp, _vp, _vp, _vp]),
+    "slam_detect_scan_noise_dev": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "slam_detect_noise_count": (_i, [_vp, _vp]),
     "slam_pf_prune_set": (_i, [_vp, _i, _i, _i, _f]),
     "slam_pf_evidence_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_evidence_host": (_i, [_vp, _vp]),
@@ -490,6 +500,47 @@ class Engine:
         self._ck(self.lib.slam_assoc_aniso_counts(self.h, c), "assoc_aniso_counts")
         return int(c[0]), int(c[1])
 
+    def detections_cov_upload(self, qxx, qxy, qyy):
+        """``slam_detections_cov_upload_host``: a sensor-frame covariance Q_k = (qxx[k], qxy[k], qyy[k]) for each of the
+        detections handed over last."""
+        qxx, qxy, qyy = _np(qxx, np.float32), _np(qxy, np.float32), _np(qyy, np.float32)
+        assert len(qxx) == len(qxy) == len(qyy)
+        self._ck(self.lib.slam_detections_cov_upload_host(self.h, _ptr(qxx), _ptr(qxy), _ptr(qyy), len(qxx)), "detections_cov_upload")
+
+    def detections_cov_set_dev(self, d_qxx, d_qxy, d_qyy, ndet):
+        """``slam_detections_cov_set_dev``: the same from three device arrays, adopted and read afresh by every launch."""
+        self._ck(self.lib.slam_detections_cov_set_dev(self.h, _ptr(d_qxx), _ptr(d_qxy), _ptr(d_qyy), ndet), "detections_cov_set_dev")
+        self.__dict__.setdefault("_adopted", {})["detcov"] = (d_qxx, d_qxy, d_qyy)
+
+    def detections_cov(self):
+        """``slam_detections_get_cov_host``: the covariances of the current detections -> (qxx, qxy, qyy) float32 [ndet];
+        synchronises."""
+        q = [np.full(64, np.nan, np.float32) for _ in range(3)]
+        k = C.c_int32(-1)
+        self._ck(self.lib.slam_detections_get_cov_host(self.h, _ptr(q[0]), _ptr(q[1]), _ptr(q[2]), C.byref(k)), "detections_get_cov_host")
+        return tuple(v[:k.value].copy() for v in q)
+
+    def associate_detcov_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, gate, new_gate, create,
+                             d_assoc, assoc_stride, d_stats):
+        """``slam_associate_detcov_dev``: associate_aniso_dev with the covariance each detection carries in the place of one Q."""
+        self._ck(self.lib.slam_associate_detcov_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x), _ptr(d_y),
+                                                    _ptr(d_th), _ptr(d_anc), n, gate, new_gate, int(create), _ptr(d_assoc),
+                                                    assoc_stride, _ptr(d_stats)), "associate_detcov_dev")
+
+    def ekf_update_assoc_detcov_dev(self, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n,
+                                    d_assoc, assoc_stride, d_loglik):
+        """``slam_ekf_update_assoc_detcov_dev``: ekf_update_assoc_aniso_dev with, for every landmark, the covariance of the
+        detection its table entry names."""
+        self._ck(self.lib.slam_ekf_update_assoc_detcov_dev(self.h, _ptr(d_map_in), _ptr(d_map_out), row_stride, plane_stride, nlandmarks,
+                                                           _ptr(d_x), _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, _ptr(d_assoc),
+                                                           assoc_stride, _ptr(d_loglik)), "ekf_update_assoc_detcov_dev")
+
+    def assoc_detcov_counts(self):
+        """-> (associate launches, assoc-update launches) under per-detection covariances of this engine so far."""
+        c = (C.c_int64 * 2)()
+        self._ck(self.lib.slam_assoc_detcov_counts(self.h, c), "assoc_detcov_counts")
+        return int(c[0]), int(c[1])
+
     def landmark_evidence_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_anc, n, d_assoc, assoc_stride, d_ev_in,
                               d_ev_out, ev_stride, hit, miss, cmax, view_range, d_stats):
         """``slam_landmark_evidence_dev``: the evidence bytes uint8 [n][ev_stride] behind a frame's associating update; pruned
@@ -517,6 +568,21 @@ class Engine:
         f = DetectFit.of(fit)
         self._ck(self.lib.slam_detect_scan_fit_dev(self.h, C.byref(p), C.byref(f) if f is not None else None, _ptr(d_stats)),
                  "detect_scan_fit_dev")
+
+    def detect_scan_noise_dev(self, noise, fit=None, params: "DetectParams | None" = None, d_stats=None, **kw):
+        """``slam_detect_scan_noise_dev``: detect_scan_fit_dev with the noise model (range_var, bearing_var, lateral_var) (None:
+        exactly detect_scan_fit_dev): the detections carry covariances; d_stats: int32 [6]."""
+        p = params if params is not None else DetectParams.default(**kw)
+        f = DetectFit.of(fit)
+        z = DetectNoise.of(noise)
+        self._ck(self.lib.slam_detect_scan_noise_dev(self.h, C.byref(p), C.byref(f) if f is not None else None,
+                                                     C.byref(z) if z is not None else None, _ptr(d_stats)), "detect_scan_noise_dev")
+
+    def detect_noise_count(self) -> int:
+        """Detector launches of this engine so far that ran the noise model."""
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_detect_noise_count(self.h, C.byref(c)), "detect_noise_count")
+        return c.value
 
     def detect_fit_count(self) -> int:
         """Detector launches of this engine so far that ran the fit."""
@@ -691,6 +757,20 @@ class DetectParams(C.Structure):
                 raise TypeError(f"slam_detect_params has no field {k!r}")
             setattr(p, k, v)
         return p
+
+
+class DetectNoise(C.Structure):
+    """``slam_detect_noise``: the detector's noise model — variance along the line of sight, of the bearing [rad^2], and a
+    range-independent one across the line of sight (slam_detect_scan_noise_dev)."""
+
+    _fields_ = [("range_var", C.c_float), ("bearing_var", C.c_float), ("lateral_var", C.c_float)]
+
+    @classmethod
+    def of(cls, noise):
+        """None, a DetectNoise or (range_var, bearing_var[, lateral_var]) -> None or a DetectNoise."""
+        if noise is None or isinstance(noise, cls):
+            return noise
+        return cls(*noise)
 
 
 class DetectFit(C.Structure):
@@ -1049,6 +1129,11 @@ class PfSession:
         gate = 0 switches it off."""
         self.e._ck(self.e.lib.slam_pf_assoc_set(self.h, gate, new_gate, 1 if create else 0), "pf_assoc_set")
 
+    def assoc_detcov_set(self, gate: float, new_gate: float = 0.0, create: bool = True):
+        """``slam_pf_assoc_detcov_set``: association under the covariance each detection carries (Engine.detections_cov_upload
+        behind every hand-over of detections)."""
+        self.e._ck(self.e.lib.slam_pf_assoc_detcov_set(self.h, gate, new_gate, 1 if create else 0), "pf_assoc_detcov_set")
+
     def assoc_cov_set(self, meas_cov, gate: float, new_gate: float = 0.0, create: bool = True):
         """``slam_pf_assoc_cov_set``: association under the 2x2 sensor-frame covariance (qxx, qxy, qyy) — covariance and gates in one
         switch; (meas_var, 0, meas_var) is exactly assoc_set(gate, new_gate, create)."""
@@ -1074,6 +1159,17 @@ class PfSession:
             return
         p = DetectParams.default(**kw) if params is True else params
         self.e._ck(self.e.lib.slam_pf_detect_set(self.h, C.byref(p)), "pf_detect_set")
+
+    def detect_noise_set(self, noise, fit=None, params: "DetectParams | None | bool" = True, **kw):
+        """``slam_pf_detect_noise_set``: detect_fit_set with the noise model (range_var, bearing_var, lateral_var): the detector's
+        detections carry covariances (None: detect_fit_set)."""
+        if params is None or params is False:
+            self.e._ck(self.e.lib.slam_pf_detect_noise_set(self.h, None, None, None), "pf_detect_noise_set")
+            return
+        p = DetectParams.default(**kw) if params is True else params
+        f, z = DetectFit.of(fit), DetectNoise.of(noise)
+        self.e._ck(self.e.lib.slam_pf_detect_noise_set(self.h, C.byref(p), C.byref(f) if f is not None else None,
+                                                       C.byref(z) if z is not None else None), "pf_detect_noise_set")
 
     def detect_fit_set(self, fit: "DetectFit | tuple | None", params: "DetectParams | None | bool" = True, **kw):
         """``slam_pf_detect_fit_set``: detect_set with the fit (a DetectFit or (radius, spread_tol); None: detect_set)."""

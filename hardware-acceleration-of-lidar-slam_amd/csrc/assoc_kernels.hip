@@ -19,6 +19,11 @@
 // Under a full 2x2 sensor-frame measurement covariance Q (specification: tests/_assoc_aniso_spec.py) association and update run
 // with S = P + R_w(theta_i): associate_body takes the noise as a policy (AssocNoiseIso: the lines above; AssocNoiseAniso: R_w once
 // per wavefront, S^-1 with the operations of ekf_aniso_update_one), and the update's noise policy is EkfNoiseAniso.
+//
+// Under a covariance PER DETECTION (specification: tests/_assoc_detcov_spec.py) S = P + R_w(theta_i, k) differs from detection
+// to detection: AssocNoiseDet has lane k form R_w(theta_i, k) once (all K in one pass, beside the world-frame point it already
+// holds), the loop over k reads it into scalar registers with the point, and S^-1 — the same operations, the same reciprocal —
+// moves INSIDE that loop, per (landmark, detection) pair.  The update's noise policy is EkfNoiseDet.
 
 #include "ekf_aniso_math.h"
 #include "ekf_wave.h"
@@ -56,6 +61,7 @@ __device__ __forceinline__ u64 below(unsigned lane) { return (1ull << lane) - 1u
 // The measurement noise of one particle as the association sees it: S^-1 = (P + noise)^-1 of the two landmarks of a lane, in
 // EkfShared's i00 / i01 / i11.
 struct AssocNoiseIso {   // q I: ekf_det_terms without the logarithm, then ekf_shared_from
+    static constexpr bool kPerDetection = false;
     v2f q;
     __device__ __forceinline__ AssocNoiseIso(float meas_var, float, float) : q(bc2(meas_var)) {}
     __device__ __forceinline__ EkfShared<v2f> inverse(v2f pxx, v2f pxy, v2f pyy) const
@@ -66,7 +72,9 @@ struct AssocNoiseIso {   // q I: ekf_det_terms without the logarithm, then ekf_s
     }
 };
 struct AssocNoiseAniso {   // R_w = H^T Q H of the particle's heading: the operations of ekf_aniso_update_one, the update's own reciprocal
+    static constexpr bool kPerDetection = false;
     float rxx, rxy, ryy;   // wave-uniform, held in scalar registers
+    __device__ __forceinline__ AssocNoiseAniso(float xx, float xy, float yy) : rxx(xx), rxy(xy), ryy(yy) {}   // (wave-uniform values)
     __device__ __forceinline__ AssocNoiseAniso(const EkfAnisoCov& q, float s, float c)
     {
         float xx, xy, yy;
@@ -87,8 +95,23 @@ struct AssocNoiseAniso {   // R_w = H^T Q H of the particle's heading: the opera
         return h;
     }
 };
+struct AssocNoiseDet {   // R_w(k) = H^T Q_k H: AssocNoiseAniso per detection, S^-1 per (landmark, detection) pair
+    static constexpr bool kPerDetection = true;
+    float rxx, rxy, ryy;   // lane k: R_w of detection k (lanes from ndet on: of the identity, never read)
+    __device__ __forceinline__ AssocNoiseDet(const DetCovArgs& q, float s, float c)
+    {
+        const int lane = (int)(threadIdx.x & 63u);
+        const float qxx = lane < q.ndet ? q.qxx[lane] : 1.0f, qxy = lane < q.ndet ? q.qxy[lane] : 0.0f, qyy = lane < q.ndet ? q.qyy[lane] : 1.0f;
+        ekf_aniso_world_noise<float>(qxx, qxy, qyy, s, c, rxx, rxy, ryy);
+    }
+    __device__ __forceinline__ EkfShared<v2f> inverse(v2f pxx, v2f pxy, v2f pyy, unsigned k) const
+    {
+        const AssocNoiseAniso one(lane_value(rxx, (int)k), lane_value(rxy, (int)k), lane_value(ryy, (int)k));
+        return one.inverse(pxx, pxy, pyy);
+    }
+};
 
-// NOISE(qp, sine, cosine): one of the two above; qp: meas_var, or Q
+// NOISE(qp, sine, cosine): one of the three above; qp: meas_var, Q, or the detections' Q_k
 template <bool CREATE, class NOISE, class QP> __device__ __forceinline__ void associate_body(const AssocArgs& a, const QP& qp)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -145,13 +168,15 @@ template <bool CREATE, class NOISE, class QP> __device__ __forceinline__ void as
             // a landmark that takes no part: NaN in its mean makes every m NaN, and NaN passes none of the comparisons below
             mx[t] = seen[t] ? mx[t] : __uint_as_float(0x7fc00000u);
         }
-        // b. S^-1, once per landmark
-        const EkfShared<v2f> h = noise.inverse(pxx, pxy, pyy);
+        // b. S^-1, once per landmark — or, under a covariance per detection, per pair inside the loop
+        EkfShared<v2f> h;
+        if constexpr (!NOISE::kPerDetection) h = noise.inverse(pxx, pxy, pyy);
         // c. the cheapest detection of each landmark
         v2f best = bc2(inf);
         unsigned bk[2] = { 0u, 0u };
         for (unsigned k = 0; k < K; ++k) {
             const v2f wx = bc2(lane_value(wxk, (int)k)), wy = bc2(lane_value(wyk, (int)k));
+            if constexpr (NOISE::kPerDetection) h = noise.inverse(pxx, pxy, pyy, k);
             const v2f dx = wx - mx, dy = wy - my;
             const v2f t0 = h.i00 * dx + h.i01 * dy, t1 = h.i01 * dx + h.i11 * dy;
             const v2f maha = dx * t0 + dy * t1;
@@ -227,6 +252,12 @@ template <bool CREATE> __global__ __launch_bounds__(kEkfWaves * 64) void associa
     associate_body<CREATE, AssocNoiseAniso>(a, q);
 }
 
+// ... under S = P + R_w(k), Q_k per detection (a.meas_var is not read)
+template <bool CREATE> __global__ __launch_bounds__(kEkfWaves * 64) void associate_detcov_kernel(AssocArgs a, DetCovArgs q)
+{
+    associate_body<CREATE, AssocNoiseDet>(a, q);
+}
+
 // the shapes the LDS carve and the row accesses of the associating kernels are sized by
 bool assoc_args_ok(const AssocArgs& a)
 {
@@ -251,6 +282,20 @@ hipError_t launch_associate(hipStream_t stream, const AssocArgs& a_in, const Ekf
         if (create) associate_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
         else associate_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
     }
+    if (ev) (void)hipEventRecord(ev->stop, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_associate_detcov(hipStream_t stream, const AssocArgs& a_in, const DetCovArgs& q, bool create, const EventPair* ev)
+{
+    if (a_in.n <= 0) return hipSuccess;
+    if (!assoc_args_ok(a_in) || q.ndet != a_in.ndet || (q.ndet > 0 && (!q.qxx || !q.qxy || !q.qyy))) return hipErrorInvalidValue;
+    AssocArgs a = a_in;
+    const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
+    const size_t lds = (size_t)kEkfWaves * assoc_lds((unsigned)a.nlandmarks).per_wave;
+    if (ev) (void)hipEventRecord(ev->start, stream);
+    if (create) associate_detcov_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
+    else associate_detcov_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
     if (ev) (void)hipEventRecord(ev->stop, stream);
     return hipGetLastError();
 }

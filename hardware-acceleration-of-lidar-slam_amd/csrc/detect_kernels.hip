@@ -19,6 +19,9 @@
 // m <= 64 LDS points once more for their spread s2 about the centroid; s2 <= rho^2 + tol^2 or the segment is no pole (the shape
 // test: a third mask of the same shape, only counted), and the detection is the point sqrt(rho^2 - s2) behind the centroid on
 // its line of sight — the circle's centre.
+// THE NOISE MODEL (kNoise, a second compile-time policy; specification: tests/_detect_noise_spec.py): the owning lane gives the
+// point that passed its range test its covariance Q = a u u^T + b v v^T (det_noise: one rounded operation per line of the spec);
+// r2 == 0 or a Q that fails the rule of ekf_aniso_cov_ok is no detection (a fourth mask, only counted), in front of the cap.
 
 #include "kernels.h"
 
@@ -68,10 +71,31 @@ __device__ __forceinline__ float det_r2(const DetScan& s, int b)
     return xx + yy;
 }
 
+// Q of the detection (zx, zy), r2 = zx * zx + zy * zy as its range test formed it; false: no detection
+__device__ __forceinline__ bool det_noise(const DetectNoiseArgs& nz, float zx, float zy, float r2, float& qxx, float& qxy, float& qyy)
+{
+    if (!(r2 > 0.0f)) return false;
+    const float rho = sqrtf(r2);
+    const float ux = zx / rho, uy = zy / rho;
+    const float a = nz.range_var;
+    const float t = nz.bearing_var * r2;
+    const float b = t + nz.lateral_var;
+    const float uxx = ux * ux, uyy = uy * uy, uxy = ux * uy;
+    const float x0 = a * uxx, x1 = b * uyy;
+    qxx = x0 + x1;
+    const float d = a - b;
+    qxy = d * uxy;
+    const float y0 = a * uyy, y1 = b * uxx;
+    qyy = y0 + y1;
+    const float d0 = qxx * qyy, d1 = qxy * qxy;
+    EkfAnisoCov q{ qxx, qxy, qyy, d0 - d1 };
+    return ekf_aniso_cov_ok(q);
+}
+
 // the segment that starts at break f: accepted -> its centroid, with kFit the centre fitted to it (shape: the shape test rejected it)
 template <bool kFit>
 __device__ __forceinline__ bool det_segment(const DetScan& s, const DetectArgs& a, const u64* brk, int f, float& zx, float& zy,
-                                            bool& shape)
+                                            bool& shape, float& r2)
 {
     const int P = s.P, span = a.max_points + 1;   // an implementation may stop counting at max_points + 1
     int q = first_set(brk, f + 1, min(f + span + 1, P)), m = -1;
@@ -101,7 +125,8 @@ __device__ __forceinline__ bool det_segment(const DetScan& s, const DetectArgs& 
     zy = sy / fm;
     const float zxx = zx * zx, zyy = zy * zy;
     if constexpr (!kFit) {
-        return zxx + zyy <= a.range2;   // NaN and inf fail: what comes out is finite
+        r2 = zxx + zyy;
+        return r2 <= a.range2;   // NaN and inf fail: what comes out is finite
     } else {
         const float c2 = zxx + zyy;
         if (!(c2 <= a.range2)) return false;   // ... so everything that enters the fit is finite
@@ -126,16 +151,17 @@ __device__ __forceinline__ bool det_segment(const DetScan& s, const DetectArgs& 
         zx = cx + ox;
         zy = cy + oy;
         const float fxx = zx * zx, fyy = zy * zy;
-        return fxx + fyy <= a.range2;
+        r2 = fxx + fyy;
+        return r2 <= a.range2;
     }
 }
 
-template <bool kFit>
-__global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs a)
+template <bool kFit, bool kNoise>
+__device__ __forceinline__ void detect_scan_body(const DetectArgs& a, const DetectNoiseArgs& nz)
 {
     __shared__ float s_x[SLAM_MAX_BEAMS], s_y[SLAM_MAX_BEAMS];
-    __shared__ u64 s_brk[kDetWords], s_acc[kDetWords], s_shp[kFit ? kDetWords : 1];
-    __shared__ int s_pre[kDetWords], s_tot[kFit ? 3 : 2];
+    __shared__ u64 s_brk[kDetWords], s_acc[kDetWords], s_shp[kFit ? kDetWords : 1], s_nz[kNoise ? kDetWords : 1];
+    __shared__ int s_pre[kDetWords], s_tot[kNoise ? 4 : kFit ? 3 : 2];
     const int T = (int)blockDim.x, tid = (int)threadIdx.x, lane = tid & 63;
     const int P = a.nbeams, nwords = (kDetRounds * T) >> 6;   // the words the ballots below write (kDetRounds * T >= P)
     DetScan s;
@@ -166,6 +192,7 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
     __syncthreads();
 
     float zx[kDetRounds], zy[kDetRounds];
+    float qxx[kNoise ? kDetRounds : 1], qxy[kNoise ? kDetRounds : 1], qyy[kNoise ? kDetRounds : 1];
     unsigned kept = 0;
 #pragma unroll
     for (int k = 0; k < kDetRounds; ++k) {
@@ -173,7 +200,15 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
         zx[k] = 0.0f;
         zy[k] = 0.0f;
         bool acc = false, shape = false;
-        if ((mine >> k) & 1u) acc = det_segment<kFit>(s, a, s_brk, b, zx[k], zy[k], shape);
+        float r2 = 0.0f;
+        if ((mine >> k) & 1u) acc = det_segment<kFit>(s, a, s_brk, b, zx[k], zy[k], shape, r2);
+        if constexpr (kNoise) {   // the fourth mask: passed its range test, dropped by the noise rule
+            qxx[k] = qxy[k] = qyy[k] = 0.0f;
+            const bool ok = acc && det_noise(nz, zx[k], zy[k], r2, qxx[k], qxy[k], qyy[k]);
+            const u64 dropped = __ballot(acc && !ok);
+            if (lane == 0) s_nz[b >> 6] = dropped;
+            acc = ok;
+        }
         const u64 word = __ballot(acc);
         if (lane == 0) s_acc[b >> 6] = word;
         if constexpr (kFit) {   // the third mask: rejected by the shape test
@@ -189,6 +224,8 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
         int segs = tid < nwords ? __popcll(s_brk[tid]) : 0;
         int shp = 0;
         if constexpr (kFit) shp = tid < nwords ? __popcll(s_shp[tid]) : 0;
+        int nzd = 0;
+        if constexpr (kNoise) nzd = tid < nwords ? __popcll(s_nz[tid]) : 0;
         int inc = c;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -196,12 +233,15 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
             inc += lane >= d ? up : 0;
             segs += other;
             if constexpr (kFit) shp += __shfl_xor(shp, d, 64);
+            if constexpr (kNoise) nzd += __shfl_xor(nzd, d, 64);
         }
         s_pre[tid] = inc - c;
         if (tid == 63) s_tot[0] = inc;
         if (tid == 0) s_tot[1] = segs;
         if constexpr (kFit)
             if (tid == 0) s_tot[2] = shp;
+        if constexpr (kNoise)
+            if (tid == 0) s_tot[3] = nzd;
     }
     __syncthreads();
 
@@ -214,11 +254,21 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
         if (rank < SLAM_MAX_DETECTIONS) {
             a.det[rank] = zx[k];
             a.det[SLAM_MAX_DETECTIONS + rank] = zy[k];
+            if constexpr (kNoise) {
+                nz.cov[rank] = qxx[k];
+                nz.cov[SLAM_MAX_DETECTIONS + rank] = qxy[k];
+                nz.cov[2 * SLAM_MAX_DETECTIONS + rank] = qyy[k];
+            }
         }
     }
     if (tid < SLAM_MAX_DETECTIONS && tid >= written) {
         a.det[tid] = 0.0f;
         a.det[SLAM_MAX_DETECTIONS + tid] = 0.0f;
+        if constexpr (kNoise) {
+            nz.cov[tid] = 0.0f;
+            nz.cov[SLAM_MAX_DETECTIONS + tid] = 0.0f;
+            nz.cov[2 * SLAM_MAX_DETECTIONS + tid] = 0.0f;
+        }
     }
     if (tid == 0) {
         if (a.stats) {
@@ -227,6 +277,10 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
             a.stats[2] = written;
             if constexpr (kFit) a.stats[3] = s_tot[2];
             else a.stats[3] = 0;
+            if constexpr (kNoise) {
+                a.stats[4] = s_tot[3];
+                a.stats[5] = 0;
+            }
         }
         a.h_out[0] = written;
         __threadfence_system();
@@ -234,9 +288,20 @@ __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs 
     }
 }
 
+template <bool kFit> __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_kernel(DetectArgs a)
+{
+    detect_scan_body<kFit, false>(a, DetectNoiseArgs{});
+}
+
+// ... with the noise model: Q beside every detection, the noise rule in front of the cap, six stats words
+template <bool kFit> __global__ __launch_bounds__(kDetMaxThreads) void detect_scan_noise_kernel(DetectArgs a, DetectNoiseArgs nz)
+{
+    detect_scan_body<kFit, true>(a, nz);
+}
+
 }  // namespace
 
-hipError_t launch_detect_scan(hipStream_t stream, const DetectArgs& a, const EventPair* ev)
+hipError_t launch_detect_scan(hipStream_t stream, const DetectArgs& a, const EventPair* ev, const DetectNoiseArgs* noise)
 {
     if (a.nbeams < 0 || a.nbeams > SLAM_MAX_BEAMS || a.min_points < 1 || a.max_points > SLAM_DETECT_MAX_POINTS ||
         a.min_points > a.max_points || !a.det || !a.h_out || (a.nbeams > 0 && (!a.bx || !a.by)) || (a.fit != 0 && a.fit != 1))
@@ -244,7 +309,10 @@ hipError_t launch_detect_scan(hipStream_t stream, const DetectArgs& a, const Eve
     int threads = ((a.nbeams + kDetRounds - 1) / kDetRounds + 63) & ~63;
     threads = threads < 64 ? 64 : threads;
     if (ev) (void)hipEventRecord(ev->start, stream);
-    if (a.fit) detect_scan_kernel<true><<<1, threads, 0, stream>>>(a);
+    if (noise && !noise->cov) return hipErrorInvalidValue;
+    if (noise && a.fit) detect_scan_noise_kernel<true><<<1, threads, 0, stream>>>(a, *noise);
+    else if (noise) detect_scan_noise_kernel<false><<<1, threads, 0, stream>>>(a, *noise);
+    else if (a.fit) detect_scan_kernel<true><<<1, threads, 0, stream>>>(a);
     else detect_scan_kernel<false><<<1, threads, 0, stream>>>(a);
     if (ev) (void)hipEventRecord(ev->stop, stream);
     return hipGetLastError();

@@ -27,6 +27,17 @@ __device__ __forceinline__ void ekf_aniso_world_noise(const EkfAnisoCov& q, floa
     ryy = b1 * c - b0 * s;
 }
 
+// ... of a Q that differs between the components of T (a covariance per detection: ekf_aniso_lane.h, EkfNoiseDet); the same
+// operations in the same order
+template <class T> __device__ __forceinline__ void ekf_aniso_world_noise(T qxx, T qxy, T qyy, T s, T c, T& rxx, T& rxy, T& ryy)
+{
+    const T a0 = c * qxx + s * qxy, a1 = c * qxy + s * qyy;
+    const T b0 = c * qxy - s * qxx, b1 = c * qyy - s * qxy;
+    rxx = a0 * c + a1 * s;
+    rxy = a1 * c - a0 * s;
+    ryy = b1 * c - b0 * s;
+}
+
 // prior (mx, my, pxx, pxy, pyy), observation (zx, zy) in the sensor frame, pose (px, py, heading sine s / cosine c), the
 // particle's R_w (rxx, rxy, ryy) and det Q.  What the update of a landmark seen before gives (o0 .. o4, ll) and the observed
 // point in the world frame (f0, f1: what a first sighting stores, with P = R_w and no term); the caller selects as for

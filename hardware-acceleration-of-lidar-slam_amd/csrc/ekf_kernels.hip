@@ -1,11 +1,10 @@
 // ekf_kernels.hip — the motion sample and the landmark update of the particle filter: the 2x2 EKF
-// per (particle, landmark) with a row per wavefront (in its four forms: noise meas_var * I or a 2x2 Q, observations from the
-// frame's table or through a per-particle association table), grouped and on the split layout (the bodies: ekf_row_body.h,
-// ekf_aniso_lane.h, ekf_group_body.h, ekf_split_body.h; what they share and the data layout: ekf_wave.h), plus the copy ceiling
-// and the reciprocal self-test.  Fused with the scorer into the front of a frame: front_kernels.hip; sparse in place behind the compact
-// observation list: ekf_sparse_kernels.hip.  The only
-// reference anchor is the zero-noise motion step = the constant-velocity predict of
-// Subsystem_1/main.c:875-898.
+// per (particle, landmark) with a row per wavefront (in its five forms: noise meas_var * I or a 2x2 Q, observations from the
+// frame's table or through a per-particle association table — and, through the table, a Q per detection), grouped and on
+// the split layout (the bodies: ekf_row_body.h, ekf_aniso_lane.h, ekf_group_body.h, ekf_split_body.h; what they share and
+// the data layout: ekf_wave.h), plus the copy ceiling and the reciprocal self-test.  Fused with the scorer into the front of a
+// frame: front_kernels.hip; sparse in place behind the compact observation list: ekf_sparse_kernels.hip.  The only reference
+// anchor is the zero-noise motion step = the constant-velocity predict of Subsystem_1/main.c:875-898.
 
 #include "ekf_aniso_lane.h"
 #include "ekf_group_body.h"
@@ -173,6 +172,15 @@ hipError_t launch_ekf_rows(hipStream_t stream, const EkfArgs& a, const EkfAnisoC
     if (q) return launch_rows<EkfNoiseAniso, EkfObsFrame>(stream, a, *q, {}, ev);
     if (tab) return launch_rows<EkfNoiseIso, EkfObsTable>(stream, a, {}, *tab, ev);
     return launch_rows<EkfNoiseIso, EkfObsFrame>(stream, a, {}, {}, ev);
+}
+
+hipError_t launch_ekf_rows_detcov(hipStream_t stream, const EkfArgs& a, const DetCovArgs& q, const EkfAssocTable& tab, const EventPair* ev)
+{
+    if (a.n <= 0) return hipSuccess;
+    if (a.cov || tab.assoc_stride < a.nlandmarks || tab.ndet < 0 || tab.ndet > SLAM_MAX_DETECTIONS || q.ndet != tab.ndet ||
+        (q.ndet > 0 && (!q.qxx || !q.qxy || !q.qyy)))
+        return hipErrorInvalidValue;
+    return launch_rows<EkfNoiseDet, EkfObsTable>(stream, a, q, tab, ev);
 }
 
 hipError_t launch_ekf_update(hipStream_t stream, const EkfArgs& a_in, const EventPair* ev, int group_size)

@@ -59,13 +59,16 @@ __device__ __forceinline__ void ekf_select(v2f& r0, v2f& r1, v2f& r2, v2f& r3, v
 // (Args), an init() for one particle and the one operation ekf_batches asks of it.
 //
 // NOISE — the measurement noise and the arithmetic per landmark.  This one: meas_var * I (a first sighting stores P = q I);
-// EkfNoiseAniso of ekf_aniso_lane.h: the particle's R_w from a 2x2 sensor-frame Q.
+// EkfNoiseAniso of ekf_aniso_lane.h: the particle's R_w from a 2x2 sensor-frame Q; EkfNoiseDet there: from the Q_k of the detection
+// each landmark takes, which the lane fetches (fetch) beside z while the row's loads are issued and keeps in an Aux per batch.
 struct EkfNoiseIso {
     struct Args {};   // a.meas_var is all it needs
+    struct Aux {};    // what a lane keeps per batch beside z for its two landmarks: nothing (EkfNoiseDet: their detections' Q)
     v2f q;
     __device__ __forceinline__ void init(const EkfArgs& a, const Args&, float s, float c) { q = bc2(a.meas_var); }
+    template <class OBS> __device__ __forceinline__ void fetch(const OBS&, unsigned l, bool in, int t, Aux&) const {}
     // what goes into the row for the two landmarks of a lane (ob0 / ob1: they have an observation) and their likelihood terms
-    __device__ __forceinline__ void update(const EkfPose& p, v2f mx, v2f my, v2f pxx, v2f pxy, v2f pyy, v2f zx, v2f zy, bool ob0, bool ob1,
+    __device__ __forceinline__ void update(const EkfPose& p, v2f mx, v2f my, v2f pxx, v2f pxy, v2f pyy, v2f zx, v2f zy, const Aux&, bool ob0, bool ob1,
                                            v2f& r0, v2f& r1, v2f& r2, v2f& r3, v2f& r4, v2f& ll) const
     {
         const EkfResult<v2f> u = ekf_update_one<v2f, false>(mx, my, pxx, pxy, pyy, zx, zy, p.s, p.c, p.px, p.py, q);
@@ -104,11 +107,15 @@ struct EkfObsTable {
         detx = (int)lane < tab.ndet ? tab.det_zx[lane] : nan;
         dety = (int)lane < tab.ndet ? tab.det_zy[lane] : nan;
     }
+    // the table byte of landmark l (clamped index: the caller discards what lanes beyond L get) ...
+    __device__ __forceinline__ unsigned entry(unsigned l, bool in) const { return *(const guchar*)(arow + (in ? l : 0u)); }
+    // ... and the lane that holds what belongs to it (SLAM_ASSOC_NONE reads some lane; get() says NaN then)
+    static __device__ __forceinline__ int lane_of(unsigned k) { return (int)(k & 63u); }
     __device__ __forceinline__ void get(unsigned l, bool in, float& vx, float& vy) const
     {
         const float nan = __uint_as_float(0x7fc00000u);
-        const unsigned k = *(const guchar*)(arow + (in ? l : 0u));   // clamped index: the caller discards what lanes beyond L get
-        const float dx = __shfl(detx, (int)(k & 63u), 64), dy = __shfl(dety, (int)(k & 63u), 64);
+        const unsigned k = entry(l, in);
+        const float dx = __shfl(detx, lane_of(k), 64), dy = __shfl(dety, lane_of(k), 64);
         const bool has = k < 64u;   // SLAM_ASSOC_NONE, and any value that is no detection
         vx = has ? dx : nan;
         vy = has ? dy : nan;
@@ -116,6 +123,7 @@ struct EkfObsTable {
 };
 
 template <class NOISE, class OBS> struct EkfRowLane {   // per-wavefront constants of one particle
+    typedef NOISE Noise;
     // source row and destination row (p.rout) as buffer resources (wave-uniform descriptors in SGPRs): an access is
     // "descriptor + 32-bit lane offset + scalar plane offset", no 64-bit vector arithmetic for loads or stores
     __amdgpu_buffer_rsrc_t rin;
@@ -139,6 +147,7 @@ __device__ __forceinline__ void ekf_batches(const W& w, unsigned lb, unsigned la
 {
     const float nan = __uint_as_float(0x7fc00000u);
     v2f m[NB][5], zx[NB], zy[NB];
+    typename W::Noise::Aux aux[NB];
     unsigned off[NB][2];
     bool obs[NB][2], use[NB][2];
 #pragma unroll
@@ -150,6 +159,7 @@ __device__ __forceinline__ void ekf_batches(const W& w, unsigned lb, unsigned la
             off[g][t] = ((FULL || in) ? l : 0u) * 4u;
             float vx, vy;
             w.obs.get(l, in, vx, vy);
+            w.noise.fetch(w.obs, l, in, t, aux[g]);
             zx[g][t] = in ? vx : nan;
             zy[g][t] = in ? vy : nan;
             // NaN = no observation (also what lanes beyond L were given).  Testing zy as well keeps its load up here
@@ -179,7 +189,7 @@ __device__ __forceinline__ void ekf_batches(const W& w, unsigned lb, unsigned la
             continue;
         }
         v2f r0, r1, r2, r3, r4, ll;
-        w.noise.update(w.p, mx, my, pxx, pxy, pyy, zx[g], zy[g], obs[g][0], obs[g][1], r0, r1, r2, r3, r4, ll);
+        w.noise.update(w.p, mx, my, pxx, pxy, pyy, zx[g], zy[g], aux[g], obs[g][0], obs[g][1], r0, r1, r2, r3, r4, ll);
 #pragma unroll
         for (int t = 0; t < 2; ++t)
             if (FULL || use[g][t]) {

@@ -1,5 +1,6 @@
 // engine_assoc.hip — what a frame of detections without identity adds behind the C ABI: the detections themselves (uploaded, set,
-// or made from the scan by the detector), the association stage with meas_var * I or a 2x2 Q, and the landmarks' existence
+// or made from the scan by the detector; optionally a covariance per detection), the association stage with meas_var * I, a 2x2 Q
+// or the detections' own Q_k, and the landmarks' existence
 // evidence.  The landmark update under the table the association makes: engine_ekf.hip.
 
 #include <hip/hip_runtime.h>
@@ -51,6 +52,7 @@ int slam_detections_upload_host(slam_engine* e, const float* zx, const float* zy
     e->ndet = ndet;
     e->det_pending = false;   // (a detector launch still in flight wrote the buffer in front of this copy, in stream order)
     e->det_from_scan = false;
+    e->det_has_cov = false;
     return SLAM_OK;
 }
 
@@ -63,6 +65,68 @@ int slam_detections_set_dev(slam_engine* e, const float* d_zx, const float* d_zy
     e->ndet = ndet;
     e->det_pending = false;
     e->det_from_scan = false;
+    e->det_has_cov = false;
+    return SLAM_OK;
+}
+
+int slam_detections_cov_upload_host(slam_engine* e, const float* qxx, const float* qxy, const float* qyy, int ndet)
+{
+    SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (ndet != e->ndet || (ndet > 0 && (!qxx || !qxy || !qyy))) return SLAM_ERR_INVALID_ARG;
+    for (int k = 0; k < ndet; ++k) {
+        const float q3[3] = { qxx[k], qxy[k], qyy[k] };
+        EkfAnisoCov q;
+        if (!slam_aniso_cov_from(e, q3, &q)) return SLAM_ERR_INVALID_ARG;
+    }
+    if (!e->detcov_buf.p) SLAM_HIP_TRY(e, e->detcov_buf.ensure(sizeof(float) * 3 * SLAM_MAX_DETECTIONS));
+    if (ndet > 0) {
+        float* h = e->stage_acquire();
+        for (int k = 0; k < SLAM_MAX_DETECTIONS; ++k) {   // qxx[64] | qxy[64] | qyy[64], the identity from ndet on: one copy
+            h[k] = k < ndet ? qxx[k] : 1.0f;
+            h[SLAM_MAX_DETECTIONS + k] = k < ndet ? qxy[k] : 0.0f;
+            h[2 * SLAM_MAX_DETECTIONS + k] = k < ndet ? qyy[k] : 1.0f;
+        }
+        const hipError_t err = hipMemcpyAsync(e->detcov_buf.as<float>(), h, sizeof(float) * 3 * SLAM_MAX_DETECTIONS, hipMemcpyHostToDevice, e->stream);
+        SLAM_HIP_TRY(e, e->stage_release(h));
+        SLAM_HIP_TRY(e, err);
+    }
+    // (ndet == 0: nothing was copied and nothing reads the three arrays; they point into the buffer all the same)
+    e->d_det_qxx = e->detcov_buf.as<float>();
+    e->d_det_qxy = e->detcov_buf.as<float>() + SLAM_MAX_DETECTIONS;
+    e->d_det_qyy = e->detcov_buf.as<float>() + 2 * SLAM_MAX_DETECTIONS;
+    e->det_has_cov = true;
+    return SLAM_OK;
+}
+
+int slam_detections_cov_set_dev(slam_engine* e, const float* d_qxx, const float* d_qxy, const float* d_qyy, int ndet)
+{
+    SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (ndet != e->ndet || (ndet > 0 && (!d_qxx || !d_qxy || !d_qyy))) return SLAM_ERR_INVALID_ARG;
+    e->d_det_qxx = d_qxx;
+    e->d_det_qxy = d_qxy;
+    e->d_det_qyy = d_qyy;
+    e->det_has_cov = true;
+    return SLAM_OK;
+}
+
+int slam_detections_get_cov_host(slam_engine* e, float* qxx, float* qxy, float* qyy, int32_t* ndet)
+{
+    SLAM_ENTER(e);
+    if (!qxx || !qxy || !qyy || !ndet) return SLAM_ERR_INVALID_ARG;
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (e->ndet < 0 || !e->det_has_cov) return SLAM_ERR_NOT_READY;
+    const size_t count = (size_t)e->ndet;
+    if (count > 0) {
+        SLAM_HIP_TRY(e, hipMemcpyAsync(qxx, e->d_det_qxx, sizeof(float) * count, hipMemcpyDeviceToHost, e->stream));
+        SLAM_HIP_TRY(e, hipMemcpyAsync(qxy, e->d_det_qxy, sizeof(float) * count, hipMemcpyDeviceToHost, e->stream));
+        SLAM_HIP_TRY(e, hipMemcpyAsync(qyy, e->d_det_qyy, sizeof(float) * count, hipMemcpyDeviceToHost, e->stream));
+    }
+    SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
+    *ndet = e->ndet;
     return SLAM_OK;
 }
 
@@ -110,12 +174,20 @@ int slam_engine_associate(slam_engine* e, const float* d_map, int64_t row_stride
     SLAM_ENTER(e);
     if (int rc = slam_engine_resolve_detections(e)) return rc;
     if (!associate_args_ok(d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, n, gate, new_gate, create, d_assoc, assoc_stride) ||
-        (noise.full ? !noise.meas_cov : !(noise.meas_var > 0.0f)))
+        (noise.per_det ? false : noise.full ? !noise.meas_cov : !(noise.meas_var > 0.0f)))
         return SLAM_ERR_INVALID_ARG;
     EkfAnisoCov q;
-    if (noise.full && !slam_aniso_cov_from(e, noise.meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
-    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (!noise.per_det && noise.full && !slam_aniso_cov_from(e, noise.meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
+    if (e->ndet < 0 || (noise.per_det && !e->det_has_cov)) return SLAM_ERR_NOT_READY;
     if (n == 0) return SLAM_OK;
+    if (noise.per_det) {
+        const AssocArgs a = assoc_args(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, 0.0f, gate, new_gate, d_assoc,
+                                       assoc_stride, d_stats);
+        const DetCovArgs dq{ e->d_det_qxx, e->d_det_qxy, e->d_det_qyy, e->ndet };
+        SLAM_HIP_TRY(e, launch_associate_detcov(e->stream, a, dq, create != 0, e->prof_next(SLAM_PROF_PAGES)));
+        e->assoc_detcov_launches[0]++;
+        return SLAM_OK;
+    }
     // (meas_var of the arguments is not read under a 2x2 covariance)
     const AssocArgs a = assoc_args(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, noise.full ? 0.0f : noise.meas_var,
                                    gate, new_gate, d_assoc, assoc_stride, d_stats);
@@ -138,6 +210,23 @@ int slam_associate_aniso_dev(slam_engine* e, const float* d_map, int64_t row_str
 {
     return slam_engine_associate(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, slam_meas_noise{ 0.0f, meas_cov, true },
                                  gate, new_gate, create, d_assoc, assoc_stride, d_stats);
+}
+
+int slam_associate_detcov_dev(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                              const float* d_y, const float* d_th, const int32_t* d_anc, int n, float gate, float new_gate, int create,
+                              uint8_t* d_assoc, int assoc_stride, int32_t* d_stats)
+{
+    return slam_engine_associate(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, slam_meas_noise{ 0.0f, nullptr, false, true },
+                                 gate, new_gate, create, d_assoc, assoc_stride, d_stats);
+}
+
+int slam_assoc_detcov_counts(slam_engine* e, int64_t counts[2])
+{
+    SLAM_ENTER(e);
+    if (!counts) return SLAM_ERR_INVALID_ARG;
+    counts[0] = e->assoc_detcov_launches[0];
+    counts[1] = e->assoc_detcov_launches[1];
+    return SLAM_OK;
 }
 
 int slam_assoc_aniso_counts(slam_engine* e, int64_t counts[2])
@@ -179,8 +268,10 @@ void slam_detect_fit_default(slam_detect_fit* f)
     f->spread_tol = 0.0f;
 }
 
-// the one checked path of both entry points (fit == nullptr: the centroid, the kernel instantiation without the fit)
-static int detect_scan(slam_engine* e, const slam_detect_params* params, const slam_detect_fit* fit, int32_t* d_stats)
+// the one checked path of the three entry points (fit == nullptr: the centroid, the kernel instantiation without the fit;
+// noise == nullptr: the instantiations without the noise model — the detections then carry no covariance)
+static int detect_scan(slam_engine* e, const slam_detect_params* params, const slam_detect_fit* fit, const slam_detect_noise* noise,
+                       int32_t* d_stats)
 {
     SLAM_ENTER(e);
     if (!params) return SLAM_ERR_INVALID_ARG;
@@ -192,8 +283,13 @@ static int detect_scan(slam_engine* e, const slam_detect_params* params, const s
         slam_detect_fit_error(e);
         return SLAM_ERR_INVALID_ARG;
     }
+    if (noise && !slam_detect_noise_ok(noise)) {
+        slam_detect_noise_error(e);
+        return SLAM_ERR_INVALID_ARG;
+    }
     if (e->nbeams < 0) return SLAM_ERR_NOT_READY;
     if (!e->det_buf.p) SLAM_HIP_TRY(e, e->det_buf.ensure(sizeof(float) * 2 * SLAM_MAX_DETECTIONS));
+    if (noise && !e->detcov_buf.p) SLAM_HIP_TRY(e, e->detcov_buf.ensure(sizeof(float) * 3 * SLAM_MAX_DETECTIONS));
     DetectArgs a;
     a.bx = e->d_bx;
     a.by = e->d_by;
@@ -212,13 +308,22 @@ static int detect_scan(slam_engine* e, const slam_detect_params* params, const s
     a.fit = fit ? 1 : 0;
     a.rho2 = fit ? fit->radius * fit->radius : 0.0f;
     a.lim = fit ? a.rho2 + fit->spread_tol * fit->spread_tol : 0.0f;
-    SLAM_HIP_TRY(e, launch_detect_scan(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
+    const DetectNoiseArgs nz{ noise ? noise->range_var : 0.0f, noise ? noise->bearing_var : 0.0f, noise ? noise->lateral_var : 0.0f,
+                              noise ? e->detcov_buf.as<float>() : nullptr };
+    SLAM_HIP_TRY(e, launch_detect_scan(e->stream, a, e->prof_next(SLAM_PROF_PAGES), noise ? &nz : nullptr));
     e->det_seq = a.seq;
     e->d_det_zx = e->det_buf.as<float>();
     e->d_det_zy = e->det_buf.as<float>() + SLAM_MAX_DETECTIONS;
     e->ndet = 0;   // until the count is picked up
     e->det_pending = true;
     e->det_from_scan = true;
+    e->det_has_cov = noise != nullptr;   // the model's Q_k beside the detections, in the engine's own buffer
+    if (noise) {
+        e->d_det_qxx = e->detcov_buf.as<float>();
+        e->d_det_qxy = e->detcov_buf.as<float>() + SLAM_MAX_DETECTIONS;
+        e->d_det_qyy = e->detcov_buf.as<float>() + 2 * SLAM_MAX_DETECTIONS;
+        e->detect_noise_launches++;
+    }
     e->detect_launches++;
     if (fit) e->detect_fit_launches++;
     return SLAM_OK;
@@ -226,12 +331,26 @@ static int detect_scan(slam_engine* e, const slam_detect_params* params, const s
 
 int slam_detect_scan_dev(slam_engine* e, const slam_detect_params* params, int32_t* d_stats)
 {
-    return detect_scan(e, params, nullptr, d_stats);
+    return detect_scan(e, params, nullptr, nullptr, d_stats);
 }
 
 int slam_detect_scan_fit_dev(slam_engine* e, const slam_detect_params* params, const slam_detect_fit* fit, int32_t* d_stats)
 {
-    return detect_scan(e, params, fit, d_stats);
+    return detect_scan(e, params, fit, nullptr, d_stats);
+}
+
+int slam_detect_scan_noise_dev(slam_engine* e, const slam_detect_params* params, const slam_detect_fit* fit, const slam_detect_noise* noise,
+                               int32_t* d_stats)
+{
+    return detect_scan(e, params, fit, noise, d_stats);
+}
+
+int slam_detect_noise_count(slam_engine* e, int64_t* launches)
+{
+    SLAM_ENTER(e);
+    if (!launches) return SLAM_ERR_INVALID_ARG;
+    *launches = e->detect_noise_launches;
+    return SLAM_OK;
 }
 
 int slam_detect_count(slam_engine* e, int64_t* launches)

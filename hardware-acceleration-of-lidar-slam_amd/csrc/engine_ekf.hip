@@ -248,19 +248,25 @@ int slam_engine_ekf_update(slam_engine* e, const float* d_map_in, float* d_map_o
     if (table)
         if (int rc = slam_engine_resolve_detections(e)) return rc;
     if (n < 0 || nlandmarks < 0 || (table && (nlandmarks > SLAM_MAX_OBS || table->assoc_stride < nlandmarks)) || plane_stride < nlandmarks ||
-        row_stride < 5 * (int64_t)plane_stride || (noise.full ? !noise.meas_cov : !(noise.meas_var > 0.0f)) ||
+        row_stride < 5 * (int64_t)plane_stride || (noise.per_det ? !table : noise.full ? !noise.meas_cov : !(noise.meas_var > 0.0f)) ||
         (n > 0 && (!d_map_in || !d_map_out || !d_x || !d_y || !d_th || (table && !table->d_assoc))))
         return SLAM_ERR_INVALID_ARG;
     EkfAnisoCov q;
-    if (noise.full && !slam_aniso_cov_from(e, noise.meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
+    if (!noise.per_det && noise.full && !slam_aniso_cov_from(e, noise.meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
     if (d_anc && d_map_in == d_map_out) return SLAM_ERR_INVALID_ARG;
     if (table ? e->ndet < 0 : (e->obs_nlandmarks < 0 || e->obs_nlandmarks != nlandmarks)) return SLAM_ERR_NOT_READY;
+    if (noise.per_det && !e->det_has_cov) return SLAM_ERR_NOT_READY;
     if (n == 0) return SLAM_OK;
     SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
     // (under a 2x2 covariance meas_var of the arguments is not read, under a table their observation table is not)
     const EkfArgs a = ekf_args(e, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n,
-                               noise.full ? 0.0f : noise.meas_var, d_loglik);
-    if (!noise.full && !table) {
+                               noise.full || noise.per_det ? 0.0f : noise.meas_var, d_loglik);
+    if (noise.per_det) {
+        const EkfAssocTable tab{ table->d_assoc, table->assoc_stride, e->d_det_zx, e->d_det_zy, e->ndet };
+        const DetCovArgs dq{ e->d_det_qxx, e->d_det_qxy, e->d_det_qyy, e->ndet };
+        SLAM_HIP_TRY(e, launch_ekf_rows_detcov(e->stream, a, dq, tab, e->prof_next(SLAM_PROF_EKF)));
+        e->assoc_detcov_launches[1]++;
+    } else if (!noise.full && !table) {
         if (int rc = launch_iso_frame_update(e, a)) return rc;
     } else {
         const EkfAssocTable tab{ table ? table->d_assoc : nullptr, table ? table->assoc_stride : 0, e->d_det_zx, e->d_det_zy, e->ndet };
@@ -304,6 +310,15 @@ int slam_ekf_update_assoc_aniso_dev(slam_engine* e, const float* d_map_in, float
     const slam_assoc_view table{ d_assoc, assoc_stride };
     return slam_engine_ekf_update(e, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n,
                                   slam_meas_noise{ 0.0f, meas_cov, true }, &table, d_loglik);
+}
+
+int slam_ekf_update_assoc_detcov_dev(slam_engine* e, const float* d_map_in, float* d_map_out, int64_t row_stride, int plane_stride,
+                                     int nlandmarks, const float* d_x, const float* d_y, const float* d_th, const int32_t* d_anc, int n,
+                                     const uint8_t* d_assoc, int assoc_stride, float* d_loglik)
+{
+    const slam_assoc_view table{ d_assoc, assoc_stride };
+    return slam_engine_ekf_update(e, d_map_in, d_map_out, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n,
+                                  slam_meas_noise{ 0.0f, nullptr, false, true }, &table, d_loglik);
 }
 
 int slam_ekf_aniso_count(slam_engine* e, int64_t* launches)

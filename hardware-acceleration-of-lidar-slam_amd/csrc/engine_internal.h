@@ -90,6 +90,12 @@ struct slam_engine {
     const float *d_det_zx = nullptr, *d_det_zy = nullptr;
     int64_t assoc_launches[2] = { 0, 0 };   // slam_assoc_counts: associate launches, assoc-update launches (in no form counter)
     int64_t assoc_aniso_launches[2] = { 0, 0 };   // slam_assoc_aniso_counts: the same two under a 2x2 Q (in no other counter)
+    // ... and, optionally, a covariance per detection beside them (slam_detections_cov_upload_host / _set_dev): what
+    // slam_associate_detcov_dev and slam_ekf_update_assoc_detcov_dev read.  Whatever installs new detections drops it.
+    DevBuf detcov_buf;   // qxx[SLAM_MAX_DETECTIONS] qxy[..] qyy[..] when uploaded from the host
+    const float *d_det_qxx = nullptr, *d_det_qxy = nullptr, *d_det_qyy = nullptr;
+    bool det_has_cov = false;
+    int64_t assoc_detcov_launches[2] = { 0, 0 };   // slam_assoc_detcov_counts: the same two under per-detection Q (in no other counter)
     int64_t evidence_launches[2] = { 0, 0 };   // slam_evidence_counts: evidence launches, init launches (in no other counter)
     // the detector (slam_detect_scan_dev): its kernel writes det_buf and leaves {ndet, sequence} in mapped host memory; until the
     // next stage that needs the count on the host has picked it up (slam_engine_resolve_detections) it is PENDING
@@ -100,6 +106,7 @@ struct slam_engine {
     bool det_from_scan = false;   // the current detections are the detector's: det_buf holds 0 from ndet on
     int64_t detect_launches = 0;   // slam_detect_count (in no other counter)
     int64_t detect_fit_launches = 0;   // slam_detect_fit_count: those of them that ran the fit
+    int64_t detect_noise_launches = 0;   // slam_detect_noise_count: those of them that ran the noise model
 
     DevBuf fm_buf;             // kFmIn + kFmOut floats
     DevBuf fm_work;            // 2 x 27 x SLAM_MAX_BEAMS floats: per-candidate hit rows of the lattice kernel, two sweeps (the chained pair)
@@ -307,12 +314,27 @@ inline void slam_detect_fit_error(slam_engine* e)
     snprintf(e->err, sizeof e->err, "the detector's fit needs a finite radius > 0 and a finite spread_tol >= 0");
 }
 
+// ... and of slam_detect_scan_noise_dev on a noise model
+inline bool slam_detect_noise_ok(const slam_detect_noise* z)
+{
+    const float big = 3.402823466e+38f;
+    return z->range_var > 0.0f && z->range_var <= big && z->bearing_var >= 0.0f && z->bearing_var <= big && z->lateral_var >= 0.0f &&
+           z->lateral_var <= big && z->bearing_var + z->lateral_var > 0.0f;
+}
+inline void slam_detect_noise_error(slam_engine* e)
+{
+    snprintf(e->err, sizeof e->err, "the detector's noise model needs a finite range_var > 0, finite bearing_var >= 0 and lateral_var >= 0, "
+                                    "and bearing_var + lateral_var > 0");
+}
+
 // The two choices a landmark update on rows has (kernels.h: launch_ekf_rows), as the engine's stages take them.
 // The measurement noise: meas_var * I, or — full — the 2x2 sensor-frame covariance meas_cov[3] = {qxx, qxy, qyy}
+// — or per_det — the covariances the engine's detections carry (meas_var and meas_cov are not read)
 struct slam_meas_noise {
     float meas_var;
     const float* meas_cov;
     bool full;
+    bool per_det = false;
 };
 // ... and a per-particle association table as the source of the observations (no table: the engine's observation table)
 struct slam_assoc_view {

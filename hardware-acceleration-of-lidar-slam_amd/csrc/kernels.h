@@ -196,7 +196,7 @@ inline EkfAnisoCov ekf_aniso_cov(const float meas_cov[3])
     return q;
 }
 // every value finite, qxx > 0, qyy > 0 and the float32 determinant > 0 (NaN fails every comparison)
-inline bool ekf_aniso_cov_ok(const EkfAnisoCov& q)
+__host__ __device__ inline bool ekf_aniso_cov_ok(const EkfAnisoCov& q)
 {
     const float big = 3.402823466e+38f;
     return q.qxx > 0.0f && q.qyy > 0.0f && q.detq > 0.0f && q.qxx <= big && q.qyy <= big && q.qxy >= -big && q.qxy <= big;
@@ -214,6 +214,15 @@ struct EkfAssocTable {
 // landmarks with one touched); a.cov must be null. q == nullptr: noise a.meas_var * I, else R_w(theta_i) of *q (a.meas_var is not read; ekf_aniso_cov_ok(*q)).
 // tab == nullptr: observations a.obs_zx / a.obs_zy, else through *tab (a.obs_zx / a.obs_zy are not read).
 hipError_t launch_ekf_rows(hipStream_t stream, const EkfArgs& a, const EkfAnisoCov* q, const EkfAssocTable* tab, const EventPair* ev = nullptr);
+// A measurement covariance PER DETECTION (specification: tests/_assoc_detcov_spec.py): Q_k = {qxx[k], qxy[k], qyy[k]} in the
+// sensor frame beside detection k of an EkfAssocTable / of AssocArgs, every one by the rule of ekf_aniso_cov_ok (whoever hands
+// them over has checked that, or made them so); det Q_k is formed from them where it is needed, never handed in
+struct DetCovArgs {
+    const float *qxx, *qxy, *qyy;   // [ndet]
+    int ndet;
+};
+// ... the row update through *tab with R_w(theta_i, k) of the detection each landmark of particle i takes (a.meas_var is not read)
+hipError_t launch_ekf_rows_detcov(hipStream_t stream, const EkfArgs& a, const DetCovArgs& q, const EkfAssocTable& tab, const EventPair* ev = nullptr);
 // ---- assoc_kernels.hip: data association (specification: tests/_assoc_spec.py).  The detections of a frame
 // are sensor-frame points WITHOUT identity; every particle decides for itself which of its landmarks each one belongs to and
 // which ones start a new landmark.  Rows only: the table is per particle, so "which landmarks a frame observes" is too.
@@ -237,6 +246,8 @@ struct AssocArgs {
 // a full 2x2 sensor-frame measurement covariance (specification: tests/_assoc_aniso_spec.py) — every particle gates, matches and
 // creates with S = P + R_w(theta_i), a.meas_var is not read, ekf_aniso_cov_ok(*q) is checked; nullptr: a.meas_var * I
 hipError_t launch_associate(hipStream_t stream, const AssocArgs& a, const EkfAnisoCov* q, bool create, const EventPair* ev = nullptr);
+// ... under S = P + R_w(theta_i, k), Q_k per detection (q.ndet == a.ndet; a.meas_var is not read)
+hipError_t launch_associate_detcov(hipStream_t stream, const AssocArgs& a, const DetCovArgs& q, bool create, const EventPair* ev = nullptr);
 // ---- evidence_kernels.hip: landmark existence evidence (specification: tests/_evidence_spec.py).  One byte
 // c in [0, cmax] per (particle, landmark slot) beside the rows; behind the update of a frame a matched landmark gains `hit`, a
 // visible unmatched one loses `miss`, and one that cannot pay is pruned: its slot gets the bits of a slot that was never used.
@@ -292,8 +303,15 @@ struct DetectArgs {
     int fit;                // 0: the centroid; 1: the centre of a circle of squared radius rho2 through the segment
     float rho2, lim;        // radius * radius; rho2 + spread_tol * spread_tol: one float32 operation each, made on the host
 };
-// one workgroup of 64 .. 1024 threads by the size of the scan
-hipError_t launch_detect_scan(hipStream_t stream, const DetectArgs& a, const EventPair* ev = nullptr);
+// The detector's noise model (specification: tests/_detect_noise_spec.py): a detection (zx, zy) that passed its range test gets
+// Q = a u u^T + b v v^T, u its line of sight, a = range_var, b = bearing_var * r2 + lateral_var; one whose r2 is 0 or whose Q
+// fails ekf_aniso_cov_ok is no detection (counted in stats[4] of then six words, stats[5] = 0), in front of the cap at 64
+struct DetectNoiseArgs {
+    float range_var, bearing_var, lateral_var;
+    float* cov;             // qxx[SLAM_MAX_DETECTIONS] | qxy[..] | qyy[..]: the first ndet, then 0
+};
+// one workgroup of 64 .. 1024 threads by the size of the scan; noise == nullptr: the kernels without the model, as they were
+hipError_t launch_detect_scan(hipStream_t stream, const DetectArgs& a, const EventPair* ev = nullptr, const DetectNoiseArgs* noise = nullptr);
 bool frame_front_fits(int n, int nlandmarks, int group_size);   // the shapes launch_frame_front takes
 // motion sample + scan-match score AND the grouped out-of-place landmark update in ONE launch (single-GPU frames on rows): the
 // gathers of the scorer run in the shadow of the update's row stores.  `a.x / a.y / a.th` are not read (the update works out

@@ -141,6 +141,13 @@ struct slam_pf {
     // while assoc_aniso is set; `aniso` above stays false)
     bool assoc_aniso = false;
     float assoc_cov[3] = { 0.0f, 0.0f, 0.0f };
+    // slam_pf_assoc_detcov_set: association under the covariance each detection carries — the same two launches under it
+    // (update_noise); cleared by slam_pf_assoc_set and slam_pf_assoc_cov_set
+    bool assoc_detcov = false;
+    // slam_pf_detect_noise_set: the detector's launch runs the noise model (slam_detect_scan_noise_dev), so its detections carry
+    // covariances; cleared by slam_pf_detect_set, slam_pf_detect_fit_set and slam_pf_assoc_set(0)
+    bool detect_noise_on = false;
+    slam_detect_noise detect_noise = { 0.0f, 0.0f, 0.0f };
     uint8_t* assoc_tab = nullptr;     // [n][Lp] the last frame's table, indexed like `score`; made by the first slam_pf_assoc_set
     int32_t* assoc_stats = nullptr;   // [n][3], behind the table in the same allocation
     // slam_pf_prune_set (only while association is on): one evidence byte per (particle, landmark slot) beside the rows, brought up

@@ -347,9 +347,11 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
     if (gate == 0.0f) {   // off: the session runs exactly what it ran before the first call (pruning and the detector go off with it)
         pf->assoc_on = false;
         pf->assoc_aniso = false;
+        pf->assoc_detcov = false;
         pf->prune_on = false;
         pf->detect_on = false;
         pf->detect_fit_on = false;
+        pf->detect_noise_on = false;
         return SLAM_OK;
     }
     if (pf->layout_cfg != SLAM_MAP_ROWS || pf->L == 0 || pf->comm) {
@@ -377,6 +379,7 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
     }
     pf->assoc_on = true;
     pf->assoc_aniso = false;   // (slam_pf_assoc_cov_set behind this call says otherwise)
+    pf->assoc_detcov = false;  // (slam_pf_assoc_detcov_set likewise)
     pf->assoc_gate = gate;
     pf->assoc_new_gate = new_gate;
     pf->assoc_create = create;
@@ -397,6 +400,19 @@ int slam_pf_assoc_cov_set(slam_pf* pf, const float meas_cov[3], float gate, floa
     // {meas_var, 0, meas_var}: exactly slam_pf_assoc_set — the isotropic kernels, the same bits
     for (int k = 0; k < 3; ++k) pf->assoc_cov[k] = meas_cov[k];
     pf->assoc_aniso = !pf->is_meas_var(meas_cov);
+    return SLAM_OK;
+}
+
+int slam_pf_assoc_detcov_set(slam_pf* pf, float gate, float new_gate, int create)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    if (gate == 0.0f) {   // slam_pf_assoc_set(0, ..) is the switch-off: here a gate has to be given
+        snprintf(pf->e->err, sizeof pf->e->err, "association needs a finite gate > 0 (slam_pf_assoc_set(0, ..) switches it off)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    // the conditions, the refusals and the table of the isotropic switch; a refused call leaves the session as it was
+    if (int rc = slam_pf_assoc_set(pf, gate, new_gate, create)) return rc;
+    pf->assoc_detcov = true;
     return SLAM_OK;
 }
 
@@ -438,11 +454,18 @@ int slam_pf_detect_set(slam_pf* pf, const slam_detect_params* params) { return s
 // fit == nullptr: the centroid detector (slam_pf_detect_set); a refused call leaves the session as it was
 int slam_pf_detect_fit_set(slam_pf* pf, const slam_detect_params* params, const slam_detect_fit* fit)
 {
+    return slam_pf_detect_noise_set(pf, params, fit, nullptr);
+}
+
+// noise == nullptr: the detector without the model (slam_pf_detect_fit_set); a refused call leaves the session as it was
+int slam_pf_detect_noise_set(slam_pf* pf, const slam_detect_params* params, const slam_detect_fit* fit, const slam_detect_noise* noise)
+{
     if (!pf) return SLAM_ERR_INVALID_ARG;
     slam_engine* e = pf->e;
     if (!params) {   // off: the session runs exactly what it ran before the first call
         pf->detect_on = false;
         pf->detect_fit_on = false;
+        pf->detect_noise_on = false;
         return SLAM_OK;
     }
     if (!pf->assoc_on) {   // (which is what every layout but rows, a sharded session and a 2x2 covariance come down to)
@@ -458,10 +481,16 @@ int slam_pf_detect_fit_set(slam_pf* pf, const slam_detect_params* params, const 
         slam_detect_fit_error(e);
         return SLAM_ERR_INVALID_ARG;
     }
+    if (noise && !slam_detect_noise_ok(noise)) {
+        slam_detect_noise_error(e);
+        return SLAM_ERR_INVALID_ARG;
+    }
     pf->detect_on = true;
     pf->detect_params = *params;
     pf->detect_fit_on = fit != nullptr;
     if (fit) pf->detect_fit = *fit;
+    pf->detect_noise_on = noise != nullptr;
+    if (noise) pf->detect_noise = *noise;
     return SLAM_OK;
 }
 

@@ -294,6 +294,7 @@ int gate_and_exchange(slam_pf* pf, FrameFacts& f, bool* collective_verdict)
 // association's own while association is on (slam_pf_assoc_cov_set), else slam_pf_meas_cov_set's — or meas_var * I
 slam_meas_noise update_noise(const slam_pf* pf)
 {
+    if (pf->assoc_on && pf->assoc_detcov) return slam_meas_noise{ 0.0f, nullptr, false, true };   // the detections' own Q_k
     if (pf->assoc_on ? pf->assoc_aniso : pf->aniso) return slam_meas_noise{ 0.0f, pf->assoc_on ? pf->assoc_cov : pf->meas_cov, true };
     return slam_meas_noise{ pf->cfg.meas_var, nullptr, false };
 }
@@ -555,9 +556,19 @@ int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations,
     }
     if (int rc = auto_layout(pf)) return rc;   // may move the maps to another layout (never changes a result)
     FrameFacts f = frame_facts(pf, use_observations);
+    // per-detection noise: an observing frame whose detections will carry no covariance (none uploaded and no detector; or the
+    // session's detector has no noise model) is refused here, before its first launch — the session is as if the frame was never
+    // asked for
+    if (pf->assoc_on && pf->assoc_detcov && f.ekf && (pf->detect_on ? !pf->detect_noise_on : !e->det_has_cov)) {
+        snprintf(e->err, sizeof e->err, "association under per-detection covariances (slam_pf_assoc_detcov_set): the frame's detections "
+                                        "carry none (slam_detections_cov_upload_host / _set_dev, or slam_pf_detect_noise_set)");
+        return SLAM_ERR_NOT_READY;
+    }
     // the detector: in front of the frame's first launch, so that its count has arrived when update_rows' association asks for it
     if (pf->detect_on && pf->assoc_on && f.ekf)
-        if (int rc = slam_detect_scan_fit_dev(e, &pf->detect_params, pf->detect_fit_on ? &pf->detect_fit : nullptr, nullptr)) return rc;
+        if (int rc = slam_detect_scan_noise_dev(e, &pf->detect_params, pf->detect_fit_on ? &pf->detect_fit : nullptr,
+                                                pf->detect_noise_on ? &pf->detect_noise : nullptr, nullptr))
+            return rc;
     if (int rc = front_stage(pf, f, slot, dp)) return rc;
     if (int rc = gate_and_exchange(pf, f, collective_verdict)) return rc;
     if (int rc = pf->paged ? update_paged(pf, f) : pf->split ? update_split(pf, f) : update_rows(pf, f)) return rc;

@@ -21,7 +21,8 @@
  * usage: slam_pf_main dataset.csv frames beams map_out.csv particles [seed [mean|best]]
  *                     [--gpus N] [--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]]
  *                     [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE]
- *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]]]] [--landmarks-out FILE]]
+ *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
+ *                     [--landmarks-out FILE]]
  *   particles      the whole population (a multiple of N)
  *   --ess F        ESS-gated resampling: resample only in frames whose effective sample size is below F * N
  *   --refine SWEEPS  scan-match refinement of every particle (slam_pf_refine_set): SWEEPS (1..16) sweeps of the reference's
@@ -36,6 +37,8 @@
  *   --prune HIT MISS CMAX RANGE  existence evidence and pruning of clutter landmarks (slam_pf_prune_set)
  *   --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]  the detector (slam_pf_detect_set; no values: slam_detect_params_default):
  *                  every frame makes its detections from its own scan, so the landmark map grows from nothing but lidar frames
+ *   --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]  only with --assoc and --detect: the detector's noise model
+ *                  (slam_pf_detect_noise_set) and association under the covariance each detection carries (slam_pf_assoc_detcov_set)
  *   --pole-radius R [TOL]  only with --detect: a detection is the centre of the circle of radius R fitted to its segment, not the
  *                  segment's centroid, and segments more spread out than such a circle (by more than TOL, default 0) are no
  *                  detections (slam_pf_detect_fit_set)
@@ -78,6 +81,8 @@ typedef struct {
     slam_detect_params detect;
     int use_fit;           /* --pole-radius R [TOL] */
     slam_detect_fit fit;
+    int use_noise;         /* --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --detect */
+    slam_detect_noise noise;
     const char *landmarks_out;   /* --landmarks-out FILE */
     /* the ranks */
     int world, use_rccl, same_device;
@@ -154,9 +159,11 @@ static void *rank_main(void *arg)
         else if (rank == 0) fprintf(stderr, "--meas-cov has no effect here: %s\n", slam_last_error(eng));
     }
     /* the landmark pipeline: association reads detections, the detector makes them from each frame's scan */
-    if (run->use_assoc && !assoc_cov) CHECK(slam_pf_assoc_set(pf, run->assoc_gate[0], run->assoc_gate[1], 1));
+    if (run->use_assoc && !assoc_cov && !run->use_noise) CHECK(slam_pf_assoc_set(pf, run->assoc_gate[0], run->assoc_gate[1], 1));
+    /* --range-noise: every detection carries its own covariance, association and update run under it */
+    if (run->use_assoc && !assoc_cov && run->use_noise) CHECK(slam_pf_assoc_detcov_set(pf, run->assoc_gate[0], run->assoc_gate[1], 1));
     if (run->use_prune) CHECK(slam_pf_prune_set(pf, run->prune[0], run->prune[1], run->prune[2], run->prune_range));
-    if (run->use_detect) CHECK(slam_pf_detect_fit_set(pf, &run->detect, run->use_fit ? &run->fit : NULL));
+    if (run->use_detect) CHECK(slam_pf_detect_noise_set(pf, &run->detect, run->use_fit ? &run->fit : NULL, run->use_noise ? &run->noise : NULL));
     const int observe = run->landmarks > 0 && run->use_assoc && run->use_detect;   /* else: no frame has observations */
     if (fe_scan_init(&scan, beams, -2.351831f, 0.004363f) || fe_points_init(&map, FE_MAP_CAPACITY + beams) ||
         fe_points_init(&local, FE_LOCAL_CAPACITY) || fe_grid_init(&coarse, FE_COARSE_LD) || fe_grid_init(&fine, FE_FINE_LD) ||
@@ -347,22 +354,32 @@ int main(int argc, char **argv)
             run.fit.radius = (float)atof(argv[++a]);
             if (a + 1 < argc && strchr("0123456789.+", argv[a + 1][0])) run.fit.spread_tol = (float)atof(argv[++a]);
         }
+        else if (!strcmp(argv[a], "--range-noise") && a + 2 < argc) {
+            run.use_noise = 1;
+            run.noise.range_var = (float)atof(argv[++a]);
+            run.noise.bearing_var = (float)atof(argv[++a]);
+            run.noise.lateral_var = 0.0f;
+            if (a + 1 < argc && strchr("0123456789.+", argv[a + 1][0])) run.noise.lateral_var = (float)atof(argv[++a]);
+        }
         else if (!strcmp(argv[a], "--landmarks-out") && a + 1 < argc) run.landmarks_out = argv[++a];
         else if (npos < 8) pos[npos++] = argv[a];
     }
     const int landmark_options = run.use_assoc || run.use_prune || run.use_detect || run.landmarks_out != NULL;
     if (npos < 5 || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
-        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect)) {
+        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) ||
+        (run.use_noise && (!run.use_detect || !run.use_assoc || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
-                        "  [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]]]] "
+                        "  [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
                         "[--landmarks-out FILE]]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
                         "              without --landmarks; with --landmarks and --assoc the association gates and updates under it\n"
                         "  --landmarks: L landmark slots per particle on rows, one GPU; --assoc, --prune, --detect and --landmarks-out need it.\n"
                         "              With --assoc and --detect every frame makes its detections from its own scan\n"
                         "  --pole-radius R [TOL]: only with --detect; a detection is the centre of the circle of radius R fitted to its segment,\n"
-                        "              and segments more spread out than that circle (by more than TOL, default 0) are dropped\n", argv[0]);
+                        "              and segments more spread out than that circle (by more than TOL, default 0) are dropped\n"
+                        "  --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --assoc and --detect, not with --meas-cov; every detection\n"
+                        "              carries its own covariance (RANGE_VAR along its beam, BEARING_VAR r^2 + LATERAL_VAR across) and is gated under it\n", argv[0]);
         return 2;
     }
     if (run.use_meas_cov) {   /* the conditions of slam_pf_meas_cov_set: finite, qxx > 0, qyy > 0, float determinant > 0 */

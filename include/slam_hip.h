@@ -371,6 +371,38 @@ int slam_ekf_update_assoc_aniso_dev(slam_engine *e, const float *d_map_in, float
                                     int nlandmarks, const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc,
                                     int n, const float meas_cov[3], const uint8_t *d_assoc, int assoc_stride, float *d_loglik);
 int slam_assoc_aniso_counts(slam_engine *e, int64_t counts[2]);
+/* DATA ASSOCIATION UNDER A MEASUREMENT COVARIANCE PER DETECTION.  A lidar's noise is small along the beam and larger across it,
+ * and the cross-beam part grows with range: in the sensor's x/y frame that is a different 2x2 matrix for every detection.  Each
+ * of the engine's current detections may therefore carry Q_k = {qxx[k], qxy[k], qyy[k]} in the sensor frame.
+ * slam_detections_cov_upload_host / slam_detections_cov_set_dev attach covariances to the detections handed over last (a
+ * detector's pending count is picked up first): ndet must equal the engine's ndet (else SLAM_ERR_INVALID_ARG; no detections at
+ * all: SLAM_ERR_NOT_READY).  The host form checks every Q_k by the rule of slam_ekf_update_aniso_dev's meas_cov (finite, qxx > 0,
+ * qyy > 0, qxx * qyy - qxy * qxy > 0 in float32; a bad one: SLAM_ERR_INVALID_ARG, nothing changes); the device form adopts the
+ * three arrays as slam_detections_set_dev adopts its two, and whoever filled them answers for that rule.  det Q_k is never an
+ * input: whoever uses Q_k computes t0 = qxx * qyy, t1 = qxy * qxy, detq = t0 - t1 in float32.  Whatever installs new detections
+ * (slam_detections_upload_host / _set_dev, slam_detect_scan_dev / _fit_dev) installs them WITHOUT covariances: those calls do
+ * exactly what they did and the covariance state is dropped.  slam_detections_get_cov_host reads the covariances back (ndet
+ * values each; synchronises; SLAM_ERR_NOT_READY without any).
+ * slam_associate_detcov_dev / slam_ekf_update_assoc_detcov_dev are slam_associate_aniso_dev / slam_ekf_update_assoc_aniso_dev
+ * without the meas_cov argument and with Q_k in the place of Q, and nothing else changes: particle i forms R_w(i, k) =
+ * H^T Q_k H of its own heading, step b reads m(l, k) = d^T (P + R_w(i, k))^-1 d per (landmark, detection) pair — still the very
+ * Mahalanobis term of the likelihood the update computes for that pair, through the same reciprocal — the update of landmark l
+ * runs with R_w(i, d_assoc[i][l]) and det Q of that detection, and a landmark a detection creates starts with P = R_w(i, k) of
+ * that detection.  Operation order: tests/_assoc_detcov_spec.py.
+ * Errors: those of the parents; SLAM_ERR_NOT_READY also when the detections carry no covariances.  Timing: the association is
+ * bracketed as SLAM_PROF_PAGES, the update as SLAM_PROF_EKF.  The launches are counted by slam_assoc_detcov_counts (counts[0]
+ * associate, counts[1] update) and by no other counter. */
+int slam_detections_cov_upload_host(slam_engine *e, const float *qxx, const float *qxy, const float *qyy, int ndet);
+int slam_detections_cov_set_dev(slam_engine *e, const float *d_qxx, const float *d_qxy, const float *d_qyy, int ndet);
+int slam_detections_get_cov_host(slam_engine *e, float *qxx, float *qxy, float *qyy, int32_t *ndet);
+int slam_associate_detcov_dev(slam_engine *e, const float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                              const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc, int n,
+                              float gate, float new_gate, int create,
+                              uint8_t *d_assoc, int assoc_stride, int32_t *d_stats /* may be NULL */);
+int slam_ekf_update_assoc_detcov_dev(slam_engine *e, const float *d_map_in, float *d_map_out, int64_t row_stride, int plane_stride,
+                                     int nlandmarks, const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc,
+                                     int n, const uint8_t *d_assoc, int assoc_stride, float *d_loglik);
+int slam_assoc_detcov_counts(slam_engine *e, int64_t counts[2]);
 /* EXISTENCE EVIDENCE.  A detector produces false detections; with association alone each one that lies far from every landmark
  * takes an unseen slot and keeps it for good.  Every particle therefore keeps one EVIDENCE byte c in [0, cmax] per landmark slot
  * beside its row (uint8 [rows][ev_stride]); the counter goes up when the landmark is matched, down when it should have been
@@ -471,6 +503,26 @@ int slam_detect_scan_fit_dev(slam_engine *e, const slam_detect_params *params, c
                              int32_t *d_stats /* [4], may be NULL */);
 int slam_detect_fit_count(slam_engine *e, int64_t *launches);   /* launches that ran the fit; slam_detect_count counts all */
 int slam_detections_get_host(slam_engine *e, float *zx, float *zy, int32_t *ndet);
+/* THE DETECTOR'S NOISE MODEL.  A lidar measures range well and bearing less well, and the cross-beam error grows with range.
+ * slam_detect_scan_noise_dev is slam_detect_scan_fit_dev (noise == NULL: exactly that call, bit for bit and launch for launch)
+ * and, with a model, gives every detection (zx, zy) that passed its range test the covariance the per-detection stages read
+ * (slam_associate_detcov_dev): r2 = zx zx + zy zy, rho = sqrt(r2), u = (zx, zy) / rho, a = range_var, b = bearing_var r2 +
+ * lateral_var, Q = a u u^T + b v v^T with v normal to u: qxx = a ux^2 + b uy^2, qxy = (a - b) ux uy, qyy = a uy^2 + b ux^2 — every
+ * step one rounded float32 operation, in the order of tests/_detect_noise_spec.py.  A detection with r2 == 0, or whose Q fails
+ * the rule of slam_detections_cov_upload_host (cancellation in its determinant at extreme a : b), is NO detection; the cap at
+ * SLAM_MAX_DETECTIONS applies after this rule.  d_stats (may be NULL) is then int32[6]: the four words of
+ * slam_detect_scan_fit_dev (accepted and written count what passed this rule too), the number dropped by it, 0.
+ * SLAM_ERR_INVALID_ARG, nothing launched: as slam_detect_scan_fit_dev, or range_var not finite and > 0, bearing_var [rad^2] or
+ * lateral_var not finite and >= 0, bearing_var + lateral_var not > 0.  One launch of one workgroup; counted by slam_detect_count
+ * (and slam_detect_fit_count with a fit) and, with a model, by slam_detect_noise_count too. */
+typedef struct slam_detect_noise {
+    float range_var;     /* variance along the line of sight [m^2] */
+    float bearing_var;   /* variance of the bearing [rad^2]: bearing_var * r^2 across the line of sight */
+    float lateral_var;   /* range-independent variance across the line of sight [m^2] */
+} slam_detect_noise;
+int slam_detect_scan_noise_dev(slam_engine *e, const slam_detect_params *params, const slam_detect_fit *fit /* NULL: the centroid */,
+                               const slam_detect_noise *noise /* NULL: slam_detect_scan_fit_dev */, int32_t *d_stats /* [6] with noise, may be NULL */);
+int slam_detect_noise_count(slam_engine *e, int64_t *launches);
 /* The FRONT of a frame of a single-GPU slam_pf session on rows — motion sample + scan-match score (FastMatch's inner loop,
  * main.c:459-518, for every particle) and the out-of-place landmark update — goes out as ONE launch whose scoring and
  * updating workgroups are dealt out interleaved: the scorer's gathers (texture addresser, L2) run in the shadow of the
@@ -793,6 +845,16 @@ int slam_pf_assoc_device_view(slam_pf *pf, const uint8_t **assoc, int32_t *assoc
  * association off.  Not implemented: the split, paged, AUTO and sharded forms, an evidence stage fused into the update, more than
  * SLAM_MAX_DETECTIONS detections. */
 int slam_pf_assoc_cov_set(slam_pf *pf, const float meas_cov[3], float gate, float new_gate, int create);
+/* ... under the covariance EACH DETECTION carries (slam_detections_cov_upload_host / _set_dev): every observing frame runs
+ * slam_associate_detcov_dev + slam_ekf_update_assoc_detcov_dev.  The conditions and refusals of slam_pf_assoc_set (rows,
+ * n_landmarks > 0, one GPU, no slam_pf_meas_cov_set in force; gate = 0 is refused here: slam_pf_assoc_set(0, ..) switches off); a
+ * refused call leaves the session as it was.  slam_pf_assoc_set(gate > 0) afterwards returns to isotropic association,
+ * slam_pf_assoc_cov_set to one Q.  Pruning, refinement and the resample gate (the in-place update on kept frames included) are
+ * accepted as on any associating session; no frame fuses its front.  An observing frame whose detections carry no covariance —
+ * no detector and none attached since the last hand-over, or a detector without a noise model (slam_pf_detect_set /
+ * slam_pf_detect_fit_set; slam_pf_detect_noise_set gives it one) — returns SLAM_ERR_NOT_READY before its first launch: the session is unchanged and the next good frame runs as if the
+ * bad one was never asked for. */
+int slam_pf_assoc_detcov_set(slam_pf *pf, float gate, float new_gate, int create);
 /* Pruning of clutter landmarks inside the session (slam_landmark_evidence_dev behind every associating update).  Accepted only
  * while association is on — so never off single-GPU rows: otherwise SLAM_ERR_INVALID_ARG (slam_last_error says why) and the
  * session goes on as before; likewise for hit, miss or cmax outside 1 .. 255 or a view_range that is not finite and > 0.
@@ -821,6 +883,11 @@ int slam_pf_detect_set(slam_pf *pf, const slam_detect_params *params /* NULL: of
  * slam_detect_scan_fit_dev refuses.  params == NULL: the detector off; fit == NULL: slam_pf_detect_set(params).
  * slam_pf_detect_set and slam_pf_assoc_set(gate = 0) clear the fit.  The frame's launches and their order are the same. */
 int slam_pf_detect_fit_set(slam_pf *pf, const slam_detect_params *params /* NULL: off */, const slam_detect_fit *fit /* NULL: the centroid */);
+/* ... with the noise model (slam_detect_scan_noise_dev): accepted and refused exactly where slam_pf_detect_fit_set is — in any
+ * associating mode; the two older modes ignore the covariances — and for a model that slam_detect_scan_noise_dev refuses.
+ * noise == NULL: slam_pf_detect_fit_set(params, fit).  Under slam_pf_assoc_detcov_set this is the detector whose frames run. */
+int slam_pf_detect_noise_set(slam_pf *pf, const slam_detect_params *params /* NULL: off */, const slam_detect_fit *fit /* NULL: the centroid */,
+                             const slam_detect_noise *noise /* NULL: no model */);
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
  * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
