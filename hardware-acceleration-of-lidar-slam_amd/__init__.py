@@ -132,6 +132,11 @@ SIGNATURES = {
     "slam_landmark_evidence_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "slam_evidence_init_dev": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _i]),
     "slam_evidence_counts": (_i, [_vp, _vp]),
+    "slam_sight_table_dev": (_i, [_vp, _i]),
+    "slam_sight_table_get_host": (_i, [_vp, _vp, _vp]),
+    "slam_landmark_evidence_sight_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f,
+                                              _vp, _vp]),
+    "slam_sight_counts": (_i, [_vp, _vp]),
     "slam_detect_params_default": (None, [_vp]),
     "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
     "slam_detect_count": (_i, [_vp, _vp]),
@@ -185,6 +190,8 @@ SIGNATURES = {
     "slam_pf_prune_set": (_i, [_vp, _i, _i, _i, _f]),
     "slam_pf_evidence_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_get_evidence_host": (_i, [_vp, _vp]),
+    "slam_pf_prune_sight_set": (_i, [_vp, _i, _f]),
+    "slam_pf_sight_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_detect_set": (_i, [_vp, _vp]),
     "slam_pf_detect_fit_set": (_i, [_vp, _vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
@@ -554,6 +561,32 @@ class Engine:
         """``slam_evidence_init_dev``: evidence = seen ? value : 0 for the nrows rows of d_map."""
         self._ck(self.lib.slam_evidence_init_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, nrows, _ptr(d_ev), ev_stride,
                                                  int(value)), "evidence_init_dev")
+
+    def sight_table_dev(self, bins: int):
+        """``slam_sight_table_dev``: the sight table of the current scan (bins a power of two in 32 .. 1024), in the engine's buffer."""
+        self._ck(self.lib.slam_sight_table_dev(self.h, int(bins)), "sight_table_dev")
+
+    def sight_table(self):
+        """``slam_sight_table_get_host``: the current sight table float32 [bins]; synchronises."""
+        t, bins = np.full(1024, np.nan, np.float32), C.c_int32(0)
+        self._ck(self.lib.slam_sight_table_get_host(self.h, _ptr(t), C.byref(bins)), "sight_table_get_host")
+        return t[:bins.value].copy()
+
+    def landmark_evidence_sight_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, d_assoc, assoc_stride,
+                                    d_ev_in, d_ev_out, ev_stride, hit, miss, cmax, view_range, margin, d_stats, d_spared):
+        """``slam_landmark_evidence_sight_dev``: landmark_evidence_dev in which a landmark behind what the engine's sight table
+        holds in its direction takes no miss; spared int32 [n] = the landmarks spared one."""
+        self._ck(self.lib.slam_landmark_evidence_sight_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x),
+                                                           _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, _ptr(d_assoc), assoc_stride,
+                                                           _ptr(d_ev_in), _ptr(d_ev_out), ev_stride, int(hit), int(miss), int(cmax),
+                                                           view_range, margin, _ptr(d_stats), _ptr(d_spared)),
+                 "landmark_evidence_sight_dev")
+
+    def sight_counts(self):
+        """-> (sight-table launches, sight evidence-stage launches) of this engine so far."""
+        c = (C.c_int64 * 2)()
+        self._ck(self.lib.slam_sight_counts(self.h, c), "sight_counts")
+        return int(c[0]), int(c[1])
 
     def detect_scan_dev(self, params: "DetectParams | None" = None, d_stats=None, **kw):
         """``slam_detect_scan_dev``: the engine's current scan -> its current detections (asynchronous; the count is picked up by
@@ -1150,6 +1183,18 @@ class PfSession:
         """``slam_pf_prune_set``: existence evidence and pruning of clutter landmarks behind every associating update (only while
         association is on); hit = 0 switches it off."""
         self.e._ck(self.e.lib.slam_pf_prune_set(self.h, int(hit), int(miss), int(cmax), view_range), "pf_prune_set")
+
+    def prune_sight_set(self, bins: int, margin: float = 0.3):
+        """``slam_pf_prune_sight_set``: the pruning's evidence stage with line of sight (only while association is on; in force
+        while pruning is); bins = 0 switches it off."""
+        self.e._ck(self.e.lib.slam_pf_prune_sight_set(self.h, int(bins), margin), "pf_prune_sight_set")
+
+    def sight_view(self):
+        """``slam_pf_sight_device_view``: the engine's sight table float32 [1024] (the first `bins` in use), the bins in force and
+        the last stage's spared counts int32 [n]."""
+        t, sp, bins = C.c_void_p(), C.c_void_p(), C.c_int32(0)
+        self.e._ck(self.e.lib.slam_pf_sight_device_view(self.h, C.byref(t), C.byref(bins), C.byref(sp)), "pf_sight_device_view")
+        return {"table": DeviceArray(t.value, (1024,), "<f4", self), "bins": bins.value, "spared": DeviceArray(sp.value, (self.n,), "<i4", self)}
 
     def detect_set(self, params: "DetectParams | None | bool" = True, **kw):
         """``slam_pf_detect_set``: observing frames make their detections from the engine's scan (only while association is on).

@@ -165,6 +165,7 @@ int slam_engine_destroy(slam_engine* e)
     e->scan_buf.release();
     e->obs_buf.release();
     e->det_buf.release();
+    e->sight_buf.release();
     e->fm_buf.release();
     e->fm_work.release();
     e->scratch.release();

@@ -1,5 +1,5 @@
 // engine_internal.h — the engine object shared by the translation units that implement the C ABI
-// (engine.hip and the engine_*.hip units by stage — match, ekf, assoc, resample —, the pf_session*.hip units, comm.hip, mapper.hip).  Not part of the public interface.
+// (engine.hip and the engine_*.hip units by stage — match, ekf, assoc, sight, resample —, the pf_session*.hip units, comm.hip, mapper.hip).  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -97,6 +97,11 @@ struct slam_engine {
     bool det_has_cov = false;
     int64_t assoc_detcov_launches[2] = { 0, 0 };   // slam_assoc_detcov_counts: the same two under per-detection Q (in no other counter)
     int64_t evidence_launches[2] = { 0, 0 };   // slam_evidence_counts: evidence launches, init launches (in no other counter)
+    // the sight table of the current scan (slam_sight_table_dev), what slam_landmark_evidence_sight_dev reads; whatever hands a
+    // scan over drops it (sight_bins = 0), so a stale table is never read
+    DevBuf sight_buf;   // kSightMaxBins floats
+    int sight_bins = 0;
+    int64_t sight_launches[2] = { 0, 0 };   // slam_sight_counts: table launches, stage launches (in no other counter)
     // the detector (slam_detect_scan_dev): its kernel writes det_buf and leaves {ndet, sequence} in mapped host memory; until the
     // next stage that needs the count on the host has picked it up (slam_engine_resolve_detections) it is PENDING
     int32_t* h_det = nullptr;

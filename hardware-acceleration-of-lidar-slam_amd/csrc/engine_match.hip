@@ -229,6 +229,7 @@ int slam_scan_upload_host(slam_engine* e, const float* bx, const float* by, int 
     e->d_bx = d;
     e->d_by = d + nbeams;
     e->nbeams = nbeams;
+    e->sight_bins = 0;   // (the sight table belonged to the scan before)
     return SLAM_OK;
 }
 
@@ -240,6 +241,7 @@ int slam_scan_set_dev(slam_engine* e, const float* d_bx, const float* d_by, int 
     e->d_bx = d_bx;
     e->d_by = d_by;
     e->nbeams = nbeams;
+    e->sight_bins = 0;
     return SLAM_OK;
 }
 

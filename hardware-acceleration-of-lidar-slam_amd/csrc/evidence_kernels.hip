@@ -16,60 +16,11 @@
 // evidence_init_kernel: c = seen ? value : 0 for whole rows (the same lanes, packing and stores).  evidence_gather_kernel:
 // out[i] = in[anc[i]], whole rows of bytes (a frame without a landmark update: the evidence follows its particles).
 
-#include "ekf_wave.h"
+#include "evidence_common.h"
 
 namespace slam {
 
 namespace {
-
-typedef __attribute__((address_space(1))) unsigned int guint;
-
-// r2 of the visibility test: six separately rounded float32 operations (tests/_evidence_spec.py), never contracted
-__device__ __forceinline__ float evidence_r2(float mx, float my, float px, float py)
-{
-#pragma clang fp contract(off)
-    const float dx = mx - px;
-    const float dy = my - py;
-    const float t = dx * dx;
-    const float u = dy * dy;
-    return t + u;
-}
-
-// WIDE: the bytes of landmarks l and l + 64 (l = 128 b + lane) out of w — lanes 0..31 hold the batch's 32 dwords of one byte
-// array, lanes 32..63 those of another; second = false / true says which.  (Every lane of the wavefront takes part.)
-__device__ __forceinline__ void batch_bytes(unsigned w, unsigned lane, bool second, unsigned& c0, unsigned& c1)
-{
-    const int from = (int)(lane >> 2) + (second ? 32 : 0);
-    const unsigned sh = 8u * (lane & 3u);
-    c0 = (__shfl(w, from, 64) >> sh) & 255u;
-    c1 = (__shfl(w, from + 16, 64) >> sh) & 255u;
-}
-
-// WIDE: the new bytes of landmarks l and l + 64 of every lane -> the 32 dwords of batch b of `row`; dwords from ndw on are not stored
-__device__ __forceinline__ void batch_store(guint* row, unsigned b, unsigned lane, unsigned c0, unsigned c1, unsigned ndw)
-{
-    const unsigned sh = 8u * (lane & 3u);
-    unsigned v0 = c0 << sh, v1 = c1 << sh;
-    v0 |= __shfl_xor(v0, 1, 64);
-    v1 |= __shfl_xor(v1, 1, 64);
-    v0 |= __shfl_xor(v0, 2, 64);
-    v1 |= __shfl_xor(v1, 2, 64);
-    const int from = (int)((lane & 15u) * 4u);
-    const unsigned o0 = __shfl(v0, from, 64), o1 = __shfl(v1, from, 64);
-    const unsigned d = b * 32u + lane;
-    if (lane < 32u && d < ndw) row[d] = (lane & 16u) ? o1 : o0;
-}
-
-// the columns [from, stride) of a row of bytes <- 0 (WIDE: from is a multiple of 4 then)
-template <bool WIDE> __device__ __forceinline__ void zero_tail(guchar* row, unsigned from, unsigned stride, unsigned lane)
-{
-    if (WIDE) {
-        guint* row32 = (guint*)row;
-        for (unsigned d = from / 4u + lane; d < stride / 4u; d += 64u) row32[d] = 0u;
-    } else {
-        for (unsigned c = from + lane; c < stride; c += 64u) row[c] = 0;
-    }
-}
 
 template <bool WIDE>
 __global__ __launch_bounds__(kEkfWaves * 64) void evidence_kernel(EvidenceArgs a)
@@ -201,18 +152,12 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_gather_kernel(const u
     }
 }
 
-// every row of a byte array starts on a dword
-bool dword_rows(const void* base, int stride) { return (stride & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 3u) == 0; }
-
 }  // namespace
 
 hipError_t launch_landmark_evidence(hipStream_t stream, const EvidenceArgs& a_in, const EventPair* ev)
 {
     if (a_in.n <= 0) return hipSuccess;
-    if (a_in.nlandmarks < 0 || a_in.nlandmarks > SLAM_MAX_OBS || a_in.ndet < 0 || a_in.ndet > SLAM_MAX_DETECTIONS ||
-        a_in.assoc_stride < a_in.nlandmarks || a_in.ev_stride < a_in.nlandmarks || a_in.plane_stride < a_in.nlandmarks ||
-        a_in.hit < 1 || a_in.hit > 255 || a_in.miss < 1 || a_in.miss > 255 || a_in.cmax < 1 || a_in.cmax > 255 ||
-        (a_in.anc && a_in.ev_in == a_in.ev_out))
+    if (!evidence_args_ok(a_in))
         return hipErrorInvalidValue;   // what the row and byte accesses are sized by
     EvidenceArgs a = a_in;
     const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);

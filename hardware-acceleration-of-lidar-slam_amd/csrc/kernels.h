@@ -1,5 +1,5 @@
 // kernels.h — launchers of the gfx950 kernels, one section per kernel file in the Makefile's order; called by the C-ABI layer
-// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_resample.hip by stage), the particle-filter session (the pf_session*.hip units) and the mapper (mapper.hip).
+// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_sight / engine_resample.hip by stage), the particle-filter session (the pf_session*.hip units) and the mapper (mapper.hip).
 // Every launcher enqueues on `stream` and returns the hipError_t of the launch; none synchronises.
 #pragma once
 
@@ -286,6 +286,22 @@ struct EvidenceInitArgs {
 hipError_t launch_evidence_init(hipStream_t stream, const EvidenceInitArgs& a, const EventPair* ev = nullptr);
 // a frame without a landmark update: the evidence follows its particles, out[i] = in[anc[i]] (whole rows of `stride` bytes)
 hipError_t launch_evidence_gather(hipStream_t stream, const uint8_t* in, uint8_t* out, int stride, const int32_t* anc, int n);
+// ---- sight_kernels.hip: line of sight for the existence evidence (specification: tests/_sight_spec.py).
+// The SIGHT TABLE of a scan: per direction bin (the diamond angle of a sensor-frame point in `bins` equal steps) the smallest
+// squared range of the scan's points in it, +inf: none.  A landmark behind what the table holds in its direction is hidden.
+constexpr int kSightMinBins = 32, kSightMaxBins = 1024;
+bool sight_bins_ok(int bins);   // a power of two in kSightMinBins .. kSightMaxBins
+// one workgroup over the scan; out: kSightMaxBins floats, the first `bins` the table, +inf behind them
+hipError_t launch_sight_table(hipStream_t stream, const float* bx, const float* by, int nbeams, int bins, float* out, const EventPair* ev = nullptr);
+struct SightArgs {
+    const float* th;       // [n] the headings the update used (beside EvidenceArgs::x / y)
+    const float* table;    // [bins] a sight table (launch_sight_table)
+    int bins;
+    float margin;          // > 0: hidden = the nearest return of the landmark's bin and its two neighbours < (r - margin)^2
+    int32_t* spared;       // [n] landmarks due a miss and hidden; may be nullptr
+};
+// launch_landmark_evidence with miss_now = seen & ~hit_now & visible & ~hidden: the same grid, lanes and byte paths
+hipError_t launch_landmark_evidence_sight(hipStream_t stream, const EvidenceArgs& a, const SightArgs& sg, const EventPair* ev = nullptr);
 // ---- detect_kernels.hip: the landmark detector (specification: tests/_detect_spec.py).  The scan's short,
 // narrow, unoccluded runs of points between two range jumps become the frame's detections: their centroids, in scan order.
 // fit (specification: tests/_detect_fit_spec.py): the runs that are no more spread out than a circle of the given radius, each

@@ -157,6 +157,11 @@ struct slam_pf {
     float prune_range = 0.0f;
     uint8_t* ev[2] = { nullptr, nullptr };   // [n][Lp] each, one allocation made by the first slam_pf_prune_set that switches on
     int32_t* ev_stats = nullptr;             // [n][2] pruned, seen after pruning (the last frame that ran the stage), behind them
+    // slam_pf_prune_sight_set (only while association is on; in force only while pruning is): the evidence stage of an observing
+    // frame is slam_landmark_evidence_sight_dev behind one slam_sight_table_dev over the engine's scan — the same buffers and stats
+    int sight_bins = 0;                      // 0: off
+    float sight_margin = 0.0f;
+    int32_t* sight_spared = nullptr;         // [n] landmarks spared a miss (the last frame that ran the sight stage); made at the first switch-on
     // slam_pf_detect_set (only while association is on): every observing frame makes its detections from the engine's scan
     // (slam_detect_scan_dev), issued in front of the frame's first launch
     bool detect_on = false;

@@ -195,6 +195,7 @@ int slam_pf_destroy(slam_pf* pf)
     if (pf->surv_store) (void)hipFree(pf->surv_store);
     if (pf->assoc_tab) (void)hipFree(pf->assoc_tab);   // (the stats live behind the table)
     if (pf->ev[0]) (void)hipFree(pf->ev[0]);           // (the second buffer and the stats live behind the first)
+    if (pf->sight_spared) (void)hipFree(pf->sight_spared);
     free_page_tables(pf);
     free_split_tables(pf);
     for (void* p : { (void*)pf->score, (void*)pf->logw, (void*)pf->count, (void*)pf->first, (void*)pf->pose_all, (void*)pf->pose_stage, (void*)pf->first_all,
@@ -349,6 +350,7 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
         pf->assoc_aniso = false;
         pf->assoc_detcov = false;
         pf->prune_on = false;
+        pf->sight_bins = 0;
         pf->detect_on = false;
         pf->detect_fit_on = false;
         pf->detect_noise_on = false;
@@ -447,6 +449,34 @@ int slam_pf_prune_set(slam_pf* pf, int hit, int miss, int cmax, float view_range
     pf->prune_cmax = cmax;
     pf->prune_range = view_range;
     return evidence_from_maps(pf);   // the current maps are trusted (indexed like them: before the pending gather)
+}
+
+int slam_pf_prune_sight_set(slam_pf* pf, int bins, float margin)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (bins == 0) {   // off: the evidence stage the session ran before the first call
+        pf->sight_bins = 0;
+        return SLAM_OK;
+    }
+    if (!pf->assoc_on) {   // (accepted where slam_pf_prune_set is)
+        snprintf(e->err, sizeof e->err, "line of sight belongs to the pruning of an associating session: it needs data association "
+                                        "switched on (slam_pf_assoc_set: the row layout on one GPU, not sharded, meas_var * I)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (!sight_bins_ok(bins) || !(margin > 0.0f && margin <= FLT_MAX)) {
+        snprintf(e->err, sizeof e->err, "line of sight needs bins a power of two in %d .. %d and a finite margin > 0", kSightMinBins, kSightMaxBins);
+        return SLAM_ERR_INVALID_ARG;
+    }
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    if (!pf->sight_spared) {   // once, at the switch — never inside a frame: the counts, and the engine's table
+        SLAM_HIP_TRY(e, dev_alloc((void**)&pf->sight_spared, (size_t)pf->n * sizeof(int32_t)));
+        SLAM_HIP_TRY(e, hipMemsetAsync(pf->sight_spared, 0, (size_t)pf->n * sizeof(int32_t), e->stream));
+    }
+    if (!e->sight_buf.p) SLAM_HIP_TRY(e, e->sight_buf.ensure(sizeof(float) * kSightMaxBins));
+    pf->sight_bins = bins;
+    pf->sight_margin = margin;
+    return SLAM_OK;
 }
 
 int slam_pf_detect_set(slam_pf* pf, const slam_detect_params* params) { return slam_pf_detect_fit_set(pf, params, nullptr); }

@@ -344,6 +344,16 @@ int slam_pf_evidence_device_view(slam_pf* pf, const uint8_t** ev, int32_t* ev_st
     return SLAM_OK;
 }
 
+int slam_pf_sight_device_view(slam_pf* pf, const float** table, int32_t* bins, const int32_t** spared)
+{
+    if (!pf || !table || !bins || !spared) return SLAM_ERR_INVALID_ARG;
+    if (!pf->sight_spared) return SLAM_ERR_NOT_READY;   // slam_pf_prune_sight_set never switched line of sight on
+    *table = pf->e->sight_buf.as<float>();
+    *bins = pf->sight_bins;
+    *spared = pf->sight_spared;
+    return SLAM_OK;
+}
+
 int slam_pf_get_evidence_host(slam_pf* pf, uint8_t* ev)
 {
     if (!pf || !ev) return SLAM_ERR_INVALID_ARG;

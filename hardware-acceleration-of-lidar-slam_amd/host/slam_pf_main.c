@@ -20,7 +20,7 @@
  *
  * usage: slam_pf_main dataset.csv frames beams map_out.csv particles [seed [mean|best]]
  *                     [--gpus N] [--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]]
- *                     [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE]
+ *                     [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN]]
  *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
  *                     [--landmarks-out FILE]]
  *   particles      the whole population (a multiple of N)
@@ -35,6 +35,8 @@
  *   --assoc GATE NEW_GATE  data association (slam_pf_assoc_set, create = 1): frames read the engine's detections.  Together
  *                  with --meas-cov and --landmarks: association under that covariance (slam_pf_assoc_cov_set, one call for both)
  *   --prune HIT MISS CMAX RANGE  existence evidence and pruning of clutter landmarks (slam_pf_prune_set)
+ *   --prune-sight BINS MARGIN  only with --prune: a landmark behind what the frame's scan hit in its direction (BINS directions, a
+ *                  power of two in 32 .. 1024; nearer than the landmark by more than MARGIN metres) takes no miss (slam_pf_prune_sight_set)
  *   --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]  the detector (slam_pf_detect_set; no values: slam_detect_params_default):
  *                  every frame makes its detections from its own scan, so the landmark map grows from nothing but lidar frames
  *   --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]  only with --assoc and --detect: the detector's noise model
@@ -77,6 +79,9 @@ typedef struct {
     int use_prune;         /* --prune HIT MISS CMAX RANGE */
     int prune[3];
     float prune_range;
+    int use_sight;         /* --prune-sight BINS MARGIN: only with --prune */
+    int sight_bins;
+    float sight_margin;
     int use_detect;        /* --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] */
     slam_detect_params detect;
     int use_fit;           /* --pole-radius R [TOL] */
@@ -163,6 +168,7 @@ static void *rank_main(void *arg)
     /* --range-noise: every detection carries its own covariance, association and update run under it */
     if (run->use_assoc && !assoc_cov && run->use_noise) CHECK(slam_pf_assoc_detcov_set(pf, run->assoc_gate[0], run->assoc_gate[1], 1));
     if (run->use_prune) CHECK(slam_pf_prune_set(pf, run->prune[0], run->prune[1], run->prune[2], run->prune_range));
+    if (run->use_sight) CHECK(slam_pf_prune_sight_set(pf, run->sight_bins, run->sight_margin));
     if (run->use_detect) CHECK(slam_pf_detect_noise_set(pf, &run->detect, run->use_fit ? &run->fit : NULL, run->use_noise ? &run->noise : NULL));
     const int observe = run->landmarks > 0 && run->use_assoc && run->use_detect;   /* else: no frame has observations */
     if (fe_scan_init(&scan, beams, -2.351831f, 0.004363f) || fe_points_init(&map, FE_MAP_CAPACITY + beams) ||
@@ -330,6 +336,11 @@ int main(int argc, char **argv)
             for (int k = 0; k < 3; ++k) run.prune[k] = atoi(argv[++a]);
             run.prune_range = (float)atof(argv[++a]);
         }
+        else if (!strcmp(argv[a], "--prune-sight") && a + 2 < argc) {
+            run.use_sight = 1;
+            run.sight_bins = atoi(argv[++a]);
+            run.sight_margin = (float)atof(argv[++a]);
+        }
         else if (!strcmp(argv[a], "--detect")) {
             run.use_detect = 1;
             slam_detect_params_default(&run.detect);
@@ -366,16 +377,18 @@ int main(int argc, char **argv)
     }
     const int landmark_options = run.use_assoc || run.use_prune || run.use_detect || run.landmarks_out != NULL;
     if (npos < 5 || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
-        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) ||
+        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) ||
         (run.use_noise && (!run.use_detect || !run.use_assoc || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
-                        "  [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
+                        "  [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
                         "[--landmarks-out FILE]]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
                         "              without --landmarks; with --landmarks and --assoc the association gates and updates under it\n"
                         "  --landmarks: L landmark slots per particle on rows, one GPU; --assoc, --prune, --detect and --landmarks-out need it.\n"
                         "              With --assoc and --detect every frame makes its detections from its own scan\n"
+                        "  --prune-sight BINS MARGIN: only with --prune; a landmark hidden behind what the scan hit (BINS directions, a power of\n"
+                        "              two in 32 .. 1024; nearer by more than MARGIN metres) takes no miss\n"
                         "  --pole-radius R [TOL]: only with --detect; a detection is the centre of the circle of radius R fitted to its segment,\n"
                         "              and segments more spread out than that circle (by more than TOL, default 0) are dropped\n"
                         "  --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --assoc and --detect, not with --meas-cov; every detection\n"

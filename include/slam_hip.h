@@ -440,6 +440,41 @@ int slam_landmark_evidence_dev(slam_engine *e, float *d_map, int64_t row_stride,
 int slam_evidence_init_dev(slam_engine *e, const float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
                            int nrows, uint8_t *d_ev, int ev_stride, int value);
 int slam_evidence_counts(slam_engine *e, int64_t counts[2]);   /* evidence launches, init launches */
+/* LINE OF SIGHT.  The rule above treats the lidar as if it saw through things: a landmark that passes behind a pole or a wall takes
+ * a miss in every frame it is hidden, and is pruned with a converged mean and covariance.  The scan itself says what hides what.
+ * THE BIN of a sensor-frame point (x, y), for bins a power of two in 32 .. 1024, every step one rounded float32 operation:
+ *   ax = |x|, ay = |y|, s = ax + ay; !(s > 0) or s not finite: the point has NO bin; q = ay / s (IEEE division);
+ *   p = q (x >= 0, y >= 0), 2 - q (x < 0, y >= 0), 2 + q (x < 0, y < 0), 4 - q (x >= 0, y < 0) — the tests are x < 0 and y < 0, so
+ *   -0.0 is not negative; j = (int)(p * (bins / 4)) & (bins - 1) (the product is exact; p == 4 wraps to bin 0).
+ * p is the "diamond angle": monotone in the true angle, so bins are contiguous sectors (narrowest on the axes, widest on the
+ * diagonals, by a factor of 2).
+ * slam_sight_table_dev: THE SIGHT TABLE of the engine's current scan, T[j] = the minimum of r2 = x*x + y*y over the scan's points of
+ * bin j, +inf for an empty bin; one launch of one workgroup, into the engine's own buffer.  SLAM_ERR_NOT_READY: no scan;
+ * SLAM_ERR_INVALID_ARG: bins.  slam_scan_upload_host / _set_dev drop the table (a stale table is never read).
+ * slam_sight_table_get_host: t receives the *bins floats of the table; synchronises.  SLAM_ERR_NOT_READY: no table.
+ * slam_landmark_evidence_sight_dev: slam_landmark_evidence_dev with, for the pose (px, py, th = d_th[i]) and dx, dy, r2 of the
+ * visibility test:
+ *   (s, c) = the update's deterministic sine and cosine of th; zx = c*dx - s*dy, zy = s*dx + c*dy (four products, two sums:
+ *   z = R(theta)(w - t)); j = the bin of (zx, zy); near = min(T[(j-1) & (bins-1)], T[j], T[(j+1) & (bins-1)]);
+ *   r = sqrtf(r2), g = r - margin (both correctly rounded);
+ *   hidden = has a bin && g > 0 && near < g * g                (a NaN anywhere: not hidden)
+ * and "seen, no hit, visible" above read "seen, no hit, visible, NOT hidden"; a landmark that is seen, no hit, visible and hidden
+ * keeps c.  A hit counts whether the landmark is hidden or not.  d_spared (may be NULL) is int32 [n] = the landmarks spared a
+ * miss this way; d_stats as above.  It reads the engine's table (the bins it was built with).  Operation order:
+ * tests/_sight_spec.py.  Errors: those of slam_landmark_evidence_dev, a null d_th, a margin that is not finite or <= 0
+ * (SLAM_ERR_INVALID_ARG), and SLAM_ERR_NOT_READY without a table.  Both launches are bracketed as SLAM_PROF_PAGES and counted by
+ * slam_sight_counts (counts[0] table launches, counts[1] stage launches) — not by slam_evidence_counts.
+ * KNOWN LIMIT: a clutter landmark that lies BEHIND a wall is hidden in every frame and is never pruned.  The detector cannot make
+ * one (a detection is a piece of the scan); detections handed over from elsewhere can.  d_spared shows it. */
+int slam_sight_table_dev(slam_engine *e, int bins);
+int slam_sight_table_get_host(slam_engine *e, float *t /* [*bins] out, room for 1024 */, int32_t *bins);
+int slam_landmark_evidence_sight_dev(slam_engine *e, float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                                     const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc, int n,
+                                     const uint8_t *d_assoc, int assoc_stride,
+                                     const uint8_t *d_ev_in, uint8_t *d_ev_out, int ev_stride,
+                                     int hit, int miss, int cmax, float view_range, float margin,
+                                     int32_t *d_stats /* [n][2], may be NULL */, int32_t *d_spared /* [n], may be NULL */);
+int slam_sight_counts(slam_engine *e, int64_t counts[2]);      /* table launches, stage launches */
 /* THE DETECTOR: the detections of a frame made on the device from the engine's current scan (slam_scan_upload_host / _set_dev),
  * P = nbeams points in scan order — what fe_clean left, so a removed beam leaves no hole and the rule uses distances only, never
  * beam angles.  With jump2 = jump * jump, guard2, width2 and range2 likewise (each rounded once to float32), and every step below
@@ -872,6 +907,18 @@ int slam_pf_assoc_detcov_set(slam_pf *pf, float gate, float new_gate, int create
 int slam_pf_prune_set(slam_pf *pf, int hit, int miss, int cmax, float view_range);   /* hit == 0: off */
 int slam_pf_evidence_device_view(slam_pf *pf, const uint8_t **ev, int32_t *ev_stride, const int32_t **stats);
 int slam_pf_get_evidence_host(slam_pf *pf, uint8_t *ev /* [n][nlandmarks] */);       /* pending gather applied, like slam_pf_get_map_host */
+/* Line of sight inside the session.  Accepted where slam_pf_prune_set is (only while association is on; otherwise, or for bins
+ * that are no power of two in 32 .. 1024 or a margin that is not finite and > 0: SLAM_ERR_INVALID_ARG, and the session goes on as
+ * before); it is IN FORCE only while pruning is on.  bins == 0 switches it off, and so does slam_pf_assoc_set(gate = 0); with it
+ * off the session runs exactly what it ran before the first call, and slam_sight_counts does not move.  In force, the evidence
+ * stage of an observing frame is one slam_sight_table_dev(bins) over the engine's current scan (the scan the frame scores and
+ * the detector reads) and then slam_landmark_evidence_sight_dev in the place of slam_landmark_evidence_dev: the same evidence
+ * buffers, the same stats.  Switching on allocates (once) the spared counts; no frame allocates.
+ * slam_pf_sight_device_view: the engine's table (1024 floats, the first *bins in use), the bins in force (0: off) and the spared
+ * counts ([n_particles], indexed like slam_pf_view.score) of the last frame that ran the stage.  SLAM_ERR_NOT_READY until line
+ * of sight was switched on. */
+int slam_pf_prune_sight_set(slam_pf *pf, int bins /* 0: off */, float margin);
+int slam_pf_sight_device_view(slam_pf *pf, const float **table, int32_t *bins, const int32_t **spared);
 /* The detector inside the session (slam_detect_scan_dev with these parameters; NULL: off).  Accepted only while association is on
  * — otherwise SLAM_ERR_INVALID_ARG (slam_last_error says why) and the session goes on as before; likewise for parameters that
  * slam_detect_scan_dev refuses.  slam_pf_assoc_set(gate = 0) switches it off too.  With it on, every frame with use_observations
