@@ -137,6 +137,10 @@ SIGNATURES = {
     "slam_landmark_evidence_sight_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f,
                                               _vp, _vp]),
     "slam_sight_counts": (_i, [_vp, _vp]),
+    "slam_fov_bound": (_f, [_f]),
+    "slam_landmark_evidence_fov_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f,
+                                            _f, _f, _i, _vp, _vp, _vp]),
+    "slam_fov_counts": (_i, [_vp, _vp]),
     "slam_detect_params_default": (None, [_vp]),
     "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
     "slam_detect_count": (_i, [_vp, _vp]),
@@ -192,6 +196,8 @@ SIGNATURES = {
     "slam_pf_get_evidence_host": (_i, [_vp, _vp]),
     "slam_pf_prune_sight_set": (_i, [_vp, _i, _f]),
     "slam_pf_sight_device_view": (_i, [_vp, _vp, _vp, _vp]),
+    "slam_pf_prune_fov_set": (_i, [_vp, _i, _f, _f, _f]),
+    "slam_pf_fov_device_view": (_i, [_vp, _vp, _vp]),
     "slam_pf_detect_set": (_i, [_vp, _vp]),
     "slam_pf_detect_fit_set": (_i, [_vp, _vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
@@ -587,6 +593,24 @@ class Engine:
         c = (C.c_int64 * 2)()
         self._ck(self.lib.slam_sight_counts(self.h, c), "sight_counts")
         return int(c[0]), int(c[1])
+
+    def landmark_evidence_fov_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, d_assoc, assoc_stride,
+                                  d_ev_in, d_ev_out, ev_stride, hit, miss, cmax, view_range, margin, lo, hi, use_sight, d_stats, d_spared,
+                                  d_outside):
+        """``slam_landmark_evidence_fov_dev``: landmark_evidence_sight_dev (use_sight) or landmark_evidence_dev in which a landmark
+        due a miss whose diamond angle in the sensor frame lies outside [lo, hi] takes none; outside int32 [n] = those landmarks."""
+        self._ck(self.lib.slam_landmark_evidence_fov_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x),
+                                                         _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, _ptr(d_assoc), assoc_stride,
+                                                         _ptr(d_ev_in), _ptr(d_ev_out), ev_stride, int(hit), int(miss), int(cmax),
+                                                         view_range, margin, lo, hi, int(bool(use_sight)), _ptr(d_stats),
+                                                         _ptr(d_spared), _ptr(d_outside)),
+                 "landmark_evidence_fov_dev")
+
+    def fov_counts(self):
+        """-> the launches of the evidence stage with a field of view of this engine so far."""
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_fov_counts(self.h, C.byref(c)), "fov_counts")
+        return int(c.value)
 
     def detect_scan_dev(self, params: "DetectParams | None" = None, d_stats=None, **kw):
         """``slam_detect_scan_dev``: the engine's current scan -> its current detections (asynchronous; the count is picked up by
@@ -1196,6 +1220,17 @@ class PfSession:
         self.e._ck(self.e.lib.slam_pf_sight_device_view(self.h, C.byref(t), C.byref(bins), C.byref(sp)), "pf_sight_device_view")
         return {"table": DeviceArray(t.value, (1024,), "<f4", self), "bins": bins.value, "spared": DeviceArray(sp.value, (self.n,), "<i4", self)}
 
+    def prune_fov_set(self, on: bool, angle_min: float = -2.351831, angle_max: float = 2.351831, edge: float = 0.0):
+        """``slam_pf_prune_fov_set``: the pruning's evidence stage with a field of view [angle_min + edge, angle_max - edge] (only
+        while association is on; in force while pruning is); on = False switches it off."""
+        self.e._ck(self.e.lib.slam_pf_prune_fov_set(self.h, int(bool(on)), angle_min, angle_max, edge), "pf_prune_fov_set")
+
+    def fov_view(self):
+        """``slam_pf_fov_device_view``: the bounds (lo, hi) in force as float32 and the last stage's outside counts int32 [n]."""
+        b, out = (C.c_float * 2)(), C.c_void_p()
+        self.e._ck(self.e.lib.slam_pf_fov_device_view(self.h, b, C.byref(out)), "pf_fov_device_view")
+        return {"bounds": (np.float32(b[0]), np.float32(b[1])), "outside": DeviceArray(out.value, (self.n,), "<i4", self)}
+
     def detect_set(self, params: "DetectParams | None | bool" = True, **kw):
         """``slam_pf_detect_set``: observing frames make their detections from the engine's scan (only while association is on).
         params: a DetectParams; True: the defaults with the keywords applied; None / False: off."""
@@ -1277,6 +1312,11 @@ def plan_words(world: int) -> int:
 
 def comb_offset(seed: int, frame: int, total: int) -> int:
     return int(load_library().slam_comb_offset(seed, frame, total))
+
+
+def fov_bound(angle: float):
+    """``slam_fov_bound``: the diamond angle in [0, 4] of the direction `angle` (radians) -> numpy float32; needs no GPU."""
+    return np.float32(load_library().slam_fov_bound(float(angle)))
 
 
 def grid_meta(rows, cols, ld, pixel, min_x, min_y) -> GridMeta:

@@ -1,6 +1,7 @@
-// evidence_common.h — what the two forms of the existence-evidence stage share (evidence_kernels.hip: every landmark within
-// view_range is visible; sight_kernels.hip: one behind what the scan hit is hidden): the visibility test's r2, and the byte
-// traffic of a batch of 128 landmarks as dwords (WIDE) — see the head of evidence_kernels.hip for the access shape.
+// evidence_common.h — what the forms of the existence-evidence stage share (evidence_kernels.hip: every landmark within
+// view_range is visible; sight_kernels.hip: one behind what the scan hit is hidden; fov_kernels.hip: one outside the sensor's arc
+// is not looked at): the visibility test's r2, the diamond angle of a direction, and the byte traffic of a batch of 128 landmarks
+// as dwords (WIDE) — see the head of evidence_kernels.hip for the access shape.
 #pragma once
 
 #include "ekf_wave.h"
@@ -18,6 +19,28 @@ __device__ __forceinline__ float evidence_r2(float mx, float my, float px, float
     const float t = dx * dx;
     const float u = dy * dy;
     return t + u;
+}
+
+// the DIAMOND ANGLE p in [0, 4] of the sensor-frame point (x, y) (tests/_sight_spec.py: bin_of; tests/_fov_spec.py: diamond):
+// false — none (the origin, a point that is not finite; p = 0 then).  One IEEE division, every step rounded once.  (Host too:
+// slam_fov_bound.)
+__host__ __device__ __forceinline__ bool diamond_angle(float x, float y, float& p)
+{
+#pragma clang fp contract(off)
+    const float ax = fabsf(x), ay = fabsf(y);
+    const float s = ax + ay;
+    const bool has = s > 0.0f && s <= 3.402823466e+38f;   // (NaN fails both)
+    const float q = has ? ay / s : 0.0f;                  // IEEE division (-fno-fast-math)
+    const bool nx = x < 0.0f, ny = y < 0.0f;              // -0.0 is not negative
+    p = nx ? (ny ? 2.0f + q : 2.0f - q) : (ny ? 4.0f - q : q);
+    return has;
+}
+
+// the direction bin of a diamond angle: quarter = bins / 4 as a float, a power of two: the product is exact; p == 4 wraps to bin 0
+__device__ __forceinline__ unsigned diamond_bin(float p, float quarter, unsigned mask)
+{
+#pragma clang fp contract(off)
+    return (unsigned)(int)(p * quarter) & mask;
 }
 
 // WIDE: the bytes of landmarks l and l + 64 (l = 128 b + lane) out of w — lanes 0..31 hold the batch's 32 dwords of one byte

@@ -1,5 +1,5 @@
 // kernels.h — launchers of the gfx950 kernels, one section per kernel file in the Makefile's order; called by the C-ABI layer
-// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_sight / engine_resample.hip by stage), the particle-filter session (the pf_session*.hip units) and the mapper (mapper.hip).
+// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_sight / engine_fov / engine_resample.hip by stage), the particle-filter session (the pf_session*.hip units) and the mapper (mapper.hip).
 // Every launcher enqueues on `stream` and returns the hipError_t of the launch; none synchronises.
 #pragma once
 
@@ -302,6 +302,17 @@ struct SightArgs {
 };
 // launch_landmark_evidence with miss_now = seen & ~hit_now & visible & ~hidden: the same grid, lanes and byte paths
 hipError_t launch_landmark_evidence_sight(hipStream_t stream, const EvidenceArgs& a, const SightArgs& sg, const EventPair* ev = nullptr);
+// ---- fov_kernels.hip: a field of view for the existence evidence (specification: tests/_fov_spec.py).  A
+// landmark due a miss whose sensor-frame direction (its diamond angle p) lies outside the arc takes none and keeps its counter.
+struct FovArgs {
+    float lo, hi;          // in [0, 4]; lo <= hi: in view = lo <= p <= hi; lo > hi: p >= lo || p <= hi (the arc through p = 4 = 0)
+    int32_t* outside;      // [n] landmarks due a miss and outside the arc; may be nullptr
+};
+bool fov_bounds_ok(float lo, float hi);
+// launch_landmark_evidence_sight with miss_now = due & in view & ~hidden; sg.table == nullptr: without line of sight (nothing is
+// hidden; sg.bins and sg.margin are not read, sg.th is, sg.spared is written 0).  The same grid, lanes and byte paths
+hipError_t launch_landmark_evidence_fov(hipStream_t stream, const EvidenceArgs& a, const SightArgs& sg, const FovArgs& fv,
+                                        const EventPair* ev = nullptr);
 // ---- detect_kernels.hip: the landmark detector (specification: tests/_detect_spec.py).  The scan's short,
 // narrow, unoccluded runs of points between two range jumps become the frame's detections: their centroids, in scan order.
 // fit (specification: tests/_detect_fit_spec.py): the runs that are no more spread out than a circle of the given radius, each

@@ -162,6 +162,11 @@ struct slam_pf {
     int sight_bins = 0;                      // 0: off
     float sight_margin = 0.0f;
     int32_t* sight_spared = nullptr;         // [n] landmarks spared a miss (the last frame that ran the sight stage); made at the first switch-on
+    // slam_pf_prune_fov_set (accepted and in force as line of sight is): the evidence stage of an observing frame is
+    // slam_landmark_evidence_fov_dev — behind the sight table and with use_sight = 1 where sight_bins != 0
+    bool fov_on = false;
+    float fov_lo = 0.0f, fov_hi = 4.0f;      // slam_fov_bound(angle_min + edge), slam_fov_bound(angle_max - edge)
+    int32_t* fov_outside = nullptr;          // [n] landmarks due a miss outside the arc (the last frame that ran the stage); made at the first switch-on
     // slam_pf_detect_set (only while association is on): every observing frame makes its detections from the engine's scan
     // (slam_detect_scan_dev), issued in front of the frame's first launch
     bool detect_on = false;

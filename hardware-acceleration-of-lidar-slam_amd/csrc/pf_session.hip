@@ -196,6 +196,7 @@ int slam_pf_destroy(slam_pf* pf)
     if (pf->assoc_tab) (void)hipFree(pf->assoc_tab);   // (the stats live behind the table)
     if (pf->ev[0]) (void)hipFree(pf->ev[0]);           // (the second buffer and the stats live behind the first)
     if (pf->sight_spared) (void)hipFree(pf->sight_spared);
+    if (pf->fov_outside) (void)hipFree(pf->fov_outside);
     free_page_tables(pf);
     free_split_tables(pf);
     for (void* p : { (void*)pf->score, (void*)pf->logw, (void*)pf->count, (void*)pf->first, (void*)pf->pose_all, (void*)pf->pose_stage, (void*)pf->first_all,
@@ -351,6 +352,7 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
         pf->assoc_detcov = false;
         pf->prune_on = false;
         pf->sight_bins = 0;
+        pf->fov_on = false;
         pf->detect_on = false;
         pf->detect_fit_on = false;
         pf->detect_noise_on = false;
@@ -476,6 +478,37 @@ int slam_pf_prune_sight_set(slam_pf* pf, int bins, float margin)
     if (!e->sight_buf.p) SLAM_HIP_TRY(e, e->sight_buf.ensure(sizeof(float) * kSightMaxBins));
     pf->sight_bins = bins;
     pf->sight_margin = margin;
+    return SLAM_OK;
+}
+
+int slam_pf_prune_fov_set(slam_pf* pf, int on, float angle_min, float angle_max, float edge)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (!on) {   // off: the evidence stage the session ran before the first call
+        pf->fov_on = false;
+        return SLAM_OK;
+    }
+    if (!pf->assoc_on) {   // (accepted where slam_pf_prune_sight_set is)
+        snprintf(e->err, sizeof e->err, "a field of view belongs to the pruning of an associating session: it needs data association "
+                                        "switched on (slam_pf_assoc_set: the row layout on one GPU, not sharded, meas_var * I)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    const float pi = 3.14159274f;   // float32 pi
+    const float from = angle_min + edge, to = angle_max - edge;   // (a NaN or an infinity anywhere fails a comparison below)
+    if (!(edge >= 0.0f && edge <= FLT_MAX && angle_min >= -pi && angle_max <= pi && from < to)) {
+        snprintf(e->err, sizeof e->err, "a field of view needs finite angles -pi <= angle_min, angle_max <= pi and a finite edge >= 0 "
+                                        "with angle_min + edge < angle_max - edge");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    if (!pf->fov_outside) {   // once, at the switch — never inside a frame
+        SLAM_HIP_TRY(e, dev_alloc((void**)&pf->fov_outside, (size_t)pf->n * sizeof(int32_t)));
+        SLAM_HIP_TRY(e, hipMemsetAsync(pf->fov_outside, 0, (size_t)pf->n * sizeof(int32_t), e->stream));
+    }
+    pf->fov_lo = slam_fov_bound(from);
+    pf->fov_hi = slam_fov_bound(to);
+    pf->fov_on = true;
     return SLAM_OK;
 }
 

@@ -323,7 +323,15 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
             if (int rc = slam_engine_ekf_update(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, noise, &table, nullptr))
                 return rc;
             // existence evidence, on the row the update wrote: through the frame's gather into the other buffer, or in place
-            if (pf->prune_on && pf->sight_bins) {   // ... with line of sight: the table of this frame's scan, then the stage that reads it
+            if (pf->prune_on && pf->fov_on) {   // ... with a field of view (and line of sight: the table of this frame's scan first)
+                if (pf->sight_bins)
+                    if (int rc = slam_sight_table_dev(e, pf->sight_bins)) return rc;
+                if (int rc = slam_landmark_evidence_fov_dev(e, out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->assoc_tab, pf->Lp,
+                                                            pf->ev[mc], pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit, pf->prune_miss,
+                                                            pf->prune_cmax, pf->prune_range, pf->sight_margin, pf->fov_lo, pf->fov_hi,
+                                                            pf->sight_bins != 0, pf->ev_stats, pf->sight_spared, pf->fov_outside))
+                    return rc;
+            } else if (pf->prune_on && pf->sight_bins) {   // ... with line of sight: the table of this frame's scan, then the stage that reads it
                 if (int rc = slam_sight_table_dev(e, pf->sight_bins)) return rc;
                 if (int rc = slam_landmark_evidence_sight_dev(e, out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->assoc_tab,
                                                               pf->Lp, pf->ev[mc], pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit,

@@ -354,6 +354,16 @@ int slam_pf_sight_device_view(slam_pf* pf, const float** table, int32_t* bins, c
     return SLAM_OK;
 }
 
+int slam_pf_fov_device_view(slam_pf* pf, float bounds[2], const int32_t** outside)
+{
+    if (!pf || !bounds || !outside) return SLAM_ERR_INVALID_ARG;
+    if (!pf->fov_outside) return SLAM_ERR_NOT_READY;   // slam_pf_prune_fov_set never switched the field of view on
+    bounds[0] = pf->fov_on ? pf->fov_lo : 0.0f;        // (off: everything is in view)
+    bounds[1] = pf->fov_on ? pf->fov_hi : 4.0f;
+    *outside = pf->fov_outside;
+    return SLAM_OK;
+}
+
 int slam_pf_get_evidence_host(slam_pf* pf, uint8_t* ev)
 {
     if (!pf || !ev) return SLAM_ERR_INVALID_ARG;

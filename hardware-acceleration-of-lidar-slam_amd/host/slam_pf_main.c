@@ -20,7 +20,7 @@
  *
  * usage: slam_pf_main dataset.csv frames beams map_out.csv particles [seed [mean|best]]
  *                     [--gpus N] [--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]]
- *                     [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN]]
+ *                     [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]]
  *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
  *                     [--landmarks-out FILE]]
  *   particles      the whole population (a multiple of N)
@@ -37,6 +37,8 @@
  *   --prune HIT MISS CMAX RANGE  existence evidence and pruning of clutter landmarks (slam_pf_prune_set)
  *   --prune-sight BINS MARGIN  only with --prune: a landmark behind what the frame's scan hit in its direction (BINS directions, a
  *                  power of two in 32 .. 1024; nearer than the landmark by more than MARGIN metres) takes no miss (slam_pf_prune_sight_set)
+ *   --prune-fov EDGE  only with --prune: a landmark whose direction lies outside the lidar's arc — the first to the last beam angle
+ *                  of the scan, narrowed by EDGE >= 0 radians at both ends — takes no miss (slam_pf_prune_fov_set)
  *   --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]  the detector (slam_pf_detect_set; no values: slam_detect_params_default):
  *                  every frame makes its detections from its own scan, so the landmark map grows from nothing but lidar frames
  *   --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]  only with --assoc and --detect: the detector's noise model
@@ -82,6 +84,8 @@ typedef struct {
     int use_sight;         /* --prune-sight BINS MARGIN: only with --prune */
     int sight_bins;
     float sight_margin;
+    int use_fov;           /* --prune-fov EDGE: only with --prune */
+    float fov_edge;
     int use_detect;        /* --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] */
     slam_detect_params detect;
     int use_fit;           /* --pole-radius R [TOL] */
@@ -177,6 +181,8 @@ static void *rank_main(void *arg)
         fprintf(stderr, "rank %d: out of memory\n", rank);
         goto fail;
     }
+    /* --prune-fov: the arc is the scan's own, its first and its last beam angle */
+    if (run->use_fov) CHECK(slam_pf_prune_fov_set(pf, 1, scan.angle[0], scan.angle[beams - 1], run->fov_edge));
     int32_t nhits = 0;
     double t_step = 0;
     const double t_begin = now_s();
@@ -341,6 +347,15 @@ int main(int argc, char **argv)
             run.sight_bins = atoi(argv[++a]);
             run.sight_margin = (float)atof(argv[++a]);
         }
+        else if (!strcmp(argv[a], "--prune-fov") && a + 1 < argc) {
+            char *end = NULL;
+            run.use_fov = 1;
+            run.fov_edge = strtof(argv[++a], &end);
+            if (end == argv[a] || *end || !isfinite(run.fov_edge) || run.fov_edge < 0.0f) {
+                fprintf(stderr, "--prune-fov %s: EDGE must be a finite number of radians >= 0\n", argv[a]);
+                return 2;
+            }
+        }
         else if (!strcmp(argv[a], "--detect")) {
             run.use_detect = 1;
             slam_detect_params_default(&run.detect);
@@ -377,11 +392,11 @@ int main(int argc, char **argv)
     }
     const int landmark_options = run.use_assoc || run.use_prune || run.use_detect || run.landmarks_out != NULL;
     if (npos < 5 || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
-        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) ||
+        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) ||
         (run.use_noise && (!run.use_detect || !run.use_assoc || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
-                        "  [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
+                        "  [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
                         "[--landmarks-out FILE]]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
                         "              without --landmarks; with --landmarks and --assoc the association gates and updates under it\n"
@@ -389,6 +404,8 @@ int main(int argc, char **argv)
                         "              With --assoc and --detect every frame makes its detections from its own scan\n"
                         "  --prune-sight BINS MARGIN: only with --prune; a landmark hidden behind what the scan hit (BINS directions, a power of\n"
                         "              two in 32 .. 1024; nearer by more than MARGIN metres) takes no miss\n"
+                        "  --prune-fov EDGE: only with --prune; a landmark outside the lidar's arc (first to last beam angle, narrowed by EDGE\n"
+                        "              radians at both ends) takes no miss\n"
                         "  --pole-radius R [TOL]: only with --detect; a detection is the centre of the circle of radius R fitted to its segment,\n"
                         "              and segments more spread out than that circle (by more than TOL, default 0) are dropped\n"
                         "  --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --assoc and --detect, not with --meas-cov; every detection\n"

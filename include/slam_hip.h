@@ -414,7 +414,8 @@ int slam_assoc_detcov_counts(slam_engine *e, int64_t counts[2]);
  *   seen     = !(P_xx < 0)          (the update's own test: -0.0 counts as seen)
  *   hit_now  = a < K                (a byte that names no detection of this frame, K <= a <= 255, is no hit — as in the update)
  *   visible  = r2 <= range2 with dx = mu_x - px, dy = mu_y - py, t = dx * dx, u = dy * dy, r2 = t + u: six separately rounded
- *              float32 operations, no fused multiply-add; a NaN mean is not visible.  (A 360-degree sensor: no bearing test.)
+ *              float32 operations, no fused multiply-add; a NaN mean is not visible.  (A 360-degree sensor: no bearing test;
+ *              a sensor with a field of view: slam_landmark_evidence_fov_dev below.)
  *   not seen:                              c' = 0
  *   seen, hit_now:                         c' = min(c + hit, cmax), in integers (c = 200, hit = 255 does not wrap)
  *   seen, no hit, visible, c >= miss:      c' = c - miss
@@ -475,6 +476,37 @@ int slam_landmark_evidence_sight_dev(slam_engine *e, float *d_map, int64_t row_s
                                      int hit, int miss, int cmax, float view_range, float margin,
                                      int32_t *d_stats /* [n][2], may be NULL */, int32_t *d_spared /* [n], may be NULL */);
 int slam_sight_counts(slam_engine *e, int64_t counts[2]);      /* table launches, stage launches */
+/* A FIELD OF VIEW.  Both rules above treat the sensor as a full circle.  The lidar this project is built around sees 269.5 degrees
+ * (1079 beams from -2.351831 rad in steps of 0.004363 rad): a landmark that drifts into the blind quarter behind the robot is
+ * "seen, no hit, visible" in every frame, takes a miss per frame and is pruned with a converged mean and covariance — and line of
+ * sight does not help, because the bins of the blind quarter are empty and nothing is hidden there.
+ * Directions are the DIAMOND ANGLE p of THE BIN above (p in [0, 4], before it is scaled to a bin; no arctangent).
+ * slam_fov_bound: a pure host function, the diamond angle of (cosf(angle), sinf(angle)) — the C library's cosine and sine, then the
+ * operations of THE BIN; 0 for an angle that is not finite.
+ * slam_landmark_evidence_fov_dev: slam_landmark_evidence_sight_dev (use_sight != 0) or slam_landmark_evidence_dev (use_sight == 0)
+ * with, for zx, zy as slam_landmark_evidence_sight_dev computes them (the same rotation, the same operation order) and p, "has a
+ * bin" of (zx, zy):
+ *   in_view = !has a bin || (lo <= hi ? (p >= lo && p <= hi) : (p >= lo || p <= hi))
+ * — lo, hi in [0, 4]; a bound itself is in view; a landmark at the sensor is in view; lo > hi is the arc that wraps through p = 4 =
+ * 0, the ordinary one for a sensor whose blind sector straddles p = 2; lo = 0, hi = 4 puts everything in view (and the outputs are
+ * then, bit for bit, those of the stage it stands in for).  With due = seen, no hit, visible:
+ *   due && !in_view: OUTSIDE, c stays;   hidden (use_sight != 0 only) counts only where due && in_view;
+ *   a miss is paid where due && in_view && !hidden.   A hit counts whatever the direction.
+ * d_outside (may be NULL) is int32 [n] = the landmarks that were due a miss and outside; d_stats and d_spared as above (use_sight ==
+ * 0: no table is needed, margin is ignored, d_th is still required, d_spared, if given, is written 0).  Operation order:
+ * tests/_fov_spec.py.  Errors: those of slam_landmark_evidence_sight_dev (the margin's and SLAM_ERR_NOT_READY without a table only
+ * when use_sight != 0), and SLAM_ERR_INVALID_ARG for a bound that is NaN or outside [0, 4].  The launch is bracketed as
+ * SLAM_PROF_PAGES and counted by slam_fov_counts — in no other counter (a table launch still counts in slam_sight_counts[0]). */
+float slam_fov_bound(float angle);
+int slam_landmark_evidence_fov_dev(slam_engine *e, float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                                   const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc, int n,
+                                   const uint8_t *d_assoc, int assoc_stride,
+                                   const uint8_t *d_ev_in, uint8_t *d_ev_out, int ev_stride,
+                                   int hit, int miss, int cmax, float view_range, float margin,
+                                   float lo, float hi, int use_sight,
+                                   int32_t *d_stats /* [n][2], may be NULL */, int32_t *d_spared /* [n], may be NULL */,
+                                   int32_t *d_outside /* [n], may be NULL */);
+int slam_fov_counts(slam_engine *e, int64_t *launches);        /* stage launches */
 /* THE DETECTOR: the detections of a frame made on the device from the engine's current scan (slam_scan_upload_host / _set_dev),
  * P = nbeams points in scan order — what fe_clean left, so a removed beam leaves no hole and the rule uses distances only, never
  * beam angles.  With jump2 = jump * jump, guard2, width2 and range2 likewise (each rounded once to float32), and every step below
@@ -919,6 +951,20 @@ int slam_pf_get_evidence_host(slam_pf *pf, uint8_t *ev /* [n][nlandmarks] */);  
  * of sight was switched on. */
 int slam_pf_prune_sight_set(slam_pf *pf, int bins /* 0: off */, float margin);
 int slam_pf_sight_device_view(slam_pf *pf, const float **table, int32_t *bins, const int32_t **spared);
+/* The field of view inside the session.  Accepted where slam_pf_prune_sight_set is (only while association is on); IN FORCE only
+ * while pruning is on; on == 0 switches it off, and so does slam_pf_assoc_set(gate = 0); with it off the session runs exactly what
+ * it ran before the first call, launch for launch, and slam_fov_counts does not move.  The arc is [angle_min + edge, angle_max -
+ * edge] in radians of the sensor frame (float32 sums): lo = slam_fov_bound(angle_min + edge), hi = slam_fov_bound(angle_max -
+ * edge); edge >= 0 narrows the view at both ends — it covers the strip in which the detector (wrap = 0) drops the segments that
+ * touch the edge of the view.  SLAM_ERR_INVALID_ARG (and the session goes on as before) for a value that is not finite, edge < 0,
+ * angle_min < -pi or angle_max > pi (float32 pi), or angle_min + edge >= angle_max - edge.  In force, the evidence stage of an
+ * observing frame is slam_landmark_evidence_fov_dev in the place of slam_landmark_evidence_dev (use_sight = 0) or, with line of
+ * sight on, behind its slam_sight_table_dev in the place of slam_landmark_evidence_sight_dev (use_sight = 1): the same evidence
+ * buffers, the same stats.  Switching on allocates (once) the outside counts; no frame allocates.
+ * slam_pf_fov_device_view: the bounds in force (0, 4 while it is off: everything in view) and the outside counts ([n_particles],
+ * indexed like slam_pf_view.score) of the last frame that ran the stage.  SLAM_ERR_NOT_READY until it was switched on. */
+int slam_pf_prune_fov_set(slam_pf *pf, int on, float angle_min, float angle_max, float edge);
+int slam_pf_fov_device_view(slam_pf *pf, float bounds[2], const int32_t **outside);
 /* The detector inside the session (slam_detect_scan_dev with these parameters; NULL: off).  Accepted only while association is on
  * — otherwise SLAM_ERR_INVALID_ARG (slam_last_error says why) and the session goes on as before; likewise for parameters that
  * slam_detect_scan_dev refuses.  slam_pf_assoc_set(gate = 0) switches it off too.  With it on, every frame with use_observations
