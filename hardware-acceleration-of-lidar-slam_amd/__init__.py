@@ -141,6 +141,8 @@ SIGNATURES = {
     "slam_landmark_evidence_fov_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f,
                                             _f, _f, _i, _vp, _vp, _vp]),
     "slam_fov_counts": (_i, [_vp, _vp]),
+    "slam_landmark_merge_dev": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp]),
+    "slam_merge_count": (_i, [_vp, _vp]),
     "slam_detect_params_default": (None, [_vp]),
     "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
     "slam_detect_count": (_i, [_vp, _vp]),
@@ -198,6 +200,8 @@ SIGNATURES = {
     "slam_pf_sight_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_prune_fov_set": (_i, [_vp, _i, _f, _f, _f]),
     "slam_pf_fov_device_view": (_i, [_vp, _vp, _vp]),
+    "slam_pf_merge_set": (_i, [_vp, _f]),
+    "slam_pf_merge_device_view": (_i, [_vp, _vp]),
     "slam_pf_detect_set": (_i, [_vp, _vp]),
     "slam_pf_detect_fit_set": (_i, [_vp, _vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
@@ -610,6 +614,21 @@ class Engine:
         """-> the launches of the evidence stage with a field of view of this engine so far."""
         c = C.c_int64(0)
         self._ck(self.lib.slam_fov_counts(self.h, C.byref(c)), "fov_counts")
+        return int(c.value)
+
+    def landmark_merge_dev(self, d_map, row_stride, plane_stride, nlandmarks, n, d_assoc, assoc_stride, d_ev, ev_stride, cmax, merge_gate,
+                           d_stats=None):
+        """``slam_landmark_merge_dev``: behind the frame's associating update and evidence stage, in place — a seen landmark the
+        table does not name that lies within merge_gate of one it names is fused into it and its slot cleared (d_ev None: without
+        evidence); stats int32 [n][3] = merged, refused, seen after."""
+        self._ck(self.lib.slam_landmark_merge_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, n, _ptr(d_assoc), assoc_stride,
+                                                  _ptr(d_ev), ev_stride, int(cmax), merge_gate, _ptr(d_stats)),
+                 "landmark_merge_dev")
+
+    def merge_count(self):
+        """-> the launches of the merge stage of this engine so far."""
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_merge_count(self.h, C.byref(c)), "merge_count")
         return int(c.value)
 
     def detect_scan_dev(self, params: "DetectParams | None" = None, d_stats=None, **kw):
@@ -1230,6 +1249,17 @@ class PfSession:
         b, out = (C.c_float * 2)(), C.c_void_p()
         self.e._ck(self.e.lib.slam_pf_fov_device_view(self.h, b, C.byref(out)), "pf_fov_device_view")
         return {"bounds": (np.float32(b[0]), np.float32(b[1])), "outside": DeviceArray(out.value, (self.n,), "<i4", self)}
+
+    def merge_set(self, merge_gate: float):
+        """``slam_pf_merge_set``: every observing frame merges duplicate landmarks behind its update and evidence stage (only
+        while association is on); merge_gate = 0 switches it off."""
+        self.e._ck(self.e.lib.slam_pf_merge_set(self.h, merge_gate), "pf_merge_set")
+
+    def merge_view(self):
+        """``slam_pf_merge_device_view``: the last stage's stats int32 [n][3] = merged, refused, seen after."""
+        st = C.c_void_p()
+        self.e._ck(self.e.lib.slam_pf_merge_device_view(self.h, C.byref(st)), "pf_merge_device_view")
+        return DeviceArray(st.value, (self.n, 3), "<i4", self)
 
     def detect_set(self, params: "DetectParams | None | bool" = True, **kw):
         """``slam_pf_detect_set``: observing frames make their detections from the engine's scan (only while association is on).

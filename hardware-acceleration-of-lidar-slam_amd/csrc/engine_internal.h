@@ -1,5 +1,5 @@
 // engine_internal.h — the engine object shared by the translation units that implement the C ABI
-// (engine.hip and the engine_*.hip units by stage — match, ekf, assoc, sight, fov, resample —, the pf_session*.hip units, comm.hip, mapper.hip).  Not part of the public interface.
+// (engine.hip and the engine_*.hip units by stage — match, ekf, assoc, sight, fov, merge, resample —, the pf_session*.hip units, comm.hip, mapper.hip).  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -103,6 +103,7 @@ struct slam_engine {
     int sight_bins = 0;
     int64_t sight_launches[2] = { 0, 0 };   // slam_sight_counts: table launches, stage launches (in no other counter)
     int64_t fov_launches = 0;               // slam_fov_counts: launches of the stage with a field of view (in no other counter)
+    int64_t merge_launches = 0;             // slam_merge_count: launches of the merge stage (in no other counter)
     // the detector (slam_detect_scan_dev): its kernel writes det_buf and leaves {ndet, sequence} in mapped host memory; until the
     // next stage that needs the count on the host has picked it up (slam_engine_resolve_detections) it is PENDING
     int32_t* h_det = nullptr;

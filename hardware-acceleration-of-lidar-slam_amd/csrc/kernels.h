@@ -1,5 +1,5 @@
 // kernels.h — launchers of the gfx950 kernels, one section per kernel file in the Makefile's order; called by the C-ABI layer
-// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_sight / engine_fov / engine_resample.hip by stage), the particle-filter session (the pf_session*.hip units) and the mapper (mapper.hip).
+// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_sight / engine_fov / engine_merge / engine_resample.hip by stage), the particle-filter session (the pf_session*.hip units) and the mapper (mapper.hip).
 // Every launcher enqueues on `stream` and returns the hipError_t of the launch; none synchronises.
 #pragma once
 
@@ -313,6 +313,28 @@ bool fov_bounds_ok(float lo, float hi);
 // hidden; sg.bins and sg.margin are not read, sg.th is, sg.spared is written 0).  The same grid, lanes and byte paths
 hipError_t launch_landmark_evidence_fov(hipStream_t stream, const EvidenceArgs& a, const SightArgs& sg, const FovArgs& fv,
                                         const EventPair* ev = nullptr);
+// ---- merge_kernels.hip: merging duplicate landmarks (specification: tests/_merge_spec.py).  Behind the
+// frame's associating update (and its evidence stage), in place: a seen landmark the frame's table does not name (free) that lies
+// within merge_gate — the Mahalanobis term of mu_l - mu_w under P_l + P_w — of a landmark it names (an anchor) is fused into it.
+struct MergeArgs {
+    float* map;            // rows as in EkfArgs, AFTER the frame's update: read, and written where a pair is merged
+    int64_t row_stride;
+    int plane_stride;
+    int nlandmarks;        // <= SLAM_MAX_OBS
+    int n;
+    const uint8_t* assoc;  // [n][assoc_stride] the frame's table
+    int assoc_stride;      // >= nlandmarks
+    int ndet;              // K: a table byte < K names an anchor
+    uint8_t* ev;           // [n][ev_stride] evidence bytes, in place; nullptr: without evidence (ev_stride and cmax are not read)
+    int ev_stride;         // >= nlandmarks
+    int cmax;              // 1 .. 255
+    float gate;            // finite, > 0
+    int32_t* stats;        // [n][3] merged, refused, seen after the stage; may be nullptr
+    int xcd_chunk;         // set by the launcher
+};
+bool merge_args_ok(const MergeArgs& a);
+// one wavefront per particle; the table's bytes as dwords when every row of it starts on a dword, else as bytes
+hipError_t launch_landmark_merge(hipStream_t stream, const MergeArgs& a, const EventPair* ev = nullptr);
 // ---- detect_kernels.hip: the landmark detector (specification: tests/_detect_spec.py).  The scan's short,
 // narrow, unoccluded runs of points between two range jumps become the frame's detections: their centroids, in scan order.
 // fit (specification: tests/_detect_fit_spec.py): the runs that are no more spread out than a circle of the given radius, each

@@ -167,6 +167,10 @@ struct slam_pf {
     bool fov_on = false;
     float fov_lo = 0.0f, fov_hi = 4.0f;      // slam_fov_bound(angle_min + edge), slam_fov_bound(angle_max - edge)
     int32_t* fov_outside = nullptr;          // [n] landmarks due a miss outside the arc (the last frame that ran the stage); made at the first switch-on
+    // slam_pf_merge_set (only while association is on): behind the update and the evidence stage of every observing frame,
+    // slam_landmark_merge_dev on the row (and, while pruning is on, the evidence buffer) that frame wrote
+    float merge_gate = 0.0f;                 // 0: off
+    int32_t* merge_stats = nullptr;          // [n][3] merged, refused, seen after (the last frame that ran the stage); made at the first switch-on
     // slam_pf_detect_set (only while association is on): every observing frame makes its detections from the engine's scan
     // (slam_detect_scan_dev), issued in front of the frame's first launch
     bool detect_on = false;

@@ -197,6 +197,7 @@ int slam_pf_destroy(slam_pf* pf)
     if (pf->ev[0]) (void)hipFree(pf->ev[0]);           // (the second buffer and the stats live behind the first)
     if (pf->sight_spared) (void)hipFree(pf->sight_spared);
     if (pf->fov_outside) (void)hipFree(pf->fov_outside);
+    if (pf->merge_stats) (void)hipFree(pf->merge_stats);
     free_page_tables(pf);
     free_split_tables(pf);
     for (void* p : { (void*)pf->score, (void*)pf->logw, (void*)pf->count, (void*)pf->first, (void*)pf->pose_all, (void*)pf->pose_stage, (void*)pf->first_all,
@@ -353,6 +354,7 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
         pf->prune_on = false;
         pf->sight_bins = 0;
         pf->fov_on = false;
+        pf->merge_gate = 0.0f;
         pf->detect_on = false;
         pf->detect_fit_on = false;
         pf->detect_noise_on = false;
@@ -509,6 +511,33 @@ int slam_pf_prune_fov_set(slam_pf* pf, int on, float angle_min, float angle_max,
     pf->fov_lo = slam_fov_bound(from);
     pf->fov_hi = slam_fov_bound(to);
     pf->fov_on = true;
+    return SLAM_OK;
+}
+
+int slam_pf_merge_set(slam_pf* pf, float merge_gate)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (merge_gate == 0.0f) {   // off: the session runs exactly what it ran before the first call
+        pf->merge_gate = 0.0f;
+        return SLAM_OK;
+    }
+    if (!pf->assoc_on) {   // (accepted where slam_pf_prune_set is; under any of the three noise forms)
+        snprintf(e->err, sizeof e->err, "merging reads the frame's association table: it needs data association switched on "
+                                        "(slam_pf_assoc_set: the row layout on one GPU, not sharded)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (!(merge_gate > 0.0f && merge_gate <= FLT_MAX)) {
+        snprintf(e->err, sizeof e->err, "merging needs a finite merge_gate > 0 (0 switches it off)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    if (!pf->merge_stats) {   // once, at the switch — never inside a frame
+        const size_t st = (size_t)pf->n * 3 * sizeof(int32_t);
+        SLAM_HIP_TRY(e, dev_alloc((void**)&pf->merge_stats, st));
+        SLAM_HIP_TRY(e, hipMemsetAsync(pf->merge_stats, 0, st, e->stream));
+    }
+    pf->merge_gate = merge_gate;
     return SLAM_OK;
 }
 

@@ -343,6 +343,12 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
                                                         pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit, pf->prune_miss,
                                                         pf->prune_cmax, pf->prune_range, pf->ev_stats))
                     return rc;
+            // duplicates: behind the update and the evidence stage, in place on the row and the evidence buffer this frame wrote
+            if (pf->merge_gate != 0.0f)
+                if (int rc = slam_landmark_merge_dev(e, out, stride, pf->Lp, L, n, pf->assoc_tab, pf->Lp,
+                                                     pf->prune_on ? pf->ev[f.in_place ? mc : mn] : nullptr, pf->Lp, pf->prune_cmax,
+                                                     pf->merge_gate, pf->merge_stats))
+                    return rc;
         } else if (!f.fused) {
             if (int rc = slam_engine_ekf_update(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, noise, nullptr, nullptr))
                 return rc;

@@ -364,6 +364,14 @@ int slam_pf_fov_device_view(slam_pf* pf, float bounds[2], const int32_t** outsid
     return SLAM_OK;
 }
 
+int slam_pf_merge_device_view(slam_pf* pf, const int32_t** stats)
+{
+    if (!pf || !stats) return SLAM_ERR_INVALID_ARG;
+    if (!pf->merge_stats) return SLAM_ERR_NOT_READY;   // slam_pf_merge_set never switched merging on
+    *stats = pf->merge_stats;
+    return SLAM_OK;
+}
+
 int slam_pf_get_evidence_host(slam_pf* pf, uint8_t* ev)
 {
     if (!pf || !ev) return SLAM_ERR_INVALID_ARG;

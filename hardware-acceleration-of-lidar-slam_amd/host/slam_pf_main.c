@@ -20,7 +20,7 @@
  *
  * usage: slam_pf_main dataset.csv frames beams map_out.csv particles [seed [mean|best]]
  *                     [--gpus N] [--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]]
- *                     [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]]
+ *                     [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]]
  *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
  *                     [--landmarks-out FILE]]
  *   particles      the whole population (a multiple of N)
@@ -39,6 +39,9 @@
  *                  power of two in 32 .. 1024; nearer than the landmark by more than MARGIN metres) takes no miss (slam_pf_prune_sight_set)
  *   --prune-fov EDGE  only with --prune: a landmark whose direction lies outside the lidar's arc — the first to the last beam angle
  *                  of the scan, narrowed by EDGE >= 0 radians at both ends — takes no miss (slam_pf_prune_fov_set)
+ *   --merge GATE   only with --assoc: behind every frame's update a landmark that took no detection and lies within GATE (the
+ *                  Mahalanobis term under the sum of the two covariances) of one that took one is fused into it and its slot
+ *                  freed — duplicates of one pole become one landmark (slam_pf_merge_set)
  *   --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]  the detector (slam_pf_detect_set; no values: slam_detect_params_default):
  *                  every frame makes its detections from its own scan, so the landmark map grows from nothing but lidar frames
  *   --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]  only with --assoc and --detect: the detector's noise model
@@ -86,6 +89,8 @@ typedef struct {
     float sight_margin;
     int use_fov;           /* --prune-fov EDGE: only with --prune */
     float fov_edge;
+    int use_merge;         /* --merge GATE: only with --assoc */
+    float merge_gate;
     int use_detect;        /* --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] */
     slam_detect_params detect;
     int use_fit;           /* --pole-radius R [TOL] */
@@ -173,6 +178,7 @@ static void *rank_main(void *arg)
     if (run->use_assoc && !assoc_cov && run->use_noise) CHECK(slam_pf_assoc_detcov_set(pf, run->assoc_gate[0], run->assoc_gate[1], 1));
     if (run->use_prune) CHECK(slam_pf_prune_set(pf, run->prune[0], run->prune[1], run->prune[2], run->prune_range));
     if (run->use_sight) CHECK(slam_pf_prune_sight_set(pf, run->sight_bins, run->sight_margin));
+    if (run->use_merge) CHECK(slam_pf_merge_set(pf, run->merge_gate));
     if (run->use_detect) CHECK(slam_pf_detect_noise_set(pf, &run->detect, run->use_fit ? &run->fit : NULL, run->use_noise ? &run->noise : NULL));
     const int observe = run->landmarks > 0 && run->use_assoc && run->use_detect;   /* else: no frame has observations */
     if (fe_scan_init(&scan, beams, -2.351831f, 0.004363f) || fe_points_init(&map, FE_MAP_CAPACITY + beams) ||
@@ -356,6 +362,15 @@ int main(int argc, char **argv)
                 return 2;
             }
         }
+        else if (!strcmp(argv[a], "--merge") && a + 1 < argc) {
+            char *end = NULL;
+            run.use_merge = 1;
+            run.merge_gate = strtof(argv[++a], &end);
+            if (end == argv[a] || *end || !isfinite(run.merge_gate) || run.merge_gate <= 0.0f) {
+                fprintf(stderr, "--merge %s: GATE must be a finite number > 0\n", argv[a]);
+                return 2;
+            }
+        }
         else if (!strcmp(argv[a], "--detect")) {
             run.use_detect = 1;
             slam_detect_params_default(&run.detect);
@@ -392,11 +407,11 @@ int main(int argc, char **argv)
     }
     const int landmark_options = run.use_assoc || run.use_prune || run.use_detect || run.landmarks_out != NULL;
     if (npos < 5 || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
-        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) ||
+        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) ||
         (run.use_noise && (!run.use_detect || !run.use_assoc || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
-                        "  [--landmarks L [--assoc GATE NEW_GATE [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
+                        "  [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
                         "[--landmarks-out FILE]]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
                         "              without --landmarks; with --landmarks and --assoc the association gates and updates under it\n"
@@ -406,6 +421,8 @@ int main(int argc, char **argv)
                         "              two in 32 .. 1024; nearer by more than MARGIN metres) takes no miss\n"
                         "  --prune-fov EDGE: only with --prune; a landmark outside the lidar's arc (first to last beam angle, narrowed by EDGE\n"
                         "              radians at both ends) takes no miss\n"
+                        "  --merge GATE: only with --assoc; a landmark that took no detection within GATE (Mahalanobis, under the sum of the two\n"
+                        "              covariances) of one that took one is fused into it and its slot freed: duplicates of a pole become one\n"
                         "  --pole-radius R [TOL]: only with --detect; a detection is the centre of the circle of radius R fitted to its segment,\n"
                         "              and segments more spread out than that circle (by more than TOL, default 0) are dropped\n"
                         "  --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --assoc and --detect, not with --meas-cov; every detection\n"

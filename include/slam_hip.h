@@ -507,6 +507,44 @@ int slam_landmark_evidence_fov_dev(slam_engine *e, float *d_map, int64_t row_str
                                    int32_t *d_stats /* [n][2], may be NULL */, int32_t *d_spared /* [n], may be NULL */,
                                    int32_t *d_outside /* [n], may be NULL */);
 int slam_fov_counts(slam_engine *e, int64_t *launches);        /* stage launches */
+/* MERGING DUPLICATE LANDMARKS: the counterpart of creation.  A gate tight enough for the short axis of an elongated covariance
+ * starts a second landmark on a pole that has one; from then on the two slots take turns winning the pole's detection and split
+ * its measurements between two half-converged estimates.  Within ONE particle a detection updates exactly one landmark, so two
+ * slots on one pole were fed disjoint measurement sets: given the particle's path they are independent estimates of one point,
+ * and their product is the posterior — the fusion below is exact per particle, not a heuristic.
+ * slam_landmark_merge_dev runs behind the frame's associating update (and behind its evidence stage), IN PLACE on the row the
+ * update wrote ([n] rows of the layout of slam_ekf_update_dev, slots l < nlandmarks), with the frame's table d_assoc, K = the
+ * engine's current detection count and, optionally, the evidence bytes d_ev:
+ *   roles     seen = !(P_xx < 0).  ANCHOR: seen and a_l < K (matched or created this frame).  FREE: seen and not a_l < K.  A table
+ *             names a detection at most once, so a particle has at most K <= 64 anchors (of a table that does not, the anchors
+ *             behind the 64th in ascending l take no part).  Two anchors are never merged: the detector saw two objects.
+ *   choice 1  a free l, over the anchors w in ascending w: d = mu_l - mu_w, S = P_l + P_w element by element, m = d^T S^-1 d in
+ *             the operation order of the association's cost with S in the place of P + q I; strict < from +inf — the lowest w on
+ *             ties, NaN never wins.  l is a candidate iff 0 <= m <= merge_gate.
+ *   choice 2  an anchor absorbs, of the candidates that chose it, the one with the smallest m (the lowest l on ties) — ONE per
+ *             frame; the others wait for the next frame.
+ *   fusion    the general-covariance update (slam_ekf_update_aniso_dev's arithmetic) of the anchor with mu_l as the observed
+ *             point and P_l as the noise: mu' = mu_l - P_l S^-1 (mu_l - mu_w), P' = (det P_w * P_l + det P_l * P_w) / det S.
+ *             No likelihood term.
+ *   guard     REFUSED — counted, nothing written — unless the five fused values are finite, P'_xx > 0, P'_yy > 0 and
+ *             P'_xx P'_yy - P'_xy^2 > 0 in float32: a merge never writes a covariance that is negative or not finite into an
+ *             anchor (P_xx < 0 would silently turn it into an unused slot).
+ *   result    the anchor takes the fused values; the five planes of slot l become 0, 0, -1, 0, 0 (a slot that was never used,
+ *             as in pruning); with evidence c_w' = min(c_w + c_l, cmax) in integers and c_l' = 0.  Padding columns are never
+ *             written.
+ * d_stats (may be NULL) is int32 [n][3] = merged, refused, seen after the stage.  Operation order: tests/_merge_spec.py.
+ * KNOWN LIMITS: one absorption per anchor and frame; anchors are never merged with anchors (two slots that were both matched
+ * or created this frame stay two); rows on one GPU only.
+ * Errors, nothing launched: SLAM_ERR_INVALID_ARG for a merge_gate that is not finite or <= 0, plane_stride or assoc_stride <
+ * nlandmarks, row_stride < 5 * plane_stride, nlandmarks > SLAM_MAX_OBS, n < 0, a null d_map or d_assoc, and — when d_ev is given —
+ * ev_stride < nlandmarks or cmax outside 1 .. 255 (d_ev == NULL: ev_stride and cmax are not read); SLAM_ERR_NOT_READY when no
+ * detections were handed over.  No detections in the frame (K = 0) is legal: no anchors, nothing happens, seen is counted.  The
+ * launch is bracketed as SLAM_PROF_PAGES and counted by slam_merge_count — in no other counter. */
+int slam_landmark_merge_dev(slam_engine *e, float *d_map, int64_t row_stride, int plane_stride, int nlandmarks, int n,
+                            const uint8_t *d_assoc, int assoc_stride,
+                            uint8_t *d_ev /* may be NULL */, int ev_stride, int cmax, float merge_gate,
+                            int32_t *d_stats /* [n][3], may be NULL */);
+int slam_merge_count(slam_engine *e, int64_t *launches);       /* stage launches */
 /* THE DETECTOR: the detections of a frame made on the device from the engine's current scan (slam_scan_upload_host / _set_dev),
  * P = nbeams points in scan order — what fe_clean left, so a removed beam leaves no hole and the rule uses distances only, never
  * beam angles.  With jump2 = jump * jump, guard2, width2 and range2 likewise (each rounded once to float32), and every step below
@@ -965,6 +1003,19 @@ int slam_pf_sight_device_view(slam_pf *pf, const float **table, int32_t *bins, c
  * indexed like slam_pf_view.score) of the last frame that ran the stage.  SLAM_ERR_NOT_READY until it was switched on. */
 int slam_pf_prune_fov_set(slam_pf *pf, int on, float angle_min, float angle_max, float edge);
 int slam_pf_fov_device_view(slam_pf *pf, float bounds[2], const int32_t **outside);
+/* Merging inside the session (slam_landmark_merge_dev).  merge_gate == 0 switches it off, and so does slam_pf_assoc_set(gate =
+ * 0); with it off the session runs exactly what it ran before the first call, launch for launch, and slam_merge_count does not
+ * move.  Accepted only while association is on — under any of its three noise forms (slam_pf_assoc_set, slam_pf_assoc_cov_set,
+ * slam_pf_assoc_detcov_set): the rule reads only the landmarks' own covariances — otherwise SLAM_ERR_INVALID_ARG (slam_last_error
+ * says why), as slam_pf_prune_set refuses: split, paged, AUTO and sharded sessions never get there.  SLAM_ERR_INVALID_ARG too for a
+ * gate that is not finite or < 0.  A refused call leaves the session unchanged.  In force, every frame with use_observations runs
+ * the stage behind its update and its evidence stage, on the rows that frame wrote (the other map buffer, or in place on a frame
+ * a gated session kept) and — while pruning is on — on the evidence buffer it wrote with the pruning's cmax; with pruning off,
+ * without evidence.  Switching on allocates (once) the stats; no frame allocates.
+ * slam_pf_merge_device_view: the stats ([n_particles][3] = merged, refused, seen after; indexed like slam_pf_view.score) of the
+ * last frame that ran the stage.  SLAM_ERR_NOT_READY until merging was switched on. */
+int slam_pf_merge_set(slam_pf *pf, float merge_gate /* 0: off */);
+int slam_pf_merge_device_view(slam_pf *pf, const int32_t **stats);
 /* The detector inside the session (slam_detect_scan_dev with these parameters; NULL: off).  Accepted only while association is on
  * — otherwise SLAM_ERR_INVALID_ARG (slam_last_error says why) and the session goes on as before; likewise for parameters that
  * slam_detect_scan_dev refuses.  slam_pf_assoc_set(gate = 0) switches it off too.  With it on, every frame with use_observations
