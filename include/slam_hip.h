@@ -934,7 +934,13 @@ int slam_pf_meas_cov_set(slam_pf *pf, const float meas_cov[3]);
  * return SLAM_ERR_INVALID_ARG (slam_last_error says why) and go on as before; setting a 2x2 covariance while association is
  * on is refused likewise.  gate == 0 (new_gate and create are then ignored) returns the session to exactly what it ran before.
  * slam_pf_assoc_device_view: the table ([n_particles][*assoc_stride] bytes) and stats ([n_particles][3]) of the last such
- * frame, indexed like slam_pf_view.score (BEFORE the pending gather); SLAM_ERR_NOT_READY until association was switched on. */
+ * frame, indexed like slam_pf_view.score (BEFORE the pending gather); SLAM_ERR_NOT_READY until association was switched on.
+ * The noise form given anew: a call with gate > 0 — this one, slam_pf_assoc_cov_set or slam_pf_assoc_detcov_set, which both go
+ * through it — on a session that already associates changes the noise form and the gates and NOTHING else: pruning and its
+ * evidence bytes, line of sight, field of view, merging and the detector (slam_pf_prune_set, slam_pf_prune_sight_set,
+ * slam_pf_prune_fov_set, slam_pf_merge_set, slam_pf_detect_*_set) stay as they were.  Only gate == 0 clears them, all of them;
+ * switched on again afterwards the session runs as a fresh one would from its poses and maps (slam_pf_prune_set makes the
+ * evidence from the maps again).  tests/_pipeline_spec.py states this, and tests/test_gpu_pipeline_session.py holds the session to it. */
 int slam_pf_assoc_set(slam_pf *pf, float gate, float new_gate, int create);
 int slam_pf_assoc_device_view(slam_pf *pf, const uint8_t **assoc, int32_t *assoc_stride, const int32_t **stats);
 /* Data association under a 2x2 measurement covariance inside the session: ONE switch that sets covariance and gates together
