@@ -143,6 +143,13 @@ SIGNATURES = {
     "slam_fov_counts": (_i, [_vp, _vp]),
     "slam_landmark_merge_dev": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp]),
     "slam_merge_count": (_i, [_vp, _vp]),
+    "slam_landmark_evidence_missed_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "slam_landmark_evidence_sight_missed_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f,
+                                                     _vp, _vp, _vp]),
+    "slam_landmark_evidence_fov_missed_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _f, _f,
+                                                   _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "slam_assoc_weight_dev": (_i, [_vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
+    "slam_assoc_weight_count": (_i, [_vp, _vp]),
     "slam_detect_params_default": (None, [_vp]),
     "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
     "slam_detect_count": (_i, [_vp, _vp]),
@@ -202,6 +209,8 @@ SIGNATURES = {
     "slam_pf_fov_device_view": (_i, [_vp, _vp, _vp]),
     "slam_pf_merge_set": (_i, [_vp, _f]),
     "slam_pf_merge_device_view": (_i, [_vp, _vp]),
+    "slam_pf_assoc_weight_set": (_i, [_vp, _f, _f, _f, _i]),
+    "slam_pf_assoc_weight_device_view": (_i, [_vp, _vp, _vp]),
     "slam_pf_detect_set": (_i, [_vp, _vp]),
     "slam_pf_detect_fit_set": (_i, [_vp, _vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
@@ -559,9 +568,16 @@ class Engine:
         return int(c[0]), int(c[1])
 
     def landmark_evidence_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_anc, n, d_assoc, assoc_stride, d_ev_in,
-                              d_ev_out, ev_stride, hit, miss, cmax, view_range, d_stats):
+                              d_ev_out, ev_stride, hit, miss, cmax, view_range, d_stats, d_missed=None):
         """``slam_landmark_evidence_dev``: the evidence bytes uint8 [n][ev_stride] behind a frame's associating update; pruned
-        landmarks' slots in d_map become unused ones; stats int32 [n][2] = pruned, seen after pruning."""
+        landmarks' slots in d_map become unused ones; stats int32 [n][2] = pruned, seen after pruning.  d_missed (int32 [n]: the
+        slots scored as a miss): ``slam_landmark_evidence_missed_dev``."""
+        if d_missed is not None:
+            self._ck(self.lib.slam_landmark_evidence_missed_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x),
+                                                                _ptr(d_y), _ptr(d_anc), n, _ptr(d_assoc), assoc_stride, _ptr(d_ev_in),
+                                                                _ptr(d_ev_out), ev_stride, int(hit), int(miss), int(cmax), view_range,
+                                                                _ptr(d_stats), _ptr(d_missed)), "landmark_evidence_missed_dev")
+            return
         self._ck(self.lib.slam_landmark_evidence_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x), _ptr(d_y),
                                                      _ptr(d_anc), n, _ptr(d_assoc), assoc_stride, _ptr(d_ev_in), _ptr(d_ev_out),
                                                      ev_stride, int(hit), int(miss), int(cmax), view_range, _ptr(d_stats)),
@@ -583,9 +599,17 @@ class Engine:
         return t[:bins.value].copy()
 
     def landmark_evidence_sight_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, d_assoc, assoc_stride,
-                                    d_ev_in, d_ev_out, ev_stride, hit, miss, cmax, view_range, margin, d_stats, d_spared):
+                                    d_ev_in, d_ev_out, ev_stride, hit, miss, cmax, view_range, margin, d_stats, d_spared, d_missed=None):
         """``slam_landmark_evidence_sight_dev``: landmark_evidence_dev in which a landmark behind what the engine's sight table
-        holds in its direction takes no miss; spared int32 [n] = the landmarks spared one."""
+        holds in its direction takes no miss; spared int32 [n] = the landmarks spared one.  d_missed:
+        ``slam_landmark_evidence_sight_missed_dev``."""
+        if d_missed is not None:
+            self._ck(self.lib.slam_landmark_evidence_sight_missed_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x),
+                                                                      _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, _ptr(d_assoc), assoc_stride,
+                                                                      _ptr(d_ev_in), _ptr(d_ev_out), ev_stride, int(hit), int(miss),
+                                                                      int(cmax), view_range, margin, _ptr(d_stats), _ptr(d_spared),
+                                                                      _ptr(d_missed)), "landmark_evidence_sight_missed_dev")
+            return
         self._ck(self.lib.slam_landmark_evidence_sight_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x),
                                                            _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, _ptr(d_assoc), assoc_stride,
                                                            _ptr(d_ev_in), _ptr(d_ev_out), ev_stride, int(hit), int(miss), int(cmax),
@@ -600,9 +624,18 @@ class Engine:
 
     def landmark_evidence_fov_dev(self, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, d_assoc, assoc_stride,
                                   d_ev_in, d_ev_out, ev_stride, hit, miss, cmax, view_range, margin, lo, hi, use_sight, d_stats, d_spared,
-                                  d_outside):
+                                  d_outside, d_missed=None):
         """``slam_landmark_evidence_fov_dev``: landmark_evidence_sight_dev (use_sight) or landmark_evidence_dev in which a landmark
-        due a miss whose diamond angle in the sensor frame lies outside [lo, hi] takes none; outside int32 [n] = those landmarks."""
+        due a miss whose diamond angle in the sensor frame lies outside [lo, hi] takes none; outside int32 [n] = those landmarks.
+        d_missed: ``slam_landmark_evidence_fov_missed_dev``."""
+        if d_missed is not None:
+            self._ck(self.lib.slam_landmark_evidence_fov_missed_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x),
+                                                                    _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, _ptr(d_assoc), assoc_stride,
+                                                                    _ptr(d_ev_in), _ptr(d_ev_out), ev_stride, int(hit), int(miss),
+                                                                    int(cmax), view_range, margin, lo, hi, int(bool(use_sight)),
+                                                                    _ptr(d_stats), _ptr(d_spared), _ptr(d_outside), _ptr(d_missed)),
+                     "landmark_evidence_fov_missed_dev")
+            return
         self._ck(self.lib.slam_landmark_evidence_fov_dev(self.h, _ptr(d_map), row_stride, plane_stride, nlandmarks, _ptr(d_x),
                                                          _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, _ptr(d_assoc), assoc_stride,
                                                          _ptr(d_ev_in), _ptr(d_ev_out), ev_stride, int(hit), int(miss), int(cmax),
@@ -629,6 +662,18 @@ class Engine:
         """-> the launches of the merge stage of this engine so far."""
         c = C.c_int64(0)
         self._ck(self.lib.slam_merge_count(self.h, C.byref(c)), "merge_count")
+        return int(c.value)
+
+    def assoc_weight_dev(self, d_stats, d_missed, n, log_new, log_clutter, log_miss, d_loglik=None, d_terms=None):
+        """``slam_assoc_weight_dev``: loglik[i] += created_i * log_new + dropped_i * log_clutter + missed_i * log_miss (d_stats: the
+        association's int32 [n][3]; d_missed None: 0; d_loglik None: the engine's buffer; d_terms: the sum that was added)."""
+        self._ck(self.lib.slam_assoc_weight_dev(self.h, _ptr(d_stats), _ptr(d_missed), n, log_new, log_clutter, log_miss, _ptr(d_loglik),
+                                                _ptr(d_terms)), "assoc_weight_dev")
+
+    def assoc_weight_count(self):
+        """-> the launches of slam_assoc_weight_dev of this engine so far."""
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_assoc_weight_count(self.h, C.byref(c)), "assoc_weight_count")
         return int(c.value)
 
     def detect_scan_dev(self, params: "DetectParams | None" = None, d_stats=None, **kw):
@@ -1260,6 +1305,18 @@ class PfSession:
         st = C.c_void_p()
         self.e._ck(self.e.lib.slam_pf_merge_device_view(self.h, C.byref(st)), "pf_merge_device_view")
         return DeviceArray(st.value, (self.n, 3), "<i4", self)
+
+    def assoc_weight_set(self, log_new: float = 0.0, log_clutter: float = 0.0, log_miss: float = 0.0, on: bool = True):
+        """``slam_pf_assoc_weight_set``: every observing frame adds created * log_new + dropped * log_clutter + missed * log_miss
+        to its log-likelihood in front of the weights (only while association is on; each constant finite and <= 0)."""
+        self.e._ck(self.e.lib.slam_pf_assoc_weight_set(self.h, log_new, log_clutter, log_miss, int(bool(on))), "pf_assoc_weight_set")
+
+    def assoc_weight_view(self):
+        """``slam_pf_assoc_weight_device_view``: of the last frame that ran the stage -> (missed int32 [n] or None while pruning is
+        off, terms float32 [n])."""
+        ms, tm = C.c_void_p(), C.c_void_p()
+        self.e._ck(self.e.lib.slam_pf_assoc_weight_device_view(self.h, C.byref(ms), C.byref(tm)), "pf_assoc_weight_device_view")
+        return (DeviceArray(ms.value, (self.n,), "<i4", self) if ms.value else None), DeviceArray(tm.value, (self.n,), "<f4", self)
 
     def detect_set(self, params: "DetectParams | None | bool" = True, **kw):
         """``slam_pf_detect_set``: observing frames make their detections from the engine's scan (only while association is on).

@@ -394,6 +394,15 @@ int slam_landmark_evidence_dev(slam_engine* e, float* d_map, int64_t row_stride,
                                const uint8_t* d_ev_in, uint8_t* d_ev_out, int ev_stride, int hit, int miss, int cmax, float view_range,
                                int32_t* d_stats)
 {
+    return slam_landmark_evidence_missed_dev(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_anc, n, d_assoc, assoc_stride, d_ev_in,
+                                             d_ev_out, ev_stride, hit, miss, cmax, view_range, d_stats, nullptr);
+}
+
+int slam_landmark_evidence_missed_dev(slam_engine* e, float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                                      const float* d_y, const int32_t* d_anc, int n, const uint8_t* d_assoc, int assoc_stride,
+                                      const uint8_t* d_ev_in, uint8_t* d_ev_out, int ev_stride, int hit, int miss, int cmax,
+                                      float view_range, int32_t* d_stats, int32_t* d_missed)
+{
     SLAM_ENTER(e);
     if (int rc = slam_engine_resolve_detections(e)) return rc;
     if (n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
@@ -423,6 +432,7 @@ int slam_landmark_evidence_dev(slam_engine* e, float* d_map, int64_t row_stride,
     a.cmax = cmax;
     a.range2 = view_range * view_range;   // one float32 product (-ffp-contract=off)
     a.stats = d_stats;
+    a.missed = d_missed;
     a.xcd_chunk = 0;
     SLAM_HIP_TRY(e, launch_landmark_evidence(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
     e->evidence_launches[0]++;
@@ -467,6 +477,30 @@ int slam_evidence_gather_dev(slam_engine* e, const uint8_t* d_in, uint8_t* d_out
     if (n < 0 || ev_stride < 0 || (n > 0 && ev_stride > 0 && (!d_in || !d_out || !d_anc || d_in == d_out))) return SLAM_ERR_INVALID_ARG;
     const ProfScope prof(e, SLAM_PROF_PAGES);
     SLAM_HIP_TRY(e, launch_evidence_gather(e->stream, d_in, d_out, ev_stride, d_anc, n));
+    return SLAM_OK;
+}
+
+/* ------------------------------------------------------------------ what the association leaves unexplained (assoc_weight_kernels.hip) */
+
+int slam_assoc_weight_dev(slam_engine* e, const int32_t* d_stats, const int32_t* d_missed, int n, float log_new, float log_clutter,
+                          float log_miss, float* d_loglik, float* d_terms)
+{
+    SLAM_ENTER(e);
+    if (n < 0 || !d_stats || !assoc_weight_const_ok(log_new) || !assoc_weight_const_ok(log_clutter) || !assoc_weight_const_ok(log_miss))
+        return SLAM_ERR_INVALID_ARG;
+    if (n == 0) return SLAM_OK;
+    if (!d_loglik && e->ll_n != n) return SLAM_ERR_NOT_READY;   // needs the landmark update of n particles on this engine first
+    const AssocWeightArgs a{ d_stats, d_missed, n, log_new, log_clutter, log_miss, d_loglik ? d_loglik : e->ll_buf.as<float>(), d_terms };
+    SLAM_HIP_TRY(e, launch_assoc_weight(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
+    e->assoc_weight_launches++;
+    return SLAM_OK;
+}
+
+int slam_assoc_weight_count(slam_engine* e, int64_t* launches)
+{
+    SLAM_ENTER(e);
+    if (!launches) return SLAM_ERR_INVALID_ARG;
+    *launches = e->assoc_weight_launches;
     return SLAM_OK;
 }
 

@@ -26,6 +26,17 @@ int slam_landmark_evidence_fov_dev(slam_engine* e, float* d_map, int64_t row_str
                                    float view_range, float margin, float lo, float hi, int use_sight, int32_t* d_stats, int32_t* d_spared,
                                    int32_t* d_outside)
 {
+    return slam_landmark_evidence_fov_missed_dev(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, d_assoc, assoc_stride,
+                                                 d_ev_in, d_ev_out, ev_stride, hit, miss, cmax, view_range, margin, lo, hi, use_sight, d_stats,
+                                                 d_spared, d_outside, nullptr);
+}
+
+int slam_landmark_evidence_fov_missed_dev(slam_engine* e, float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
+                                          const float* d_y, const float* d_th, const int32_t* d_anc, int n, const uint8_t* d_assoc,
+                                          int assoc_stride, const uint8_t* d_ev_in, uint8_t* d_ev_out, int ev_stride, int hit, int miss,
+                                          int cmax, float view_range, float margin, float lo, float hi, int use_sight, int32_t* d_stats,
+                                          int32_t* d_spared, int32_t* d_outside, int32_t* d_missed)
+{
     SLAM_ENTER(e);
     if (int rc = slam_engine_resolve_detections(e)) return rc;
     const float big = std::numeric_limits<float>::max();
@@ -56,6 +67,7 @@ int slam_landmark_evidence_fov_dev(slam_engine* e, float* d_map, int64_t row_str
     a.cmax = cmax;
     a.range2 = view_range * view_range;   // one float32 product (-ffp-contract=off)
     a.stats = d_stats;
+    a.missed = d_missed;
     a.xcd_chunk = 0;
     const SightArgs sg{ d_th, use_sight ? e->sight_buf.as<float>() : nullptr, use_sight ? e->sight_bins : 0, use_sight ? margin : 0.0f, d_spared };
     const FovArgs fv{ lo, hi, d_outside };

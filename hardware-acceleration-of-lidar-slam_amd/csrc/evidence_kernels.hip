@@ -44,7 +44,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_kernel(EvidenceArgs a
     // WIDE: the dwords that are stored — out of place every one of the row, in place those that hold a landmark
     const unsigned store_dw = in_place ? (L + 3u) / 4u : ev_dw;
     const unsigned batches = (L + 127u) / 128u;
-    int npruned = 0, nseen = 0;
+    int npruned = 0, nseen = 0, nmissed = 0;
     for (unsigned b = 0; b < batches; ++b) {
         unsigned tk[2], c[2];
         if (WIDE) {
@@ -94,14 +94,18 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_kernel(EvidenceArgs a
             if (!WIDE && in[t]) cout[l[t]] = (uint8_t)cn[t];
             npruned += __popcll(__ballot(prune));
             nseen += __popcll(__ballot(seen && !prune));
+            nmissed += __popcll(__ballot(missed));
         }
         if (WIDE) batch_store((guint*)cout, b, lane, cn[0], cn[1], store_dw);
     }
     if (!in_place) zero_tail<WIDE>(cout, WIDE ? batches * 128u : L, (unsigned)a.ev_stride, lane);
-    if (lane == 0 && a.stats) {
-        int32_t* st2 = a.stats + 2 * (size_t)i;
-        st2[0] = npruned;
-        st2[1] = nseen;
+    if (lane == 0) {
+        if (a.stats) {
+            int32_t* st2 = a.stats + 2 * (size_t)i;
+            st2[0] = npruned;
+            st2[1] = nseen;
+        }
+        if (a.missed) a.missed[i] = nmissed;
     }
 }
 

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_fov_kernel(EvidenceAr
     // WIDE: the dwords that are stored — out of place every one of the row, in place those that hold a landmark
     const unsigned store_dw = in_place ? (L + 3u) / 4u : ev_dw;
     const unsigned batches = (L + 127u) / 128u;
-    int npruned = 0, nseen = 0, nspared = 0, noutside = 0;
+    int npruned = 0, nseen = 0, nmissed = 0, nspared = 0, noutside = 0;
     for (unsigned b = 0; b < batches; ++b) {
         unsigned tk[2], c[2];
         if (WIDE) {
@@ -138,6 +138,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_fov_kernel(EvidenceAr
             if (!WIDE && in[t]) cout[l[t]] = (uint8_t)cn[t];
             npruned += __popcll(__ballot(prune));
             nseen += __popcll(__ballot(seen[t] && !prune));
+            nmissed += __popcll(__ballot(missed));
             if (SIGHT) nspared += __popcll(__ballot(hidden[t]));
             noutside += __popcll(__ballot(outside));
         }
@@ -150,6 +151,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_fov_kernel(EvidenceAr
             st2[0] = npruned;
             st2[1] = nseen;
         }
+        if (a.missed) a.missed[i] = nmissed;
         if (sg.spared) sg.spared[i] = nspared;
         if (fv.outside) fv.outside[i] = noutside;
     }

@@ -268,6 +268,7 @@ struct EvidenceArgs {
     int hit, miss, cmax;   // 1 .. 255
     float range2;          // view_range * view_range, one float32 product made on the host
     int32_t* stats;        // [n][2] pruned, seen after pruning; may be nullptr
+    int32_t* missed;       // [n] landmarks the stage scored as a miss (lowered or pruned), in whichever form runs; may be nullptr
     int xcd_chunk;         // set by the launcher
 };
 // one wavefront per particle; byte traffic as dwords when every row of the three byte arrays starts on a dword, else as bytes
@@ -335,6 +336,20 @@ struct MergeArgs {
 bool merge_args_ok(const MergeArgs& a);
 // one wavefront per particle; the table's bytes as dwords when every row of it starts on a dword, else as bytes
 hipError_t launch_landmark_merge(hipStream_t stream, const MergeArgs& a, const EventPair* ev = nullptr);
+// ---- assoc_weight_kernels.hip: the weight of what the association leaves unexplained (specification:
+// tests/_assoc_weight_spec.py).  Behind the frame's update, evidence stage and merge, in front of the weights:
+// loglik[i] += created_i * log_new + dropped_i * log_clutter + missed_i * log_miss, every operation rounded once.
+struct AssocWeightArgs {
+    const int32_t* stats;   // [n][3] the association's matched, created, dropped
+    const int32_t* missed;  // [n] EvidenceArgs::missed of the frame; nullptr: 0 (pruning off)
+    int n;
+    float log_new, log_clutter, log_miss;   // finite, <= 0
+    float* loglik;          // [n] read and written
+    float* terms;           // [n] the sum that was added; may be nullptr
+};
+bool assoc_weight_const_ok(float v);
+// one thread per particle
+hipError_t launch_assoc_weight(hipStream_t stream, const AssocWeightArgs& a, const EventPair* ev = nullptr);
 // ---- detect_kernels.hip: the landmark detector (specification: tests/_detect_spec.py).  The scan's short,
 // narrow, unoccluded runs of points between two range jumps become the frame's detections: their centroids, in scan order.
 // fit (specification: tests/_detect_fit_spec.py): the runs that are no more spread out than a circle of the given radius, each

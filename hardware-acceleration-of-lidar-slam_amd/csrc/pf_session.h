@@ -171,6 +171,12 @@ struct slam_pf {
     // slam_landmark_merge_dev on the row (and, while pruning is on, the evidence buffer) that frame wrote
     float merge_gate = 0.0f;                 // 0: off
     int32_t* merge_stats = nullptr;          // [n][3] merged, refused, seen after (the last frame that ran the stage); made at the first switch-on
+    // slam_pf_assoc_weight_set (only while association is on): the evidence stage of every observing frame also counts its misses,
+    // and slam_assoc_weight_dev runs behind the merge, in front of the weights, on the engine's log-likelihood buffer
+    bool assoc_weight_on = false;
+    float assoc_weight_log[3] = { 0.0f, 0.0f, 0.0f };   // log_new, log_clutter, log_miss
+    int32_t* assoc_weight_missed = nullptr;  // [n] the frame's misses, then (float) [n] the terms that were added; made at the first switch-on
+    float* assoc_weight_terms = nullptr;     // (behind the misses in the same allocation)
     // slam_pf_detect_set (only while association is on): every observing frame makes its detections from the engine's scan
     // (slam_detect_scan_dev), issued in front of the frame's first launch
     bool detect_on = false;

@@ -198,6 +198,7 @@ int slam_pf_destroy(slam_pf* pf)
     if (pf->sight_spared) (void)hipFree(pf->sight_spared);
     if (pf->fov_outside) (void)hipFree(pf->fov_outside);
     if (pf->merge_stats) (void)hipFree(pf->merge_stats);
+    if (pf->assoc_weight_missed) (void)hipFree(pf->assoc_weight_missed);   // (the terms live behind the misses)
     free_page_tables(pf);
     free_split_tables(pf);
     for (void* p : { (void*)pf->score, (void*)pf->logw, (void*)pf->count, (void*)pf->first, (void*)pf->pose_all, (void*)pf->pose_stage, (void*)pf->first_all,
@@ -355,6 +356,7 @@ int slam_pf_assoc_set(slam_pf* pf, float gate, float new_gate, int create)
         pf->sight_bins = 0;
         pf->fov_on = false;
         pf->merge_gate = 0.0f;
+        pf->assoc_weight_on = false;
         pf->detect_on = false;
         pf->detect_fit_on = false;
         pf->detect_noise_on = false;
@@ -538,6 +540,37 @@ int slam_pf_merge_set(slam_pf* pf, float merge_gate)
         SLAM_HIP_TRY(e, hipMemsetAsync(pf->merge_stats, 0, st, e->stream));
     }
     pf->merge_gate = merge_gate;
+    return SLAM_OK;
+}
+
+int slam_pf_assoc_weight_set(slam_pf* pf, float log_new, float log_clutter, float log_miss, int on)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (!on) {   // off: the session runs exactly what it ran before the first call
+        pf->assoc_weight_on = false;
+        return SLAM_OK;
+    }
+    if (!pf->assoc_on) {   // (accepted where slam_pf_merge_set is; under any of the three noise forms)
+        snprintf(e->err, sizeof e->err, "weighing what the association leaves unexplained reads the frame's association stats: it needs data "
+                                        "association switched on (slam_pf_assoc_set: the row layout on one GPU, not sharded)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (!assoc_weight_const_ok(log_new) || !assoc_weight_const_ok(log_clutter) || !assoc_weight_const_ok(log_miss)) {
+        snprintf(e->err, sizeof e->err, "log_new, log_clutter and log_miss are log-likelihoods of events: each must be finite and <= 0");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    if (!pf->assoc_weight_missed) {   // once, at the switch — never inside a frame
+        const size_t bytes = (size_t)pf->n * (sizeof(int32_t) + sizeof(float));
+        SLAM_HIP_TRY(e, dev_alloc((void**)&pf->assoc_weight_missed, bytes));
+        SLAM_HIP_TRY(e, hipMemsetAsync(pf->assoc_weight_missed, 0, bytes, e->stream));
+        pf->assoc_weight_terms = reinterpret_cast<float*>(pf->assoc_weight_missed + pf->n);
+    }
+    pf->assoc_weight_log[0] = log_new;
+    pf->assoc_weight_log[1] = log_clutter;
+    pf->assoc_weight_log[2] = log_miss;
+    pf->assoc_weight_on = true;
     return SLAM_OK;
 }
 

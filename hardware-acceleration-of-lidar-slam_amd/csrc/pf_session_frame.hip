@@ -323,31 +323,38 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
             if (int rc = slam_engine_ekf_update(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, noise, &table, nullptr))
                 return rc;
             // existence evidence, on the row the update wrote: through the frame's gather into the other buffer, or in place
+            int32_t* missed = pf->assoc_weight_on ? pf->assoc_weight_missed : nullptr;   // the stage's misses, for the weight below
             if (pf->prune_on && pf->fov_on) {   // ... with a field of view (and line of sight: the table of this frame's scan first)
                 if (pf->sight_bins)
                     if (int rc = slam_sight_table_dev(e, pf->sight_bins)) return rc;
-                if (int rc = slam_landmark_evidence_fov_dev(e, out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->assoc_tab, pf->Lp,
-                                                            pf->ev[mc], pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit, pf->prune_miss,
-                                                            pf->prune_cmax, pf->prune_range, pf->sight_margin, pf->fov_lo, pf->fov_hi,
-                                                            pf->sight_bins != 0, pf->ev_stats, pf->sight_spared, pf->fov_outside))
+                if (int rc = slam_landmark_evidence_fov_missed_dev(e, out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->assoc_tab,
+                                                                   pf->Lp, pf->ev[mc], pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit,
+                                                                   pf->prune_miss, pf->prune_cmax, pf->prune_range, pf->sight_margin, pf->fov_lo,
+                                                                   pf->fov_hi, pf->sight_bins != 0, pf->ev_stats, pf->sight_spared,
+                                                                   pf->fov_outside, missed))
                     return rc;
             } else if (pf->prune_on && pf->sight_bins) {   // ... with line of sight: the table of this frame's scan, then the stage that reads it
                 if (int rc = slam_sight_table_dev(e, pf->sight_bins)) return rc;
-                if (int rc = slam_landmark_evidence_sight_dev(e, out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->assoc_tab,
-                                                              pf->Lp, pf->ev[mc], pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit,
-                                                              pf->prune_miss, pf->prune_cmax, pf->prune_range, pf->sight_margin,
-                                                              pf->ev_stats, pf->sight_spared))
+                if (int rc = slam_landmark_evidence_sight_missed_dev(e, out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->assoc_tab,
+                                                                     pf->Lp, pf->ev[mc], pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit,
+                                                                     pf->prune_miss, pf->prune_cmax, pf->prune_range, pf->sight_margin,
+                                                                     pf->ev_stats, pf->sight_spared, missed))
                     return rc;
             } else if (pf->prune_on)
-                if (int rc = slam_landmark_evidence_dev(e, out, stride, pf->Lp, L, dst, dst + sn, anc, n, pf->assoc_tab, pf->Lp, pf->ev[mc],
-                                                        pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit, pf->prune_miss,
-                                                        pf->prune_cmax, pf->prune_range, pf->ev_stats))
+                if (int rc = slam_landmark_evidence_missed_dev(e, out, stride, pf->Lp, L, dst, dst + sn, anc, n, pf->assoc_tab, pf->Lp, pf->ev[mc],
+                                                               pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit, pf->prune_miss,
+                                                               pf->prune_cmax, pf->prune_range, pf->ev_stats, missed))
                     return rc;
             // duplicates: behind the update and the evidence stage, in place on the row and the evidence buffer this frame wrote
             if (pf->merge_gate != 0.0f)
                 if (int rc = slam_landmark_merge_dev(e, out, stride, pf->Lp, L, n, pf->assoc_tab, pf->Lp,
                                                      pf->prune_on ? pf->ev[f.in_place ? mc : mn] : nullptr, pf->Lp, pf->prune_cmax,
                                                      pf->merge_gate, pf->merge_stats))
+                    return rc;
+            // the unexplained: created, dropped and missed enter the log-likelihood the update left, in front of the weights
+            if (pf->assoc_weight_on)
+                if (int rc = slam_assoc_weight_dev(e, pf->assoc_stats, pf->prune_on ? missed : nullptr, n, pf->assoc_weight_log[0],
+                                                   pf->assoc_weight_log[1], pf->assoc_weight_log[2], nullptr, pf->assoc_weight_terms))
                     return rc;
         } else if (!f.fused) {
             if (int rc = slam_engine_ekf_update(e, pf->map[mc], out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, noise, nullptr, nullptr))

@@ -372,6 +372,15 @@ int slam_pf_merge_device_view(slam_pf* pf, const int32_t** stats)
     return SLAM_OK;
 }
 
+int slam_pf_assoc_weight_device_view(slam_pf* pf, const int32_t** missed, const float** terms)
+{
+    if (!pf || !missed || !terms) return SLAM_ERR_INVALID_ARG;
+    if (!pf->assoc_weight_missed) return SLAM_ERR_NOT_READY;   // slam_pf_assoc_weight_set never switched it on
+    *missed = pf->prune_on ? pf->assoc_weight_missed : nullptr;
+    *terms = pf->assoc_weight_terms;
+    return SLAM_OK;
+}
+
 int slam_pf_get_evidence_host(slam_pf* pf, uint8_t* ev)
 {
     if (!pf || !ev) return SLAM_ERR_INVALID_ARG;

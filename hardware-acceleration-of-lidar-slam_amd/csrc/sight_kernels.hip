@@ -81,7 +81,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_sight_kernel(Evidence
     // WIDE: the dwords that are stored — out of place every one of the row, in place those that hold a landmark
     const unsigned store_dw = in_place ? (L + 3u) / 4u : ev_dw;
     const unsigned batches = (L + 127u) / 128u;
-    int npruned = 0, nseen = 0, nspared = 0;
+    int npruned = 0, nseen = 0, nmissed = 0, nspared = 0;
     for (unsigned b = 0; b < batches; ++b) {
         unsigned tk[2], c[2];
         if (WIDE) {
@@ -155,6 +155,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_sight_kernel(Evidence
             if (!WIDE && in[t]) cout[l[t]] = (uint8_t)cn[t];
             npruned += __popcll(__ballot(prune));
             nseen += __popcll(__ballot(seen[t] && !prune));
+            nmissed += __popcll(__ballot(missed));
             nspared += __popcll(__ballot(hidden[t]));
         }
         if (WIDE) batch_store((guint*)cout, b, lane, cn[0], cn[1], store_dw);
@@ -166,6 +167,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_sight_kernel(Evidence
             st2[0] = npruned;
             st2[1] = nseen;
         }
+        if (a.missed) a.missed[i] = nmissed;
         if (sg.spared) sg.spared[i] = nspared;
     }
 }

@@ -20,7 +20,7 @@
  *
  * usage: slam_pf_main dataset.csv frames beams map_out.csv particles [seed [mean|best]]
  *                     [--gpus N] [--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]]
- *                     [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]]
+ *                     [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]]
  *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
  *                     [--landmarks-out FILE]]
  *   particles      the whole population (a multiple of N)
@@ -42,6 +42,9 @@
  *   --merge GATE   only with --assoc: behind every frame's update a landmark that took no detection and lies within GATE (the
  *                  Mahalanobis term under the sum of the two covariances) of one that took one is fused into it and its slot
  *                  freed — duplicates of one pole become one landmark (slam_pf_merge_set)
+ *   --assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS  only with --assoc: every detection that starts a landmark adds LOG_NEW to its
+ *                  particle's log-likelihood, every dropped one LOG_CLUTTER and — with --prune — every landmark in view that took
+ *                  none LOG_MISS; each finite and <= 0 (slam_pf_assoc_weight_set)
  *   --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]  the detector (slam_pf_detect_set; no values: slam_detect_params_default):
  *                  every frame makes its detections from its own scan, so the landmark map grows from nothing but lidar frames
  *   --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]  only with --assoc and --detect: the detector's noise model
@@ -91,6 +94,8 @@ typedef struct {
     float fov_edge;
     int use_merge;         /* --merge GATE: only with --assoc */
     float merge_gate;
+    int use_assoc_weight;  /* --assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS: only with --assoc */
+    float assoc_weight[3];
     int use_detect;        /* --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] */
     slam_detect_params detect;
     int use_fit;           /* --pole-radius R [TOL] */
@@ -179,6 +184,7 @@ static void *rank_main(void *arg)
     if (run->use_prune) CHECK(slam_pf_prune_set(pf, run->prune[0], run->prune[1], run->prune[2], run->prune_range));
     if (run->use_sight) CHECK(slam_pf_prune_sight_set(pf, run->sight_bins, run->sight_margin));
     if (run->use_merge) CHECK(slam_pf_merge_set(pf, run->merge_gate));
+    if (run->use_assoc_weight) CHECK(slam_pf_assoc_weight_set(pf, run->assoc_weight[0], run->assoc_weight[1], run->assoc_weight[2], 1));
     if (run->use_detect) CHECK(slam_pf_detect_noise_set(pf, &run->detect, run->use_fit ? &run->fit : NULL, run->use_noise ? &run->noise : NULL));
     const int observe = run->landmarks > 0 && run->use_assoc && run->use_detect;   /* else: no frame has observations */
     if (fe_scan_init(&scan, beams, -2.351831f, 0.004363f) || fe_points_init(&map, FE_MAP_CAPACITY + beams) ||
@@ -371,6 +377,17 @@ int main(int argc, char **argv)
                 return 2;
             }
         }
+        else if (!strcmp(argv[a], "--assoc-weight") && a + 3 < argc) {
+            run.use_assoc_weight = 1;
+            for (int k = 0; k < 3; ++k) {
+                char *end = NULL;
+                run.assoc_weight[k] = strtof(argv[++a], &end);
+                if (end == argv[a] || *end || !isfinite(run.assoc_weight[k]) || run.assoc_weight[k] > 0.0f) {
+                    fprintf(stderr, "--assoc-weight %s: LOG_NEW, LOG_CLUTTER and LOG_MISS must be finite numbers <= 0\n", argv[a]);
+                    return 2;
+                }
+            }
+        }
         else if (!strcmp(argv[a], "--detect")) {
             run.use_detect = 1;
             slam_detect_params_default(&run.detect);
@@ -407,11 +424,11 @@ int main(int argc, char **argv)
     }
     const int landmark_options = run.use_assoc || run.use_prune || run.use_detect || run.landmarks_out != NULL;
     if (npos < 5 || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
-        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) ||
+        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) || (run.use_assoc_weight && !run.use_assoc) ||
         (run.use_noise && (!run.use_detect || !run.use_assoc || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
-                        "  [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
+                        "  [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
                         "[--landmarks-out FILE]]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
                         "              without --landmarks; with --landmarks and --assoc the association gates and updates under it\n"
@@ -423,6 +440,9 @@ int main(int argc, char **argv)
                         "              radians at both ends) takes no miss\n"
                         "  --merge GATE: only with --assoc; a landmark that took no detection within GATE (Mahalanobis, under the sum of the two\n"
                         "              covariances) of one that took one is fused into it and its slot freed: duplicates of a pole become one\n"
+                        "  --assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS: only with --assoc; a detection that starts a landmark adds LOG_NEW to its\n"
+                        "              particle's log-likelihood, a dropped one LOG_CLUTTER, a landmark in view that took none (--prune) LOG_MISS;\n"
+                        "              each finite and <= 0\n"
                         "  --pole-radius R [TOL]: only with --detect; a detection is the centre of the circle of radius R fitted to its segment,\n"
                         "              and segments more spread out than that circle (by more than TOL, default 0) are dropped\n"
                         "  --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --assoc and --detect, not with --meas-cov; every detection\n"

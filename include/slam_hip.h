@@ -545,6 +545,53 @@ int slam_landmark_merge_dev(slam_engine *e, float *d_map, int64_t row_stride, in
                             uint8_t *d_ev /* may be NULL */, int ev_stride, int cmax, float merge_gate,
                             int32_t *d_stats /* [n][3], may be NULL */);
 int slam_merge_count(slam_engine *e, int64_t *launches);       /* stage launches */
+/* WHAT THE ASSOCIATION LEAVES UNEXPLAINED.  The associating update's log-likelihood (slam_ekf_update_assoc_dev and its siblings)
+ * sums one term per MATCHED pair, -m/2 - log det S / 2 - log 2 pi: a log DENSITY in 1/m^2.  A detection that starts a landmark, one
+ * that is dropped (between the two gates, or because no slot is left) and a landmark in view that took no detection contribute
+ * nothing — an implicit, dimensionless 0, so which particle the filter prefers depends on the unit of length: for P = p I under
+ * q = meas_var the matched term is -m/2 - log(2 pi (p + q)), negative for EVERY m once p + q > 1 / (2 pi) = 0.159 m^2, and a
+ * particle whose pose is wrong enough that every detection misses the gate then outweighs one that matches all of them.  The
+ * remedy is FastSLAM with unknown data association: a constant log-likelihood for a new feature, a log clutter density for an
+ * unexplained detection and log(1 - P_D) for a missed landmark.
+ * THE MISS COUNT.  The _missed siblings of the three evidence stages are those stages — the same kernels, launch counters, errors,
+ * map, evidence bytes and stats — with one more optional output: d_missed int32 [n] = the slots of particle i the stage scored as
+ * a miss in the form it runs (plain, line of sight, field of view, both): the slots whose evidence byte it lowered or whose
+ * landmark it pruned.  A landmark spared by line of sight or outside the arc is no miss.  d_missed == NULL: exactly the call
+ * without the suffix (which is how those are implemented).
+ * slam_assoc_weight_dev: one thread per particle, with created_i = d_stats[3 i + 1] and dropped_i = d_stats[3 i + 2] (the stats of
+ * the association: matched, created, dropped) and missed_i = d_missed[i] (NULL: 0), every line one rounded float32 operation
+ * (tests/_assoc_weight_spec.py), the counts converted exactly:
+ *   t = created * log_new;  u = dropped * log_clutter;  t = t + u;  u = missed * log_miss;  t = t + u;  ll[i] = ll[i] + t
+ * in place on d_loglik — NULL: the engine's log-likelihood buffer, what slam_logweight_ekf_dev consumes (SLAM_ERR_NOT_READY unless
+ * the last landmark update on this engine was of n particles); d_terms (may be NULL) receives t.  The three constants must be
+ * finite and <= 0 (-0.0 is), else SLAM_ERR_INVALID_ARG and nothing is launched; likewise for n < 0 or a null d_stats.  A sum that
+ * overflows is -inf, as the specification's is.  Bracketed as SLAM_PROF_PAGES and counted by slam_assoc_weight_count — in no other
+ * counter. */
+int slam_landmark_evidence_missed_dev(slam_engine *e, float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                                      const float *d_x, const float *d_y, const int32_t *d_anc, int n,
+                                      const uint8_t *d_assoc, int assoc_stride,
+                                      const uint8_t *d_ev_in, uint8_t *d_ev_out, int ev_stride,
+                                      int hit, int miss, int cmax, float view_range, int32_t *d_stats /* [n][2], may be NULL */,
+                                      int32_t *d_missed /* [n], may be NULL */);
+int slam_landmark_evidence_sight_missed_dev(slam_engine *e, float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                                            const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc, int n,
+                                            const uint8_t *d_assoc, int assoc_stride,
+                                            const uint8_t *d_ev_in, uint8_t *d_ev_out, int ev_stride,
+                                            int hit, int miss, int cmax, float view_range, float margin,
+                                            int32_t *d_stats /* [n][2], may be NULL */, int32_t *d_spared /* [n], may be NULL */,
+                                            int32_t *d_missed /* [n], may be NULL */);
+int slam_landmark_evidence_fov_missed_dev(slam_engine *e, float *d_map, int64_t row_stride, int plane_stride, int nlandmarks,
+                                          const float *d_x, const float *d_y, const float *d_th, const int32_t *d_anc, int n,
+                                          const uint8_t *d_assoc, int assoc_stride,
+                                          const uint8_t *d_ev_in, uint8_t *d_ev_out, int ev_stride,
+                                          int hit, int miss, int cmax, float view_range, float margin,
+                                          float lo, float hi, int use_sight,
+                                          int32_t *d_stats /* [n][2], may be NULL */, int32_t *d_spared /* [n], may be NULL */,
+                                          int32_t *d_outside /* [n], may be NULL */, int32_t *d_missed /* [n], may be NULL */);
+int slam_assoc_weight_dev(slam_engine *e, const int32_t *d_stats /* [n][3] */, const int32_t *d_missed /* [n], may be NULL */, int n,
+                          float log_new, float log_clutter, float log_miss,
+                          float *d_loglik /* [n]; NULL: the engine's buffer */, float *d_terms /* [n], may be NULL */);
+int slam_assoc_weight_count(slam_engine *e, int64_t *launches);   /* stage launches */
 /* THE DETECTOR: the detections of a frame made on the device from the engine's current scan (slam_scan_upload_host / _set_dev),
  * P = nbeams points in scan order — what fe_clean left, so a removed beam leaves no hole and the rule uses distances only, never
  * beam angles.  With jump2 = jump * jump, guard2, width2 and range2 likewise (each rounded once to float32), and every step below
@@ -1022,6 +1069,22 @@ int slam_pf_fov_device_view(slam_pf *pf, float bounds[2], const int32_t **outsid
  * last frame that ran the stage.  SLAM_ERR_NOT_READY until merging was switched on. */
 int slam_pf_merge_set(slam_pf *pf, float merge_gate /* 0: off */);
 int slam_pf_merge_device_view(slam_pf *pf, const int32_t **stats);
+/* The weight of the unexplained inside the session (slam_assoc_weight_dev).  on == 0 switches it off, and so does
+ * slam_pf_assoc_set(gate = 0); a noise form given anew leaves it as it was.  With it off the session runs exactly what it ran
+ * before the first call, launch for launch, and slam_assoc_weight_count does not move.  Accepted where slam_pf_merge_set is — only
+ * while association is on, under any of its three noise forms — otherwise SLAM_ERR_INVALID_ARG (slam_last_error says why): split,
+ * paged, AUTO and sharded sessions never get there.  SLAM_ERR_INVALID_ARG too for a constant that is not finite or > 0.  A refused
+ * call leaves the session unchanged.  In force, every frame with use_observations runs its evidence stage (while pruning is on) in
+ * the _missed form and the stage behind its update, evidence stage and merge, in front of the weights, on the engine's
+ * log-likelihood buffer; a frame without a hand-over runs neither.  Merging runs behind the evidence stage and does not change the
+ * counts.  (0, 0, 0) is a valid "on": the weights are bit for bit those of "off".  A non-zero log_miss while pruning is off is
+ * accepted and inert: nothing scores a miss.  Calling it again changes the constants from the next frame on.  Switching on
+ * allocates (once) the two buffers below; no frame allocates.
+ * slam_pf_assoc_weight_device_view: of the last frame that ran the stage, indexed like slam_pf_view.score — missed int32
+ * [n_particles] (NULL while pruning is off) and terms float32 [n_particles], the t that was added.  SLAM_ERR_NOT_READY until the
+ * switch was on once. */
+int slam_pf_assoc_weight_set(slam_pf *pf, float log_new, float log_clutter, float log_miss, int on);
+int slam_pf_assoc_weight_device_view(slam_pf *pf, const int32_t **missed, const float **terms);
 /* The detector inside the session (slam_detect_scan_dev with these parameters; NULL: off).  Accepted only while association is on
  * — otherwise SLAM_ERR_INVALID_ARG (slam_last_error says why) and the session goes on as before; likewise for parameters that
  * slam_detect_scan_dev refuses.  slam_pf_assoc_set(gate = 0) switches it off too.  With it on, every frame with use_observations
