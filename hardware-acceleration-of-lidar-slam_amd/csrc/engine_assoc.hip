@@ -1,7 +1,7 @@
 // engine_assoc.hip — what a frame of detections without identity adds behind the C ABI: the detections themselves (uploaded, set,
 // or made from the scan by the detector; optionally a covariance per detection), the association stage with meas_var * I, a 2x2 Q
-// or the detections' own Q_k, and the landmarks' existence
-// evidence.  The landmark update under the table the association makes: engine_ekf.hip.
+// or the detections' own Q_k, and the weight of what it leaves unexplained.  The landmark update under the table the association
+// makes: engine_ekf.hip; the landmarks' existence evidence: engine_evidence.hip.
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -384,99 +384,6 @@ int slam_detections_get_host(slam_engine* e, float* zx, float* zy, int32_t* ndet
     }
     SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
     *ndet = e->ndet;
-    return SLAM_OK;
-}
-
-/* ------------------------------------------------------------------ landmark existence evidence (evidence_kernels.hip) */
-
-int slam_landmark_evidence_dev(slam_engine* e, float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
-                               const float* d_y, const int32_t* d_anc, int n, const uint8_t* d_assoc, int assoc_stride,
-                               const uint8_t* d_ev_in, uint8_t* d_ev_out, int ev_stride, int hit, int miss, int cmax, float view_range,
-                               int32_t* d_stats)
-{
-    return slam_landmark_evidence_missed_dev(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_anc, n, d_assoc, assoc_stride, d_ev_in,
-                                             d_ev_out, ev_stride, hit, miss, cmax, view_range, d_stats, nullptr);
-}
-
-int slam_landmark_evidence_missed_dev(slam_engine* e, float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, const float* d_x,
-                                      const float* d_y, const int32_t* d_anc, int n, const uint8_t* d_assoc, int assoc_stride,
-                                      const uint8_t* d_ev_in, uint8_t* d_ev_out, int ev_stride, int hit, int miss, int cmax,
-                                      float view_range, int32_t* d_stats, int32_t* d_missed)
-{
-    SLAM_ENTER(e);
-    if (int rc = slam_engine_resolve_detections(e)) return rc;
-    if (n < 0 || nlandmarks < 0 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride ||
-        assoc_stride < nlandmarks || ev_stride < nlandmarks || hit < 1 || hit > 255 || miss < 1 || miss > 255 || cmax < 1 || cmax > 255 ||
-        !(view_range > 0.0f && view_range <= std::numeric_limits<float>::max()) ||   // (NaN fails every comparison)
-        !d_map || !d_x || !d_y || !d_assoc || !d_ev_in || !d_ev_out || (d_anc && d_ev_in == d_ev_out))
-        return SLAM_ERR_INVALID_ARG;
-    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
-    if (n == 0) return SLAM_OK;
-    EvidenceArgs a;
-    a.map = d_map;
-    a.row_stride = row_stride;
-    a.plane_stride = plane_stride;
-    a.nlandmarks = nlandmarks;
-    a.x = d_x;
-    a.y = d_y;
-    a.anc = d_anc;
-    a.n = n;
-    a.assoc = d_assoc;
-    a.assoc_stride = assoc_stride;
-    a.ndet = e->ndet;
-    a.ev_in = d_ev_in;
-    a.ev_out = d_ev_out;
-    a.ev_stride = ev_stride;
-    a.hit = hit;
-    a.miss = miss;
-    a.cmax = cmax;
-    a.range2 = view_range * view_range;   // one float32 product (-ffp-contract=off)
-    a.stats = d_stats;
-    a.missed = d_missed;
-    a.xcd_chunk = 0;
-    SLAM_HIP_TRY(e, launch_landmark_evidence(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
-    e->evidence_launches[0]++;
-    return SLAM_OK;
-}
-
-int slam_evidence_init_dev(slam_engine* e, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks, int nrows,
-                           uint8_t* d_ev, int ev_stride, int value)
-{
-    SLAM_ENTER(e);
-    if (nrows < 0 || nlandmarks < 0 || plane_stride < nlandmarks || row_stride < 5 * (int64_t)plane_stride || ev_stride < nlandmarks ||
-        value < 0 || value > 255 || !d_map || !d_ev)
-        return SLAM_ERR_INVALID_ARG;
-    if (nrows == 0) return SLAM_OK;
-    EvidenceInitArgs a;
-    a.map = d_map;
-    a.row_stride = row_stride;
-    a.plane_stride = plane_stride;
-    a.nlandmarks = nlandmarks;
-    a.nrows = nrows;
-    a.ev = d_ev;
-    a.ev_stride = ev_stride;
-    a.value = value;
-    a.xcd_chunk = 0;
-    SLAM_HIP_TRY(e, launch_evidence_init(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
-    e->evidence_launches[1]++;
-    return SLAM_OK;
-}
-
-int slam_evidence_counts(slam_engine* e, int64_t counts[2])
-{
-    SLAM_ENTER(e);
-    if (!counts) return SLAM_ERR_INVALID_ARG;
-    counts[0] = e->evidence_launches[0];
-    counts[1] = e->evidence_launches[1];
-    return SLAM_OK;
-}
-
-int slam_evidence_gather_dev(slam_engine* e, const uint8_t* d_in, uint8_t* d_out, int ev_stride, const int32_t* d_anc, int n)
-{
-    SLAM_ENTER(e);
-    if (n < 0 || ev_stride < 0 || (n > 0 && ev_stride > 0 && (!d_in || !d_out || !d_anc || d_in == d_out))) return SLAM_ERR_INVALID_ARG;
-    const ProfScope prof(e, SLAM_PROF_PAGES);
-    SLAM_HIP_TRY(e, launch_evidence_gather(e->stream, d_in, d_out, ev_stride, d_anc, n));
     return SLAM_OK;
 }
 

@@ -1,5 +1,5 @@
 // engine_internal.h — the engine object shared by the translation units that implement the C ABI
-// (engine.hip and the engine_*.hip units by stage — match, ekf, assoc, sight, fov, merge, resample —, the pf_session*.hip units, comm.hip, mapper.hip).  Not part of the public interface.
+// (engine.hip and the engine_*.hip units by stage — match, ekf, assoc, evidence, merge, resample —, the pf_session*.hip units, comm.hip, mapper.hip).  Not part of the public interface.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -97,7 +97,7 @@ struct slam_engine {
     bool det_has_cov = false;
     int64_t assoc_detcov_launches[2] = { 0, 0 };   // slam_assoc_detcov_counts: the same two under per-detection Q (in no other counter)
     int64_t evidence_launches[2] = { 0, 0 };   // slam_evidence_counts: evidence launches, init launches (in no other counter)
-    // the sight table of the current scan (slam_sight_table_dev), what slam_landmark_evidence_sight_dev reads; whatever hands a
+    // the sight table of the current scan (slam_sight_table_dev), what the evidence stage reads with line of sight; whatever hands a
     // scan over drops it (sight_bins = 0), so a stale table is never read
     DevBuf sight_buf;   // kSightMaxBins floats
     int sight_bins = 0;
@@ -369,6 +369,28 @@ extern "C" int slam_engine_associate(slam_engine* e, const float* d_map, int64_t
                                      const slam_meas_noise& noise, float gate, float new_gate, int create, uint8_t* d_assoc,
                                      int assoc_stride, int32_t* d_stats);
 
+// The switches of the existence-evidence stage (kernels.h: launch_landmark_evidence), as the engine's stage takes them: which of
+// the two rules spare a landmark that is due a miss.  Neither: d_th is not read
+struct slam_evidence_form {
+    const float* d_th = nullptr;    // [n] the headings the update used; needed under either rule
+    float margin = 0.0f;            // line of sight: finite, > 0 (not read without use_sight)
+    bool use_sight = false;         // line of sight against the engine's sight table (slam_sight_table_dev first)
+    bool fov = false;               // a field of view: the arc lo .. hi of the diamond angle, each in [0, 4]
+    float lo = 0.0f, hi = 4.0f;
+    int32_t* d_spared = nullptr;    // [n] hidden; written under either rule (0 without use_sight); may be nullptr
+    int32_t* d_outside = nullptr;   // [n] outside the arc; written with fov; may be nullptr
+};
+// engine_evidence.hip: slam_landmark_evidence[_sight | _fov][_missed]_dev are this one function, their checks and status codes in
+// one order: the detections resolved first, SLAM_ERR_INVALID_ARG, SLAM_ERR_NOT_READY (no detections; line of sight without a
+// table), n == 0.  Counts in the counter of its form: fov_launches with fov, else sight_launches[1] with use_sight, else
+// evidence_launches[0]
+__attribute__((visibility("hidden"))) int slam_engine_evidence(slam_engine* e, float* d_map, int64_t row_stride, int plane_stride,
+                                                               int nlandmarks, const float* d_x, const float* d_y, const int32_t* d_anc,
+                                                               int n, const uint8_t* d_assoc, int assoc_stride, const uint8_t* d_ev_in,
+                                                               uint8_t* d_ev_out, int ev_stride, int hit, int miss, int cmax,
+                                                               float view_range, int32_t* d_stats, int32_t* d_missed,
+                                                               const slam_evidence_form& form);
+
 // engine_match.hip
 namespace slam_detail {
 // slot in range, its grid and a scan present
@@ -415,7 +437,7 @@ extern "C" int slam_ekf_materialise_dev(slam_engine* e, const float* d_mean_in, 
                              int nlandmarks, const float* d_obs_save, const float* d_x, const float* d_y, const float* d_th,
                              const int32_t* d_anc, int n, float meas_var, const slam::SplitIO* split, const uint32_t* d_survivor,
                              uint32_t stamp, int group);
-// engine_assoc.hip: a frame of a pruning session without a landmark update: the evidence follows its particles, d_out[i] = d_in[d_anc[i]] (rows of
+// engine_evidence.hip: a frame of a pruning session without a landmark update: the evidence follows its particles, d_out[i] = d_in[d_anc[i]] (rows of
 // ev_stride bytes; bracketed as SLAM_PROF_PAGES like slam_gather_map_dev's table gathers; counted nowhere)
 extern "C" int slam_evidence_gather_dev(slam_engine* e, const uint8_t* d_in, uint8_t* d_out, int ev_stride, const int32_t* d_anc, int n);
 // engine_resample.hip: slam_ancestors_from_scan_dev that also marks the particles it kept (kernels.h: SurvivorOut); needs

@@ -1,7 +1,7 @@
-// evidence_common.h — what the forms of the existence-evidence stage share (evidence_kernels.hip: every landmark within
-// view_range is visible; sight_kernels.hip: one behind what the scan hit is hidden; fov_kernels.hip: one outside the sensor's arc
-// is not looked at): the visibility test's r2, the diamond angle of a direction, and the byte traffic of a batch of 128 landmarks
-// as dwords (WIDE) — see the head of evidence_kernels.hip for the access shape.
+// evidence_common.h — what the kernels of the existence evidence share (evidence_kernels.hip: the stage, init and gather;
+// sight_kernels.hip: the sight table; merge_kernels.hip) and the host's slam_fov_bound: the visibility test's r2, the diamond
+// angle of a direction, and the byte traffic of a batch of 128 landmarks as dwords (WIDE) — see the head of evidence_kernels.hip
+// for the access shape.
 #pragma once
 
 #include "ekf_wave.h"

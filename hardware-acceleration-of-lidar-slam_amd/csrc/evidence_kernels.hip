@@ -4,9 +4,22 @@
 // view_range of the particle's pose loses `miss`; one that cannot pay the miss is PRUNED — its slot gets the bits of a slot that
 // was never used (0, 0, -1, 0, 0), so the association hands it out again — and a clutter detection no longer keeps a slot for good.
 //
-// evidence_kernel: ONE WAVEFRONT OWNS ONE PARTICLE, lanes own landmarks l and l + 64 of each batch of 128 (the access shape of
-// ekf_row_body.h, the grid and row resources of associate_kernel).  Per landmark it reads three planes of the row (12 B), the
-// table byte and the evidence byte, and writes one byte; only a prune, which is rare, writes the five floats of the slot.
+// Two rules spare a landmark that is due a miss (seen, not hit, within view_range); either, both or neither may be on:
+//   FOV (specification: tests/_fov_spec.py): its direction in the sensor frame lies OUTSIDE the arc [lo, hi] of the diamond angle
+//   — the reference's lidar sees 269.5 degrees, and a landmark that drifts into the blind quarter behind the robot is not missing,
+//   it is not looked at.  A hit counts whatever the direction.
+//   SIGHT (specification: tests/_sight_spec.py; the table: sight_kernels.hip): it lies BEHIND what the frame's scan hit in its
+//   direction — the nearest return of its bin and the two neighbours is closer than (r - margin)^2.  The arc test comes first.
+//
+// evidence_stage_kernel<WIDE, FOV, SIGHT>, one body for every form: ONE WAVEFRONT OWNS ONE PARTICLE, lanes own landmarks l and
+// l + 64 of each batch of 128 (the access shape of ekf_row_body.h, the grid and row resources of associate_kernel).  Per landmark
+// it reads three planes of the row (12 B), the table byte and the evidence byte, and writes one byte; only a prune, which is
+// rare, writes the five floats of the slot.
+// FOV || SIGHT: the heading is read and, only in wavefronts in which some lane is due a miss, the offset is rotated into the
+// sensor frame and its diamond angle taken (one division).  SIGHT: the table is staged once per workgroup in LDS (at most 4 KB:
+// eight workgroups of a CU hold 32 KB of its 160; the workgroup's only barrier behind it), and the square root and the three
+// table reads run only where some lane is due a miss AND in view.  The results depend on neither skip.  Neither switch on: no
+// heading is read (sg.th may be nullptr), no LDS, no barrier.
 // Byte traffic: 64 byte accesses of a wavefront move 64 B per instruction.  WIDE (every row of the three byte arrays starts on a
 // dword: strides multiples of 4, bases aligned — decided by the launcher) moves the bytes of a batch as dwords instead: lanes
 // 0..31 load the 32 dwords of the table, lanes 32..63 those of the evidence in the SAME instruction, every lane picks its bytes
@@ -22,18 +35,36 @@ namespace slam {
 
 namespace {
 
-template <bool WIDE>
-__global__ __launch_bounds__(kEkfWaves * 64) void evidence_kernel(EvidenceArgs a)
+// lo <= hi: the arc [lo, hi]; lo > hi: the arc that wraps through p = 4 = 0.  A bound itself is in view
+__device__ __forceinline__ bool fov_in_view(float p, bool has, float lo, float hi, bool wraps)
 {
+    const bool ge = p >= lo, le = p <= hi;
+    return !has || (wraps ? (ge || le) : (ge && le));
+}
+
+template <bool WIDE, bool FOV, bool SIGHT>
+__global__ __launch_bounds__(kEkfWaves * 64) void evidence_stage_kernel(EvidenceArgs a, SightArgs sg, FovArgs fv)
+{
+    constexpr bool DIR = FOV || SIGHT;   // the landmark's direction in the sensor frame is needed
+    __shared__ float s_tab[SIGHT ? kSightMaxBins : 1];
+    if (SIGHT) {
+        for (int j = (int)threadIdx.x; j < sg.bins; j += kEkfWaves * 64) s_tab[j] = sg.table[j];
+        __syncthreads();
+    }
     const unsigned lane = threadIdx.x & 63u;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int i = xcd_block(a.xcd_chunk) * kEkfWaves + wave;
-    if (i >= a.n) return;   // (no workgroup barrier below: a wavefront is on its own)
+    if (i >= a.n) return;   // (SIGHT: behind the workgroup's only barrier; from here a wavefront is on its own)
     const unsigned L = (unsigned)a.nlandmarks, K = (unsigned)a.ndet;
     const unsigned hit = (unsigned)a.hit, miss = (unsigned)a.miss, cmax = (unsigned)a.cmax;
     const bool in_place = a.ev_in == a.ev_out;
     const int src = a.anc ? a.anc[i] : i;
     const float px = a.x[i], py = a.y[i];
+    float sn = 0.0f, cs = 1.0f;
+    if (DIR) det_sincosf(sg.th[i], sn, cs);
+    const bool wraps = fv.lo > fv.hi;
+    const float quarter = (float)(sg.bins >> 2);
+    const unsigned mask = (unsigned)sg.bins - 1u;
     const int row_bytes = __builtin_amdgcn_readfirstlane(5 * a.plane_stride * 4);
     const __amdgpu_buffer_rsrc_t row = row_rsrc(a.map, i, a.row_stride, row_bytes);   // read, and written where a landmark is pruned
     const int pl = __builtin_amdgcn_readfirstlane(a.plane_stride * 4);
@@ -44,7 +75,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_kernel(EvidenceArgs a
     // WIDE: the dwords that are stored — out of place every one of the row, in place those that hold a landmark
     const unsigned store_dw = in_place ? (L + 3u) / 4u : ev_dw;
     const unsigned batches = (L + 127u) / 128u;
-    int npruned = 0, nseen = 0, nmissed = 0;
+    int npruned = 0, nseen = 0, nmissed = 0, nspared = 0, noutside = 0;
     for (unsigned b = 0; b < batches; ++b) {
         unsigned tk[2], c[2];
         if (WIDE) {
@@ -70,18 +101,52 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_kernel(EvidenceArgs a
 #pragma unroll
             for (int p = 0; p < 3; ++p) m[p][t] = row_load(row, at * 4u, p * pl);
         }
+        bool seen[2], hit_now[2], due[2], view[2], hidden[2];
+        float r2[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            seen[t] = in[t] && !(m[2][t] < 0.0f);   // the update's own first-sighting test: -0 counts as seen
+            hit_now[t] = tk[t] < K;                  // a byte that names no detection of this frame is no hit
+            r2[t] = evidence_r2(m[0][t], m[1][t], px, py);
+            due[t] = seen[t] && !hit_now[t] && r2[t] <= a.range2;   // due a miss unless outside or hidden (a NaN mean is not visible)
+            view[t] = true;
+            hidden[t] = false;
+        }
+        if (DIR && __ballot(due[0] || due[1])) {   // wave-uniform: the rotation, the division and the compares only where some lane needs them
+            float p[2];
+            bool has[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const float dx = m[0][t] - px, dy = m[1][t] - py;   // the visibility test's own dx, dy
+                const float xa = cs * dx, xb = sn * dy;
+                const float zx = xa - xb;                            // z = R(theta) (w - t)
+                const float ya = sn * dx, yb = cs * dy;
+                const float zy = ya + yb;
+                has[t] = diamond_angle(zx, zy, p[t]);
+                view[t] = FOV ? fov_in_view(p[t], has[t], fv.lo, fv.hi, wraps) : true;
+            }
+            if (SIGHT && __ballot((due[0] && view[0]) || (due[1] && view[1]))) {   // the square root and the table: due AND in view
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const unsigned j = diamond_bin(p[t], quarter, mask);
+                    const float near = fminf(fminf(s_tab[(j - 1u) & mask], s_tab[j]), s_tab[(j + 1u) & mask]);   // (no NaN in the table)
+                    const float r = sqrtf(r2[t]);   // correctly rounded (NOT __fsqrt_rn: det_math.h)
+                    const float g = r - sg.margin;
+                    const float g2 = g * g;
+                    hidden[t] = due[t] && view[t] && has[t] && g > 0.0f && near < g2;   // a NaN anywhere: not hidden
+                }
+            }
+        }
         unsigned cn[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const bool seen = in[t] && !(m[2][t] < 0.0f);   // the update's own first-sighting test: -0 counts as seen
-            const bool hit_now = tk[t] < K;                  // a byte that names no detection of this frame is no hit
-            const bool visible = evidence_r2(m[0][t], m[1][t], px, py) <= a.range2;   // (a NaN mean is not visible)
-            const bool missed = seen && !hit_now && visible;
+            const bool outside = due[t] && !view[t];
+            const bool missed = due[t] && view[t] && !hidden[t];
             const bool prune = missed && c[t] < miss;
             const unsigned up = c[t] + hit < cmax ? c[t] + hit : cmax;   // integers: 200 + 255 does not wrap
-            unsigned v = seen && hit_now ? up : c[t];
+            unsigned v = seen[t] && hit_now[t] ? up : c[t];
             v = missed ? c[t] - miss : v;
-            v = (prune || !seen) ? 0u : v;
+            v = (prune || !seen[t]) ? 0u : v;
             // beyond L: out of place the padding is written 0, in place it is left alone (WIDE: its own bytes go back)
             cn[t] = in[t] ? v : (in_place ? c[t] : 0u);
             if (prune) {   // rare: the five planes of a slot that was never used
@@ -93,8 +158,10 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_kernel(EvidenceArgs a
             }
             if (!WIDE && in[t]) cout[l[t]] = (uint8_t)cn[t];
             npruned += __popcll(__ballot(prune));
-            nseen += __popcll(__ballot(seen && !prune));
+            nseen += __popcll(__ballot(seen[t] && !prune));
             nmissed += __popcll(__ballot(missed));
+            if (SIGHT) nspared += __popcll(__ballot(hidden[t]));
+            if (FOV) noutside += __popcll(__ballot(outside));
         }
         if (WIDE) batch_store((guint*)cout, b, lane, cn[0], cn[1], store_dw);
     }
@@ -106,6 +173,8 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_kernel(EvidenceArgs a
             st2[1] = nseen;
         }
         if (a.missed) a.missed[i] = nmissed;
+        if (DIR && sg.spared) sg.spared[i] = nspared;   // (FOV without SIGHT: nothing is hidden, 0)
+        if (FOV && fv.outside) fv.outside[i] = noutside;
     }
 }
 
@@ -158,17 +227,30 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_gather_kernel(const u
 
 }  // namespace
 
-hipError_t launch_landmark_evidence(hipStream_t stream, const EvidenceArgs& a_in, const EventPair* ev)
+bool fov_bounds_ok(float lo, float hi) { return lo >= 0.0f && lo <= 4.0f && hi >= 0.0f && hi <= 4.0f; }   // (NaN fails)
+
+template <bool FOV, bool SIGHT>
+static void (*evidence_stage(bool wide))(EvidenceArgs, SightArgs, FovArgs)
+{
+    return wide ? evidence_stage_kernel<true, FOV, SIGHT> : evidence_stage_kernel<false, FOV, SIGHT>;
+}
+
+hipError_t launch_landmark_evidence(hipStream_t stream, const EvidenceArgs& a_in, const SightArgs* sg, const FovArgs* fv, const EventPair* ev)
 {
     if (a_in.n <= 0) return hipSuccess;
-    if (!evidence_args_ok(a_in))
-        return hipErrorInvalidValue;   // what the row and byte accesses are sized by
+    const bool fov = fv != nullptr;
+    const bool sight = sg && (!fov || sg->table);   // under a field of view, no table: without line of sight
+    // what the row, byte and LDS accesses are sized by, each part for the form that needs it
+    if (!evidence_args_ok(a_in) || (fov && (!sg || !fov_bounds_ok(fv->lo, fv->hi))) || (sg && !sg->th) ||
+        (sight && (!sg->table || !sight_bins_ok(sg->bins) || !(sg->margin > 0.0f))))
+        return hipErrorInvalidValue;
     EvidenceArgs a = a_in;
     const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
     const bool wide = dword_rows(a.assoc, a.assoc_stride) && dword_rows(a.ev_in, a.ev_stride) && dword_rows(a.ev_out, a.ev_stride);
+    const auto kernel = fov ? (sight ? evidence_stage<true, true>(wide) : evidence_stage<true, false>(wide))
+                            : (sight ? evidence_stage<false, true>(wide) : evidence_stage<false, false>(wide));
     if (ev) (void)hipEventRecord(ev->start, stream);
-    if (wide) evidence_kernel<true><<<blocks, kEkfWaves * 64, 0, stream>>>(a);
-    else evidence_kernel<false><<<blocks, kEkfWaves * 64, 0, stream>>>(a);
+    kernel<<<blocks, kEkfWaves * 64, 0, stream>>>(a, sg ? *sg : SightArgs{}, fv ? *fv : FovArgs{});
     if (ev) (void)hipEventRecord(ev->stop, stream);
     return hipGetLastError();
 }

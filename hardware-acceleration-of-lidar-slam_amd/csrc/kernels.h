@@ -1,5 +1,5 @@
 // kernels.h — launchers of the gfx950 kernels, one section per kernel file in the Makefile's order; called by the C-ABI layer
-// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_sight / engine_fov / engine_merge / engine_resample.hip by stage), the particle-filter session (the pf_session*.hip units) and the mapper (mapper.hip).
+// (engine.hip and engine_match / engine_ekf / engine_assoc / engine_evidence / engine_merge / engine_resample.hip by stage), the particle-filter session (the pf_session*.hip units) and the mapper (mapper.hip).
 // Every launcher enqueues on `stream` and returns the hipError_t of the launch; none synchronises.
 #pragma once
 
@@ -271,8 +271,27 @@ struct EvidenceArgs {
     int32_t* missed;       // [n] landmarks the stage scored as a miss (lowered or pruned), in whichever form runs; may be nullptr
     int xcd_chunk;         // set by the launcher
 };
-// one wavefront per particle; byte traffic as dwords when every row of the three byte arrays starts on a dword, else as bytes
-hipError_t launch_landmark_evidence(hipStream_t stream, const EvidenceArgs& a, const EventPair* ev = nullptr);
+// the two rules that spare a landmark due a miss (seen, not hit, within view_range); each is a switch of the one stage.
+// LINE OF SIGHT (specification: tests/_sight_spec.py): hidden behind what the scan hit in its direction
+struct SightArgs {
+    const float* th;       // [n] the headings the update used (beside EvidenceArgs::x / y); read under either rule
+    const float* table;    // [bins] a sight table (launch_sight_table)
+    int bins;
+    float margin;          // > 0: hidden = the nearest return of the landmark's bin and its two neighbours < (r - margin)^2
+    int32_t* spared;       // [n] landmarks due a miss and hidden; may be nullptr
+};
+// FIELD OF VIEW (specification: tests/_fov_spec.py): its sensor-frame direction (the diamond angle p) outside the arc
+struct FovArgs {
+    float lo, hi;          // in [0, 4]; lo <= hi: in view = lo <= p <= hi; lo > hi: p >= lo || p <= hi (the arc through p = 4 = 0)
+    int32_t* outside;      // [n] landmarks due a miss and outside the arc; may be nullptr
+};
+bool fov_bounds_ok(float lo, float hi);
+// one wavefront per particle; byte traffic as dwords when every row of the three byte arrays starts on a dword, else as bytes.
+// miss_now = due & in view & ~hidden.  sg == fv == nullptr: everything is in view, nothing hidden.  sg alone: line of sight.
+// fv (sg with it, for th): the arc test first; sg->table == nullptr then: without line of sight (nothing is hidden; sg->bins and
+// sg->margin are not read, sg->spared is written 0).  One grid, the same lanes and byte paths in every form
+hipError_t launch_landmark_evidence(hipStream_t stream, const EvidenceArgs& a, const SightArgs* sg, const FovArgs* fv,
+                                    const EventPair* ev = nullptr);
 struct EvidenceInitArgs {
     const float* map;      // [nrows] rows as above (read only)
     int64_t row_stride;
@@ -287,33 +306,13 @@ struct EvidenceInitArgs {
 hipError_t launch_evidence_init(hipStream_t stream, const EvidenceInitArgs& a, const EventPair* ev = nullptr);
 // a frame without a landmark update: the evidence follows its particles, out[i] = in[anc[i]] (whole rows of `stride` bytes)
 hipError_t launch_evidence_gather(hipStream_t stream, const uint8_t* in, uint8_t* out, int stride, const int32_t* anc, int n);
-// ---- sight_kernels.hip: line of sight for the existence evidence (specification: tests/_sight_spec.py).
-// The SIGHT TABLE of a scan: per direction bin (the diamond angle of a sensor-frame point in `bins` equal steps) the smallest
+// ---- sight_kernels.hip: the table behind the evidence stage's line of sight (specification: tests/_sight_spec.py; DESIGN.md
+// section 7).  The SIGHT TABLE of a scan: per direction bin (the diamond angle of a sensor-frame point in `bins` equal steps) the smallest
 // squared range of the scan's points in it, +inf: none.  A landmark behind what the table holds in its direction is hidden.
 constexpr int kSightMinBins = 32, kSightMaxBins = 1024;
 bool sight_bins_ok(int bins);   // a power of two in kSightMinBins .. kSightMaxBins
 // one workgroup over the scan; out: kSightMaxBins floats, the first `bins` the table, +inf behind them
 hipError_t launch_sight_table(hipStream_t stream, const float* bx, const float* by, int nbeams, int bins, float* out, const EventPair* ev = nullptr);
-struct SightArgs {
-    const float* th;       // [n] the headings the update used (beside EvidenceArgs::x / y)
-    const float* table;    // [bins] a sight table (launch_sight_table)
-    int bins;
-    float margin;          // > 0: hidden = the nearest return of the landmark's bin and its two neighbours < (r - margin)^2
-    int32_t* spared;       // [n] landmarks due a miss and hidden; may be nullptr
-};
-// launch_landmark_evidence with miss_now = seen & ~hit_now & visible & ~hidden: the same grid, lanes and byte paths
-hipError_t launch_landmark_evidence_sight(hipStream_t stream, const EvidenceArgs& a, const SightArgs& sg, const EventPair* ev = nullptr);
-// ---- fov_kernels.hip: a field of view for the existence evidence (specification: tests/_fov_spec.py).  A
-// landmark due a miss whose sensor-frame direction (its diamond angle p) lies outside the arc takes none and keeps its counter.
-struct FovArgs {
-    float lo, hi;          // in [0, 4]; lo <= hi: in view = lo <= p <= hi; lo > hi: p >= lo || p <= hi (the arc through p = 4 = 0)
-    int32_t* outside;      // [n] landmarks due a miss and outside the arc; may be nullptr
-};
-bool fov_bounds_ok(float lo, float hi);
-// launch_landmark_evidence_sight with miss_now = due & in view & ~hidden; sg.table == nullptr: without line of sight (nothing is
-// hidden; sg.bins and sg.margin are not read, sg.th is, sg.spared is written 0).  The same grid, lanes and byte paths
-hipError_t launch_landmark_evidence_fov(hipStream_t stream, const EvidenceArgs& a, const SightArgs& sg, const FovArgs& fv,
-                                        const EventPair* ev = nullptr);
 // ---- merge_kernels.hip: merging duplicate landmarks (specification: tests/_merge_spec.py).  Behind the
 // frame's associating update (and its evidence stage), in place: a seen landmark the frame's table does not name (free) that lies
 // within merge_gate — the Mahalanobis term of mu_l - mu_w under P_l + P_w — of a landmark it names (an anchor) is fused into it.

@@ -5,7 +5,7 @@
 // "noise" (ekf_aniso_math.h) — is the posterior.  Behind the frame's associating update (and its evidence stage), in place.
 //
 // merge_kernel: ONE WAVEFRONT OWNS ONE PARTICLE, lanes own landmarks l and l + 64 of each batch of 128 (the access shape, grid
-// and row resources of associate_kernel and evidence_kernel).
+// and row resources of associate_kernel and evidence_stage_kernel).
 //   1. roles: seen = !(P_xx < 0); an ANCHOR is seen and named by the frame's table (a_l < K: matched or created this frame), a
 //      FREE landmark is seen and not named.  The anchors — at most K <= 64 under a table that names a detection once; of any
 //      other table the first 64 — are compacted in ascending l by ballot and lane prefix into LDS: five values and the slot.

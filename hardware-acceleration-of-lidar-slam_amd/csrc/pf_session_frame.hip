@@ -324,27 +324,16 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
                 return rc;
             // existence evidence, on the row the update wrote: through the frame's gather into the other buffer, or in place
             int32_t* missed = pf->assoc_weight_on ? pf->assoc_weight_missed : nullptr;   // the stage's misses, for the weight below
-            if (pf->prune_on && pf->fov_on) {   // ... with a field of view (and line of sight: the table of this frame's scan first)
+            if (pf->prune_on) {   // ... in the form that is switched on; line of sight: the table of this frame's scan first
                 if (pf->sight_bins)
                     if (int rc = slam_sight_table_dev(e, pf->sight_bins)) return rc;
-                if (int rc = slam_landmark_evidence_fov_missed_dev(e, out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->assoc_tab,
-                                                                   pf->Lp, pf->ev[mc], pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit,
-                                                                   pf->prune_miss, pf->prune_cmax, pf->prune_range, pf->sight_margin, pf->fov_lo,
-                                                                   pf->fov_hi, pf->sight_bins != 0, pf->ev_stats, pf->sight_spared,
-                                                                   pf->fov_outside, missed))
+                const slam_evidence_form form{ dst + 2 * sn, pf->sight_margin, pf->sight_bins != 0, pf->fov_on, pf->fov_lo, pf->fov_hi,
+                                               pf->sight_spared, pf->fov_outside };
+                if (int rc = slam_engine_evidence(e, out, stride, pf->Lp, L, dst, dst + sn, anc, n, pf->assoc_tab, pf->Lp, pf->ev[mc],
+                                                  pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit, pf->prune_miss, pf->prune_cmax,
+                                                  pf->prune_range, pf->ev_stats, missed, form))
                     return rc;
-            } else if (pf->prune_on && pf->sight_bins) {   // ... with line of sight: the table of this frame's scan, then the stage that reads it
-                if (int rc = slam_sight_table_dev(e, pf->sight_bins)) return rc;
-                if (int rc = slam_landmark_evidence_sight_missed_dev(e, out, stride, pf->Lp, L, dst, dst + sn, dst + 2 * sn, anc, n, pf->assoc_tab,
-                                                                     pf->Lp, pf->ev[mc], pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit,
-                                                                     pf->prune_miss, pf->prune_cmax, pf->prune_range, pf->sight_margin,
-                                                                     pf->ev_stats, pf->sight_spared, missed))
-                    return rc;
-            } else if (pf->prune_on)
-                if (int rc = slam_landmark_evidence_missed_dev(e, out, stride, pf->Lp, L, dst, dst + sn, anc, n, pf->assoc_tab, pf->Lp, pf->ev[mc],
-                                                               pf->ev[f.in_place ? mc : mn], pf->Lp, pf->prune_hit, pf->prune_miss,
-                                                               pf->prune_cmax, pf->prune_range, pf->ev_stats, missed))
-                    return rc;
+            }
             // duplicates: behind the update and the evidence stage, in place on the row and the evidence buffer this frame wrote
             if (pf->merge_gate != 0.0f)
                 if (int rc = slam_landmark_merge_dev(e, out, stride, pf->Lp, L, n, pf->assoc_tab, pf->Lp,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/fov_measure.py [N L ROUNDS REPS] — the existence-evidence stage with a field of view on the GPU, through the package, in
+"""profiles/fov_measure.py [N L ROUNDS REPS [LIBDIR ...]] — the existence-evidence stage with a field of view on the GPU, through the package, in
 ONE process, on the scene and the shape of profiles/sight_measure.py.  Behind the same slam_ekf_update_assoc_dev, on the rows that
 launch wrote, through the same ancestors, table and evidence, interleaved round by round (SLAM_PROF_PAGES around each stage):
   * slam_landmark_evidence_dev                       — the plain stage (unchanged by the field of view: the parent of the next two),
@@ -10,7 +10,12 @@ launch wrote, through the same ancestors, table and evidence, interleaved round 
 Then a rows session of 4096 particles x 32 slots with association, pruning and the detector, frame by frame (wall clock, one
 synchronisation per frame): one that never heard of the field of view against one in which it was switched on and off again.
 Per variant the median, minimum and maximum over the rounds; the SPREAD of a variant is max - min.  Measurement tooling: prints,
-asserts nothing about time.  Default: 65 536 x 500 (plane stride 512), 6 rounds of 10 pairs."""
+asserts nothing about time.  Default: 65 536 x 500 (plane stride 512), 6 rounds of 10 pairs.
+LIBDIR ...: builds of the library to compare (directories beside the package's lib/, e.g. lib_parent lib, as
+make -C csrc OUT=../lib_parent leaves them): every build is loaded into this one process, each with an engine of its own on the
+same stream and the same buffers, and every variant runs build after build inside each round.  None: the product's lib/."""
+import importlib.util
+import os
 import statistics
 import sys
 import time
@@ -21,18 +26,34 @@ import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-from __graft_entry__ import load_package  # noqa: E402
+from __graft_entry__ import PKG_DIR, load_package  # noqa: E402
 
-n, L, rounds, reps = (int(v) for v in (sys.argv[1:5] + ["65536", "500", "6", "10"][len(sys.argv) - 1:]))
+
+def load_build(libdir):
+    """The package once more under a name of its own, bound to PKG_DIR / libdir / libslam_hip.so."""
+    os.environ["SLAM_HIP_LIB"] = str(PKG_DIR / libdir / "libslam_hip.so")
+    name = "slam_build_" + libdir
+    spec = importlib.util.spec_from_file_location(name, PKG_DIR / "__init__.py", submodule_search_locations=[str(PKG_DIR)])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[name] = mod
+    spec.loader.exec_module(mod)
+    del os.environ["SLAM_HIP_LIB"]
+    return mod
+
+
+n, L, rounds, reps = (int(v) for v in (sys.argv[1:5] + ["65536", "500", "6", "10"][min(len(sys.argv), 5) - 1:]))
+BUILDS = {d: load_build(d) for d in sys.argv[5:]} or {"lib": load_package()}
 Lp = (L + 31) // 32 * 32
 DEV, Q, GATE, NEW_GATE = "cuda:0", 0.02, 9.21, 50.0
 HIT, MISS, CMAX, RANGE = 1, 1, 8, 15.0
 BINS, MARGIN, NBEAMS = 128, 0.3, 360
-pkg = load_package()
+pkg = next(iter(BUILDS.values()))
 ANGLE_MIN, ANGLE_MAX, EDGE = np.float32(-2.351831), np.float32(-2.351831 + 0.004363 * 1078), np.float32(0.1)
 ARC = (float(pkg.fov_bound(float(ANGLE_MIN + EDGE))), float(pkg.fov_bound(float(ANGLE_MAX - EDGE))))
-e = pkg.Engine(0)
-e.set_stream(torch.cuda.current_stream().cuda_stream)
+ENGINES = {b: m.Engine(0) for b, m in BUILDS.items()}
+for eng in ENGINES.values():
+    eng.set_stream(torch.cuda.current_stream().cuda_stream)
+e = next(iter(ENGINES.values()))   # (the scene is made once, by the first build)
 rng = np.random.default_rng(1)
 lm = rng.uniform(-20, 20, (L, 2)).astype(np.float32)
 x, y, th = (torch.as_tensor((s * rng.standard_normal(n)).astype(np.float32)).to(DEV) for s in (0.05, 0.05, 0.002))
@@ -55,11 +76,13 @@ K = min(56, L)
 ids = rng.permutation(L)[:K]
 zx = np.concatenate([lm[ids, 0], rng.uniform(-20, 20, 8).astype(np.float32)])   # (the pose is the origin, heading 0: z = m)
 zy = np.concatenate([lm[ids, 1], rng.uniform(-20, 20, 8).astype(np.float32)])
-e.detections_upload(zx, zy)
+for eng in ENGINES.values():
+    eng.detections_upload(zx, zy)
 ang = -np.pi + 2 * np.pi * np.arange(NBEAMS) / NBEAMS
 rad = rng.uniform(8.0, 20.0, NBEAMS)
-e.scan_upload((rad * np.cos(ang)).astype(np.float32), (rad * np.sin(ang)).astype(np.float32))
-e.sight_table_dev(BINS)
+for eng in ENGINES.values():
+    eng.scan_upload((rad * np.cos(ang)).astype(np.float32), (rad * np.sin(ang)).astype(np.float32))
+    eng.sight_table_dev(BINS)
 e.associate_dev(d_in, 5 * Lp, Lp, L, x, y, th, anc, n, Q, GATE, NEW_GATE, 1, d_assoc, Lp, None)
 e.evidence_init_dev(d_in, 5 * Lp, Lp, L, n, d_ev_in, Lp, 3)
 d_ev_in = torch.minimum(d_ev_in, torch.randint(0, 4, (n, Lp), dtype=torch.uint8, device=DEV))
@@ -75,7 +98,7 @@ VARIANTS = {
 }
 
 
-def pair(stage, bounds):
+def pair(e, stage, bounds):
     e.ekf_update_assoc_dev(d_in, d_out, 5 * Lp, Lp, L, x, y, th, anc, n, Q, d_assoc, Lp, None)
     head = (d_out, 5 * Lp, Lp, L, x, y)
     tail = (anc, n, d_assoc, Lp, d_ev_in, d_ev_out, Lp, HIT, MISS, CMAX, RANGE)
@@ -95,34 +118,39 @@ def report(name, t):
 print(f"{n} x {L} (plane stride {Lp}), {len(heads)} distinct ancestors, K = {len(zx)}, {NBEAMS} beams, {BINS} bins; {rounds} rounds x {reps} pairs; "
       f"sensor arc lo = {ARC[0]:.6f}, hi = {ARC[1]:.6f}")
 for name, (stage, bounds) in VARIANTS.items():
-    d_spared.zero_()
-    d_outside.zero_()
-    for _ in range(5):
-        pair(stage, bounds)
-    e.sync()
-    st = d_stats.sum(dim=0).cpu().numpy() / n
-    print(f"      {name}: per particle pruned {st[0]:.2f}  seen after pruning {st[1]:.2f}  spared {d_spared.sum().item() / n:.2f}  "
-          f"outside {d_outside.sum().item() / n:.2f}")
-e.profile_enable(pkg.Engine.PROF_EKF, pkg.Engine.PROF_PAGES)
-times = {name: [] for name in VARIANTS}
-update = []
+    for b, eng in ENGINES.items():
+        d_spared.zero_()
+        d_outside.zero_()
+        for _ in range(5):
+            pair(eng, stage, bounds)
+        eng.sync()
+        st = d_stats.sum(dim=0).cpu().numpy() / n
+        print(f"      {b}: {name}: per particle pruned {st[0]:.2f}  seen after pruning {st[1]:.2f}  spared {d_spared.sum().item() / n:.2f}  "
+              f"outside {d_outside.sum().item() / n:.2f}")
+for eng in ENGINES.values():
+    eng.profile_enable(pkg.Engine.PROF_EKF, pkg.Engine.PROF_PAGES)
+times = {b: {name: [] for name in VARIANTS} for b in BUILDS}
+update = {b: [] for b in BUILDS}
 for _ in range(rounds):
     for name, (stage, bounds) in VARIANTS.items():
-        for _ in range(reps):
-            pair(stage, bounds)
-        e.sync()
-        ms, launches = e.profile_read(pkg.Engine.PROF_PAGES)
-        assert launches == reps
-        times[name].append(1e3 * ms / launches)
-        ms, launches = e.profile_read(pkg.Engine.PROF_EKF)
-        update.append(1e3 * ms / launches)
-report("slam_ekf_update_assoc_dev in front of each", update)
-med = {name: report(name, t) for name, t in times.items()}
+        for b, eng in ENGINES.items():   # build after build on the same rows: never one build's block of rounds against another's
+            for _ in range(reps):
+                pair(eng, stage, bounds)
+            eng.sync()
+            ms, launches = eng.profile_read(pkg.Engine.PROF_PAGES)
+            assert launches == reps
+            times[b][name].append(1e3 * ms / launches)
+            ms, launches = eng.profile_read(pkg.Engine.PROF_EKF)
+            update[b].append(1e3 * ms / launches)
 names = list(VARIANTS)
-print(f"  fov use_sight=0 all in view / plain stage: {med[names[1]] / med[names[0]]:.3f}; sensor arc / plain stage: {med[names[2]] / med[names[0]]:.3f}")
-print(f"  fov use_sight=1 all in view / sight stage: {med[names[4]] / med[names[3]]:.3f}; sensor arc / sight stage: {med[names[5]] / med[names[3]]:.3f}")
-e.profile_enable()
-e.close()
+for b, eng in ENGINES.items():
+    print(f" build {b}:")
+    report("slam_ekf_update_assoc_dev in front of each", update[b])
+    med = {name: report(name, t) for name, t in times[b].items()}
+    print(f"  fov use_sight=0 all in view / plain stage: {med[names[1]] / med[names[0]]:.3f}; sensor arc / plain stage: {med[names[2]] / med[names[0]]:.3f}")
+    print(f"  fov use_sight=1 all in view / sight stage: {med[names[4]] / med[names[3]]:.3f}; sensor arc / sight stage: {med[names[5]] / med[names[3]]:.3f}")
+    eng.profile_enable()
+    eng.close()
 sys.stdout.flush()
 
 # ---- a session frame with the feature off: never switched on against switched on and off again
@@ -138,7 +166,7 @@ poles = np.array([(-1.5, 2), (3, -2), (4, .6), (1, 3.5), (2.5, 3)], np.float64)
 scans = [D.raycast((0.0, 0.03 * (f + 1), 0.0), poles, 0.1, 6.0, noise=np.random.default_rng(100 + f), angles=angles)[:2] for f in range(FRAMES)]
 
 
-def session_frames(ask):
+def session_frames(pkg, ask):
     eng = pkg.Engine(0)
     eng.grid_set_dev(0, d_edt, pkg.grid_meta(meta.rows, meta.cols, meta.ld, meta.pixel, meta.min_x, meta.min_y))
     ses = pkg.PfSession(eng, SN, SL, map_layout="rows", seed=5, sigma=(0.005, 0.005, 0.001), meas_var=2.5e-3, score_gain=0.05)
@@ -167,9 +195,11 @@ def session_frames(ask):
 
 
 print(f"session frame, {SN} x {SL} rows, association + pruning + detector (wrap = 0), 1079 beams; median of frames 5 .. {FRAMES - 1}, {SROUNDS} rounds:")
-frames = {"never switched on": [], "switched on and off again": []}
+frames = {b: {"never switched on": [], "switched on and off again": []} for b in BUILDS}
 for _ in range(SROUNDS):
-    for ask, name in zip((False, True), frames):
-        frames[name].append(session_frames(ask))
-for name, t in frames.items():
-    report(name, t)
+    for ask, name in zip((False, True), ("never switched on", "switched on and off again")):
+        for b, m in BUILDS.items():
+            frames[b][name].append(session_frames(m, ask))
+for b in BUILDS:
+    for name, t in frames[b].items():
+        report(f"{b}: {name}", t)

@@ -1,4 +1,4 @@
-"""slam_landmark_evidence_dev and slam_evidence_init_dev (csrc/evidence_kernels.hip) against their specification
+"""slam_landmark_evidence_dev and slam_evidence_init_dev (csrc/evidence_kernels.hip: the one stage with neither switch on) against their specification
 tests/_evidence_spec.py: map rows, evidence bytes and stats are equal bit for bit, whatever the shape, the gather index, the
 strides and the alignment of the byte arrays (the dword and the byte path); nothing outside what the rule names is written; the
 argument checks and the counters."""

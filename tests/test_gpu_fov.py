@@ -1,4 +1,4 @@
-"""slam_landmark_evidence_fov_dev (csrc/fov_kernels.hip) against its specification tests/_fov_spec.py: map rows, evidence bytes,
+"""slam_landmark_evidence_fov_dev (the evidence stage of csrc/evidence_kernels.hip with its field of view) against its specification tests/_fov_spec.py: map rows, evidence bytes,
 stats, spared and outside counts bit for bit whatever the shape, the gather index, the strides (the dword and the byte path), the
 arc (ordinary, wrapping, the reference sensor's) and line of sight on or off; landmarks exactly on a bound; with everything in
 view the outputs of the stages it stands in for; the argument checks launch nothing."""
@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import _assoc_weight_spec as W
+import _evidence_spec as E
 import _fov_spec as V
 import _sight_spec as S
 from __graft_entry__ import load_package
@@ -282,6 +284,68 @@ def test_everything_in_view_is_the_stage_it_stands_in_for(eng, bins):
             assert np.array_equal(fov["sp"], parent["sp"]) and fov["sp"].sum() > 0
         else:
             assert np.all(fov["sp"] == 0)
+
+
+def test_six_entry_points_side_by_side(eng):
+    """The stage is one path behind six entry points: per form the call with the miss count and the one without write the same
+    bytes, the count is the specification's, and each call moves its own launch counter and no other."""
+    n, BINS = 7, 128
+    lo, hi = ARCS["sensor"][0]
+    for L in (13, 65, 129):
+        for j in (0, 1):                                # the dword path, the byte path (odd strides); both through ancestors
+            ps, es, ts, _, _ = configs(L)[j]
+            rows = n + 3
+            rng = np.random.default_rng(900 + 10 * L + j)
+            anc = rng.permutation(rows)[:n].astype(np.int32)
+            (x, y, th), (bx, by), mp, tab, c, ev, _ = make_case(n, L, ps, rows, "sensor", seed=60 + L + j)
+            ev[anc] = c
+            h_in = rng.integers(0, 256, (rows, es)).astype(np.uint8)
+            h_in[:, :L] = ev
+            h_tab = rng.integers(0, 256, (n, ts)).astype(np.uint8)
+            h_tab[:, :L] = tab
+            eng.scan_upload(bx, by)
+            eng.sight_table_dev(BINS)
+            T = S.table(bx, by, BINS)
+            spec = {"plain": E.evidence(mp, x, y, anc, h_tab, K, h_in, HIT, MISS, CMAX, RANGE, L=L),
+                    "sight": S.evidence(mp, x, y, th, anc, h_tab, K, h_in, HIT, MISS, CMAX, RANGE, T, MARGIN, L=L),
+                    "fov": V.evidence(mp, x, y, th, anc, h_tab, K, h_in, HIT, MISS, CMAX, RANGE, lo, hi, T, MARGIN, L=L)}
+            # which of (evidence stage, sight stage, fov stage) launches a form counts in
+            for form, moves in (("plain", (1, 0, 0)), ("sight", (0, 1, 0)), ("fov", (0, 0, 1))):
+                w_mp, w_ev, w_st = spec[form][:3]
+                want = W.missed_of(h_in, anc, w_ev, mp, w_mp, L)
+                outs = []
+                for with_missed in (False, True):
+                    d_mp, d_in, d_tab = dev(mp), dev(h_in), dev(h_tab)
+                    d_out = torch.full((n, es), 7, dtype=torch.uint8, device=DEV)
+                    d_st = torch.full((n, 2), -1, dtype=torch.int32, device=DEV)
+                    d_sp, d_ou, d_ms = (torch.full((n,), -1, dtype=torch.int32, device=DEV) for _ in range(3))
+                    head = (d_mp, 5 * ps, ps, L, dev(x), dev(y))
+                    mid = (dev(anc), n, d_tab, ts, d_in, d_out, es, HIT, MISS, CMAX, RANGE)
+                    ms = dict(d_missed=d_ms) if with_missed else {}
+                    before = (eng.evidence_counts()[0], eng.sight_counts()[1], eng.fov_counts())
+                    tables = (eng.evidence_counts()[1], eng.sight_counts()[0])
+                    if form == "plain":
+                        eng.landmark_evidence_dev(*head, *mid, d_st, **ms)
+                    elif form == "sight":
+                        eng.landmark_evidence_sight_dev(*head, dev(th), *mid, MARGIN, d_st, d_sp, **ms)
+                    else:
+                        eng.landmark_evidence_fov_dev(*head, dev(th), *mid, MARGIN, float(lo), float(hi), True, d_st, d_sp, d_ou, **ms)
+                    after = (eng.evidence_counts()[0], eng.sight_counts()[1], eng.fov_counts())
+                    label = f"L={L} config {j} {form} missed={with_missed}"
+                    assert tuple(a - b for a, b in zip(after, before)) == moves, f"{label}: counters moved by {before} -> {after}"
+                    assert (eng.evidence_counts()[1], eng.sight_counts()[0]) == tables, f"{label}: an init or table counter moved"
+                    outs.append(tuple(host(t) for t in (d_mp, d_out, d_st, d_sp, d_ou, d_ms)))
+                without, with_ = outs
+                label = f"L={L} config {j} {form}"
+                for a, b, what in zip(without[:5], with_[:5], ("map rows", "evidence", "stats", "spared", "outside")):
+                    assert a.tobytes() == b.tobytes(), f"{label}: {what} differ between the call with the miss count and the one without"
+                assert np.all(without[5] == -1) and np.array_equal(with_[5], want), f"{label}: missed {with_[5].tolist()} != {want.tolist()}"
+                assert want.sum() > 0, f"{label}: the case holds no miss"
+                # ... and they are the specification's
+                assert np.array_equal(bits(with_[0]), bits(w_mp)) and np.array_equal(with_[1][:, :L], w_ev[:, :L]) and np.all(with_[1][:, L:] == 0)
+                assert np.array_equal(with_[2], w_st), f"{label}: stats"
+                assert np.array_equal(with_[3], spec[form][3] if form != "plain" else np.full(n, -1)), f"{label}: spared"
+                assert np.array_equal(with_[4], spec[form][4] if form == "fov" else np.full(n, -1)), f"{label}: outside"
 
 
 def test_argument_checks_and_counters(eng):

@@ -1,4 +1,4 @@
-"""slam_sight_table_dev and slam_landmark_evidence_sight_dev (csrc/sight_kernels.hip) against their specification
+"""slam_sight_table_dev and slam_landmark_evidence_sight_dev (csrc/sight_kernels.hip; csrc/evidence_kernels.hip: the one stage with line of sight) against their specification
 tests/_sight_spec.py: the table bit for bit whatever the scan and the bins; map rows, evidence bytes, stats and spared counts bit
 for bit whatever the shape, the gather index, the strides (the dword and the byte path) and the geometry; the scan hand-over drops
 the table; the argument checks launch nothing."""
