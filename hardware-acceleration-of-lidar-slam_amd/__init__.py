@@ -150,6 +150,9 @@ SIGNATURES = {
                                                    _f, _f, _i, _vp, _vp, _vp, _vp]),
     "slam_assoc_weight_dev": (_i, [_vp, _vp, _vp, _i, _f, _f, _f, _vp, _vp]),
     "slam_assoc_weight_count": (_i, [_vp, _vp]),
+    "slam_known_map_prepare_dev": (_i, [_vp, _vp, _i, _i, _f, _vp]),
+    "slam_localise_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp]),
+    "slam_localise_counts": (_i, [_vp, _vp]),
     "slam_detect_params_default": (None, [_vp]),
     "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
     "slam_detect_count": (_i, [_vp, _vp]),
@@ -211,6 +214,8 @@ SIGNATURES = {
     "slam_pf_merge_device_view": (_i, [_vp, _vp]),
     "slam_pf_assoc_weight_set": (_i, [_vp, _f, _f, _f, _i]),
     "slam_pf_assoc_weight_device_view": (_i, [_vp, _vp, _vp]),
+    "slam_pf_known_map_set": (_i, [_vp, _vp, _i, _f, _f]),
+    "slam_pf_known_map_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_detect_set": (_i, [_vp, _vp]),
     "slam_pf_detect_fit_set": (_i, [_vp, _vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
@@ -499,6 +504,23 @@ class Engine:
         self._ck(self.lib.slam_ekf_update_assoc_dev(self.h, _ptr(d_map_in), _ptr(d_map_out), row_stride, plane_stride, nlandmarks,
                                                     _ptr(d_x), _ptr(d_y), _ptr(d_th), _ptr(d_anc), n, meas_var, _ptr(d_assoc),
                                                     assoc_stride, _ptr(d_loglik)), "ekf_update_assoc_dev")
+
+    def known_map_prepare_dev(self, d_map, plane_stride, nlandmarks, meas_var, d_prepared):
+        """``slam_known_map_prepare_dev``: a known map float32 [5][plane_stride] -> the prepared map [6][plane_stride]."""
+        self._ck(self.lib.slam_known_map_prepare_dev(self.h, _ptr(d_map), plane_stride, nlandmarks, meas_var, _ptr(d_prepared)),
+                 "known_map_prepare_dev")
+
+    def localise_dev(self, d_prepared, plane_stride, nlandmarks, d_x, d_y, d_th, n, gate, d_assoc, assoc_stride, d_stats, d_loglik=None):
+        """``slam_localise_dev``: the engine's detections against ONE prepared map per particle: stats int32 [n][3], the
+        log-likelihood (d_loglik None: the engine's buffer) and, with d_assoc, the table uint8 [n][assoc_stride]."""
+        self._ck(self.lib.slam_localise_dev(self.h, _ptr(d_prepared), plane_stride, nlandmarks, _ptr(d_x), _ptr(d_y), _ptr(d_th), n, gate,
+                                            _ptr(d_assoc), assoc_stride, _ptr(d_stats), _ptr(d_loglik)), "localise_dev")
+
+    def localise_counts(self):
+        """-> (prepare launches, stage launches) of this engine so far."""
+        c = (C.c_int64 * 2)()
+        self._ck(self.lib.slam_localise_counts(self.h, c), "localise_counts")
+        return int(c[0]), int(c[1])
 
     def assoc_counts(self):
         """-> (associate launches, assoc-update launches) of this engine so far."""
@@ -1259,6 +1281,25 @@ class PfSession:
         """``slam_pf_assoc_cov_set``: association under the 2x2 sensor-frame covariance (qxx, qxy, qyy) — covariance and gates in one
         switch; (meas_var, 0, meas_var) is exactly assoc_set(gate, new_gate, create)."""
         self.e._ck(self.e.lib.slam_pf_assoc_cov_set(self.h, _f3(meas_cov), gate, new_gate, 1 if create else 0), "pf_assoc_cov_set")
+
+    def known_map_set(self, rows, gate: float = 0.0, log_clutter: float = 0.0):
+        """``slam_pf_known_map_set``: rows float32 [5][L] (mx, my, P_xx, P_xy, P_yy; P_xx < 0: no landmark): observing frames
+        localise in this ONE map (sessions with n_landmarks == 0 on one GPU); rows None switches it off."""
+        if rows is None:
+            self.e._ck(self.e.lib.slam_pf_known_map_set(self.h, None, 0, 0.0, 0.0), "pf_known_map_set")
+            return
+        rows = _np(rows, np.float32)
+        assert rows.ndim == 2 and rows.shape[0] == 5
+        self.e._ck(self.e.lib.slam_pf_known_map_set(self.h, _ptr(rows), rows.shape[1], gate, log_clutter), "pf_known_map_set")
+
+    def known_map_view(self):
+        """``slam_pf_known_map_device_view``: the prepared map float32 [6][L rounded up to 32] (None while the mode is off), L, and
+        the last stage's stats int32 [n][3] = matched, 0, dropped."""
+        p, st, L = C.c_void_p(), C.c_void_p(), C.c_int32(0)
+        self.e._ck(self.e.lib.slam_pf_known_map_device_view(self.h, C.byref(p), C.byref(L), C.byref(st)), "pf_known_map_device_view")
+        Lp = (L.value + 31) // 32 * 32
+        return {"prepared": DeviceArray(p.value, (6, Lp), "<f4", self) if p.value else None, "nlandmarks": L.value,
+                "stats": DeviceArray(st.value, (self.n, 3), "<i4", self)}
 
     def assoc_view(self):
         """``slam_pf_assoc_device_view``: the last frame's table uint8 [n][stride] and stats int32 [n][3], indexed like score."""

@@ -1,0 +1,67 @@
+// engine_localise.hip — localisation in a known landmark map behind the C ABI (localise_kernels.hip): the prepared map, made once
+// per map, and the stage of a frame — the engine's current detections against that map, per particle, into the engine's
+// log-likelihood buffer (what slam_logweight_ekf_dev consumes) or the caller's.
+
+#include <hip/hip_runtime.h>
+
+#include <limits>
+
+#include "engine_internal.h"
+
+using namespace slam;
+
+extern "C" {
+
+int slam_known_map_prepare_dev(slam_engine* e, const float* d_map, int plane_stride, int nlandmarks, float meas_var, float* d_prepared)
+{
+    SLAM_ENTER(e);
+    if (!d_map || !d_prepared || nlandmarks < 1 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || !(meas_var > 0.0f)) return SLAM_ERR_INVALID_ARG;
+    const KnownMapArgs a{ d_map, plane_stride, nlandmarks, meas_var, d_prepared };
+    SLAM_HIP_TRY(e, launch_known_map_prepare(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
+    e->localise_launches[0]++;
+    return SLAM_OK;
+}
+
+int slam_localise_dev(slam_engine* e, const float* d_prepared, int plane_stride, int nlandmarks, const float* d_x, const float* d_y,
+                      const float* d_th, int n, float gate, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats, float* d_loglik)
+{
+    SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (n < 0 || nlandmarks < 1 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || (d_assoc && assoc_stride < nlandmarks) ||
+        !(gate > 0.0f && gate <= std::numeric_limits<float>::max()) || !d_prepared || (n > 0 && (!d_x || !d_y || !d_th || !d_stats)))
+        return SLAM_ERR_INVALID_ARG;
+    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    if (!d_loglik) SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
+    LocaliseArgs a;
+    a.prep = d_prepared;
+    a.plane_stride = plane_stride;
+    a.nlandmarks = nlandmarks;
+    a.x = d_x;
+    a.y = d_y;
+    a.th = d_th;
+    a.n = n;
+    a.det_zx = e->d_det_zx;
+    a.det_zy = e->d_det_zy;
+    a.ndet = e->ndet;
+    a.gate = gate;
+    a.assoc = d_assoc;
+    a.assoc_stride = assoc_stride;
+    a.stats = d_stats;
+    a.loglik = d_loglik ? d_loglik : e->ll_buf.as<float>();
+    SLAM_HIP_TRY(e, launch_localise(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
+    if (!d_loglik) e->ll_n = n;
+    e->localise_launches[1]++;
+    return SLAM_OK;
+}
+
+int slam_localise_counts(slam_engine* e, int64_t counts[2])
+{
+    SLAM_ENTER(e);
+    if (!counts) return SLAM_ERR_INVALID_ARG;
+    counts[0] = e->localise_launches[0];
+    counts[1] = e->localise_launches[1];
+    return SLAM_OK;
+}
+
+}  // extern "C"

@@ -248,6 +248,34 @@ struct AssocArgs {
 hipError_t launch_associate(hipStream_t stream, const AssocArgs& a, const EkfAnisoCov* q, bool create, const EventPair* ev = nullptr);
 // ... under S = P + R_w(theta_i, k), Q_k per detection (q.ndet == a.ndet; a.meas_var is not read)
 hipError_t launch_associate_detcov(hipStream_t stream, const AssocArgs& a, const DetCovArgs& q, bool create, const EventPair* ev = nullptr);
+// ---- localise_kernels.hip: localisation in a known landmark map (specification: tests/_localise_spec.py).
+// ONE map every particle shares, never changed: what depends on a covariance is prepared once per map, and the stage associates
+// the frame's detections per particle (create = 0) and leaves the matched pairs' log-likelihood.  No rows.
+struct KnownMapArgs {
+    const float* map;      // [5][plane_stride]: mx, my, P_xx, P_xy, P_yy; P_xx < 0: the slot holds no landmark
+    int plane_stride;
+    int nlandmarks;        // 1 .. SLAM_MAX_OBS
+    float meas_var;
+    float* prep;           // [6][plane_stride]: mx (NaN: no landmark), my, i00, i01, i11, hl
+};
+// one thread per slot of the plane stride
+hipError_t launch_known_map_prepare(hipStream_t stream, const KnownMapArgs& a, const EventPair* ev = nullptr);
+struct LocaliseArgs {
+    const float* prep;     // the prepared map
+    int plane_stride;
+    int nlandmarks;        // 1 .. SLAM_MAX_OBS
+    const float *x, *y, *th;
+    int n;
+    const float *det_zx, *det_zy;   // [ndet] finite sensor-frame points
+    int ndet;                       // <= SLAM_MAX_DETECTIONS
+    float gate;
+    uint8_t* assoc;        // [n][assoc_stride] as AssocArgs::assoc; nullptr: no table is written
+    int assoc_stride;
+    int32_t* stats;        // [n][3] matched, 0, dropped
+    float* loglik;         // [n]
+};
+// one wavefront per particle at a time, persistent workgroups; the prepared map staged in LDS where it fits
+hipError_t launch_localise(hipStream_t stream, const LocaliseArgs& a, const EventPair* ev = nullptr);
 // ---- evidence_kernels.hip: landmark existence evidence (specification: tests/_evidence_spec.py).  One byte
 // c in [0, cmax] per (particle, landmark slot) beside the rows; behind the update of a frame a matched landmark gains `hit`, a
 // visible unmatched one loses `miss`, and one that cannot pay is pruned: its slot gets the bits of a slot that was never used.

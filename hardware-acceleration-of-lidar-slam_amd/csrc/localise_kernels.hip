@@ -1,0 +1,270 @@
+// localise_kernels.hip — localisation in a known landmark map (no counterpart in the reference; specification:
+// tests/_localise_spec.py).  Every particle associates the frame's detections with ONE map all particles
+// share and takes the matched pairs' log-likelihood; the map is never changed.  With one map and meas_var * I noise nothing that
+// involves a covariance depends on the particle, so it is worked out once per map, not once per (particle, landmark, frame):
+//
+// known_map_prepare_kernel: M [5][stride] -> the prepared map [6][stride] = mx, my, i00, i01, i11, hl with S^-1 = (P + q I)^-1 and
+// hl = 0.5 log det S: the operations of ekf_det_terms / ekf_shared_from (ekf_rcp, det_logf), the bits the specification computes
+// per particle.  A slot that holds no landmark (P_xx < 0) and the padding behind L get a NaN mean: every Mahalanobis term of
+// theirs is NaN, NaN passes no comparison, they never become candidates.
+//
+// localise_kernel: associate_body's mapping (assoc_kernels.hip) without rows.  ONE WAVEFRONT OWNS ONE PARTICLE at a time, lanes own
+// landmarks l and l + 64 of each batch of 128 and walk the K detections in a wave-uniform loop; det_sincosf once, the K world
+// points once (lane k keeps point k).
+//   c. every landmark keeps its cheapest detection (strict <, k ascending: the lowest k on ties, NaN never wins);
+//   d. the candidates (0 <= m <= gate) post (bits(m) << 32 | l) to an LDS 64-bit minimum per detection;
+//   e. lane k then holds detection k's winner: its term ((0 - 0.5 m) - hl) - log 2 pi from the m in the key and one read of hl, added
+//      to accumulator l mod 128 in ascending l — batch by batch, batches without a winner skipped: what they would add is +0 to an
+//      accumulator that is never -0 — then accumulators j and j + 64 and the xor butterfly: orc_ekf_update's order.
+// The workgroups are persistent (a grid that fills the machine once, each wavefront takes particles a grid apart), so the prepared
+// map is staged in LDS once per workgroup where it fits (24 B per landmark, padded to whole batches: nothing is predicated) and
+// read from memory, L2-resident, where it does not.  No row is read and none is written: a frame without a table pointer reads
+// 12 B and writes 16 B per particle.
+
+#include "ekf_wave.h"
+
+namespace slam {
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr unsigned kLocStagedMax = 2048;   // landmarks (whole batches) up to which the prepared map is staged: 48 KB
+
+// LDS of one workgroup, in multiples of 16 bytes: [staged: map 6 x Lr floats] | per wavefront: best[64] u64 | acc[128] float |
+// [table wanted: row[L rounded up to 16] u8]
+struct LocLds {
+    unsigned batches, Lr, rowb, map_bytes, per_wave;
+};
+__host__ __device__ inline LocLds loc_lds(unsigned L, bool staged, bool table)
+{
+    LocLds s;
+    s.batches = (L + 127u) / 128u;
+    s.Lr = s.batches * 128u;
+    s.rowb = table ? (L + 15u) & ~15u : 0u;
+    s.map_bytes = staged ? 6u * 4u * s.Lr : 0u;
+    s.per_wave = 64u * 8u + 128u * 4u + s.rowb;
+    return s;
+}
+
+__device__ __forceinline__ void loc_lds_sync()   // what one lane wrote to LDS, every lane of the SAME wavefront may read afterwards
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(256) void known_map_prepare_kernel(KnownMapArgs a)
+{
+    const int l = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (l >= a.plane_stride) return;
+    const size_t ps = (size_t)a.plane_stride;
+    const bool in = l < a.nlandmarks;
+    const float nan = __uint_as_float(0x7fc00000u);
+    // (padding: the identity, whose terms are finite — the values are never read as a landmark's)
+    const float mx = in ? a.map[l] : 0.0f, my = in ? a.map[ps + l] : 0.0f;
+    const float pxx = in ? a.map[2 * ps + l] : 1.0f, pxy = in ? a.map[3 * ps + l] : 0.0f, pyy = in ? a.map[4 * ps + l] : 1.0f;
+    float idet, hl;
+    ekf_det_terms<float>(pxx, pxy, pyy, a.meas_var, idet, hl);
+    const EkfShared<float> h = ekf_shared_from<float, false>(pxx, pxy, pyy, a.meas_var, idet, hl);
+    const bool seen = in && !(pxx < 0.0f);   // the update's own first-sighting test
+    a.prep[l] = seen ? mx : nan;
+    a.prep[ps + l] = my;
+    a.prep[2 * ps + l] = h.i00;
+    a.prep[3 * ps + l] = h.i01;
+    a.prep[4 * ps + l] = h.i11;
+    a.prep[5 * ps + l] = h.hl;
+}
+
+// the prepared map as a wavefront reads it: the two landmarks of a lane in batch b, and hl of one landmark
+struct LocMapLds {
+    const float* s;   // [6][Lr], NaN means from L on
+    unsigned Lr;
+    __device__ __forceinline__ void pair(unsigned b, unsigned lane, v2f (&m)[5]) const
+    {
+        const unsigned l = b * 128u + lane;
+#pragma unroll
+        for (int p = 0; p < 5; ++p) m[p] = (v2f){s[(unsigned)p * Lr + l], s[(unsigned)p * Lr + l + 64u]};
+    }
+    __device__ __forceinline__ float hl(unsigned l) const { return s[5u * Lr + l]; }
+};
+struct LocMapMem {
+    const float* g;   // [6][ps]
+    unsigned ps, L;
+    __device__ __forceinline__ void pair(unsigned b, unsigned lane, v2f (&m)[5]) const
+    {
+        const float nan = __uint_as_float(0x7fc00000u);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const unsigned l = b * 128u + 64u * t + lane;
+            const bool in = l < L;
+            const unsigned c = in ? l : 0u;   // clamped index + select instead of a predicated load
+#pragma unroll
+            for (int p = 0; p < 5; ++p) m[p][t] = g[(size_t)p * ps + c];
+            m[0][t] = in ? m[0][t] : nan;
+        }
+    }
+    __device__ __forceinline__ float hl(unsigned l) const { return g[(size_t)5 * ps + l]; }
+};
+
+template <class MAP>
+__device__ __forceinline__ void localise_particle(const LocaliseArgs& a, const MAP& map, int i, unsigned lane, const LocLds& lds, u64* s_best,
+                                                  float* s_acc, unsigned char* s_row)
+{
+    const unsigned K = (unsigned)a.ndet;
+    unsigned* s_row32 = reinterpret_cast<unsigned*>(s_row);
+    loc_lds_sync();   // (the particle before this one has read what is written here)
+    s_best[lane] = ~0ull;
+    s_acc[lane] = 0.0f;
+    s_acc[lane + 64u] = 0.0f;
+    for (unsigned d = lane; d < lds.rowb / 4u; d += 64u) s_row32[d] = 0xffffffffu;
+
+    float st, ct;
+    det_sincosf(a.th[i], st, ct);
+    const float px = a.x[i], py = a.y[i];
+    // a. lane k: detection k in the world frame (the observed point of ekf_particle)
+    const float zxk = lane < K ? a.det_zx[lane] : 0.0f, zyk = lane < K ? a.det_zy[lane] : 0.0f;
+    float wxk, wyk;
+    ekf_first_sighting<float>(zxk, zyk, st, ct, px, py, wxk, wyk);
+
+    const float inf = __uint_as_float(0x7f800000u);
+    for (unsigned b = 0; b < lds.batches; ++b) {
+        v2f m[5];
+        map.pair(b, lane, m);
+        const v2f mx = m[0], my = m[1], i00 = m[2], i01 = m[3], i11 = m[4];
+        // c. the cheapest detection of each landmark
+        v2f best = bc2(inf);
+        unsigned bk[2] = { 0u, 0u };
+        for (unsigned k = 0; k < K; ++k) {
+            const v2f wx = bc2(lane_value(wxk, (int)k)), wy = bc2(lane_value(wyk, (int)k));
+            const v2f dx = wx - mx, dy = wy - my;
+            const v2f t0 = i00 * dx + i01 * dy, t1 = i01 * dx + i11 * dy;
+            const v2f maha = dx * t0 + dy * t1;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const bool take = maha[t] < best[t];
+                best[t] = take ? maha[t] : best[t];
+                bk[t] = take ? k : bk[t];
+            }
+        }
+        // d. candidates post to their detection's minimum (a NaN mean — no landmark, padding — left best at +inf)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            if (best[t] >= 0.0f && best[t] <= a.gate) {
+                const unsigned bits = best[t] == 0.0f ? 0u : __float_as_uint(best[t]);   // -0 -> +0
+                atomicMin(&s_best[bk[t]], ((u64)bits << 32) | (b * 128u + 64u * (unsigned)t + lane));
+            }
+    }
+    loc_lds_sync();
+
+    // e. lane k: detection k's winner and its term (m = +0 where it was -0: the two subtractions behind it erase that sign)
+    const u64 won = s_best[lane];
+    const bool matched = lane < K && won != ~0ull;
+    const unsigned wl = matched ? (unsigned)won : 0u;
+    float term = 0.0f;
+    if (matched) {
+        const float maha = __uint_as_float((unsigned)(won >> 32));
+        term = (-(0.5f * maha) - map.hl(wl)) - 1.8378770664f;
+        if (lds.rowb) s_row[wl] = (unsigned char)lane;
+    }
+    const u64 mm = __ballot(matched);
+    const int nmatched = __popcll(mm);
+    if (mm != 0)
+        for (unsigned b = 0; b < lds.batches; ++b) {
+            const bool mine = matched && (wl >> 7) == b;   // at most one winner per accumulator and batch
+            if (__ballot(mine) == 0) continue;
+            if (mine) s_acc[wl & 127u] = s_acc[wl & 127u] + term;
+            loc_lds_sync();
+        }
+    loc_lds_sync();
+    const float total = wave_xor_tree_sum(s_acc[lane] + s_acc[lane + 64u]);
+    if (lane == 0) {
+        a.loglik[i] = total;
+        int32_t* st3 = a.stats + 3 * (size_t)i;
+        st3[0] = nmatched;
+        st3[1] = 0;
+        st3[2] = (int)K - nmatched;
+    }
+    if (lds.rowb) {   // the row: [0, rowb) from LDS (255 from L on), the rest of the stride 255
+        const unsigned stride = (unsigned)a.assoc_stride;
+        uint8_t* out = a.assoc + (size_t)i * stride;
+        if ((stride & 3u) == 0 && (reinterpret_cast<uintptr_t>(a.assoc) & 3u) == 0) {   // (wave-uniform) every row starts on a dword
+            unsigned* out32 = reinterpret_cast<unsigned*>(out);
+            for (unsigned d = lane; d < stride / 4u; d += 64u) out32[d] = d < lds.rowb / 4u ? s_row32[d] : 0xffffffffu;
+        } else {
+            for (unsigned c = lane; c < stride; c += 64u) out[c] = c < lds.rowb ? s_row[c] : (uint8_t)255;
+        }
+    }
+}
+
+template <bool STAGED> __global__ __launch_bounds__(kEkfWaves * 64) void localise_kernel(LocaliseArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const unsigned lane = threadIdx.x & 63u;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned L = (unsigned)a.nlandmarks;
+    const LocLds lds = loc_lds(L, STAGED, a.assoc != nullptr);
+    unsigned char* mine = smem + lds.map_bytes + (unsigned)wave * lds.per_wave;
+    u64* s_best = reinterpret_cast<u64*>(mine);
+    float* s_acc = reinterpret_cast<float*>(s_best + 64);
+    unsigned char* s_row = reinterpret_cast<unsigned char*>(s_acc + 128);
+    const int first = (int)blockIdx.x * kEkfWaves + wave, step = (int)gridDim.x * kEkfWaves;
+    if constexpr (STAGED) {
+        float* s_map = reinterpret_cast<float*>(smem);
+        const float nan = __uint_as_float(0x7fc00000u);
+        for (unsigned l = threadIdx.x; l < lds.Lr; l += kEkfWaves * 64u)
+#pragma unroll
+            for (unsigned p = 0; p < 6u; ++p)
+                s_map[p * lds.Lr + l] = l < L ? a.prep[(size_t)p * (size_t)a.plane_stride + l] : (p == 0u ? nan : 0.0f);
+        __syncthreads();   // (the only workgroup barrier: from here on a wavefront is on its own)
+        const LocMapLds map{ s_map, lds.Lr };
+        for (int i = first; i < a.n; i += step) localise_particle(a, map, i, lane, lds, s_best, s_acc, s_row);
+    } else {
+        const LocMapMem map{ a.prep, (unsigned)a.plane_stride, L };
+        for (int i = first; i < a.n; i += step) localise_particle(a, map, i, lane, lds, s_best, s_acc, s_row);
+    }
+}
+
+}  // namespace
+
+bool localise_args_ok(const LocaliseArgs& a)
+{
+    return !(a.nlandmarks < 1 || a.nlandmarks > SLAM_MAX_OBS || a.plane_stride < a.nlandmarks || a.ndet < 0 ||
+             a.ndet > SLAM_MAX_DETECTIONS || (a.assoc && a.assoc_stride < a.nlandmarks) || !a.prep || !a.stats || !a.loglik);
+}
+
+hipError_t launch_known_map_prepare(hipStream_t stream, const KnownMapArgs& a, const EventPair* ev)
+{
+    if (a.nlandmarks < 1 || a.nlandmarks > SLAM_MAX_OBS || a.plane_stride < a.nlandmarks || !a.map || !a.prep) return hipErrorInvalidValue;
+    if (ev) (void)hipEventRecord(ev->start, stream);
+    known_map_prepare_kernel<<<(a.plane_stride + 255) / 256, 256, 0, stream>>>(a);
+    if (ev) (void)hipEventRecord(ev->stop, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_localise(hipStream_t stream, const LocaliseArgs& a, const EventPair* ev)
+{
+    if (a.n <= 0) return hipSuccess;
+    if (!localise_args_ok(a)) return hipErrorInvalidValue;
+    const bool staged = (unsigned)(a.nlandmarks + 127) / 128u * 128u <= kLocStagedMax;
+    const LocLds s = loc_lds((unsigned)a.nlandmarks, staged, a.assoc != nullptr);
+    const size_t lds = (size_t)s.map_bytes + (size_t)kEkfWaves * s.per_wave;   // at most 60 KB staged, 36 KB from memory
+    // a grid that fills the machine once: as many workgroups as are resident together, or as the particles need
+    const int need = (a.n + kEkfWaves - 1) / kEkfWaves;
+    int dev = 0, cus = 0, per_cu = 0;
+    hipError_t err = hipGetDevice(&dev);
+    if (err == hipSuccess) err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (err == hipSuccess)
+        err = staged ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, localise_kernel<true>, kEkfWaves * 64, lds)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, localise_kernel<false>, kEkfWaves * 64, lds);
+    if (err != hipSuccess) return err;
+    const int64_t resident = (int64_t)cus * per_cu;
+    const int blocks = resident > 0 && resident < need ? (int)resident : need;
+    if (ev) (void)hipEventRecord(ev->start, stream);
+    if (staged) localise_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
+    else localise_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
+    if (ev) (void)hipEventRecord(ev->stop, stream);
+    return hipGetLastError();
+}
+
+}  // namespace slam

@@ -185,6 +185,16 @@ struct slam_pf {
     // slam_pf_assoc_set(0)
     bool detect_fit_on = false;
     slam_detect_fit detect_fit{};
+    // slam_pf_known_map_set (n_landmarks == 0, one GPU): every observing frame associates its detections with ONE known map all
+    // particles share (slam_localise_dev on the prepared map, then the clutter term) and weighs with the result; no map is kept
+    // per particle and none is changed.  The detector switches are accepted while it is on.
+    bool known_on = false;
+    bool known_ll = false;            // the engine's log-likelihood buffer was last claimed by this mode
+    int known_L = 0, known_Lp = 0;    // landmarks; plane stride of the prepared map (known_L rounded up to 32)
+    size_t known_cap = 0;             // floats of the allocation behind known_prep
+    float known_gate = 0.0f, known_log_clutter = 0.0f;
+    float* known_prep = nullptr;      // [6][known_Lp] the prepared map, then [5][known_Lp] the map as it was given
+    int32_t* known_stats = nullptr;   // [n][3] matched, 0, dropped (the last frame that ran the stage); an allocation of its own
     // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe (RES_OBS) and moves between split and
     // split pages while it runs (between rows and pages when it could not have the split layout's tables)
     int layout_cfg = SLAM_MAP_AUTO;
@@ -245,6 +255,7 @@ struct FrameFacts {
     CovArgs cov;
     int cov_bound;
     bool in_place;       // gate: the last frame kept its population, the maps have not moved
+    bool localise;       // a known map is set and the host asks for observations: the frame weighs with the localise stage (no maps: ekf is false)
 };
 
 // ---- pf_session_store.hip: the storage forms and the moves between them

@@ -1,5 +1,5 @@
 // pf_session.hip — the session object of the slam_pf_* interface (pf_session.h): made and destroyed, reset and loaded (poses, maps),
-// its option switches (refinement, 2x2 measurement covariance, association, pruning, the detector) and its small counters.
+// its option switches (refinement, 2x2 measurement covariance, association, pruning, the detector, a known map) and its small counters.
 // The storage forms are pf_session_store.hip, the frame pf_session_frame.hip, the read-backs pf_session_read.hip.
 
 #include <float.h>
@@ -199,6 +199,9 @@ int slam_pf_destroy(slam_pf* pf)
     if (pf->fov_outside) (void)hipFree(pf->fov_outside);
     if (pf->merge_stats) (void)hipFree(pf->merge_stats);
     if (pf->assoc_weight_missed) (void)hipFree(pf->assoc_weight_missed);   // (the terms live behind the misses)
+    if (pf->known_prep) (void)hipFree(pf->known_prep);                      // (the map as it was given lives behind the prepared one)
+    if (pf->known_stats) (void)hipFree(pf->known_stats);
+    if (pf->known_ll) pf->e->ll_n = -1;
     free_page_tables(pf);
     free_split_tables(pf);
     for (void* p : { (void*)pf->score, (void*)pf->logw, (void*)pf->count, (void*)pf->first, (void*)pf->pose_all, (void*)pf->pose_stage, (void*)pf->first_all,
@@ -593,9 +596,15 @@ int slam_pf_detect_noise_set(slam_pf* pf, const slam_detect_params* params, cons
         pf->detect_noise_on = false;
         return SLAM_OK;
     }
-    if (!pf->assoc_on) {   // (which is what every layout but rows, a sharded session and a 2x2 covariance come down to)
+    if (!pf->assoc_on && !pf->known_on) {   // (which is what every layout but rows, a sharded session and a 2x2 covariance come down to)
         snprintf(e->err, sizeof e->err, "the detector makes the detections the association reads: it needs data association switched "
-                                        "on (slam_pf_assoc_set: the row layout on one GPU, not sharded, meas_var * I)");
+                                        "on (slam_pf_assoc_set: the row layout on one GPU, not sharded, meas_var * I) or a known map "
+                                        "(slam_pf_known_map_set)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (pf->known_on && noise) {
+        snprintf(e->err, sizeof e->err, "localisation in a known map weighs with meas_var * I: the detector's noise model cannot be "
+                                        "switched on (slam_pf_detect_set / slam_pf_detect_fit_set)");
         return SLAM_ERR_INVALID_ARG;
     }
     if (!slam_detect_params_ok(params)) {
@@ -616,6 +625,87 @@ int slam_pf_detect_noise_set(slam_pf* pf, const slam_detect_params* params, cons
     if (fit) pf->detect_fit = *fit;
     pf->detect_noise_on = noise != nullptr;
     if (noise) pf->detect_noise = *noise;
+    return SLAM_OK;
+}
+
+int slam_pf_known_map_set(slam_pf* pf, const float* rows, int nlandmarks, float gate, float log_clutter)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (!rows) {   // off: the session runs exactly what it ran before the first call (the detector goes off with it)
+        if (pf->known_on) {
+            pf->detect_on = false;
+            pf->detect_fit_on = false;
+        }
+        if (pf->known_ll) e->ll_n = -1;   // (the stage's log-likelihoods are nobody's any more)
+        pf->known_ll = false;
+        pf->known_on = false;
+        return SLAM_OK;
+    }
+    if (pf->L != 0 || pf->comm) {
+        snprintf(e->err, sizeof e->err, "localisation in a known map is for a session without maps of its own on one GPU "
+                                        "(n_landmarks == 0, not sharded)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (nlandmarks < 1 || nlandmarks > SLAM_MAX_OBS || !(gate > 0.0f && gate <= FLT_MAX) || !assoc_weight_const_ok(log_clutter)) {
+        snprintf(e->err, sizeof e->err, "a known map needs 1 .. %d landmarks, a finite gate > 0 and a finite log_clutter <= 0", (int)SLAM_MAX_OBS);
+        return SLAM_ERR_INVALID_ARG;
+    }
+    const size_t L = (size_t)nlandmarks, Lp = (L + 31) / 32 * 32;
+    const float q = pf->cfg.meas_var;
+    for (size_t k = 0; k < 5 * L; ++k)
+        if (!(rows[k] >= -FLT_MAX && rows[k] <= FLT_MAX)) {   // (NaN fails every comparison)
+            snprintf(e->err, sizeof e->err, "known map: value %zu of plane %zu is not finite", k % L, k / L);
+            return SLAM_ERR_INVALID_ARG;
+        }
+    for (size_t l = 0; l < L; ++l) {
+        const float pxx = rows[2 * L + l], pxy = rows[3 * L + l], pyy = rows[4 * L + l];
+        if (pxx < 0.0f) continue;   // the slot holds no landmark
+        const float a = pxx + q, c = pyy + q;
+        const float det = a * c - pxy * pxy;   // (the prepare kernel's own operations)
+        if (!(a > 0.0f && c > 0.0f && det > 0.0f)) {
+            snprintf(e->err, sizeof e->err, "known map: landmark %zu has no positive definite P + meas_var * I", l);
+            return SLAM_ERR_INVALID_ARG;
+        }
+    }
+    // ---- accepted: everything the frames need is made here, never inside a frame
+    if (int rc = slam_engine_sync(e)) return rc;   // (a frame in flight may still read the map that is replaced; also selects the device)
+    if (11 * Lp > pf->known_cap) {
+        float* fresh = nullptr;
+        SLAM_HIP_TRY(e, dev_alloc((void**)&fresh, 11 * Lp * sizeof(float)));
+        if (pf->known_prep) (void)hipFree(pf->known_prep);
+        pf->known_prep = fresh;
+        pf->known_cap = 11 * Lp;
+        pf->known_on = false;   // (the old map is gone: until the new one is prepared below there is none)
+    }
+    if (!pf->known_stats) {
+        const size_t st = (size_t)pf->n * 3 * sizeof(int32_t);
+        SLAM_HIP_TRY(e, dev_alloc((void**)&pf->known_stats, st));
+        SLAM_HIP_TRY(e, hipMemsetAsync(pf->known_stats, 0, st, e->stream));
+    }
+    SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)pf->n));
+    std::vector<float> h(5 * Lp, 0.0f);
+    for (size_t l = 0; l < Lp; ++l) h[2 * Lp + l] = -1.0f;   // padding: slots that hold no landmark
+    for (int p = 0; p < 5; ++p) memcpy(&h[(size_t)p * Lp], rows + (size_t)p * L, L * sizeof(float));
+    float* raw = pf->known_prep + 6 * Lp;
+    pf->known_on = false;
+    SLAM_HIP_TRY(e, hipMemcpy(raw, h.data(), 5 * Lp * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = slam_known_map_prepare_dev(e, raw, (int)Lp, nlandmarks, q, pf->known_prep)) return rc;
+    pf->known_L = nlandmarks;
+    pf->known_Lp = (int)Lp;
+    pf->known_gate = gate;
+    pf->known_log_clutter = log_clutter;
+    pf->known_on = true;
+    return SLAM_OK;
+}
+
+int slam_pf_known_map_device_view(slam_pf* pf, const float** prepared, int32_t* nlandmarks, const int32_t** stats)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    if (!pf->known_stats) return SLAM_ERR_NOT_READY;
+    if (prepared) *prepared = pf->known_on ? pf->known_prep : nullptr;
+    if (nlandmarks) *nlandmarks = pf->known_on ? pf->known_L : 0;
+    if (stats) *stats = pf->known_stats;
     return SLAM_OK;
 }
 

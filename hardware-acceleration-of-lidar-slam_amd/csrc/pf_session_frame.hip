@@ -85,6 +85,7 @@ FrameFacts frame_facts(const slam_pf* pf, int use_observations)
     // the current layout, every 8th frame otherwise
     f.sample_obs = pf->layout_cfg == SLAM_MAP_AUTO && !pf->auto_stuck && f.observing &&
                    (pf->frame < 8 || (pf->frame & 7u) == 0 || (pf->paged ? pf->votes_rows : pf->votes_pages) > 0);
+    f.localise = pf->known_on && use_observations;
     f.anc = pf->has_anc ? pf->anc[pf->cur] : nullptr;
     f.src = pf->pose[pf->cur];
     f.dst = pf->pose[1 - pf->cur];
@@ -308,6 +309,15 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
     const size_t sn = (size_t)n;
     const int64_t stride = pf->row_stride();
     float* dst = f.dst;
+    if (f.localise) {   // a known map (no maps of the session's own): the stage on the poses the front launch left, the clutter term, the weights
+        if (int rc = slam_localise_dev(e, pf->known_prep, pf->known_Lp, pf->known_L, dst, dst + sn, dst + 2 * sn, n, pf->known_gate, nullptr, 0,
+                                       pf->known_stats, nullptr))
+            return rc;
+        pf->known_ll = true;
+        if (pf->known_log_clutter != 0.0f)
+            if (int rc = slam_assoc_weight_dev(e, pf->known_stats, nullptr, n, 0.0f, pf->known_log_clutter, 0.0f, nullptr, nullptr)) return rc;
+        return slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
+    }
     if (f.ekf) {
         if (f.sample_obs)
             if (int rc = issue_obs_count(pf)) return rc;
@@ -581,8 +591,9 @@ int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations,
                                         "carry none (slam_detections_cov_upload_host / _set_dev, or slam_pf_detect_noise_set)");
         return SLAM_ERR_NOT_READY;
     }
-    // the detector: in front of the frame's first launch, so that its count has arrived when update_rows' association asks for it
-    if (pf->detect_on && pf->assoc_on && f.ekf)
+    // the detector: in front of the frame's first launch, so that its count has arrived when update_rows' association (or its
+    // localise stage: a known map) asks for it
+    if (pf->detect_on && (pf->assoc_on ? f.ekf : f.localise))
         if (int rc = slam_detect_scan_noise_dev(e, &pf->detect_params, pf->detect_fit_on ? &pf->detect_fit : nullptr,
                                                 pf->detect_noise_on ? &pf->detect_noise : nullptr, nullptr))
             return rc;
@@ -593,7 +604,7 @@ int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations,
     if (int rc = resample_stage(pf, f.dst, f.survivors)) return rc;
     pf->cur = 1 - pf->cur;
     pf->has_anc = true;
-    pf->last_ekf = f.ekf;
+    pf->last_ekf = f.ekf || f.localise;
     pf->frame++;
     return SLAM_OK;
 }

@@ -23,6 +23,7 @@
  *                     [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]]
  *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
  *                     [--landmarks-out FILE]]
+ *                     [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]]]]
  *   particles      the whole population (a multiple of N)
  *   --ess F        ESS-gated resampling: resample only in frames whose effective sample size is below F * N
  *   --refine SWEEPS  scan-match refinement of every particle (slam_pf_refine_set): SWEEPS (1..16) sweeps of the reference's
@@ -53,6 +54,11 @@
  *                  segment's centroid, and segments more spread out than such a circle (by more than TOL, default 0) are no
  *                  detections (slam_pf_detect_fit_set)
  *   --landmarks-out FILE  at the end, the seen landmarks (P_xx >= 0) of the heaviest particle as "%f,%f" lines
+ *   --known-map FILE GATE MAP_VAR [LOG_CLUTTER]  localisation in a known landmark map (slam_pf_known_map_set): FILE holds "%f,%f"
+ *                  lines as --landmarks-out writes them, every landmark gets P = MAP_VAR * I (MAP_VAR >= 0); the filter keeps no
+ *                  landmarks of its own, every frame associates its detections (--detect) with this one map within GATE, weighs
+ *                  each particle with the matched pairs' likelihood and adds LOG_CLUTTER (<= 0, default 0) per unmatched
+ *                  detection.  One GPU; not with --landmarks or --meas-cov
  */
 #define _POSIX_C_SOURCE 200809L
 #include <math.h>
@@ -103,6 +109,10 @@ typedef struct {
     int use_noise;         /* --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --detect */
     slam_detect_noise noise;
     const char *landmarks_out;   /* --landmarks-out FILE */
+    const char *known_map;       /* --known-map FILE GATE MAP_VAR [LOG_CLUTTER] */
+    float known_gate, known_var, known_log_clutter;
+    float *known_rows;           /* [5][known_n]: the file's points, P = MAP_VAR * I */
+    int known_n;
     /* the ranks */
     int world, use_rccl, same_device;
     uint8_t comm_id[SLAM_COMM_ID_BYTES];
@@ -155,7 +165,7 @@ static void *rank_main(void *arg)
     }
     /* motion noise of the order of the reference's fine lattice step (0.025 m, 0.004363 rad; main.c:833) */
     /* ... and, with landmarks, a detection noise of the order of a pole's radius (0.1 m); without them meas_var is not read */
-    const slam_pf_config cfg = { n, run->landmarks, { 0.01f, 0.01f, 0.002f }, run->landmarks > 0 ? 0.01f : 1.0f, 0.25f, run->seed, run->ess_frac,
+    const slam_pf_config cfg = { n, run->landmarks, { 0.01f, 0.01f, 0.002f }, run->landmarks > 0 || run->known_map ? 0.01f : 1.0f, 0.25f, run->seed, run->ess_frac,
                                  run->use_meas_cov || run->landmarks > 0 ? SLAM_MAP_ROWS : SLAM_MAP_AUTO };
     if (world > 1 || run->use_rccl || run->group) {
         if (run->group) CHECK(slam_comm_create_local(eng, run->group, rank, &comm));
@@ -185,8 +195,9 @@ static void *rank_main(void *arg)
     if (run->use_sight) CHECK(slam_pf_prune_sight_set(pf, run->sight_bins, run->sight_margin));
     if (run->use_merge) CHECK(slam_pf_merge_set(pf, run->merge_gate));
     if (run->use_assoc_weight) CHECK(slam_pf_assoc_weight_set(pf, run->assoc_weight[0], run->assoc_weight[1], run->assoc_weight[2], 1));
+    if (run->known_map) CHECK(slam_pf_known_map_set(pf, run->known_rows, run->known_n, run->known_gate, run->known_log_clutter));
     if (run->use_detect) CHECK(slam_pf_detect_noise_set(pf, &run->detect, run->use_fit ? &run->fit : NULL, run->use_noise ? &run->noise : NULL));
-    const int observe = run->landmarks > 0 && run->use_assoc && run->use_detect;   /* else: no frame has observations */
+    const int observe = (run->known_map || (run->landmarks > 0 && run->use_assoc)) && run->use_detect;   /* else: no frame has observations */
     if (fe_scan_init(&scan, beams, -2.351831f, 0.004363f) || fe_points_init(&map, FE_MAP_CAPACITY + beams) ||
         fe_points_init(&local, FE_LOCAL_CAPACITY) || fe_grid_init(&coarse, FE_COARSE_LD) || fe_grid_init(&fine, FE_FINE_LD) ||
         !(hits = (float *)calloc((size_t)beams + 1, sizeof(float)))) {
@@ -420,16 +431,30 @@ int main(int argc, char **argv)
             if (a + 1 < argc && strchr("0123456789.+", argv[a + 1][0])) run.noise.lateral_var = (float)atof(argv[++a]);
         }
         else if (!strcmp(argv[a], "--landmarks-out") && a + 1 < argc) run.landmarks_out = argv[++a];
+        else if (!strcmp(argv[a], "--known-map") && a + 3 < argc) {
+            run.known_map = argv[++a];
+            float *v[3] = { &run.known_gate, &run.known_var, &run.known_log_clutter };
+            const int given = a + 3 < argc && strchr("0123456789.+-", argv[a + 3][0]) && strncmp(argv[a + 3], "--", 2) ? 3 : 2;
+            for (int k = 0; k < given; ++k) {
+                char *end = NULL;
+                *v[k] = strtof(argv[++a], &end);
+                if (end == argv[a] || *end || !isfinite(*v[k]) || (k == 0 && *v[k] <= 0.0f) || (k == 1 && *v[k] < 0.0f) || (k == 2 && *v[k] > 0.0f)) {
+                    fprintf(stderr, "--known-map %s: GATE must be a finite number > 0, MAP_VAR >= 0 and LOG_CLUTTER <= 0\n", argv[a]);
+                    return 2;
+                }
+            }
+        }
         else if (npos < 8) pos[npos++] = argv[a];
     }
-    const int landmark_options = run.use_assoc || run.use_prune || run.use_detect || run.landmarks_out != NULL;
-    if (npos < 5 || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
+    const int landmark_options = run.use_assoc || run.use_prune || (run.use_detect && !run.known_map) || run.landmarks_out != NULL;
+    if (npos < 5 || (run.known_map && (run.landmarks > 0 || run.world > 1 || run.use_meas_cov)) || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
         (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) || (run.use_assoc_weight && !run.use_assoc) ||
         (run.use_noise && (!run.use_detect || !run.use_assoc || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
                         "  [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
                         "[--landmarks-out FILE]]\n"
+                        "  [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]]]]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
                         "              without --landmarks; with --landmarks and --assoc the association gates and updates under it\n"
                         "  --landmarks: L landmark slots per particle on rows, one GPU; --assoc, --prune, --detect and --landmarks-out need it.\n"
@@ -446,7 +471,10 @@ int main(int argc, char **argv)
                         "  --pole-radius R [TOL]: only with --detect; a detection is the centre of the circle of radius R fitted to its segment,\n"
                         "              and segments more spread out than that circle (by more than TOL, default 0) are dropped\n"
                         "  --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --assoc and --detect, not with --meas-cov; every detection\n"
-                        "              carries its own covariance (RANGE_VAR along its beam, BEARING_VAR r^2 + LATERAL_VAR across) and is gated under it\n", argv[0]);
+                        "              carries its own covariance (RANGE_VAR along its beam, BEARING_VAR r^2 + LATERAL_VAR across) and is gated under it\n"
+                        "  --known-map FILE GATE MAP_VAR [LOG_CLUTTER]: localise in the landmark map of FILE (\"x,y\" lines, as --landmarks-out writes\n"
+                        "              them; P = MAP_VAR * I each): every frame associates its detections (--detect) with that one map within GATE and\n"
+                        "              weighs with the result, LOG_CLUTTER <= 0 per unmatched detection; one GPU, not with --landmarks or --meas-cov\n", argv[0]);
         return 2;
     }
     if (run.use_meas_cov) {   /* the conditions of slam_pf_meas_cov_set: finite, qxx > 0, qyy > 0, float determinant > 0 */
@@ -457,6 +485,32 @@ int main(int argc, char **argv)
                     (double)q[0], (double)q[1], (double)q[2]);
             return 2;
         }
+    }
+    if (run.known_map) {
+        FILE *km = fopen(run.known_map, "r");
+        if (!km) { perror(run.known_map); return 2; }
+        float *xy = (float *)malloc(sizeof(float) * 2 * SLAM_MAX_OBS);
+        float px, py;
+        int cnt = 0, got;
+        while (xy && (got = fscanf(km, "%f,%f", &px, &py)) == 2 && cnt < SLAM_MAX_OBS) { xy[2 * cnt] = px; xy[2 * cnt + 1] = py; ++cnt; }
+        const int clean = xy && feof(km);
+        fclose(km);
+        if (!clean || cnt < 1) {
+            fprintf(stderr, "--known-map %s: expected 1 .. %d lines \"x,y\"\n", run.known_map, (int)SLAM_MAX_OBS);
+            free(xy);
+            return 2;
+        }
+        run.known_n = cnt;
+        run.known_rows = (float *)calloc(5 * (size_t)cnt, sizeof(float));
+        if (!run.known_rows) { free(xy); return 1; }
+        for (int l = 0; l < cnt; ++l) {
+            run.known_rows[l] = xy[2 * l];
+            run.known_rows[cnt + l] = xy[2 * l + 1];
+            run.known_rows[2 * cnt + l] = run.known_var;
+            run.known_rows[4 * cnt + l] = run.known_var;
+        }
+        free(xy);
+        if (!run.use_detect) fprintf(stderr, "--known-map without --detect: no frame has detections, the map is not used\n");
     }
     run.dataset = pos[0];
     run.frames = atoi(pos[1]);
@@ -500,5 +554,6 @@ int main(int argc, char **argv)
     int rc = 0;
     for (int r = 0; r < run.world; ++r) rc |= ranks[r].rc;
     slam_local_group_destroy(run.group);
+    free(run.known_rows);
     return rc;
 }

@@ -592,6 +592,31 @@ int slam_assoc_weight_dev(slam_engine *e, const int32_t *d_stats /* [n][3] */, c
                           float log_new, float log_clutter, float log_miss,
                           float *d_loglik /* [n]; NULL: the engine's buffer */, float *d_terms /* [n], may be NULL */);
 int slam_assoc_weight_count(slam_engine *e, int64_t *launches);   /* stage launches */
+/* LOCALISATION IN A KNOWN MAP (specification: tests/_localise_spec.py).  ONE landmark map every particle
+ * shares, which nothing changes: d_map is float32 [5][plane_stride], planes mx, my, P_xx, P_xy, P_yy as in a row, 1 <= nlandmarks
+ * <= SLAM_MAX_OBS, plane_stride >= nlandmarks; a slot with P_xx < 0 holds no landmark.  With meas_var * I noise S^-1 = (P + meas_var I)^-1 and
+ * 0.5 log det S do not depend on the particle:
+ * slam_known_map_prepare_dev works them out once per map (one launch) into d_prepared, float32 [6][plane_stride] = mx, my, i00,
+ * i01, i11, hl — the operations of the landmark update, so the bits the specification computes per particle; a slot without a
+ * landmark, and the padding behind nlandmarks, get a NaN mx and never become candidates.  The caller guarantees P + meas_var I
+ * positive definite for every landmark (slam_pf_known_map_set checks it).
+ * slam_localise_dev (one launch): every particle associates the engine's current detections (uploaded, set or made by the
+ * detector; K = 0 is legal: loglik = +0, stats = 0) with the prepared map exactly as slam_associate_dev(create = 0, new_gate = gate)
+ * would with a row that holds it — each landmark its cheapest detection, each detection the cheapest landmark that chose it, 0 <=
+ * m <= gate, the lowest k and the lowest l on ties, NaN never wins — and leaves the log-likelihood slam_ekf_update_assoc_dev would
+ * leave under that table (the matched pairs' terms, summed in its order) in d_loglik (NULL: the engine's buffer, what
+ * slam_logweight_ekf_dev and slam_assoc_weight_dev consume).  d_stats int32 [n][3] = matched, 0, K - matched.  d_assoc (may be
+ * NULL: no table is written) is uint8 [n][assoc_stride >= nlandmarks] as slam_associate_dev writes it.  No row is read and none is
+ * written.  SLAM_ERR_INVALID_ARG: nlandmarks outside 1 .. SLAM_MAX_OBS, plane_stride or (with d_assoc) assoc_stride < nlandmarks,
+ * a gate that is not finite and > 0, n < 0, a null pointer other than d_assoc / d_loglik.  SLAM_ERR_NOT_READY: no detections.
+ * Out of scope: 2x2 and per-detection noise (S^-1 then depends on the particle), miss terms, any change of the map, K > 64. */
+int slam_known_map_prepare_dev(slam_engine *e, const float *d_map /* [5][plane_stride] */, int plane_stride, int nlandmarks,
+                               float meas_var, float *d_prepared /* [6][plane_stride] */);
+int slam_localise_dev(slam_engine *e, const float *d_prepared, int plane_stride, int nlandmarks,
+                      const float *d_x, const float *d_y, const float *d_th, int n, float gate,
+                      uint8_t *d_assoc /* may be NULL */, int assoc_stride, int32_t *d_stats /* [n][3] */,
+                      float *d_loglik /* NULL: the engine's buffer, what slam_logweight_ekf_dev consumes */);
+int slam_localise_counts(slam_engine *e, int64_t counts[2]);        /* prepare launches, stage launches */
 /* THE DETECTOR: the detections of a frame made on the device from the engine's current scan (slam_scan_upload_host / _set_dev),
  * P = nbeams points in scan order — what fe_clean left, so a removed beam leaves no hole and the rule uses distances only, never
  * beam angles.  With jump2 = jump * jump, guard2, width2 and range2 likewise (each rounded once to float32), and every step below
@@ -1101,6 +1126,27 @@ int slam_pf_detect_fit_set(slam_pf *pf, const slam_detect_params *params /* NULL
  * noise == NULL: slam_pf_detect_fit_set(params, fit).  Under slam_pf_assoc_detcov_set this is the detector whose frames run. */
 int slam_pf_detect_noise_set(slam_pf *pf, const slam_detect_params *params /* NULL: off */, const slam_detect_fit *fit /* NULL: the centroid */,
                              const slam_detect_noise *noise /* NULL: no model */);
+/* Localisation in a known map inside the session (slam_known_map_prepare_dev at the switch, slam_localise_dev per frame; the
+ * session's frame loop: tests/_localise_spec.py frame_loop).  rows: host float32 [5][nlandmarks], planes mx, my, P_xx, P_xy, P_yy,
+ * P_xx < 0: the slot holds no landmark; the noise is the session's meas_var * I.  rows == NULL switches the mode off (and the
+ * detector with it): the session then runs exactly what it ran before the first call.  Accepted on a session created with
+ * n_landmarks == 0 on one GPU, whatever its map_layout (it has no maps).  SLAM_ERR_INVALID_ARG (slam_last_error says why), the
+ * session left as it was: a session with n_landmarks > 0; a sharded session; nlandmarks < 1 or > SLAM_MAX_OBS; a gate that is not
+ * finite and > 0; a log_clutter that is positive, NaN or infinite; a map value that is not finite; a landmark with P_xx + meas_var
+ * <= 0, P_yy + meas_var <= 0 or det (P + meas_var I) <= 0.  Everything is allocated at the switch, no frame allocates; calling it
+ * again replaces map and constants from the next frame on.
+ * While it is on, slam_pf_step(.., use_observations = 1) runs front launch (a refining session: motion + refine, and the REFINED
+ * poses go to the stage), the stage on the engine's current detections, slam_assoc_weight_dev with log_new = log_miss = 0 and no
+ * misses (left out when log_clutter == 0), slam_logweight_ekf_dev, scan, resample; a frame with use_observations = 0 is the
+ * frame of a session without the mode: plain weights.  slam_pf_detect_set / slam_pf_detect_fit_set are accepted while it is on
+ * (the detector's launch goes out in front of the frame's first launch); slam_pf_detect_noise_set with a model is refused: the
+ * noise is meas_var * I only.  Out of scope: sharded sessions, 2x2 and per-detection noise, miss terms, pruning, merging.
+ * slam_pf_known_map_device_view: the prepared map ([6][nlandmarks rounded up to 32]; NULL and 0 while the mode is off) and the
+ * stats ([n_particles][3] = matched, 0, dropped; indexed like slam_pf_view.score) of the last frame that ran the stage; any of the
+ * three pointers may be NULL.  SLAM_ERR_NOT_READY until a map was accepted once. */
+int slam_pf_known_map_set(slam_pf *pf, const float *rows /* host [5][nlandmarks]; NULL: off */, int nlandmarks,
+                          float gate, float log_clutter);
+int slam_pf_known_map_device_view(slam_pf *pf, const float **prepared, int32_t *nlandmarks, const int32_t **stats);
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
  * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
