@@ -785,6 +785,11 @@ class Engine:
     def ancestors_from_scan_dev(self, n, seed, frame, d_anc):
         self._ck(self.lib.slam_ancestors_from_scan_dev(self.h, n, seed, frame, _ptr(d_anc)), "ancestors_from_scan_dev")
 
+    def argmax_dev(self, d_values, n, d_index, d_value):
+        """``slam_argmax_dev``: index (int32) and value (float32) of the largest of d_values[0..n) to device memory: the lowest
+        index on ties, NaN never wins, index 0 with nothing but -inf and NaN."""
+        self._ck(self.lib.slam_argmax_dev(self.h, _ptr(d_values), n, _ptr(d_index), _ptr(d_value)), "argmax_dev")
+
     def ancestors_sharded_dev(self, d_first_all, n_total, n_local, rank, world, d_src, d_plan, d_pose_idx=None):
         """d_plan: int32[plan_words(world)] on the device: [0] anything moves, send_cnt[world], recv_cnt[world], ...
         d_pose_idx (optional): ancestor's position in an all-gather of the ranks' [x | y | theta] pose blocks."""

@@ -1,7 +1,7 @@
 // The covariance classes' update of the split layout, as a body that a launch of another kernel can carry in workgroups of
 // its own: the classes' update depends on the landmark update's stamps only and
-// nothing behind it in the frame depends on it, so it travels in the launch of the weights (resample_kernels.hip:
-// logweight_cov_kernel) — or, on a frame whose front launch made the weights, of the scan (quantise_scan_cov_kernel) — instead
+// nothing behind it in the frame depends on it, so it travels in the launch of the weights (weights_kernels.hip:
+// logweight_cov_kernel) — or, on a frame whose front launch made the weights, of the scan (scan_kernels.hip: quantise_scan_cov_kernel) — instead
 // of costing a launch of its own (4-5 us of a 0.12 ms frame).
 // No counterpart in the reference (it has no particles or landmarks).
 #pragma once

@@ -367,10 +367,7 @@ int slam_frame_front_dev(slam_engine* e, int slot, const float* d_src_x, const f
     FrontWeights fw{};
     bool weighted = false;
     if (weights && weights->d_logw && e->gate_frac_q16 == 0) {
-        if (e->bmax_buf.cap < sizeof(float) * (size_t)logweight_scratch_floats()) {
-            SLAM_HIP_TRY(e, e->bmax_buf.ensure(sizeof(float) * (size_t)logweight_scratch_floats()));
-            SLAM_HIP_TRY(e, hipMemsetAsync(e->bmax_buf.p, 0, e->bmax_buf.cap, e->stream));
-        }
+        if (int rc = slam_engine_bmax_ready(e)) return rc;
         fw = FrontWeights{ weights->score_gain, weights->d_logw, e->bmax_buf.as<float>(), nullptr, nullptr, &weighted };
     }
     SLAM_HIP_TRY(e, launch_frame_front(e->stream, sg, e->d_bx, e->d_by, e->nbeams, io, first_id, dp, sigma, seed,

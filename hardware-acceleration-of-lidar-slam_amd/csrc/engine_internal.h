@@ -400,6 +400,8 @@ __attribute__((visibility("hidden"))) int check_score_inputs(slam_engine* e, int
 __attribute__((visibility("hidden"))) int many_pose_grid(slam_engine* e, int slot, int nposes, slam::ScoreGrid* out);
 }  // namespace slam_detail
 // engine_resample.hip:
+// e->bmax_buf holds logweight_scratch_floats() floats, zeroed when it was made: in front of whichever launch leaves the block maxima
+__attribute__((visibility("hidden"))) int slam_engine_bmax_ready(slam_engine* e);
 // slam_logweight_dev / slam_logweight_ekf_dev (use_ekf) with, optionally, a split session's covariance classes brought up to
 // date by workgroups of the same launch (launch_logweight)
 extern "C" int slam_logweight_cov_dev(slam_engine* e, const float* d_score, bool use_ekf, float score_gain, int n, float* d_logw, float* d_max,

@@ -25,16 +25,22 @@ void philox_host(uint32_t c[4], uint32_t k0, uint32_t k1)
 
 }  // namespace
 
+int slam_engine_bmax_ready(slam_engine* e)
+{
+    if (e->bmax_buf.cap < sizeof(float) * (size_t)logweight_scratch_floats()) {   // block maxima + a ticket word kept at zero
+        SLAM_HIP_TRY(e, e->bmax_buf.ensure(sizeof(float) * (size_t)logweight_scratch_floats()));
+        SLAM_HIP_TRY(e, hipMemsetAsync(e->bmax_buf.p, 0, e->bmax_buf.cap, e->stream));
+    }
+    return SLAM_OK;
+}
+
 extern "C" {
 
 static int logweight_common(slam_engine* e, const float* d_score, const float* d_loglik, float score_gain, int n,
                             float* d_logw, float* d_max, const CovArgs* cov = nullptr, int cov_bound = 0)
 {
     if (n <= 0 || !d_logw) return SLAM_ERR_INVALID_ARG;
-    if (e->bmax_buf.cap < sizeof(float) * (size_t)logweight_scratch_floats()) {   // block maxima + a ticket word kept at zero
-        SLAM_HIP_TRY(e, e->bmax_buf.ensure(sizeof(float) * (size_t)logweight_scratch_floats()));
-        SLAM_HIP_TRY(e, hipMemsetAsync(e->bmax_buf.p, 0, e->bmax_buf.cap, e->stream));
-    }
+    if (int rc = slam_engine_bmax_ready(e)) return rc;
     const ProfScope prof(e, SLAM_PROF_WEIGHTS);
     // with a resample gate: the weights of a frame that did not resample carry into this one (device-side decision)
     const bool carry = e->gate_frac_q16 != 0 && e->carry_n == n;

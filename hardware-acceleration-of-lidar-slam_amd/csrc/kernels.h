@@ -628,7 +628,7 @@ hipError_t launch_class_gather(hipStream_t stream, const int32_t* cls_in, int32_
 // every particle: all landmarks "not seen yet", one class (a new epoch, as launch_split_from_rows)
 hipError_t launch_split_reset(hipStream_t stream, float* mean, const ClassStore& cs, int n, int32_t* h_live, uint32_t epoch);
 
-// ---- resample_kernels.hip (rows A11-A12; no reference counterpart): weights, resampling on one GPU, results and gathers
+// ---- weights_kernels.hip (row A11; no reference counterpart): the weights of a frame
 // carry / prev_resampled (optional): see logweight_kernel — the weights a frame without resample left behind
 // cov (optional): the same launch carries the covariance classes' update of cov_bound classes in workgroups of its own — cov_update_body.h;
 // cov->nlandmarks == 0: a frame without observations — only the list is brought up to date (classes whose last particle went
@@ -641,6 +641,21 @@ int logweight_scratch_floats();   // size of block_max_scratch: block maxima + t
 hipError_t launch_quantise_weights(hipStream_t stream, const float* logw, const float* d_max, int n, uint64_t* wq,
                                    uint64_t* d_sum);
 
+// ---- scan_kernels.hip (row A12): the integer CDF — staged over quantised weights, or quantise + tile scan in one pass
+hipError_t launch_prefix_sum(hipStream_t stream, const uint64_t* in, int n, uint64_t* out, uint64_t* block_scratch);
+int prefix_sum_scratch_elems(int n);
+int scan_tile_count(int n);   // 2048-element tiles of the fused quantise + scan
+// fused frame-loop form (the offsets then come straight from the tile-local scan: launch_offspring_from_scan).  The scan state is
+// cdf_local[n] followed by tile_total[ntiles] | tile_s16[ntiles] | tile_q16[ntiles] (the last two only with a gate:
+// carry != nullptr).  With a gate d_sum receives three values (total, S, Q) and d_shard_totals holds such triples.
+// cov (optional; ungated, block maxima): the launch carries the covariance classes' update as launch_logweight does — for a
+// frame whose front launch made the weights itself (launch_frame_front's FrontWeights), which has no weights' launch.
+hipError_t launch_quantise_scan(hipStream_t stream, const float* logw, const float* d_max, const float* block_max,
+                                int nblock_max, int n, uint64_t* cdf_local, uint64_t* tile_total, uint64_t* d_sum,
+                                float* carry = nullptr, uint64_t* tile_s16 = nullptr, uint64_t* tile_q16 = nullptr,
+                                unsigned int* ticket = nullptr, const CovArgs* cov = nullptr, int cov_bound = 0);
+
+// ---- resample_kernels.hip (row A12): the ESS gate, the comb's offspring offsets, the ancestors on one GPU
 // Where a resample stage reports roughly how many distinct ancestors it left: counter = one 8-byte-aligned pair of words
 // (device, zeroed once, left zeroed), h_out = {count, n} in mapped host memory.
 struct HeadsOut {
@@ -658,22 +673,10 @@ struct GateOut {
     int32_t* h_flag = nullptr;
     uint32_t seq = 0;
 };
-// fused frame-loop form (quantise + tile scan; offsets straight from the tile-local scan).  The scan state is
-// cdf_local[n] followed by tile_total[ntiles] | tile_s16[ntiles] | tile_q16[ntiles] (the last two only with a gate:
-// carry != nullptr).  With a gate d_sum receives three values (total, S, Q) and d_shard_totals holds such triples.
-// cov (optional; ungated, block maxima): the launch carries the covariance classes' update as launch_logweight does — for a
-// frame whose front launch made the weights itself (launch_frame_front's FrontWeights), which has no weights' launch.
-hipError_t launch_quantise_scan(hipStream_t stream, const float* logw, const float* d_max, const float* block_max,
-                                int nblock_max, int n, uint64_t* cdf_local, uint64_t* tile_total, uint64_t* d_sum,
-                                float* carry = nullptr, uint64_t* tile_s16 = nullptr, uint64_t* tile_q16 = nullptr,
-                                unsigned int* ticket = nullptr, const CovArgs* cov = nullptr, int cov_bound = 0);
 hipError_t launch_offspring_from_scan(hipStream_t stream, const uint64_t* cdf_local, const uint64_t* tile_total, int n,
                                       const uint64_t* d_base, const uint64_t* d_total, const uint64_t* d_shard_totals,
                                       int rank, int world, uint64_t seed, uint32_t frame, int64_t n_total,
                                       int32_t* first, uint32_t frac_q16 = 0, const GateOut& gate = GateOut());
-hipError_t launch_prefix_sum(hipStream_t stream, const uint64_t* in, int n, uint64_t* out, uint64_t* block_scratch);
-int prefix_sum_scratch_elems(int n);
-int scan_tile_count(int n);   // 2048-element tiles of the fused quantise + scan
 hipError_t launch_offspring_offsets(hipStream_t stream, const uint64_t* cdf, int n, const uint64_t* d_base,
                                     const uint64_t* d_total, uint64_t seed, uint32_t frame, int64_t n_total,
                                     int32_t* first);
@@ -691,6 +694,9 @@ hipError_t launch_ancestors_from_scan(hipStream_t stream, const uint64_t* cdf_lo
                                       uint64_t seed, uint32_t frame, int32_t* anc, uint32_t frac_q16 = 0,
                                       const GateOut& gate = GateOut(), const HeadsOut& heads = HeadsOut(),
                                       const SurvivorOut& survivors = SurvivorOut());
+
+// ---- estimate_kernels.hip: what is read out of a population — the heaviest particle, the sums for the mean, the gathers
+// index and value of the largest of v[0..n): lowest index on ties, NaN never wins, index 0 with nothing but -inf and NaN
 hipError_t launch_argmax(hipStream_t stream, const float* v, int n, int32_t* idx_out, float* val_out);
 // heaviest particle {logw, global id (int bits), x, y, theta} -> out5 (device) and optionally mapped host memory + seq
 hipError_t launch_best_particle(hipStream_t stream, const float* v, int n, const float* px, const float* py,

@@ -3,7 +3,8 @@
 //
 // No reference counterpart: the specification is DESIGN.md + oracle/slam_oracle_pf.c, matched bit for bit.
 
-#include "pf_common.h"
+#include "block_reduce.h"
+#include "resample_common.h"
 
 namespace slam {
 
@@ -19,16 +20,7 @@ __device__ __forceinline__ int64_t first_or_total(const int32_t* __restrict__ fi
     return idx < n_total ? (int64_t)first_all[idx] : n_total;
 }
 
-__device__ __forceinline__ int64_t last_with_first_le(const int32_t* __restrict__ first_all, int64_t n_total, int64_t j)
-{
-    int64_t lo = 0, hi = n_total;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)first_all[mid] <= j) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
-}
-
+// (last_with_first_le: resample_common.h)
 // ---- exchange with duplicates removed.  After a resample many slots share one ancestor; a remote ancestor's row
 // is sent ONCE per destination rank, however many of that rank's slots descend from it.  Both sides derive the
 // same order from first_all alone:
@@ -39,8 +31,8 @@ __device__ __forceinline__ int64_t last_with_first_le(const int32_t* __restrict_
 //               particles with offspring in d's slot range, in order: the q-th is the first a with
 //               P(a) = P(first ancestor of the run) + q.
 // Both counts are prefix sums over n elements (two-level: 2048-element tiles, then the tile totals).
-constexpr int kShardTile = 2048;                       // elements per workgroup in the flag scan
-constexpr int kShardItems = kShardTile / kBlock;       // per thread
+constexpr int kShardTile = kScanTile;                  // elements per workgroup in the flag scan: the tile of the CDF's scan
+constexpr int kShardItems = kScanItems;                // per thread
 
 // global ancestor of each of my slots: one thread per slot
 __global__ __launch_bounds__(kBlock) void shard_search_kernel(const int32_t* __restrict__ first_all, int64_t n_total, int n,
@@ -89,22 +81,13 @@ __global__ __launch_bounds__(kBlock) void shard_flag_scan_kernel(const int32_t* 
             f[k] = run;   // inclusive within the thread
         }
     }
-    // exclusive offset of this thread inside the tile: wave scan + wave totals through LDS
-    int32_t incl = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int32_t v = __shfl_up(incl, o, 64);
-        if ((int)(threadIdx.x & 63) >= o) incl += v;
-    }
-    if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int32_t woff = 0;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += s_wave[w];
-    const int32_t excl = woff + incl - run;
+    // exclusive offset of this thread inside the tile
+    int32_t total;
+    const int32_t excl = block_inclusive_scan<int32_t, false>(run, s_wave, total) - run;
 #pragma unroll
     for (int k = 0; k < kShardItems; ++k)
         if (base + k < n) pfx[(int64_t)y * n + base + k] = excl + f[k];
-    if (threadIdx.x == kBlock - 1) btot[y * ntiles + blockIdx.x] = woff + incl;
+    if (threadIdx.x == kBlock - 1) btot[y * ntiles + blockIdx.x] = total;
 }
 
 __device__ __forceinline__ int32_t shard_prefix(const int32_t* __restrict__ pfx, const int32_t* __restrict__ boff, int y,

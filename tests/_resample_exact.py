@@ -12,7 +12,7 @@ tests/_f64_pf.py, not from oracle/slam_oracle_pf.c.  A grand total of 0 (or >= 2
 formula above then gives ancestor N - 1 for every slot by itself.
 
 The kernels' constants appear here as plain numbers: 2048-element scan tiles, 32-element blocks inside a tile, 256 slots
-per workgroup (csrc/resample_kernels.hip: kScanTile, kSub, kBlock).
+per workgroup (csrc/resample_common.h: kScanTile; csrc/pf_common.h: kBlock).
 """
 import functools
 from bisect import bisect_right

@@ -1,6 +1,6 @@
 """One workgroup scores AND updates its 64 particles and makes their log-weights (csrc/front_kernels.hip:
 frame_particle_kernel; score_body.h: score_stage / STAGED; ekf_split_body.h: ekf_split_group / kPosesStaged;
-resample_kernels.hip: quantise_scan_cov_kernel): a survivor-rows frame of the split layout with 8 particles per wavefront then
+scan_kernels.hip: quantise_scan_cov_kernel): a survivor-rows frame of the split layout with 8 particles per wavefront then
 has no weights' launch, and the covariance classes' update rides in the scan's launch.  Not a bit may change.
 
 The comparison partner is the same session with frame_fusion_set(False) — the separate launches, which
