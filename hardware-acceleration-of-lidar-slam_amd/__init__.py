@@ -153,6 +153,8 @@ SIGNATURES = {
     "slam_known_map_prepare_dev": (_i, [_vp, _vp, _i, _i, _f, _vp]),
     "slam_localise_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp]),
     "slam_localise_counts": (_i, [_vp, _vp]),
+    "slam_localise_detcov_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp]),
+    "slam_localise_detcov_count": (_i, [_vp, _vp]),
     "slam_detect_params_default": (None, [_vp]),
     "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
     "slam_detect_count": (_i, [_vp, _vp]),
@@ -215,6 +217,7 @@ SIGNATURES = {
     "slam_pf_assoc_weight_set": (_i, [_vp, _f, _f, _f, _i]),
     "slam_pf_assoc_weight_device_view": (_i, [_vp, _vp, _vp]),
     "slam_pf_known_map_set": (_i, [_vp, _vp, _i, _f, _f]),
+    "slam_pf_known_map_detcov_set": (_i, [_vp, _vp, _i, _f, _f]),
     "slam_pf_known_map_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_detect_set": (_i, [_vp, _vp]),
     "slam_pf_detect_fit_set": (_i, [_vp, _vp, _vp]),
@@ -521,6 +524,18 @@ class Engine:
         c = (C.c_int64 * 2)()
         self._ck(self.lib.slam_localise_counts(self.h, c), "localise_counts")
         return int(c[0]), int(c[1])
+
+    def localise_detcov_dev(self, d_map, plane_stride, nlandmarks, d_x, d_y, d_th, n, gate, d_assoc, assoc_stride, d_stats, d_loglik=None):
+        """``slam_localise_detcov_dev``: the engine's detections AND THEIR COVARIANCES against ONE map float32 [5][plane_stride] as it
+        was given, per particle: stats, log-likelihood and table as ``localise_dev``."""
+        self._ck(self.lib.slam_localise_detcov_dev(self.h, _ptr(d_map), plane_stride, nlandmarks, _ptr(d_x), _ptr(d_y), _ptr(d_th), n, gate,
+                                                   _ptr(d_assoc), assoc_stride, _ptr(d_stats), _ptr(d_loglik)), "localise_detcov_dev")
+
+    def localise_detcov_count(self):
+        """-> stage launches under per-detection covariances of this engine so far."""
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_localise_detcov_count(self.h, C.byref(c)), "localise_detcov_count")
+        return int(c.value)
 
     def assoc_counts(self):
         """-> (associate launches, assoc-update launches) of this engine so far."""
@@ -1297,8 +1312,19 @@ class PfSession:
         assert rows.ndim == 2 and rows.shape[0] == 5
         self.e._ck(self.e.lib.slam_pf_known_map_set(self.h, _ptr(rows), rows.shape[1], gate, log_clutter), "pf_known_map_set")
 
+    def known_map_detcov_set(self, rows, gate: float = 0.0, log_clutter: float = 0.0):
+        """``slam_pf_known_map_detcov_set``: ``known_map_set`` for the form of the stage that weighs every detection under its own
+        covariance (uploaded with the detections, or the detector's noise model); rows None switches it off."""
+        if rows is None:
+            self.e._ck(self.e.lib.slam_pf_known_map_detcov_set(self.h, None, 0, 0.0, 0.0), "pf_known_map_detcov_set")
+            return
+        rows = _np(rows, np.float32)
+        assert rows.ndim == 2 and rows.shape[0] == 5
+        self.e._ck(self.e.lib.slam_pf_known_map_detcov_set(self.h, _ptr(rows), rows.shape[1], gate, log_clutter), "pf_known_map_detcov_set")
+
     def known_map_view(self):
-        """``slam_pf_known_map_device_view``: the prepared map float32 [6][L rounded up to 32] (None while the mode is off), L, and
+        """``slam_pf_known_map_device_view``: the prepared map float32 [6][L rounded up to 32] (None while the mode is off and under
+        ``known_map_detcov_set``), L, and
         the last stage's stats int32 [n][3] = matched, 0, dropped."""
         p, st, L = C.c_void_p(), C.c_void_p(), C.c_int32(0)
         self.e._ck(self.e.lib.slam_pf_known_map_device_view(self.h, C.byref(p), C.byref(L), C.byref(st)), "pf_known_map_device_view")

@@ -1,6 +1,7 @@
 // engine_localise.hip — localisation in a known landmark map behind the C ABI (localise_kernels.hip): the prepared map, made once
 // per map, and the stage of a frame — the engine's current detections against that map, per particle, into the engine's
-// log-likelihood buffer (what slam_logweight_ekf_dev consumes) or the caller's.
+// log-likelihood buffer (what slam_logweight_ekf_dev consumes) or the caller's.  Under the detections' own covariances
+// (slam_localise_detcov_dev) nothing is prepared: the stage reads the map as it was given.
 
 #include <hip/hip_runtime.h>
 
@@ -34,7 +35,7 @@ int slam_localise_dev(slam_engine* e, const float* d_prepared, int plane_stride,
     if (n == 0) return SLAM_OK;
     if (!d_loglik) SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
     LocaliseArgs a;
-    a.prep = d_prepared;
+    a.map = d_prepared;
     a.plane_stride = plane_stride;
     a.nlandmarks = nlandmarks;
     a.x = d_x;
@@ -52,6 +53,48 @@ int slam_localise_dev(slam_engine* e, const float* d_prepared, int plane_stride,
     SLAM_HIP_TRY(e, launch_localise(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
     if (!d_loglik) e->ll_n = n;
     e->localise_launches[1]++;
+    return SLAM_OK;
+}
+
+int slam_localise_detcov_dev(slam_engine* e, const float* d_map, int plane_stride, int nlandmarks, const float* d_x, const float* d_y,
+                             const float* d_th, int n, float gate, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats, float* d_loglik)
+{
+    SLAM_ENTER(e);
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (n < 0 || nlandmarks < 1 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || (d_assoc && assoc_stride < nlandmarks) ||
+        !(gate > 0.0f && gate <= std::numeric_limits<float>::max()) || !d_map || (n > 0 && (!d_x || !d_y || !d_th || !d_stats)))
+        return SLAM_ERR_INVALID_ARG;
+    if (e->ndet < 0 || !e->det_has_cov) return SLAM_ERR_NOT_READY;
+    if (n == 0) return SLAM_OK;
+    if (!d_loglik) SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
+    LocaliseArgs a;
+    a.map = d_map;
+    a.plane_stride = plane_stride;
+    a.nlandmarks = nlandmarks;
+    a.x = d_x;
+    a.y = d_y;
+    a.th = d_th;
+    a.n = n;
+    a.det_zx = e->d_det_zx;
+    a.det_zy = e->d_det_zy;
+    a.ndet = e->ndet;
+    a.gate = gate;
+    a.assoc = d_assoc;
+    a.assoc_stride = assoc_stride;
+    a.stats = d_stats;
+    a.loglik = d_loglik ? d_loglik : e->ll_buf.as<float>();
+    const DetCovArgs dq{ e->d_det_qxx, e->d_det_qxy, e->d_det_qyy, e->ndet };
+    SLAM_HIP_TRY(e, launch_localise_detcov(e->stream, a, dq, e->prof_next(SLAM_PROF_PAGES)));
+    if (!d_loglik) e->ll_n = n;
+    e->localise_detcov_launches++;
+    return SLAM_OK;
+}
+
+int slam_localise_detcov_count(slam_engine* e, int64_t* launches)
+{
+    SLAM_ENTER(e);
+    if (!launches) return SLAM_ERR_INVALID_ARG;
+    *launches = e->localise_detcov_launches;
     return SLAM_OK;
 }
 

@@ -261,7 +261,7 @@ struct KnownMapArgs {
 // one thread per slot of the plane stride
 hipError_t launch_known_map_prepare(hipStream_t stream, const KnownMapArgs& a, const EventPair* ev = nullptr);
 struct LocaliseArgs {
-    const float* prep;     // the prepared map
+    const float* map;      // the prepared map [6][plane_stride] — launch_localise_detcov: the map as it was given [5][plane_stride]
     int plane_stride;
     int nlandmarks;        // 1 .. SLAM_MAX_OBS
     const float *x, *y, *th;
@@ -276,6 +276,9 @@ struct LocaliseArgs {
 };
 // one wavefront per particle at a time, persistent workgroups; the prepared map staged in LDS where it fits
 hipError_t launch_localise(hipStream_t stream, const LocaliseArgs& a, const EventPair* ev = nullptr);
+// ... under S = P + R_w(theta_i, k), Q_k per detection (specification: tests/_localise_detcov_spec.py; q.ndet == a.ndet): nothing
+// can be prepared, a.map is the RAW map (KnownMapArgs::map) and S^-1 is formed per (landmark, detection) pair
+hipError_t launch_localise_detcov(hipStream_t stream, const LocaliseArgs& a, const DetCovArgs& q, const EventPair* ev = nullptr);
 // ---- evidence_kernels.hip: landmark existence evidence (specification: tests/_evidence_spec.py).  One byte
 // c in [0, cmax] per (particle, landmark slot) beside the rows; behind the update of a frame a matched landmark gains `hit`, a
 // visible unmatched one loses `miss`, and one that cannot pay is pruned: its slot gets the bits of a slot that was never used.

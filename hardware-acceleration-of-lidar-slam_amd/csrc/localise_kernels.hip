@@ -20,8 +20,17 @@
 // map is staged in LDS once per workgroup where it fits (24 B per landmark, padded to whole batches: nothing is predicated) and
 // read from memory, L2-resident, where it does not.  No row is read and none is written: a frame without a table pointer reads
 // 12 B and writes 16 B per particle.
+//
+// Under a covariance PER DETECTION (specification: tests/_localise_detcov_spec.py) S = P + R_w(theta_i, k) depends on the particle
+// and the detection, nothing can be prepared, and localise_detcov_kernel is the same body on the RAW map [5][stride]: the noise is
+// AssocNoiseDet (assoc_noise.h: lane k forms R_w(theta_i, k) once, beside its world point; the loop over k reads point and noise as
+// wave-uniform values and forms (P + R_w)^-1 per (landmark, detection) pair — the two landmarks of a lane are the two independent
+// reciprocal chains in flight; ekf_rcp's wave-uniform range test is a branch, which keeps the loop from being unrolled across
+// detections), a slot without a landmark gets its NaN mean where the map is read
+// (staged: once per workgroup, 20 B per landmark), and lane k rebuilds its winner's det S from one read of the landmark's three
+// covariance planes and its own R_w for hl = 0.5 log det S.  Everything else — minima, accumulation order, stats, table — is shared.
 
-#include "ekf_wave.h"
+#include "assoc_noise.h"
 
 namespace slam {
 
@@ -31,18 +40,18 @@ typedef unsigned long long u64;
 
 constexpr unsigned kLocStagedMax = 2048;   // landmarks (whole batches) up to which the prepared map is staged: 48 KB
 
-// LDS of one workgroup, in multiples of 16 bytes: [staged: map 6 x Lr floats] | per wavefront: best[64] u64 | acc[128] float |
+// LDS of one workgroup, in multiples of 16 bytes: [staged: map `planes` x Lr floats] | per wavefront: best[64] u64 | acc[128] float |
 // [table wanted: row[L rounded up to 16] u8]
 struct LocLds {
     unsigned batches, Lr, rowb, map_bytes, per_wave;
 };
-__host__ __device__ inline LocLds loc_lds(unsigned L, bool staged, bool table)
+__host__ __device__ inline LocLds loc_lds(unsigned L, bool staged, bool table, unsigned planes)
 {
     LocLds s;
     s.batches = (L + 127u) / 128u;
     s.Lr = s.batches * 128u;
     s.rowb = table ? (L + 15u) & ~15u : 0u;
-    s.map_bytes = staged ? 6u * 4u * s.Lr : 0u;
+    s.map_bytes = staged ? planes * 4u * s.Lr : 0u;
     s.per_wave = 64u * 8u + 128u * 4u + s.rowb;
     return s;
 }
@@ -76,9 +85,10 @@ __global__ __launch_bounds__(256) void known_map_prepare_kernel(KnownMapArgs a)
     a.prep[5 * ps + l] = h.hl;
 }
 
-// the prepared map as a wavefront reads it: the two landmarks of a lane in batch b, and hl of one landmark
+// the map as a wavefront reads it: the two landmarks of a lane in batch b (planes 0 .. 4), and one plane of one landmark.
+// RAW: the map as it was given (mx, my, P_xx, P_xy, P_yy), else the prepared one (mx, my, i00, i01, i11, hl)
 struct LocMapLds {
-    const float* s;   // [6][Lr], NaN means from L on
+    const float* s;   // [planes][Lr], NaN means from L on and (RAW) where the slot holds no landmark
     unsigned Lr;
     __device__ __forceinline__ void pair(unsigned b, unsigned lane, v2f (&m)[5]) const
     {
@@ -86,10 +96,10 @@ struct LocMapLds {
 #pragma unroll
         for (int p = 0; p < 5; ++p) m[p] = (v2f){s[(unsigned)p * Lr + l], s[(unsigned)p * Lr + l + 64u]};
     }
-    __device__ __forceinline__ float hl(unsigned l) const { return s[5u * Lr + l]; }
+    __device__ __forceinline__ float plane(unsigned p, unsigned l) const { return s[p * Lr + l]; }
 };
-struct LocMapMem {
-    const float* g;   // [6][ps]
+template <bool RAW> struct LocMapMem {
+    const float* g;   // [planes][ps]
     unsigned ps, L;
     __device__ __forceinline__ void pair(unsigned b, unsigned lane, v2f (&m)[5]) const
     {
@@ -101,15 +111,29 @@ struct LocMapMem {
             const unsigned c = in ? l : 0u;   // clamped index + select instead of a predicated load
 #pragma unroll
             for (int p = 0; p < 5; ++p) m[p][t] = g[(size_t)p * ps + c];
-            m[0][t] = in ? m[0][t] : nan;
+            m[0][t] = in && !(RAW && m[2][t] < 0.0f) ? m[0][t] : nan;   // (RAW: the update's own first-sighting test)
         }
     }
-    __device__ __forceinline__ float hl(unsigned l) const { return g[(size_t)5 * ps + l]; }
+    __device__ __forceinline__ float plane(unsigned p, unsigned l) const { return g[(size_t)p * ps + l]; }
 };
 
-template <class MAP>
-__device__ __forceinline__ void localise_particle(const LocaliseArgs& a, const MAP& map, int i, unsigned lane, const LocLds& lds, u64* s_best,
-                                                  float* s_acc, unsigned char* s_row)
+// The noise of the stage: LocNoisePrepared — meas_var * I, S^-1 and hl are planes of the prepared map — or AssocNoiseDet on the raw map
+struct LocNoisePrepared {
+    static constexpr bool kPerDetection = false;
+    __device__ __forceinline__ LocNoisePrepared(const DetCovArgs&, float, float) {}
+};
+// 0.5 log det S of lane k's winner wl
+template <class MAP> __device__ __forceinline__ float loc_half_logdet(const LocNoisePrepared&, const MAP& map, unsigned wl) { return map.plane(5u, wl); }
+template <class MAP> __device__ __forceinline__ float loc_half_logdet(const AssocNoiseDet& r, const MAP& map, unsigned wl)
+{
+    const float a = map.plane(2u, wl) + r.rxx, b = map.plane(3u, wl) + r.rxy, cc = map.plane(4u, wl) + r.ryy;   // ekf_aniso_update_one's det
+    const float det = a * cc - b * b;
+    return 0.5f * ekf_log(det);
+}
+
+template <class NOISE, class MAP>
+__device__ __forceinline__ void localise_particle(const LocaliseArgs& a, const DetCovArgs& q, const MAP& map, int i, unsigned lane, const LocLds& lds,
+                                                  u64* s_best, float* s_acc, unsigned char* s_row)
 {
     const unsigned K = (unsigned)a.ndet;
     unsigned* s_row32 = reinterpret_cast<unsigned*>(s_row);
@@ -126,17 +150,23 @@ __device__ __forceinline__ void localise_particle(const LocaliseArgs& a, const M
     const float zxk = lane < K ? a.det_zx[lane] : 0.0f, zyk = lane < K ? a.det_zy[lane] : 0.0f;
     float wxk, wyk;
     ekf_first_sighting<float>(zxk, zyk, st, ct, px, py, wxk, wyk);
+    const NOISE noise(q, st, ct);   // (per detection: lane k's R_w(theta_i, k))
 
     const float inf = __uint_as_float(0x7f800000u);
     for (unsigned b = 0; b < lds.batches; ++b) {
         v2f m[5];
         map.pair(b, lane, m);
-        const v2f mx = m[0], my = m[1], i00 = m[2], i01 = m[3], i11 = m[4];
+        const v2f mx = m[0], my = m[1];
         // c. the cheapest detection of each landmark
         v2f best = bc2(inf);
         unsigned bk[2] = { 0u, 0u };
-        for (unsigned k = 0; k < K; ++k) {
+        const auto pair_cost = [&](unsigned k) {
             const v2f wx = bc2(lane_value(wxk, (int)k)), wy = bc2(lane_value(wyk, (int)k));
+            v2f i00 = m[2], i01 = m[3], i11 = m[4];   // the prepared S^-1 — or (P + R_w(theta_i, k))^-1 of this pair
+            if constexpr (NOISE::kPerDetection) {
+                const EkfShared<v2f> h = noise.inverse(m[2], m[3], m[4], k);
+                i00 = h.i00, i01 = h.i01, i11 = h.i11;
+            }
             const v2f dx = wx - mx, dy = wy - my;
             const v2f t0 = i00 * dx + i01 * dy, t1 = i01 * dx + i11 * dy;
             const v2f maha = dx * t0 + dy * t1;
@@ -146,7 +176,8 @@ __device__ __forceinline__ void localise_particle(const LocaliseArgs& a, const M
                 best[t] = take ? maha[t] : best[t];
                 bk[t] = take ? k : bk[t];
             }
-        }
+        };
+        for (unsigned k = 0; k < K; ++k) pair_cost(k);
         // d. candidates post to their detection's minimum (a NaN mean — no landmark, padding — left best at +inf)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -164,7 +195,7 @@ __device__ __forceinline__ void localise_particle(const LocaliseArgs& a, const M
     float term = 0.0f;
     if (matched) {
         const float maha = __uint_as_float((unsigned)(won >> 32));
-        term = (-(0.5f * maha) - map.hl(wl)) - 1.8378770664f;
+        term = (-(0.5f * maha) - loc_half_logdet(noise, map, wl)) - 1.8378770664f;
         if (lds.rowb) s_row[wl] = (unsigned char)lane;
     }
     const u64 mm = __ballot(matched);
@@ -197,13 +228,15 @@ __device__ __forceinline__ void localise_particle(const LocaliseArgs& a, const M
     }
 }
 
-template <bool STAGED> __global__ __launch_bounds__(kEkfWaves * 64) void localise_kernel(LocaliseArgs a)
+// RAW: a.map is the map as it was given and NOISE reads q; else the prepared map (q is not read)
+template <bool STAGED, bool RAW, class NOISE> __device__ __forceinline__ void localise_body(const LocaliseArgs& a, const DetCovArgs& q)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr unsigned kPlanes = RAW ? 5u : 6u;
     const unsigned lane = threadIdx.x & 63u;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const unsigned L = (unsigned)a.nlandmarks;
-    const LocLds lds = loc_lds(L, STAGED, a.assoc != nullptr);
+    const LocLds lds = loc_lds(L, STAGED, a.assoc != nullptr, kPlanes);
     unsigned char* mine = smem + lds.map_bytes + (unsigned)wave * lds.per_wave;
     u64* s_best = reinterpret_cast<u64*>(mine);
     float* s_acc = reinterpret_cast<float*>(s_best + 64);
@@ -212,17 +245,48 @@ template <bool STAGED> __global__ __launch_bounds__(kEkfWaves * 64) void localis
     if constexpr (STAGED) {
         float* s_map = reinterpret_cast<float*>(smem);
         const float nan = __uint_as_float(0x7fc00000u);
-        for (unsigned l = threadIdx.x; l < lds.Lr; l += kEkfWaves * 64u)
+        const size_t ps = (size_t)a.plane_stride;
+        for (unsigned l = threadIdx.x; l < lds.Lr; l += kEkfWaves * 64u) {
+            // (RAW padding: P = I, whose terms are finite — the values are never read as a landmark's)
+            const bool seen = l < L && !(RAW && a.map[2 * ps + l] < 0.0f);
 #pragma unroll
-            for (unsigned p = 0; p < 6u; ++p)
-                s_map[p * lds.Lr + l] = l < L ? a.prep[(size_t)p * (size_t)a.plane_stride + l] : (p == 0u ? nan : 0.0f);
+            for (unsigned p = 0; p < kPlanes; ++p) {
+                const float pad = RAW && (p == 2u || p == 4u) ? 1.0f : 0.0f;
+                s_map[p * lds.Lr + l] = p == 0u ? (seen ? a.map[l] : nan) : (l < L ? a.map[p * ps + l] : pad);
+            }
+        }
         __syncthreads();   // (the only workgroup barrier: from here on a wavefront is on its own)
         const LocMapLds map{ s_map, lds.Lr };
-        for (int i = first; i < a.n; i += step) localise_particle(a, map, i, lane, lds, s_best, s_acc, s_row);
+        for (int i = first; i < a.n; i += step) localise_particle<NOISE>(a, q, map, i, lane, lds, s_best, s_acc, s_row);
     } else {
-        const LocMapMem map{ a.prep, (unsigned)a.plane_stride, L };
-        for (int i = first; i < a.n; i += step) localise_particle(a, map, i, lane, lds, s_best, s_acc, s_row);
+        const LocMapMem<RAW> map{ a.map, (unsigned)a.plane_stride, L };
+        for (int i = first; i < a.n; i += step) localise_particle<NOISE>(a, q, map, i, lane, lds, s_best, s_acc, s_row);
     }
+}
+
+template <bool STAGED> __global__ __launch_bounds__(kEkfWaves * 64) void localise_kernel(LocaliseArgs a)
+{
+    localise_body<STAGED, false, LocNoisePrepared>(a, DetCovArgs{});
+}
+
+// ... on the raw map under S = P + R_w(theta_i, k), Q_k per detection
+template <bool STAGED> __global__ __launch_bounds__(kEkfWaves * 64) void localise_detcov_kernel(LocaliseArgs a, DetCovArgs q)
+{
+    localise_body<STAGED, true, AssocNoiseDet>(a, q);
+}
+
+// a grid that fills the machine once: as many workgroups as are resident together, or as the particles need
+template <class KERNEL> hipError_t loc_grid(KERNEL kernel, int n, size_t lds, int* blocks)
+{
+    const int need = (n + kEkfWaves - 1) / kEkfWaves;
+    int dev = 0, cus = 0, per_cu = 0;
+    hipError_t err = hipGetDevice(&dev);
+    if (err == hipSuccess) err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (err == hipSuccess) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kEkfWaves * 64, lds);
+    if (err != hipSuccess) return err;
+    const int64_t resident = (int64_t)cus * per_cu;
+    *blocks = resident > 0 && resident < need ? (int)resident : need;
+    return hipSuccess;
 }
 
 }  // namespace
@@ -230,7 +294,7 @@ template <bool STAGED> __global__ __launch_bounds__(kEkfWaves * 64) void localis
 bool localise_args_ok(const LocaliseArgs& a)
 {
     return !(a.nlandmarks < 1 || a.nlandmarks > SLAM_MAX_OBS || a.plane_stride < a.nlandmarks || a.ndet < 0 ||
-             a.ndet > SLAM_MAX_DETECTIONS || (a.assoc && a.assoc_stride < a.nlandmarks) || !a.prep || !a.stats || !a.loglik);
+             a.ndet > SLAM_MAX_DETECTIONS || (a.assoc && a.assoc_stride < a.nlandmarks) || !a.map || !a.stats || !a.loglik);
 }
 
 hipError_t launch_known_map_prepare(hipStream_t stream, const KnownMapArgs& a, const EventPair* ev)
@@ -247,22 +311,30 @@ hipError_t launch_localise(hipStream_t stream, const LocaliseArgs& a, const Even
     if (a.n <= 0) return hipSuccess;
     if (!localise_args_ok(a)) return hipErrorInvalidValue;
     const bool staged = (unsigned)(a.nlandmarks + 127) / 128u * 128u <= kLocStagedMax;
-    const LocLds s = loc_lds((unsigned)a.nlandmarks, staged, a.assoc != nullptr);
+    const LocLds s = loc_lds((unsigned)a.nlandmarks, staged, a.assoc != nullptr, 6u);
     const size_t lds = (size_t)s.map_bytes + (size_t)kEkfWaves * s.per_wave;   // at most 60 KB staged, 36 KB from memory
-    // a grid that fills the machine once: as many workgroups as are resident together, or as the particles need
-    const int need = (a.n + kEkfWaves - 1) / kEkfWaves;
-    int dev = 0, cus = 0, per_cu = 0;
-    hipError_t err = hipGetDevice(&dev);
-    if (err == hipSuccess) err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (err == hipSuccess)
-        err = staged ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, localise_kernel<true>, kEkfWaves * 64, lds)
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, localise_kernel<false>, kEkfWaves * 64, lds);
-    if (err != hipSuccess) return err;
-    const int64_t resident = (int64_t)cus * per_cu;
-    const int blocks = resident > 0 && resident < need ? (int)resident : need;
+    int blocks = 0;
+    if (hipError_t err = staged ? loc_grid(localise_kernel<true>, a.n, lds, &blocks) : loc_grid(localise_kernel<false>, a.n, lds, &blocks)) return err;
     if (ev) (void)hipEventRecord(ev->start, stream);
     if (staged) localise_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
     else localise_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
+    if (ev) (void)hipEventRecord(ev->stop, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_localise_detcov(hipStream_t stream, const LocaliseArgs& a, const DetCovArgs& q, const EventPair* ev)
+{
+    if (a.n <= 0) return hipSuccess;
+    if (!localise_args_ok(a) || q.ndet != a.ndet || (q.ndet > 0 && (!q.qxx || !q.qxy || !q.qyy))) return hipErrorInvalidValue;
+    const bool staged = (unsigned)(a.nlandmarks + 127) / 128u * 128u <= kLocStagedMax;   // the same landmark cap: 40 KB of map
+    const LocLds s = loc_lds((unsigned)a.nlandmarks, staged, a.assoc != nullptr, 5u);
+    const size_t lds = (size_t)s.map_bytes + (size_t)kEkfWaves * s.per_wave;   // at most 52 KB staged, 36 KB from memory
+    int blocks = 0;
+    if (hipError_t err = staged ? loc_grid(localise_detcov_kernel<true>, a.n, lds, &blocks) : loc_grid(localise_detcov_kernel<false>, a.n, lds, &blocks))
+        return err;
+    if (ev) (void)hipEventRecord(ev->start, stream);
+    if (staged) localise_detcov_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
+    else localise_detcov_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
     if (ev) (void)hipEventRecord(ev->stop, stream);
     return hipGetLastError();
 }

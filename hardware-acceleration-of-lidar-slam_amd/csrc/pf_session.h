@@ -189,6 +189,7 @@ struct slam_pf {
     // particles share (slam_localise_dev on the prepared map, then the clutter term) and weighs with the result; no map is kept
     // per particle and none is changed.  The detector switches are accepted while it is on.
     bool known_on = false;
+    bool known_detcov = false;        // slam_pf_known_map_detcov_set: the stage under the detections' own covariances, on the map as given
     bool known_ll = false;            // the engine's log-likelihood buffer was last claimed by this mode
     int known_L = 0, known_Lp = 0;    // landmarks; plane stride of the prepared map (known_L rounded up to 32)
     size_t known_cap = 0;             // floats of the allocation behind known_prep

@@ -602,7 +602,7 @@ int slam_pf_detect_noise_set(slam_pf* pf, const slam_detect_params* params, cons
                                         "(slam_pf_known_map_set)");
         return SLAM_ERR_INVALID_ARG;
     }
-    if (pf->known_on && noise) {
+    if (pf->known_on && !pf->known_detcov && noise) {
         snprintf(e->err, sizeof e->err, "localisation in a known map weighs with meas_var * I: the detector's noise model cannot be "
                                         "switched on (slam_pf_detect_set / slam_pf_detect_fit_set)");
         return SLAM_ERR_INVALID_ARG;
@@ -628,7 +628,8 @@ int slam_pf_detect_noise_set(slam_pf* pf, const slam_detect_params* params, cons
     return SLAM_OK;
 }
 
-int slam_pf_known_map_set(slam_pf* pf, const float* rows, int nlandmarks, float gate, float log_clutter)
+// detcov: the stage under the detections' own covariances (slam_pf_known_map_detcov_set) — nothing is prepared, meas_var is not read
+static int known_map_set(slam_pf* pf, const float* rows, int nlandmarks, float gate, float log_clutter, bool detcov)
 {
     if (!pf) return SLAM_ERR_INVALID_ARG;
     slam_engine* e = pf->e;
@@ -636,10 +637,12 @@ int slam_pf_known_map_set(slam_pf* pf, const float* rows, int nlandmarks, float 
         if (pf->known_on) {
             pf->detect_on = false;
             pf->detect_fit_on = false;
+            pf->detect_noise_on = false;
         }
         if (pf->known_ll) e->ll_n = -1;   // (the stage's log-likelihoods are nobody's any more)
         pf->known_ll = false;
         pf->known_on = false;
+        pf->known_detcov = false;
         return SLAM_OK;
     }
     if (pf->L != 0 || pf->comm) {
@@ -661,6 +664,13 @@ int slam_pf_known_map_set(slam_pf* pf, const float* rows, int nlandmarks, float 
     for (size_t l = 0; l < L; ++l) {
         const float pxx = rows[2 * L + l], pxy = rows[3 * L + l], pyy = rows[4 * L + l];
         if (pxx < 0.0f) continue;   // the slot holds no landmark
+        if (detcov) {   // P alone: every Q_k is positive definite, so P + R_w is wherever P is positive semi-definite
+            if (!(pyy >= 0.0f && pxx * pyy - pxy * pxy >= 0.0f)) {
+                snprintf(e->err, sizeof e->err, "known map: landmark %zu has no positive semi-definite P", l);
+                return SLAM_ERR_INVALID_ARG;
+            }
+            continue;
+        }
         const float a = pxx + q, c = pyy + q;
         const float det = a * c - pxy * pxy;   // (the prepare kernel's own operations)
         if (!(a > 0.0f && c > 0.0f && det > 0.0f)) {
@@ -690,7 +700,10 @@ int slam_pf_known_map_set(slam_pf* pf, const float* rows, int nlandmarks, float 
     float* raw = pf->known_prep + 6 * Lp;
     pf->known_on = false;
     SLAM_HIP_TRY(e, hipMemcpy(raw, h.data(), 5 * Lp * sizeof(float), hipMemcpyHostToDevice));
-    if (int rc = slam_known_map_prepare_dev(e, raw, (int)Lp, nlandmarks, q, pf->known_prep)) return rc;
+    if (!detcov)
+        if (int rc = slam_known_map_prepare_dev(e, raw, (int)Lp, nlandmarks, q, pf->known_prep)) return rc;
+    if (!detcov && pf->detect_noise_on) pf->detect_noise_on = false;   // (this form takes no model: the detector goes on without it)
+    pf->known_detcov = detcov;
     pf->known_L = nlandmarks;
     pf->known_Lp = (int)Lp;
     pf->known_gate = gate;
@@ -699,11 +712,21 @@ int slam_pf_known_map_set(slam_pf* pf, const float* rows, int nlandmarks, float 
     return SLAM_OK;
 }
 
+int slam_pf_known_map_set(slam_pf* pf, const float* rows, int nlandmarks, float gate, float log_clutter)
+{
+    return known_map_set(pf, rows, nlandmarks, gate, log_clutter, false);
+}
+
+int slam_pf_known_map_detcov_set(slam_pf* pf, const float* rows, int nlandmarks, float gate, float log_clutter)
+{
+    return known_map_set(pf, rows, nlandmarks, gate, log_clutter, true);
+}
+
 int slam_pf_known_map_device_view(slam_pf* pf, const float** prepared, int32_t* nlandmarks, const int32_t** stats)
 {
     if (!pf) return SLAM_ERR_INVALID_ARG;
     if (!pf->known_stats) return SLAM_ERR_NOT_READY;
-    if (prepared) *prepared = pf->known_on ? pf->known_prep : nullptr;
+    if (prepared) *prepared = pf->known_on && !pf->known_detcov ? pf->known_prep : nullptr;
     if (nlandmarks) *nlandmarks = pf->known_on ? pf->known_L : 0;
     if (stats) *stats = pf->known_stats;
     return SLAM_OK;

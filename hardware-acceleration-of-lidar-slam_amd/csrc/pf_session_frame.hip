@@ -310,8 +310,11 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
     const int64_t stride = pf->row_stride();
     float* dst = f.dst;
     if (f.localise) {   // a known map (no maps of the session's own): the stage on the poses the front launch left, the clutter term, the weights
-        if (int rc = slam_localise_dev(e, pf->known_prep, pf->known_Lp, pf->known_L, dst, dst + sn, dst + 2 * sn, n, pf->known_gate, nullptr, 0,
-                                       pf->known_stats, nullptr))
+        // (the map as it was given lies behind the prepared one)
+        if (int rc = pf->known_detcov ? slam_localise_detcov_dev(e, pf->known_prep + 6 * (size_t)pf->known_Lp, pf->known_Lp, pf->known_L, dst, dst + sn,
+                                                                 dst + 2 * sn, n, pf->known_gate, nullptr, 0, pf->known_stats, nullptr)
+                                      : slam_localise_dev(e, pf->known_prep, pf->known_Lp, pf->known_L, dst, dst + sn, dst + 2 * sn, n, pf->known_gate,
+                                                          nullptr, 0, pf->known_stats, nullptr))
             return rc;
         pf->known_ll = true;
         if (pf->known_log_clutter != 0.0f)
@@ -588,6 +591,11 @@ int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations,
     // asked for
     if (pf->assoc_on && pf->assoc_detcov && f.ekf && (pf->detect_on ? !pf->detect_noise_on : !e->det_has_cov)) {
         snprintf(e->err, sizeof e->err, "association under per-detection covariances (slam_pf_assoc_detcov_set): the frame's detections "
+                                        "carry none (slam_detections_cov_upload_host / _set_dev, or slam_pf_detect_noise_set)");
+        return SLAM_ERR_NOT_READY;
+    }
+    if (pf->known_detcov && f.localise && (pf->detect_on ? !pf->detect_noise_on : !e->det_has_cov)) {   // ... and the same for a known map
+        snprintf(e->err, sizeof e->err, "localisation under per-detection covariances (slam_pf_known_map_detcov_set): the frame's detections "
                                         "carry none (slam_detections_cov_upload_host / _set_dev, or slam_pf_detect_noise_set)");
         return SLAM_ERR_NOT_READY;
     }

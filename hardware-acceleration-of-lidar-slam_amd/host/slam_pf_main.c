@@ -23,7 +23,7 @@
  *                     [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]]
  *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
  *                     [--landmarks-out FILE]]
- *                     [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]]]]
+ *                     [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
  *   particles      the whole population (a multiple of N)
  *   --ess F        ESS-gated resampling: resample only in frames whose effective sample size is below F * N
  *   --refine SWEEPS  scan-match refinement of every particle (slam_pf_refine_set): SWEEPS (1..16) sweeps of the reference's
@@ -48,8 +48,9 @@
  *                  none LOG_MISS; each finite and <= 0 (slam_pf_assoc_weight_set)
  *   --detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP]  the detector (slam_pf_detect_set; no values: slam_detect_params_default):
  *                  every frame makes its detections from its own scan, so the landmark map grows from nothing but lidar frames
- *   --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]  only with --assoc and --detect: the detector's noise model
- *                  (slam_pf_detect_noise_set) and association under the covariance each detection carries (slam_pf_assoc_detcov_set)
+ *   --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]  only with --detect and --assoc or --known-map: the detector's noise model
+ *                  (slam_pf_detect_noise_set) and association under the covariance each detection carries
+ *                  (slam_pf_assoc_detcov_set; with --known-map: slam_pf_known_map_detcov_set)
  *   --pole-radius R [TOL]  only with --detect: a detection is the centre of the circle of radius R fitted to its segment, not the
  *                  segment's centroid, and segments more spread out than such a circle (by more than TOL, default 0) are no
  *                  detections (slam_pf_detect_fit_set)
@@ -58,7 +59,8 @@
  *                  lines as --landmarks-out writes them, every landmark gets P = MAP_VAR * I (MAP_VAR >= 0); the filter keeps no
  *                  landmarks of its own, every frame associates its detections (--detect) with this one map within GATE, weighs
  *                  each particle with the matched pairs' likelihood and adds LOG_CLUTTER (<= 0, default 0) per unmatched
- *                  detection.  One GPU; not with --landmarks or --meas-cov
+ *                  detection.  With --range-noise every detection is weighed under its own covariance instead of the session's
+ *                  meas_var * I (slam_pf_known_map_detcov_set).  One GPU; not with --landmarks or --meas-cov
  */
 #define _POSIX_C_SOURCE 200809L
 #include <math.h>
@@ -195,7 +197,10 @@ static void *rank_main(void *arg)
     if (run->use_sight) CHECK(slam_pf_prune_sight_set(pf, run->sight_bins, run->sight_margin));
     if (run->use_merge) CHECK(slam_pf_merge_set(pf, run->merge_gate));
     if (run->use_assoc_weight) CHECK(slam_pf_assoc_weight_set(pf, run->assoc_weight[0], run->assoc_weight[1], run->assoc_weight[2], 1));
-    if (run->known_map) CHECK(slam_pf_known_map_set(pf, run->known_rows, run->known_n, run->known_gate, run->known_log_clutter));
+    /* --range-noise: the form of the stage that weighs every detection under the covariance the detector's model gives it */
+    if (run->known_map)
+        CHECK((run->use_noise ? slam_pf_known_map_detcov_set : slam_pf_known_map_set)(pf, run->known_rows, run->known_n, run->known_gate,
+                                                                                    run->known_log_clutter));
     if (run->use_detect) CHECK(slam_pf_detect_noise_set(pf, &run->detect, run->use_fit ? &run->fit : NULL, run->use_noise ? &run->noise : NULL));
     const int observe = (run->known_map || (run->landmarks > 0 && run->use_assoc)) && run->use_detect;   /* else: no frame has observations */
     if (fe_scan_init(&scan, beams, -2.351831f, 0.004363f) || fe_points_init(&map, FE_MAP_CAPACITY + beams) ||
@@ -449,12 +454,12 @@ int main(int argc, char **argv)
     const int landmark_options = run.use_assoc || run.use_prune || (run.use_detect && !run.known_map) || run.landmarks_out != NULL;
     if (npos < 5 || (run.known_map && (run.landmarks > 0 || run.world > 1 || run.use_meas_cov)) || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
         (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) || (run.use_assoc_weight && !run.use_assoc) ||
-        (run.use_noise && (!run.use_detect || !run.use_assoc || run.use_meas_cov))) {
+        (run.use_noise && (!run.use_detect || !(run.use_assoc || run.known_map) || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
                         "  [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
                         "[--landmarks-out FILE]]\n"
-                        "  [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]]]]\n"
+                        "  [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
                         "              without --landmarks; with --landmarks and --assoc the association gates and updates under it\n"
                         "  --landmarks: L landmark slots per particle on rows, one GPU; --assoc, --prune, --detect and --landmarks-out need it.\n"
@@ -470,11 +475,12 @@ int main(int argc, char **argv)
                         "              each finite and <= 0\n"
                         "  --pole-radius R [TOL]: only with --detect; a detection is the centre of the circle of radius R fitted to its segment,\n"
                         "              and segments more spread out than that circle (by more than TOL, default 0) are dropped\n"
-                        "  --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --assoc and --detect, not with --meas-cov; every detection\n"
+                        "  --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --detect and --assoc or --known-map, not with --meas-cov; every detection\n"
                         "              carries its own covariance (RANGE_VAR along its beam, BEARING_VAR r^2 + LATERAL_VAR across) and is gated under it\n"
                         "  --known-map FILE GATE MAP_VAR [LOG_CLUTTER]: localise in the landmark map of FILE (\"x,y\" lines, as --landmarks-out writes\n"
                         "              them; P = MAP_VAR * I each): every frame associates its detections (--detect) with that one map within GATE and\n"
-                        "              weighs with the result, LOG_CLUTTER <= 0 per unmatched detection; one GPU, not with --landmarks or --meas-cov\n", argv[0]);
+                        "              weighs with the result, LOG_CLUTTER <= 0 per unmatched detection — with --range-noise under each detection's own\n"
+                        "              covariance; one GPU, not with --landmarks or --meas-cov\n", argv[0]);
         return 2;
     }
     if (run.use_meas_cov) {   /* the conditions of slam_pf_meas_cov_set: finite, qxx > 0, qyy > 0, float determinant > 0 */

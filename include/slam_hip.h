@@ -609,7 +609,17 @@ int slam_assoc_weight_count(slam_engine *e, int64_t *launches);   /* stage launc
  * NULL: no table is written) is uint8 [n][assoc_stride >= nlandmarks] as slam_associate_dev writes it.  No row is read and none is
  * written.  SLAM_ERR_INVALID_ARG: nlandmarks outside 1 .. SLAM_MAX_OBS, plane_stride or (with d_assoc) assoc_stride < nlandmarks,
  * a gate that is not finite and > 0, n < 0, a null pointer other than d_assoc / d_loglik.  SLAM_ERR_NOT_READY: no detections.
- * Out of scope: 2x2 and per-detection noise (S^-1 then depends on the particle), miss terms, any change of the map, K > 64. */
+ * Out of scope: one 2x2 noise for all detections as a form of its own (attach the same Q to every detection of
+ * slam_localise_detcov_dev), miss terms, any change of the map, K > 64.
+ * UNDER A COVARIANCE PER DETECTION (specification: tests/_localise_detcov_spec.py): slam_localise_detcov_dev (one launch) is
+ * slam_localise_dev under S = P + R_w(theta_i, k) of the engine's current detections AND THEIR COVARIANCES
+ * (slam_detections_cov_upload_host / _set_dev, slam_detect_scan_noise_dev) — exactly what slam_associate_detcov_dev(create = 0,
+ * new_gate = gate) and the log-likelihood of slam_ekf_update_assoc_detcov_dev give on rows that each hold the map.  S^-1 depends on
+ * the particle and the detection, so nothing is prepared: d_map is the map as it was given, float32 [5][plane_stride]; a slot with
+ * P_xx < 0, and the padding behind nlandmarks, never become candidates.  The caller guarantees P positive semi-definite for every
+ * landmark (slam_pf_known_map_detcov_set checks it; every Q_k is positive definite).  d_stats, d_assoc, d_loglik and the refused
+ * arguments as for slam_localise_dev; SLAM_ERR_NOT_READY also when the detections carry no covariances.
+ * slam_localise_detcov_count: its launches (in no other counter). */
 int slam_known_map_prepare_dev(slam_engine *e, const float *d_map /* [5][plane_stride] */, int plane_stride, int nlandmarks,
                                float meas_var, float *d_prepared /* [6][plane_stride] */);
 int slam_localise_dev(slam_engine *e, const float *d_prepared, int plane_stride, int nlandmarks,
@@ -617,6 +627,11 @@ int slam_localise_dev(slam_engine *e, const float *d_prepared, int plane_stride,
                       uint8_t *d_assoc /* may be NULL */, int assoc_stride, int32_t *d_stats /* [n][3] */,
                       float *d_loglik /* NULL: the engine's buffer, what slam_logweight_ekf_dev consumes */);
 int slam_localise_counts(slam_engine *e, int64_t counts[2]);        /* prepare launches, stage launches */
+int slam_localise_detcov_dev(slam_engine *e, const float *d_map /* [5][plane_stride] */, int plane_stride, int nlandmarks,
+                             const float *d_x, const float *d_y, const float *d_th, int n, float gate,
+                             uint8_t *d_assoc /* may be NULL */, int assoc_stride, int32_t *d_stats /* [n][3] */,
+                             float *d_loglik /* NULL: the engine's buffer, what slam_logweight_ekf_dev consumes */);
+int slam_localise_detcov_count(slam_engine *e, int64_t *launches);  /* stage launches */
 /* THE DETECTOR: the detections of a frame made on the device from the engine's current scan (slam_scan_upload_host / _set_dev),
  * P = nbeams points in scan order — what fe_clean left, so a removed beam leaves no hole and the rule uses distances only, never
  * beam angles.  With jump2 = jump * jump, guard2, width2 and range2 likewise (each rounded once to float32), and every step below
@@ -1140,12 +1155,26 @@ int slam_pf_detect_noise_set(slam_pf *pf, const slam_detect_params *params /* NU
  * misses (left out when log_clutter == 0), slam_logweight_ekf_dev, scan, resample; a frame with use_observations = 0 is the
  * frame of a session without the mode: plain weights.  slam_pf_detect_set / slam_pf_detect_fit_set are accepted while it is on
  * (the detector's launch goes out in front of the frame's first launch); slam_pf_detect_noise_set with a model is refused: the
- * noise is meas_var * I only.  Out of scope: sharded sessions, 2x2 and per-detection noise, miss terms, pruning, merging.
- * slam_pf_known_map_device_view: the prepared map ([6][nlandmarks rounded up to 32]; NULL and 0 while the mode is off) and the
+ * noise is meas_var * I only (slam_pf_known_map_detcov_set is the form that takes it).  Out of scope: sharded sessions, miss
+ * terms, pruning, merging.
+ * slam_pf_known_map_detcov_set (the frame loop: tests/_localise_detcov_spec.py frame_loop) is the same switch for the second
+ * form of the stage: every observing frame runs slam_localise_detcov_dev on the map as it was given, under the covariances its
+ * detections carry; meas_var is not read.  Accepted and refused where slam_pf_known_map_set is, except that the landmarks'
+ * covariances are checked on their own: P_xx >= 0 (else the slot holds no landmark), P_yy >= 0 and det P >= 0.  rows == NULL
+ * switches the mode off; either switch replaces the other, map and constants, from the next frame on (slam_pf_known_map_set
+ * drops the detector's noise model, which it does not take; the detector itself stays on).  While it is on
+ * slam_pf_detect_noise_set with a model is accepted, and the frame is: the detector's launch (in its noise form), the front
+ * launch, slam_localise_detcov_dev, slam_assoc_weight_dev (left out at log_clutter == 0), slam_logweight_ekf_dev, scan, resample.
+ * An observing frame whose detections will carry no covariance (none uploaded and no detector, or a detector without a model)
+ * returns SLAM_ERR_NOT_READY before its first launch and leaves the session unchanged.
+ * slam_pf_known_map_device_view: the prepared map ([6][nlandmarks rounded up to 32]; NULL while the mode is off and under
+ * slam_pf_known_map_detcov_set, which prepares none; nlandmarks 0 while the mode is off) and the
  * stats ([n_particles][3] = matched, 0, dropped; indexed like slam_pf_view.score) of the last frame that ran the stage; any of the
  * three pointers may be NULL.  SLAM_ERR_NOT_READY until a map was accepted once. */
 int slam_pf_known_map_set(slam_pf *pf, const float *rows /* host [5][nlandmarks]; NULL: off */, int nlandmarks,
                           float gate, float log_clutter);
+int slam_pf_known_map_detcov_set(slam_pf *pf, const float *rows /* host [5][nlandmarks]; NULL: off */, int nlandmarks,
+                                 float gate, float log_clutter);
 int slam_pf_known_map_device_view(slam_pf *pf, const float **prepared, int32_t *nlandmarks, const int32_t **stats);
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
  * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
