@@ -186,6 +186,8 @@ SIGNATURES = {
     "slam_comm_destroy": (_i, [_vp]),
     "slam_pf_create_sharded": (_i, [_vp, _vp, _vp, _i, C.POINTER(_vp)]),
     "slam_pf_mean": (_i, [_vp, _f, _fp]),
+    "slam_pf_spread": (_i, [_vp, _f, _fp, _fp, _fp]),
+    "slam_pose_spread_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _fp, _fp, _fp]),
     "slam_pf_rows_received": (_i, [_vp]),
     "slam_pf_device_view": (_i, [_vp, _vp]),
     "slam_pf_frames_resampled": (_i64, [_vp]),
@@ -799,6 +801,14 @@ class Engine:
 
     def ancestors_from_scan_dev(self, n, seed, frame, d_anc):
         self._ck(self.lib.slam_ancestors_from_scan_dev(self.h, n, seed, frame, _ptr(d_anc)), "ancestors_from_scan_dev")
+
+    def pose_spread_dev(self, d_x, d_y, d_theta, n, ref_theta, d_idx=None, d_carry=None):
+        """``slam_pose_spread_dev``: -> (pose, cov, heading_r) of n poses in device memory, as ``PfSession.spread`` defines them.
+        d_idx: a pending gather (int32, optional); d_carry: log-weight minus the largest, one float per slot (optional)."""
+        pose, cov, r = (C.c_float * 3)(), (C.c_float * 6)(), C.c_float(0)
+        self._ck(self.lib.slam_pose_spread_dev(self.h, _ptr(d_x), _ptr(d_y), _ptr(d_theta), _ptr(d_idx), _ptr(d_carry), n,
+                                               float(ref_theta), pose, cov, C.byref(r)), "pose_spread_dev")
+        return np.array(list(pose), np.float32), np.array(list(cov), np.float32), np.float32(r.value)
 
     def argmax_dev(self, d_values, n, d_index, d_value):
         """``slam_argmax_dev``: index (int32) and value (float32) of the largest of d_values[0..n) to device memory: the lowest
@@ -1445,6 +1455,14 @@ class PfSession:
         pose = (C.c_float * 3)()
         self.e._ck(self.e.lib.slam_pf_mean(self.h, float(ref_theta), pose), "pf_mean")
         return np.array(list(pose), np.float32)
+
+    def spread(self, ref_theta: float):
+        """``slam_pf_spread``: -> (pose, cov, heading_r).  pose: ``mean(ref_theta)``, bit for bit; cov: float32 [6] = xx, xy, yy,
+        xs, ys, ss, the covariance of the population over (x, y, sin(theta - pose[2])) about that mean; heading_r: the length of
+        the mean heading vector (1: one heading).  A small spread says the particles agree, not that they are right."""
+        pose, cov, r = (C.c_float * 3)(), (C.c_float * 6)(), C.c_float(0)
+        self.e._ck(self.e.lib.slam_pf_spread(self.h, float(ref_theta), pose, cov, C.byref(r)), "pf_spread")
+        return np.array(list(pose), np.float32), np.array(list(cov), np.float32), np.float32(r.value)
 
     def poses(self):
         x, y, th = (np.empty(self.n, np.float32) for _ in range(3))

@@ -7,6 +7,7 @@
 
 #include <vector>
 
+#include "estimate_host.h"
 #include "kernels.h"
 
 using slam::EventPair;
@@ -148,6 +149,7 @@ struct slam_engine {
     uint32_t gate_seq = 0;
     DevBuf carry_buf;          // float[n]
     int carry_n = -1;
+    DevBuf spread_buf;         // slam_pose_spread_dev: the accumulators and tickets of the two launches (kept zeroed), then their sums
 
     // feedback of the resample stages: roughly how many distinct ancestors the last one left {count, n} (mapped host
     // memory, read without synchronisation: it only steers the choice between two equivalent EKF kernels)
@@ -171,7 +173,7 @@ struct slam_engine {
     bool obs_table_owned = false;   // the table is the engine's own copy (slam_obs_upload_host), not the caller's arrays
     int32_t* h_obs = nullptr;
     int32_t* d_hobs = nullptr;
-    // 128 bytes of mapped host memory the engine's (one) particle-filter session delivers its results through.  It belongs to
+    // 512 bytes of mapped host memory the engine's (one) particle-filter session delivers its results through (pf_session.h: ResWord).  It belongs to
     // the ENGINE, not to the session: freeing pinned host memory makes the driver hold the process's queues for 65-80 ms some
     // 10-50 ms later (profiles/r03_stall_trigger.txt) — a session that came and went would stall the frames of the next one.
     void* h_block = nullptr;        // the one pinned allocation every h_* pointer of the engine points into
@@ -465,6 +467,10 @@ int slam_engine_fastmatch_pair(slam_engine* e, int slot1, int slot2, const float
                                const int32_t* d_nbeams, const float pose[3], const float res1[3], const float res2[3],
                                float out_pose[3], int32_t* best_hits_size, float* d_hits_persist);
 
+// engine_resample.hip: what slam_pose_spread_dev and slam_pf_spread return from the mean and the sums of pose_moments_kernel
+// (estimate_host.h); SLAM_ERR_INVALID_ARG, with the reason in slam_last_error, when a particle lay outside the domain
+__attribute__((visibility("hidden"))) int slam_engine_spread_result(slam_engine* e, const slam::PoseMean& mean, const long long m[slam::kPoseMoments],
+                                                                    float pose[3], float cov[6], float* heading_r);
 // engine_resample.hip: slam_migrate_pack_dev for a session with paged maps (d_pt: page tables of nb entries, d_map: the page pool)
 extern "C" int slam_migrate_pack_paged(slam_engine* e, int n_local, int rank, int world, const int32_t* plan, const float* d_pose,
                             int64_t pose_ld, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks,

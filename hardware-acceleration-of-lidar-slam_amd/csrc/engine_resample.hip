@@ -34,6 +34,23 @@ int slam_engine_bmax_ready(slam_engine* e)
     return SLAM_OK;
 }
 
+int slam_engine_spread_result(slam_engine* e, const slam::PoseMean& mean, const long long m[slam::kPoseMoments], float pose[3],
+                              float cov[6], float* heading_r)
+{
+    if (m[kPoseMomentsFlag] != 0) {
+        snprintf(e->err, sizeof e->err, "pose spread: %lld particles lie 2048 m or more from the mean in x or y (or are not numbers)",
+                 m[kPoseMomentsFlag]);
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (!cov_from_moment_sums(m, cov)) {
+        snprintf(e->err, sizeof e->err, "pose spread: the weights of the population sum to %lld", m[kPoseMomentsD]);
+        return SLAM_ERR_INVALID_ARG;
+    }
+    for (int k = 0; k < 3; ++k) pose[k] = mean.pose[k];
+    *heading_r = heading_length(mean);
+    return SLAM_OK;
+}
+
 extern "C" {
 
 static int logweight_common(slam_engine* e, const float* d_score, const float* d_loglik, float score_gain, int n,
@@ -362,6 +379,41 @@ int slam_argmax_dev(slam_engine* e, const float* d_values, int n, int32_t* d_ind
     if (n <= 0 || !d_values || !d_index || !d_value) return SLAM_ERR_INVALID_ARG;
     SLAM_HIP_TRY(e, launch_argmax(e->stream, d_values, n, d_index, d_value));
     return SLAM_OK;
+}
+
+int slam_pose_spread_dev(slam_engine* e, const float* d_x, const float* d_y, const float* d_theta, const int32_t* d_idx,
+                         const float* d_carry, int n, float ref_theta, float pose[3], float cov[6], float* heading_r)
+{
+    SLAM_ENTER(e);
+    if (n <= 0 || !d_x || !d_y || !d_theta || !pose || !cov || !heading_r) return SLAM_ERR_INVALID_ARG;
+    // 8-byte words: the sums' accumulators and ticket | the moments' accumulators and ticket | what either launch hands over
+    constexpr size_t kSumsAt = 0, kMomentsAt = kPoseSumsWeighted + 1, kOutAt = kMomentsAt + kPoseMoments + 1, kWords = kOutAt + kPoseMoments;
+    if (!e->spread_buf.p) {
+        SLAM_HIP_TRY(e, e->spread_buf.ensure(kWords * 8));
+        SLAM_HIP_TRY(e, hipMemsetAsync(e->spread_buf.p, 0, kWords * 8, e->stream));
+    }
+    unsigned long long* w = e->spread_buf.as<unsigned long long>();
+    long long* d_out = reinterpret_cast<long long*>(w + kOutAt);
+    long long h[kPoseMoments];
+    auto sums = [&](const float* carry) -> int {
+        SLAM_HIP_TRY(e, launch_pose_sums(e->stream, d_x, d_y, d_theta, d_idx, n, ref_theta, w + kSumsAt,
+                                         reinterpret_cast<unsigned int*>(w + kSumsAt + kPoseSumsWeighted), d_out, nullptr, nullptr, 0, carry));
+        SLAM_HIP_TRY(e, hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, e->stream));
+        SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
+        return SLAM_OK;
+    };
+    if (d_carry)
+        if (int rc = sums(d_carry)) return rc;
+    const bool weighted = d_carry && h[kPoseSumsWeighted - 1] > 0;   // (no weight at all: the plain form, as slam_pf_mean)
+    if (!weighted)
+        if (int rc = sums(nullptr)) return rc;
+    const PoseMean m = weighted ? mean_from_weighted_sums(h, ref_theta) : mean_from_plain_sums(h, n, ref_theta);
+    SLAM_HIP_TRY(e, launch_pose_moments(e->stream, d_x, d_y, d_theta, d_idx, n, m.pose, w + kMomentsAt,
+                                        reinterpret_cast<unsigned int*>(w + kMomentsAt + kPoseMoments), d_out, nullptr, nullptr, 0,
+                                        weighted ? d_carry : nullptr));
+    SLAM_HIP_TRY(e, hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, e->stream));
+    SLAM_HIP_TRY(e, hipStreamSynchronize(e->stream));
+    return slam_engine_spread_result(e, m, h, pose, cov, heading_r);
 }
 
 int slam_gather_f32_dev(slam_engine* e, const float* d_src, const int32_t* d_idx, int n, float* d_dst)

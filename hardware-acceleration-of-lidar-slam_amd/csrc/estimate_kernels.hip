@@ -1,5 +1,5 @@
 // estimate_kernels.hip — what is read out of a population: the heaviest particle (arg-max, or with its pose in one launch), the
-// exact sums for the posterior mean, and the gathers through the resample indices (gather_f32, gather_map).
+// exact sums for the posterior mean and for the second moments about it, and the gathers through the resample indices (gather_f32, gather_map).
 //
 // No reference counterpart: the specification is DESIGN.md + oracle/slam_oracle_pf.c, matched bit for bit.
 
@@ -90,11 +90,38 @@ __global__ __launch_bounds__(kBestBlock) void best_particle_kernel(const float* 
     }
 }
 
+// The end of the kernels that sum over the population: the workgroup's sums into the accumulators, one atomic each; the last
+// workgroup to finish (a ticket) hands the totals over — to device memory and, optionally, mapped host memory behind a sequence
+// number — and clears the accumulators and the ticket for the next call.
+template <int kSums>
+__device__ __forceinline__ void hand_over_sums(uint64_t (&sum)[kSums], unsigned long long* __restrict__ acc,
+                                               unsigned int* __restrict__ ticket, long long* __restrict__ out,
+                                               long long* __restrict__ h_out, uint32_t* __restrict__ h_seq, uint32_t seq)
+{
+    __shared__ uint64_t s_red[kBlock / 64];
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) sum[k] = block_sum_u64(sum[k], s_red);
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) atomicAdd(&acc[k], (unsigned long long)sum[k]);
+    __threadfence();
+    if (atomicAdd(ticket, 1u) != gridDim.x - 1) return;
+    __threadfence();
+    long long r[kSums];
+    for (int k = 0; k < kSums; ++k) r[k] = (long long)atomicExch(&acc[k], 0ull);   // read and clear for the next call
+    *ticket = 0;
+    for (int k = 0; k < kSums; ++k) out[k] = r[k];
+    if (h_out) {
+        for (int k = 0; k < kSums; ++k) h_out[k] = r[k];
+        __threadfence_system();
+        __hip_atomic_store(h_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // Exact, order-independent sums over the population for the posterior mean: x and y as 2^-32 fixed point, the heading
 // as sin / cos of (theta - ref) in 2^-30 fixed point (det_sincosf: the specified polynomial), accumulated with 64-bit
 // integer atomics — the same bits for any summation order, workgroup count or sharding.  idx (optional): the pending
-// resample gather.  The last workgroup to finish (a ticket) hands the sums over — to device memory and,
-// optionally, mapped host memory behind a sequence number — and clears the accumulators for the next call.
+// resample gather.  The sums are handed over by hand_over_sums.
 // WEIGHTED (a frame the resample gate kept): slot i counts with the 16-bit weight the gate's S is made
 // of, w16 = quantise(det_exp(carry[i])) >> 16 <= 2^16.  The products pass 64 bits, so every value V goes in as two limbs,
 // w16 * (V >> 21) and w16 * (V & 0x1fffff): nine sums {x hi, x lo, y hi, y lo, sin hi, sin lo, cos hi, cos lo, sum w16}.
@@ -109,7 +136,6 @@ __global__ __launch_bounds__(kBlock) void pose_sums_kernel(const float* __restri
                                                            uint32_t seq)
 {
     constexpr int kSums = WEIGHTED ? kPoseSumsWeighted : kPoseSumsPlain;
-    __shared__ uint64_t s_red[kBlock / 64];
     uint64_t sum[kSums];   // two's complement: signed sums through unsigned adds
 #pragma unroll
     for (int k = 0; k < kSums; ++k) sum[k] = 0;
@@ -132,23 +158,53 @@ __global__ __launch_bounds__(kBlock) void pose_sums_kernel(const float* __restri
             for (int k = 0; k < 4; ++k) sum[k] += (uint64_t)v[k];
         }
     }
+    hand_over_sums<kSums>(sum, acc, ticket, out, h_out, h_seq, seq);
+}
+
+// Exact, order-independent second moments of the population about the mean the sums above gave (slam_pf_spread; DESIGN.md
+// section 7): per particle dx = x - mean_x, dy = y - mean_y (one binary32 subtraction each) and s = the sine det_sincosf gives for
+// theta - mean_theta, cast to 2^-20 fixed point towards zero: DX, DY, SS.  Six sums of w * A * B and D = sum w, with w = 1 or
+// (WEIGHTED) the w16 of pose_sums_kernel; same block size, ticket and hand-over.
+// Limbs: |dx|, |dy| < 2048 m makes |DX|, |DY| < 2^31 (|SS| <= 2^20), so a product P = A * B is ONE 32 x 32 -> 64-bit signed
+// multiply, |P| < 2^62.  P goes in as three limbs, P & 0x1fffff, (P >> 21) & 0x1fffff (both in [0, 2^21)) and P >> 42 (arithmetic:
+// |P >> 42| <= 2^20), each times w <= 2^16 — again one 32 x 32 -> 64-bit multiply-add.  A limb term is below 2^37 in size and
+// n_total <= 2^23 of them stay below 2^60 < 2^63, over all workgroups and all ranks; the host joins the limbs in 128 bits.
+// A particle outside the domain (or with a NaN delta) counts in the flag word and adds zeros.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kBlock) void pose_moments_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                              const float* __restrict__ th, const int32_t* __restrict__ idx,
+                                                              const float* __restrict__ carry, int n, float mean_x, float mean_y,
+                                                              float mean_th, unsigned long long* __restrict__ acc,
+                                                              unsigned int* __restrict__ ticket, long long* __restrict__ out,
+                                                              long long* __restrict__ h_out, uint32_t* __restrict__ h_seq,
+                                                              uint32_t seq)
+{
+    uint64_t sum[kPoseMoments];   // two's complement: signed sums through unsigned adds
 #pragma unroll
-    for (int k = 0; k < kSums; ++k) sum[k] = block_sum_u64(sum[k], s_red);
-    if (threadIdx.x != 0) return;
+    for (int k = 0; k < kPoseMoments; ++k) sum[k] = 0;
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+        const int j = idx ? idx[i] : i;
+        const float dx = x[j] - mean_x, dy = y[j] - mean_y;
+        float s, c;
+        det_sincosf(th[j] - mean_th, s, c);
+        const bool inside = fabsf(dx) < 2048.0f && fabsf(dy) < 2048.0f;   // (false for NaN)
+        const int32_t d[3] = { inside ? (int32_t)(dx * 1048576.0f) : 0, inside ? (int32_t)(dy * 1048576.0f) : 0,
+                               (int32_t)(s * 1048576.0f) };
+        const uint32_t w = WEIGHTED ? (uint32_t)((uint64_t)(det_expf(carry[i]) * 4294967296.0f) >> 16) : 1u;
+        constexpr int kA[6] = { 0, 0, 1, 0, 1, 2 }, kB[6] = { 0, 1, 1, 2, 2, 2 };
 #pragma unroll
-    for (int k = 0; k < kSums; ++k) atomicAdd(&acc[k], (unsigned long long)sum[k]);
-    __threadfence();
-    if (atomicAdd(ticket, 1u) != gridDim.x - 1) return;
-    __threadfence();
-    long long r[kSums];
-    for (int k = 0; k < kSums; ++k) r[k] = (long long)atomicExch(&acc[k], 0ull);   // read and clear for the next call
-    *ticket = 0;
-    for (int k = 0; k < kSums; ++k) out[k] = r[k];
-    if (h_out) {
-        for (int k = 0; k < kSums; ++k) h_out[k] = r[k];
-        __threadfence_system();
-        __hip_atomic_store(h_seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        for (int k = 0; k < 6; ++k) {
+            const long long p = (long long)d[kA[k]] * (long long)d[kB[k]];
+            const uint32_t p0 = (uint32_t)p & 0x1fffffu, p1 = (uint32_t)(p >> 21) & 0x1fffffu;
+            const int32_t p2 = (int32_t)(p >> 42);
+            sum[3 * k] += (uint64_t)w * p0;
+            sum[3 * k + 1] += (uint64_t)w * p1;
+            sum[3 * k + 2] += (uint64_t)((long long)(int32_t)w * (long long)p2);
+        }
+        sum[kPoseMomentsD] += w;
+        sum[kPoseMomentsFlag] += inside ? 0u : 1u;
     }
+    hand_over_sums<kPoseMoments>(sum, acc, ticket, out, h_out, h_seq, seq);
 }
 
 }  // namespace
@@ -179,6 +235,22 @@ hipError_t launch_pose_sums(hipStream_t stream, const float* x, const float* y, 
         pose_sums_kernel<true><<<nb, kBlock, 0, stream>>>(x, y, th, idx, carry, n, ref_th, acc, ticket, out, h_out, h_seq, seq);
     else
         pose_sums_kernel<false><<<nb, kBlock, 0, stream>>>(x, y, th, idx, nullptr, n, ref_th, acc, ticket, out, h_out, h_seq, seq);
+    return hipGetLastError();
+}
+
+hipError_t launch_pose_moments(hipStream_t stream, const float* x, const float* y, const float* th, const int32_t* idx,
+                               int n, const float mean[3], unsigned long long* acc, unsigned int* ticket, long long* out,
+                               long long* h_out, uint32_t* h_seq, uint32_t seq, const float* carry)
+{
+    if (n <= 0) return hipSuccess;
+    // Eight particles per thread, at most 64 workgroups: every workgroup ends on 20 atomics to the same 20 words, and that fixed part,
+    // not the bytes, bounds the launch (profiles/spread.md: 256 workgroups took 55 us here at 65 536 particles, 32 take 23 us)
+    const int want = (blocks_for(n) + 7) / 8;
+    const int nb = want < 1 ? 1 : want < 64 ? want : 64;
+    if (carry)
+        pose_moments_kernel<true><<<nb, kBlock, 0, stream>>>(x, y, th, idx, carry, n, mean[0], mean[1], mean[2], acc, ticket, out, h_out, h_seq, seq);
+    else
+        pose_moments_kernel<false><<<nb, kBlock, 0, stream>>>(x, y, th, idx, nullptr, n, mean[0], mean[1], mean[2], acc, ticket, out, h_out, h_seq, seq);
     return hipGetLastError();
 }
 

@@ -713,6 +713,16 @@ constexpr int kPoseSumsPlain = 4, kPoseSumsWeighted = 9;
 hipError_t launch_pose_sums(hipStream_t stream, const float* x, const float* y, const float* th, const int32_t* idx,
                             int n, float ref_th, unsigned long long* acc, unsigned int* ticket, long long* out,
                             long long* h_out, uint32_t* h_seq, uint32_t seq, const float* carry = nullptr);
+// exact second moments about `mean` (what the sums above gave): with DX = trunc((x - mean[0]) * 2^20), DY likewise and
+// SS = trunc(sin_det(theta - mean[2]) * 2^20), the six sums of w * A * B for (A, B) = (DX,DX) (DX,DY) (DY,DY) (DX,SS) (DY,SS)
+// (SS,SS), each as three limbs of the product P = A * B — out[3k] = sum w (P & 0x1fffff), out[3k + 1] = sum w ((P >> 21) & 0x1fffff),
+// out[3k + 2] = sum w (P >> 42) — then out[kPoseMomentsD] = sum w and out[kPoseMomentsFlag] = how many particles lie outside the
+// domain |x - mean[0]|, |y - mean[1]| < 2048 m (they count as zeros: the caller refuses the result).  w = 1, or with carry the w16 of
+// launch_pose_sums.  acc[kPoseMoments] / ticket: zero-initialised device scratch the kernel leaves zeroed.
+constexpr int kPoseMoments = 20, kPoseMomentsD = 18, kPoseMomentsFlag = 19;
+hipError_t launch_pose_moments(hipStream_t stream, const float* x, const float* y, const float* th, const int32_t* idx,
+                               int n, const float mean[3], unsigned long long* acc, unsigned int* ticket, long long* out,
+                               long long* h_out, uint32_t* h_seq, uint32_t seq, const float* carry = nullptr);
 hipError_t launch_gather_f32(hipStream_t stream, const float* src, const int32_t* idx, int n, float* dst);
 hipError_t launch_gather_map(hipStream_t stream, const float* in, float* out, int64_t in_row_stride,
                              int64_t out_row_stride, int in_plane_stride, int out_plane_stride, int nlandmarks,

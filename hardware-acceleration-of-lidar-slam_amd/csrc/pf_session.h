@@ -17,7 +17,7 @@
 #include "engine_internal.h"
 #include "kernels.h"
 
-// The 32 words of the engine's mapped result block (slam_pf::h_res as the host sees it, d_hres as the device does)
+// The words of the engine's mapped result block (slam_pf::h_res as the host sees it, d_hres as the device does)
 enum ResWord {
     RES_PAYLOAD = 0,      // 0..15: 8 x 8 bytes, what slam_pf_best / slam_pf_mean ask for
     RES_SEQ = 16,         // the sequence number behind the payload
@@ -28,6 +28,7 @@ enum ResWord {
     RES_OBS_SEQ = 26,     //        page_list_kernel / obs_count_kernel
     RES_VOTES_PAGES = 27, RES_VOTES_ROWS = 28,
     RES_PAGE_HINT = 30,   // pages the last frames touched per pass (page_list_kernel)
+    RES_MOMENTS = 32,     // 32..71: kPoseMoments x 8 bytes, what slam_pf_spread asks for (behind RES_SEQ as well)
 };
 
 struct slam_pf {
@@ -64,8 +65,9 @@ struct slam_pf {
     float* h_res = nullptr;         // pinned + mapped: the words of ResWord
     float* d_hres = nullptr;        // the same memory as the device sees it
     uint32_t res_seq = 0;
-    float* res_dev = nullptr;       // device copy of the payload (what the ranks all-gather)
+    float* res_dev = nullptr;       // device copy of the payload (what the ranks all-gather): kResBytes
     unsigned long long* sums_acc = nullptr;   // 9 accumulators + ticket of pose_sums_kernel (kept zeroed by the kernel)
+    unsigned long long* moments_acc = nullptr;   // kPoseMoments accumulators + ticket of pose_moments_kernel (likewise)
     void* res_all = nullptr;        // [world] payloads
     // ---- paged maps (slam_pf_paged_set before the session is made; one GPU): copy-on-write pages behind a page table
     // per particle instead of one row per particle (paged_kernels.hip); map[] stays unallocated
@@ -221,6 +223,8 @@ struct slam_pf {
 };
 
 namespace slam::session {
+
+constexpr size_t kResBytes = 256;   // of res_dev and of each rank's share of res_all: the largest payload is kPoseMoments x 8 bytes
 
 inline hipError_t dev_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes ? bytes : 4); }
 

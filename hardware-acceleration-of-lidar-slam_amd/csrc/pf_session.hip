@@ -117,9 +117,9 @@ int create_common(slam_engine* e, const slam_pf_config* cfg, slam_comm* comm, in
     }
     ok = ok && dev_alloc((void**)&pf->score, n * 4) == hipSuccess && dev_alloc((void**)&pf->logw, n * 4) == hipSuccess &&
          dev_alloc((void**)&pf->count, n * 4) == hipSuccess && dev_alloc((void**)&pf->first, n * 4) == hipSuccess &&
-         dev_alloc((void**)&pf->res_dev, 128) == hipSuccess && dev_alloc((void**)&pf->sums_acc, 128) == hipSuccess &&
-         dev_alloc(&pf->res_all, 128 * G) == hipSuccess &&
-         hipMemset(pf->sums_acc, 0, 128) == hipSuccess;
+         dev_alloc((void**)&pf->res_dev, kResBytes) == hipSuccess && dev_alloc((void**)&pf->sums_acc, 128) == hipSuccess &&
+         dev_alloc((void**)&pf->moments_acc, 256) == hipSuccess && dev_alloc(&pf->res_all, kResBytes * G) == hipSuccess &&
+         hipMemset(pf->sums_acc, 0, 128) == hipSuccess && hipMemset(pf->moments_acc, 0, 256) == hipSuccess;
     // results come back through the engine's mapped buffer (one session per engine; see engine_internal.h for why the
     // session does not allocate its own); the engine was drained above, so nothing of an earlier session writes to it any more
     pf->h_res = static_cast<decltype(pf->h_res)>(e->h_pf_res);
@@ -206,7 +206,7 @@ int slam_pf_destroy(slam_pf* pf)
     free_split_tables(pf);
     for (void* p : { (void*)pf->score, (void*)pf->logw, (void*)pf->count, (void*)pf->first, (void*)pf->pose_all, (void*)pf->pose_stage, (void*)pf->first_all,
                      (void*)pf->d_sum, (void*)pf->totals, (void*)pf->d_plan, (void*)pf->sbuf,
-                     (void*)pf->rbuf, (void*)pf->res_dev, (void*)pf->sums_acc, pf->res_all })
+                     (void*)pf->rbuf, (void*)pf->res_dev, (void*)pf->sums_acc, (void*)pf->moments_acc, pf->res_all })
         (void)hipFree(p);
     (void)hipFree(pf->sel);
     (void)hipFree(pf->conv_tmp);

@@ -1,5 +1,5 @@
-// pf_session_read.hip — what a host reads back from a session: the heaviest particle and the posterior mean (slam_pf_best,
-// slam_pf_mean), poses, map rows and evidence copied out, the device views, the layout in force; the pending gather of the last
+// pf_session_read.hip — what a host reads back from a session: the heaviest particle, the posterior mean and the spread about it
+// (slam_pf_best, slam_pf_mean, slam_pf_spread), poses, map rows and evidence copied out, the device views, the layout in force; the pending gather of the last
 // resample is applied on the way.  On a sharded session the copying calls are collective (collective_result).
 
 #include <math.h>
@@ -54,7 +54,7 @@ int shares_to_host(slam_pf* pf, size_t bytes, void* h_all)
     return wait_stream(pf);
 }
 
-// the K integer sums pose_sums_kernel left in res_dev, added over the ranks: in any order they give the single-GPU bits (every
+// the K integer sums pose_sums_kernel or pose_moments_kernel left in res_dev, added over the ranks: in any order they give the single-GPU bits (every
 // limb sum of the whole population fits 64 bits)
 int summed_shares(slam_pf* pf, int K, long long* total)
 {
@@ -98,15 +98,24 @@ int pf_best(slam_pf* pf, float pose[3], float* logw, int32_t* index)
     return SLAM_OK;
 }
 
-int pf_mean(slam_pf* pf, float ref_theta, float pose[3])
+// What slam_pf_mean and slam_pf_spread share: the poses behind the pending gather, whether the mean is the weighted one, the mean
+struct MeanOf {
+    const float* x = nullptr;
+    const int32_t* idx = nullptr;
+    bool weighted = false;
+    PoseMean m;
+};
+
+int mean_of(slam_pf* pf, float ref_theta, MeanOf* out)
 {
-    if (!pf || !pose) return SLAM_ERR_INVALID_ARG;
     slam_engine* e = pf->e;
     SLAM_HIP_TRY(e, hipSetDevice(e->device));
     const size_t sn = (size_t)pf->n;
     const float* x = nullptr;
     const int32_t* idx = nullptr;
     if (int rc = ancestor_poses(pf, &x, &idx)) return rc;
+    out->x = x;
+    out->idx = idx;
     const float *y = x + sn, *th = x + 2 * sn;
     unsigned int* ticket = reinterpret_cast<unsigned int*>(pf->sums_acc + kPoseSumsWeighted);
     // A frame the resample gate kept (its verdict is on its way to mapped host memory: wait for it) left unequal weights:
@@ -120,12 +129,8 @@ int pf_mean(slam_pf* pf, float ref_theta, float pose[3])
         long long w[kPoseSumsWeighted] = { 0 };
         if (int rc = summed_shares(pf, kPoseSumsWeighted, w)) return rc;
         if (w[8] > 0) {   // (no weight at all: log-weights that are not numbers — the plain mean below)
-            double v[4];
-            for (int k = 0; k < 4; ++k)   // trunc(sum w16 V / sum w16): C's division truncates
-                v[k] = (double)(long long)(((__int128)w[2 * k] * 2097152 + w[2 * k + 1]) / w[8]);
-            pose[0] = (float)(v[0] / 4294967296.0);
-            pose[1] = (float)(v[1] / 4294967296.0);
-            pose[2] = (float)((double)ref_theta + atan2(v[2], v[3]));
+            out->weighted = true;
+            out->m = mean_from_weighted_sums(w, ref_theta);
             return SLAM_OK;
         }
     }
@@ -142,11 +147,45 @@ int pf_mean(slam_pf* pf, float ref_theta, float pose[3])
                                          reinterpret_cast<long long*>(pf->res_dev), nullptr, nullptr, 0));
         if (int rc = summed_shares(pf, 4, sums)) return rc;
     }
-    const double nt = (double)pf->n_total;
-    pose[0] = (float)((double)sums[0] / 4294967296.0 / nt);
-    pose[1] = (float)((double)sums[1] / 4294967296.0 / nt);
-    pose[2] = (float)((double)ref_theta + atan2((double)sums[2], (double)sums[3]));
+    out->weighted = false;
+    out->m = mean_from_plain_sums(sums, pf->n_total, ref_theta);
     return SLAM_OK;
+}
+
+int pf_mean(slam_pf* pf, float ref_theta, float pose[3])
+{
+    if (!pf || !pose) return SLAM_ERR_INVALID_ARG;
+    MeanOf mo;
+    if (int rc = mean_of(pf, ref_theta, &mo)) return rc;
+    memcpy(pose, mo.m.pose, sizeof mo.m.pose);
+    return SLAM_OK;
+}
+
+// the mean (mean_of), then the second moments about it in a launch of their own: one GPU — the sums land in mapped host memory;
+// sharded — the mean is the global one by now, and the moments' shares are added over the ranks like the mean's
+int pf_spread(slam_pf* pf, float ref_theta, float pose[3], float cov[6], float* heading_r)
+{
+    if (!pf || !pose || !cov || !heading_r) return SLAM_ERR_INVALID_ARG;
+    MeanOf mo;
+    if (int rc = mean_of(pf, ref_theta, &mo)) return rc;
+    slam_engine* e = pf->e;
+    const size_t sn = (size_t)pf->n;
+    const float* carry = mo.weighted ? e->carry_buf.as<float>() : nullptr;
+    unsigned int* ticket = reinterpret_cast<unsigned int*>(pf->moments_acc + kPoseMoments);
+    long long m[kPoseMoments] = { 0 };
+    if (!pf->comm) {
+        const uint32_t seq = ++pf->res_seq;
+        SLAM_HIP_TRY(e, launch_pose_moments(e->stream, mo.x, mo.x + sn, mo.x + 2 * sn, mo.idx, pf->n, mo.m.pose, pf->moments_acc, ticket,
+                                            reinterpret_cast<long long*>(pf->res_dev), reinterpret_cast<long long*>(dev_word(pf, RES_MOMENTS)),
+                                            reinterpret_cast<uint32_t*>(dev_word(pf, RES_SEQ)), seq, carry));
+        if (int rc = wait_result(pf, seq)) return rc;
+        memcpy(m, host_word(pf, RES_MOMENTS), sizeof m);
+    } else {
+        SLAM_HIP_TRY(e, launch_pose_moments(e->stream, mo.x, mo.x + sn, mo.x + 2 * sn, mo.idx, pf->n, mo.m.pose, pf->moments_acc, ticket,
+                                            reinterpret_cast<long long*>(pf->res_dev), nullptr, nullptr, 0, carry));
+        if (int rc = summed_shares(pf, kPoseMoments, m)) return rc;
+    }
+    return slam_engine_spread_result(e, mo.m, m, pose, cov, heading_r);
 }
 
 int pf_get_poses_host(slam_pf* pf, float* x, float* y, float* theta)
@@ -247,6 +286,7 @@ extern "C" {
 
 int slam_pf_best(slam_pf* pf, float pose[3], float* logw, int32_t* index) { return collective_result(pf, pf_best(pf, pose, logw, index)); }
 int slam_pf_mean(slam_pf* pf, float ref_theta, float pose[3]) { return collective_result(pf, pf_mean(pf, ref_theta, pose)); }
+int slam_pf_spread(slam_pf* pf, float ref_theta, float pose[3], float cov[6], float* heading_r) { return collective_result(pf, pf_spread(pf, ref_theta, pose, cov, heading_r)); }
 int slam_pf_get_poses_host(slam_pf* pf, float* x, float* y, float* theta) { return collective_result(pf, pf_get_poses_host(pf, x, y, theta)); }
 int slam_pf_get_map_host(slam_pf* pf, float* rows) { return collective_result(pf, pf_get_map_host(pf, rows)); }
 int slam_pf_get_map_rows_host(slam_pf* pf, const int32_t* particle, int count, float* rows) { return collective_result(pf, pf_get_map_rows_host(pf, particle, count, rows)); }

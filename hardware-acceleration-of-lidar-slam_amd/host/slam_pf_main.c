@@ -24,6 +24,7 @@
  *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
  *                     [--landmarks-out FILE]]
  *                     [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
+ *                     [--spread-out FILE]
  *   particles      the whole population (a multiple of N)
  *   --ess F        ESS-gated resampling: resample only in frames whose effective sample size is below F * N
  *   --refine SWEEPS  scan-match refinement of every particle (slam_pf_refine_set): SWEEPS (1..16) sweeps of the reference's
@@ -61,6 +62,11 @@
  *                  each particle with the matched pairs' likelihood and adds LOG_CLUTTER (<= 0, default 0) per unmatched
  *                  detection.  With --range-noise every detection is weighed under its own covariance instead of the session's
  *                  meas_var * I (slam_pf_known_map_detcov_set).  One GPU; not with --landmarks or --meas-cov
+ *   --spread-out FILE  every frame also asks for the spread of the population about its mean (slam_pf_spread, around the same
+ *                  predicted heading) and writes one line to FILE: the frame number, the six entries of the covariance over
+ *                  (x, y, sin dtheta) — xx, xy, yy, xs, ys, ss — and the length of the mean heading vector, comma-separated, each
+ *                  number as %.9g (enough to give back its binary32).  A small spread says that the particles agree, not that
+ *                  they are right.  Every other output stays byte for byte what it is without the flag
  */
 #define _POSIX_C_SOURCE 200809L
 #include <math.h>
@@ -111,6 +117,8 @@ typedef struct {
     int use_noise;         /* --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --detect */
     slam_detect_noise noise;
     const char *landmarks_out;   /* --landmarks-out FILE */
+    const char *spread_out;      /* --spread-out FILE */
+    FILE *spread;                /* ... opened in main, before any rank runs; rank 0 writes */
     const char *known_map;       /* --known-map FILE GATE MAP_VAR [LOG_CLUTTER] */
     float known_gate, known_var, known_log_clutter;
     float *known_rows;           /* [5][known_n]: the file's points, P = MAP_VAR * I */
@@ -260,6 +268,13 @@ static void *rank_main(void *arg)
             CHECK(slam_pf_best(pf, best, NULL, NULL));   /* sharded: the heaviest of the whole population, on every rank */
         }
         t_step += now_s() - t0;
+        if (run->spread_out) {   /* collective on several GPUs: every rank asks, rank 0 writes */
+            float sp[3], cov[6], heading_r;
+            CHECK(slam_pf_spread(pf, pose[2] + dp[2], sp, cov, &heading_r));
+            if (rank == 0)
+                fprintf(run->spread, "%d,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g\n", k + 1, (double)cov[0], (double)cov[1], (double)cov[2],
+                        (double)cov[3], (double)cov[4], (double)cov[5], (double)heading_r);
+        }
         memcpy(prev, pose, sizeof prev);
         memcpy(pose, best, sizeof pose);
 
@@ -436,6 +451,7 @@ int main(int argc, char **argv)
             if (a + 1 < argc && strchr("0123456789.+", argv[a + 1][0])) run.noise.lateral_var = (float)atof(argv[++a]);
         }
         else if (!strcmp(argv[a], "--landmarks-out") && a + 1 < argc) run.landmarks_out = argv[++a];
+        else if (!strcmp(argv[a], "--spread-out") && a + 1 < argc) run.spread_out = argv[++a];
         else if (!strcmp(argv[a], "--known-map") && a + 3 < argc) {
             run.known_map = argv[++a];
             float *v[3] = { &run.known_gate, &run.known_var, &run.known_log_clutter };
@@ -459,7 +475,7 @@ int main(int argc, char **argv)
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
                         "  [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
                         "[--landmarks-out FILE]]\n"
-                        "  [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]]\n"
+                        "  [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] [--spread-out FILE]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
                         "              without --landmarks; with --landmarks and --assoc the association gates and updates under it\n"
                         "  --landmarks: L landmark slots per particle on rows, one GPU; --assoc, --prune, --detect and --landmarks-out need it.\n"
@@ -480,7 +496,10 @@ int main(int argc, char **argv)
                         "  --known-map FILE GATE MAP_VAR [LOG_CLUTTER]: localise in the landmark map of FILE (\"x,y\" lines, as --landmarks-out writes\n"
                         "              them; P = MAP_VAR * I each): every frame associates its detections (--detect) with that one map within GATE and\n"
                         "              weighs with the result, LOG_CLUTTER <= 0 per unmatched detection — with --range-noise under each detection's own\n"
-                        "              covariance; one GPU, not with --landmarks or --meas-cov\n", argv[0]);
+                        "              covariance; one GPU, not with --landmarks or --meas-cov\n"
+                        "  --spread-out FILE: one line per frame to FILE: frame, the covariance of the population over (x, y, sin dtheta) about its\n"
+                        "              mean (xx, xy, yy, xs, ys, ss) and the length of the mean heading vector, %%.9g each; a small spread says the\n"
+                        "              particles agree, not that they are right\n", argv[0]);
         return 2;
     }
     if (run.use_meas_cov) {   /* the conditions of slam_pf_meas_cov_set: finite, qxx > 0, qyy > 0, float determinant > 0 */
@@ -518,6 +537,8 @@ int main(int argc, char **argv)
         free(xy);
         if (!run.use_detect) fprintf(stderr, "--known-map without --detect: no frame has detections, the map is not used\n");
     }
+    /* opened here: a rank that failed on it alone would leave the others waiting in their first collective */
+    if (run.spread_out && !(run.spread = fopen(run.spread_out, "w"))) { perror(run.spread_out); free(run.known_rows); return 2; }
     run.dataset = pos[0];
     run.frames = atoi(pos[1]);
     run.beams = atoi(pos[2]);
@@ -561,5 +582,6 @@ int main(int argc, char **argv)
     for (int r = 0; r < run.world; ++r) rc |= ranks[r].rc;
     slam_local_group_destroy(run.group);
     free(run.known_rows);
+    if (run.spread && fclose(run.spread) != 0) { perror(run.spread_out); rc |= 1; }
     return rc;
 }

@@ -870,6 +870,13 @@ int slam_migrate_unpack_dev(slam_engine *e, const float *d_in, int world, const 
 /* Index (lowest on ties) and value of the largest element: the heaviest particle. */
 int slam_argmax_dev(slam_engine *e, const float *d_values, int n, int32_t *d_index, float *d_value);
 
+/* Mean, spread and heading length of n poses in device memory, exactly as slam_pf_spread defines them (n_total = n), without a
+ * session: d_idx (optional) is a pending gather — slot i holds particle d_idx[i]; d_carry (optional) is the source of the
+ * 16-bit weights, one float per SLOT: logw_i - max logw, w16_i = (uint64)(det_exp(d_carry[i]) * 2^32) >> 16 (all zero: the
+ * plain form).  Synchronises; the results come back by copies.  SLAM_ERR_INVALID_ARG outside the domain of slam_pf_spread. */
+int slam_pose_spread_dev(slam_engine *e, const float *d_x, const float *d_y, const float *d_theta, const int32_t *d_idx,
+                         const float *d_carry, int n, float ref_theta, float pose[3], float cov[6], float *heading_r);
+
 /* Plain gather of particle attributes through an index (used when the gather is not fused into the
  * next stage, and to pack rows for migration between GPUs). */
 int slam_gather_f32_dev(slam_engine *e, const float *d_src, const int32_t *d_idx, int n, float *d_dst);
@@ -1201,6 +1208,34 @@ int slam_pf_best(slam_pf *pf, float pose[3], float *logw, int32_t *index);
  *   set_poses / reset discard the carried weights: the mean after them is the plain one again.
  * Sharded: collective, the same answer on every rank. */
 int slam_pf_mean(slam_pf *pf, float ref_theta, float pose[3]);
+/* The mean together with the spread of the population about it: has the cloud settled?  `pose` is exactly what
+ * slam_pf_mean(pf, ref_theta, pose) returns, bit for bit — the plain mean where that is plain, the weighted one on a frame the
+ * resample gate kept; call it (mx, my, mt).  A second launch then forms, per particle (behind the pending gather),
+ *     dx = x_i - mx,  dy = y_i - my  (one binary32 subtraction each),  s_i = sin_det(theta_i - mt)  (one binary32 subtraction,
+ *     then the specified polynomial of the mean),  DX = trunc(dx * 2^20), DY and SS likewise (the cast of C: towards zero),
+ * and the six exact integer sums of w_i * A_i * B_i for (A, B) = (DX,DX) (DX,DY) (DY,DY) (DX,SS) (DY,SS) (SS,SS) with D = sum w_i:
+ * w_i = 1 and D = n_total where the mean is plain, w_i = w16_i and D = the gate's S where it is weighted.  Then
+ *     cov[k] = float(double(trunc(sum_k / D)) / 2^40)    in that order:  xx, xy, yy, xs, ys, ss
+ * — the 3 x 3 covariance over (x, y, sin(theta - mt)) in its population (biased) form about the mean the call returns.  The sine
+ * of a heading difference is the difference itself for a settled cloud and saturates for a spread one, so the call also returns
+ *     *heading_r = float(hypot(double(Qs), double(Qc)) / 2^30),
+ * the length of the mean heading vector from the mean's own sums (Qs, Qc as above; where the mean is plain
+ * Qs = trunc(sum S / n_total), Qc likewise): 1 = one heading, near 0 = headings all round the circle.
+ * n = 1 and a population of identical poses give +0 in all six entries and heading_r = 1 up to the truncation of C.
+ * A SMALL SPREAD SAYS THAT THE PARTICLES AGREE, NOT THAT THEY ARE RIGHT: a cloud that settled on a wrong pose reports the same.
+ *   Domain: |dx|, |dy| < 2048 m, so |DX|, |DY| < 2^31 and a product P = A * B is one 32 x 32 -> 64-bit multiply, |P| < 2^62.  The
+ *   device sums w * P as three limbs, w * (P & 0x1fffff), w * ((P >> 21) & 0x1fffff) and w * (P >> 42): with w <= 2^16 a term is
+ *   below 2^37 in size and n_total <= 2^23 of them below 2^60 < 2^63 in every 64-bit accumulator; the host joins the limbs in
+ *   128 bits.  A delta outside the domain never gives a silently wrong number: the kernel counts such particles in a flag word
+ *   and the call returns SLAM_ERR_INVALID_ARG (slam_last_error says why) without writing its outputs.  The domains of
+ *   slam_pf_mean hold as well.  NaN poses are the caller's error, as for the mean: the result is then unspecified (a NaN in x or y
+ *   fails the domain test; a NaN heading does not).
+ *   One GPU: two launches, each delivering through mapped host memory (on kept frames the mean's nine sums come by a copy, as in
+ *   slam_pf_mean); no copy of the population.  set_poses / reset discard the carried weights; before the first step the answer
+ *   is the plain form.
+ * Sharded: collective, supported — two exchanges (the mean must be the global one before the second launch), the integer sums
+ * add over the ranks in any order, the same answer (and the same verdict on the domain) on every rank. */
+int slam_pf_spread(slam_pf *pf, float ref_theta, float pose[3], float cov[6], float *heading_r);
 /* rows this rank received in the exchange of the last completed frame (0 on a single GPU) */
 int slam_pf_rows_received(const slam_pf *pf);
 /* With cfg.resample_ess_frac in (0, 1): how many of the frames the host has looked at so far did resample (the
