@@ -5,33 +5,20 @@
 // Rows only: a table per particle means "which landmarks a frame observes" differs between particles, which the split, paged
 // and grouped forms rely on being the same.
 //
-// associate_kernel: ONE WAVEFRONT OWNS ONE PARTICLE, lanes own landmarks l and l + 64 of each batch of 128 (the access shape of
-// ekf_row_body.h) and walk the K detections in a wave-uniform loop: (P + q I)^-1 once per landmark, then per detection the
-// Mahalanobis term of the update's own likelihood on v2f (the operations of ekf_shared_from / ekf_particle, the same bits).
-//   c. every landmark keeps its cheapest detection (strict <, k ascending: the lowest k on ties, NaN never wins);
-//   d. the candidates (0 <= m <= gate) post (bits(m) << 32 | l) to an LDS 64-bit minimum per detection — m >= 0, so the
-//      order of the bits is the order of the values, -0 is made +0 first, and l in the low word breaks ties towards the lowest
-//      landmark: the result does not depend on the order in which lanes or batches arrive;
-//   e. a detection that matched nothing and lies within new_gate of no seen landmark (a flag per detection, from a ballot, kept by lane k)
-//      takes the next unseen slot: the ranks come from popcounts over a 64-bit "unseen" mask per 64 landmarks.
-// The particle's table row is assembled in LDS and written out as whole dwords.
-//
-// Under a full 2x2 sensor-frame measurement covariance Q (specification: tests/_assoc_aniso_spec.py) association and update run
-// with S = P + R_w(theta_i): associate_body takes the noise as a policy (AssocNoiseIso: the lines above; AssocNoiseAniso: R_w once
-// per wavefront, S^-1 with the operations of ekf_aniso_update_one), and the update's noise policy is EkfNoiseAniso.
-//
-// Under a covariance PER DETECTION (specification: tests/_assoc_detcov_spec.py) S = P + R_w(theta_i, k) differs from detection
-// to detection: AssocNoiseDet has lane k form R_w(theta_i, k) once (all K in one pass, beside the world-frame point it already
-// holds), the loop over k reads it into scalar registers with the point, and S^-1 — the same operations, the same reciprocal —
-// moves INSIDE that loop, per (landmark, detection) pair.  The update's noise policy is EkfNoiseDet.
+// associate_kernel: the matching of match_body.h (a wavefront per particle; steps a, c, d and the table row are its functions)
+// on the particle's OWN ROW, read through a buffer resource in the access shape of ekf_row_body.h, under one of the noise
+// policies of assoc_noise.h (step b: meas_var * I, a full 2x2 Q, or a Q_k per detection).  What is the association's own:
+//   - seen and unseen: a slot with P_xx < 0 gets the NaN mean that keeps it out of the matching, and its bit in a 64-bit
+//     "unseen" mask per 64 landmarks;
+//   e. a detection that matched nothing and lies within new_gate of no seen landmark (a flag per detection, from a ballot
+//      beside step c, kept by lane k) takes the next unseen slot: the ranks come from popcounts over the unseen masks.
 
 #include "assoc_noise.h"
+#include "match_body.h"
 
 namespace slam {
 
 namespace {
-
-typedef unsigned long long u64;
 
 // LDS of one wavefront, carved out of the dynamic region in multiples of 16 bytes:
 //   best[64] u64 | unseen[2 * batches] u64 | fresh[64] u8 | row[nlandmarks rounded up to 16] u8
@@ -45,14 +32,6 @@ __host__ __device__ inline AssocLds assoc_lds(unsigned L)
     s.rowb = (L + 15u) & ~15u;
     s.per_wave = 64u * 8u + s.batches * 16u + 64u + s.rowb;
     return s;
-}
-
-// what one lane wrote to LDS, every lane of the SAME wavefront may read afterwards
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 __device__ __forceinline__ u64 below(unsigned lane) { return (1ull << lane) - 1ull; }   // the lanes in front of this one
@@ -72,10 +51,7 @@ template <bool CREATE, class NOISE, class QP> __device__ __forceinline__ void as
     u64* s_unseen = s_best + 64;
     unsigned char* s_fresh = reinterpret_cast<unsigned char*>(s_unseen + 2u * lds.batches);
     unsigned char* s_row = s_fresh + 64;
-    unsigned* s_row32 = reinterpret_cast<unsigned*>(s_row);
-
-    s_best[lane] = ~0ull;
-    for (unsigned d = lane; d < lds.rowb / 4u; d += 64u) s_row32[d] = 0xffffffffu;
+    match_reset(s_best, s_row, lds.rowb, lane);
 
     const int src = a.anc ? a.anc[i] : i;
     float st, ct;
@@ -84,23 +60,20 @@ template <bool CREATE, class NOISE, class QP> __device__ __forceinline__ void as
     const int row_bytes = __builtin_amdgcn_readfirstlane(5 * a.plane_stride * 4);
     const __amdgpu_buffer_rsrc_t rin = row_rsrc(a.map, src, a.row_stride, row_bytes);
     const int pl = __builtin_amdgcn_readfirstlane(a.plane_stride * 4);
-    // a. lane k: detection k in the world frame (the observed point of ekf_particle / ekf_first_sighting)
-    const float zxk = lane < K ? a.det_zx[lane] : 0.0f, zyk = lane < K ? a.det_zy[lane] : 0.0f;
     float wxk, wyk;
-    ekf_first_sighting<float>(zxk, zyk, st, ct, px, py, wxk, wyk);
+    match_world_point(a.det_zx, a.det_zy, K, lane, st, ct, px, py, wxk, wyk);
 
     const NOISE noise(qp, st, ct);
     const float inf = __uint_as_float(0x7f800000u);
     bool near = false;   // lane k: some seen landmark lies within new_gate of detection k
     for (unsigned b = 0; b < lds.batches; ++b) {
         v2f m[5];
-        unsigned l[2];
-        bool in[2], seen[2];
+        const unsigned l0 = b * 128u + lane;
+        bool in[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            l[t] = b * 128u + 64u * t + lane;
-            in[t] = l[t] < L;
-            const unsigned off = (in[t] ? l[t] : 0u) * 4u;   // clamped index + select instead of a predicated load
+            in[t] = l0 + 64u * t < L;
+            const unsigned off = (in[t] ? l0 + 64u * t : 0u) * 4u;   // clamped index + select instead of a predicated load
 #pragma unroll
             for (int p = 0; p < 5; ++p) m[p][t] = row_load(rin, off, p * pl);
         }
@@ -108,48 +81,33 @@ template <bool CREATE, class NOISE, class QP> __device__ __forceinline__ void as
         const v2f my = m[1], pxx = m[2], pxy = m[3], pyy = m[4];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            seen[t] = in[t] && !(pxx[t] < 0.0f);   // the update's own first-sighting test
+            const bool seen = in[t] && !(pxx[t] < 0.0f);   // the update's own first-sighting test
             const u64 unseen = __ballot(in[t] && pxx[t] < 0.0f);
             if (lane == 0) s_unseen[2u * b + t] = unseen;
-            // a landmark that takes no part: NaN in its mean makes every m NaN, and NaN passes none of the comparisons below
-            mx[t] = seen[t] ? mx[t] : __uint_as_float(0x7fc00000u);
+            mx[t] = seen ? mx[t] : __uint_as_float(0x7fc00000u);   // (takes no part: match_body.h)
         }
         // b. S^-1, once per landmark — or, under a covariance per detection, per pair inside the loop
         EkfShared<v2f> h;
         if constexpr (!NOISE::kPerDetection) h = noise.inverse(pxx, pxy, pyy);
-        // c. the cheapest detection of each landmark
         v2f best = bc2(inf);
         unsigned bk[2] = { 0u, 0u };
         for (unsigned k = 0; k < K; ++k) {
-            const v2f wx = bc2(lane_value(wxk, (int)k)), wy = bc2(lane_value(wyk, (int)k));
+            v2f wx, wy;
+            match_point(wxk, wyk, k, wx, wy);
             if constexpr (NOISE::kPerDetection) h = noise.inverse(pxx, pxy, pyy, k);
-            const v2f dx = wx - mx, dy = wy - my;
-            const v2f t0 = h.i00 * dx + h.i01 * dy, t1 = h.i01 * dx + h.i11 * dy;
-            const v2f maha = dx * t0 + dy * t1;
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const bool take = maha[t] < best[t];
-                best[t] = take ? maha[t] : best[t];
-                bk[t] = take ? k : bk[t];
-            }
+            const v2f maha = match_pair(wx, wy, k, mx, my, h, best, bk);
             if (CREATE) {   // lane k keeps detection k's flag
                 const bool any = __builtin_amdgcn_ballot_w64(maha[0] <= a.new_gate || maha[1] <= a.new_gate) != 0;
                 near = (lane == k && any) ? true : near;
             }
         }
-        // d. candidates post to their detection's minimum
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-            if (seen[t] && best[t] >= 0.0f && best[t] <= a.gate) {
-                const unsigned bits = best[t] == 0.0f ? 0u : __float_as_uint(best[t]);   // -0 -> +0
-                atomicMin(&s_best[bk[t]], ((u64)bits << 32) | l[t]);
-            }
+        match_post(s_best, best, bk, a.gate, l0);
     }
     wave_lds_sync();
 
-    const u64 won = s_best[lane];
-    const bool matched = lane < K && won != ~0ull;
-    if (matched) s_row[(unsigned)won] = (unsigned char)lane;
+    const MatchWinner won = match_winner(s_best, lane, K);
+    const bool matched = won.matched;
+    if (matched) s_row[won.l] = (unsigned char)lane;
     const int nmatched = __popcll(__ballot(matched));
     int ncreated = 0;
     if (CREATE) {
@@ -176,15 +134,7 @@ template <bool CREATE, class NOISE, class QP> __device__ __forceinline__ void as
     }
     wave_lds_sync();
 
-    // the row: [0, rowb) from LDS (255 from L on), the rest of the stride 255
-    const unsigned stride = (unsigned)a.assoc_stride;
-    uint8_t* out = a.assoc + (size_t)i * stride;
-    if ((stride & 3u) == 0 && (reinterpret_cast<uintptr_t>(a.assoc) & 3u) == 0) {   // (wave-uniform) every row starts on a dword
-        unsigned* out32 = reinterpret_cast<unsigned*>(out);
-        for (unsigned d = lane; d < stride / 4u; d += 64u) out32[d] = d < lds.rowb / 4u ? s_row32[d] : 0xffffffffu;
-    } else {
-        for (unsigned c = lane; c < stride; c += 64u) out[c] = c < lds.rowb ? s_row[c] : (uint8_t)255;
-    }
+    match_row_write(s_row, lds.rowb, a.assoc, i, (unsigned)a.assoc_stride, lane);
 }
 
 template <bool CREATE> __global__ __launch_bounds__(kEkfWaves * 64) void associate_kernel(AssocArgs a)
@@ -213,36 +163,23 @@ bool assoc_args_ok(const AssocArgs& a)
 
 }  // namespace
 
-hipError_t launch_associate(hipStream_t stream, const AssocArgs& a_in, const EkfAnisoCov* q, bool create, const EventPair* ev)
+hipError_t launch_associate(hipStream_t stream, const AssocArgs& a_in, const EkfAnisoCov* q, const DetCovArgs* dq, bool create, const EventPair* ev)
 {
     if (a_in.n <= 0) return hipSuccess;
-    if (!assoc_args_ok(a_in) || (q && !ekf_aniso_cov_ok(*q))) return hipErrorInvalidValue;
+    if (!assoc_args_ok(a_in) || (q && dq) || (q && !ekf_aniso_cov_ok(*q)) ||
+        (dq && (dq->ndet != a_in.ndet || (dq->ndet > 0 && (!dq->qxx || !dq->qxy || !dq->qyy)))))
+        return hipErrorInvalidValue;
     AssocArgs a = a_in;
     const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
     const size_t lds = (size_t)kEkfWaves * assoc_lds((unsigned)a.nlandmarks).per_wave;   // at most 4 x 9 792 bytes
-    if (ev) (void)hipEventRecord(ev->start, stream);
-    if (q) {
-        if (create) associate_aniso_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a, *q);
-        else associate_aniso_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a, *q);
-    } else {
-        if (create) associate_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
-        else associate_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
-    }
-    if (ev) (void)hipEventRecord(ev->stop, stream);
-    return hipGetLastError();
-}
-
-hipError_t launch_associate_detcov(hipStream_t stream, const AssocArgs& a_in, const DetCovArgs& q, bool create, const EventPair* ev)
-{
-    if (a_in.n <= 0) return hipSuccess;
-    if (!assoc_args_ok(a_in) || q.ndet != a_in.ndet || (q.ndet > 0 && (!q.qxx || !q.qxy || !q.qyy))) return hipErrorInvalidValue;
-    AssocArgs a = a_in;
-    const int blocks = xcd_grid(a.n, kEkfWaves, a.xcd_chunk);
-    const size_t lds = (size_t)kEkfWaves * assoc_lds((unsigned)a.nlandmarks).per_wave;
-    if (ev) (void)hipEventRecord(ev->start, stream);
-    if (create) associate_detcov_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
-    else associate_detcov_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
-    if (ev) (void)hipEventRecord(ev->stop, stream);
+    const auto launch = [&](auto kernel, const auto&... noise) {
+        if (ev) (void)hipEventRecord(ev->start, stream);
+        kernel<<<blocks, kEkfWaves * 64, lds, stream>>>(a, noise...);
+        if (ev) (void)hipEventRecord(ev->stop, stream);
+    };
+    if (dq) create ? launch(associate_detcov_kernel<true>, *dq) : launch(associate_detcov_kernel<false>, *dq);
+    else if (q) create ? launch(associate_aniso_kernel<true>, *q) : launch(associate_aniso_kernel<false>, *q);
+    else create ? launch(associate_kernel<true>) : launch(associate_kernel<false>);
     return hipGetLastError();
 }
 

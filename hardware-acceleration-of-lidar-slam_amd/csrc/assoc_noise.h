@@ -1,7 +1,12 @@
 // assoc_noise.h — the measurement noise of one particle as an associating kernel sees it (associate_body of assoc_kernels.hip,
 // localise_particle of localise_kernels.hip): one policy per noise form, each giving S^-1 = (P + noise)^-1 of the two landmarks of
-// a lane with the operations, and the reciprocal, of the landmark update under that form.  One copy of the arithmetic for every
-// kernel that gates and matches.
+// a lane — step b of the matching, whose other steps are match_body.h — with the operations, and the reciprocal, of the landmark
+// update under that form.  One copy of the arithmetic for every kernel that gates and matches.
+//
+// A policy is constructed from (its parameters, sine, cosine of the particle's heading), says in kPerDetection whether S^-1 is
+// formed once per landmark — inverse(pxx, pxy, pyy) — or per (landmark, detection) pair — inverse(pxx, pxy, pyy, k) — and returns it
+// in EkfShared's i00 / i01 / i11.  (A fourth policy of this shape, the inverse read from a prepared map, is LocNoisePrepared of
+// localise_kernels.hip.)
 #pragma once
 
 #include "ekf_aniso_math.h"
@@ -9,8 +14,6 @@
 
 namespace slam {
 
-// The measurement noise of one particle as the association sees it: S^-1 = (P + noise)^-1 of the two landmarks of a lane, in
-// EkfShared's i00 / i01 / i11.
 struct AssocNoiseIso {   // q I: ekf_det_terms without the logarithm, then ekf_shared_from
     static constexpr bool kPerDetection = false;
     v2f q;

@@ -180,19 +180,13 @@ int slam_engine_associate(slam_engine* e, const float* d_map, int64_t row_stride
     if (!noise.per_det && noise.full && !slam_aniso_cov_from(e, noise.meas_cov, &q)) return SLAM_ERR_INVALID_ARG;
     if (e->ndet < 0 || (noise.per_det && !e->det_has_cov)) return SLAM_ERR_NOT_READY;
     if (n == 0) return SLAM_OK;
-    if (noise.per_det) {
-        const AssocArgs a = assoc_args(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, 0.0f, gate, new_gate, d_assoc,
-                                       assoc_stride, d_stats);
-        const DetCovArgs dq{ e->d_det_qxx, e->d_det_qxy, e->d_det_qyy, e->ndet };
-        SLAM_HIP_TRY(e, launch_associate_detcov(e->stream, a, dq, create != 0, e->prof_next(SLAM_PROF_PAGES)));
-        e->assoc_detcov_launches[0]++;
-        return SLAM_OK;
-    }
-    // (meas_var of the arguments is not read under a 2x2 covariance)
-    const AssocArgs a = assoc_args(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n, noise.full ? 0.0f : noise.meas_var,
-                                   gate, new_gate, d_assoc, assoc_stride, d_stats);
-    SLAM_HIP_TRY(e, launch_associate(e->stream, a, noise.full ? &q : nullptr, create != 0, e->prof_next(SLAM_PROF_PAGES)));
-    (noise.full ? e->assoc_aniso_launches : e->assoc_launches)[0]++;
+    // (meas_var of the arguments is not read under a covariance)
+    const AssocArgs a = assoc_args(e, d_map, row_stride, plane_stride, nlandmarks, d_x, d_y, d_th, d_anc, n,
+                                   noise.per_det || noise.full ? 0.0f : noise.meas_var, gate, new_gate, d_assoc, assoc_stride, d_stats);
+    const DetCovArgs dq{ e->d_det_qxx, e->d_det_qxy, e->d_det_qyy, e->ndet };
+    SLAM_HIP_TRY(e, launch_associate(e->stream, a, !noise.per_det && noise.full ? &q : nullptr, noise.per_det ? &dq : nullptr, create != 0,
+                                     e->prof_next(SLAM_PROF_PAGES)));
+    (noise.per_det ? e->assoc_detcov_launches : noise.full ? e->assoc_aniso_launches : e->assoc_launches)[0]++;
     return SLAM_OK;
 }
 

@@ -23,48 +23,17 @@ int slam_known_map_prepare_dev(slam_engine* e, const float* d_map, int plane_str
     return SLAM_OK;
 }
 
-int slam_localise_dev(slam_engine* e, const float* d_prepared, int plane_stride, int nlandmarks, const float* d_x, const float* d_y,
-                      const float* d_th, int n, float gate, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats, float* d_loglik)
-{
-    SLAM_ENTER(e);
-    if (int rc = slam_engine_resolve_detections(e)) return rc;
-    if (n < 0 || nlandmarks < 1 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || (d_assoc && assoc_stride < nlandmarks) ||
-        !(gate > 0.0f && gate <= std::numeric_limits<float>::max()) || !d_prepared || (n > 0 && (!d_x || !d_y || !d_th || !d_stats)))
-        return SLAM_ERR_INVALID_ARG;
-    if (e->ndet < 0) return SLAM_ERR_NOT_READY;
-    if (n == 0) return SLAM_OK;
-    if (!d_loglik) SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
-    LocaliseArgs a;
-    a.map = d_prepared;
-    a.plane_stride = plane_stride;
-    a.nlandmarks = nlandmarks;
-    a.x = d_x;
-    a.y = d_y;
-    a.th = d_th;
-    a.n = n;
-    a.det_zx = e->d_det_zx;
-    a.det_zy = e->d_det_zy;
-    a.ndet = e->ndet;
-    a.gate = gate;
-    a.assoc = d_assoc;
-    a.assoc_stride = assoc_stride;
-    a.stats = d_stats;
-    a.loglik = d_loglik ? d_loglik : e->ll_buf.as<float>();
-    SLAM_HIP_TRY(e, launch_localise(e->stream, a, e->prof_next(SLAM_PROF_PAGES)));
-    if (!d_loglik) e->ll_n = n;
-    e->localise_launches[1]++;
-    return SLAM_OK;
-}
-
-int slam_localise_detcov_dev(slam_engine* e, const float* d_map, int plane_stride, int nlandmarks, const float* d_x, const float* d_y,
-                             const float* d_th, int n, float gate, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats, float* d_loglik)
+// the one checked path of the two entry points.  detcov: d_map is the map as it was given, the engine's detections must carry
+// their covariances, and the launch counts as slam_localise_detcov_dev's; else d_map is the prepared map
+static int localise(slam_engine* e, bool detcov, const float* d_map, int plane_stride, int nlandmarks, const float* d_x, const float* d_y,
+                    const float* d_th, int n, float gate, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats, float* d_loglik)
 {
     SLAM_ENTER(e);
     if (int rc = slam_engine_resolve_detections(e)) return rc;
     if (n < 0 || nlandmarks < 1 || nlandmarks > SLAM_MAX_OBS || plane_stride < nlandmarks || (d_assoc && assoc_stride < nlandmarks) ||
         !(gate > 0.0f && gate <= std::numeric_limits<float>::max()) || !d_map || (n > 0 && (!d_x || !d_y || !d_th || !d_stats)))
         return SLAM_ERR_INVALID_ARG;
-    if (e->ndet < 0 || !e->det_has_cov) return SLAM_ERR_NOT_READY;
+    if (e->ndet < 0 || (detcov && !e->det_has_cov)) return SLAM_ERR_NOT_READY;
     if (n == 0) return SLAM_OK;
     if (!d_loglik) SLAM_HIP_TRY(e, e->ll_buf.ensure(sizeof(float) * (size_t)n));
     LocaliseArgs a;
@@ -84,10 +53,22 @@ int slam_localise_detcov_dev(slam_engine* e, const float* d_map, int plane_strid
     a.stats = d_stats;
     a.loglik = d_loglik ? d_loglik : e->ll_buf.as<float>();
     const DetCovArgs dq{ e->d_det_qxx, e->d_det_qxy, e->d_det_qyy, e->ndet };
-    SLAM_HIP_TRY(e, launch_localise_detcov(e->stream, a, dq, e->prof_next(SLAM_PROF_PAGES)));
+    SLAM_HIP_TRY(e, launch_localise(e->stream, a, detcov ? &dq : nullptr, e->prof_next(SLAM_PROF_PAGES)));
     if (!d_loglik) e->ll_n = n;
-    e->localise_detcov_launches++;
+    (detcov ? e->localise_detcov_launches : e->localise_launches[1])++;
     return SLAM_OK;
+}
+
+int slam_localise_dev(slam_engine* e, const float* d_prepared, int plane_stride, int nlandmarks, const float* d_x, const float* d_y,
+                      const float* d_th, int n, float gate, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats, float* d_loglik)
+{
+    return localise(e, false, d_prepared, plane_stride, nlandmarks, d_x, d_y, d_th, n, gate, d_assoc, assoc_stride, d_stats, d_loglik);
+}
+
+int slam_localise_detcov_dev(slam_engine* e, const float* d_map, int plane_stride, int nlandmarks, const float* d_x, const float* d_y,
+                             const float* d_th, int n, float gate, uint8_t* d_assoc, int assoc_stride, int32_t* d_stats, float* d_loglik)
+{
+    return localise(e, true, d_map, plane_stride, nlandmarks, d_x, d_y, d_th, n, gate, d_assoc, assoc_stride, d_stats, d_loglik);
 }
 
 int slam_localise_detcov_count(slam_engine* e, int64_t* launches)

@@ -242,12 +242,12 @@ struct AssocArgs {
     int32_t* stats;        // [n][3] matched, created, dropped; may be nullptr
     int xcd_chunk;         // set by the launcher
 };
-// one wavefront per particle; create: unmatched detections far from every seen landmark take the unseen slots.  q (optional):
-// a full 2x2 sensor-frame measurement covariance (specification: tests/_assoc_aniso_spec.py) — every particle gates, matches and
-// creates with S = P + R_w(theta_i), a.meas_var is not read, ekf_aniso_cov_ok(*q) is checked; nullptr: a.meas_var * I
-hipError_t launch_associate(hipStream_t stream, const AssocArgs& a, const EkfAnisoCov* q, bool create, const EventPair* ev = nullptr);
-// ... under S = P + R_w(theta_i, k), Q_k per detection (q.ndet == a.ndet; a.meas_var is not read)
-hipError_t launch_associate_detcov(hipStream_t stream, const AssocArgs& a, const DetCovArgs& q, bool create, const EventPair* ev = nullptr);
+// one wavefront per particle; create: unmatched detections far from every seen landmark take the unseen slots.  The noise every
+// particle gates, matches and creates under, at most one of q and dq: neither — a.meas_var * I; q — a full 2x2 sensor-frame
+// covariance, S = P + R_w(theta_i) (specification: tests/_assoc_aniso_spec.py; ekf_aniso_cov_ok(*q) is checked); dq — a Q_k per
+// detection, S = P + R_w(theta_i, k) (dq->ndet == a.ndet).  Under q or dq a.meas_var is not read
+hipError_t launch_associate(hipStream_t stream, const AssocArgs& a, const EkfAnisoCov* q, const DetCovArgs* dq, bool create,
+                            const EventPair* ev = nullptr);
 // ---- localise_kernels.hip: localisation in a known landmark map (specification: tests/_localise_spec.py).
 // ONE map every particle shares, never changed: what depends on a covariance is prepared once per map, and the stage associates
 // the frame's detections per particle (create = 0) and leaves the matched pairs' log-likelihood.  No rows.
@@ -261,7 +261,7 @@ struct KnownMapArgs {
 // one thread per slot of the plane stride
 hipError_t launch_known_map_prepare(hipStream_t stream, const KnownMapArgs& a, const EventPair* ev = nullptr);
 struct LocaliseArgs {
-    const float* map;      // the prepared map [6][plane_stride] — launch_localise_detcov: the map as it was given [5][plane_stride]
+    const float* map;      // the prepared map [6][plane_stride] — under a DetCovArgs: the map as it was given [5][plane_stride]
     int plane_stride;
     int nlandmarks;        // 1 .. SLAM_MAX_OBS
     const float *x, *y, *th;
@@ -274,11 +274,10 @@ struct LocaliseArgs {
     int32_t* stats;        // [n][3] matched, 0, dropped
     float* loglik;         // [n]
 };
-// one wavefront per particle at a time, persistent workgroups; the prepared map staged in LDS where it fits
-hipError_t launch_localise(hipStream_t stream, const LocaliseArgs& a, const EventPair* ev = nullptr);
-// ... under S = P + R_w(theta_i, k), Q_k per detection (specification: tests/_localise_detcov_spec.py; q.ndet == a.ndet): nothing
-// can be prepared, a.map is the RAW map (KnownMapArgs::map) and S^-1 is formed per (landmark, detection) pair
-hipError_t launch_localise_detcov(hipStream_t stream, const LocaliseArgs& a, const DetCovArgs& q, const EventPair* ev = nullptr);
+// one wavefront per particle at a time, persistent workgroups; the map staged in LDS where it fits.  q == nullptr: a.map is the
+// prepared map; else S = P + R_w(theta_i, k), Q_k per detection (specification: tests/_localise_detcov_spec.py; q->ndet == a.ndet):
+// nothing can be prepared, a.map is the RAW map (KnownMapArgs::map) and S^-1 is formed per (landmark, detection) pair
+hipError_t launch_localise(hipStream_t stream, const LocaliseArgs& a, const DetCovArgs* q, const EventPair* ev = nullptr);
 // ---- evidence_kernels.hip: landmark existence evidence (specification: tests/_evidence_spec.py).  One byte
 // c in [0, cmax] per (particle, landmark slot) beside the rows; behind the update of a frame a matched landmark gains `hit`, a
 // visible unmatched one loses `miss`, and one that cannot pay is pruned: its slot gets the bits of a slot that was never used.

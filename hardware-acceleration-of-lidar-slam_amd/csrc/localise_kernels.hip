@@ -5,15 +5,11 @@
 //
 // known_map_prepare_kernel: M [5][stride] -> the prepared map [6][stride] = mx, my, i00, i01, i11, hl with S^-1 = (P + q I)^-1 and
 // hl = 0.5 log det S: the operations of ekf_det_terms / ekf_shared_from (ekf_rcp, det_logf), the bits the specification computes
-// per particle.  A slot that holds no landmark (P_xx < 0) and the padding behind L get a NaN mean: every Mahalanobis term of
-// theirs is NaN, NaN passes no comparison, they never become candidates.
+// per particle.  A slot that holds no landmark (P_xx < 0) and the padding behind L get a NaN mean: they take no part (match_body.h).
 //
-// localise_kernel: associate_body's mapping (assoc_kernels.hip) without rows.  ONE WAVEFRONT OWNS ONE PARTICLE at a time, lanes own
-// landmarks l and l + 64 of each batch of 128 and walk the K detections in a wave-uniform loop; det_sincosf once, the K world
-// points once (lane k keeps point k).
-//   c. every landmark keeps its cheapest detection (strict <, k ascending: the lowest k on ties, NaN never wins);
-//   d. the candidates (0 <= m <= gate) post (bits(m) << 32 | l) to an LDS 64-bit minimum per detection;
-//   e. lane k then holds detection k's winner: its term ((0 - 0.5 m) - hl) - log 2 pi from the m in the key and one read of hl, added
+// localise_kernel: the matching of match_body.h (a wavefront per particle at a time; steps a, c, d and the table row are its
+// functions) on that one map, without rows; det_sincosf once per particle.  What is the stage's own:
+//   e. lane k holds detection k's winner: its term ((0 - 0.5 m) - hl) - log 2 pi from the m in the key and one read of hl, added
 //      to accumulator l mod 128 in ascending l — batch by batch, batches without a winner skipped: what they would add is +0 to an
 //      accumulator that is never -0 — then accumulators j and j + 64 and the xor butterfly: orc_ekf_update's order.
 // The workgroups are persistent (a grid that fills the machine once, each wavefront takes particles a grid apart), so the prepared
@@ -31,12 +27,11 @@
 // covariance planes and its own R_w for hl = 0.5 log det S.  Everything else — minima, accumulation order, stats, table — is shared.
 
 #include "assoc_noise.h"
+#include "match_body.h"
 
 namespace slam {
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr unsigned kLocStagedMax = 2048;   // landmarks (whole batches) up to which the prepared map is staged: 48 KB
 
@@ -54,13 +49,6 @@ __host__ __device__ inline LocLds loc_lds(unsigned L, bool staged, bool table, u
     s.map_bytes = staged ? planes * 4u * s.Lr : 0u;
     s.per_wave = 64u * 8u + 128u * 4u + s.rowb;
     return s;
-}
-
-__device__ __forceinline__ void loc_lds_sync()   // what one lane wrote to LDS, every lane of the SAME wavefront may read afterwards
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 __global__ __launch_bounds__(256) void known_map_prepare_kernel(KnownMapArgs a)
@@ -117,10 +105,19 @@ template <bool RAW> struct LocMapMem {
     __device__ __forceinline__ float plane(unsigned p, unsigned l) const { return g[(size_t)p * ps + l]; }
 };
 
-// The noise of the stage: LocNoisePrepared — meas_var * I, S^-1 and hl are planes of the prepared map — or AssocNoiseDet on the raw map
+// The noise of the stage, a policy in the shape of assoc_noise.h's: LocNoisePrepared — meas_var * I, S^-1 and hl are planes 2 .. 5
+// of the prepared map — or AssocNoiseDet on the raw map
 struct LocNoisePrepared {
     static constexpr bool kPerDetection = false;
     __device__ __forceinline__ LocNoisePrepared(const DetCovArgs&, float, float) {}
+    __device__ __forceinline__ EkfShared<v2f> inverse(v2f m2, v2f m3, v2f m4) const
+    {
+        EkfShared<v2f> h;   // (only S^-1 is filled in)
+        h.i00 = m2;
+        h.i01 = m3;
+        h.i11 = m4;
+        return h;
+    }
 };
 // 0.5 log det S of lane k's winner wl
 template <class MAP> __device__ __forceinline__ float loc_half_logdet(const LocNoisePrepared&, const MAP& map, unsigned wl) { return map.plane(5u, wl); }
@@ -136,66 +133,43 @@ __device__ __forceinline__ void localise_particle(const LocaliseArgs& a, const D
                                                   u64* s_best, float* s_acc, unsigned char* s_row)
 {
     const unsigned K = (unsigned)a.ndet;
-    unsigned* s_row32 = reinterpret_cast<unsigned*>(s_row);
-    loc_lds_sync();   // (the particle before this one has read what is written here)
-    s_best[lane] = ~0ull;
+    wave_lds_sync();   // (the particle before this one has read what is written here)
+    match_reset(s_best, s_row, lds.rowb, lane);
     s_acc[lane] = 0.0f;
     s_acc[lane + 64u] = 0.0f;
-    for (unsigned d = lane; d < lds.rowb / 4u; d += 64u) s_row32[d] = 0xffffffffu;
 
     float st, ct;
     det_sincosf(a.th[i], st, ct);
-    const float px = a.x[i], py = a.y[i];
-    // a. lane k: detection k in the world frame (the observed point of ekf_particle)
-    const float zxk = lane < K ? a.det_zx[lane] : 0.0f, zyk = lane < K ? a.det_zy[lane] : 0.0f;
     float wxk, wyk;
-    ekf_first_sighting<float>(zxk, zyk, st, ct, px, py, wxk, wyk);
+    match_world_point(a.det_zx, a.det_zy, K, lane, st, ct, a.x[i], a.y[i], wxk, wyk);
     const NOISE noise(q, st, ct);   // (per detection: lane k's R_w(theta_i, k))
 
     const float inf = __uint_as_float(0x7f800000u);
     for (unsigned b = 0; b < lds.batches; ++b) {
         v2f m[5];
         map.pair(b, lane, m);
-        const v2f mx = m[0], my = m[1];
-        // c. the cheapest detection of each landmark
+        // b. S^-1: the prepared one — or (P + R_w(theta_i, k))^-1 per pair inside the loop
+        EkfShared<v2f> h;
+        if constexpr (!NOISE::kPerDetection) h = noise.inverse(m[2], m[3], m[4]);
         v2f best = bc2(inf);
         unsigned bk[2] = { 0u, 0u };
-        const auto pair_cost = [&](unsigned k) {
-            const v2f wx = bc2(lane_value(wxk, (int)k)), wy = bc2(lane_value(wyk, (int)k));
-            v2f i00 = m[2], i01 = m[3], i11 = m[4];   // the prepared S^-1 — or (P + R_w(theta_i, k))^-1 of this pair
-            if constexpr (NOISE::kPerDetection) {
-                const EkfShared<v2f> h = noise.inverse(m[2], m[3], m[4], k);
-                i00 = h.i00, i01 = h.i01, i11 = h.i11;
-            }
-            const v2f dx = wx - mx, dy = wy - my;
-            const v2f t0 = i00 * dx + i01 * dy, t1 = i01 * dx + i11 * dy;
-            const v2f maha = dx * t0 + dy * t1;
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const bool take = maha[t] < best[t];
-                best[t] = take ? maha[t] : best[t];
-                bk[t] = take ? k : bk[t];
-            }
-        };
-        for (unsigned k = 0; k < K; ++k) pair_cost(k);
-        // d. candidates post to their detection's minimum (a NaN mean — no landmark, padding — left best at +inf)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-            if (best[t] >= 0.0f && best[t] <= a.gate) {
-                const unsigned bits = best[t] == 0.0f ? 0u : __float_as_uint(best[t]);   // -0 -> +0
-                atomicMin(&s_best[bk[t]], ((u64)bits << 32) | (b * 128u + 64u * (unsigned)t + lane));
-            }
+        for (unsigned k = 0; k < K; ++k) {
+            v2f wx, wy;
+            match_point(wxk, wyk, k, wx, wy);
+            if constexpr (NOISE::kPerDetection) h = noise.inverse(m[2], m[3], m[4], k);
+            match_pair(wx, wy, k, m[0], m[1], h, best, bk);
+        }
+        match_post(s_best, best, bk, a.gate, b * 128u + lane);
     }
-    loc_lds_sync();
+    wave_lds_sync();
 
     // e. lane k: detection k's winner and its term (m = +0 where it was -0: the two subtractions behind it erase that sign)
-    const u64 won = s_best[lane];
-    const bool matched = lane < K && won != ~0ull;
-    const unsigned wl = matched ? (unsigned)won : 0u;
+    const MatchWinner won = match_winner(s_best, lane, K);
+    const bool matched = won.matched;
+    const unsigned wl = won.l;
     float term = 0.0f;
     if (matched) {
-        const float maha = __uint_as_float((unsigned)(won >> 32));
-        term = (-(0.5f * maha) - loc_half_logdet(noise, map, wl)) - 1.8378770664f;
+        term = (-(0.5f * __uint_as_float(won.mbits)) - loc_half_logdet(noise, map, wl)) - 1.8378770664f;
         if (lds.rowb) s_row[wl] = (unsigned char)lane;
     }
     const u64 mm = __ballot(matched);
@@ -205,9 +179,9 @@ __device__ __forceinline__ void localise_particle(const LocaliseArgs& a, const D
             const bool mine = matched && (wl >> 7) == b;   // at most one winner per accumulator and batch
             if (__ballot(mine) == 0) continue;
             if (mine) s_acc[wl & 127u] = s_acc[wl & 127u] + term;
-            loc_lds_sync();
+            wave_lds_sync();
         }
-    loc_lds_sync();
+    wave_lds_sync();
     const float total = wave_xor_tree_sum(s_acc[lane] + s_acc[lane + 64u]);
     if (lane == 0) {
         a.loglik[i] = total;
@@ -216,16 +190,7 @@ __device__ __forceinline__ void localise_particle(const LocaliseArgs& a, const D
         st3[1] = 0;
         st3[2] = (int)K - nmatched;
     }
-    if (lds.rowb) {   // the row: [0, rowb) from LDS (255 from L on), the rest of the stride 255
-        const unsigned stride = (unsigned)a.assoc_stride;
-        uint8_t* out = a.assoc + (size_t)i * stride;
-        if ((stride & 3u) == 0 && (reinterpret_cast<uintptr_t>(a.assoc) & 3u) == 0) {   // (wave-uniform) every row starts on a dword
-            unsigned* out32 = reinterpret_cast<unsigned*>(out);
-            for (unsigned d = lane; d < stride / 4u; d += 64u) out32[d] = d < lds.rowb / 4u ? s_row32[d] : 0xffffffffu;
-        } else {
-            for (unsigned c = lane; c < stride; c += 64u) out[c] = c < lds.rowb ? s_row[c] : (uint8_t)255;
-        }
-    }
+    if (lds.rowb) match_row_write(s_row, lds.rowb, a.assoc, i, (unsigned)a.assoc_stride, lane);
 }
 
 // RAW: a.map is the map as it was given and NOISE reads q; else the prepared map (q is not read)
@@ -275,18 +240,23 @@ template <bool STAGED> __global__ __launch_bounds__(kEkfWaves * 64) void localis
     localise_body<STAGED, true, AssocNoiseDet>(a, q);
 }
 
-// a grid that fills the machine once: as many workgroups as are resident together, or as the particles need
-template <class KERNEL> hipError_t loc_grid(KERNEL kernel, int n, size_t lds, int* blocks)
+// the launch of one of the four kernels: a grid that fills the machine once — as many workgroups as are resident together, or as
+// the particles need
+template <class KERNEL, class... NOISE>
+hipError_t loc_launch(KERNEL kernel, hipStream_t stream, const LocaliseArgs& a, size_t lds, const EventPair* ev, const NOISE&... noise)
 {
-    const int need = (n + kEkfWaves - 1) / kEkfWaves;
+    const int need = (a.n + kEkfWaves - 1) / kEkfWaves;
     int dev = 0, cus = 0, per_cu = 0;
     hipError_t err = hipGetDevice(&dev);
     if (err == hipSuccess) err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (err == hipSuccess) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kEkfWaves * 64, lds);
     if (err != hipSuccess) return err;
     const int64_t resident = (int64_t)cus * per_cu;
-    *blocks = resident > 0 && resident < need ? (int)resident : need;
-    return hipSuccess;
+    const int blocks = resident > 0 && resident < need ? (int)resident : need;
+    if (ev) (void)hipEventRecord(ev->start, stream);
+    kernel<<<blocks, kEkfWaves * 64, lds, stream>>>(a, noise...);
+    if (ev) (void)hipEventRecord(ev->stop, stream);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -306,37 +276,15 @@ hipError_t launch_known_map_prepare(hipStream_t stream, const KnownMapArgs& a, c
     return hipGetLastError();
 }
 
-hipError_t launch_localise(hipStream_t stream, const LocaliseArgs& a, const EventPair* ev)
+hipError_t launch_localise(hipStream_t stream, const LocaliseArgs& a, const DetCovArgs* q, const EventPair* ev)
 {
     if (a.n <= 0) return hipSuccess;
-    if (!localise_args_ok(a)) return hipErrorInvalidValue;
-    const bool staged = (unsigned)(a.nlandmarks + 127) / 128u * 128u <= kLocStagedMax;
-    const LocLds s = loc_lds((unsigned)a.nlandmarks, staged, a.assoc != nullptr, 6u);
+    if (!localise_args_ok(a) || (q && (q->ndet != a.ndet || (q->ndet > 0 && (!q->qxx || !q->qxy || !q->qyy))))) return hipErrorInvalidValue;
+    const bool staged = (unsigned)(a.nlandmarks + 127) / 128u * 128u <= kLocStagedMax;   // (either map: 48 KB prepared, 40 KB raw)
+    const LocLds s = loc_lds((unsigned)a.nlandmarks, staged, a.assoc != nullptr, q ? 5u : 6u);
     const size_t lds = (size_t)s.map_bytes + (size_t)kEkfWaves * s.per_wave;   // at most 60 KB staged, 36 KB from memory
-    int blocks = 0;
-    if (hipError_t err = staged ? loc_grid(localise_kernel<true>, a.n, lds, &blocks) : loc_grid(localise_kernel<false>, a.n, lds, &blocks)) return err;
-    if (ev) (void)hipEventRecord(ev->start, stream);
-    if (staged) localise_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
-    else localise_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a);
-    if (ev) (void)hipEventRecord(ev->stop, stream);
-    return hipGetLastError();
-}
-
-hipError_t launch_localise_detcov(hipStream_t stream, const LocaliseArgs& a, const DetCovArgs& q, const EventPair* ev)
-{
-    if (a.n <= 0) return hipSuccess;
-    if (!localise_args_ok(a) || q.ndet != a.ndet || (q.ndet > 0 && (!q.qxx || !q.qxy || !q.qyy))) return hipErrorInvalidValue;
-    const bool staged = (unsigned)(a.nlandmarks + 127) / 128u * 128u <= kLocStagedMax;   // the same landmark cap: 40 KB of map
-    const LocLds s = loc_lds((unsigned)a.nlandmarks, staged, a.assoc != nullptr, 5u);
-    const size_t lds = (size_t)s.map_bytes + (size_t)kEkfWaves * s.per_wave;   // at most 52 KB staged, 36 KB from memory
-    int blocks = 0;
-    if (hipError_t err = staged ? loc_grid(localise_detcov_kernel<true>, a.n, lds, &blocks) : loc_grid(localise_detcov_kernel<false>, a.n, lds, &blocks))
-        return err;
-    if (ev) (void)hipEventRecord(ev->start, stream);
-    if (staged) localise_detcov_kernel<true><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
-    else localise_detcov_kernel<false><<<blocks, kEkfWaves * 64, lds, stream>>>(a, q);
-    if (ev) (void)hipEventRecord(ev->stop, stream);
-    return hipGetLastError();
+    if (q) return staged ? loc_launch(localise_detcov_kernel<true>, stream, a, lds, ev, *q) : loc_launch(localise_detcov_kernel<false>, stream, a, lds, ev, *q);
+    return staged ? loc_launch(localise_kernel<true>, stream, a, lds, ev) : loc_launch(localise_kernel<false>, stream, a, lds, ev);
 }
 
 }  // namespace slam

@@ -28,20 +28,13 @@
 
 #include "ekf_aniso_math.h"
 #include "evidence_common.h"
+#include "match_body.h"
 
 namespace slam {
 
 namespace {
 
 typedef unsigned long long u64;
-
-// what one lane wrote to LDS, every lane of the SAME wavefront may read afterwards
-__device__ __forceinline__ void merge_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // the table bytes of landmarks l and l + 64 (l = 128 b + lane) of one particle
 template <bool WIDE>
@@ -136,7 +129,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void merge_kernel(MergeArgs a)
     const unsigned A = count < 64u ? count : 64u;
     int nmerged = 0, nrefused = 0;
     if (A != 0u) {   // (wave-uniform)
-        merge_lds_sync();
+        wave_lds_sync();
         float w[5];   // lane j: anchor j
 #pragma unroll
         for (int p = 0; p < 5; ++p) w[p] = s_anchor[p][lane < A ? lane : 0u];
@@ -188,7 +181,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void merge_kernel(MergeArgs a)
                     atomicMin(&s_best[bj[t]], ((u64)bits << 32) | l[t]);
                 }
         }
-        merge_lds_sync();
+        wave_lds_sync();
         // 3. the anchor chooses and absorbs (every lane runs the arithmetic, the stores are selected)
         const u64 won = s_best[lane];
         const bool has = lane < A && won != ~0ull;
