@@ -155,6 +155,9 @@ SIGNATURES = {
     "slam_localise_counts": (_i, [_vp, _vp]),
     "slam_localise_detcov_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp]),
     "slam_localise_detcov_count": (_i, [_vp, _vp]),
+    "slam_localise_miss_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slam_localise_detcov_miss_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "slam_localise_miss_count": (_i, [_vp, _vp]),
     "slam_detect_params_default": (None, [_vp]),
     "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
     "slam_detect_count": (_i, [_vp, _vp]),
@@ -221,6 +224,8 @@ SIGNATURES = {
     "slam_pf_known_map_set": (_i, [_vp, _vp, _i, _f, _f]),
     "slam_pf_known_map_detcov_set": (_i, [_vp, _vp, _i, _f, _f]),
     "slam_pf_known_map_device_view": (_i, [_vp, _vp, _vp, _vp]),
+    "slam_pf_known_map_miss_set": (_i, [_vp, _f, _f, _i, _f, _f, _f, _i, _f]),
+    "slam_pf_known_map_miss_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_detect_set": (_i, [_vp, _vp]),
     "slam_pf_detect_fit_set": (_i, [_vp, _vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
@@ -537,6 +542,29 @@ class Engine:
         """-> stage launches under per-detection covariances of this engine so far."""
         c = C.c_int64(0)
         self._ck(self.lib.slam_localise_detcov_count(self.h, C.byref(c)), "localise_detcov_count")
+        return int(c.value)
+
+    def localise_miss_dev(self, d_prepared, plane_stride, nlandmarks, d_x, d_y, d_th, n, gate, d_assoc, assoc_stride, d_stats, d_loglik,
+                          view, d_missed, d_spared=None, d_outside=None):
+        """``slam_localise_miss_dev``: ``localise_dev`` whose launch also counts the landmarks in view that no detection matched —
+        view: a ``LocaliseView``; missed, spared, outside int32 [n] (the last two may be None)."""
+        self._ck(self.lib.slam_localise_miss_dev(self.h, _ptr(d_prepared), plane_stride, nlandmarks, _ptr(d_x), _ptr(d_y), _ptr(d_th), n, gate,
+                                                 _ptr(d_assoc), assoc_stride, _ptr(d_stats), _ptr(d_loglik),
+                                                 C.byref(view) if view is not None else None, _ptr(d_missed), _ptr(d_spared),
+                                                 _ptr(d_outside)), "localise_miss_dev")
+
+    def localise_detcov_miss_dev(self, d_map, plane_stride, nlandmarks, d_x, d_y, d_th, n, gate, d_assoc, assoc_stride, d_stats, d_loglik,
+                                 view, d_missed, d_spared=None, d_outside=None):
+        """``slam_localise_detcov_miss_dev``: ``localise_detcov_dev`` with the counts of ``localise_miss_dev``."""
+        self._ck(self.lib.slam_localise_detcov_miss_dev(self.h, _ptr(d_map), plane_stride, nlandmarks, _ptr(d_x), _ptr(d_y), _ptr(d_th), n,
+                                                        gate, _ptr(d_assoc), assoc_stride, _ptr(d_stats), _ptr(d_loglik),
+                                                        C.byref(view) if view is not None else None, _ptr(d_missed), _ptr(d_spared),
+                                                        _ptr(d_outside)), "localise_detcov_miss_dev")
+
+    def localise_miss_count(self):
+        """-> launches of the two miss forms of the localise stage of this engine so far."""
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_localise_miss_count(self.h, C.byref(c)), "localise_miss_count")
         return int(c.value)
 
     def assoc_counts(self):
@@ -913,6 +941,13 @@ class Engine:
         self._ck(self.lib.slam_gather_map_dev(self.h, _ptr(d_in), _ptr(d_out), in_row_stride, out_row_stride,
                                               in_plane_stride, out_plane_stride, nlandmarks, _ptr(d_idx), n),
                  "gather_map_dev")
+
+
+class LocaliseView(C.Structure):
+    """``slam_localise_view``: what a pose sees of a known map — view_range, the arc [lo, hi] of the diamond angle (0, 4: the whole
+    circle), sight != 0: the engine's current sight table with `margin`."""
+
+    _fields_ = [("view_range", C.c_float), ("lo", C.c_float), ("hi", C.c_float), ("sight", C.c_int32), ("margin", C.c_float)]
 
 
 class DetectParams(C.Structure):
@@ -1341,6 +1376,20 @@ class PfSession:
         Lp = (L.value + 31) // 32 * 32
         return {"prepared": DeviceArray(p.value, (6, Lp), "<f4", self) if p.value else None, "nlandmarks": L.value,
                 "stats": DeviceArray(st.value, (self.n, 3), "<i4", self)}
+
+    def known_map_miss_set(self, log_miss: float, view_range: float, fov=None, sight=None):
+        """``slam_pf_known_map_miss_set`` (only while a known map is set): observing frames also count the landmarks in view that no
+        detection matched and charge log_miss for each.  fov: None (the whole circle) or (angle_min, angle_max, edge); sight: None
+        or (bins, margin); view_range = 0 switches it off."""
+        on, (a0, a1, edge) = (1, fov) if fov is not None else (0, (0.0, 0.0, 0.0))
+        bins, margin = sight if sight is not None else (0, 0.0)
+        self.e._ck(self.e.lib.slam_pf_known_map_miss_set(self.h, log_miss, view_range, on, a0, a1, edge, int(bins), margin), "pf_known_map_miss_set")
+
+    def known_map_miss_view(self):
+        """``slam_pf_known_map_miss_device_view``: the last miss stage's missed, spared and outside counts, int32 [n] each."""
+        m, s, o = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.e._ck(self.e.lib.slam_pf_known_map_miss_device_view(self.h, C.byref(m), C.byref(s), C.byref(o)), "pf_known_map_miss_device_view")
+        return {k: DeviceArray(v.value, (self.n,), "<i4", self) for k, v in (("missed", m), ("spared", s), ("outside", o))}
 
     def assoc_view(self):
         """``slam_pf_assoc_device_view``: the last frame's table uint8 [n][stride] and stats int32 [n][3], indexed like score."""

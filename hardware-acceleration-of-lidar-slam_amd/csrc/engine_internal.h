@@ -108,6 +108,7 @@ struct slam_engine {
     int64_t assoc_weight_launches = 0;      // slam_assoc_weight_count: launches of slam_assoc_weight_dev (in no other counter)
     int64_t localise_launches[2] = { 0, 0 };   // slam_localise_counts: prepare launches, stage launches (in no other counter)
     int64_t localise_detcov_launches = 0;      // slam_localise_detcov_count: stage launches under per-detection Q (in no other counter)
+    int64_t localise_miss_launches = 0;        // slam_localise_miss_count: launches of the miss form, either noise (in no other counter)
     // the detector (slam_detect_scan_dev): its kernel writes det_buf and leaves {ndet, sequence} in mapped host memory; until the
     // next stage that needs the count on the host has picked it up (slam_engine_resolve_detections) it is PENDING
     int32_t* h_det = nullptr;

@@ -1,6 +1,7 @@
 // evidence_common.h — what the kernels of the existence evidence share (evidence_kernels.hip: the stage, init and gather;
-// sight_kernels.hip: the sight table; merge_kernels.hip) and the host's slam_fov_bound: the visibility test's r2, the diamond
-// angle of a direction, and the byte traffic of a batch of 128 landmarks as dwords (WIDE) — see the head of evidence_kernels.hip
+// sight_kernels.hip: the sight table; merge_kernels.hip), the misses of the localise stage (localise_kernels.hip) and the host's
+// slam_fov_bound: the visibility test's r2, the diamond angle of a direction, the visibility predicate itself
+// (evidence_visibility), and the byte traffic of a batch of 128 landmarks as dwords (WIDE) — see the head of evidence_kernels.hip
 // for the access shape.
 #pragma once
 
@@ -41,6 +42,77 @@ __device__ __forceinline__ unsigned diamond_bin(float p, float quarter, unsigned
 {
 #pragma clang fp contract(off)
     return (unsigned)(int)(p * quarter) & mask;
+}
+
+// lo <= hi: the arc [lo, hi]; lo > hi: the arc that wraps through p = 4 = 0.  A bound itself is in view
+__device__ __forceinline__ bool fov_in_view(float p, bool has, float lo, float hi, bool wraps)
+{
+    const bool ge = p >= lo, le = p <= hi;
+    return !has || (wraps ? (ge || le) : (ge && le));
+}
+
+// THE VISIBILITY PREDICATE of a pose (tests/_evidence_spec.py, _sight_spec.py, _fov_spec.py), the one copy the evidence stage
+// (evidence_kernels.hip) and the misses of the localise stage (localise_kernels.hip) share.  What a wavefront knows of its pose
+// and of the frame:
+struct EvidenceView {
+    float px, py, sn, cs;   // the pose; sn, cs = det_sincosf(theta), read only under fov || sight
+    float range2;           // view_range * view_range, one float32 product made on the host
+    float lo, hi;           // the arc of the diamond angle (fov)
+    bool wraps;             // lo > hi
+    const float* tab;       // the sight table, staged in LDS (sight)
+    float quarter;          // bins / 4
+    unsigned mask;          // bins - 1
+    float margin;
+};
+// N landmarks of every lane (means mx, my; open: the landmark can be due a miss at all — it is seen and, where the caller knows
+// already, not hit) -> due = open & r2 <= range2 (a NaN mean is not visible); view: its direction in the sensor frame lies in
+// the arc (fov; a direction without a diamond angle is in view); hidden: due & view & behind what the scan hit — the nearest
+// return of its bin and the two neighbours is closer than (r - margin)^2 (sight).  fov, sight: compile-time constants or
+// wave-uniform values.  EVERY LANE OF THE WAVEFRONT TAKES PART: the rotation, the division and the compares run only in
+// wavefronts in which some lane is due, the square root and the three table reads only where some lane is due AND in view; the
+// results depend on neither skip
+template <int N>
+__device__ __forceinline__ void evidence_visibility(const EvidenceView& v, bool fov, bool sight, const float (&mx)[N], const float (&my)[N],
+                                                    const bool (&open)[N], bool (&due)[N], bool (&view)[N], bool (&hidden)[N])
+{
+#pragma clang fp contract(off)
+    float r2[N];
+    bool some = false;
+#pragma unroll
+    for (int t = 0; t < N; ++t) {
+        r2[t] = evidence_r2(mx[t], my[t], v.px, v.py);
+        due[t] = open[t] && r2[t] <= v.range2;
+        view[t] = true;
+        hidden[t] = false;
+        some = some || due[t];
+    }
+    if ((fov || sight) && __ballot(some)) {
+        float p[N];
+        bool has[N];
+        some = false;
+#pragma unroll
+        for (int t = 0; t < N; ++t) {
+            const float dx = mx[t] - v.px, dy = my[t] - v.py;   // the visibility test's own dx, dy
+            const float xa = v.cs * dx, xb = v.sn * dy;
+            const float zx = xa - xb;                            // z = R(theta) (w - t)
+            const float ya = v.sn * dx, yb = v.cs * dy;
+            const float zy = ya + yb;
+            has[t] = diamond_angle(zx, zy, p[t]);
+            view[t] = fov ? fov_in_view(p[t], has[t], v.lo, v.hi, v.wraps) : true;
+            some = some || (due[t] && view[t]);
+        }
+        if (sight && __ballot(some)) {
+#pragma unroll
+            for (int t = 0; t < N; ++t) {
+                const unsigned j = diamond_bin(p[t], v.quarter, v.mask);
+                const float near = fminf(fminf(v.tab[(j - 1u) & v.mask], v.tab[j]), v.tab[(j + 1u) & v.mask]);   // (no NaN in the table)
+                const float r = sqrtf(r2[t]);   // correctly rounded (NOT __fsqrt_rn: det_math.h)
+                const float g = r - v.margin;
+                const float g2 = g * g;
+                hidden[t] = due[t] && view[t] && has[t] && g > 0.0f && near < g2;   // a NaN anywhere: not hidden
+            }
+        }
+    }
 }
 
 // WIDE: the bytes of landmarks l and l + 64 (l = 128 b + lane) out of w — lanes 0..31 hold the batch's 32 dwords of one byte

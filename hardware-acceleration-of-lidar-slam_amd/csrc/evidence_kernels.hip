@@ -15,6 +15,7 @@
 // l + 64 of each batch of 128 (the access shape of ekf_row_body.h, the grid and row resources of associate_kernel).  Per landmark
 // it reads three planes of the row (12 B), the table byte and the evidence byte, and writes one byte; only a prune, which is
 // rare, writes the five floats of the slot.
+// The predicate — due, in view, hidden — is evidence_visibility of evidence_common.h, which the localise stage's misses call too.
 // FOV || SIGHT: the heading is read and, only in wavefronts in which some lane is due a miss, the offset is rotated into the
 // sensor frame and its diamond angle taken (one division).  SIGHT: the table is staged once per workgroup in LDS (at most 4 KB:
 // eight workgroups of a CU hold 32 KB of its 160; the workgroup's only barrier behind it), and the square root and the three
@@ -34,13 +35,6 @@
 namespace slam {
 
 namespace {
-
-// lo <= hi: the arc [lo, hi]; lo > hi: the arc that wraps through p = 4 = 0.  A bound itself is in view
-__device__ __forceinline__ bool fov_in_view(float p, bool has, float lo, float hi, bool wraps)
-{
-    const bool ge = p >= lo, le = p <= hi;
-    return !has || (wraps ? (ge || le) : (ge && le));
-}
 
 template <bool WIDE, bool FOV, bool SIGHT>
 __global__ __launch_bounds__(kEkfWaves * 64) void evidence_stage_kernel(EvidenceArgs a, SightArgs sg, FovArgs fv)
@@ -62,9 +56,7 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_stage_kernel(Evidence
     const float px = a.x[i], py = a.y[i];
     float sn = 0.0f, cs = 1.0f;
     if (DIR) det_sincosf(sg.th[i], sn, cs);
-    const bool wraps = fv.lo > fv.hi;
-    const float quarter = (float)(sg.bins >> 2);
-    const unsigned mask = (unsigned)sg.bins - 1u;
+    const EvidenceView ev{ px, py, sn, cs, a.range2, fv.lo, fv.hi, fv.lo > fv.hi, s_tab, (float)(sg.bins >> 2), (unsigned)sg.bins - 1u, sg.margin };
     const int row_bytes = __builtin_amdgcn_readfirstlane(5 * a.plane_stride * 4);
     const __amdgpu_buffer_rsrc_t row = row_rsrc(a.map, i, a.row_stride, row_bytes);   // read, and written where a landmark is pruned
     const int pl = __builtin_amdgcn_readfirstlane(a.plane_stride * 4);
@@ -101,42 +93,14 @@ __global__ __launch_bounds__(kEkfWaves * 64) void evidence_stage_kernel(Evidence
 #pragma unroll
             for (int p = 0; p < 3; ++p) m[p][t] = row_load(row, at * 4u, p * pl);
         }
-        bool seen[2], hit_now[2], due[2], view[2], hidden[2];
-        float r2[2];
+        bool seen[2], hit_now[2], open[2], due[2], view[2], hidden[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             seen[t] = in[t] && !(m[2][t] < 0.0f);   // the update's own first-sighting test: -0 counts as seen
             hit_now[t] = tk[t] < K;                  // a byte that names no detection of this frame is no hit
-            r2[t] = evidence_r2(m[0][t], m[1][t], px, py);
-            due[t] = seen[t] && !hit_now[t] && r2[t] <= a.range2;   // due a miss unless outside or hidden (a NaN mean is not visible)
-            view[t] = true;
-            hidden[t] = false;
+            open[t] = seen[t] && !hit_now[t];        // due a miss unless out of range, outside or hidden
         }
-        if (DIR && __ballot(due[0] || due[1])) {   // wave-uniform: the rotation, the division and the compares only where some lane needs them
-            float p[2];
-            bool has[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const float dx = m[0][t] - px, dy = m[1][t] - py;   // the visibility test's own dx, dy
-                const float xa = cs * dx, xb = sn * dy;
-                const float zx = xa - xb;                            // z = R(theta) (w - t)
-                const float ya = sn * dx, yb = cs * dy;
-                const float zy = ya + yb;
-                has[t] = diamond_angle(zx, zy, p[t]);
-                view[t] = FOV ? fov_in_view(p[t], has[t], fv.lo, fv.hi, wraps) : true;
-            }
-            if (SIGHT && __ballot((due[0] && view[0]) || (due[1] && view[1]))) {   // the square root and the table: due AND in view
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const unsigned j = diamond_bin(p[t], quarter, mask);
-                    const float near = fminf(fminf(s_tab[(j - 1u) & mask], s_tab[j]), s_tab[(j + 1u) & mask]);   // (no NaN in the table)
-                    const float r = sqrtf(r2[t]);   // correctly rounded (NOT __fsqrt_rn: det_math.h)
-                    const float g = r - sg.margin;
-                    const float g2 = g * g;
-                    hidden[t] = due[t] && view[t] && has[t] && g > 0.0f && near < g2;   // a NaN anywhere: not hidden
-                }
-            }
-        }
+        evidence_visibility<2>(ev, FOV, SIGHT, m[0], m[1], open, due, view, hidden);
         unsigned cn[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {

@@ -276,8 +276,23 @@ struct LocaliseArgs {
 };
 // one wavefront per particle at a time, persistent workgroups; the map staged in LDS where it fits.  q == nullptr: a.map is the
 // prepared map; else S = P + R_w(theta_i, k), Q_k per detection (specification: tests/_localise_detcov_spec.py; q->ndet == a.ndet):
-// nothing can be prepared, a.map is the RAW map (KnownMapArgs::map) and S^-1 is formed per (landmark, detection) pair
-hipError_t launch_localise(hipStream_t stream, const LocaliseArgs& a, const DetCovArgs* q, const EventPair* ev = nullptr);
+// nothing can be prepared, a.map is the RAW map (KnownMapArgs::map) and S^-1 is formed per (landmark, detection) pair.
+// v != nullptr: the MISS form of either (specification: tests/_localise_miss_spec.py) — the same launch also counts, per particle,
+// the landmarks the map predicts in view that no detection matched, under the evidence stage's own predicate; loglik, stats and the
+// table are what the launch without v writes, bit for bit
+struct LocMissArgs {
+    float range2;          // view_range * view_range, one float32 product made on the host
+    int fov;               // 0: the whole circle (lo, hi are not read)
+    float lo, hi;          // as FovArgs
+    const float* table;    // [bins] a sight table (launch_sight_table); nullptr: no line of sight (bins = 0 then)
+    int bins;
+    float margin;          // as SightArgs
+    int32_t* missed;       // [n] seen, matched by no detection, within view_range, in the arc, not hidden
+    int32_t* spared;       // [n] ... in the arc and hidden; may be nullptr
+    int32_t* outside;      // [n] ... outside the arc; may be nullptr
+};
+hipError_t launch_localise(hipStream_t stream, const LocaliseArgs& a, const DetCovArgs* q, const LocMissArgs* v = nullptr,
+                           const EventPair* ev = nullptr);
 // ---- evidence_kernels.hip: landmark existence evidence (specification: tests/_evidence_spec.py).  One byte
 // c in [0, cmax] per (particle, landmark slot) beside the rows; behind the update of a frame a matched landmark gains `hit`, a
 // visible unmatched one loses `miss`, and one that cannot pay is pruned: its slot gets the bits of a slot that was never used.

@@ -198,6 +198,13 @@ struct slam_pf {
     float known_gate = 0.0f, known_log_clutter = 0.0f;
     float* known_prep = nullptr;      // [6][known_Lp] the prepared map, then [5][known_Lp] the map as it was given
     int32_t* known_stats = nullptr;   // [n][3] matched, 0, dropped (the last frame that ran the stage); an allocation of its own
+    // slam_pf_known_map_miss_set (only while a known map is set): the stage of every observing frame is its miss form — behind one
+    // slam_sight_table_dev where line of sight is on — and slam_assoc_weight_dev charges log_miss per landmark it counted as missed
+    bool known_miss_on = false;
+    float known_log_miss = 0.0f;
+    slam_localise_view known_view{};  // view_range, the arc (0, 4: the whole circle), sight != 0 and its margin
+    int known_sight_bins = 0;         // 0: no line of sight
+    int32_t* known_missed = nullptr;  // [3][n] missed, spared, outside (the last frame that ran the miss form); made at the first switch-on
     // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe (RES_OBS) and moves between split and
     // split pages while it runs (between rows and pages when it could not have the split layout's tables)
     int layout_cfg = SLAM_MAP_AUTO;

@@ -201,6 +201,7 @@ int slam_pf_destroy(slam_pf* pf)
     if (pf->assoc_weight_missed) (void)hipFree(pf->assoc_weight_missed);   // (the terms live behind the misses)
     if (pf->known_prep) (void)hipFree(pf->known_prep);                      // (the map as it was given lives behind the prepared one)
     if (pf->known_stats) (void)hipFree(pf->known_stats);
+    if (pf->known_missed) (void)hipFree(pf->known_missed);
     if (pf->known_ll) pf->e->ll_n = -1;
     free_page_tables(pf);
     free_split_tables(pf);
@@ -643,6 +644,7 @@ static int known_map_set(slam_pf* pf, const float* rows, int nlandmarks, float g
         pf->known_ll = false;
         pf->known_on = false;
         pf->known_detcov = false;
+        pf->known_miss_on = false;   // (the misses go off with the map; replacing the map keeps them)
         return SLAM_OK;
     }
     if (pf->L != 0 || pf->comm) {
@@ -720,6 +722,63 @@ int slam_pf_known_map_set(slam_pf* pf, const float* rows, int nlandmarks, float 
 int slam_pf_known_map_detcov_set(slam_pf* pf, const float* rows, int nlandmarks, float gate, float log_clutter)
 {
     return known_map_set(pf, rows, nlandmarks, gate, log_clutter, true);
+}
+
+int slam_pf_known_map_miss_set(slam_pf* pf, float log_miss, float view_range, int fov_on, float angle_min, float angle_max, float edge,
+                               int sight_bins, float margin)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (view_range == 0.0f) {   // off: the session runs exactly what it ran before the first call
+        pf->known_miss_on = false;
+        return SLAM_OK;
+    }
+    if (!pf->known_on) {
+        snprintf(e->err, sizeof e->err, "the misses of localisation are counted against a known map: it needs one set "
+                                        "(slam_pf_known_map_set or slam_pf_known_map_detcov_set)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (!assoc_weight_const_ok(log_miss) || !(view_range > 0.0f && view_range <= FLT_MAX)) {
+        snprintf(e->err, sizeof e->err, "the misses of localisation need a finite log_miss <= 0 and a finite view_range > 0 (0 switches them off)");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    const float pi = 3.14159274f;   // float32 pi
+    const float from = angle_min + edge, to = angle_max - edge;   // (a NaN or an infinity anywhere fails a comparison below)
+    if (fov_on && !(edge >= 0.0f && edge <= FLT_MAX && angle_min >= -pi && angle_max <= pi && from < to)) {   // as slam_pf_prune_fov_set
+        snprintf(e->err, sizeof e->err, "a field of view needs finite angles -pi <= angle_min, angle_max <= pi and a finite edge >= 0 "
+                                        "with angle_min + edge < angle_max - edge");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (sight_bins != 0 && (!sight_bins_ok(sight_bins) || !(margin > 0.0f && margin <= FLT_MAX))) {   // as slam_pf_prune_sight_set
+        snprintf(e->err, sizeof e->err, "line of sight needs bins a power of two in %d .. %d and a finite margin > 0", kSightMinBins, kSightMaxBins);
+        return SLAM_ERR_INVALID_ARG;
+    }
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    if (!pf->known_missed) {   // once, at the switch — never inside a frame: the counts, and the engine's table
+        const size_t bytes = 3 * (size_t)pf->n * sizeof(int32_t);
+        SLAM_HIP_TRY(e, dev_alloc((void**)&pf->known_missed, bytes));
+        SLAM_HIP_TRY(e, hipMemsetAsync(pf->known_missed, 0, bytes, e->stream));
+    }
+    if (sight_bins != 0 && !e->sight_buf.p) SLAM_HIP_TRY(e, e->sight_buf.ensure(sizeof(float) * kSightMaxBins));
+    pf->known_log_miss = log_miss;
+    pf->known_view.view_range = view_range;
+    pf->known_view.lo = fov_on ? slam_fov_bound(from) : 0.0f;
+    pf->known_view.hi = fov_on ? slam_fov_bound(to) : 4.0f;
+    pf->known_view.sight = sight_bins != 0;
+    pf->known_view.margin = sight_bins != 0 ? margin : 0.0f;
+    pf->known_sight_bins = sight_bins;
+    pf->known_miss_on = true;
+    return SLAM_OK;
+}
+
+int slam_pf_known_map_miss_device_view(slam_pf* pf, const int32_t** missed, const int32_t** spared, const int32_t** outside)
+{
+    if (!pf) return SLAM_ERR_INVALID_ARG;
+    if (!pf->known_missed) return SLAM_ERR_NOT_READY;   // slam_pf_known_map_miss_set never switched the misses on
+    if (missed) *missed = pf->known_missed;
+    if (spared) *spared = pf->known_missed + (size_t)pf->n;
+    if (outside) *outside = pf->known_missed + 2 * (size_t)pf->n;
+    return SLAM_OK;
 }
 
 int slam_pf_known_map_device_view(slam_pf* pf, const float** prepared, int32_t* nlandmarks, const int32_t** stats)

@@ -311,6 +311,20 @@ int update_rows(slam_pf* pf, const FrameFacts& f)
     float* dst = f.dst;
     if (f.localise) {   // a known map (no maps of the session's own): the stage on the poses the front launch left, the clutter term, the weights
         // (the map as it was given lies behind the prepared one)
+        if (pf->known_miss_on) {   // the miss form of either stage: behind the table of this frame's scan where line of sight is on
+            if (pf->known_sight_bins)
+                if (int rc = slam_sight_table_dev(e, pf->known_sight_bins)) return rc;
+            int32_t* cnt = pf->known_missed;
+            if (int rc = (pf->known_detcov ? slam_localise_detcov_miss_dev : slam_localise_miss_dev)(
+                    e, pf->known_detcov ? pf->known_prep + 6 * (size_t)pf->known_Lp : pf->known_prep, pf->known_Lp, pf->known_L, dst, dst + sn,
+                    dst + 2 * sn, n, pf->known_gate, nullptr, 0, pf->known_stats, nullptr, &pf->known_view, cnt, cnt + sn, cnt + 2 * sn))
+                return rc;
+            pf->known_ll = true;
+            if (pf->known_log_clutter != 0.0f || pf->known_log_miss != 0.0f)
+                if (int rc = slam_assoc_weight_dev(e, pf->known_stats, cnt, n, 0.0f, pf->known_log_clutter, pf->known_log_miss, nullptr, nullptr))
+                    return rc;
+            return slam_logweight_ekf_dev(e, pf->score, pf->cfg.score_gain, n, pf->logw, nullptr);
+        }
         if (int rc = pf->known_detcov ? slam_localise_detcov_dev(e, pf->known_prep + 6 * (size_t)pf->known_Lp, pf->known_Lp, pf->known_L, dst, dst + sn,
                                                                  dst + 2 * sn, n, pf->known_gate, nullptr, 0, pf->known_stats, nullptr)
                                       : slam_localise_dev(e, pf->known_prep, pf->known_Lp, pf->known_L, dst, dst + sn, dst + 2 * sn, n, pf->known_gate,

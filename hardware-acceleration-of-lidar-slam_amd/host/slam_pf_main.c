@@ -62,6 +62,10 @@
  *                  each particle with the matched pairs' likelihood and adds LOG_CLUTTER (<= 0, default 0) per unmatched
  *                  detection.  With --range-noise every detection is weighed under its own covariance instead of the session's
  *                  meas_var * I (slam_pf_known_map_detcov_set).  One GPU; not with --landmarks or --meas-cov
+ *   --known-miss LOG_MISS VIEW_RANGE [--known-miss-fov EDGE] [--known-miss-sight BINS MARGIN]  only with --known-map
+ *                  (slam_pf_known_map_miss_set): a landmark of the map within VIEW_RANGE metres of a particle's pose that no detection
+ *                  matched costs the particle LOG_MISS (<= 0) — unless it lies outside the lidar's arc (--known-miss-fov: the first
+ *                  to the last beam angle, narrowed by EDGE radians at each end) or behind what the scan hit (--known-miss-sight)
  *   --spread-out FILE  every frame also asks for the spread of the population about its mean (slam_pf_spread, around the same
  *                  predicted heading) and writes one line to FILE: the frame number, the six entries of the covariance over
  *                  (x, y, sin dtheta) — xx, xy, yy, xs, ys, ss — and the length of the mean heading vector, comma-separated, each
@@ -122,6 +126,12 @@ typedef struct {
     const char *known_map;       /* --known-map FILE GATE MAP_VAR [LOG_CLUTTER] */
     float known_gate, known_var, known_log_clutter;
     float *known_rows;           /* [5][known_n]: the file's points, P = MAP_VAR * I */
+    int use_known_miss;          /* --known-miss LOG_MISS VIEW_RANGE: only with --known-map */
+    float known_log_miss, known_view_range;
+    int known_miss_fov;          /* --known-miss-fov EDGE: only with --known-miss */
+    float known_miss_edge;
+    int known_miss_bins;         /* --known-miss-sight BINS MARGIN: only with --known-miss; 0: off */
+    float known_miss_margin;
     int known_n;
     /* the ranks */
     int world, use_rccl, same_device;
@@ -219,6 +229,10 @@ static void *rank_main(void *arg)
     }
     /* --prune-fov: the arc is the scan's own, its first and its last beam angle */
     if (run->use_fov) CHECK(slam_pf_prune_fov_set(pf, 1, scan.angle[0], scan.angle[beams - 1], run->fov_edge));
+    /* --known-miss: the arc, if asked for, likewise */
+    if (run->use_known_miss)
+        CHECK(slam_pf_known_map_miss_set(pf, run->known_log_miss, run->known_view_range, run->known_miss_fov, scan.angle[0], scan.angle[beams - 1],
+                                         run->known_miss_edge, run->known_miss_bins, run->known_miss_margin));
     int32_t nhits = 0;
     double t_step = 0;
     const double t_begin = now_s();
@@ -452,6 +466,27 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(argv[a], "--landmarks-out") && a + 1 < argc) run.landmarks_out = argv[++a];
         else if (!strcmp(argv[a], "--spread-out") && a + 1 < argc) run.spread_out = argv[++a];
+        else if (!strcmp(argv[a], "--known-miss") && a + 2 < argc) {
+            run.use_known_miss = 1;
+            run.known_log_miss = (float)atof(argv[++a]);
+            run.known_view_range = (float)atof(argv[++a]);
+            if (!isfinite(run.known_log_miss) || run.known_log_miss > 0.0f || !isfinite(run.known_view_range) || run.known_view_range <= 0.0f) {
+                fprintf(stderr, "--known-miss: LOG_MISS must be a finite number <= 0 and VIEW_RANGE a finite number > 0\n");
+                return 2;
+            }
+        }
+        else if (!strcmp(argv[a], "--known-miss-fov") && a + 1 < argc) {
+            run.known_miss_fov = 1;
+            run.known_miss_edge = (float)atof(argv[++a]);
+            if (!isfinite(run.known_miss_edge) || run.known_miss_edge < 0.0f) {
+                fprintf(stderr, "--known-miss-fov %s: EDGE must be a finite number of radians >= 0\n", argv[a]);
+                return 2;
+            }
+        }
+        else if (!strcmp(argv[a], "--known-miss-sight") && a + 2 < argc) {
+            run.known_miss_bins = atoi(argv[++a]);
+            run.known_miss_margin = (float)atof(argv[++a]);
+        }
         else if (!strcmp(argv[a], "--known-map") && a + 3 < argc) {
             run.known_map = argv[++a];
             float *v[3] = { &run.known_gate, &run.known_var, &run.known_log_clutter };
@@ -469,7 +504,7 @@ int main(int argc, char **argv)
     }
     const int landmark_options = run.use_assoc || run.use_prune || (run.use_detect && !run.known_map) || run.landmarks_out != NULL;
     if (npos < 5 || (run.known_map && (run.landmarks > 0 || run.world > 1 || run.use_meas_cov)) || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
-        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) || (run.use_assoc_weight && !run.use_assoc) ||
+        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) || (run.use_assoc_weight && !run.use_assoc) || (run.use_known_miss && !run.known_map) || ((run.known_miss_fov || run.known_miss_bins) && !run.use_known_miss) ||
         (run.use_noise && (!run.use_detect || !(run.use_assoc || run.known_map) || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
@@ -493,6 +528,8 @@ int main(int argc, char **argv)
                         "              and segments more spread out than that circle (by more than TOL, default 0) are dropped\n"
                         "  --range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]: only with --detect and --assoc or --known-map, not with --meas-cov; every detection\n"
                         "              carries its own covariance (RANGE_VAR along its beam, BEARING_VAR r^2 + LATERAL_VAR across) and is gated under it\n"
+                        "  --known-miss LOG_MISS VIEW_RANGE [--known-miss-fov EDGE] [--known-miss-sight BINS MARGIN]: only with --known-map; a map\n"
+                        "      landmark within VIEW_RANGE of a pose that no detection matched costs LOG_MISS, unless outside the arc or hidden\n"
                         "  --known-map FILE GATE MAP_VAR [LOG_CLUTTER]: localise in the landmark map of FILE (\"x,y\" lines, as --landmarks-out writes\n"
                         "              them; P = MAP_VAR * I each): every frame associates its detections (--detect) with that one map within GATE and\n"
                         "              weighs with the result, LOG_CLUTTER <= 0 per unmatched detection — with --range-noise under each detection's own\n"

@@ -610,7 +610,7 @@ int slam_assoc_weight_count(slam_engine *e, int64_t *launches);   /* stage launc
  * written.  SLAM_ERR_INVALID_ARG: nlandmarks outside 1 .. SLAM_MAX_OBS, plane_stride or (with d_assoc) assoc_stride < nlandmarks,
  * a gate that is not finite and > 0, n < 0, a null pointer other than d_assoc / d_loglik.  SLAM_ERR_NOT_READY: no detections.
  * Out of scope: one 2x2 noise for all detections as a form of its own (attach the same Q to every detection of
- * slam_localise_detcov_dev), miss terms, any change of the map, K > 64.
+ * slam_localise_detcov_dev), any change of the map, K > 64.
  * UNDER A COVARIANCE PER DETECTION (specification: tests/_localise_detcov_spec.py): slam_localise_detcov_dev (one launch) is
  * slam_localise_dev under S = P + R_w(theta_i, k) of the engine's current detections AND THEIR COVARIANCES
  * (slam_detections_cov_upload_host / _set_dev, slam_detect_scan_noise_dev) — exactly what slam_associate_detcov_dev(create = 0,
@@ -619,7 +619,28 @@ int slam_assoc_weight_count(slam_engine *e, int64_t *launches);   /* stage launc
  * P_xx < 0, and the padding behind nlandmarks, never become candidates.  The caller guarantees P positive semi-definite for every
  * landmark (slam_pf_known_map_detcov_set checks it; every Q_k is positive definite).  d_stats, d_assoc, d_loglik and the refused
  * arguments as for slam_localise_dev; SLAM_ERR_NOT_READY also when the detections carry no covariances.
- * slam_localise_detcov_count: its launches (in no other counter). */
+ * slam_localise_detcov_count: its launches (in no other counter).
+ * THE LANDMARKS IN VIEW THAT NO DETECTION MATCHED (specification: tests/_localise_miss_spec.py): slam_localise_miss_dev and
+ * slam_localise_detcov_miss_dev are the two stages above — d_loglik, d_stats and d_assoc bit for bit — whose ONE launch also
+ * counts, per particle, what the map says the pose should have seen, under the evidence stage's own predicate
+ * (slam_landmark_evidence_fov_dev) with every landmark the frame's matching hit taken as hit: a landmark that is seen, is no
+ * detection's match and lies within view->view_range of the pose is
+ *   outside  its sensor-frame direction lies outside the arc [view->lo, view->hi] of the diamond angle (slam_fov_bound; lo > hi: the
+ *            arc through 4 = 0; 0, 4: the whole circle, nothing is outside);
+ *   spared   in the arc and hidden behind what the scan hit (view->sight != 0: the engine's current sight table,
+ *            slam_sight_table_dev, and view->margin; else nothing is hidden);
+ *   missed   in the arc and not hidden.
+ * d_missed int32 [n]; d_spared and d_outside likewise, each may be NULL.  The log-likelihood does not contain the misses:
+ * slam_assoc_weight_dev(d_stats, d_missed, .., log_miss) adds their term, as in the mapping pipeline.  A pose that is not finite
+ * counts nothing.  SLAM_ERR_INVALID_ARG besides the stage's own: a null view or d_missed, a view_range that is not finite and > 0,
+ * bounds outside [0, 4], with sight a margin that is not finite and > 0.  SLAM_ERR_NOT_READY besides the stage's own: sight and no
+ * sight table made since the current scan.  slam_localise_miss_count: the launches of the two (in no other counter). */
+typedef struct {
+    float view_range;
+    float lo, hi;   /* diamond bounds; 0, 4: the whole circle */
+    int sight;      /* 0: off; else the engine's current sight table is read */
+    float margin;
+} slam_localise_view;
 int slam_known_map_prepare_dev(slam_engine *e, const float *d_map /* [5][plane_stride] */, int plane_stride, int nlandmarks,
                                float meas_var, float *d_prepared /* [6][plane_stride] */);
 int slam_localise_dev(slam_engine *e, const float *d_prepared, int plane_stride, int nlandmarks,
@@ -632,6 +653,17 @@ int slam_localise_detcov_dev(slam_engine *e, const float *d_map /* [5][plane_str
                              uint8_t *d_assoc /* may be NULL */, int assoc_stride, int32_t *d_stats /* [n][3] */,
                              float *d_loglik /* NULL: the engine's buffer, what slam_logweight_ekf_dev consumes */);
 int slam_localise_detcov_count(slam_engine *e, int64_t *launches);  /* stage launches */
+int slam_localise_miss_dev(slam_engine *e, const float *d_prepared, int plane_stride, int nlandmarks,
+                           const float *d_x, const float *d_y, const float *d_th, int n, float gate,
+                           uint8_t *d_assoc /* may be NULL */, int assoc_stride, int32_t *d_stats /* [n][3] */,
+                           float *d_loglik /* NULL: the engine's buffer */, const slam_localise_view *view,
+                           int32_t *d_missed /* [n] */, int32_t *d_spared /* may be NULL */, int32_t *d_outside /* may be NULL */);
+int slam_localise_detcov_miss_dev(slam_engine *e, const float *d_map /* [5][plane_stride] */, int plane_stride, int nlandmarks,
+                                  const float *d_x, const float *d_y, const float *d_th, int n, float gate,
+                                  uint8_t *d_assoc /* may be NULL */, int assoc_stride, int32_t *d_stats /* [n][3] */,
+                                  float *d_loglik /* NULL: the engine's buffer */, const slam_localise_view *view,
+                                  int32_t *d_missed /* [n] */, int32_t *d_spared /* may be NULL */, int32_t *d_outside /* may be NULL */);
+int slam_localise_miss_count(slam_engine *e, int64_t *launches);    /* launches of the two miss forms */
 /* THE DETECTOR: the detections of a frame made on the device from the engine's current scan (slam_scan_upload_host / _set_dev),
  * P = nbeams points in scan order — what fe_clean left, so a removed beam leaves no hole and the rule uses distances only, never
  * beam angles.  With jump2 = jump * jump, guard2, width2 and range2 likewise (each rounded once to float32), and every step below
@@ -1162,8 +1194,8 @@ int slam_pf_detect_noise_set(slam_pf *pf, const slam_detect_params *params /* NU
  * misses (left out when log_clutter == 0), slam_logweight_ekf_dev, scan, resample; a frame with use_observations = 0 is the
  * frame of a session without the mode: plain weights.  slam_pf_detect_set / slam_pf_detect_fit_set are accepted while it is on
  * (the detector's launch goes out in front of the frame's first launch); slam_pf_detect_noise_set with a model is refused: the
- * noise is meas_var * I only (slam_pf_known_map_detcov_set is the form that takes it).  Out of scope: sharded sessions, miss
- * terms, pruning, merging.
+ * noise is meas_var * I only (slam_pf_known_map_detcov_set is the form that takes it).  Out of scope: sharded sessions,
+ * pruning, merging.
  * slam_pf_known_map_detcov_set (the frame loop: tests/_localise_detcov_spec.py frame_loop) is the same switch for the second
  * form of the stage: every observing frame runs slam_localise_detcov_dev on the map as it was given, under the covariances its
  * detections carry; meas_var is not read.  Accepted and refused where slam_pf_known_map_set is, except that the landmarks'
@@ -1183,6 +1215,21 @@ int slam_pf_known_map_set(slam_pf *pf, const float *rows /* host [5][nlandmarks]
 int slam_pf_known_map_detcov_set(slam_pf *pf, const float *rows /* host [5][nlandmarks]; NULL: off */, int nlandmarks,
                                  float gate, float log_clutter);
 int slam_pf_known_map_device_view(slam_pf *pf, const float **prepared, int32_t *nlandmarks, const int32_t **stats);
+/* The landmarks in view that no detection matched, inside the session (the frame loop: tests/_localise_miss_spec.py frame_loop).
+ * Accepted only while a known map of either form is set (else SLAM_ERR_INVALID_ARG); view_range == 0 switches it off; switching
+ * the known map off switches it off too, replacing the map keeps it.  log_miss finite and <= 0 (0 with a view is valid: the counts
+ * are made and nothing is added); view_range finite and > 0; fov_on, angle_min, angle_max, edge as slam_pf_prune_fov_set (fov_on
+ * == 0: the whole circle, the three are not read); sight_bins (0: no line of sight) and margin as slam_pf_prune_sight_set.  A
+ * refused call leaves the session as it was.  With it off a frame runs exactly the launches it ran before the first call.  With
+ * it on an observing frame runs, behind the front launch: slam_sight_table_dev (only with line of sight), slam_localise_miss_dev
+ * or slam_localise_detcov_miss_dev in the place of the stage, slam_assoc_weight_dev(stats, missed, 0, log_clutter, log_miss) (left
+ * out only when both constants are 0), slam_logweight_ekf_dev, scan, resample.  Still one GPU, n_landmarks == 0.
+ * slam_pf_known_map_miss_device_view: missed, spared, outside, int32 [n_particles] each (indexed like slam_pf_view.score), of the
+ * last frame that ran the miss form; any pointer may be NULL.  SLAM_ERR_NOT_READY until the misses were switched on once. */
+int slam_pf_known_map_miss_set(slam_pf *pf, float log_miss, float view_range,
+                               int fov_on, float angle_min, float angle_max, float edge,   /* as slam_pf_prune_fov_set */
+                               int sight_bins /* 0: off */, float margin);                 /* as slam_pf_prune_sight_set */
+int slam_pf_known_map_miss_device_view(slam_pf *pf, const int32_t **missed, const int32_t **spared, const int32_t **outside);
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
  * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
