@@ -21,7 +21,7 @@ import _assoc_aniso_spec as AA
 import _assoc_detcov_spec as AD
 import _assoc_spec as A
 import _f64_pf as F
-from test_aniso_spec_cpu import bounds, q_matrix, world_noise64
+from _aniso_bounds import check_pairs, q_matrix
 
 U, SC = F.U, F.SINCOS_ABS
 NONE = AD.NONE
@@ -179,31 +179,4 @@ def test_update_within_its_bounds_of_the_float64_ekf(orc, q):
     out, ll = AD.update(rows, x, y, th, None, assoc, dx, dy, covs)
     untouched = np.setdiff1d(np.arange(L), perm)
     assert np.array_equal(bits(out[:, :, untouched]), bits(rows[:, :, untouched]))
-    worst = dict(mean=0.0, cov=0.0, first=0.0)
-    ll64, b_sum, a_max = np.zeros(N), np.zeros(N), 1.0
-    for k in range(K):
-        l = perm[k]
-        p, g = rows[:, :, l].T.astype(np.float64), out[:, :, l].T.astype(np.float64)
-        first = p[2] < 0
-        seen = ~first
-        pp = np.where(seen, p, np.array([0, 0, 1, 0, 1], np.float64)[:, None])
-        ref, b = bounds(pp, (x, y, th), dx[k], dy[k], cov[k])
-        worst["mean"] = max(worst["mean"], float(np.where(seen, np.hypot(g[0] - ref[0], g[1] - ref[1]) / b["mean"], 0.0).max()))
-        e_cov = np.maximum(np.maximum(np.abs(g[2] - ref[2]), np.abs(g[3] - ref[3])), np.abs(g[4] - ref[4]))
-        worst["cov"] = max(worst["cov"], float(np.where(seen, e_cov / b["cov"], 0.0).max()))
-        assert np.all(((g[2] > 0) & (g[4] > 0) & (g[2] * g[4] - g[3] * g[3] > 0))[seen]), f"k={k}: posteriors not positive definite"
-        fx, fy = F.first_sighting(dx[k], dy[k], x, y, th)
-        b_first = 4 * U * (np.hypot(x, y) + np.hypot(fx, fy)) + 4 * (SC + U) * np.hypot(dx[k], dy[k])
-        rw = world_noise64(cov[k], th)
-        e_first = np.maximum(np.maximum(np.abs(g[2] - rw[0]), np.abs(g[3] - rw[1])), np.abs(g[4] - rw[2]))
-        r_first = np.maximum(np.hypot(g[0] - fx, g[1] - fy) / b_first, e_first / b["e_r"])
-        worst["first"] = max(worst["first"], float(np.where(first, r_first, 0.0).max()))
-        t = np.where(seen, ref[5], 0.0)
-        ll64 += t
-        b_sum += np.where(seen, b["ll"], 0.0) + (-(-L // 128) + 7) * U * np.abs(t)
-        a_max = max(a_max, float(np.where(seen, b["a_p"], 1.0).max()))
-    worst["loglik"] = float((np.abs(ll.astype(np.float64) - ll64) / (b_sum + 1e-30)).max())
-    print(f"lambda_max(Q)={q:g}: max error / bound  mean {worst['mean']:.3g}  cov {worst['cov']:.3g}  first {worst['first']:.3g}  "
-          f"loglik {worst['loglik']:.3g}; largest a_P {a_max:.4g}")
-    for name, v in worst.items():
-        assert v <= 1.0, f"{name} error {v:.3g} x its bound"
+    check_pairs(rows, out, ll, (x, y, th), perm, dx, dy, cov, f"lambda_max(Q)={q:g}")

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import _assoc_spec as A
+from _detections import detections   # noqa: F401 - other tests import it from here
 from __graft_entry__ import load_package
 from conftest import bits
 from test_gpu_aniso import make_case
@@ -34,16 +35,6 @@ def eng(orc):
     yield e
     torch.cuda.synchronize()
     e.close()
-
-
-def detections(zx, zy, K, seed):
-    """K detections: observations of landmarks of the case in shuffled order (their identity is what the kernel has to find), and
-    once those run out points that belong to nothing."""
-    rng = np.random.default_rng(seed)
-    pick = rng.permutation(len(zx))[:K]
-    dx = np.concatenate([zx[pick], rng.uniform(-20, 20, K - len(pick)).astype(np.float32)])
-    dy = np.concatenate([zy[pick], rng.uniform(-20, 20, K - len(pick)).astype(np.float32)])
-    return dx.astype(np.float32), dy.astype(np.float32)
 
 
 def check(eng, poses, rows, L, dx, dy, anc=None, stride=None, gate=GATE, new_gate=NEW_GATE, create=1, label=""):

@@ -11,6 +11,7 @@ import _aniso_spec as S
 import _assoc_aniso_spec as AA
 import _assoc_detcov_spec as AD
 import oracle
+from _detections import covariances
 from __graft_entry__ import load_package
 from conftest import bits
 from test_aniso_spec_cpu import q_matrix
@@ -22,15 +23,6 @@ LS = (1, 31, 127, 128, 129, 257)     # one lane pair; the 128-landmark pass seam
 KS = (0, 1, 63, 64)
 NS = (1, 5, 259)                     # no multiples of the waves per workgroup
 FORMS = ("gather", "identity", "inplace")
-
-
-def covariances(K, seed, qm=0.04):
-    """Every Q_k different: the large eigenvalue within a decade of qm, a : b from 1 : 1 to 1 : 1e4, the axes turned per detection."""
-    rng = np.random.default_rng(seed)
-    q = [q_matrix(qm * 10.0 ** rng.uniform(-1, 0), 10.0 ** rng.uniform(0, 4), rng.uniform(0, np.pi)) for _ in range(K)]
-    q = np.array(q, np.float32).reshape(K, 3)
-    assert AD.valid_covs(q.T)
-    return q[:, 0].copy(), q[:, 1].copy(), q[:, 2].copy()
 
 
 def check(eng, poses, rows, L, dx, dy, covs, anc=None, stride=None, gate=GATE, new_gate=NEW_GATE, create=1, label=""):

@@ -6,6 +6,7 @@ import pytest
 
 import _assoc_spec as A
 import _localise_spec as S
+from _localise_bounds import textbook, within
 
 F = np.float32
 Q, GATE = 0.02, 9.21
@@ -30,24 +31,12 @@ def case(orc):
     return x, y, th, zx[::-1].copy(), zy[::-1].copy()   # (detection 0 belongs to landmark 2, detection 1 to landmark 0)
 
 
-def textbook(x, y, th, zx, zy, pairs):
-    """sum over (l, k) of -1/2 d^T S^-1 d - 1/2 log det S - log 2 pi in float64."""
-    c, s = np.cos(float(th)), np.sin(float(th))
-    ll = 0.0
-    for l, k in pairs:
-        w = np.array([float(x) + c * float(zx[k]) + s * float(zy[k]), float(y) + c * float(zy[k]) - s * float(zx[k])])
-        Sm = np.array([[M[2, l], M[3, l]], [M[3, l], M[4, l]]], np.float64) + float(F(Q)) * np.eye(2)
-        d = w - M[:2, l].astype(np.float64)
-        ll += -0.5 * d @ np.linalg.solve(Sm, d) - 0.5 * np.log(np.linalg.det(Sm)) - np.log(2 * np.pi)
-    return ll
-
-
 def test_loglik_is_the_textbook_likelihood(case):
     x, y, th, zx, zy = case
     assoc, stats, ll = S.localise(M, x, y, th, zx, zy, Q, GATE, 0.0)
     assert assoc[0].tolist() == [1, A.NONE, 0] and stats[0].tolist() == [2, 0, 0]
-    want = textbook(x[0], y[0], th[0], zx, zy, [(0, 1), (2, 0)])
-    assert abs(float(ll[0]) - want) <= 1e-5 * abs(want), (ll[0], want)
+    want = textbook(M, Q, x[0], y[0], th[0], zx, zy, [(0, 1), (2, 0)])
+    assert within(ll[0], want), (ll[0], want)
     assert assoc[1].tolist() == [A.NONE] * 3 and stats[1].tolist() == [0, 0, 2]
 
 

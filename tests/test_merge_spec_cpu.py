@@ -19,6 +19,7 @@ import pytest
 
 import _merge_cases as MC
 import _merge_spec as M
+from _merge_bounds import fusion_check
 
 F = np.float32
 U = 2.0 ** -24
@@ -218,27 +219,4 @@ def test_fusion_within_its_bounds_of_the_float64_product():
     ml, pl, mw, pw = regimes(n, 11)
     with np.errstate(all="ignore"):
         o = np.array(M.fuse((ml[0], ml[1], pl[0], pl[1], pl[2]), (mw[0], mw[1], pw[0], pw[1], pw[2])), np.float64)
-    mat = lambda p: np.stack([np.stack([p[0], p[1]], -1), np.stack([p[1], p[2]], -1)], -2).astype(np.float64)
-    Pl, Pw = mat(pl), mat(pw)
-    use = (np.linalg.det(Pl) > 0) & (np.linalg.det(Pw) > 0)           # (a rounded input may have lost its definiteness)
-    assert use.mean() > 0.9
-    Pl, Pw, o = Pl[use], Pw[use], o[:, use]
-    mul, muw = ml.astype(np.float64).T[use], mw.astype(np.float64).T[use]
-    info = np.linalg.inv(Pw) + np.linalg.inv(Pl)
-    P64 = np.linalg.inv(info)
-    mu64 = np.einsum("nij,nj->ni", P64, np.einsum("nij,nj->ni", np.linalg.inv(Pw), muw) + np.einsum("nij,nj->ni", np.linalg.inv(Pl), mul))
-    S = Pl + Pw
-    ev_s = np.linalg.eigvalsh(S)
-    lmin, kappa = ev_s[:, 0], ev_s[:, 1] / ev_s[:, 0]
-    lmax = lambda m: np.linalg.eigvalsh(m)[:, 1]
-    d = np.linalg.norm(mul - muw, axis=1)
-    a = np.maximum(1.0, np.linalg.norm(Pl @ np.linalg.inv(S), 2, axis=(1, 2)))
-    b_mean = a * U * d + 2 * U * (np.linalg.norm(mul, axis=1) + d) + U * (6 * kappa + 18) * lmax(Pl) * d / lmin
-    quad = lambda p: p[:, 0, 0] * p[:, 1, 1] + p[:, 0, 1] ** 2
-    b_cov = 4 * U * ((kappa + 2) * lmax(P64) + (lmax(Pl) * quad(Pw) + lmax(Pw) * quad(Pl)) / np.linalg.det(S))
-    e_mean = np.linalg.norm(o[:2].T - mu64, axis=1)
-    e_cov = np.max(np.abs(np.stack([o[2] - P64[:, 0, 0], o[3] - P64[:, 0, 1], o[4] - P64[:, 1, 1]])), axis=0)
-    print(f"fusion vs float64 information form over {use.sum()} pairs: max error / bound  mean {np.max(e_mean / b_mean):.3g}  "
-          f"cov {np.max(e_cov / b_cov):.3g}; kappa(S) up to {kappa.max():.3g}")
-    assert np.all(e_mean <= b_mean), f"mean: {np.max(e_mean / b_mean):.3g} x its bound"
-    assert np.all(e_cov <= b_cov), f"covariance: {np.max(e_cov / b_cov):.3g} x its bound"
+    fusion_check(o, ml, pl, mw, pw)
