@@ -158,6 +158,8 @@ SIGNATURES = {
     "slam_localise_miss_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "slam_localise_detcov_miss_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "slam_localise_miss_count": (_i, [_vp, _vp]),
+    "slam_pose_reseed_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _u64, _u32, _f, _vp, _vp]),
+    "slam_pose_reseed_count": (_i, [_vp, _vp]),
     "slam_detect_params_default": (None, [_vp]),
     "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
     "slam_detect_count": (_i, [_vp, _vp]),
@@ -226,6 +228,7 @@ SIGNATURES = {
     "slam_pf_known_map_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_known_map_miss_set": (_i, [_vp, _f, _f, _i, _f, _f, _f, _i, _f]),
     "slam_pf_known_map_miss_device_view": (_i, [_vp, _vp, _vp, _vp]),
+    "slam_pf_known_map_reseed": (_i, [_vp, _f, _vp]),
     "slam_pf_detect_set": (_i, [_vp, _vp]),
     "slam_pf_detect_fit_set": (_i, [_vp, _vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
@@ -565,6 +568,23 @@ class Engine:
         """-> launches of the two miss forms of the localise stage of this engine so far."""
         c = C.c_int64(0)
         self._ck(self.lib.slam_localise_miss_count(self.h, C.byref(c)), "localise_miss_count")
+        return int(c.value)
+
+    def pose_reseed_dev(self, d_map, plane_stride, nlandmarks, d_x_in, d_y_in, d_th_in, d_anc, d_x_out, d_y_out, d_th_out, n, first_id,
+                        seed, frame, fraction, d_flag=None):
+        """``slam_pose_reseed_dev``: a chosen fraction of n slots becomes pose proposals at which one of the engine's current
+        detections coincides with one landmark of d_map (float32 [5][plane_stride], as it was given); the rest copy the pose of
+        d_anc[i] (None: i, and out may be in).  d_flag uint8 [n] or None.  -> (replaced, chosen but not replaced).  Synchronises."""
+        c = (C.c_int32 * 2)()
+        self._ck(self.lib.slam_pose_reseed_dev(self.h, _ptr(d_map), plane_stride, nlandmarks, _ptr(d_x_in), _ptr(d_y_in), _ptr(d_th_in),
+                                               _ptr(d_anc), _ptr(d_x_out), _ptr(d_y_out), _ptr(d_th_out), n, first_id, seed, frame,
+                                               float(fraction), _ptr(d_flag), c), "pose_reseed_dev")
+        return int(c[0]), int(c[1])
+
+    def pose_reseed_count(self):
+        """-> launches of ``pose_reseed_dev`` (the session's reseeds included) of this engine so far."""
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_pose_reseed_count(self.h, C.byref(c)), "pose_reseed_count")
         return int(c.value)
 
     def assoc_counts(self):
@@ -1390,6 +1410,14 @@ class PfSession:
         m, s, o = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self.e._ck(self.e.lib.slam_pf_known_map_miss_device_view(self.h, C.byref(m), C.byref(s), C.byref(o)), "pf_known_map_miss_device_view")
         return {k: DeviceArray(v.value, (self.n,), "<i4", self) for k, v in (("missed", m), ("spared", s), ("outside", o))}
+
+    def known_map_reseed(self, fraction: float):
+        """``slam_pf_known_map_reseed`` (between frames, while a known map is set): the pending resample and pose proposals from
+        the engine's current detections for `fraction` of the slots, in one launch.  -> (replaced, chosen but not replaced).
+        ``best`` is refused until the next ``step``; two calls with no step between them draw the same slots."""
+        c = (C.c_int32 * 2)()
+        self.e._ck(self.e.lib.slam_pf_known_map_reseed(self.h, float(fraction), c), "pf_known_map_reseed")
+        return int(c[0]), int(c[1])
 
     def assoc_view(self):
         """``slam_pf_assoc_device_view``: the last frame's table uint8 [n][stride] and stats int32 [n][3], indexed like score."""

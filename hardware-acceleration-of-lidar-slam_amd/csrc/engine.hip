@@ -188,6 +188,7 @@ int slam_engine_destroy(slam_engine* e)
     e->gate_buf.release();
     e->carry_buf.release();
     e->spread_buf.release();
+    e->reseed_buf.release();
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     delete e;
     return SLAM_OK;

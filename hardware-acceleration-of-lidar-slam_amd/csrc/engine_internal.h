@@ -109,6 +109,8 @@ struct slam_engine {
     int64_t localise_launches[2] = { 0, 0 };   // slam_localise_counts: prepare launches, stage launches (in no other counter)
     int64_t localise_detcov_launches = 0;      // slam_localise_detcov_count: stage launches under per-detection Q (in no other counter)
     int64_t localise_miss_launches = 0;        // slam_localise_miss_count: launches of the miss form, either noise (in no other counter)
+    int64_t reseed_launches = 0;               // slam_pose_reseed_count: launches of slam_pose_reseed_dev (in no other counter)
+    DevBuf reseed_buf;                         // its two accumulators and ticket (kept zeroed), then the two counts
     // the detector (slam_detect_scan_dev): its kernel writes det_buf and leaves {ndet, sequence} in mapped host memory; until the
     // next stage that needs the count on the host has picked it up (slam_engine_resolve_detections) it is PENDING
     int32_t* h_det = nullptr;
@@ -395,6 +397,22 @@ __attribute__((visibility("hidden"))) int slam_engine_evidence(slam_engine* e, f
                                                                uint8_t* d_ev_out, int ev_stride, int hit, int miss, int cmax,
                                                                float view_range, int32_t* d_stats, int32_t* d_missed,
                                                                const slam_evidence_form& form);
+
+// engine_reseed.hip: slam_pose_reseed_dev with its checks and status codes, and a choice of how the two counts come back.
+// mapped == nullptr: by a copy behind a stream synchronisation, into counts.  Else the launch leaves them in mapped host memory
+// behind a sequence number (the session waits for that word and reads them there; counts is not written) and nothing synchronises.
+// *launched = false: K == 0, nothing was issued and nothing will arrive
+struct slam_reseed_mapped {
+    int32_t* d_hout;    // the two words as the device sees them
+    uint32_t* d_hseq;
+    uint32_t seq;
+};
+__attribute__((visibility("hidden"))) int slam_engine_pose_reseed(slam_engine* e, const float* d_map, int plane_stride, int nlandmarks,
+                                                                  const float* d_x_in, const float* d_y_in, const float* d_th_in,
+                                                                  const int32_t* d_anc, float* d_x_out, float* d_y_out, float* d_th_out,
+                                                                  int n, int64_t first_id, uint64_t seed, uint32_t frame, float fraction,
+                                                                  uint8_t* d_flag, const slam_reseed_mapped* mapped, int32_t counts[2],
+                                                                  bool* launched);
 
 // engine_match.hip
 namespace slam_detail {

@@ -29,6 +29,7 @@ enum ResWord {
     RES_VOTES_PAGES = 27, RES_VOTES_ROWS = 28,
     RES_PAGE_HINT = 30,   // pages the last frames touched per pass (page_list_kernel)
     RES_MOMENTS = 32,     // 32..71: kPoseMoments x 8 bytes, what slam_pf_spread asks for (behind RES_SEQ as well)
+    RES_RESEED = 72,      // 72..73 {replaced, chosen but not replaced} of slam_pf_known_map_reseed (behind RES_SEQ as well)
 };
 
 struct slam_pf {
@@ -205,6 +206,9 @@ struct slam_pf {
     slam_localise_view known_view{};  // view_range, the arc (0, 4: the whole circle), sight != 0 and its margin
     int known_sight_bins = 0;         // 0: no line of sight
     int32_t* known_missed = nullptr;  // [3][n] missed, spared, outside (the last frame that ran the miss form); made at the first switch-on
+    // slam_pf_known_map_reseed: from a successful reseed until the next step the last frame's log-weights belong to no pose
+    // (slam_pf_best is refused)
+    bool reseeded = false;
     // SLAM_MAP_AUTO: the session watches how many landmarks the frames observe (RES_OBS) and moves between split and
     // split pages while it runs (between rows and pages when it could not have the split layout's tables)
     int layout_cfg = SLAM_MAP_AUTO;

@@ -791,6 +791,57 @@ int slam_pf_known_map_device_view(slam_pf* pf, const float** prepared, int32_t* 
     return SLAM_OK;
 }
 
+// The pending resample and the proposals in ONE launch: pose[cur] through anc[cur] -> the other pose buffer, which becomes the
+// current one.  The counts come back through the mapped result block; nothing else is waited for.
+int slam_pf_known_map_reseed(slam_pf* pf, float fraction, int32_t counts[2])
+{
+    if (!pf || !counts) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    if (pf->comm || pf->L > 0 || !pf->known_on) {
+        snprintf(e->err, sizeof e->err, "reseeding draws its proposals from a known map: %s",
+                 pf->comm ? "a sharded session cannot have one" : pf->L > 0 ? "a session with n_landmarks > 0 cannot have one"
+                                                                           : "the mode is off (slam_pf_known_map_set or slam_pf_known_map_detcov_set)");
+        return SLAM_ERR_NOT_READY;
+    }
+    if (!(fraction > 0.0f && fraction <= 1.0f)) {   // (NaN fails every comparison)
+        snprintf(e->err, sizeof e->err, "reseed: the fraction must lie in (0, 1]");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    if (int rc = slam_engine_resolve_detections(e)) return rc;
+    if (e->ndet < 0) {
+        snprintf(e->err, sizeof e->err, "reseed: no detections were handed over");
+        return SLAM_ERR_NOT_READY;
+    }
+    counts[0] = counts[1] = 0;
+    if (e->ndet == 0) return SLAM_OK;   // nothing to propose from: the session is as it was
+    if (pf->gated && pf->has_anc) {     // the verdict of the last frame, before the gate forgets it below
+        int resampled = 1;
+        if (int rc = slam_resample_happened_host(e, &resampled)) return rc;
+        pf->frames_resampled += resampled ? 1 : 0;
+    }
+    const size_t sn = (size_t)pf->n;
+    const float* src = pf->pose[pf->cur];
+    float* dst = pf->pose[1 - pf->cur];
+    const uint32_t seq = ++pf->res_seq;
+    const slam_reseed_mapped mapped{ dev_word(pf, RES_RESEED), reinterpret_cast<uint32_t*>(dev_word(pf, RES_SEQ)), seq };
+    bool launched = false;
+    if (int rc = slam_engine_pose_reseed(e, pf->known_prep + 6 * (size_t)pf->known_Lp, pf->known_Lp, pf->known_L, src, src + sn, src + 2 * sn,
+                                         pf->has_anc ? pf->anc[pf->cur] : nullptr, dst, dst + sn, dst + 2 * sn, pf->n, 0, pf->cfg.seed,
+                                         pf->frame, fraction, nullptr, &mapped, nullptr, &launched))
+        return rc;
+    pf->cur = 1 - pf->cur;
+    pf->has_anc = false;
+    pf->reseeded = true;
+    if (pf->gated)   // no weight is carried into the next frame
+        if (int rc = slam_resample_gate_set(e, pf->cfg.resample_ess_frac)) return rc;
+    const volatile uint32_t* h_seq = reinterpret_cast<const volatile uint32_t*>(host_word(pf, RES_SEQ));
+    if (int rc = slam_engine_wait_flag(e, nullptr, h_seq, seq, "reseed flag")) return rc;
+    counts[0] = host_word(pf, RES_RESEED)[0];
+    counts[1] = host_word(pf, RES_RESEED)[1];
+    return SLAM_OK;
+}
+
 int slam_pf_rows_received(const slam_pf* pf) { return pf ? pf->rows_received : 0; }
 int64_t slam_pf_frames_resampled(const slam_pf* pf) { return pf ? pf->frames_resampled : 0; }
 int64_t slam_pf_layout_changes(const slam_pf* pf) { return pf ? pf->conversions : 0; }

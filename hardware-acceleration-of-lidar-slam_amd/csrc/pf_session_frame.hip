@@ -627,6 +627,7 @@ int pf_step_impl(slam_pf* pf, int slot, const float dp[3], int use_observations,
     pf->cur = 1 - pf->cur;
     pf->has_anc = true;
     pf->last_ekf = f.ekf || f.localise;
+    pf->reseeded = false;   // (slam_pf_known_map_reseed: the log-weights are this frame's again)
     pf->frame++;
     return SLAM_OK;
 }

@@ -70,6 +70,11 @@ int pf_best(slam_pf* pf, float pose[3], float* logw, int32_t* index)
     if (!pf || !pose) return SLAM_ERR_INVALID_ARG;
     slam_engine* e = pf->e;
     SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    if (pf->reseeded) {   // pose[cur] is the reseeded population: the last frame's log-weights belong to none of it
+        snprintf(e->err, sizeof e->err, "the population was reseeded (slam_pf_known_map_reseed): the last frame's log-weights no longer "
+                                        "belong to the poses; the heaviest particle is known again after the next slam_pf_step");
+        return SLAM_ERR_NOT_READY;
+    }
     // the log-weights of the last frame belong to pose[cur] BEFORE the pending gather
     const float* p = pf->pose[pf->cur];
     const size_t sn = (size_t)pf->n;

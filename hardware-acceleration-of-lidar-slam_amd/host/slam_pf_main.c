@@ -23,7 +23,8 @@
  *                     [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]]
  *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
  *                     [--landmarks-out FILE]]
- *                     [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
+ *                     [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]
+ *                      [--known-reseed FRACTION [EVERY]]]
  *                     [--spread-out FILE]
  *   particles      the whole population (a multiple of N)
  *   --ess F        ESS-gated resampling: resample only in frames whose effective sample size is below F * N
@@ -66,6 +67,10 @@
  *                  (slam_pf_known_map_miss_set): a landmark of the map within VIEW_RANGE metres of a particle's pose that no detection
  *                  matched costs the particle LOG_MISS (<= 0) — unless it lies outside the lidar's arc (--known-miss-fov: the first
  *                  to the last beam angle, narrowed by EDGE radians at each end) or behind what the scan hit (--known-miss-sight)
+ *   --known-reseed FRACTION [EVERY]  only with --known-map: behind every EVERY-th observing frame (default 1), once the frame's
+ *                  outputs are read, FRACTION (in (0, 1]) of the particles is replaced by pose proposals at which one of the
+ *                  frame's detections coincides with one landmark of the map (slam_pf_known_map_reseed) — what brings back a cloud
+ *                  that settled on a wrong pose; the frame's line then ends in "  reseed = REPLACED NOT_REPLACED"
  *   --spread-out FILE  every frame also asks for the spread of the population about its mean (slam_pf_spread, around the same
  *                  predicted heading) and writes one line to FILE: the frame number, the six entries of the covariance over
  *                  (x, y, sin dtheta) — xx, xy, yy, xs, ys, ss — and the length of the mean heading vector, comma-separated, each
@@ -133,6 +138,9 @@ typedef struct {
     int known_miss_bins;         /* --known-miss-sight BINS MARGIN: only with --known-miss; 0: off */
     float known_miss_margin;
     int known_n;
+    int use_known_reseed;        /* --known-reseed FRACTION [EVERY]: only with --known-map */
+    float known_reseed_fraction;
+    int known_reseed_every;
     /* the ranks */
     int world, use_rccl, same_device;
     uint8_t comm_id[SLAM_COMM_ID_BYTES];
@@ -247,6 +255,7 @@ static void *rank_main(void *arg)
     memcpy(map.pose, pose, sizeof pose);
     CHECK(slam_pf_reset(pf, pose));
     int mini_updated = 1;
+    int observing_frames = 0;   /* --known-reseed: every EVERY-th of them is followed by a reseed */
 
     for (int k = 1; k < frames; ++k) {
         if (rank == 0) printf("scan %d\n", k + 1);
@@ -310,7 +319,12 @@ static void *rank_main(void *arg)
         } else {
             mini_updated = 0;
         }
-        if (rank == 0) printf("pose = %f  %f  %f\n", pose[0], pose[1], pose[2]);
+        if (run->use_known_reseed && observe) {   /* the frame's outputs are read: now the proposals for the next one */
+            int32_t reseed[2] = { 0, 0 };
+            const int due = ++observing_frames % run->known_reseed_every == 0;
+            if (due) CHECK(slam_pf_known_map_reseed(pf, run->known_reseed_fraction, reseed));
+            if (rank == 0) printf("pose = %f  %f  %f  reseed = %d %d\n", pose[0], pose[1], pose[2], (int)reseed[0], (int)reseed[1]);
+        } else if (rank == 0) printf("pose = %f  %f  %f\n", pose[0], pose[1], pose[2]);
     }
     if (rank == 0) {
         const double wall = now_s() - t_begin;
@@ -487,6 +501,16 @@ int main(int argc, char **argv)
             run.known_miss_bins = atoi(argv[++a]);
             run.known_miss_margin = (float)atof(argv[++a]);
         }
+        else if (!strcmp(argv[a], "--known-reseed") && a + 1 < argc) {
+            run.use_known_reseed = 1;
+            run.known_reseed_fraction = (float)atof(argv[++a]);
+            run.known_reseed_every = 1;
+            if (a + 1 < argc && strchr("0123456789+", argv[a + 1][0])) run.known_reseed_every = atoi(argv[++a]);
+            if (!(run.known_reseed_fraction > 0.0f && run.known_reseed_fraction <= 1.0f) || run.known_reseed_every < 1) {
+                fprintf(stderr, "--known-reseed: FRACTION must lie in (0, 1] and EVERY must be a whole number >= 1\n");
+                return 2;
+            }
+        }
         else if (!strcmp(argv[a], "--known-map") && a + 3 < argc) {
             run.known_map = argv[++a];
             float *v[3] = { &run.known_gate, &run.known_var, &run.known_log_clutter };
@@ -504,7 +528,7 @@ int main(int argc, char **argv)
     }
     const int landmark_options = run.use_assoc || run.use_prune || (run.use_detect && !run.known_map) || run.landmarks_out != NULL;
     if (npos < 5 || (run.known_map && (run.landmarks > 0 || run.world > 1 || run.use_meas_cov)) || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
-        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) || (run.use_assoc_weight && !run.use_assoc) || (run.use_known_miss && !run.known_map) || ((run.known_miss_fov || run.known_miss_bins) && !run.use_known_miss) ||
+        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) || (run.use_assoc_weight && !run.use_assoc) || (run.use_known_miss && !run.known_map) || (run.use_known_reseed && !run.known_map) || ((run.known_miss_fov || run.known_miss_bins) && !run.use_known_miss) ||
         (run.use_noise && (!run.use_detect || !(run.use_assoc || run.known_map) || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
@@ -530,6 +554,8 @@ int main(int argc, char **argv)
                         "              carries its own covariance (RANGE_VAR along its beam, BEARING_VAR r^2 + LATERAL_VAR across) and is gated under it\n"
                         "  --known-miss LOG_MISS VIEW_RANGE [--known-miss-fov EDGE] [--known-miss-sight BINS MARGIN]: only with --known-map; a map\n"
                         "      landmark within VIEW_RANGE of a pose that no detection matched costs LOG_MISS, unless outside the arc or hidden\n"
+                        "  --known-reseed FRACTION [EVERY]: only with --known-map; behind every EVERY-th observing frame FRACTION of the particles\n"
+                        "              becomes pose proposals from the frame's detections and the map (slam_pf_known_map_reseed)\n"
                         "  --known-map FILE GATE MAP_VAR [LOG_CLUTTER]: localise in the landmark map of FILE (\"x,y\" lines, as --landmarks-out writes\n"
                         "              them; P = MAP_VAR * I each): every frame associates its detections (--detect) with that one map within GATE and\n"
                         "              weighs with the result, LOG_CLUTTER <= 0 per unmatched detection — with --range-noise under each detection's own\n"

@@ -664,6 +664,33 @@ int slam_localise_detcov_miss_dev(slam_engine *e, const float *d_map /* [5][plan
                                   float *d_loglik /* NULL: the engine's buffer */, const slam_localise_view *view,
                                   int32_t *d_missed /* [n] */, int32_t *d_spared /* may be NULL */, int32_t *d_outside /* may be NULL */);
 int slam_localise_miss_count(slam_engine *e, int64_t *launches);    /* launches of the two miss forms */
+/* RESEEDING THE CLOUD FROM WHAT THE LIDAR SEES (specification: tests/_reseed_spec.py reseed): sensor-resetting
+ * localisation.  If detection k is landmark j, the robot stands on a circle of radius |z_k| around landmark j and its heading is
+ * fixed by where on the circle it stands; drawing j, k and the heading gives a one-dimensional family per (j, k) instead of the
+ * volume a cloud scattered over x, y and theta has to fill.  slam_pose_reseed_dev (one launch, no pose passes through the host)
+ * replaces a chosen fraction of n slots by such proposals over the engine's current detections (uploaded, set or made by the
+ * detector; K of them) and a known map as it was given, d_map float32 [5][plane_stride], P_xx < 0: the slot holds no landmark.
+ * Slot i, gid = first_id + i:
+ *     r = philox4x32_10(lo(gid), hi(gid), frame, 2, key = lo(seed), hi(seed))     (stream 2; 0 and 1 are motion and resample)
+ *     chosen iff (uint64)r[0] < thr,   thr = floor((double)fraction * 2^32) held in 64 bits (fraction == 1: 2^32, every slot)
+ *     j = umulhi(r[1], nlandmarks),  k = umulhi(r[2], K),  theta = 6.2831853072f * ((float)(r[3] >> 8) * 2^-24)
+ *     (s, c) = the specified sine and cosine of theta; then, every product and sum one binary32 rounding in this order — the
+ *     update's w = p + H^T z read backwards:
+ *         t = c * zx_k;  v = s * zy_k;  t = t + v;  x' = mx_j - t;
+ *         t = c * zy_k;  v = s * zx_k;  t = t - v;  y' = my_j - t;     th' = theta
+ * A chosen slot whose slot j holds no landmark is not replaced.  A slot that is not replaced copies (x, y, th)[d_anc[i]] (d_anc
+ * NULL: i) — the pending resample rides along.  No jitter is added: the next frame's motion sample spreads the proposals.
+ * d_flag (may be NULL) uint8 [n]: 1 replaced, 2 chosen but not replaced, 0 otherwise; counts = {replaced, chosen but not replaced},
+ * exact; the call synchronises to return them.  In place (every out array is its in array) is allowed exactly when d_anc is NULL;
+ * any other overlap of an in and an out array is SLAM_ERR_INVALID_ARG, as are n <= 0, nlandmarks <= 0, plane_stride < nlandmarks,
+ * a fraction that is not in (0, 1] (or not a number) and a null pointer other than d_anc / d_flag.  SLAM_ERR_NOT_READY: no
+ * detections were handed over.  K == 0: SLAM_OK, nothing is written, counts 0.  slam_pose_reseed_count: its launches (in no other
+ * counter).  Out of scope: proposals from detection pairs; deciding when to reseed. */
+int slam_pose_reseed_dev(slam_engine *e, const float *d_map /* [5][plane_stride] */, int plane_stride, int nlandmarks,
+                         const float *d_x_in, const float *d_y_in, const float *d_th_in, const int32_t *d_anc /* NULL: identity */,
+                         float *d_x_out, float *d_y_out, float *d_th_out, int n, int64_t first_id, uint64_t seed, uint32_t frame,
+                         float fraction, uint8_t *d_flag /* may be NULL */, int32_t counts[2]);
+int slam_pose_reseed_count(slam_engine *e, int64_t *launches);
 /* THE DETECTOR: the detections of a frame made on the device from the engine's current scan (slam_scan_upload_host / _set_dev),
  * P = nbeams points in scan order — what fe_clean left, so a removed beam leaves no hole and the rule uses distances only, never
  * beam angles.  With jump2 = jump * jump, guard2, width2 and range2 likewise (each rounded once to float32), and every step below
@@ -1230,8 +1257,25 @@ int slam_pf_known_map_miss_set(slam_pf *pf, float log_miss, float view_range,
                                int fov_on, float angle_min, float angle_max, float edge,   /* as slam_pf_prune_fov_set */
                                int sight_bins /* 0: off */, float margin);                 /* as slam_pf_prune_sight_set */
 int slam_pf_known_map_miss_device_view(slam_pf *pf, const int32_t **missed, const int32_t **spared, const int32_t **outside);
+/* Reseeding inside the session (slam_pose_reseed_dev; the frame loop: tests/_reseed_spec.py frame_loop): what to do about a cloud
+ * that settled on a wrong pose, was moved while it was not looking, or never knew where it started.  Called BETWEEN frames on a
+ * session whose known-map mode is on, in either noise form; it reads the map as it was given.  One launch applies the pending
+ * resample and the proposals: it reads the current poses through the pending gather and writes the other pose buffer, which
+ * becomes the current one; no gather is pending afterwards, and a gated session drops the weights it would have carried (as
+ * slam_pf_set_poses_host does).  The detections are the engine's current ones — those of the frame just run, unless the host handed
+ * over others since; first_id = 0, the seed is the session's, and the Philox frame word is the session's frame counter (the number
+ * of the NEXT frame): two calls with no slam_pf_step between them draw the same slots, landmarks, detections and headings.
+ * counts = {replaced, chosen but not replaced}; the call waits for the two words in mapped host memory and for nothing else (a
+ * gated session: the stream, where it drops the weights).  K == 0: SLAM_OK, counts 0, the session is as it was.
+ * After a successful reseed the last frame's log-weights no longer belong to the poses: slam_pf_best returns SLAM_ERR_NOT_READY
+ * (slam_last_error says why) until the next slam_pf_step; slam_pf_mean, slam_pf_spread and slam_pf_get_poses_host see the reseeded
+ * population with equal weights, as after slam_pf_set_poses_host.  A session that never calls it runs exactly what it ran before.
+ * SLAM_ERR_NOT_READY, the reason in slam_last_error and the session as it was: the mode is off; the session is sharded; it has
+ * n_landmarks > 0; no detections were handed over.  SLAM_ERR_INVALID_ARG: a null pointer, a fraction outside (0, 1]. */
+int slam_pf_known_map_reseed(slam_pf *pf, float fraction, int32_t counts[2]);
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
- * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.
+ * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.  SLAM_ERR_NOT_READY between a successful
+ * slam_pf_known_map_reseed and the next slam_pf_step.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
 int slam_pf_best(slam_pf *pf, float pose[3], float *logw, int32_t *index);
 /* Posterior mean of the current population: x and y are averaged, the heading is averaged on the circle around
@@ -1269,7 +1313,8 @@ int slam_pf_mean(slam_pf *pf, float ref_theta, float pose[3]);
  * the length of the mean heading vector from the mean's own sums (Qs, Qc as above; where the mean is plain
  * Qs = trunc(sum S / n_total), Qc likewise): 1 = one heading, near 0 = headings all round the circle.
  * n = 1 and a population of identical poses give +0 in all six entries and heading_r = 1 up to the truncation of C.
- * A SMALL SPREAD SAYS THAT THE PARTICLES AGREE, NOT THAT THEY ARE RIGHT: a cloud that settled on a wrong pose reports the same.
+ * A SMALL SPREAD SAYS THAT THE PARTICLES AGREE, NOT THAT THEY ARE RIGHT: a cloud that settled on a wrong pose reports the same
+ * (what to do about such a cloud in a known map: slam_pf_known_map_reseed).
  *   Domain: |dx|, |dy| < 2048 m, so |DX|, |DY| < 2^31 and a product P = A * B is one 32 x 32 -> 64-bit multiply, |P| < 2^62.  The
  *   device sums w * P as three limbs, w * (P & 0x1fffff), w * ((P >> 21) & 0x1fffff) and w * (P >> 42): with w <= 2^16 a term is
  *   below 2^37 in size and n_total <= 2^23 of them below 2^60 < 2^63 in every 64-bit accumulator; the host joins the limbs in
