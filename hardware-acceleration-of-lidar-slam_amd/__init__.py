@@ -160,6 +160,8 @@ SIGNATURES = {
     "slam_localise_miss_count": (_i, [_vp, _vp]),
     "slam_pose_reseed_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _u64, _u32, _f, _vp, _vp]),
     "slam_pose_reseed_count": (_i, [_vp, _vp]),
+    "slam_pose_reseed_pairs_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _u64, _u32, _f, _f, _f, _vp, _vp]),
+    "slam_pose_reseed_pairs_count": (_i, [_vp, _vp]),
     "slam_detect_params_default": (None, [_vp]),
     "slam_detect_scan_dev": (_i, [_vp, _vp, _vp]),
     "slam_detect_count": (_i, [_vp, _vp]),
@@ -229,6 +231,7 @@ SIGNATURES = {
     "slam_pf_known_map_miss_set": (_i, [_vp, _f, _f, _i, _f, _f, _f, _i, _f]),
     "slam_pf_known_map_miss_device_view": (_i, [_vp, _vp, _vp, _vp]),
     "slam_pf_known_map_reseed": (_i, [_vp, _f, _vp]),
+    "slam_pf_known_map_reseed_pairs": (_i, [_vp, _f, _f, _f, _vp]),
     "slam_pf_detect_set": (_i, [_vp, _vp]),
     "slam_pf_detect_fit_set": (_i, [_vp, _vp, _vp]),
     "slam_pf_best": (_i, [_vp, _fp, _fp, C.POINTER(C.c_int32)]),
@@ -585,6 +588,25 @@ class Engine:
         """-> launches of ``pose_reseed_dev`` (the session's reseeds included) of this engine so far."""
         c = C.c_int64(0)
         self._ck(self.lib.slam_pose_reseed_count(self.h, C.byref(c)), "pose_reseed_count")
+        return int(c.value)
+
+    def pose_reseed_pairs_dev(self, d_map, plane_stride, nlandmarks, d_x_in, d_y_in, d_th_in, d_anc, d_x_out, d_y_out, d_th_out, n,
+                              first_id, seed, frame, fraction, tol, min_sep, d_flag=None):
+        """``slam_pose_reseed_pairs_dev``: a chosen fraction of n slots becomes pose proposals at which TWO of the engine's current
+        detections coincide with two landmarks of d_map whose distance is the detections' within tol (detections closer than
+        min_sep make no pair); the rest copy the pose of d_anc[i] (None: i, and out may be in).  d_flag uint8 [n] or None.
+        -> (replaced, first landmark slot empty, detections too close, no partner in the map).  Synchronises."""
+        c = (C.c_int32 * 4)()
+        self._ck(self.lib.slam_pose_reseed_pairs_dev(self.h, _ptr(d_map), plane_stride, nlandmarks, _ptr(d_x_in), _ptr(d_y_in),
+                                                     _ptr(d_th_in), _ptr(d_anc), _ptr(d_x_out), _ptr(d_y_out), _ptr(d_th_out), n, first_id,
+                                                     seed, frame, float(fraction), float(tol), float(min_sep), _ptr(d_flag), c),
+                 "pose_reseed_pairs_dev")
+        return tuple(int(v) for v in c)
+
+    def pose_reseed_pairs_count(self):
+        """-> launches of ``pose_reseed_pairs_dev`` (the session's included) of this engine so far."""
+        c = C.c_int64(0)
+        self._ck(self.lib.slam_pose_reseed_pairs_count(self.h, C.byref(c)), "pose_reseed_pairs_count")
         return int(c.value)
 
     def assoc_counts(self):
@@ -1418,6 +1440,14 @@ class PfSession:
         c = (C.c_int32 * 2)()
         self.e._ck(self.e.lib.slam_pf_known_map_reseed(self.h, float(fraction), c), "pf_known_map_reseed")
         return int(c[0]), int(c[1])
+
+    def known_map_reseed_pairs(self, fraction: float, tol: float, min_sep: float):
+        """``slam_pf_known_map_reseed_pairs`` (between frames, while a known map is set): as ``known_map_reseed``, with proposals
+        from pairs of detections whose heading the lidar fixes.  -> (replaced, first landmark slot empty, detections too close,
+        no partner in the map).  ``best`` is refused until the next ``step``."""
+        c = (C.c_int32 * 4)()
+        self.e._ck(self.e.lib.slam_pf_known_map_reseed_pairs(self.h, float(fraction), float(tol), float(min_sep), c), "pf_known_map_reseed_pairs")
+        return tuple(int(v) for v in c)
 
     def assoc_view(self):
         """``slam_pf_assoc_device_view``: the last frame's table uint8 [n][stride] and stats int32 [n][3], indexed like score."""

@@ -52,6 +52,39 @@ __device__ __forceinline__ void det_sincosf(float a, float& s, float& c)
     c = ((quad + 1) & 2) ? -c0 : c0;
 }
 
+// atan2 (specification: tests/_reseed_pair_spec.py det_atan2): the ratio of the smaller to the larger magnitude by one correctly
+// rounded division, the one Cephes atanf reduction a ratio in [0, 1] can need, Cephes' four coefficients, then the octants.
+// (0, 0) is outside its domain (0 / 0).  `/` is the compiler's correctly rounded division (NOT __fdividef).
+__device__ __forceinline__ float det_atan2f(float y, float x)
+{
+    const float ax = fabsf(x), ay = fabsf(y);
+    const bool swap = ay > ax;
+    const float hi = swap ? ay : ax, lo = swap ? ax : ay;
+    float t = lo / hi;
+    float y0 = 0.0f;
+    if (t > 0.4142135623730950f) {
+        const float num = t - 1.0f;
+        const float den = t + 1.0f;
+        t = num / den;
+        y0 = 0.7853981634f;
+    }
+    const float z = t * t;
+    float p = 8.05374449538e-2f * z;
+    p = p - 1.38776856032e-1f;
+    p = p * z;
+    p = p + 1.99777106478e-1f;
+    p = p * z;
+    p = p - 3.33329491539e-1f;
+    p = p * z;
+    p = p * t;
+    p = p + t;
+    float r = y0 + p;
+    if (swap) r = 1.5707963268f - r;
+    if (x < 0.0f) r = 3.1415926536f - r;
+    if (y < 0.0f) r = -r;
+    return r;
+}
+
 __device__ __forceinline__ float det_expf(float x)
 {
     if (!(x > -80.0f)) return 0.0f;

@@ -189,6 +189,7 @@ int slam_engine_destroy(slam_engine* e)
     e->carry_buf.release();
     e->spread_buf.release();
     e->reseed_buf.release();
+    e->reseed_pair_buf.release();
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     delete e;
     return SLAM_OK;

@@ -111,6 +111,8 @@ struct slam_engine {
     int64_t localise_miss_launches = 0;        // slam_localise_miss_count: launches of the miss form, either noise (in no other counter)
     int64_t reseed_launches = 0;               // slam_pose_reseed_count: launches of slam_pose_reseed_dev (in no other counter)
     DevBuf reseed_buf;                         // its two accumulators and ticket (kept zeroed), then the two counts
+    int64_t reseed_pair_launches = 0;          // slam_pose_reseed_pairs_count: launches of slam_pose_reseed_pairs_dev (in no other counter)
+    DevBuf reseed_pair_buf;                    // its four accumulators and ticket (kept zeroed), then the four counts
     // the detector (slam_detect_scan_dev): its kernel writes det_buf and leaves {ndet, sequence} in mapped host memory; until the
     // next stage that needs the count on the host has picked it up (slam_engine_resolve_detections) it is PENDING
     int32_t* h_det = nullptr;
@@ -413,6 +415,14 @@ __attribute__((visibility("hidden"))) int slam_engine_pose_reseed(slam_engine* e
                                                                   int n, int64_t first_id, uint64_t seed, uint32_t frame, float fraction,
                                                                   uint8_t* d_flag, const slam_reseed_mapped* mapped, int32_t counts[2],
                                                                   bool* launched);
+
+// ... and slam_pose_reseed_pairs_dev the same way (four words in mapped host memory).  *launched = false: K < 2
+__attribute__((visibility("hidden"))) int slam_engine_pose_reseed_pairs(slam_engine* e, const float* d_map, int plane_stride, int nlandmarks,
+                                                                        const float* d_x_in, const float* d_y_in, const float* d_th_in,
+                                                                        const int32_t* d_anc, float* d_x_out, float* d_y_out, float* d_th_out,
+                                                                        int n, int64_t first_id, uint64_t seed, uint32_t frame, float fraction,
+                                                                        float tol, float min_sep, uint8_t* d_flag,
+                                                                        const slam_reseed_mapped* mapped, int32_t counts[4], bool* launched);
 
 // engine_match.hip
 namespace slam_detail {

@@ -318,6 +318,34 @@ struct ReseedArgs {
 };
 // one thread per slot; the counts are exact (one atomic per workgroup and count, handed over by the last workgroup to arrive)
 hipError_t launch_pose_reseed(hipStream_t stream, const ReseedArgs& a, const EventPair* ev = nullptr);
+// ---- reseed_pair_kernels.hip: reseeding from detection PAIRS (specification: tests/_reseed_pair_spec.py).  A
+// chosen fraction of the slots becomes pose proposals at which two detections coincide with two landmarks of the known map — the
+// first landmark and both detections drawn, the second landmark searched for by the wavefront; the rest take the pending resample.
+struct ReseedPairArgs {
+    const float* map;      // the map as it was given [5][plane_stride] (KnownMapArgs::map); P_xx < 0: the slot holds no landmark
+    int plane_stride;
+    int nlandmarks;        // >= 2, <= plane_stride
+    const float *x_in, *y_in, *th_in;
+    const int32_t* anc;    // a slot that is not replaced copies the pose of anc[i] (nullptr: i, and out may be in)
+    float *x_out, *y_out, *th_out;
+    int n;
+    const float *det_zx, *det_zy;   // [ndet] sensor-frame points
+    int ndet;                       // 2 .. SLAM_MAX_DETECTIONS
+    uint64_t first_id;     // global id of slot 0
+    uint32_t key0, key1, frame;
+    uint64_t thr;          // floor(fraction * 2^32), 1 .. 2^32: slot i is chosen iff its first Philox word (stream 2) is below it
+    float tol;             // >= 0: a landmark is a partner if its distance from j1 is the detections' distance within tol
+    float min_sep2;        // (min_sep * min_sep, rounded once; min_sep > tol): detections closer than that make no pair
+    uint8_t* flag;         // [n] 1 replaced, 2 slot j1 empty, 3 detections too close, 4 no partner, 0 not chosen; may be nullptr
+    unsigned int* acc;     // {replaced, j1 empty, too close, no partner, ticket}: zero on entry, left zero
+    int32_t* out;          // [4] the four counts
+    int32_t* h_out;        // the same in mapped host memory behind *h_seq = seq; may be nullptr
+    uint32_t* h_seq;
+    uint32_t seq;
+};
+// one thread per slot, the search by its wavefront; the counts are exact (one atomic per workgroup and count, handed over by the
+// last workgroup to arrive)
+hipError_t launch_pose_reseed_pairs(hipStream_t stream, const ReseedPairArgs& a, const EventPair* ev = nullptr);
 // ---- evidence_kernels.hip: landmark existence evidence (specification: tests/_evidence_spec.py).  One byte
 // c in [0, cmax] per (particle, landmark slot) beside the rows; behind the update of a frame a matched landmark gains `hit`, a
 // visible unmatched one loses `miss`, and one that cannot pay is pruned: its slot gets the bits of a slot that was never used.

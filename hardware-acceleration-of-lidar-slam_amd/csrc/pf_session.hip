@@ -3,6 +3,7 @@
 // The storage forms are pf_session_store.hip, the frame pf_session_frame.hip, the read-backs pf_session_read.hip.
 
 #include <float.h>
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -792,8 +793,9 @@ int slam_pf_known_map_device_view(slam_pf* pf, const float** prepared, int32_t* 
 }
 
 // The pending resample and the proposals in ONE launch: pose[cur] through anc[cur] -> the other pose buffer, which becomes the
-// current one.  The counts come back through the mapped result block; nothing else is waited for.
-int slam_pf_known_map_reseed(slam_pf* pf, float fraction, int32_t counts[2])
+// current one.  The counts come back through the mapped result block; nothing else is waited for.  pair == nullptr: proposals
+// from single detections (two counts, min_det 1); else from detection pairs under pair = {tol, min_sep} (four counts, min_det 2).
+static int known_map_reseed(slam_pf* pf, float fraction, const float* pair, int32_t* counts)
 {
     if (!pf || !counts) return SLAM_ERR_INVALID_ARG;
     slam_engine* e = pf->e;
@@ -808,13 +810,19 @@ int slam_pf_known_map_reseed(slam_pf* pf, float fraction, int32_t counts[2])
         snprintf(e->err, sizeof e->err, "reseed: the fraction must lie in (0, 1]");
         return SLAM_ERR_INVALID_ARG;
     }
+    if (pair && (!(pair[0] >= 0.0f) || !(pair[1] > pair[0]) || !isfinite(pair[1]) || pf->known_L < 2)) {
+        snprintf(e->err, sizeof e->err, "reseed from pairs: 0 <= tol < min_sep, both finite, and a map of two landmarks or more");
+        return SLAM_ERR_INVALID_ARG;
+    }
     if (int rc = slam_engine_resolve_detections(e)) return rc;
     if (e->ndet < 0) {
         snprintf(e->err, sizeof e->err, "reseed: no detections were handed over");
         return SLAM_ERR_NOT_READY;
     }
-    counts[0] = counts[1] = 0;
-    if (e->ndet == 0) return SLAM_OK;   // nothing to propose from: the session is as it was
+    const int ncounts = pair ? 4 : 2;
+    const ResWord words = pair ? RES_RESEED_PAIRS : RES_RESEED;
+    for (int k = 0; k < ncounts; ++k) counts[k] = 0;
+    if (e->ndet < (pair ? 2 : 1)) return SLAM_OK;   // nothing to propose from: the session is as it was
     if (pf->gated && pf->has_anc) {     // the verdict of the last frame, before the gate forgets it below
         int resampled = 1;
         if (int rc = slam_resample_happened_host(e, &resampled)) return rc;
@@ -823,12 +831,16 @@ int slam_pf_known_map_reseed(slam_pf* pf, float fraction, int32_t counts[2])
     const size_t sn = (size_t)pf->n;
     const float* src = pf->pose[pf->cur];
     float* dst = pf->pose[1 - pf->cur];
+    const float* map = pf->known_prep + 6 * (size_t)pf->known_Lp;
+    const int32_t* anc = pf->has_anc ? pf->anc[pf->cur] : nullptr;
     const uint32_t seq = ++pf->res_seq;
-    const slam_reseed_mapped mapped{ dev_word(pf, RES_RESEED), reinterpret_cast<uint32_t*>(dev_word(pf, RES_SEQ)), seq };
+    const slam_reseed_mapped mapped{ dev_word(pf, words), reinterpret_cast<uint32_t*>(dev_word(pf, RES_SEQ)), seq };
     bool launched = false;
-    if (int rc = slam_engine_pose_reseed(e, pf->known_prep + 6 * (size_t)pf->known_Lp, pf->known_Lp, pf->known_L, src, src + sn, src + 2 * sn,
-                                         pf->has_anc ? pf->anc[pf->cur] : nullptr, dst, dst + sn, dst + 2 * sn, pf->n, 0, pf->cfg.seed,
-                                         pf->frame, fraction, nullptr, &mapped, nullptr, &launched))
+    if (int rc = pair ? slam_engine_pose_reseed_pairs(e, map, pf->known_Lp, pf->known_L, src, src + sn, src + 2 * sn, anc, dst, dst + sn,
+                                                      dst + 2 * sn, pf->n, 0, pf->cfg.seed, pf->frame, fraction, pair[0], pair[1], nullptr,
+                                                      &mapped, nullptr, &launched)
+                      : slam_engine_pose_reseed(e, map, pf->known_Lp, pf->known_L, src, src + sn, src + 2 * sn, anc, dst, dst + sn,
+                                                dst + 2 * sn, pf->n, 0, pf->cfg.seed, pf->frame, fraction, nullptr, &mapped, nullptr, &launched))
         return rc;
     pf->cur = 1 - pf->cur;
     pf->has_anc = false;
@@ -837,9 +849,16 @@ int slam_pf_known_map_reseed(slam_pf* pf, float fraction, int32_t counts[2])
         if (int rc = slam_resample_gate_set(e, pf->cfg.resample_ess_frac)) return rc;
     const volatile uint32_t* h_seq = reinterpret_cast<const volatile uint32_t*>(host_word(pf, RES_SEQ));
     if (int rc = slam_engine_wait_flag(e, nullptr, h_seq, seq, "reseed flag")) return rc;
-    counts[0] = host_word(pf, RES_RESEED)[0];
-    counts[1] = host_word(pf, RES_RESEED)[1];
+    for (int k = 0; k < ncounts; ++k) counts[k] = host_word(pf, words)[k];
     return SLAM_OK;
+}
+
+int slam_pf_known_map_reseed(slam_pf* pf, float fraction, int32_t counts[2]) { return known_map_reseed(pf, fraction, nullptr, counts); }
+
+int slam_pf_known_map_reseed_pairs(slam_pf* pf, float fraction, float tol, float min_sep, int32_t counts[4])
+{
+    const float pair[2] = { tol, min_sep };
+    return known_map_reseed(pf, fraction, pair, counts);
 }
 
 int slam_pf_rows_received(const slam_pf* pf) { return pf ? pf->rows_received : 0; }

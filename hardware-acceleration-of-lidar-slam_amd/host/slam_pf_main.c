@@ -24,7 +24,7 @@
  *                      [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]]
  *                     [--landmarks-out FILE]]
  *                     [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]
- *                      [--known-reseed FRACTION [EVERY]]]
+ *                      [--known-reseed FRACTION [EVERY] | --known-reseed-pairs FRACTION TOL MIN_SEP [EVERY]]]
  *                     [--spread-out FILE]
  *   particles      the whole population (a multiple of N)
  *   --ess F        ESS-gated resampling: resample only in frames whose effective sample size is below F * N
@@ -71,6 +71,11 @@
  *                  outputs are read, FRACTION (in (0, 1]) of the particles is replaced by pose proposals at which one of the
  *                  frame's detections coincides with one landmark of the map (slam_pf_known_map_reseed) — what brings back a cloud
  *                  that settled on a wrong pose; the frame's line then ends in "  reseed = REPLACED NOT_REPLACED"
+ *   --known-reseed-pairs FRACTION TOL MIN_SEP [EVERY]  only with --known-map, not with --known-reseed: the same with proposals
+ *                  from PAIRS of detections (slam_pf_known_map_reseed_pairs) — two detections at least MIN_SEP metres apart on
+ *                  two landmarks whose distance is the detections' within TOL metres (0 <= TOL < MIN_SEP) fix the heading as
+ *                  well; a frame with fewer than two detections is skipped (counts 0); the frame's line then ends in
+ *                  "  reseed-pairs = REPLACED EMPTY TOO_CLOSE NO_PARTNER"
  *   --spread-out FILE  every frame also asks for the spread of the population about its mean (slam_pf_spread, around the same
  *                  predicted heading) and writes one line to FILE: the frame number, the six entries of the covariance over
  *                  (x, y, sin dtheta) — xx, xy, yy, xs, ys, ss — and the length of the mean heading vector, comma-separated, each
@@ -141,6 +146,8 @@ typedef struct {
     int use_known_reseed;        /* --known-reseed FRACTION [EVERY]: only with --known-map */
     float known_reseed_fraction;
     int known_reseed_every;
+    int use_known_reseed_pairs;  /* --known-reseed-pairs FRACTION TOL MIN_SEP [EVERY]: FRACTION and EVERY in the two fields above */
+    float known_reseed_tol, known_reseed_min_sep;
     /* the ranks */
     int world, use_rccl, same_device;
     uint8_t comm_id[SLAM_COMM_ID_BYTES];
@@ -324,6 +331,14 @@ static void *rank_main(void *arg)
             const int due = ++observing_frames % run->known_reseed_every == 0;
             if (due) CHECK(slam_pf_known_map_reseed(pf, run->known_reseed_fraction, reseed));
             if (rank == 0) printf("pose = %f  %f  %f  reseed = %d %d\n", pose[0], pose[1], pose[2], (int)reseed[0], (int)reseed[1]);
+        } else if (run->use_known_reseed_pairs && observe) {
+            int32_t reseed[4] = { 0, 0, 0, 0 };
+            const int due = ++observing_frames % run->known_reseed_every == 0;
+            if (due)
+                CHECK(slam_pf_known_map_reseed_pairs(pf, run->known_reseed_fraction, run->known_reseed_tol, run->known_reseed_min_sep, reseed));
+            if (rank == 0)
+                printf("pose = %f  %f  %f  reseed-pairs = %d %d %d %d\n", pose[0], pose[1], pose[2], (int)reseed[0], (int)reseed[1],
+                       (int)reseed[2], (int)reseed[3]);
         } else if (rank == 0) printf("pose = %f  %f  %f\n", pose[0], pose[1], pose[2]);
     }
     if (rank == 0) {
@@ -511,6 +526,19 @@ int main(int argc, char **argv)
                 return 2;
             }
         }
+        else if (!strcmp(argv[a], "--known-reseed-pairs") && a + 3 < argc) {
+            run.use_known_reseed_pairs = 1;
+            run.known_reseed_fraction = (float)atof(argv[++a]);
+            run.known_reseed_tol = (float)atof(argv[++a]);
+            run.known_reseed_min_sep = (float)atof(argv[++a]);
+            run.known_reseed_every = 1;
+            if (a + 1 < argc && strchr("0123456789+", argv[a + 1][0])) run.known_reseed_every = atoi(argv[++a]);
+            if (!(run.known_reseed_fraction > 0.0f && run.known_reseed_fraction <= 1.0f) || run.known_reseed_every < 1 ||
+                !(run.known_reseed_tol >= 0.0f) || !(run.known_reseed_min_sep > run.known_reseed_tol) || !(run.known_reseed_min_sep < 1e30f)) {
+                fprintf(stderr, "--known-reseed-pairs: FRACTION must lie in (0, 1], 0 <= TOL < MIN_SEP, and EVERY must be a whole number >= 1\n");
+                return 2;
+            }
+        }
         else if (!strcmp(argv[a], "--known-map") && a + 3 < argc) {
             run.known_map = argv[++a];
             float *v[3] = { &run.known_gate, &run.known_var, &run.known_log_clutter };
@@ -528,7 +556,7 @@ int main(int argc, char **argv)
     }
     const int landmark_options = run.use_assoc || run.use_prune || (run.use_detect && !run.known_map) || run.landmarks_out != NULL;
     if (npos < 5 || (run.known_map && (run.landmarks > 0 || run.world > 1 || run.use_meas_cov)) || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
-        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) || (run.use_assoc_weight && !run.use_assoc) || (run.use_known_miss && !run.known_map) || (run.use_known_reseed && !run.known_map) || ((run.known_miss_fov || run.known_miss_bins) && !run.use_known_miss) ||
+        (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) || (run.use_assoc_weight && !run.use_assoc) || (run.use_known_miss && !run.known_map) || (run.use_known_reseed && !run.known_map) || (run.use_known_reseed_pairs && (!run.known_map || run.use_known_reseed)) || ((run.known_miss_fov || run.known_miss_bins) && !run.use_known_miss) ||
         (run.use_noise && (!run.use_detect || !(run.use_assoc || run.known_map) || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
                         "[--transport rccl|local] [--same-device] [--ess F] [--refine SWEEPS [--refine-res T R]] [--meas-cov QXX QXY QYY]\n"
@@ -556,6 +584,8 @@ int main(int argc, char **argv)
                         "      landmark within VIEW_RANGE of a pose that no detection matched costs LOG_MISS, unless outside the arc or hidden\n"
                         "  --known-reseed FRACTION [EVERY]: only with --known-map; behind every EVERY-th observing frame FRACTION of the particles\n"
                         "              becomes pose proposals from the frame's detections and the map (slam_pf_known_map_reseed)\n"
+                        "  --known-reseed-pairs FRACTION TOL MIN_SEP [EVERY]: only with --known-map, not with --known-reseed; the same from PAIRS of\n"
+                        "              detections at least MIN_SEP apart on two landmarks as far apart within TOL (slam_pf_known_map_reseed_pairs)\n"
                         "  --known-map FILE GATE MAP_VAR [LOG_CLUTTER]: localise in the landmark map of FILE (\"x,y\" lines, as --landmarks-out writes\n"
                         "              them; P = MAP_VAR * I each): every frame associates its detections (--detect) with that one map within GATE and\n"
                         "              weighs with the result, LOG_CLUTTER <= 0 per unmatched detection — with --range-noise under each detection's own\n"

@@ -685,12 +685,54 @@ int slam_localise_miss_count(slam_engine *e, int64_t *launches);    /* launches 
  * any other overlap of an in and an out array is SLAM_ERR_INVALID_ARG, as are n <= 0, nlandmarks <= 0, plane_stride < nlandmarks,
  * a fraction that is not in (0, 1] (or not a number) and a null pointer other than d_anc / d_flag.  SLAM_ERR_NOT_READY: no
  * detections were handed over.  K == 0: SLAM_OK, nothing is written, counts 0.  slam_pose_reseed_count: its launches (in no other
- * counter).  Out of scope: proposals from detection pairs; deciding when to reseed. */
+ * counter).  Out of scope: deciding when to reseed.  Proposals from detection pairs: slam_pose_reseed_pairs_dev below. */
 int slam_pose_reseed_dev(slam_engine *e, const float *d_map /* [5][plane_stride] */, int plane_stride, int nlandmarks,
                          const float *d_x_in, const float *d_y_in, const float *d_th_in, const int32_t *d_anc /* NULL: identity */,
                          float *d_x_out, float *d_y_out, float *d_th_out, int n, int64_t first_id, uint64_t seed, uint32_t frame,
                          float fraction, uint8_t *d_flag /* may be NULL */, int32_t counts[2]);
 int slam_pose_reseed_count(slam_engine *e, int64_t *launches);
+/* RESEEDING FROM DETECTION PAIRS (specification: tests/_reseed_pair_spec.py reseed_pairs): one detection on one
+ * landmark leaves the heading to be drawn blind; two detections k1, k2 on two landmarks j1, j2 fix the pose completely, and the
+ * pairing is checked before the proposal is made, because |z_k2 - z_k1| must be |m_j2 - m_j1|.  j1, k1 and k2 are drawn, j2 is
+ * searched for in the map (O(nlandmarks) per proposal, done by the wavefront) and drawn among the landmarks that fit.  Map,
+ * detections, in/out arrays, d_anc, first_id, seed, frame and fraction as slam_pose_reseed_dev.  tol >= 0, min_sep > tol, both
+ * finite; min_sep2 = min_sep * min_sep rounded once.  Every product, sum, difference, quotient and square root below is one
+ * binary32 rounding, in this order.  Slot i, gid = first_id + i:
+ *     rA = philox4x32_10(lo(gid), hi(gid), frame, 2, key)   the stream and threshold of slam_pose_reseed_dev: chosen iff
+ *          (uint64)rA[0] < thr, so both calls choose the same slots
+ *     j1 = umulhi(rA[1], nlandmarks),  k1 = umulhi(rA[2], K),  k2 = umulhi(rA[3], K - 1);  k2 += (k2 >= k1)
+ *     rB = philox4x32_10(lo(gid), hi(gid), frame, 3, key)   stream 3: rB[0] picks the partner, the other words are unused
+ * and for a chosen slot, in this order:
+ *     1. ax = zx_k2 - zx_k1;  ay = zy_k2 - zy_k1;  t = ax * ax;  u = ay * ay;  dz2 = t + u.  !(dz2 >= min_sep2) (a NaN as well):
+ *        the detections are too close to fix a heading — flag 3.
+ *     2. P_xx[j1] < 0: slot j1 holds no landmark — flag 2.
+ *     3. dz = sqrt(dz2);  lo = dz - tol;  hi = dz + tol;  lo2 = lo * lo;  hi2 = hi * hi.  Landmark j is a PARTNER iff j != j1,
+ *        !(P_xx[j] < 0), and with bx = mx_j - mx_j1; by = my_j - my_j1; t = bx * bx; u = by * by; dm2 = t + u:
+ *        dm2 > 0 && lo2 <= dm2 && dm2 <= hi2 (squared distances only; both bounds inclusive).  cnt = the number of partners;
+ *        cnt == 0 — flag 4.
+ *     4. c = umulhi(rB[0], cnt), j2 = the c-th partner in ascending j (so the result does not depend on how the search is
+ *        scheduled), b = m_j2 - m_j1 as above;
+ *            t = bx * ay;  u = by * ax;  cr = t - u;   t = ax * bx;  u = ay * by;  dt = t + u;
+ *            theta = det_atan2(cr, dt);  theta < 0: theta = theta + 6.2831853072f     (the angle of a less the angle of b: the
+ *            update's world offset of a detection is (c zx + s zy, c zy - s zx))
+ *        (s, c) = the specified sine and cosine of theta, and (x', y') from (m_j1, z_k1, s, c) exactly as slam_pose_reseed_dev
+ *        forms them; th' = theta — flag 1.
+ *     det_atan2(y, x): hi = max(|x|, |y|), lo = the other (swapped iff |y| > |x|);  t = lo / hi;  t > 0.4142135623730950f:
+ *        y0 = 0.7853981634f, t = (t - 1) / (t + 1), else y0 = 0;  z = t * t;
+ *        p = 8.05374449538e-2f * z; p = p - 1.38776856032e-1f; p = p * z; p = p + 1.99777106478e-1f; p = p * z;
+ *        p = p - 3.33329491539e-1f; p = p * z; p = p * t; p = p + t;  r = y0 + p;  swapped: r = 1.5707963268f - r;
+ *        x < 0: r = 3.1415926536f - r;  y < 0: r = -r.  (0, 0) cannot arise: min_sep > tol >= 0 and dm2 > 0 keep a and b non-zero.
+ * A slot that is not replaced copies (x, y, th)[d_anc[i]] (d_anc NULL: i).  d_flag (may be NULL) uint8 [n]: the flags above, 0 not
+ * chosen; counts = {replaced, j1 empty, too close, no partner}, exact; the call synchronises to return them.
+ * Every refusal of slam_pose_reseed_dev applies; SLAM_ERR_INVALID_ARG also for !(tol >= 0), !(min_sep > tol), a non-finite value of
+ * either, and nlandmarks < 2.  K < 2: SLAM_OK, nothing is written, counts 0.  slam_pose_reseed_pairs_count: its launches (in no
+ * other counter).  Out of scope: a fallback to single-detection proposals in the same call (call slam_pose_reseed_dev), searching
+ * all pairs of landmarks, deciding when to reseed. */
+int slam_pose_reseed_pairs_dev(slam_engine *e, const float *d_map /* [5][plane_stride] */, int plane_stride, int nlandmarks,
+                               const float *d_x_in, const float *d_y_in, const float *d_th_in, const int32_t *d_anc /* NULL: identity */,
+                               float *d_x_out, float *d_y_out, float *d_th_out, int n, int64_t first_id, uint64_t seed, uint32_t frame,
+                               float fraction, float tol, float min_sep, uint8_t *d_flag /* may be NULL */, int32_t counts[4]);
+int slam_pose_reseed_pairs_count(slam_engine *e, int64_t *launches);
 /* THE DETECTOR: the detections of a frame made on the device from the engine's current scan (slam_scan_upload_host / _set_dev),
  * P = nbeams points in scan order — what fe_clean left, so a removed beam leaves no hole and the rule uses distances only, never
  * beam angles.  With jump2 = jump * jump, guard2, width2 and range2 likewise (each rounded once to float32), and every step below
@@ -1273,9 +1315,17 @@ int slam_pf_known_map_miss_device_view(slam_pf *pf, const int32_t **missed, cons
  * SLAM_ERR_NOT_READY, the reason in slam_last_error and the session as it was: the mode is off; the session is sharded; it has
  * n_landmarks > 0; no detections were handed over.  SLAM_ERR_INVALID_ARG: a null pointer, a fraction outside (0, 1]. */
 int slam_pf_known_map_reseed(slam_pf *pf, float fraction, int32_t counts[2]);
+/* The same with proposals from detection pairs (slam_pose_reseed_pairs_dev; the frame loop: tests/_reseed_pair_spec.py frame_loop):
+ * every state rule of slam_pf_known_map_reseed holds — between frames, known-map mode on in either noise form, first_id = 0, the
+ * session's seed and frame counter (two calls with no step between them draw the same), the pending resample rides along, a gated
+ * session drops its carried weights, slam_pf_best is refused until the next slam_pf_step.  counts = {replaced, j1 empty, too close,
+ * no partner}, through four words of the mapped result block behind its sequence number.  Fewer than two detections: SLAM_OK,
+ * counts 0, the session is as it was.  SLAM_ERR_NOT_READY as there; SLAM_ERR_INVALID_ARG: a null pointer, a fraction outside (0, 1],
+ * !(tol >= 0), !(min_sep > tol), a non-finite value of either, a known map of fewer than two landmark slots. */
+int slam_pf_known_map_reseed_pairs(slam_pf *pf, float fraction, float tol, float min_sep, int32_t counts[4]);
 /* heaviest particle of the last frame (lowest index on ties; a NaN log-weight never wins; nothing but -inf and NaN:
  * particle 0 with log-weight -inf): its pose, log-weight and index; synchronises.  SLAM_ERR_NOT_READY between a successful
- * slam_pf_known_map_reseed and the next slam_pf_step.
+ * slam_pf_known_map_reseed (or _reseed_pairs) and the next slam_pf_step.
  * Sharded: the heaviest of the whole population (the same answer on every rank), `index` is its global id. */
 int slam_pf_best(slam_pf *pf, float pose[3], float *logw, int32_t *index);
 /* Posterior mean of the current population: x and y are averaged, the heading is averaged on the circle around
