@@ -70,10 +70,13 @@ def write_scene(path):
     path.write_text("".join(",".join(f"{v:.6f}" for v in np.hypot(bx.astype(np.float64), by.astype(np.float64))) + "\n" for bx, by in SC.SCANS))
 
 
-def python_run(orc, csv, ess):
+def python_run(orc, csv, ess, n=None, seed=None, meas_var=1.0, configure=None, observe=False, after=None):
     """What slam_pf_main does without landmarks, from Python (the loop of tests/test_gpu_assoc_weight_session.py's python_run: the
     front end's pieces are the oracle's, pinned bit for bit on the C front end by tests/test_host_frontend.py; the session is the
-    package's) -> (pose log, per frame: the frame number and what spread returned around the heading the mean was asked around, frames the gate kept)."""
+    package's) -> (pose log, per frame: the frame number and what spread returned around the heading the mean was asked around, frames the gate kept).
+    n, seed, meas_var: the session's (default: HOST_N, HOST_SEED, 1.0).  configure(pkg, e, ses, ang): the switches the program gives
+    in front of the first frame; observe: every frame has use_observations = 1; after(ses) -> the tail of the frame's pose line
+    (the program's reseed behind the frame)."""
     import ctypes
     libm = ctypes.CDLL("libm.so.6")
     libm.cosf.restype = libm.sinf.restype = ctypes.c_float
@@ -82,7 +85,10 @@ def python_run(orc, csv, ess):
     frames = [np.array([float(v) for v in ln.split(",") if v.strip()], F) for ln in csv.read_text().splitlines()]
     ang = orc.beam_angles(-2.351831, 0.004363, len(frames[0]))
     e = pkg.Engine(0)
-    ses = pkg.PfSession(e, HOST_N, 0, seed=HOST_SEED, sigma=(0.01, 0.01, 0.002), meas_var=1.0, score_gain=0.25, resample_ess_frac=ess)
+    ses = pkg.PfSession(e, n or HOST_N, 0, seed=HOST_SEED if seed is None else seed, sigma=(0.01, 0.01, 0.002), meas_var=meas_var, score_gain=0.25,
+                        resample_ess_frac=ess)
+    if configure:
+        configure(pkg, e, ses, ang)
     pose, prev = np.zeros(3, F), np.zeros(3, F)
     bx, by = orc.clean_scan(frames[0], ang)
     map_x, map_y = orc.transform(bx, by, pose)
@@ -101,7 +107,7 @@ def python_run(orc, csv, ess):
                 grid, m = orc.rasterise(lx, ly, pixel, ld)
                 e.grid_upload(slot, grid, pkg.grid_meta(m.rows, m.cols, m.ld, m.pixel, m.min_x, m.min_y), 10.0)
         dp = (pose - prev).astype(F) if k > 1 else np.zeros(3, F)
-        ses.step(1, dp, False)
+        ses.step(1, dp, observe)
         ref = float(F(pose[2] + dp[2]))
         kept += int(bool(ess) and not e.resample_happened())
         best = ses.mean(ref)
@@ -119,7 +125,7 @@ def python_run(orc, csv, ess):
             map_pose = pose.copy()
         else:
             updated = False
-        log.append("pose = %f  %f  %f\n" % tuple(float(v) for v in pose))
+        log.append("pose = %f  %f  %f%s\n" % (tuple(float(v) for v in pose) + (after(ses) if after else "",)))
     ses.close()
     e.close()
     return "".join(log), spreads, kept
