@@ -46,6 +46,14 @@ class GridMeta(C.Structure):
                 ("min_x", C.c_float), ("min_y", C.c_float)]
 
 
+class PfMode(C.Structure):
+    """``slam_pf_mode`` — one cluster of the particle cloud: pose, mass, centre cell, member cells, weight."""
+
+    _fields_ = [("pose", C.c_float * 3), ("mass", C.c_float), ("cell", C.c_int32 * 3), ("ncells", C.c_int32), ("weight", C.c_int64)]
+
+
+MAX_MODES = 8
+
 _vp, _i, _i64, _u64, _u32, _f = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, C.c_float
 _fp = C.POINTER(C.c_float)
 
@@ -195,6 +203,9 @@ SIGNATURES = {
     "slam_pf_mean": (_i, [_vp, _f, _fp]),
     "slam_pf_spread": (_i, [_vp, _f, _fp, _fp, _fp]),
     "slam_pose_spread_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _fp, _fp, _fp]),
+    "slam_pf_modes": (_i, [_vp, _f, _f, _i, _i, C.POINTER(PfMode), C.POINTER(_i), C.POINTER(_i)]),
+    "slam_pose_modes_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _i, C.POINTER(PfMode), C.POINTER(_i), C.POINTER(_i),
+                                 C.POINTER(_i64)]),
     "slam_pf_rows_received": (_i, [_vp]),
     "slam_pf_device_view": (_i, [_vp, _vp]),
     "slam_pf_frames_resampled": (_i64, [_vp]),
@@ -286,6 +297,11 @@ def _np(a, dtype):
 
 def _f3(v):
     return (C.c_float * 3)(*[float(np.float32(x)) for x in v])
+
+
+def _mode_list(modes, count):
+    return [dict(pose=np.array(list(m.pose), np.float32), mass=np.float32(m.mass), cell=tuple(m.cell), ncells=int(m.ncells),
+                 weight=int(m.weight)) for m in modes[:count]]
 
 
 class Engine:
@@ -879,6 +895,15 @@ class Engine:
         self._ck(self.lib.slam_pose_spread_dev(self.h, _ptr(d_x), _ptr(d_y), _ptr(d_theta), _ptr(d_idx), _ptr(d_carry), n,
                                                float(ref_theta), pose, cov, C.byref(r)), "pose_spread_dev")
         return np.array(list(pose), np.float32), np.array(list(cov), np.float32), np.float32(r.value)
+
+    def pose_modes_dev(self, d_x, d_y, d_theta, n, ref_theta, cell, hbins, max_modes, d_idx=None, d_carry=None):
+        """``slam_pose_modes_dev``: -> (modes, cells, wtotal) of n poses in device memory, as ``PfSession.modes`` defines them.
+        d_idx: a pending gather (int32, optional); d_carry: log-weight minus the largest, one float per slot (optional)."""
+        modes, nm, cells, wt = (PfMode * MAX_MODES)(), _i(0), _i(0), _i64(0)
+        self._ck(self.lib.slam_pose_modes_dev(self.h, _ptr(d_x), _ptr(d_y), _ptr(d_theta), _ptr(d_idx), _ptr(d_carry), n, float(ref_theta),
+                                              float(cell), int(hbins), int(max_modes), modes, C.byref(nm), C.byref(cells), C.byref(wt)),
+                 "pose_modes_dev")
+        return _mode_list(modes, nm.value), cells.value, wt.value
 
     def argmax_dev(self, d_values, n, d_index, d_value):
         """``slam_argmax_dev``: index (int32) and value (float32) of the largest of d_values[0..n) to device memory: the lowest
@@ -1562,6 +1587,16 @@ class PfSession:
         pose = (C.c_float * 3)()
         self.e._ck(self.e.lib.slam_pf_mean(self.h, float(ref_theta), pose), "pf_mean")
         return np.array(list(pose), np.float32)
+
+    def modes(self, ref_theta: float, cell: float, hbins: int = 16, max_modes: int = 4):
+        """``slam_pf_modes``: -> (modes, cells).  modes: the heaviest clusters of the cloud, heaviest first, each a dict with pose
+        (float32 [3]), mass (float32, its share of the population's weight), cell (the centre: ix, iy, heading bin), ncells and
+        weight; cells: the number of distinct occupied cells.  cell: the cell's size in metres (at least the size of a settled
+        cloud); hbins: heading bins, 1 or 4 .. 64; max_modes: 1 .. 8.  One GPU only.  No policy: what to do with it is yours."""
+        modes, nm, cells = (PfMode * MAX_MODES)(), _i(0), _i(0)
+        self.e._ck(self.e.lib.slam_pf_modes(self.h, float(ref_theta), float(cell), int(hbins), int(max_modes), modes, C.byref(nm),
+                                            C.byref(cells)), "pf_modes")
+        return _mode_list(modes, nm.value), cells.value
 
     def spread(self, ref_theta: float):
         """``slam_pf_spread``: -> (pose, cov, heading_r).  pose: ``mean(ref_theta)``, bit for bit; cov: float32 [6] = xx, xy, yy,

@@ -45,7 +45,7 @@ static hipError_t engine_host_block(slam_engine* e)
 {
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t b_fm = up(sizeof(float) * (kFmIn + kFmOut + 4 + kFmPair)), b_plan = up(sizeof(int32_t) * (SLAM_PLAN_WORDS(kMaxRanks) + 1)),
-                 b_small = 256, b_res = 512, b_stage = up(sizeof(float) * kStageSlots * kStageFloats);
+                 b_small = 256, b_res = 1024, b_stage = up(sizeof(float) * kStageSlots * kStageFloats);
     const size_t total = b_fm + b_plan + 4 * b_small + b_res + b_stage;
     hipError_t err = hipHostMalloc(&e->h_block, total, hipHostMallocMapped);
     if (err != hipSuccess) return err;
@@ -188,6 +188,7 @@ int slam_engine_destroy(slam_engine* e)
     e->gate_buf.release();
     e->carry_buf.release();
     e->spread_buf.release();
+    e->modes_buf.release();
     e->reseed_buf.release();
     e->reseed_pair_buf.release();
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);

@@ -155,6 +155,9 @@ struct slam_engine {
     DevBuf carry_buf;          // float[n]
     int carry_n = -1;
     DevBuf spread_buf;         // slam_pose_spread_dev: the accumulators and tickets of the two launches (kept zeroed), then their sums
+    DevBuf modes_buf;          // slam_pose_modes_dev / slam_pf_modes: the table, the list of claimed slots, the control words (all kept zeroed), the result; made by the first call
+    bool modes_clean = false;  // ... and every launch so far left it zeroed (a failed launch: cleared again before the next)
+    int modes_cus = 0;         // compute units of the device (asked once)
 
     // feedback of the resample stages: roughly how many distinct ancestors the last one left {count, n} (mapped host
     // memory, read without synchronisation: it only steers the choice between two equivalent EKF kernels)
@@ -178,7 +181,7 @@ struct slam_engine {
     bool obs_table_owned = false;   // the table is the engine's own copy (slam_obs_upload_host), not the caller's arrays
     int32_t* h_obs = nullptr;
     int32_t* d_hobs = nullptr;
-    // 512 bytes of mapped host memory the engine's (one) particle-filter session delivers its results through (pf_session.h: ResWord).  It belongs to
+    // 1024 bytes of mapped host memory the engine's (one) particle-filter session delivers its results through (pf_session.h: ResWord).  It belongs to
     // the ENGINE, not to the session: freeing pinned host memory makes the driver hold the process's queues for 65-80 ms some
     // 10-50 ms later (profiles/r03_stall_trigger.txt) — a session that came and went would stall the frames of the next one.
     void* h_block = nullptr;        // the one pinned allocation every h_* pointer of the engine points into
@@ -500,6 +503,17 @@ int slam_engine_fastmatch_pair(slam_engine* e, int slot1, int slot2, const float
 // (estimate_host.h); SLAM_ERR_INVALID_ARG, with the reason in slam_last_error, when a particle lay outside the domain
 __attribute__((visibility("hidden"))) int slam_engine_spread_result(slam_engine* e, const slam::PoseMean& mean, const long long m[slam::kPoseMoments],
                                                                     float pose[3], float cov[6], float* heading_r);
+// engine_modes.hip: the three launches of the modes (kernels.h: launch_modes) on the engine's stream, parameters checked, the
+// buffers made at the first call; the raw result (kModesWords 8-byte words) goes to device memory at *d_raw and, with d_hout, to
+// mapped host memory behind *d_hseq = seq.  Then: what slam_pose_modes_dev and slam_pf_modes return from the raw words —
+// SLAM_ERR_INVALID_ARG (a particle outside the domain) or SLAM_ERR_CAPACITY (too many cells) with the reason in slam_last_error
+// and no output written.
+__attribute__((visibility("hidden"))) int slam_engine_modes_launch(slam_engine* e, const float* d_x, const float* d_y, const float* d_theta,
+                                                                   const int32_t* d_idx, const float* d_carry, int n, float ref_theta, float cell,
+                                                                   int hbins, int max_modes, long long* d_hout, uint32_t* d_hseq, uint32_t seq,
+                                                                   const long long** d_raw);
+__attribute__((visibility("hidden"))) int slam_engine_modes_result(slam_engine* e, const long long* raw, float ref_theta, float cell,
+                                                                   slam_pf_mode* modes, int* n_modes, int* cells, int64_t* wtotal);
 // engine_resample.hip: slam_migrate_pack_dev for a session with paged maps (d_pt: page tables of nb entries, d_map: the page pool)
 extern "C" int slam_migrate_pack_paged(slam_engine* e, int n_local, int rank, int world, const int32_t* plan, const float* d_pose,
                             int64_t pose_ld, const float* d_map, int64_t row_stride, int plane_stride, int nlandmarks,

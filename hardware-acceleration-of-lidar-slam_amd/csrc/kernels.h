@@ -790,6 +790,39 @@ constexpr int kPoseMoments = 20, kPoseMomentsD = 18, kPoseMomentsFlag = 19;
 hipError_t launch_pose_moments(hipStream_t stream, const float* x, const float* y, const float* th, const int32_t* idx,
                                int n, const float mean[3], unsigned long long* acc, unsigned int* ticket, long long* out,
                                long long* h_out, uint32_t* h_seq, uint32_t seq, const float* carry = nullptr);
+// ---- modes_kernels.hip: the modes of a pose population (slam_pf_modes; specification: tests/_modes_spec.py).
+// A cell is a key (ix, iy, b); the table is open addressing in device memory, one 64-byte line per cell, zero = empty.  Three
+// launches: accumulate (the population once), score (one thread per occupied cell), select (one workgroup: the centres, their
+// member sums, the hand-over, and the table cleared again for the next call).
+struct ModesCell {
+    unsigned long long key;      // 0: empty; else 1 + ((ix + 2^20) << 27 | (iy + 2^20) << 6 | b): ordered as (ix, iy, b) is
+    unsigned long long sum[5];   // W, sum w FX, sum w FY, sum w S, sum w C (two's complement)
+    unsigned long long score;    // sum of W over the neighbourhood (the score launch)
+    unsigned long long pad;
+};
+constexpr int kModesSlots = 1 << 18;      // of the table; a power of two
+constexpr int kModesMaxCells = 65536;     // distinct cells a call accepts
+constexpr int kModesMaxBlocks = 512;      // of the accumulate launch: kModesMaxCells + 1 + its threads stay below kModesSlots (see there)
+constexpr int kModesMax = 8;              // modes a call returns at most
+// what the select launch hands over, 8-byte words: {particles outside the domain, cells inserted, Wtotal, n_modes}, then per mode
+// {key, member cells, Wm, A_x, A_y, sum w S, sum w C}
+constexpr int kModesHead = 4, kModesPer = 7, kModesWords = kModesHead + kModesMax * kModesPer;
+struct ModesArgs {
+    const float *x, *y, *th;     // [n] each
+    const int32_t* idx;          // the pending gather (optional)
+    const float* carry;          // the source of the 16-bit weights, one per SLOT (optional: w = 1)
+    int n;
+    float ref_theta, inv_cell;
+    int hbins, max_modes;
+    ModesCell* table;            // [kModesSlots], all zero between calls
+    uint32_t* list;              // [kModesSlots] the slots in use, in the order they were claimed
+    unsigned long long* ctrl;    // [3] {cells inserted (its low word), particles outside the domain, Wtotal}, zero between calls
+    long long* out;              // [kModesWords] device memory
+    long long* h_out;            // the same to mapped host memory behind *h_seq = seq (optional)
+    uint32_t* h_seq;
+    uint32_t seq;
+};
+hipError_t launch_modes(hipStream_t stream, const ModesArgs& a, int cus);
 hipError_t launch_gather_f32(hipStream_t stream, const float* src, const int32_t* idx, int n, float* dst);
 hipError_t launch_gather_map(hipStream_t stream, const float* in, float* out, int64_t in_row_stride,
                              int64_t out_row_stride, int in_plane_stride, int out_plane_stride, int nlandmarks,

@@ -31,6 +31,7 @@ enum ResWord {
     RES_MOMENTS = 32,     // 32..71: kPoseMoments x 8 bytes, what slam_pf_spread asks for (behind RES_SEQ as well)
     RES_RESEED = 72,      // 72..73 {replaced, chosen but not replaced} of slam_pf_known_map_reseed (behind RES_SEQ as well)
     RES_RESEED_PAIRS = 74,   // 74..77 {replaced, j1 empty, too close, no partner} of slam_pf_known_map_reseed_pairs (behind RES_SEQ as well)
+    RES_MODES = 128,      // 128..247: kModesWords x 8 bytes, what slam_pf_modes asks for (behind RES_SEQ as well)
 };
 
 struct slam_pf {

@@ -193,6 +193,42 @@ int pf_spread(slam_pf* pf, float ref_theta, float pose[3], float cov[6], float* 
     return slam_engine_spread_result(e, mo.m, m, pose, cov, heading_r);
 }
 
+// the modes of the population behind the pending gather: the weights by the rules of mean_of (the gate's on a frame it kept,
+// else w = 1), three launches, the raw words through mapped host memory.  One GPU only.
+int pf_modes(slam_pf* pf, float ref_theta, float cell, int hbins, int max_modes, slam_pf_mode* modes, int* n_modes, int* cells)
+{
+    if (!pf || !modes || !n_modes || !cells) return SLAM_ERR_INVALID_ARG;
+    slam_engine* e = pf->e;
+    if (pf->comm) {
+        snprintf(e->err, sizeof e->err, "the modes of a sharded population are not built (cells would have to be added over the ranks): "
+                                        "one GPU only");
+        return SLAM_ERR_INVALID_ARG;
+    }
+    SLAM_HIP_TRY(e, hipSetDevice(e->device));
+    const size_t sn = (size_t)pf->n;
+    const float* x = nullptr;
+    const int32_t* idx = nullptr;
+    if (int rc = ancestor_poses(pf, &x, &idx)) return rc;
+    int resampled = 1;
+    if (pf->gated && pf->has_anc)
+        if (int rc = slam_resample_happened_host(e, &resampled)) return rc;
+    long long raw[kModesWords];
+    for (int pass = resampled ? 1 : 0; pass < 2; ++pass) {   // pass 0: weighted; pass 1: plain (also where no particle has any weight)
+        const uint32_t seq = ++pf->res_seq;
+        const long long* d_raw = nullptr;
+        if (int rc = slam_engine_modes_launch(e, x, x + sn, x + 2 * sn, idx, pass == 0 ? e->carry_buf.as<float>() : nullptr, pf->n, ref_theta,
+                                              cell, hbins, max_modes, reinterpret_cast<long long*>(dev_word(pf, RES_MODES)),
+                                              reinterpret_cast<uint32_t*>(dev_word(pf, RES_SEQ)), seq, &d_raw)) {
+            --pf->res_seq;   // (nothing was launched that would write it)
+            return rc;
+        }
+        if (int rc = wait_result(pf, seq)) return rc;
+        memcpy(raw, host_word(pf, RES_MODES), sizeof raw);
+        if (!(pass == 0 && raw[0] == 0 && raw[2] == 0)) break;
+    }
+    return slam_engine_modes_result(e, raw, ref_theta, cell, modes, n_modes, cells, nullptr);
+}
+
 int pf_get_poses_host(slam_pf* pf, float* x, float* y, float* theta)
 {
     if (!pf || !x || !y || !theta) return SLAM_ERR_INVALID_ARG;
@@ -292,6 +328,10 @@ extern "C" {
 int slam_pf_best(slam_pf* pf, float pose[3], float* logw, int32_t* index) { return collective_result(pf, pf_best(pf, pose, logw, index)); }
 int slam_pf_mean(slam_pf* pf, float ref_theta, float pose[3]) { return collective_result(pf, pf_mean(pf, ref_theta, pose)); }
 int slam_pf_spread(slam_pf* pf, float ref_theta, float pose[3], float cov[6], float* heading_r) { return collective_result(pf, pf_spread(pf, ref_theta, pose, cov, heading_r)); }
+int slam_pf_modes(slam_pf* pf, float ref_theta, float cell, int hbins, int max_modes, slam_pf_mode* modes, int* n_modes, int* cells)
+{
+    return pf_modes(pf, ref_theta, cell, hbins, max_modes, modes, n_modes, cells);   // (never collective: sharded sessions are refused)
+}
 int slam_pf_get_poses_host(slam_pf* pf, float* x, float* y, float* theta) { return collective_result(pf, pf_get_poses_host(pf, x, y, theta)); }
 int slam_pf_get_map_host(slam_pf* pf, float* rows) { return collective_result(pf, pf_get_map_host(pf, rows)); }
 int slam_pf_get_map_rows_host(slam_pf* pf, const int32_t* particle, int count, float* rows) { return collective_result(pf, pf_get_map_rows_host(pf, particle, count, rows)); }

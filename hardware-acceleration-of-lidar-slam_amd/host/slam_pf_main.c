@@ -25,7 +25,7 @@
  *                     [--landmarks-out FILE]]
  *                     [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]] [--range-noise RV BV [LV]]]
  *                      [--known-reseed FRACTION [EVERY] | --known-reseed-pairs FRACTION TOL MIN_SEP [EVERY]]]
- *                     [--spread-out FILE]
+ *                     [--spread-out FILE] [--modes-out FILE CELL HBINS M]
  *   particles      the whole population (a multiple of N)
  *   --ess F        ESS-gated resampling: resample only in frames whose effective sample size is below F * N
  *   --refine SWEEPS  scan-match refinement of every particle (slam_pf_refine_set): SWEEPS (1..16) sweeps of the reference's
@@ -81,6 +81,11 @@
  *                  (x, y, sin dtheta) — xx, xy, yy, xs, ys, ss — and the length of the mean heading vector, comma-separated, each
  *                  number as %.9g (enough to give back its binary32).  A small spread says that the particles agree, not that
  *                  they are right.  Every other output stays byte for byte what it is without the flag
+ *   --modes-out FILE CELL HBINS M  every frame also asks for the modes of the population (slam_pf_modes, around the same
+ *                  predicted heading: cells of CELL metres and HBINS heading bins, at most M modes) and writes one line to FILE:
+ *                  the frame number, the number of modes, the number of occupied cells, then x y theta mass per mode, heaviest
+ *                  first, space-separated, each number as %.9g.  One GPU: refused with --gpus N > 1 or --transport.  Every
+ *                  other output stays byte for byte what it is without the flag
  */
 #define _POSIX_C_SOURCE 200809L
 #include <math.h>
@@ -133,6 +138,10 @@ typedef struct {
     const char *landmarks_out;   /* --landmarks-out FILE */
     const char *spread_out;      /* --spread-out FILE */
     FILE *spread;                /* ... opened in main, before any rank runs; rank 0 writes */
+    const char *modes_out;       /* --modes-out FILE CELL HBINS M */
+    FILE *modes;
+    float modes_cell;
+    int modes_hbins, modes_max;
     const char *known_map;       /* --known-map FILE GATE MAP_VAR [LOG_CLUTTER] */
     float known_gate, known_var, known_log_clutter;
     float *known_rows;           /* [5][known_n]: the file's points, P = MAP_VAR * I */
@@ -304,6 +313,16 @@ static void *rank_main(void *arg)
             if (rank == 0)
                 fprintf(run->spread, "%d,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g\n", k + 1, (double)cov[0], (double)cov[1], (double)cov[2],
                         (double)cov[3], (double)cov[4], (double)cov[5], (double)heading_r);
+        }
+        if (run->modes_out) {   /* one GPU only (main refuses the rest) */
+            slam_pf_mode md[8];
+            int n_modes = 0, cells = 0;
+            CHECK(slam_pf_modes(pf, pose[2] + dp[2], run->modes_cell, run->modes_hbins, run->modes_max, md, &n_modes, &cells));
+            fprintf(run->modes, "%d %d %d", k + 1, n_modes, cells);
+            for (int m = 0; m < n_modes; ++m)
+                fprintf(run->modes, " %.9g %.9g %.9g %.9g", (double)md[m].pose[0], (double)md[m].pose[1], (double)md[m].pose[2],
+                        (double)md[m].mass);
+            fputc('\n', run->modes);
         }
         memcpy(prev, pose, sizeof prev);
         memcpy(pose, best, sizeof pose);
@@ -495,6 +514,12 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(argv[a], "--landmarks-out") && a + 1 < argc) run.landmarks_out = argv[++a];
         else if (!strcmp(argv[a], "--spread-out") && a + 1 < argc) run.spread_out = argv[++a];
+        else if (!strcmp(argv[a], "--modes-out") && a + 4 < argc) {
+            run.modes_out = argv[++a];
+            run.modes_cell = (float)atof(argv[++a]);
+            run.modes_hbins = atoi(argv[++a]);
+            run.modes_max = atoi(argv[++a]);
+        }
         else if (!strcmp(argv[a], "--known-miss") && a + 2 < argc) {
             run.use_known_miss = 1;
             run.known_log_miss = (float)atof(argv[++a]);
@@ -555,7 +580,7 @@ int main(int argc, char **argv)
         else if (npos < 8) pos[npos++] = argv[a];
     }
     const int landmark_options = run.use_assoc || run.use_prune || (run.use_detect && !run.known_map) || run.landmarks_out != NULL;
-    if (npos < 5 || (run.known_map && (run.landmarks > 0 || run.world > 1 || run.use_meas_cov)) || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
+    if (npos < 5 || (run.modes_out && (run.world > 1 || transport_given)) || (run.known_map && (run.landmarks > 0 || run.world > 1 || run.use_meas_cov)) || run.world < 1 || run.world > 16 || run.refine_sweeps < 0 || run.refine_sweeps > 16 || run.landmarks < 0 ||
         (landmark_options && run.landmarks == 0) || (run.landmarks > 0 && run.world > 1) || (run.use_fit && !run.use_detect) || (run.use_sight && !run.use_prune) || (run.use_fov && !run.use_prune) || (run.use_merge && !run.use_assoc) || (run.use_assoc_weight && !run.use_assoc) || (run.use_known_miss && !run.known_map) || (run.use_known_reseed && !run.known_map) || (run.use_known_reseed_pairs && (!run.known_map || run.use_known_reseed)) || ((run.known_miss_fov || run.known_miss_bins) && !run.use_known_miss) ||
         (run.use_noise && (!run.use_detect || !(run.use_assoc || run.known_map) || run.use_meas_cov))) {
         fprintf(stderr, "usage: %s dataset.csv frames beams map_out.csv particles [seed [mean|best]] [--gpus N] "
@@ -563,6 +588,7 @@ int main(int argc, char **argv)
                         "  [--landmarks L [--assoc GATE NEW_GATE [--merge GATE] [--assoc-weight LOG_NEW LOG_CLUTTER LOG_MISS] [--prune HIT MISS CMAX RANGE [--prune-sight BINS MARGIN] [--prune-fov EDGE]] [--detect [JUMP GUARD WIDTH RANGE MIN MAX WRAP] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] "
                         "[--landmarks-out FILE]]\n"
                         "  [--known-map FILE GATE MAP_VAR [LOG_CLUTTER] [--detect [..] [--pole-radius R [TOL]] [--range-noise RANGE_VAR BEARING_VAR [LATERAL_VAR]]]] [--spread-out FILE]\n"
+                        "  [--modes-out FILE CELL HBINS M]\n"
                         "  --meas-cov: the landmark update's 2x2 sensor-frame covariance; makes the session on rows, and is otherwise inert\n"
                         "              without --landmarks; with --landmarks and --assoc the association gates and updates under it\n"
                         "  --landmarks: L landmark slots per particle on rows, one GPU; --assoc, --prune, --detect and --landmarks-out need it.\n"
@@ -592,7 +618,10 @@ int main(int argc, char **argv)
                         "              covariance; one GPU, not with --landmarks or --meas-cov\n"
                         "  --spread-out FILE: one line per frame to FILE: frame, the covariance of the population over (x, y, sin dtheta) about its\n"
                         "              mean (xx, xy, yy, xs, ys, ss) and the length of the mean heading vector, %%.9g each; a small spread says the\n"
-                        "              particles agree, not that they are right\n", argv[0]);
+                        "              particles agree, not that they are right\n"
+                        "  --modes-out FILE CELL HBINS M: one line per frame to FILE: frame, the number of modes, the number of occupied cells, then\n"
+                        "              x y theta mass per mode of the population (slam_pf_modes: cells of CELL metres, HBINS heading bins — 1 or\n"
+                        "              4 .. 64 —, at most M <= 8 modes, heaviest first), %%.9g each; one GPU, not with --gpus N > 1 or --transport\n", argv[0]);
         return 2;
     }
     if (run.use_meas_cov) {   /* the conditions of slam_pf_meas_cov_set: finite, qxx > 0, qyy > 0, float determinant > 0 */
@@ -632,6 +661,7 @@ int main(int argc, char **argv)
     }
     /* opened here: a rank that failed on it alone would leave the others waiting in their first collective */
     if (run.spread_out && !(run.spread = fopen(run.spread_out, "w"))) { perror(run.spread_out); free(run.known_rows); return 2; }
+    if (run.modes_out && !(run.modes = fopen(run.modes_out, "w"))) { perror(run.modes_out); free(run.known_rows); return 2; }
     run.dataset = pos[0];
     run.frames = atoi(pos[1]);
     run.beams = atoi(pos[2]);
@@ -676,5 +706,6 @@ int main(int argc, char **argv)
     slam_local_group_destroy(run.group);
     free(run.known_rows);
     if (run.spread && fclose(run.spread) != 0) { perror(run.spread_out); rc |= 1; }
+    if (run.modes && fclose(run.modes) != 0) { perror(run.modes_out); rc |= 1; }
     return rc;
 }

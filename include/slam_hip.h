@@ -978,6 +978,28 @@ int slam_argmax_dev(slam_engine *e, const float *d_values, int n, int32_t *d_ind
 int slam_pose_spread_dev(slam_engine *e, const float *d_x, const float *d_y, const float *d_theta, const int32_t *d_idx,
                          const float *d_carry, int n, float ref_theta, float pose[3], float cov[6], float *heading_r);
 
+/* One mode of a pose population: a cluster of the cloud, as slam_pf_modes defines it.  40 bytes, no padding. */
+typedef struct slam_pf_mode {
+    float pose[3];    /* x, y, theta: the weighted mean of the mode's members */
+    float mass;       /* its share of the population's weight, in (0, 1] */
+    int32_t cell[3];  /* the centre cell: ix, iy, heading bin */
+    int32_t ncells;   /* occupied cells among the 27 (9 with hbins == 1) of its neighbourhood */
+    int64_t weight;   /* Wm: the sum of its members' weights (particles, where the weights are equal) */
+} slam_pf_mode;
+
+/* The modes of n poses in device memory, exactly as slam_pf_modes defines them, without a session: d_idx (optional) is a pending
+ * gather — slot i holds particle d_idx[i]; d_carry (optional) is the source of the 16-bit weights, one float per SLOT, exactly as
+ * slam_pose_spread_dev takes it (all weights zero, or no d_carry: w = 1).  modes receives up to max_modes entries, *n_modes how
+ * many, *cells the number of distinct occupied cells, *wtotal the weight of the whole population (n where w = 1).  Three launches
+ * (four words of control and the table are the engine's own, made at the first call and left zeroed by every call); the
+ * population is not copied and the table never leaves the device.  Synchronises; the result comes back by one copy of 480 bytes.
+ * Errors, outputs untouched: SLAM_ERR_INVALID_ARG for n <= 0, a null pointer, a cell that is not finite or <= 0, hbins other than
+ * 1 or 4 .. 64, max_modes outside 1 .. 8, and for a population with a particle outside the domain; SLAM_ERR_CAPACITY for more
+ * than 65 536 distinct cells (choose a larger cell). */
+int slam_pose_modes_dev(slam_engine *e, const float *d_x, const float *d_y, const float *d_theta, const int32_t *d_idx,
+                        const float *d_carry, int n, float ref_theta, float cell, int hbins, int max_modes, slam_pf_mode *modes,
+                        int *n_modes, int *cells, int64_t *wtotal);
+
 /* Plain gather of particle attributes through an index (used when the gather is not fused into the
  * next stage, and to pack rows for migration between GPUs). */
 int slam_gather_f32_dev(slam_engine *e, const float *d_src, const int32_t *d_idx, int n, float *d_dst);
@@ -1378,6 +1400,41 @@ int slam_pf_mean(slam_pf *pf, float ref_theta, float pose[3]);
  * Sharded: collective, supported — two exchanges (the mean must be the global one before the second launch), the integer sums
  * add over the ranks in any order, the same answer (and the same verdict on the domain) on every rank. */
 int slam_pf_spread(slam_pf *pf, float ref_theta, float pose[3], float cov[6], float *heading_r);
+/* The modes of the population: where mean and spread assume one hump, this call names the few heaviest clusters of the cloud, each
+ * with a pose and a mass — "settled, 97 % in one mode", "two candidates at 55 / 40 %", "proposals gather at a second place".  A
+ * function of the population alone (behind the pending gather), never of the schedule: a permuted population gives the same bytes.
+ *   Per particle, every operation one binary32 rounding, inv = 1.0f / cell formed once on the host:
+ *     u = x * inv;  fl = floorf(u);  ix = (int32)fl  (floor, not the cast);  FX = (int32)((u - fl) * 2^20);  iy, FY likewise from y;
+ *     t = theta * 0.15915494f;  t = t - floorf(t);  b = min((int32)(t * (float)hbins), hbins - 1);
+ *     (s, c) = sincos_det(theta - ref_theta);  S = trunc(s * 2^20), C = trunc(c * 2^20).
+ *   (u - fl is exact and in [0, 1) except for u in (-2^-25, 0), where it rounds to 1.0f: FX = 2^20 in cell -1, the same place.)
+ *   Domain: |u| < 2^20 in x and in y and a finite heading; a NaN anywhere is outside.  Particles outside are counted, and if there
+ *   is one the call returns SLAM_ERR_INVALID_ARG without writing its outputs (slam_last_error says how many).
+ *   Weights as in slam_pf_spread, word for word: w = 1 before the first step, on frames that resampled, after slam_pf_set_poses,
+ *   slam_pf_reset and either reseed; the gate's 16-bit weights w16 on a frame the resample gate kept (all of them zero: w = 1).
+ *   A particle of weight 0 contributes nothing and makes no cell.
+ *   A cell is a distinct key (ix, iy, b) with five exact integer sums: W = sum w, sum w FX, sum w FY, sum w S, sum w C (with
+ *   n_total <= 2^23 and w <= 2^16 every sum stays below 2^59: one 64-bit accumulator each).  More than 65 536 distinct cells:
+ *   SLAM_ERR_CAPACITY, outputs untouched — a verdict on the set of keys, not on the order they arrived in.
+ *   The score of a cell is W summed over its neighbourhood: |dix| <= 1, |diy| <= 1 and cyclic heading distance <= 1 (mod hbins) —
+ *   27 cells, 9 with hbins == 1.  Rounds r = 0 .. max_modes - 1: a cell is eligible unless an earlier centre lies within
+ *   |dix| <= 2, |diy| <= 2 and cyclic heading distance <= 2 of it, all three at once (so the neighbourhoods of centres are
+ *   disjoint); the eligible cell of the largest score is the centre of mode r, the smallest (ix, iy, b) — signed, in that order —
+ *   on ties; no eligible cell ends the list (*n_modes may be less than max_modes).
+ *   The mode of a centre (ix0, iy0, b0): its members are the occupied cells of its neighbourhood; Wm = sum W;
+ *     A = sum over members (W * (ix - ix0) * 2^20 + sum w FX),  Q = trunc(A / Wm),
+ *     pose[0] = float((double(ix0) + double(Q) / 2^20) * double(cell)),   pose[1] likewise;
+ *     pose[2] = float(double(ref_theta) + atan2(double(sum w S), double(sum w C)))  (atan2(0, 0) = 0);
+ *     mass = float(double(Wm) / double(Wtotal)),  Wtotal over all cells.
+ *   *cells receives the number of distinct cells.
+ *   A cluster wider than three cells is reported as neighbouring modes two or more cells on: choose cell at least the size of a
+ *   settled cloud.  hbins is 1 (headings ignored) or 4 .. 64; max_modes 1 .. 8; cell finite and > 0.
+ *   Allowed wherever slam_pf_spread is — also between a reseed and the next step, where slam_pf_best is not.  Three launches
+ *   (accumulate, score, select), the result through mapped host memory; the table (16 MB) is made by the first call, not with the
+ *   session: a session that never calls this runs exactly the launches it ran before.  No policy: what to do with the answer is
+ *   the application's.
+ * Sharded sessions: NOT BUILT (adding cells over ranks) — SLAM_ERR_INVALID_ARG, as slam_pf_known_map_set answers them. */
+int slam_pf_modes(slam_pf *pf, float ref_theta, float cell, int hbins, int max_modes, slam_pf_mode *modes, int *n_modes, int *cells);
 /* rows this rank received in the exchange of the last completed frame (0 on a single GPU) */
 int slam_pf_rows_received(const slam_pf *pf);
 /* With cfg.resample_ess_frac in (0, 1): how many of the frames the host has looked at so far did resample (the
